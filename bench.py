@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the hot path: mutants scored per second, ESM-1v 650M masked-marginals.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision fp32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision fp32] [--dump-outputs DIR]
 
 One *step* = one pass of the hot path over one assay-shaped batch resident in HBM:
 BASELINE.json configs[1] -- ESM-1v 650M (33 x 1280 x 20 heads x 5120), one assay shaped like
@@ -610,7 +610,12 @@ def main(argv=None, make_model=None, make_assay=None):
     ap.add_argument("--no-secondary", action="store_true", help="skip the `secondary` object (other configs; ~1 min after the headline)")
     ap.add_argument("--no-live-traffic", action="store_true", help="do not run the rocprofv3 --pmc child passes for roofline.traffic (the committed file is used)")
     ap.add_argument("--no-box-state", action="store_true", help="skip the `box` object (shader clock / socket power during ~2 s of untimed extra steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy: scores.npy, the float64 per-mutant scores "
+                         "(N > 1: the all_gathered vector of every rank, written by rank 0)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     seam = make_model is not None
 
     rank = int(os.environ.get("RANK", "0"))
@@ -688,6 +693,10 @@ def main(argv=None, make_model=None, make_assay=None):
     fence()
     dt = time.perf_counter() - t0
     model.profile_enable(False)
+    if args.dump_outputs and rank == 0:                               # before any untimed step overwrites the buffers
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        last = gathered if world > 1 else scores_dev
+        np.save(os.path.join(args.dump_outputs, "scores.npy"), last.cpu().numpy().astype(np.float64))
     if world > 1:
         tmax = torch.tensor([dt], dtype=torch.float64, device=cdev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)

@@ -11,6 +11,7 @@ change to the generator, the seeds or the case recomputes live (and says so).  T
     PGMI_FREEZE_DIR=gpurun_out/frozen python -m pytest tests -m gpu        # then: cp gpurun_out/frozen/*.npz tests/golden/frozen/
 
 (the oracle is pinned to the unmodified reference by tests/test_oracle_pinning.py, with or without these files).
+tests/test_oracle_pinning.py keeps the reference's own outputs on its inputs here too (live_reference_*.npz, ``reference_outputs``).
 """
 import hashlib
 import os

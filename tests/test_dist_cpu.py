@@ -1048,7 +1048,7 @@ class _FakeBenchModel(list):
         pass
 
 
-def _bench_main_entry():
+def _bench_main_entry(dump_dir):
     """Runs in a child process (see the test below): bench.main's N > 1 branch over gloo with the seams."""
     import bench
 
@@ -1056,13 +1056,14 @@ def _bench_main_entry():
         print("[Gloo] Rank chatter that a backend might print on stdout")        # inside bench.main: must end up on stderr
         os.system("echo chatter of a child process that inherits file descriptor 1")
         return _FakeBenchModel()
-    bench.main(["--gpus", "2", "--steps", "2", "--warmup", "1"], make_model=model, make_assay=_FakeBenchAssay)
+    bench.main(["--gpus", "2", "--steps", "2", "--warmup", "1", "--dump-outputs", dump_dir], make_model=model, make_assay=_FakeBenchAssay)
 
 
-def test_bench_n_gt_1_prints_exactly_one_json_line_on_stdout():
+def test_bench_n_gt_1_prints_exactly_one_json_line_on_stdout(tmp_path):
     """The driver launches `bench.py --gpus N` under torch.distributed.run and reads stdout: two gloo ranks through bench.main
     (model and assay seams, 24 assays of the table) -- rank 0's stdout is ONE line and it is the JSON object with the contract's
-    keys, rank 1's stdout is empty; everything any library printed is on stderr."""
+    keys, rank 1's stdout is empty; everything any library printed is on stderr.  --dump-outputs: rank 0 writes the gathered
+    score vector of both ranks."""
     import json
     import subprocess
     import sys
@@ -1072,7 +1073,8 @@ def test_bench_n_gt_1_prints_exactly_one_json_line_on_stdout():
     for r in range(2):
         env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE="2",
                    PGMI_BENCH_217_ASSAYS="24", OMP_NUM_THREADS="1")
-        code = f"import sys; sys.path[:0] = [{root!r}, {os.path.join(root, 'tests')!r}]; import test_dist_cpu as t; t._bench_main_entry()"
+        code = (f"import sys; sys.path[:0] = [{root!r}, {os.path.join(root, 'tests')!r}]; import test_dist_cpu as t; "
+                f"t._bench_main_entry({str(tmp_path / 'dump')!r})")
         procs.append(subprocess.Popen([sys.executable, "-c", code], env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=600) for p in procs]
     assert [p.returncode for p in procs] == [0, 0], outs
@@ -1086,6 +1088,9 @@ def test_bench_n_gt_1_prints_exactly_one_json_line_on_stdout():
         assert key in line, key
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and line["steps"] == 2 and line["rccl"]["world_size"] == 2
     assert line["strong_scaling_217"]["assays"] == 24 and line["value"] > 0
+    assert sorted(os.listdir(tmp_path / "dump")) == ["scores.npy"]
+    scores = np.load(tmp_path / "dump" / "scores.npy")
+    assert scores.dtype == np.float64 and scores.shape == (2 * 4996,)           # two ranks x the BLAT-shaped assay
 
 
 # ---- run_indels: a job that dies is taken up where its saved slices ended -------------------------------------------------------

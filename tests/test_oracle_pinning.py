@@ -3,6 +3,8 @@
 * test_oracle_reproduces_golden*: against tests/golden/golden_esm.npz, frozen from the unmodified
   reference by tests/golden/make_golden.py -- runs everywhere (also on the GPU box).
 * test_oracle_vs_live_reference: runs the reference itself (only where /root/reference exists).
+* *_vs_live_reference tests that go through ``reference_outputs``: the reference's outputs on the test's own inputs, computed live
+  where the reference exists and read from tests/golden/frozen/ elsewhere.
 """
 import ctypes as C
 import os
@@ -12,6 +14,7 @@ import pandas as pd
 import pytest
 import torch
 
+import frozen  # noqa: E402  (tests/frozen.py)
 from oracle import esm_oracle as eo, ref_harness as rh
 
 NAMES = ["esm1v_toy_1", "esm1v_toy_2", "esm1b_toy_lnb", "esm2_toy"]
@@ -92,27 +95,62 @@ def test_oracle_vs_live_reference(tmp_path):
                 assert cf.get_optimal_window(i, n, 1024) == eo.get_optimal_window(i, n, 1024)
 
 
-@pytest.mark.skipif(not rh.reference_available(), reason="/root/reference not present (GPU box)")
+def reference_outputs(name, parts, compute):
+    """``compute() -> {key: array}`` runs the reference on a test's inputs, ``parts`` are those inputs (tests/frozen.py fingerprint).
+    Where the reference exists its outputs are computed live and must equal the frozen copy tests/golden/frozen/<name>.npz when that
+    copy is of the same inputs; elsewhere the frozen copy stands in for it (PGMI_FREEZE_DIR=<dir> writes the copies)."""
+    if not rh.reference_available():
+        return frozen.cached(name, parts, compute)              # a missing or stale copy: compute() raises, the reference is absent
+    live = {k: np.asarray(v) for k, v in compute().items()}
+    stored = frozen.cached(name, parts, lambda: live)
+    for k, v in live.items():
+        assert k in stored and stored[k].dtype == v.dtype and np.array_equal(stored[k], v), (name, k)
+    return live
+
+
+def _json(obj):
+    """A non-array result (lists, dicts, exception texts) as one frozen string array; read back with ``_unjson``."""
+    import json
+    return np.array(json.dumps(obj))
+
+
+def _unjson(a):
+    import json
+    return json.loads(str(a))
+
+
+TOKENIZER_TEXTS = ["ACD", "A C D", "AC<mask>D", "A<mask>", "<cls>AC<eos>", "XBZ-.UO", "", "AC\nD", " A", "acd", "AJC", "A*C",
+                   "ajJ K", "A<foo>C", "A<"]
+
+
 def test_tokenizer_vs_live_reference():
     """esm/data.py:178-254 on odd inputs: whitespace dropped, literal special tokens recognised, a character outside the
     vocabulary is a KeyError (the product's Alphabet.encode / pack_sequences and the oracle's tokenize follow it)."""
     from proteingym_amd import esm as pesm
-    rh.load_reference()
-    from esm import data as ref_data
-    ref = ref_data.Alphabet.from_architecture("ESM-1b")
+
+    def compute():
+        rh.load_reference()
+        from esm import data as ref_data
+        ref = ref_data.Alphabet.from_architecture("ESM-1b")
+        out = []
+        for text in TOKENIZER_TEXTS:
+            try:
+                out.append({"encode": ref.encode(text), "tokenize": ref.tokenize(text)})
+            except KeyError as e:
+                out.append({"key_error": list(e.args)})
+        return {"results": _json(out)}
+    results = _unjson(reference_outputs("live_reference_tokenizer", TOKENIZER_TEXTS, compute)["results"])
     mine = pesm.Alphabet()
-    for text in ["ACD", "A C D", "AC<mask>D", "A<mask>", "<cls>AC<eos>", "XBZ-.UO", "", "AC\nD", " A", "acd", "AJC", "A*C",
-                 "ajJ K", "A<foo>C", "A<"]:
-        try:
-            want = ref.encode(text)
-        except KeyError as e:
+    for text, r in zip(TOKENIZER_TEXTS, results):
+        if "key_error" in r:
             with pytest.raises(KeyError) as got:
                 mine.encode(text)
-            assert got.value.args == e.args, text
+            assert list(got.value.args) == r["key_error"], text
             continue
+        want = r["encode"]
         assert mine.encode(text) == want, text
-        assert mine.tokenize(text) == ref.tokenize(text), text
-        if all(len(t) == 1 for t in ref.tokenize(text)) and " " not in text and "\n" not in text:
+        assert mine.tokenize(text) == r["tokenize"], text
+        if all(len(t) == 1 for t in r["tokenize"]) and " " not in text and "\n" not in text:
             assert eo.tokenize(text).tolist() == [0] + want + [2]
 
 
@@ -210,14 +248,12 @@ def test_msa_cluster_oracle_reproduces_reference(golden_dir, name):
 
 
 def test_msa_cluster_oracle_vs_live_reference():
-    from oracle import msa_weights_oracle as mo, ref_harness as rh
-    if not rh.reference_available():
-        pytest.skip("reference checkout not present")
-    w = rh.load_reference_weights()
+    from oracle import msa_weights_oracle as mo
     rng = np.random.default_rng(3)
     m = rng.integers(0, 21, size=(50, 23)).astype(np.int64)
     m[rng.integers(0, 50, size=20)] = m[0]                      # a cluster of duplicates
-    ref = w.calc_num_cluster_members_nogaps_parallel(m, 0.8, 20)
+    ref = reference_outputs("live_reference_msa_cluster", [m], lambda: {
+        "counts": rh.load_reference_weights().calc_num_cluster_members_nogaps_parallel(m, 0.8, 20)})["counts"]
     assert np.array_equal(mo.cluster_counts(m, 0.8, 20), ref.astype(np.int32))
 
 
@@ -819,21 +855,21 @@ def test_reference_performance_script_consumes_the_indel_csvs(tmp_path, monkeypa
         assert float(table.loc[dms_id, col]) == round(rho, 3), (dms_id, table.loc[dms_id, col], rho)
 
 
-@pytest.mark.skipif(not rh.reference_available(), reason="/root/reference not present (GPU box)")
-@pytest.mark.parametrize("kwargs", [
+PREPROCESSING_SWITCHES = [
     {},
     {"threshold_sequence_frac_gaps": 0.2, "threshold_focus_cols_frac_gaps": 0.3},
     {"preprocess_MSA": False},
     {"remove_sequences_with_indeterminate_AA_in_focus_cols": False},
     {"preprocess_MSA": False, "remove_sequences_with_indeterminate_AA_in_focus_cols": False},
-])
+]
+
+
+@pytest.mark.parametrize("kwargs", PREPROCESSING_SWITCHES)
 def test_alignment_preprocessing_vs_live_reference(tmp_path, kwargs):
     """alignment.FocusAlignment (byte-matrix numpy) against the reference's own ``MSA_processing`` (string / pandas code,
     tranception/utils/msa_utils.py:230-340) on an alignment with insert columns, '.', gappy rows and columns, X / B / Z residues and
     a sequence spread over several lines -- every attribute a caller can read, for the reference's switches on and off."""
     from proteingym_amd import tranception as ptr, msa_transformer as pmsa
-    rh.load_reference_tranception()
-    from tranception.utils import msa_utils
     rng = np.random.default_rng(11)
     aa = np.array(list("ACDEFGHIKLMNPQRSTVWY"))
     width, focus = 60, None
@@ -860,36 +896,49 @@ def test_alignment_preprocessing_vs_live_reference(tmp_path, kwargs):
         lines += [s[:25], s[25:]] if i % 3 == 1 else [s]
     a2m = tmp_path / "t.a2m"
     a2m.write_text("\n".join(lines) + "\n")
-    ref = msa_utils.MSA_processing(MSA_location=str(a2m), use_weights=False, **kwargs)
+
+    def compute():
+        rh.load_reference_tranception()
+        from tranception.utils import msa_utils
+        r = msa_utils.MSA_processing(MSA_location=str(a2m), use_weights=False, **kwargs)
+        return {"attributes": _json({
+            "focus_seq_name": r.focus_seq_name, "focus_seq": r.focus_seq, "focus_cols": [int(c) for c in r.focus_cols], "seq_len": int(r.seq_len),
+            "focus_seq_trimmed": "".join(r.focus_seq_trimmed), "raw_seq_name_to_sequence": list(dict(r.raw_seq_name_to_sequence).items()),
+            "seq_name_to_sequence": [[n, "".join(v)] for n, v in r.seq_name_to_sequence.items()], "num_sequences": int(r.num_sequences),
+            "Neff": float(r.Neff), "seq_name_to_weight": list(r.seq_name_to_weight), "focus_start_loc": int(r.focus_start_loc),
+            "focus_stop_loc": int(r.focus_stop_loc),
+            "uniprot_focus_col_to_wt_aa_dict": [[int(k), v] for k, v in r.uniprot_focus_col_to_wt_aa_dict.items()],
+            "uniprot_focus_col_to_focus_idx": [[int(k), int(v)] for k, v in r.uniprot_focus_col_to_focus_idx.items()]}),
+            "weights": r.weights, "one_hot_encoding": r.one_hot_encoding}
+    frozen_ref = reference_outputs(f"live_reference_alignment_preprocessing_{PREPROCESSING_SWITCHES.index(kwargs)}",
+                                   [lines, sorted(kwargs.items())], compute)
+    ref = _unjson(frozen_ref["attributes"])
     for mine in (ptr.MSA_processing(MSA_location=str(a2m), use_weights=False, **kwargs),
                  pmsa.MSA_processing(MSA_location=str(a2m), use_weights=False, **kwargs)):
-        assert mine.focus_seq_name == ref.focus_seq_name and mine.focus_seq == ref.focus_seq
-        assert list(mine.focus_cols) == list(ref.focus_cols) and mine.seq_len == ref.seq_len
-        assert "".join(mine.focus_seq_trimmed) == "".join(ref.focus_seq_trimmed)
-        assert dict(mine.raw_seq_name_to_sequence) == dict(ref.raw_seq_name_to_sequence)
-        assert list(mine.seq_name_to_sequence) == list(ref.seq_name_to_sequence)
-        for n in ref.seq_name_to_sequence:
-            assert "".join(mine.seq_name_to_sequence[n]) == "".join(ref.seq_name_to_sequence[n]), n
-        assert mine.num_sequences == ref.num_sequences and np.array_equal(mine.weights, ref.weights) and mine.Neff == ref.Neff
-        assert list(mine.seq_name_to_weight) == list(ref.seq_name_to_weight)
+        assert mine.focus_seq_name == ref["focus_seq_name"] and mine.focus_seq == ref["focus_seq"]
+        assert list(mine.focus_cols) == ref["focus_cols"] and mine.seq_len == ref["seq_len"]
+        assert "".join(mine.focus_seq_trimmed) == ref["focus_seq_trimmed"]
+        assert dict(mine.raw_seq_name_to_sequence) == dict(ref["raw_seq_name_to_sequence"])
+        assert list(mine.seq_name_to_sequence) == [n for n, _ in ref["seq_name_to_sequence"]]
+        for n, v in ref["seq_name_to_sequence"]:
+            assert "".join(mine.seq_name_to_sequence[n]) == v, n
+        assert mine.num_sequences == ref["num_sequences"] and np.array_equal(mine.weights, frozen_ref["weights"]) and mine.Neff == ref["Neff"]
+        assert list(mine.seq_name_to_weight) == ref["seq_name_to_weight"]
     tr = ptr.MSA_processing(MSA_location=str(a2m), use_weights=False, **kwargs)
-    assert (tr.focus_start_loc, tr.focus_stop_loc) == (ref.focus_start_loc, ref.focus_stop_loc)
-    assert tr.uniprot_focus_col_to_wt_aa_dict == ref.uniprot_focus_col_to_wt_aa_dict
-    assert tr.uniprot_focus_col_to_focus_idx == ref.uniprot_focus_col_to_focus_idx
+    assert (tr.focus_start_loc, tr.focus_stop_loc) == (ref["focus_start_loc"], ref["focus_stop_loc"])
+    assert list(tr.uniprot_focus_col_to_wt_aa_dict.items()) == [tuple(kv) for kv in ref["uniprot_focus_col_to_wt_aa_dict"]]
+    assert list(tr.uniprot_focus_col_to_focus_idx.items()) == [tuple(kv) for kv in ref["uniprot_focus_col_to_focus_idx"]]
     onehot = np.zeros((tr.num_sequences, tr.seq_len, 20))
     i, j = np.nonzero(tr.encoded >= 0)
     onehot[i, j, tr.encoded[i, j]] = 1.0
-    assert np.array_equal(onehot, ref.one_hot_encoding)
+    assert np.array_equal(onehot, frozen_ref["one_hot_encoding"])
 
 
-@pytest.mark.skipif(not rh.reference_available(), reason="/root/reference not present (GPU box)")
 @pytest.mark.parametrize("weighted", [False, True])
 def test_msa_prior_in_blocks_equals_live_reference_bitwise(tmp_path, weighted):
     """get_msa_prior reduces the alignment in blocks of sequences (bounded memory); the bits must be the reference's, which reduces
     one [sequences, width, V] array (msa_utils.py:63-138) -- 300 sequences in 24 blocks, with and without EVE weights."""
     from proteingym_amd import tranception as ptr
-    rh.load_reference_tranception()
-    from tranception.utils import msa_utils
     rng = np.random.default_rng(5)
     aa = np.array(list("ACDEFGHIKLMNPQRSTVWY"))
     width = 48
@@ -903,38 +952,51 @@ def test_msa_prior_in_blocks_equals_live_reference_bitwise(tmp_path, weighted):
         lines += [f">s{i}", "".join(row)]
     a2m = tmp_path / "p.a2m"
     a2m.write_text("\n".join(lines) + "\n")
-    wfile = None
+    wfile = str(tmp_path / "w.npy") if weighted else None
+
+    def compute():
+        rh.load_reference_tranception()
+        from tranception.utils import msa_utils
+        out = {}
+        if weighted:
+            msa_utils.MSA_processing(MSA_location=str(a2m), use_weights=True, weights_location=wfile)  # the reference computes and saves
+            out["weights"] = np.load(wfile)
+        out["prior"] = msa_utils.get_msa_prior(MSA_data_file=str(a2m), MSA_weight_file_name=wfile, MSA_start=2, MSA_end=50, len_target_seq=60,
+                                               vocab=ptr.VOCAB, verbose=False)
+        return out
+    ref = reference_outputs(f"live_reference_msa_prior_blocks_{'weighted' if weighted else 'plain'}", [lines, ptr.VOCAB], compute)
     if weighted:
-        wfile = str(tmp_path / "w.npy")
-        msa_utils.MSA_processing(MSA_location=str(a2m), use_weights=True, weights_location=wfile)      # the reference computes and saves
-    want = msa_utils.get_msa_prior(MSA_data_file=str(a2m), MSA_weight_file_name=wfile, MSA_start=2, MSA_end=50, len_target_seq=60,
-                                   vocab=ptr.VOCAB, verbose=False)
+        np.save(wfile, ref["weights"])                                          # the reference's weight file, as it saved it
+    want = ref["prior"]
     got = ptr.get_msa_prior(str(a2m), wfile, 2, 50, 60, block_bytes=13 * width * 25 * 8)
     assert np.array_equal(got, want)
     assert np.array_equal(ptr.get_msa_prior(str(a2m), wfile, 2, 50, 60), want)
 
 
-@pytest.mark.skipif(not rh.reference_available(), reason="/root/reference not present (GPU box)")
 def test_alignment_reader_oddities_vs_live_reference(tmp_path):
     """alignment.read_records against the reference's two readers (msa_utils.py:28-43 ``process_msa_data``; the loop at the top of
     ``MSA_processing.gen_alignment``) on what real a2m files occasionally hold: a sequence over several lines, a repeated header, blank
     lines, trailing blanks, lower case and '.', a header without a sequence."""
     from proteingym_amd import tranception as ptr, alignment
-    rh.load_reference_tranception()
-    from tranception.utils import msa_utils
     text = (">FOCUS/1-8\nACDE\nFGHI  \n\n>two\nac.eF-HI\n>empty\n>three\nACDEFGHI\n>two\nKLMNPQRS\n>four \nA-DE\n\nFG-I\n")
     p = tmp_path / "odd.a2m"
     p.write_text(text)
-    want = msa_utils.process_msa_data(str(p))
+
+    def compute():
+        rh.load_reference_tranception()
+        from tranception.utils import msa_utils
+        ref = msa_utils.MSA_processing.__new__(msa_utils.MSA_processing)       # only the reading loop is wanted: drive gen_alignment's own state
+        ref.MSA_location, ref.alphabet, ref.preprocess_MSA, ref.use_weights = str(p), "ACDEFGHIKLMNPQRSTVWY", False, False
+        ref.remove_sequences_with_indeterminate_AA_in_focus_cols, ref.weights_location, ref.theta = False, None, 0.2
+        ref.gen_alignment()                                                      # no pre-processing: the records as read
+        return {"process_msa_data": _json(list(msa_utils.process_msa_data(str(p)).items())), "focus_seq_name": np.array(ref.focus_seq_name),
+                "raw": _json(list(ref.raw_seq_name_to_sequence.items()))}
+    want = reference_outputs("live_reference_alignment_reader_oddities", [text], compute)
     got = ptr.process_msa_data(str(p))
-    assert list(got.items()) == list(want.items())
+    assert [list(kv) for kv in got.items()] == _unjson(want["process_msa_data"])
     first, raw = alignment.read_records(str(p))
-    ref = msa_utils.MSA_processing.__new__(msa_utils.MSA_processing)           # only the reading loop is wanted: drive gen_alignment's own state
-    ref.MSA_location, ref.alphabet, ref.preprocess_MSA, ref.use_weights = str(p), "ACDEFGHIKLMNPQRSTVWY", False, False
-    ref.remove_sequences_with_indeterminate_AA_in_focus_cols, ref.weights_location, ref.theta = False, None, 0.2
-    ref.gen_alignment()                                                          # no pre-processing: the records as read
-    assert first == ref.focus_seq_name
-    assert list(raw.items()) == list(ref.raw_seq_name_to_sequence.items())
+    assert first == str(want["focus_seq_name"])
+    assert [list(kv) for kv in raw.items()] == _unjson(want["raw"])
     with pytest.raises(ValueError, match="differ in length"):                  # '>two' was extended by its second record: ragged
         alignment.FocusAlignment(str(p), preprocess=False)
 
@@ -991,16 +1053,14 @@ def test_update_prior_indel_walk():
     assert out[:, 0].tolist() == [1, 2, 3, 4, 5, 6] and me == 6
 
 
-@pytest.mark.skipif(not rh.reference_available(), reason="/root/reference not present (GPU box)")
 def test_update_prior_indel_vs_live_reference(tmp_path):
     """The same walk through the reference's own function (msa_utils.update_retrieved_MSA_log_prior_indel driven with a stand-in model object
     and the stand-in aligner) on random indels of a random family, incl. an alignment whose reference row has gaps."""
     from oracle import tranception_oracle as to
-    rh.load_reference_tranception()
-    from tranception.utils import msa_utils
     import types
     rng = np.random.default_rng(8)
     aa = list("ACDEFGHIKLMNPQRSTVWY")
+    cases = []
     for case in range(3):
         L = 40
         ref = "".join(rng.choice(aa, size=L))
@@ -1026,10 +1086,22 @@ def test_update_prior_indel_vs_live_reference(tmp_path):
                     del s[p_]
                 else:
                     s.insert(p_, rng.choice(aa))
-            s = "".join(s)
+            cases.append((case, trial, model, prior, L, aligner, "".join(s)))
+
+    def compute():
+        rh.load_reference_tranception()
+        from tranception.utils import msa_utils
+        out = {}
+        for case, trial, model, prior, L, _, s in cases:
             want, ws, we = msa_utils.update_retrieved_MSA_log_prior_indel(model, prior.clone(), 0, L, s, "hash")
-            got, gs, ge = to.update_prior_indel(prior.clone(), 0, L, *aligner(s))
-            assert (gs, ge) == (ws, we) and got.shape == want.shape and torch.equal(got, want), (case, trial)
+            out[f"{case}/{trial}/prior"], out[f"{case}/{trial}/start_end"] = want.numpy(), np.array([ws, we])
+        return out
+    parts = [(open(c[2].MSA_filename).read(), c[3].numpy(), c[6]) for c in cases]
+    ref = reference_outputs("live_reference_update_prior_indel", [p for t in parts for p in t], compute)
+    for case, trial, model, prior, L, aligner, s in cases:
+        want, (ws, we) = torch.from_numpy(ref[f"{case}/{trial}/prior"]), ref[f"{case}/{trial}/start_end"].tolist()
+        got, gs, ge = to.update_prior_indel(prior.clone(), 0, L, *aligner(s))
+        assert (gs, ge) == (ws, we) and got.shape == want.shape and torch.equal(got, want), (case, trial)
 
 
 class _OracleBackedDevice:
@@ -1156,15 +1228,14 @@ def test_run_sharded_tranception_indels_with_retrieval_in_chunks_on_cpu(golden_d
         assert np.abs(m[c].to_numpy(dtype=np.float64) - g[f"full/{c}"]).max() < 3e-5, c
 
 
-@pytest.mark.skipif(not rh.reference_available(), reason="/root/reference not present (GPU box)")
 def test_filter_msa_vs_live_reference(tmp_path, monkeypatch):
     """--filter-msa (compute_fitness.py:76-97): the reference rewrites the alignment ('.' -> '-', upper case, headers included), shells out
     to <path>/bin/hhfilter and pre-processes what comes back.  The product does the same through subprocess; with the stand-in filter
     (tests/golden/stand_in_hhfilter.py) in place of hh-suite both hand the SAME filtered file (same relative path, same bytes) to
     MSA_processing -- whose own parity is test_alignment_preprocessing_vs_live_reference."""
     import stat
+    import types
     from proteingym_amd import msa_transformer as pmsa
-    ref_cf = rh.load_reference()
     rng = np.random.default_rng(21)
     aa = np.array(list("ACDEFGHIKLMNPQRSTVWY"))
     width = 50
@@ -1179,17 +1250,19 @@ def test_filter_msa_vs_live_reference(tmp_path, monkeypatch):
     exe = root / "bin" / "hhfilter"
     exe.write_text('#!/bin/sh\nexec python3 "%s" "$@"\n' % os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "stand_in_hhfilter.py"))
     exe.chmod(exe.stat().st_mode | stat.S_IXUSR)
-    seen = {}
-    for who, fn, mod in (("ref", ref_cf.process_msa, ref_cf), ("mine", pmsa.process_msa, pmsa)):
+    def filtered(who, mod):
         folder = tmp_path / who
         folder.mkdir()
         (folder / "fam.a2m").write_text("\n".join(lines) + "\n")
-        import types
         monkeypatch.setattr(mod, "MSA_processing",                                                 # record what the pre-processing is given
                             lambda MSA_location, **kw: types.SimpleNamespace(focus_seq_name="recorded", MSA_location=MSA_location))
-        out = fn(filename=str(folder / "fam.a2m"), weight_filename=None, filter_msa=True, path_to_hhfilter=str(root), hhfilter_min_cov=75,
-                 hhfilter_max_seq_id=90, hhfilter_min_seq_id=0).MSA_location
-        seen[who] = (os.path.relpath(out, folder), open(out).read())
+        out = mod.process_msa(filename=str(folder / "fam.a2m"), weight_filename=None, filter_msa=True, path_to_hhfilter=str(root), hhfilter_min_cov=75,
+                              hhfilter_max_seq_id=90, hhfilter_min_seq_id=0).MSA_location
+        return os.path.relpath(out, folder), open(out).read()
+    seen = {"mine": filtered("mine", pmsa)}
+    ref = reference_outputs("live_reference_filter_msa", [lines, open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "stand_in_hhfilter.py")).read()],
+                            lambda: dict(zip(("relpath", "text"), map(np.array, filtered("ref", rh.load_reference())))))
+    seen["ref"] = (str(ref["relpath"]), str(ref["text"]))
     assert seen["mine"] == seen["ref"]
     kept = seen["ref"][1].count(">")
     assert 1 < kept < 60 and ">TARGET-PROT/1-50" in seen["ref"][1]                # filtered; headers went through tr and ucase too
@@ -1197,62 +1270,83 @@ def test_filter_msa_vs_live_reference(tmp_path, monkeypatch):
         pmsa.process_msa(filename=str(tmp_path / "mine" / "fam.a2m"), weight_filename=None, filter_msa=True, path_to_hhfilter=str(tmp_path / "nowhere"))
 
 
-@pytest.mark.skipif(not rh.reference_available(), reason="/root/reference not present (GPU box)")
 def test_tranception_host_helpers_vs_live_reference():
     """The column-wise helpers of tranception.py against the reference's per-string functions (scoring_utils.py:16-31,47-69): mutated
     sequences incl. repeated positions and negative indices, the two assertion texts in the reference's order of checks, windows at
     every position of proteins around the context length, and the random replacement consuming numpy's stream like the reference."""
     from proteingym_amd import synthetic, tranception as ptr
-    rh.load_reference_tranception()
-    from tranception.utils import scoring_utils as ref
     seq, muts, _ = synthetic.random_assay(seed=3, L=90, n_single=60, n_multi=140)
     w0 = seq[4]
     muts += [f"{w0}5A:{w0}5C", f"{seq[-1]}0G", f"{seq[9]}10W:{seq[0]}1Y:{seq[9]}10H"]        # same position twice; position 0 = index -1
-    assert ptr.mutated_sequences(seq, muts) == [ref.get_mutated_sequence(seq, m) for m in muts]
-    assert ptr.get_mutated_sequence(seq, muts[7], start_idx=1) == ref.get_mutated_sequence(seq, muts[7], start_idx=1)
     other = "A" if seq[2] != "A" else "C"
-    for bad in ([muts[0], f"{other}3G"], [f"{seq[2]}3B", muts[1]], [f"{seq[2]}3G:{other}3G:{seq[4]}5B"], [f"{seq[2]}3B:{other}3G"]):
-        with pytest.raises(AssertionError) as want:
-            [ref.get_mutated_sequence(seq, m) for m in bad]
+    bads = [[muts[0], f"{other}3G"], [f"{seq[2]}3B", muts[1]], [f"{seq[2]}3G:{other}3G:{seq[4]}5B"], [f"{seq[2]}3B:{other}3G"]]
+    windows = ((50, 1022), (1022, 1022), (1023, 1022), (1500, 1022), (77, 20), (78, 21))
+    text = "MXKBXZJAXXB"
+    replacements = (("X", "ACDEFGHIKLMNPQRSTVWY"), ("B", "DN"), ("J", "IL"), ("Q", "EQ"))
+
+    def compute():
+        rh.load_reference_tranception()
+        from tranception.utils import scoring_utils as ref
+        out = {"mutated": _json([ref.get_mutated_sequence(seq, m) for m in muts]),
+               "mutated_start_1": np.array(ref.get_mutated_sequence(seq, muts[7], start_idx=1))}
+        texts = []
+        for bad in bads:
+            with pytest.raises(AssertionError) as want:
+                [ref.get_mutated_sequence(seq, m) for m in bad]
+            texts.append(str(want.value))
+        out["assertions"] = _json(texts)
+        for n, w in windows:
+            out[f"windows/{n}/{w}"] = np.array([ref.get_optimal_window(int(p), n, w) for p in np.arange(n)])
+        for ch, choices in replacements:
+            np.random.seed(11)
+            out[f"replace/{ch}"] = np.array(ref.sequence_replace_single(text, ch, choices))
+            out[f"replace_next/{ch}"] = np.array(np.random.random())
+        return out
+    ref = reference_outputs("live_reference_tranception_host_helpers", [seq, muts, bads, windows, text, replacements], compute)
+    assert ptr.mutated_sequences(seq, muts) == _unjson(ref["mutated"])
+    assert ptr.get_mutated_sequence(seq, muts[7], start_idx=1) == str(ref["mutated_start_1"])
+    for bad, want in zip(bads, _unjson(ref["assertions"])):
         with pytest.raises(AssertionError) as got:
             ptr.mutated_sequences(seq, bad)
-        assert str(got.value) == str(want.value)
+        assert str(got.value) == want
     with pytest.raises(IndexError):
         ptr.mutated_sequences(seq, [f"{seq[0]}500A"])
-    for n, w in ((50, 1022), (1022, 1022), (1023, 1022), (1500, 1022), (77, 20), (78, 21)):
+    for n, w in windows:
         pos = np.arange(n)
-        want = np.array([ref.get_optimal_window(int(p), n, w) for p in pos])
+        want = ref[f"windows/{n}/{w}"]
         assert np.array_equal(ptr.optimal_windows(pos, n, w), want)
         assert all(ptr.get_optimal_window(int(p), n, w) == list(want[p]) for p in (0, n // 2, n - 1))
-    text = "MXKBXZJAXXB"
-    for ch, choices in (("X", "ACDEFGHIKLMNPQRSTVWY"), ("B", "DN"), ("J", "IL"), ("Q", "EQ")):
+    for ch, choices in replacements:
         np.random.seed(11)
-        want = ref.sequence_replace_single(text, ch, choices)
-        want_next = np.random.random()
-        np.random.seed(11)
-        assert ptr.sequence_replace_single(text, ch, choices) == want
-        assert np.random.random() == want_next or ch == "Q"           # no occurrence: the reference still calls choice(size=0)
+        assert ptr.sequence_replace_single(text, ch, choices) == str(ref[f"replace/{ch}"])
+        assert np.random.random() == float(ref[f"replace_next/{ch}"]) or ch == "Q"   # no occurrence: the reference still calls choice(size=0)
 
 
-@pytest.mark.skipif(not rh.reference_available(), reason="/root/reference not present (GPU box)")
 def test_msa_prior_ragged_alignment_like_the_live_reference(tmp_path):
     """Rows shorter than the query: the reference tolerates them without the similarity filter (their tail holds no counts) and fails
     with ValueError in the filter's np.dot; rows longer than MSA_end - MSA_start with residues there: IndexError in both."""
     from proteingym_amd import tranception as ptr
-    rh.load_reference_tranception()
-    from tranception.utils import msa_utils
+    text = ">Q/1-12\nACDEFGHIKLMN\n>a\nACDEFGHI\n>b\nAC-EFGHIKLMN\n>c\nACD\n"
     a2m = tmp_path / "r.a2m"
-    a2m.write_text(">Q/1-12\nACDEFGHIKLMN\n>a\nACDEFGHI\n>b\nAC-EFGHIKLMN\n>c\nACD\n")
-    kw = dict(MSA_data_file=str(a2m), MSA_weight_file_name=None, MSA_start=0, MSA_end=12, len_target_seq=14, vocab=ptr.VOCAB)
-    want = msa_utils.get_msa_prior(filter_MSA=False, verbose=False, **kw)
-    assert np.array_equal(ptr.get_msa_prior(str(a2m), None, 0, 12, 14, filter_MSA=False), want)
-    with pytest.raises(ValueError):
-        msa_utils.get_msa_prior(filter_MSA=True, verbose=False, **kw)
+    a2m.write_text(text)
+
+    def compute():
+        rh.load_reference_tranception()
+        from tranception.utils import msa_utils
+        kw = dict(MSA_data_file=str(a2m), MSA_weight_file_name=None, MSA_start=0, len_target_seq=14, vocab=ptr.VOCAB, verbose=False)
+        out = {"prior": msa_utils.get_msa_prior(filter_MSA=False, MSA_end=12, **kw)}
+        for key, extra in (("filtered", dict(filter_MSA=True, MSA_end=12)), ("short_end", dict(filter_MSA=False, MSA_end=8))):
+            try:
+                msa_utils.get_msa_prior(**extra, **kw)
+                out[key] = np.array("no error")
+            except Exception as e:                                              # noqa: BLE001 -- the type is the result
+                out[key] = np.array(type(e).__name__)
+        return out
+    want = reference_outputs("live_reference_msa_prior_ragged", [text, ptr.VOCAB], compute)
+    assert np.array_equal(ptr.get_msa_prior(str(a2m), None, 0, 12, 14, filter_MSA=False), want["prior"])
+    assert str(want["filtered"]) == "ValueError" and str(want["short_end"]) == "IndexError"
     with pytest.raises(ValueError):
         ptr.get_msa_prior(str(a2m), None, 0, 12, 14, filter_MSA=True)
-    with pytest.raises(IndexError):
-        msa_utils.get_msa_prior(MSA_data_file=str(a2m), MSA_weight_file_name=None, MSA_start=0, MSA_end=8, len_target_seq=14, vocab=ptr.VOCAB,
-                                filter_MSA=False, verbose=False)
     with pytest.raises(IndexError):
         ptr.get_msa_prior(str(a2m), None, 0, 8, 14, filter_MSA=False)
 
