@@ -45,6 +45,9 @@ extern "C" {
  * (proteingym/baselines/tranception/tranception/model_pytorch.py) */
 #define PGMI_ARCH_TRANCEPTION 3
 #define PGMI_ARCH_MSA 4          /* MSA Transformer (esm_msa1b): axial attention, esm/model/msa_transformer.py */
+/* ProGen2: GPT-J-style causal LM, parallel residual, partial interleaved rotary, tanh-GELU
+ * (proteingym/baselines/progen2/models/progen/modeling_progen.py); created with pgmi_pg2_model_create */
+#define PGMI_ARCH_PROGEN2 5
 
 /* GEMM operand precision.  Residual stream, LayerNorm statistics, softmax and every
  * accumulator are fp32 in all modes. */
@@ -59,6 +62,7 @@ extern "C" {
 #define PGMI_TOK_UNK 3
 #define PGMI_TOK_MASK 32
 #define PGMI_VOCAB 33
+#define PGMI_PG2_VOCAB 32  /* ProGen2 (progen2/tokenizer.json) */
 
 typedef struct pgmi_config {
     int32_t abi_version;          /* = PGMI_ABI_VERSION */
@@ -229,7 +233,7 @@ int pgmi_set_option(const char* name, int64_t value);
 int pgmi_op_layernorm(int device, const float* x, const float* w, const float* b,
                       int rows, int D, float eps, float* y);               /* modules.py:80-81 */
 int pgmi_op_gemm(int device, int precision, const float* A, const float* W, const float* bias,
-                 const float* residual, int M, int N, int K, int epilogue /*0 none,1 gelu,2 squared relu; +256 (f16x3):
+                 const float* residual, int M, int N, int K, int epilogue /*0 none,1 gelu,2 squared relu,3 tanh-gelu; +256 (f16x3):
                  the split-fp16-plane output epilogue, its planes returned rebuilt as fp32*/,
                  float* C);          /* C = epi(A W^T + bias) + residual; modules.py:134-140 */
 int pgmi_op_attention(int device, int precision, const float* qkv, const int32_t* kv_len,
@@ -284,6 +288,31 @@ int pgmi_bench_gemm(int device, int precision, int M, int N, int K, int epilogue
  * each (within-process A/B); ms_out[v] = median over the rounds of the mean milliseconds per launch. */
 int pgmi_bench_gemm_ab(int device, int precision, int M, int N, int K, int epilogue, int split_out,
                        const int* variants, int n_variants, int rounds, int iters, double* ms_out);
+
+/* ---- ProGen2 (arch PGMI_ARCH_PROGEN2; vocab 32, max_positions = n_positions, heads % 8 == 0, precision f16x3) ----
+ * Tokens (progen2/tokenizer.json): <|pad|> 0, <|bos|> 1, <|eos|> 2, '1' 3, '2' 4, 'A'..'Z' 5..29.  head_dim = D / heads: any even
+ * value up to 256 (80 and 96 run zero-padded in the 128-lane layout, 256 = progen2-xlarge in four 64-lane slot groups).
+ * Weight blob order (fp32, nn.Linear layout [out,in], names as in the HF state dict):
+ *   transformer.wte.weight [V,D];
+ *   per layer h.{i}: ln_1 w,b; attn.qkv_proj.weight with its rows REORDERED to q | k | v, [3D,D] (row h*dh + j of each block = dim j
+ *        of head h: the mp_num = 8 interleave of q, v, k blocks of modeling_progen.py:157-168 undone by the host,
+ *        proteingym_amd/progen2.py); attn.out_proj.weight [D,D]; mlp.fc_in W[F,D], b[F]; mlp.fc_out W[D,F], b[D];
+ *   transformer.ln_f w,b; lm_head W[V,D], b[V].
+ * (qkv_proj and out_proj carry no bias; ln_2 does not exist: both branches read ln_1's output, modeling_progen.py:252-283.)
+ *
+ * pgmi_pg2_model_create: as pgmi_model_create, with the config's rotary_dim (2 .. head_dim, even; head_dim when the config has
+ *   none): the first rotary_dim dims of every q / k head rotate in interleaved pairs (2i, 2i+1), inv_freq = 10000^(-2i/rotary_dim),
+ *   angle = fp32(t) * fp32(inv_freq) (modeling_progen.py:38-58).  Returns an ordinary model: destroy, profile, synchronize as usual.
+ * pgmi_pg2_token_logprobs: log_softmax(model(input_ids).logits) over all 32 columns; tokens int32 [B,T] (no padding, T <=
+ *   n_positions), out f32 [B,T,32].
+ * pgmi_pg2_sequence_loglik: the reduction of progen2/compute_fitness.py:53-74 for B rows of L tokens each: the model reads
+ *   tokens[b, :L-1], the targets are tokens[b, 1:], the last target is dropped when it is '1' (3) or '2' (4), and out[b] = sum over
+ *   the kept targets of the log-softmax over logits columns 5..29 at the target's column.  n_kept (optional, int32 [B]) receives the
+ *   number of kept targets (the reference's score is -CE = out[b] / n_kept[b]; 0 kept targets: its mean is NaN).  Every kept target
+ *   must be an amino-acid id 5..29.  Equal-length rows only: reading direction and chunking are the host's. */
+int pgmi_pg2_model_create(const pgmi_config* cfg, int rotary_dim, const float* weights, int64_t n_weights, int device, pgmi_model** out);
+int pgmi_pg2_token_logprobs(pgmi_model* m, const int32_t* tokens, int B, int T, float* out);
+int pgmi_pg2_sequence_loglik(pgmi_model* m, const int32_t* tokens, int B, int L, float* out, int32_t* n_kept);
 
 /* ---- MSA Transformer (arch PGMI_ARCH_MSA; vocab 33, head_dim 64, precision f16x3) --------------------
  * Replaces MSATransformer.forward (proteingym/baselines/esm/esm/model/msa_transformer.py:146-205; tied

@@ -29,15 +29,24 @@ int prof_drain(pgmi_model* m) {
 int check_cfg(const pgmi_config* c) {
     if (!c) { set_error("null config"); return PGMI_EINVAL; }
     if (c->abi_version != PGMI_ABI_VERSION) { set_error("ABI version mismatch: got %d, library is %d", c->abi_version, PGMI_ABI_VERSION); return PGMI_EINVAL; }
-    if (c->arch != PGMI_ARCH_ESM1B && c->arch != PGMI_ARCH_ESM2 && c->arch != PGMI_ARCH_TRANCEPTION && c->arch != PGMI_ARCH_MSA) { set_error("unknown arch %d", c->arch); return PGMI_EINVAL; }
+    if (c->arch != PGMI_ARCH_ESM1B && c->arch != PGMI_ARCH_ESM2 && c->arch != PGMI_ARCH_TRANCEPTION && c->arch != PGMI_ARCH_MSA &&
+        c->arch != PGMI_ARCH_PROGEN2) { set_error("unknown arch %d", c->arch); return PGMI_EINVAL; }
     if (c->layers <= 0 || c->embed_dim <= 0 || c->heads <= 0 || c->ffn_dim <= 0) { set_error("non-positive model dimension"); return PGMI_EINVAL; }
     {
         // head_dim 64 natively; smaller head dims (ESM2 8M/35M/150M: 16/24/32) run zero-padded to 64 lanes per head;
         // head_dim 128 (ESM2-15B: pretrained.py:387-394) as two 64-lane slot groups per head (see pgmi_model_create)
         const int dh = c->embed_dim / c->heads;
+        // ProGen2: any even head_dim up to 256, zero-padded to one (<= 64), two (<= 128) or four (<= 256) slot groups per head
+        // (api_progen2.hip)
         const bool esm = c->arch == PGMI_ARCH_ESM1B || c->arch == PGMI_ARCH_ESM2;
+        const bool pg2 = c->arch == PGMI_ARCH_PROGEN2;
         const bool ok = c->embed_dim % c->heads == 0 &&
-                        (dh == kHeadDim || (dh < kHeadDim && dh % 2 == 0 && esm) || (dh == 2 * kHeadDim && esm));
+                        (dh == kHeadDim || (dh < kHeadDim && dh % 2 == 0 && esm) || (dh == 2 * kHeadDim && esm) ||
+                         (pg2 && dh % 2 == 0 && dh <= 4 * kHeadDim));
+        if (pg2 && !ok && c->embed_dim % c->heads == 0 && dh > 4 * kHeadDim) {
+            set_error("unsupported head_dim %d (embed_dim %d / heads %d): ProGen2 runs even head dims up to 256", dh, c->embed_dim, c->heads);
+            return PGMI_EINVAL;
+        }
         if (!ok) { set_error("unsupported head_dim %d (embed_dim %d / heads %d): this build supports head_dim 64, even head dims below 64 and head_dim 128 (ESM)", dh, c->embed_dim, c->heads); return PGMI_EINVAL; }
     }
     if (c->embed_dim % 32 || c->ffn_dim % 32) { set_error("embed_dim and ffn_dim must be multiples of 32"); return PGMI_EINVAL; }
@@ -46,6 +55,12 @@ int check_cfg(const pgmi_config* c) {
         if (c->heads % 4) { set_error("Invalid number of heads. Tranception requires the number of heads to be a multiple of 4."); return PGMI_EINVAL; }
         if (c->precision != PGMI_PREC_F16X3) { set_error("Tranception is available in precision f16x3 only"); return PGMI_EINVAL; }
         if (c->max_positions <= 0) { set_error("Tranception needs max_positions = n_ctx"); return PGMI_EINVAL; }
+    } else if (c->arch == PGMI_ARCH_PROGEN2) {
+        if (c->vocab != PGMI_PG2_VOCAB) { set_error("ProGen2 vocab must be %d", PGMI_PG2_VOCAB); return PGMI_EINVAL; }
+        // modeling_progen.py:157-168 splits the fused projection into mp_num = 8 blocks of whole heads
+        if (c->heads % 8) { set_error("ProGen2 needs the number of heads to be a multiple of 8 (mp_num = 8), got %d", c->heads); return PGMI_EINVAL; }
+        if (c->precision != PGMI_PREC_F16X3) { set_error("ProGen2 is available in precision f16x3 only"); return PGMI_EINVAL; }
+        if (c->max_positions <= 0) { set_error("ProGen2 needs max_positions = n_positions"); return PGMI_EINVAL; }
     } else if (c->vocab != PGMI_VOCAB) { set_error("vocab must be %d", PGMI_VOCAB); return PGMI_EINVAL; }
     if (c->arch == PGMI_ARCH_ESM1B && c->max_positions <= 0) { set_error("ESM-1b arch needs max_positions"); return PGMI_EINVAL; }
     if (c->arch == PGMI_ARCH_MSA) {
@@ -154,6 +169,8 @@ int64_t pgmi_weight_count(const pgmi_config* c) {
         const int64_t conv = 3 * ((64 * 3 + 64) + (64 * 5 + 64) + (64 * 7 + 64));
         return V * D + (int64_t)c->layers * (2 * D + (D * 3 * D + 3 * D) + conv + (D * D + D) + 2 * D + (D * F + F) + (F * D + D)) + 2 * D + V * D;
     }
+    if (c->arch == PGMI_ARCH_PROGEN2)        // include/pgmi.h: the ProGen2 blob
+        return V * D + (int64_t)c->layers * (2 * D + 3 * D * D + D * D + (F * D + F) + (D * F + D)) + 2 * D + V * D + V;
     if (c->arch == PGMI_ARCH_MSA) {
         const int64_t attn = 2 * D + 4 * (D * D + D);
         return V * D + (int64_t)(c->max_positions + 2) * D + 1024 * D + 2 * D +
@@ -168,6 +185,20 @@ int64_t pgmi_weight_count(const pgmi_config* c) {
 }
 
 int pgmi_model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int device, pgmi_model** out) {
+    if (cfg && cfg->arch == PGMI_ARCH_PROGEN2) {
+        if (out) *out = nullptr;
+        set_error("ProGen2 models are created with pgmi_pg2_model_create (it takes rotary_dim)");
+        return PGMI_EINVAL;
+    }
+    return model_create(cfg, w, n_weights, device, out, 0);
+}
+
+}  // extern "C"
+
+namespace pgmi {
+
+// pgmi_model_create and pgmi_pg2_model_create; rotary_dim is ProGen2's (0 for every other arch)
+int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int device, pgmi_model** out, int rotary_dim) {
     if (!out) { set_error("null out"); return PGMI_EINVAL; }
     *out = nullptr;
     int rc = check_cfg(cfg);
@@ -187,7 +218,7 @@ int pgmi_model_create(const pgmi_config* cfg, const float* w, int64_t n_weights,
     if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess) { set_error("hipStreamCreate failed"); delete m; return PGMI_EHIP; }
     const size_t D = cfg->embed_dim, F = cfg->ffn_dim, V = cfg->vocab;
     m->dh = cfg->embed_dim / cfg->heads;
-    m->rot_halves = m->dh > kHeadDim ? 2 : 1;
+    m->rot_halves = m->dh > 2 * kHeadDim ? 4 : m->dh > kHeadDim ? 2 : 1;     // 4: ProGen2 head dims above 128 (check_cfg)
     m->Hs = cfg->heads * m->rot_halves;
     m->Da = m->Hs * kHeadDim;
     m->ln_eps = cfg->ln_eps > 0.f ? cfg->ln_eps : 1e-5f;
@@ -196,6 +227,8 @@ int pgmi_model_create(const pgmi_config* cfg, const float* w, int64_t n_weights,
         TRY(create_tranception(m, cfg, w, n_weights));
     } else if (cfg->arch == PGMI_ARCH_MSA) {
         TRY(create_msa(m, cfg, w, n_weights));
+    } else if (cfg->arch == PGMI_ARCH_PROGEN2) {
+        TRY(create_progen2(m, cfg, w, n_weights, rotary_dim));
     } else {
     // embed_tokens == the tied lm_head.weight (esm1.py:101-105).  The host passes the matrix that
     // load_state_dict leaves in the tied parameter (pretrained.py:97,216), see proteingym_amd/esm.py.
@@ -317,6 +350,10 @@ int pgmi_model_create(const pgmi_config* cfg, const float* w, int64_t n_weights,
     *out = m;
     return PGMI_OK;
 }
+
+}  // namespace pgmi
+
+extern "C" {
 
 void pgmi_model_destroy(pgmi_model* m) {
     if (!m) return;

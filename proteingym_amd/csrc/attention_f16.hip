@@ -18,7 +18,10 @@
 
 namespace pgmi {
 
-template <int WPB, int OUT, int NSTG, int DH = 64, bool RAG = false>
+// DO < DH (head_dim 256): a workgroup computes the scores over all DH dims but the context of only the DO dims d0 .. d0 + DO - 1 of its
+// head (d0 = slice * DO, DH / DO slices per head, one more level of the launch's (sequence, head) list): the O accumulators of a
+// 32 x 256 tile (256 registers per lane) would not fit beside the Q fragments; S is recomputed once per slice.
+template <int WPB, int OUT, int NSTG, int DH = 64, bool RAG = false, int DO = DH>
 __global__ __launch_bounds__(WPB * 64) void attention_f16x3_v2_kernel(
     const unsigned short* __restrict__ qk16, size_t qk_plane, const unsigned short* __restrict__ vt16,
     size_t vt_plane, const int32_t* __restrict__ kv_len, const float* __restrict__ slopes, int T, int H,
@@ -31,11 +34,13 @@ __global__ __launch_bounds__(WPB * 64) void attention_f16x3_v2_kernel(
     // wave issues the same number NDMA of them (counted vmcnt needs a per-wave constant): when
     // 16 % WPB != 0 the surplus slots re-issue instruction (i - 16), i.e. write identical bytes twice.
     constexpr int KCPR = DH / 8;                        // 16-byte chunks per key row of a K plane
-    constexpr int KCH = AKT * KCPR, VCH = DH * 4;       // chunks per K plane / V^T plane of a tile
+    constexpr int KCH = AKT * KCPR, VCH = DO * 4;       // chunks per K plane / V^T plane (the slice's DO rows) of a tile
+    constexpr int NSL = DH / DO;                        // context slices per head
+    static_assert(NSL == 1 || (OUT == 1 && !RAG), "sliced context: split-plane output of dense launches only");
     constexpr int STG_CH = 2 * KCH + 2 * VCH;           // chunks per stage (16 KB at DH 64, 32 KB at DH 128)
     constexpr int NWI = STG_CH / 64;                    // wave-instructions per tile
     constexpr int NDMA = (NWI + WPB - 1) / WPB;
-    constexpr int NS = DH / 16, ND = DH / 32;
+    constexpr int NS = DH / 16, ND = DO / 32;
     extern __shared__ __attribute__((aligned(16))) u32x4 lds[];   // [NSTG][STG_CH]
 
     // Dense launches (dense_nblk > 0) are ONE-dimensional in an XCD-local order (workgroup i runs on XCD i % 8): the dense_nblk query
@@ -43,23 +48,25 @@ __global__ __launch_bounds__(WPB * 64) void attention_f16x3_v2_kernel(
     // XCD, dispatched together -- so that the K and V^T tiles every one of them streams reach that XCD's L2 once instead of once per
     // query block (the (nblk, H, B) grid, dense_nblk == 0, puts them on different XCDs: 2.45 x the algorithmic bytes fetched at
     // T = 288, profiles/r4).
-    int b, h, qblk_dense;
+    int b, h, qblk_dense, hs;                   // hs: (head, slice) index, h * NSL + slice
     if (RAG) {
         b = rag.ent_seq[blockIdx.x];
-        h = blockIdx.y;
+        hs = blockIdx.y;
         qblk_dense = 0;
     } else if (dense_nblk > 0) {
         const int within = (int)blockIdx.x % (8 * dense_nblk);
         const int pair = ((int)blockIdx.x / (8 * dense_nblk)) * 8 + (within & 7);
-        if (pair >= nseq * H) return;
+        if (pair >= nseq * H * NSL) return;
         qblk_dense = within >> 3;
-        b = pair / H;
-        h = pair - b * H;
+        b = pair / (H * NSL);
+        hs = pair - b * (H * NSL);
     } else {
         b = blockIdx.z;
-        h = blockIdx.y;
+        hs = blockIdx.y;
         qblk_dense = blockIdx.x;
     }
+    h = hs / NSL;
+    const int d0 = (hs - h * NSL) * DO;         // first context dim of this workgroup's slice
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // provably wave-uniform: scalar branches, SGPR DMA bases
     const int r = lane & 31, kh = lane >> 5;
@@ -139,8 +146,8 @@ __global__ __launch_bounds__(WPB * 64) void attention_f16x3_v2_kernel(
         } else {
             const int wv = wi - 2 * KCH / 64, p = wv / (VCH / 64), g = (wv % (VCH / 64)) * 64 + lane;
             const int d = g >> 2, c = (g & 3) ^ ((d >> 2) & 3);
-            voff[i] = voff_last[i] = d * Tpo * 2 + c * 16;
-            voff_root[i] = d * Tp * 2 + c * 16;
+            voff[i] = voff_last[i] = (d0 + d) * Tpo * 2 + c * 16;
+            voff_root[i] = (d0 + d) * Tp * 2 + c * 16;
             sbase[i] = (int)((unsigned int)p * (unsigned int)vt_plane * 2u);
             sstep[i] = (AKT / 8) * 16;
         }
@@ -346,7 +353,7 @@ __global__ __launch_bounds__(WPB * 64) void attention_f16x3_v2_kernel(
             // by store issue, not by bytes).  All 64 lanes take part in the swaps; rows beyond T only skip the stores.
             const float inv = 1.0f / l_tot;
             const bool row_ok = q0 + r < T && q0 + r >= p0;
-            unsigned short* rowp = ctx16 + (size_t)(orow0 + max(min(q0 + r, T - 1), p0)) * (size_t)(2 * D) + (size_t)(ND * h) * 64;
+            unsigned short* rowp = ctx16 + (size_t)(orow0 + max(min(q0 + r, T - 1), p0)) * (size_t)(2 * D) + (size_t)((h * DH + d0) / 32) * 64;
 #pragma unroll
             for (int dt = 0; dt < ND; ++dt)
 #pragma unroll
@@ -409,12 +416,12 @@ __global__ __launch_bounds__(WPB * 64) void attention_f16x3_v2_kernel(
 // prefetch hides is small beside that.  The XCD-local block ORDER alone (the query blocks of one (sequence, head) on one XCD, K / V^T fetched
 // into its L2 once) is +2.5 % at T = 1024 and -2 % at T = 288 (att_ab_1_xcd_local_order.log): fetch traffic is not what bounds this kernel.
 
-template <int WPB, int OUT, int NSTG, int DH, bool RAG = false>
+template <int WPB, int OUT, int NSTG, int DH, bool RAG = false, int DO = DH>
 static int launch_att16v2_one(dim3 grid, const unsigned short* qk16, size_t qk_plane, const unsigned short* vt16, size_t vt_plane,
                               const int32_t* kv_len, const float* slopes, int T, int H, int Tp, float* ctx, unsigned short* ctx16,
                               size_t plane, hipStream_t s, RagMap rag = RagMap{}, int dense_nblk = 0, int nseq = 0) {
-    constexpr size_t lds_bytes = (size_t)NSTG * (DH * 16) * 16;          // stage = DH * 16 chunks of 16 B
-    auto kfn = attention_f16x3_v2_kernel<WPB, OUT, NSTG, DH, RAG>;
+    constexpr size_t lds_bytes = (size_t)NSTG * (8 * DH + 8 * DO) * 16;  // stage = K (2 planes x 32 keys x DH / 8) + V^T (2 x DO x 4) chunks of 16 B
+    auto kfn = attention_f16x3_v2_kernel<WPB, OUT, NSTG, DH, RAG, DO>;
     if (lds_bytes > 65536) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PGMI_EHIP; }
@@ -470,7 +477,7 @@ int launch_attention_f16x3_v2(const float* qkv, const int32_t* kv_len, const flo
                               int rotary, int B, int T, int H, unsigned short* qk16, size_t qk_plane,
                               unsigned short* vt16, size_t vt_plane, float* ctx, unsigned short* ctx16, size_t plane,
                               int out_mode, hipStream_t s, const float* conv, const float* slopes, int head_dim) {
-    if (B <= 0 || T <= 0 || H <= 0 || out_mode < 0 || out_mode > 2 || (head_dim != 64 && head_dim != 128)) {      // out_mode 2: one bf16 plane
+    if (B <= 0 || T <= 0 || H <= 0 || out_mode < 0 || out_mode > 2 || (head_dim != 64 && head_dim != 128 && head_dim != 256)) {      // out_mode 2: one bf16 plane
         set_error("attention_f16x3_v2: bad arguments B=%d T=%d H=%d out=%d head_dim=%d", B, T, H, out_mode, head_dim);
         return PGMI_EINVAL;
     }
@@ -489,16 +496,33 @@ int launch_attention_f16x3_v2(const float* qkv, const int32_t* kv_len, const flo
             return PGMI_EINVAL;
         }
     }
+    if (head_dim == 256) {
+        // ProGen2-xlarge: H heads of 256 = 4 H slot groups of 64; causal only, fused-QKV operands, split-plane context out.  Sizing (160 KiB
+        // LDS per CU; VGPRs and AGPRs share one file of 512 per lane at one wave per SIMD): Q fragments of 256 dims are 2 x 16 x 4 = 128
+        // registers per lane, and the O accumulators (main + 2^-11 correction) of all 256 dims would be 256 more -- so each workgroup
+        // keeps the context of one 128-dim slice (DO = 128: 128 O registers; two slices per head, S computed by both).  A stage holds K
+        // (2 planes x 32 keys x 512 B) and the slice's V^T (2 x 128 x 64 B) = 48 KiB; the ring is 2 stages (96 KiB) with Q straight from
+        // the planes: the Q-via-LDS staging of the 3-stage ring would need 4 waves x 32 KiB inside stages 1 .. 2.
+        if (qkv || conv || !slopes || out_mode != 1) { set_error("attention_f16x3_v2: head_dim 256 is the causal, fused-QKV, split-plane-output flavour only"); return PGMI_EINVAL; }
+        const int nblk = (n32 + 3) / 4;
+        int dn = 0;
+        const dim3 grid = dense_grid(nblk, 2 * H, B, &dn);       // (sequence, head, slice) pairs
+        rc = launch_att16v2_one<4, 1, 2, 256, false, 128>(grid, qk16, qk_plane, vt16, vt_plane, kv_len, slopes, T, H, Tp, ctx, ctx16, plane, s, RagMap{}, dn, B);
+        if (rc) return rc;
+        PGMI_HIP(hipGetLastError());
+        return PGMI_OK;
+    }
     if (head_dim == 128) {
         // ESM2-15B class: H heads of 128 = 2 H slot groups of 64 in the operand planes; only the fused-QKV operand path
-        // (no prep pass), no causal / ALiBi flavour; 2-stage ring (2 x 32 KB) so that two workgroups share a CU
-        if (qkv || conv || slopes) { set_error("attention_f16x3_v2: head_dim 128 needs operands from the fused QKV projection"); return PGMI_EINVAL; }
+        // (no prep pass), no depth-wise convolution; 3-stage ring (3 x 32 KB).  slopes != nullptr: the causal flavour (ProGen2, head
+        // dims 80 / 96 / 128 zero-padded into the 128-lane layout; its all-zero slopes make the ALiBi term exactly 0)
+        if (qkv || conv) { set_error("attention_f16x3_v2: head_dim 128 needs operands from the fused QKV projection"); return PGMI_EINVAL; }
         const int nblk = (n32 + 3) / 4;
         int dn = 0;
         const dim3 grid = dense_grid(nblk, H, B, &dn);
-        if (out_mode == 0) rc = launch_att16v2_one<4, 0, 3, 128>(grid, qk16, qk_plane, vt16, vt_plane, kv_len, nullptr, T, H, Tp, ctx, ctx16, plane, s, RagMap{}, dn, B);
-        else if (out_mode == 2) rc = launch_att16v2_one<4, 3, 3, 128>(grid, qk16, qk_plane, vt16, vt_plane, kv_len, nullptr, T, H, Tp, ctx, ctx16, plane, s, RagMap{}, dn, B);
-        else rc = launch_att16v2_one<4, 1, 3, 128>(grid, qk16, qk_plane, vt16, vt_plane, kv_len, nullptr, T, H, Tp, ctx, ctx16, plane, s, RagMap{}, dn, B);
+        if (out_mode == 0) rc = launch_att16v2_one<4, 0, 3, 128>(grid, qk16, qk_plane, vt16, vt_plane, kv_len, slopes, T, H, Tp, ctx, ctx16, plane, s, RagMap{}, dn, B);
+        else if (out_mode == 2) rc = launch_att16v2_one<4, 3, 3, 128>(grid, qk16, qk_plane, vt16, vt_plane, kv_len, slopes, T, H, Tp, ctx, ctx16, plane, s, RagMap{}, dn, B);
+        else rc = launch_att16v2_one<4, 1, 3, 128>(grid, qk16, qk_plane, vt16, vt_plane, kv_len, slopes, T, H, Tp, ctx, ctx16, plane, s, RagMap{}, dn, B);
         if (rc) return rc;
         PGMI_HIP(hipGetLastError());
         return PGMI_OK;

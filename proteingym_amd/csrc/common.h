@@ -26,7 +26,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kWave = 64;
 constexpr int kHeadDim = 64;
 
-enum Epilogue { EPI_NONE = 0, EPI_GELU = 1, EPI_SQRELU = 2 };   // erf-GELU (ESM), squared ReLU (Tranception)
+enum Epilogue { EPI_NONE = 0, EPI_GELU = 1, EPI_SQRELU = 2, EPI_GELU_TANH = 3 };   // erf-GELU (ESM), squared ReLU (Tranception), tanh-GELU (ProGen2)
 
 // f16x3 activation split: x ~= hi + lo * 2^-11 with hi = fp16(x) and lo = fp16((x - hi) * 2^11).
 // The scaled lo keeps its 11 bits for every |x| >= 2^-14 (an unscaled lo would be an fp16
@@ -88,6 +88,8 @@ void launch_seq_loglik(const float* lp, const int32_t* tokens, const int32_t* le
 void launch_seq_loglik_ragged(const float* lp, const int32_t* tokens, const int32_t* seq_off, const int32_t* seq_p,
                               const int32_t* seq_root, int B, int T, int V, const float* prior, const int32_t* a0,
                               const int32_t* row0, const int32_t* n, const int32_t* flip, float alpha, float* out, hipStream_t s);
+// ProGen2: out[b] = sum over t < n_kept[b] of lp[b*T + t, col[b*T + t]] (lp [B*T,V], one wave per sequence, fixed lane order)
+void launch_pg2_seq_loglik(const float* lp, const int32_t* col, const int32_t* n_kept, int B, int T, int V, float* out, hipStream_t s);
 void launch_score_mutants(const float* table, int V, const int32_t* sub_pos, const int32_t* sub_wt,
                           const int32_t* sub_mt, const int64_t* mut_off, int64_t n_mut,
                           double* scores, hipStream_t s);

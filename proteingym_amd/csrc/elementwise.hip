@@ -432,6 +432,26 @@ void launch_seq_loglik(const float* lp, const int32_t* tokens, const int32_t* le
                        flip, alpha, out);
 }
 
+// ---- ProGen2 sequence log-likelihood (one wave per sequence) ---------------------------------
+// lp holds the log-softmax over the 25 amino-acid columns 5..29 only (compute_fitness.py:67-70); col[b*T + t] is target t's column
+// (token id - 5) and n_kept[b] the targets left after the terminal strip (:60-64).  Every row's partial sums run over the same lanes
+// in the same order whatever else is in the launch: a sequence gets the same bits in any batch.
+__global__ __launch_bounds__(256) void pg2_seq_loglik_kernel(const float* __restrict__ lp, const int32_t* __restrict__ col,
+                                                             const int32_t* __restrict__ n_kept, int B, int T, int V,
+                                                             float* __restrict__ out) {
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (b >= B) return;
+    const int n = n_kept[b];
+    double acc = 0.0;
+    for (int t = lane; t < n; t += 64) acc += (double)lp[((size_t)b * T + t) * V + col[(size_t)b * T + t]];
+    acc = wave_sum_d(acc);
+    if (lane == 0) out[b] = (float)acc;
+}
+void launch_pg2_seq_loglik(const float* lp, const int32_t* col, const int32_t* n_kept, int B, int T, int V, float* out, hipStream_t s) {
+    hipLaunchKernelGGL(pg2_seq_loglik_kernel, dim3((B + 3) / 4), dim3(256), 0, s, lp, col, n_kept, B, T, V, out);
+}
+
 // ---- label_row (compute_fitness.py:240-250): score = sum_subs f32(lp[mt] - lp[wt]) in double ---
 __global__ void score_mutants_kernel(const float* __restrict__ table, int V,
                                      const int32_t* __restrict__ sub_pos,

@@ -37,6 +37,21 @@ __device__ __forceinline__ f32x4 gelu_erf16(f32x4 x) {
     return __builtin_elementwise_fma(b, e, __builtin_elementwise_max(x, all(0.0f)));
 }
 
+// tanh-GELU ("gelu_new", transformers/activations.py NewGELUActivation; ProGen2 modeling_progen.py:230-232):
+//   0.5 x (1 + tanh(u)),  u = sqrt(2/pi) (x + 0.044715 x^3)   ==   x / (1 + 2^(-2 u log2 e))
+// The logistic form has no 1 + tanh cancellation for x < 0; for x -> -inf the denominator goes to +inf and the value to -0, for
+// x -> +inf to x.  A NaN in x stays NaN (every step propagates it), so the fp16 range guard downstream still sees it.
+__device__ __forceinline__ f32x4 gelu_tanh16(f32x4 x) {
+    constexpr float c = -2.0f * 0.7978845608028654f * 1.4426950408889634f;     // -2 sqrt(2/pi) log2(e)
+    f32x4 r;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float u = fmaf(0.044715f * x[e], x[e] * x[e], x[e]);
+        r[e] = x[e] / (1.0f + __builtin_amdgcn_exp2f(c * u));
+    }
+    return r;
+}
+
 // Attention operands straight from the fused QKV projection (OUT 2): q|k as split planes qk16 [2][M][2D] (ESM2 rotary
 // applied here, rotary_embedding.py:11-20), v as the transposed, key-permuted planes vt16 [2][B*H*64][Tp] that
 // attention_f16.hip consumes.
@@ -514,6 +529,7 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
 #pragma unroll
                         for (int e = 0; e < 4; ++e) val[e] = fmaf(a[e], out_scale, bv[j][e]);
                         if (EPI == EPI_GELU) val = gelu_erf16(val);
+                        if (EPI == EPI_GELU_TANH) val = gelu_tanh16(val);
                         if (EPI == EPI_SQRELU)   // tranception/activations.py:79-84
 #pragma unroll
                         for (int e = 0; e < 4; ++e) { const float t = fmaxf(val[e], 0.0f); val[e] = t * t; }
@@ -569,6 +585,7 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
 #pragma unroll
                             for (int e = 0; e < 4; ++e) val[e] = fmaf(acc[j][i][4 * g + e], out_scale, bv[e]);
                             if (EPI == EPI_GELU) val = gelu_erf16(val);
+                            if (EPI == EPI_GELU_TANH) val = gelu_tanh16(val);
                             if (EPI == EPI_SQRELU)
 #pragma unroll
                             for (int e = 0; e < 4; ++e) { const float t = fmaxf(val[e], 0.0f); val[e] = t * t; }
@@ -626,6 +643,7 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
 #pragma unroll
                         for (int e = 0; e < 4; ++e) val[e] = fmaf(acc[j][i][4 * g + e], out_scale, bv[e]);
                         if (EPI == EPI_GELU) val = gelu_erf16(val);
+                        if (EPI == EPI_GELU_TANH) val = gelu_tanh16(val);
                         if (EPI == EPI_SQRELU)   // tranception/activations.py:79-84
 #pragma unroll
                         for (int e = 0; e < 4; ++e) { const float t = fmaxf(val[e], 0.0f); val[e] = t * t; }

@@ -160,6 +160,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(
 #pragma unroll
                 for (int e = 0; e < 4; ++e) val[e] = acc[j][i][4 * g + e] + bv[e];
                 if (EPI == EPI_GELU) val = gelu_erf16(val);
+                if (EPI == EPI_GELU_TANH) val = gelu_tanh16(val);
                 if (EPI == EPI_SQRELU)
 #pragma unroll
                         for (int e = 0; e < 4; ++e) { const float t = fmaxf(val[e], 0.0f); val[e] = t * t; }
@@ -202,6 +203,7 @@ static int launch_bf16_cfg(const unsigned short* A, const unsigned short* W, con
     const int out = Ch ? 1 : 0;
     if (epilogue == EPI_GELU) { if (out) PGMI_LAUNCH_BF16(EPI_GELU, 1); else PGMI_LAUNCH_BF16(EPI_GELU, 0); }
     else if (epilogue == EPI_SQRELU) { if (out) PGMI_LAUNCH_BF16(EPI_SQRELU, 1); else PGMI_LAUNCH_BF16(EPI_SQRELU, 0); }
+    else if (epilogue == EPI_GELU_TANH) { if (out) PGMI_LAUNCH_BF16(EPI_GELU_TANH, 1); else PGMI_LAUNCH_BF16(EPI_GELU_TANH, 0); }
     else { if (out) PGMI_LAUNCH_BF16(EPI_NONE, 1); else PGMI_LAUNCH_BF16(EPI_NONE, 0); }
 #undef PGMI_LAUNCH_BF16
     PGMI_HIP(hipGetLastError());
@@ -316,6 +318,7 @@ static int launch_gemm16x_one(const unsigned short* A, const unsigned short* W,
     if (qkv) PGMI_LAUNCH16X(EPI_NONE, 2);
     else if (epilogue == EPI_GELU) PGMI_LAUNCH16X_O(EPI_GELU);
     else if (epilogue == EPI_SQRELU) PGMI_LAUNCH16X_O(EPI_SQRELU);
+    else if (epilogue == EPI_GELU_TANH) PGMI_LAUNCH16X_O(EPI_GELU_TANH);
     else PGMI_LAUNCH16X_O(EPI_NONE);
 #undef PGMI_LAUNCH16X_O
 #undef PGMI_LAUNCH16X

@@ -32,6 +32,10 @@ constexpr int GROUP_M = 8;
 __device__ __forceinline__ float gelu_erf(float x) {
     return x * 0.5f * (1.0f + erff(x * 0.70710678118654752440f));
 }
+// gelu_new (ProGen2), as transformers writes it: 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3)))
+__device__ __forceinline__ float gelu_tanh(float x) {
+    return 0.5f * x * (1.0f + tanhf(0.7978845608028654f * (x + 0.044715f * x * x * x)));
+}
 
 template <int EPI>
 __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(
@@ -169,6 +173,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(
                 if (m < M) {
                     float val = acc[i][j][v] + bv;
                     if (EPI == EPI_GELU) val = gelu_erf(val);
+                    if (EPI == EPI_GELU_TANH) val = gelu_tanh(val);
                     const size_t o = (size_t)m * N + n;
                     if (residual) val = residual[o] + val;
                     C[o] = val;
@@ -188,6 +193,8 @@ int launch_gemm_f32(const float* A, const float* W, const float* bias, const flo
     const dim3 grid(tiles_m * tiles_n), block(256);
     if (epilogue == EPI_GELU)
         hipLaunchKernelGGL((gemm_f32_kernel<EPI_GELU>), grid, block, 0, s, A, W, bias, residual, C, M, N, K, tiles_m, tiles_n);
+    else if (epilogue == EPI_GELU_TANH)
+        hipLaunchKernelGGL((gemm_f32_kernel<EPI_GELU_TANH>), grid, block, 0, s, A, W, bias, residual, C, M, N, K, tiles_m, tiles_n);
     else
         hipLaunchKernelGGL((gemm_f32_kernel<EPI_NONE>), grid, block, 0, s, A, W, bias, residual, C, M, N, K, tiles_m, tiles_n);
     PGMI_HIP(hipGetLastError());

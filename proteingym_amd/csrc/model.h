@@ -3,6 +3,7 @@
 //   api_model.hip        errors, configuration check, weight upload, model create / destroy, options, profiling
 //   api_esm.hip          ESM-1b / ESM-1v / ESM2 forward (run_encoder, run_head), masked-marginals assays, pseudo-ppl libraries
 //   api_tranception.hip  Tranception forward, dense and prefix-shared; token log-probs and sequence log-likelihoods
+//   api_progen2.hip      ProGen2 forward (parallel residual, GPT-J rotary); token log-probs and sequence log-likelihoods
 //   api_msa.hip          MSA Transformer forward (tied row attention, column attention)
 //   api_host.hip         host-only entries: mutant parser, table -> scores, optimal window
 //   api_ops.hip          single-op and timing entries for the numerics tests and the A/B scripts
@@ -70,6 +71,10 @@ struct pgmi_model {
     int tr_prior_rows = 0;
     int32_t* tr_meta = nullptr;                         // prefix-shared scoring: the chunk's index arrays (TrChunk)
     size_t tr_meta_cap = 0;
+    // ProGen2: rotary_dim, the biased 32-column head and its amino-acid rows 5..29, zero bias of the bias-free projections, zero slopes
+    int pg2_rotary = 0;
+    float *pg2_head_w = nullptr, *pg2_head_b = nullptr, *pg2_aa_w = nullptr, *pg2_aa_b = nullptr;
+    float *pg2_zero = nullptr, *pg2_slopes = nullptr;
     // MSA Transformer
     float* msa_pe = nullptr;                            // msa_position_embedding [1024, D]
     float* xt = nullptr;                                // residual stream in column-major token order
@@ -88,7 +93,7 @@ struct pgmi_model {
     int keep_rows = 1;                                 // last layer's row-local stages on the kept rows only (PGMI_KEEP_ROWS)
     int last_B = 0, last_T = 0;
     int dh = kHeadDim;    // true head dim; heads are laid out in 64-lane slot groups (pgmi_model_create)
-    int rot_halves = 1;   // slot groups per head: 1, or 2 for head_dim 128
+    int rot_halves = 1;   // slot groups per head: 1, 2 for head_dim 128 (and ProGen2's 80 / 96), 4 for ProGen2's 256
     int Hs = 0;           // slot groups per token = heads * rot_halves
     int Da = 0;           // attention width = heads * 64 (== embed_dim when dh == 64)
     float *rot_cos = nullptr, *rot_sin = nullptr;
@@ -199,6 +204,7 @@ int linear(pgmi_model* m, const float* in32, const unsigned short* in16, size_t 
            const W16& w16, const float* bias, const float* residual, float* out32, unsigned short* out16,
            size_t out_plane, int M, int N, int K, int epi);
 int check_nonfinite(pgmi_model* m);
+int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int device, pgmi_model** out, int rotary_dim);
 // api_esm.hip
 int ensure_rotary(pgmi_model* m, int T);
 int run_encoder(pgmi_model* m, int B, int T, const int32_t* keep = nullptr, int n_keep = 0, bool* compacted = nullptr);
@@ -207,6 +213,8 @@ int run_rows(pgmi_model* m, int B, int T, int R, const int32_t* row_idx);
 // api_tranception.hip
 int create_tranception(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights);
 int run_tranception(pgmi_model* m, int B, int T);
+// api_progen2.hip
+int create_progen2(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights, int rotary_dim);
 // api_msa.hip
 int create_msa(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights);
 int run_msa(pgmi_model* m, int R, int C, int keep_col = -1, bool* compacted = nullptr);

@@ -328,3 +328,58 @@ def random_msa_transformer_arrays(cfg, seed: int, embed_std: float = 0.25) -> Di
             out[k] = ((rng.random(shape) * 2 - 1) * b).astype(np.float32)
     out["lm_head.weight"] = out["embed_tokens.weight"]
     return out
+
+
+# ProGen2 (proteingym_amd/progen2.py).  Widths of the released checkpoints (ProGen2 paper, Table 1); rotary_dim here is a test value --
+# the product reads every dimension from the checkpoint's config.json.
+PROGEN2_WIDTHS = {
+    "small": dict(embed_dim=1024, heads=16, rotary_dim=32),
+    "medium": dict(embed_dim=1536, heads=16, rotary_dim=48),
+    "large": dict(embed_dim=2560, heads=32, rotary_dim=32),
+    "xlarge": dict(embed_dim=4096, heads=16, rotary_dim=64),
+}
+
+
+def progen2_config(layers: int, embed_dim: int, heads: int, rotary_dim: int, n_positions: int = 1024, ffn_dim: int = 0) -> dict:
+    return dict(layers=layers, embed_dim=embed_dim, heads=heads, ffn_dim=ffn_dim or 4 * embed_dim, vocab=32,
+                max_positions=n_positions, rotary_dim=rotary_dim, ln_eps=1e-5)
+
+
+def progen2_state_dict(cfg: dict, seed: int) -> Dict[str, np.ndarray]:
+    """Seeded random ProGen2 weights under the HF state-dict keys of modeling_progen.py (qkv_proj.weight in its stored mp_num = 8
+    q | v | k block order).  Linear weights ~ N(0, 1/fan_in), LayerNorm gains 1 + N(0, 0.1^2), biases N(0, 0.02^2), wte N(0, 1),
+    the LM head 3x wider so that the log-probabilities are far from uniform."""
+    rng = np.random.default_rng(seed)
+    D, F, V = cfg["embed_dim"], cfg["ffn_dim"], cfg["vocab"]
+
+    def normal(shape, std):
+        return (rng.standard_normal(shape, dtype=np.float32) * np.float32(std)).astype(np.float32)
+    sd = {"transformer.wte.weight": normal((V, D), 1.0)}
+    for i in range(cfg["layers"]):
+        p = f"transformer.h.{i}."
+        sd[p + "ln_1.weight"] = 1.0 + normal((D,), 0.1)
+        sd[p + "ln_1.bias"] = normal((D,), 0.02)
+        sd[p + "attn.qkv_proj.weight"] = normal((3 * D, D), D ** -0.5)
+        sd[p + "attn.out_proj.weight"] = normal((D, D), D ** -0.5)
+        sd[p + "mlp.fc_in.weight"] = normal((F, D), D ** -0.5)
+        sd[p + "mlp.fc_in.bias"] = normal((F,), 0.02)
+        sd[p + "mlp.fc_out.weight"] = normal((D, F), F ** -0.5)
+        sd[p + "mlp.fc_out.bias"] = normal((D,), 0.02)
+    sd["transformer.ln_f.weight"] = 1.0 + normal((D,), 0.1)
+    sd["transformer.ln_f.bias"] = normal((D,), 0.02)
+    sd["lm_head.weight"] = normal((V, D), 3.0 * D ** -0.5)
+    sd["lm_head.bias"] = normal((V,), 0.1)
+    return sd
+
+
+def save_progen2_checkpoint(path: str, cfg: dict, sd: Dict[str, np.ndarray]):
+    """config.json + pytorch_model.bin in the layout of the released ProGen2 checkpoints."""
+    import json
+    import torch
+    os.makedirs(path, exist_ok=True)
+    c = dict(model_type="progen", vocab_size=cfg["vocab"], n_positions=cfg["max_positions"], n_ctx=cfg["max_positions"],
+             n_embd=cfg["embed_dim"], n_layer=cfg["layers"], n_head=cfg["heads"], rotary_dim=cfg["rotary_dim"],
+             n_inner=cfg["ffn_dim"] if cfg["ffn_dim"] != 4 * cfg["embed_dim"] else None, activation_function="gelu_new",
+             layer_norm_epsilon=cfg["ln_eps"], resid_pdrop=0.0, embd_pdrop=0.0, attn_pdrop=0.0, bos_token_id=1, eos_token_id=2)
+    json.dump(c, open(os.path.join(path, "config.json"), "w"), indent=1)
+    torch.save({k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in sd.items()}, os.path.join(path, "pytorch_model.bin"))

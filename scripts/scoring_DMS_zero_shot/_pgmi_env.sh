@@ -43,3 +43,10 @@ pgmi_tranception() {
         --DMS_data_folder "${folder}" --DMS_reference_file_path "${mapping}" --output_scores_folder "${output_scores_folder}" "$@"
 }
 ESM1V_FIVE="${model_checkpoint1:-/path/to/esm1v_t33_650M_UR90S_1.pt} ${model_checkpoint2:-/path/to/esm1v_t33_650M_UR90S_2.pt} ${model_checkpoint3:-/path/to/esm1v_t33_650M_UR90S_3.pt} ${model_checkpoint4:-/path/to/esm1v_t33_650M_UR90S_4.pt} ${model_checkpoint5:-/path/to/esm1v_t33_650M_UR90S_5.pt}"
+# pgmi_progen2 <mapping csv> <data folder> [more flags]: assay ${DMS_index} through score_progen2_proteingym with ${Progen2_model_name_or_path}
+pgmi_progen2() {
+    local mapping="$1" folder="$2"; shift 2
+    pgmi_run proteingym_amd.score_progen2_proteingym --Progen2_model_name_or_path "${Progen2_model_name_or_path:=/path/to/progen2-small}" \
+        --DMS_reference_file_path "${mapping}" --DMS_data_folder "${folder}" --DMS_index "${DMS_index:=0}" \
+        --output_scores_folder "${output_scores_folder}" "$@"
+}
