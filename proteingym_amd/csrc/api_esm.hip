@@ -4,32 +4,71 @@
 
 namespace pgmi {
 
+// ESM-1b / ESM2 weight blob (include/pgmi.h).  embed_tokens == the tied lm_head.weight (esm1.py:101-105): the host passes the matrix
+// that load_state_dict leaves in the tied parameter (pretrained.py:97,216), see proteingym_amd/esm.py.
+int create_esm(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights) {
+    const size_t D = cfg->embed_dim, F = cfg->ffn_dim, V = cfg->vocab, dh = m->dh, Da = m->Da;
+    BlobCursor c(m, w, n_weights);
+    c.upload(&m->embed_tokens, V * D);
+    if (cfg->arch == PGMI_ARCH_ESM1B) c.upload(&m->embed_positions, (size_t)(cfg->max_positions + 2) * D);
+    if (cfg->emb_layer_norm_before) {
+        c.upload(&m->lnb_w, D);
+        c.upload(&m->lnb_b, D);
+    }
+    // head layout: every head owns 64 lanes of the attention kernels; dim j of a head sits in slot
+    // j (first half) or 32 + (j - dh/2) (second half) so that rotary pairs (j, j + dh/2) are the
+    // kernels' pairs (i, i + 32).  dh == 64 is the identity layout; smaller heads leave zero slots
+    // (zero weight rows -> q,k,v slots exactly 0 -> scores and context unchanged).
+    // head_dim 128: a head is two slot groups; group g in {0,1} holds dims 32 g + i (slots i < 32) and 64 + 32 g + i (slots 32 + i), so
+    // the rotary partners (j, j + 64) are again the kernels' pairs (i, i + 32) inside ONE 64-column wave tile of the QKV epilogue.
+    auto slot = [&](size_t col) -> size_t {
+        const size_t h = col / dh, j = col % dh;
+        if (dh > 64) return (2 * h + ((j >> 5) & 1)) * 64 + ((j >> 6) << 5) + (j & 31);
+        return h * 64 + (j < dh / 2 ? j : 32 + (j - dh / 2));
+    };
+    const float qscale = 1.0f / sqrtf((float)dh);           // multihead_attention.py:261 (exact 1/8 for dh 64)
+    m->layers.resize(cfg->layers);
+    std::vector<float> wq(3 * Da * D, 0.0f), bq(3 * Da, 0.0f), wo_r(D * Da, 0.0f);
+    for (int l = 0; l < cfg->layers; ++l) {
+        Layer& L = m->layers[l];
+        c.upload(&L.ln1_w, D);
+        c.upload(&L.ln1_b, D);
+        pack_qkv_slots(c.take(3 * (D * D + D)), D, Da, slot, qscale, wq.data(), bq.data());
+        c.linear(&L.wqkv, &L.wqkv16, wq.data(), wq.size(), D);
+        c.upload(&L.bqkv, bq.data(), bq.size());
+        pack_out_cols(c.take(D * D), D, Da, slot, wo_r.data());
+        c.linear(&L.wo, &L.wo16, wo_r.data(), wo_r.size(), Da);
+        c.upload(&L.bo, D);
+        c.upload(&L.ln2_w, D);
+        c.upload(&L.ln2_b, D);
+        c.linear(&L.w1, &L.w116, F * D, D);
+        c.upload(&L.b1, F);
+        c.linear(&L.w2, &L.w216, D * F, F);
+        c.upload(&L.b2, D);
+    }
+    c.upload(&m->lna_w, D);
+    c.upload(&m->lna_b, D);
+    c.linear(&m->hd_w, &m->hd16, D * D, D);
+    c.upload(&m->hd_b, D);
+    c.upload(&m->hln_w, D);
+    c.upload(&m->hln_b, D);
+    c.upload(&m->h_bias, V);
+    return c.finish();
+}
+
 int ensure_rotary(pgmi_model* m, int T) {
     if (m->cfg.arch != PGMI_ARCH_ESM2 || T <= m->rot_len) return PGMI_OK;
     // rotary_embedding.py:40,52-58: inv_freq = 1/10000^(2i/d) in f32; freqs = t * inv_freq (f32);
     // emb = cat(freqs, freqs); cos/sin taken in f32.
-    const int n = std::max(T, 1026);
     const int rh = m->rot_halves;                          // table rows per token: slot-group parity for head_dim 128
-    std::vector<float> c((size_t)n * rh * 64), s((size_t)n * rh * 64);
     float inv[64];
     const int half = m->dh / 2;                            // rotary pairs are (j, j + dh/2)
     for (int i = 0; i < half; ++i) inv[i] = 1.0f / powf(10000.0f, (float)(2 * i) / (float)m->dh);
     // slots i and 32+i of slot group g hold dims j and j + dh/2 with j = i (dh <= 64) or 32 g + i (dh 128)
-    for (int t = 0; t < n; ++t)
-        for (int g = 0; g < rh; ++g)
-            for (int i = 0; i < 32; ++i) {
-                const int j = (rh == 1) ? i : 32 * g + i;
-                const float f = j < half ? (float)t * inv[j] : 0.0f;       // padded slots (dh < 64): cos 1, sin 0
-                const size_t o = ((size_t)t * rh + g) * 64;
-                c[o + i] = c[o + 32 + i] = cosf(f);
-                s[o + i] = s[o + 32 + i] = sinf(f);
-            }
-    int rc = dev_upload(m->allocs, &m->rot_cos, c.data(), c.size());
-    if (rc) return rc;
-    rc = dev_upload(m->allocs, &m->rot_sin, s.data(), s.size());
-    if (rc) return rc;
-    m->rot_len = n;
-    return PGMI_OK;
+    return upload_rotary(m, std::max(T, 1026), rh, [&](int t, int g, int i) {
+        const int j = (rh == 1) ? i : 32 * g + i;
+        return j < half ? (float)t * inv[j] : 0.0f;                        // padded slots (dh < 64): cos 1, sin 0
+    });
 }
 
 // Runs the encoder on tokens already in m->tokens [B,T]; leaves the residual stream in m->x.
@@ -49,14 +88,8 @@ int run_encoder(pgmi_model* m, int B, int T, const int32_t* keep, int n_keep, bo
         return PGMI_EINVAL;
     }
     int rc = ensure_rotary(m, T);
+    if (!rc) rc = reset_pad_keys(m, B, T);
     if (rc) return rc;
-    if (m->vt16 && (B != m->last_B || T != m->last_T)) {
-        // pad keys (t >= T inside the last 32-key tile) are never written by the fused QKV epilogue:
-        // they must hold finite data (their softmax weight is exactly 0)
-        PGMI_HIP(hipMemsetAsync(m->vt16, 0, m->vt16_plane * 2 * sizeof(unsigned short), s));
-        m->last_B = B;
-        m->last_T = T;
-    }
     {
         ProfScope p(m, PGMI_K_EMBED, 0, (double)M * D * 4);
         launch_seq_stats(m->tokens, B, T, c.token_dropout, m->denom, m->pos_idx, m->kv_len, s);
@@ -183,19 +216,16 @@ int pgmi_token_logprobs(pgmi_model* m, const int32_t* tokens, int B, int T, floa
     int rc = check_tokens(tokens, B, T);
     if (rc) return rc;
     PGMI_HIP(hipSetDevice(m->device));
-    const int per = std::max(1, m->max_rows / ((T + 31) / 32 * 32));     // B * roundup(T,32) <= max_rows
     const int V = m->cfg.vocab;
-    for (int b0 = 0; b0 < B; b0 += per) {
-        const int bc = std::min(per, B - b0);
+    rc = for_each_chunk(m, B, T, [&](int b0, int bc) {
         PGMI_HIP(hipMemcpyAsync(m->tokens, tokens + (size_t)b0 * T, (size_t)bc * T * 4, hipMemcpyHostToDevice, m->stream));
-        rc = run_encoder(m, bc, T);
-        if (rc) return rc;
-        rc = run_head(m, bc * T, nullptr);
+        int rc = run_encoder(m, bc, T);
+        if (!rc) rc = run_head(m, bc * T, nullptr);
         if (rc) return rc;
         PGMI_HIP(hipMemcpyAsync(out + (size_t)b0 * T * V, m->lp, (size_t)bc * T * V * 4, hipMemcpyDeviceToHost, m->stream));
-        PGMI_HIP(hipStreamSynchronize(m->stream));
-    }
-    return check_nonfinite(m);
+        return PGMI_OK;
+    });
+    return rc ? rc : check_nonfinite(m);
 }
 
 int pgmi_masked_logprobs(pgmi_model* m, const int32_t* tokens, const int32_t* mask_pos, int B, int T, float* out) {
@@ -206,23 +236,21 @@ int pgmi_masked_logprobs(pgmi_model* m, const int32_t* tokens, const int32_t* ma
     for (int b = 0; b < B; ++b)
         if (mask_pos[b] < 0 || mask_pos[b] >= T) { set_error("mask_pos[%d]=%d out of range", b, mask_pos[b]); return PGMI_EINVAL; }
     PGMI_HIP(hipSetDevice(m->device));
-    const int per = std::max(1, m->max_rows / ((T + 31) / 32 * 32));
     const int V = m->cfg.vocab;
     std::vector<int32_t> ridx;
-    for (int b0 = 0; b0 < B; b0 += per) {
-        const int bc = std::min(per, B - b0);
+    rc = for_each_chunk(m, B, T, [&](int b0, int bc) {
         ridx.resize(bc);
         for (int b = 0; b < bc; ++b) ridx[b] = b * T + mask_pos[b0 + b];
         PGMI_HIP(hipMemcpyAsync(m->tokens, tokens + (size_t)b0 * T, (size_t)bc * T * 4, hipMemcpyHostToDevice, m->stream));
         PGMI_HIP(hipMemcpyAsync(m->aux_i, mask_pos + b0, (size_t)bc * 4, hipMemcpyHostToDevice, m->stream));
         PGMI_HIP(hipMemcpyAsync(m->row_idx, ridx.data(), (size_t)bc * 4, hipMemcpyHostToDevice, m->stream));
         launch_apply_mask(m->tokens, m->aux_i, bc, T, m->stream);
-        rc = run_rows(m, bc, T, bc, m->row_idx);
+        int rc = run_rows(m, bc, T, bc, m->row_idx);
         if (rc) return rc;
         PGMI_HIP(hipMemcpyAsync(out + (size_t)b0 * V, m->lp, (size_t)bc * V * 4, hipMemcpyDeviceToHost, m->stream));
-        PGMI_HIP(hipStreamSynchronize(m->stream));
-    }
-    return check_nonfinite(m);
+        return PGMI_OK;
+    });
+    return rc ? rc : check_nonfinite(m);
 }
 
 int pgmi_assay_create(pgmi_model* m, const int32_t* wt_tokens, int n_tok, const int32_t* positions, int P,
@@ -253,19 +281,17 @@ int pgmi_assay_create(pgmi_model* m, const int32_t* wt_tokens, int n_tok, const 
     PGMI_HIP(hipSetDevice(m->device));
     pgmi_assay* a = new pgmi_assay();
     a->m = m; a->n_tok = n_tok; a->P = P; a->T = T; a->n_mut = n_mut; a->n_sub = n_sub;
-    int rc;
-#define TRY(e) do { rc = (e); if (rc) { pgmi_assay_destroy(a); return rc; } } while (0)
-    TRY(dev_upload(a->allocs, &a->wt, wt_tokens, (size_t)n_tok));
-    TRY(dev_upload(a->allocs, &a->positions, positions, (size_t)P));
-    TRY(dev_upload(a->allocs, &a->win_start, ws.data(), (size_t)P));
-    TRY(dev_upload(a->allocs, &a->mask_rel, mr.data(), (size_t)P));
-    TRY(dev_upload(a->allocs, &a->sub_pos, sub_pos, (size_t)n_sub));
-    TRY(dev_upload(a->allocs, &a->sub_wt, sub_wt, (size_t)n_sub));
-    TRY(dev_upload(a->allocs, &a->sub_mt, sub_mt, (size_t)n_sub));
-    TRY(dev_upload(a->allocs, &a->mut_off, mut_off, (size_t)(n_mut + 1)));
-    TRY(dev_alloc(a->allocs, &a->table, (size_t)n_tok * PGMI_VOCAB));
-    TRY(dev_alloc(a->allocs, &a->scores, (size_t)n_mut));
-#undef TRY
+    int rc = dev_upload(a->allocs, &a->wt, wt_tokens, (size_t)n_tok);
+    if (!rc) rc = dev_upload(a->allocs, &a->positions, positions, (size_t)P);
+    if (!rc) rc = dev_upload(a->allocs, &a->win_start, ws.data(), (size_t)P);
+    if (!rc) rc = dev_upload(a->allocs, &a->mask_rel, mr.data(), (size_t)P);
+    if (!rc) rc = dev_upload(a->allocs, &a->sub_pos, sub_pos, (size_t)n_sub);
+    if (!rc) rc = dev_upload(a->allocs, &a->sub_wt, sub_wt, (size_t)n_sub);
+    if (!rc) rc = dev_upload(a->allocs, &a->sub_mt, sub_mt, (size_t)n_sub);
+    if (!rc) rc = dev_upload(a->allocs, &a->mut_off, mut_off, (size_t)(n_mut + 1));
+    if (!rc) rc = dev_alloc(a->allocs, &a->table, (size_t)n_tok * PGMI_VOCAB);
+    if (!rc) rc = dev_alloc(a->allocs, &a->scores, (size_t)n_mut);
+    if (rc) { pgmi_assay_destroy(a); return rc; }
     m->assays.push_back(a);
     *out = a;
     return PGMI_OK;
@@ -288,7 +314,7 @@ int pgmi_assay_run(pgmi_model* m, pgmi_assay* a, double* scores_host, float* tab
     PGMI_HIP(hipSetDevice(m->device));
     hipStream_t s = m->stream;
     const int T = a->T, V = m->cfg.vocab;
-    const int per = std::max(1, m->max_rows / ((T + 31) / 32 * 32));
+    const int per = rows_per_chunk(m, T);
     launch_fill_f32(a->table, (int64_t)a->n_tok * V, NAN, s);
     for (int p0 = 0; p0 < a->P; p0 += per) {
         const int bc = std::min(per, a->P - p0);
@@ -397,8 +423,7 @@ int pgmi_pppl_run(pgmi_model* m, pgmi_pppl* q, int64_t first, int64_t count, dou
     for (int64_t g0 = 0; g0 < R;) {
         while (rp[j0 + 1] <= g0) ++j0;                       // sequence holding row g0: the longest one left
         const int T = (int)len_of(sid[j0]);
-        const int per = std::max(1, m->max_rows / ((T + 31) / 32 * 32));
-        const int bc = (int)std::min<int64_t>(per, R - g0);
+        const int bc = (int)std::min<int64_t>(rows_per_chunk(m, T), R - g0);
         launch_make_pppl_rows(q->tok8, q->off_dev, d_sid, d_rp, J, g0, bc, T, m->tokens, m->row_idx, m->aux_i, s);
         rc = run_rows(m, bc, T, bc, m->row_idx);
         if (rc) { hipStreamSynchronize(s); cleanup(); return rc; }

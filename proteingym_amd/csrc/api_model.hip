@@ -1,7 +1,5 @@
-// C ABI of libpgmi.so (include/pgmi.h) and the host-side orchestration of the ESM forward.
-//
-// Forward order follows /root/reference/proteingym/baselines/esm/esm/model/esm1.py:116-177 and
-// esm/model/esm2.py:76-130; the per-layer order follows esm/modules.py:120-142.
+// C ABI of libpgmi.so (include/pgmi.h): errors, configuration and token checks, weight split, model create / destroy, options and
+// profiling.  The per-architecture weight walks and forwards live in api_esm / api_tranception / api_progen2 / api_msa.hip.
 #include "model.h"
 
 namespace pgmi {
@@ -89,6 +87,16 @@ int check_tokens(const int32_t* tokens, int B, int T) {
     return PGMI_OK;
 }
 
+// token ids inside [0, V)
+int check_vocab(const int32_t* tokens, int B, int T, int V) {
+    for (int b = 0; b < B; ++b)
+        for (int t = 0; t < T; ++t) {
+            const int tk = tokens[(size_t)b * T + t];
+            if (tk < 0 || tk >= V) { set_error("token id %d out of range at [%d,%d]", tk, b, t); return PGMI_EINVAL; }
+        }
+    return PGMI_OK;
+}
+
 int env_int(const char* name, int dflt) {
     const char* v = getenv(name);
     return v ? atoi(v) : dflt;
@@ -148,6 +156,16 @@ int check_nonfinite(pgmi_model* m) {
     return PGMI_OK;
 }
 
+// Pad keys (t >= T inside the last 32-key tile) are never written by the fused QKV epilogue: they must hold finite data (their
+// softmax weight is exactly 0).  The V^T planes are cleared whenever the batch shape changes (precision fp32 has none).
+int reset_pad_keys(pgmi_model* m, int B, int T) {
+    if (!m->vt16 || (B == m->last_B && T == m->last_T)) return PGMI_OK;
+    PGMI_HIP(hipMemsetAsync(m->vt16, 0, m->vt16_plane * 2 * sizeof(unsigned short), m->stream));
+    m->last_B = B;
+    m->last_T = T;
+    return PGMI_OK;
+}
+
 }  // namespace pgmi
 
 extern "C" {
@@ -197,6 +215,49 @@ int pgmi_model_create(const pgmi_config* cfg, const float* w, int64_t n_weights,
 
 namespace pgmi {
 
+// Workspace of max_rows token rows, shared by every forward of the model.
+static int alloc_workspace(pgmi_model* m) {
+    const pgmi_config& c = m->cfg;
+    const size_t R = m->max_rows, D = c.embed_dim, F = c.ffn_dim, V = c.vocab, Da = m->Da;
+    const size_t Dw = std::max(D, Da);                   // h / h16 hold LN output [.,D] and attention context [.,Da]
+    const bool f32mode = c.precision == PGMI_PREC_FP32;
+    int rc = PGMI_OK;
+    auto alloc = [&](auto** p, size_t n) { if (!rc) rc = dev_alloc(m->allocs, p, n); };
+    alloc(&m->x, R * D);
+    alloc(&m->h, R * Dw);
+    alloc(&m->qkv, R * 3 * Da);
+    alloc(&m->g, R * (f32mode ? std::max(F, D) : D));
+    if (!f32mode) {
+        const size_t planes = c.precision == PGMI_PREC_F16X3 ? 2 : 1;
+        m->h16_plane = R * Dw;
+        m->g16_plane = R * F;
+        alloc(&m->h16, m->h16_plane * planes);
+        alloc(&m->g16, m->g16_plane * planes);
+    }
+    alloc(&m->nonfinite, (size_t)1);
+    if (!f32mode) {                                      // (bf16 mode: its attention runs on the split-fp16 operands as well)
+        m->qk16_plane = R * 2 * Da;
+        m->vt16_plane = R * Da;
+        alloc(&m->qk16, m->qk16_plane * 2);
+        alloc(&m->vt16, m->vt16_plane * 2);
+    }
+    if (c.arch == PGMI_ARCH_MSA) {
+        alloc(&m->xt, R * D);
+        alloc(&m->msa_kv_len, (size_t)2048);
+    }
+    alloc(&m->lp, R * V);
+    alloc(&m->denom, R);
+    alloc(&m->tokens, R);
+    alloc(&m->pos_idx, R);
+    alloc(&m->kv_len, R);
+    alloc(&m->row_idx, R);
+    alloc(&m->aux_i, R);
+    if (rc) return rc;
+    PGMI_HIP(hipMemset(m->nonfinite, 0, 4));
+    if (m->vt16) PGMI_HIP(hipMemset(m->vt16, 0, m->vt16_plane * 2 * sizeof(unsigned short)));
+    return PGMI_OK;
+}
+
 // pgmi_model_create and pgmi_pg2_model_create; rotary_dim is ProGen2's (0 for every other arch)
 int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int device, pgmi_model** out, int rotary_dim) {
     if (!out) { set_error("null out"); return PGMI_EINVAL; }
@@ -214,139 +275,24 @@ int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int 
     pgmi_model* m = new pgmi_model();
     m->cfg = *cfg;
     m->device = device;
-#define TRY(e) do { rc = (e); if (rc) { pgmi_model_destroy(m); return rc; } } while (0)
     if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess) { set_error("hipStreamCreate failed"); delete m; return PGMI_EHIP; }
-    const size_t D = cfg->embed_dim, F = cfg->ffn_dim, V = cfg->vocab;
     m->dh = cfg->embed_dim / cfg->heads;
     m->rot_halves = m->dh > 2 * kHeadDim ? 4 : m->dh > kHeadDim ? 2 : 1;     // 4: ProGen2 head dims above 128 (check_cfg)
     m->Hs = cfg->heads * m->rot_halves;
     m->Da = m->Hs * kHeadDim;
     m->ln_eps = cfg->ln_eps > 0.f ? cfg->ln_eps : 1e-5f;
-    const float* p = w;
-    if (cfg->arch == PGMI_ARCH_TRANCEPTION) {
-        TRY(create_tranception(m, cfg, w, n_weights));
-    } else if (cfg->arch == PGMI_ARCH_MSA) {
-        TRY(create_msa(m, cfg, w, n_weights));
-    } else if (cfg->arch == PGMI_ARCH_PROGEN2) {
-        TRY(create_progen2(m, cfg, w, n_weights, rotary_dim));
-    } else {
-    // embed_tokens == the tied lm_head.weight (esm1.py:101-105).  The host passes the matrix that
-    // load_state_dict leaves in the tied parameter (pretrained.py:97,216), see proteingym_amd/esm.py.
-    TRY(dev_upload(m->allocs, &m->embed_tokens, p, V * D));
-    p += V * D;
-    if (cfg->arch == PGMI_ARCH_ESM1B) {
-        const size_t n = (size_t)(cfg->max_positions + 2) * D;
-        TRY(dev_upload(m->allocs, &m->embed_positions, p, n));
-        p += n;
+    m->max_rows = std::max(cfg->max_rows > 0 ? cfg->max_rows : 98304, 2048);
+    switch (cfg->arch) {
+        case PGMI_ARCH_TRANCEPTION: rc = create_tranception(m, cfg, w, n_weights); break;
+        case PGMI_ARCH_MSA: rc = create_msa(m, cfg, w, n_weights); break;
+        case PGMI_ARCH_PROGEN2: rc = create_progen2(m, cfg, w, n_weights, rotary_dim); break;
+        default: rc = create_esm(m, cfg, w, n_weights);
     }
-    if (cfg->emb_layer_norm_before) {
-        TRY(dev_upload(m->allocs, &m->lnb_w, p, D)); p += D;
-        TRY(dev_upload(m->allocs, &m->lnb_b, p, D)); p += D;
-    }
-    // head layout: every head owns 64 lanes of the attention kernels; dim j of a head sits in slot
-    // j (first half) or 32 + (j - dh/2) (second half) so that rotary pairs (j, j + dh/2) are the
-    // kernels' pairs (i, i + 32).  dh == 64 is the identity layout; smaller heads leave zero slots
-    // (zero weight rows -> q,k,v slots exactly 0 -> scores and context unchanged).
-    const size_t H = cfg->heads, dh = m->dh, Da = m->Da;
-    // head_dim 128: a head is two slot groups; group g in {0,1} holds dims 32 g + i (slots i < 32) and 64 + 32 g + i (slots 32 + i), so
-    // the rotary partners (j, j + 64) are again the kernels' pairs (i, i + 32) inside ONE 64-column wave tile of the QKV epilogue.
-    auto slot = [&](size_t col) -> size_t {
-        const size_t h = col / dh, j = col % dh;
-        if (dh > 64) return (2 * h + ((j >> 5) & 1)) * 64 + ((j >> 6) << 5) + (j & 31);
-        return h * 64 + (j < dh / 2 ? j : 32 + (j - dh / 2));
-    };
-    const float qscale = 1.0f / sqrtf((float)dh);           // multihead_attention.py:261 (exact 1/8 for dh 64)
-    m->layers.resize(cfg->layers);
-    std::vector<float> wq(3 * Da * D, 0.0f), bq(3 * Da, 0.0f), wo_r(D * Da, 0.0f);
-    (void)H;
-    for (int l = 0; l < cfg->layers; ++l) {
-        Layer& L = m->layers[l];
-        TRY(dev_upload(m->allocs, &L.ln1_w, p, D)); p += D;
-        TRY(dev_upload(m->allocs, &L.ln1_b, p, D)); p += D;
-        for (int k = 0; k < 3; ++k) {            // fused [3Da, D] projection, q rows pre-scaled
-            const float sc = (k == 0) ? qscale : 1.0f;
-            for (size_t o = 0; o < D; ++o) {
-                float* dst = &wq[(k * Da + slot(o)) * D];
-                for (size_t i = 0; i < D; ++i) dst[i] = p[o * D + i] * sc;
-            }
-            p += D * D;
-            for (size_t o = 0; o < D; ++o) bq[k * Da + slot(o)] = p[o] * sc;
-            p += D;
-        }
-        const bool f32w = cfg->precision == PGMI_PREC_FP32;
-        if (f32w) TRY(dev_upload(m->allocs, &L.wqkv, wq.data(), wq.size()));
-        else TRY(make_w16(m->allocs, wq.data(), wq.size(), D, cfg->precision, m->stream, &L.wqkv16));
-        TRY(dev_upload(m->allocs, &L.bqkv, bq.data(), bq.size()));
-        for (size_t o = 0; o < D; ++o)           // out-proj [D, Da]: input columns follow the slot layout
-            for (size_t i = 0; i < D; ++i) wo_r[o * Da + slot(i)] = p[o * D + i];
-        if (f32w) TRY(dev_upload(m->allocs, &L.wo, wo_r.data(), wo_r.size()));
-        else TRY(make_w16(m->allocs, wo_r.data(), wo_r.size(), Da, cfg->precision, m->stream, &L.wo16));
-        p += D * D;
-        TRY(dev_upload(m->allocs, &L.bo, p, D)); p += D;
-        TRY(dev_upload(m->allocs, &L.ln2_w, p, D)); p += D;
-        TRY(dev_upload(m->allocs, &L.ln2_b, p, D)); p += D;
-        if (f32w) TRY(dev_upload(m->allocs, &L.w1, p, F * D));
-        else TRY(make_w16(m->allocs, p, F * D, D, cfg->precision, m->stream, &L.w116));
-        p += F * D;
-        TRY(dev_upload(m->allocs, &L.b1, p, F)); p += F;
-        if (f32w) TRY(dev_upload(m->allocs, &L.w2, p, D * F));
-        else TRY(make_w16(m->allocs, p, D * F, F, cfg->precision, m->stream, &L.w216));
-        p += D * F;
-        TRY(dev_upload(m->allocs, &L.b2, p, D)); p += D;
-    }
-    TRY(dev_upload(m->allocs, &m->lna_w, p, D)); p += D;
-    TRY(dev_upload(m->allocs, &m->lna_b, p, D)); p += D;
-    if (cfg->precision == PGMI_PREC_FP32) TRY(dev_upload(m->allocs, &m->hd_w, p, D * D));
-    else TRY(make_w16(m->allocs, p, D * D, D, cfg->precision, m->stream, &m->hd16));
-    p += D * D;
-    TRY(dev_upload(m->allocs, &m->hd_b, p, D)); p += D;
-    TRY(dev_upload(m->allocs, &m->hln_w, p, D)); p += D;
-    TRY(dev_upload(m->allocs, &m->hln_b, p, D)); p += D;
-    TRY(dev_upload(m->allocs, &m->h_bias, p, V)); p += V;
-    if (p - w != n_weights) { set_error("internal: blob walk mismatch"); pgmi_model_destroy(m); return PGMI_EINVAL; }
-    }
-
-    m->max_rows = cfg->max_rows > 0 ? cfg->max_rows : 98304;
-    if (m->max_rows < 2048) m->max_rows = 2048;
-    {
-    const size_t R = m->max_rows, Da = m->Da, Dw = std::max(D, Da);   // h / h16 hold LN output [.,D] and attention context [.,Da]
-    TRY(dev_alloc(m->allocs, &m->x, R * D));
-    TRY(dev_alloc(m->allocs, &m->h, R * Dw));
-    TRY(dev_alloc(m->allocs, &m->qkv, R * 3 * Da));
-    const bool f32mode = cfg->precision == PGMI_PREC_FP32;
-    TRY(dev_alloc(m->allocs, &m->g, R * (f32mode ? std::max(F, D) : D)));
-    if (!f32mode) {
-        const size_t planes = cfg->precision == PGMI_PREC_F16X3 ? 2 : 1;
-        m->h16_plane = R * Dw;
-        m->g16_plane = R * F;
-        TRY(dev_alloc(m->allocs, &m->h16, m->h16_plane * planes));
-        TRY(dev_alloc(m->allocs, &m->g16, m->g16_plane * planes));
-    }
-    TRY(dev_alloc(m->allocs, &m->nonfinite, (size_t)1));
-    PGMI_HIP(hipMemset(m->nonfinite, 0, 4));
-    if (cfg->precision != PGMI_PREC_FP32) {              // (bf16 mode: its attention runs on the split-fp16 operands as well)
-        m->qk16_plane = R * 2 * Da;
-        m->vt16_plane = R * Da;
-        TRY(dev_alloc(m->allocs, &m->qk16, m->qk16_plane * 2));
-        TRY(dev_alloc(m->allocs, &m->vt16, m->vt16_plane * 2));
-        PGMI_HIP(hipMemset(m->vt16, 0, m->vt16_plane * 2 * sizeof(unsigned short)));
-    }
+    if (!rc) rc = alloc_workspace(m);
+    if (rc) { pgmi_model_destroy(m); return rc; }
     m->keep_rows = env_int("PGMI_KEEP_ROWS", 1);
     gemm_options_from_env();                             // the GEMM launchers' test hooks: read here, not per launch
     m->gemm_variant = env_int("PGMI_GEMM_VARIANT", 0);   // tuning only (gemm_f16.hip set_tune); below 1000 = the product configuration
-    if (cfg->arch == PGMI_ARCH_MSA) {
-        TRY(dev_alloc(m->allocs, &m->xt, R * D));
-        TRY(dev_alloc(m->allocs, &m->msa_kv_len, (size_t)2048));
-    }
-    TRY(dev_alloc(m->allocs, &m->lp, R * V));
-    TRY(dev_alloc(m->allocs, &m->denom, R));
-    TRY(dev_alloc(m->allocs, &m->tokens, R));
-    TRY(dev_alloc(m->allocs, &m->pos_idx, R));
-    TRY(dev_alloc(m->allocs, &m->kv_len, R));
-    TRY(dev_alloc(m->allocs, &m->row_idx, R));
-    TRY(dev_alloc(m->allocs, &m->aux_i, R));
-    }
-#undef TRY
     *out = m;
     return PGMI_OK;
 }

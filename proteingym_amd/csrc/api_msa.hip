@@ -9,56 +9,45 @@ namespace pgmi {
 // feed forward: ln, fc1, fc2}; emb_layer_norm_after; lm_head dense, layer_norm, bias.
 int create_msa(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights) {
     const size_t D = cfg->embed_dim, F = cfg->ffn_dim, V = cfg->vocab;
-    const float* p = w;
-    int rc = 0;
-#define TRY(e) do { rc = (e); if (rc) return rc; } while (0)
-    TRY(dev_upload(m->allocs, &m->embed_tokens, p, V * D)); p += V * D;
-    { const size_t n = (size_t)(cfg->max_positions + 2) * D; TRY(dev_upload(m->allocs, &m->embed_positions, p, n)); p += n; }
-    TRY(dev_upload(m->allocs, &m->msa_pe, p, (size_t)1024 * D)); p += (size_t)1024 * D;
-    TRY(dev_upload(m->allocs, &m->lnb_w, p, D)); p += D;
-    TRY(dev_upload(m->allocs, &m->lnb_b, p, D)); p += D;
+    BlobCursor c(m, w, n_weights);
+    c.upload(&m->embed_tokens, V * D);
+    c.upload(&m->embed_positions, (size_t)(cfg->max_positions + 2) * D);
+    c.upload(&m->msa_pe, (size_t)1024 * D);
+    c.upload(&m->lnb_w, D);
+    c.upload(&m->lnb_b, D);
     const float qscale = 1.0f / sqrtf((float)kHeadDim);      // axial_attention.py:48,212 (exact 1/8); the tied
     m->layers.resize(cfg->layers);                           // rows' extra 1/sqrt(R) is applied to the scores
     std::vector<float> wq(3 * D * D), bq(3 * D);
-    auto attn = [&](float** ln_w, float** ln_b, W16* wqkv, float** bqkv, W16* wo, float** bo) -> int {
-        TRY(dev_upload(m->allocs, ln_w, p, D)); p += D;
-        TRY(dev_upload(m->allocs, ln_b, p, D)); p += D;
-        for (int k = 0; k < 3; ++k) {
-            const float sc = (k == 0) ? qscale : 1.0f;
-            for (size_t i = 0; i < D * D; ++i) wq[k * D * D + i] = p[i] * sc;
-            p += D * D;
-            for (size_t i = 0; i < D; ++i) bq[k * D + i] = p[i] * sc;
-            p += D;
-        }
-        TRY(make_w16(m->allocs, wq.data(), wq.size(), D, cfg->precision, m->stream, wqkv));
-        TRY(dev_upload(m->allocs, bqkv, bq.data(), bq.size()));
-        TRY(make_w16(m->allocs, p, D * D, D, cfg->precision, m->stream, wo)); p += D * D;
-        TRY(dev_upload(m->allocs, bo, p, D)); p += D;
-        return PGMI_OK;
+    auto identity = [](size_t col) { return col; };
+    auto attn = [&](float** ln_w, float** ln_b, W16* wqkv, float** bqkv, W16* wo, float** bo) {
+        c.upload(ln_w, D);
+        c.upload(ln_b, D);
+        pack_qkv_slots(c.take(3 * (D * D + D)), D, D, identity, qscale, wq.data(), bq.data());
+        c.w16(wqkv, wq.data(), wq.size(), D);
+        c.upload(bqkv, bq.data(), bq.size());
+        c.w16(wo, D * D, D);
+        c.upload(bo, D);
     };
     for (int l = 0; l < cfg->layers; ++l) {
         Layer& L = m->layers[l];
-        TRY(attn(&L.ln1_w, &L.ln1_b, &L.wqkv16, &L.bqkv, &L.wo16, &L.bo));
-        TRY(attn(&L.c_ln_w, &L.c_ln_b, &L.c_wqkv16, &L.c_bqkv, &L.c_wo16, &L.c_bo));
-        TRY(dev_upload(m->allocs, &L.ln2_w, p, D)); p += D;
-        TRY(dev_upload(m->allocs, &L.ln2_b, p, D)); p += D;
-        TRY(make_w16(m->allocs, p, F * D, D, cfg->precision, m->stream, &L.w116)); p += F * D;
-        TRY(dev_upload(m->allocs, &L.b1, p, F)); p += F;
-        TRY(make_w16(m->allocs, p, D * F, F, cfg->precision, m->stream, &L.w216)); p += D * F;
-        TRY(dev_upload(m->allocs, &L.b2, p, D)); p += D;
+        attn(&L.ln1_w, &L.ln1_b, &L.wqkv16, &L.bqkv, &L.wo16, &L.bo);
+        attn(&L.c_ln_w, &L.c_ln_b, &L.c_wqkv16, &L.c_bqkv, &L.c_wo16, &L.c_bo);
+        c.upload(&L.ln2_w, D);
+        c.upload(&L.ln2_b, D);
+        c.w16(&L.w116, F * D, D);
+        c.upload(&L.b1, F);
+        c.w16(&L.w216, D * F, F);
+        c.upload(&L.b2, D);
     }
-    TRY(dev_upload(m->allocs, &m->lna_w, p, D)); p += D;
-    TRY(dev_upload(m->allocs, &m->lna_b, p, D)); p += D;
-    TRY(make_w16(m->allocs, p, D * D, D, cfg->precision, m->stream, &m->hd16)); p += D * D;
-    TRY(dev_upload(m->allocs, &m->hd_b, p, D)); p += D;
-    TRY(dev_upload(m->allocs, &m->hln_w, p, D)); p += D;
-    TRY(dev_upload(m->allocs, &m->hln_b, p, D)); p += D;
-    TRY(dev_upload(m->allocs, &m->h_bias, p, V)); p += V;
-#undef TRY
-    if (p - w != n_weights) { set_error("internal: blob walk mismatch"); return PGMI_EINVAL; }
-    return PGMI_OK;
+    c.upload(&m->lna_w, D);
+    c.upload(&m->lna_b, D);
+    c.w16(&m->hd16, D * D, D);
+    c.upload(&m->hd_b, D);
+    c.upload(&m->hln_w, D);
+    c.upload(&m->hln_b, D);
+    c.upload(&m->h_bias, V);
+    return c.finish();
 }
-
 
 // MSA Transformer forward on the token grid in m->tokens [R, C] (one alignment); leaves the residual
 // stream (row-major token order) in m->x.  msa_transformer.py:146-205.

@@ -19,31 +19,6 @@ static int pg2_slot(int j, int rd) {
     return (p / 32) * 64 + (p % 32) + 32 * (k & 1);
 }
 
-// cos / sin tables [n][G][64] in the fused epilogue's layout (api_esm.hip ensure_rotary): slot i and 32 + i of group g hold the angle
-// of pair position 32 g + i.  The angle is fp32(t) * inv_freq in fp32 as fixed_pos_embedding computes it (:38-43); an fp64 angle
-// would drift by ~1e-4 rad at t ~ 1000.
-static int pg2_rotary_tables(pgmi_model* m, int n) {
-    const int G = m->rot_halves, rd = m->pg2_rotary, half = rd / 2;
-    std::vector<float> c((size_t)n * G * 64), s((size_t)n * G * 64);
-    std::vector<float> inv(half);
-    for (int i = 0; i < half; ++i) inv[i] = 1.0f / powf(10000.0f, (float)(2 * i) / (float)rd);
-    for (int t = 0; t < n; ++t)
-        for (int g = 0; g < G; ++g)
-            for (int i = 0; i < 32; ++i) {
-                const int p = 32 * g + i;
-                const float f = p < half ? (float)t * inv[p] : 0.0f;
-                const size_t o = ((size_t)t * G + g) * 64;
-                c[o + i] = c[o + 32 + i] = p < half ? cosf(f) : 1.0f;
-                s[o + i] = s[o + 32 + i] = p < half ? sinf(f) : 0.0f;
-            }
-    int rc = dev_upload(m->allocs, &m->rot_cos, c.data(), c.size());
-    if (rc) return rc;
-    rc = dev_upload(m->allocs, &m->rot_sin, s.data(), s.size());
-    if (rc) return rc;
-    m->rot_len = n;
-    return PGMI_OK;
-}
-
 int create_progen2(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights, int rotary_dim) {
     const size_t D = cfg->embed_dim, F = cfg->ffn_dim, V = cfg->vocab, H = cfg->heads;
     const int dh = m->dh, G = m->rot_halves;
@@ -53,10 +28,8 @@ int create_progen2(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_
         return PGMI_EINVAL;
     }
     m->pg2_rotary = rotary_dim;
-    const float* p = w;
-    int rc = 0;
-#define TRY(e) do { rc = (e); if (rc) return rc; } while (0)
-    TRY(dev_upload(m->allocs, &m->embed_tokens, p, V * D)); p += V * D;
+    BlobCursor c(m, w, n_weights);
+    c.upload(&m->embed_tokens, V * D);
     auto slot = [&](size_t col) -> size_t {                        // attention column of model dim `col` (head-major)
         const size_t h = col / dh;
         return h * G * 64 + pg2_slot((int)(col % dh), rotary_dim);
@@ -67,41 +40,39 @@ int create_progen2(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_
     std::vector<float> wq(3 * Da * D, 0.0f), wo_r(D * Da, 0.0f);
     for (int l = 0; l < cfg->layers; ++l) {
         Layer& L = m->layers[l];
-        TRY(dev_upload(m->allocs, &L.ln1_w, p, D)); p += D;
-        TRY(dev_upload(m->allocs, &L.ln1_b, p, D)); p += D;
-        for (int k = 0; k < 3; ++k) {                              // q | k | v blocks of the host-reordered projection
-            const float sc = (k == 0) ? qscale : 1.0f;
-            for (size_t o = 0; o < D; ++o) {
-                float* dst = &wq[(k * Da + slot(o)) * D];
-                for (size_t i = 0; i < D; ++i) dst[i] = p[o * D + i] * sc;
-            }
-            p += D * D;
-        }
-        TRY(make_w16(m->allocs, wq.data(), wq.size(), D, cfg->precision, m->stream, &L.wqkv16));
-        for (size_t o = 0; o < D; ++o)                             // out_proj [D, Da]: input columns follow the slot layout
-            for (size_t i = 0; i < D; ++i) wo_r[o * Da + slot(i)] = p[o * D + i];
-        p += D * D;
-        TRY(make_w16(m->allocs, wo_r.data(), wo_r.size(), Da, cfg->precision, m->stream, &L.wo16));
-        TRY(make_w16(m->allocs, p, F * D, D, cfg->precision, m->stream, &L.w116)); p += F * D;
-        TRY(dev_upload(m->allocs, &L.b1, p, F)); p += F;
-        TRY(make_w16(m->allocs, p, D * F, F, cfg->precision, m->stream, &L.w216)); p += D * F;
-        TRY(dev_upload(m->allocs, &L.b2, p, D)); p += D;
+        c.upload(&L.ln1_w, D);
+        c.upload(&L.ln1_b, D);
+        pack_qkv_slots(c.take(3 * D * D), D, Da, slot, qscale, wq.data());   // q | k | v blocks of the host-reordered projection
+        c.w16(&L.wqkv16, wq.data(), wq.size(), D);
+        pack_out_cols(c.take(D * D), D, Da, slot, wo_r.data());
+        c.w16(&L.wo16, wo_r.data(), wo_r.size(), Da);
+        c.w16(&L.w116, F * D, D);
+        c.upload(&L.b1, F);
+        c.w16(&L.w216, D * F, F);
+        c.upload(&L.b2, D);
     }
-    TRY(dev_upload(m->allocs, &m->lna_w, p, D)); p += D;
-    TRY(dev_upload(m->allocs, &m->lna_b, p, D)); p += D;
-    TRY(dev_upload(m->allocs, &m->pg2_head_w, p, V * D));
-    TRY(dev_upload(m->allocs, &m->pg2_aa_w, p + 5 * D, 25 * D));   // rows 5..29: the amino-acid columns (compute_fitness.py:67-70)
-    p += V * D;
-    TRY(dev_upload(m->allocs, &m->pg2_head_b, p, V));
-    TRY(dev_upload(m->allocs, &m->pg2_aa_b, p + 5, 25));
-    p += V;
-    if (p - w != n_weights) { set_error("internal: blob walk mismatch"); return PGMI_EINVAL; }
+    c.upload(&m->lna_w, D);
+    c.upload(&m->lna_b, D);
+    const float* head_w = c.take(V * D);
+    c.upload(&m->pg2_head_w, head_w, V * D);
+    c.upload(&m->pg2_aa_w, head_w + 5 * D, 25 * D);               // rows 5..29: the amino-acid columns (compute_fitness.py:67-70)
+    const float* head_b = c.take(V);
+    c.upload(&m->pg2_head_b, head_b, V);
+    c.upload(&m->pg2_aa_b, head_b + 5, 25);
     const std::vector<float> zeros(std::max(3 * Da, D), 0.0f), zs(H, 0.0f);
-    TRY(dev_upload(m->allocs, &m->pg2_zero, zeros.data(), zeros.size()));
-    TRY(dev_upload(m->allocs, &m->pg2_slopes, zs.data(), zs.size()));
-    TRY(pg2_rotary_tables(m, cfg->max_positions));
-#undef TRY
-    return PGMI_OK;
+    c.upload(&m->pg2_zero, zeros.data(), zeros.size());
+    c.upload(&m->pg2_slopes, zs.data(), zs.size());
+    int rc = c.finish();
+    if (rc) return rc;
+    // cos / sin tables: slot i and 32 + i of group g hold the angle of pair position 32 g + i.  The angle is fp32(t) * inv_freq in
+    // fp32 as fixed_pos_embedding computes it (:38-43); an fp64 angle would drift by ~1e-4 rad at t ~ 1000.
+    const int half = rotary_dim / 2;
+    std::vector<float> inv(half);
+    for (int i = 0; i < half; ++i) inv[i] = 1.0f / powf(10000.0f, (float)(2 * i) / (float)rotary_dim);
+    return upload_rotary(m, cfg->max_positions, G, [&](int t, int g, int i) {
+        const int p = 32 * g + i;
+        return p < half ? (float)t * inv[p] : 0.0f;                // pass-through pairs: cos 1, sin 0
+    });
 }
 
 // ProGen2 forward on tokens in m->tokens [B,T]; leaves log-probabilities in m->lp: [B*T, 32] (aa_only = false) or the log-softmax over
@@ -111,13 +82,8 @@ static int run_progen2(pgmi_model* m, int B, int T, bool aa_only) {
     const int M = B * T, D = c.embed_dim, F = c.ffn_dim, H = c.heads, Da = m->Da;
     hipStream_t s = m->stream;
     if (T > c.max_positions) { set_error("sequence of %d tokens exceeds the model context n_positions=%d", T, c.max_positions); return PGMI_EINVAL; }
-    int rc = 0;
-    if (B != m->last_B || T != m->last_T) {
-        // pad keys (t >= T inside the last 32-key tile) are never written by the fused QKV epilogue: they must hold finite data
-        PGMI_HIP(hipMemsetAsync(m->vt16, 0, m->vt16_plane * 2 * sizeof(unsigned short), s));
-        m->last_B = B;
-        m->last_T = T;
-    }
+    int rc = reset_pad_keys(m, B, T);
+    if (rc) return rc;
     { ProfScope p(m, PGMI_K_EMBED, 0, (double)M * D * 4);
       launch_gather_rows(m->embed_tokens, m->tokens, M, D, m->x, s); }       // wte[input_ids]: no positional table, no embedding LayerNorm
     const double ln_bytes = 2.0 * M * D * 4;
@@ -176,19 +142,17 @@ int pgmi_pg2_token_logprobs(pgmi_model* m, const int32_t* tokens, int B, int T, 
     int rc = pg2_check(m, T);
     if (rc) return rc;
     const int V = m->cfg.vocab;
-    for (int64_t i = 0; i < (int64_t)B * T; ++i)
-        if (tokens[i] < 0 || tokens[i] >= V) { set_error("token id %d out of range", tokens[i]); return PGMI_EINVAL; }
+    rc = check_vocab(tokens, B, T, V);
+    if (rc) return rc;
     PGMI_HIP(hipSetDevice(m->device));
-    const int per = std::max(1, m->max_rows / ((T + 31) / 32 * 32));
-    for (int b0 = 0; b0 < B; b0 += per) {
-        const int bc = std::min(per, B - b0);
+    rc = for_each_chunk(m, B, T, [&](int b0, int bc) {
         PGMI_HIP(hipMemcpyAsync(m->tokens, tokens + (size_t)b0 * T, (size_t)bc * T * 4, hipMemcpyHostToDevice, m->stream));
-        rc = run_progen2(m, bc, T, false);
+        int rc = run_progen2(m, bc, T, false);
         if (rc) return rc;
         PGMI_HIP(hipMemcpyAsync(out + (size_t)b0 * T * V, m->lp, (size_t)bc * T * V * 4, hipMemcpyDeviceToHost, m->stream));
-        PGMI_HIP(hipStreamSynchronize(m->stream));
-    }
-    return check_nonfinite(m);
+        return PGMI_OK;
+    });
+    return rc ? rc : check_nonfinite(m);
 }
 
 int pgmi_pg2_sequence_loglik(pgmi_model* m, const int32_t* tokens, int B, int L, float* out, int32_t* n_kept) {
@@ -196,12 +160,11 @@ int pgmi_pg2_sequence_loglik(pgmi_model* m, const int32_t* tokens, int B, int L,
     if (L < 2) { set_error("rows of %d tokens: the model needs at least one input and one target token", L); return PGMI_EINVAL; }
     const int T = L - 1;                                            // input = ids[:-1], targets = ids[1:]
     int rc = pg2_check(m, T);
+    if (!rc) rc = check_vocab(tokens, B, L, m->cfg.vocab);
     if (rc) return rc;
     std::vector<int32_t> in((size_t)B * T), col((size_t)B * T, 0), kept(B);
     for (int b = 0; b < B; ++b) {
         const int32_t* row = tokens + (size_t)b * L;
-        for (int t = 0; t < L; ++t)
-            if (row[t] < 0 || row[t] >= m->cfg.vocab) { set_error("token id %d out of range at [%d,%d]", row[t], b, t); return PGMI_EINVAL; }
         int n = T;
         if (row[L - 1] == 3 || row[L - 1] == 4) --n;               // compute_fitness.py:59-62: drop a terminal last target
         for (int t = 0; t < n; ++t) {
@@ -214,19 +177,18 @@ int pgmi_pg2_sequence_loglik(pgmi_model* m, const int32_t* tokens, int B, int L,
     }
     PGMI_HIP(hipSetDevice(m->device));
     hipStream_t s = m->stream;
-    const int per = std::max(1, m->max_rows / ((T + 31) / 32 * 32));
-    for (int b0 = 0; b0 < B; b0 += per) {
-        const int bc = std::min(per, B - b0);
+    rc = for_each_chunk(m, B, T, [&](int b0, int bc) {
         PGMI_HIP(hipMemcpyAsync(m->tokens, in.data() + (size_t)b0 * T, (size_t)bc * T * 4, hipMemcpyHostToDevice, s));
         PGMI_HIP(hipMemcpyAsync(m->aux_i, col.data() + (size_t)b0 * T, (size_t)bc * T * 4, hipMemcpyHostToDevice, s));
         PGMI_HIP(hipMemcpyAsync(m->kv_len, kept.data() + b0, (size_t)bc * 4, hipMemcpyHostToDevice, s));
-        rc = run_progen2(m, bc, T, true);
+        int rc = run_progen2(m, bc, T, true);
         if (rc) return rc;
         { ProfScope p(m, PGMI_K_SCORE, 0, (double)bc * T * 8);
           launch_pg2_seq_loglik(m->lp, m->aux_i, m->kv_len, bc, T, 25, m->denom, s); }
         PGMI_HIP(hipMemcpyAsync(out + b0, m->denom, (size_t)bc * 4, hipMemcpyDeviceToHost, s));
-        PGMI_HIP(hipStreamSynchronize(s));               // the host vectors must outlive the copies
-    }
+        return PGMI_OK;
+    });
+    if (rc) return rc;
     if (n_kept) memcpy(n_kept, kept.data(), (size_t)B * 4);
     return check_nonfinite(m);
 }

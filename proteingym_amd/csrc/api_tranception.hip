@@ -32,61 +32,67 @@ static void conv1d_to_linear(const float* w, size_t in, size_t out, size_t scale
 
 int create_tranception(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights) {
     const size_t D = cfg->embed_dim, F = cfg->ffn_dim, V = cfg->vocab, H = cfg->heads;
-    const float* p = w;
-    int rc = 0;
-#define TRY(e) do { rc = (e); if (rc) return rc; } while (0)
-    TRY(dev_upload(m->allocs, &m->embed_tokens, p, V * D)); p += V * D;
+    BlobCursor c(m, w, n_weights);
+    c.upload(&m->embed_tokens, V * D);
     const float qscale = 1.0f / sqrtf((float)kHeadDim);
     m->layers.resize(cfg->layers);
     std::vector<float> lin, bq(3 * D), conv(3 * 4 * 64 * 8);
     static const int ksz[3] = {3, 5, 7};
     for (int l = 0; l < cfg->layers; ++l) {
         Layer& L = m->layers[l];
-        TRY(dev_upload(m->allocs, &L.ln1_w, p, D)); p += D;
-        TRY(dev_upload(m->allocs, &L.ln1_b, p, D)); p += D;
-        conv1d_to_linear(p, D, 3 * D, D, qscale, lin); p += D * 3 * D;
-        TRY(make_w16(m->allocs, lin.data(), lin.size(), D, cfg->precision, m->stream, &L.wqkv16));
-        for (size_t i = 0; i < 3 * D; ++i) bq[i] = p[i] * (i < D ? qscale : 1.0f);
-        p += 3 * D;
-        TRY(dev_upload(m->allocs, &L.bqkv, bq.data(), bq.size()));
+        c.upload(&L.ln1_w, D);
+        c.upload(&L.ln1_b, D);
+        conv1d_to_linear(c.take(D * 3 * D), D, 3 * D, D, qscale, lin);
+        c.w16(&L.wqkv16, lin.data(), lin.size(), D);
+        const float* b = c.take(3 * D);
+        for (size_t i = 0; i < 3 * D; ++i) bq[i] = b[i] * (i < D ? qscale : 1.0f);
+        c.upload(&L.bqkv, bq.data(), bq.size());
         // conv table: group 0 = identity; groups 1..3 = kernels 3,5,7 right-aligned in 7 taps
         std::fill(conv.begin(), conv.end(), 0.0f);
         for (int which = 0; which < 3; ++which) {
             for (int d = 0; d < 64; ++d) conv[((which * 4 + 0) * 64 + d) * 8 + 6] = 1.0f;
             for (int ki = 0; ki < 3; ++ki) {
                 const int k = ksz[ki];
+                const float* taps = c.take(64 * k);
                 for (int d = 0; d < 64; ++d)
-                    for (int j = 0; j < k; ++j) conv[((which * 4 + ki + 1) * 64 + d) * 8 + (7 - k) + j] = p[d * k + j];
-                p += 64 * k;
+                    for (int j = 0; j < k; ++j) conv[((which * 4 + ki + 1) * 64 + d) * 8 + (7 - k) + j] = taps[d * k + j];
                 // the q projection is pre-scaled by 1/sqrt(dh): scale the q-conv bias the same way
-                for (int d = 0; d < 64; ++d) conv[((which * 4 + ki + 1) * 64 + d) * 8 + 7] = p[d] * (which == 0 ? qscale : 1.0f);
-                p += 64;
+                const float* bias = c.take(64);
+                for (int d = 0; d < 64; ++d) conv[((which * 4 + ki + 1) * 64 + d) * 8 + 7] = bias[d] * (which == 0 ? qscale : 1.0f);
             }
         }
-        TRY(dev_upload(m->allocs, &L.conv, conv.data(), conv.size()));
-        conv1d_to_linear(p, D, D, 0, 1.0f, lin); p += D * D;
-        TRY(make_w16(m->allocs, lin.data(), lin.size(), D, cfg->precision, m->stream, &L.wo16));
-        TRY(dev_upload(m->allocs, &L.bo, p, D)); p += D;
-        TRY(dev_upload(m->allocs, &L.ln2_w, p, D)); p += D;
-        TRY(dev_upload(m->allocs, &L.ln2_b, p, D)); p += D;
-        conv1d_to_linear(p, D, F, 0, 1.0f, lin); p += D * F;
-        TRY(make_w16(m->allocs, lin.data(), lin.size(), D, cfg->precision, m->stream, &L.w116));
-        TRY(dev_upload(m->allocs, &L.b1, p, F)); p += F;
-        conv1d_to_linear(p, F, D, 0, 1.0f, lin); p += F * D;
-        TRY(make_w16(m->allocs, lin.data(), lin.size(), F, cfg->precision, m->stream, &L.w216));
-        TRY(dev_upload(m->allocs, &L.b2, p, D)); p += D;
+        c.upload(&L.conv, conv.data(), conv.size());
+        conv1d_to_linear(c.take(D * D), D, D, 0, 1.0f, lin);
+        c.w16(&L.wo16, lin.data(), lin.size(), D);
+        c.upload(&L.bo, D);
+        c.upload(&L.ln2_w, D);
+        c.upload(&L.ln2_b, D);
+        conv1d_to_linear(c.take(D * F), D, F, 0, 1.0f, lin);
+        c.w16(&L.w116, lin.data(), lin.size(), D);
+        c.upload(&L.b1, F);
+        conv1d_to_linear(c.take(F * D), F, D, 0, 1.0f, lin);
+        c.w16(&L.w216, lin.data(), lin.size(), F);
+        c.upload(&L.b2, D);
     }
-    TRY(dev_upload(m->allocs, &m->lna_w, p, D)); p += D;
-    TRY(dev_upload(m->allocs, &m->lna_b, p, D)); p += D;
-    TRY(dev_upload(m->allocs, &m->tr_lm_head, p, V * D)); p += V * D;
-    if (p - w != n_weights) { set_error("internal: blob walk mismatch"); return PGMI_EINVAL; }
+    c.upload(&m->lna_w, D);
+    c.upload(&m->lna_b, D);
+    c.upload(&m->tr_lm_head, V * D);
     std::vector<float> zb(V, 0.0f), sl;
-    TRY(dev_upload(m->allocs, &m->tr_zero_bias, zb.data(), zb.size()));
+    c.upload(&m->tr_zero_bias, zb.data(), zb.size());
     std::vector<double> quarter = alibi_slopes((int)H / 4);          // grouped: slopes of n/4 heads, tiled 4x
     for (int rep = 0; rep < 4; ++rep)
         for (double v : quarter) sl.push_back((float)v);
-    TRY(dev_upload(m->allocs, &m->tr_slopes, sl.data(), sl.size()));
-#undef TRY
+    c.upload(&m->tr_slopes, sl.data(), sl.size());
+    return c.finish();
+}
+
+// Device copy of the retrieval log-prior [P, V] (none: no retrieval), grown as needed.
+static int upload_prior(pgmi_model* m, const float* log_prior, int P) {
+    if (!log_prior) return PGMI_OK;
+    const size_t n = (size_t)P * m->cfg.vocab;
+    int rc = ensure_cap(m, &m->tr_prior, &m->tr_prior_cap, n);
+    if (rc) return rc;
+    PGMI_HIP(hipMemcpyAsync(m->tr_prior, log_prior, n * 4, hipMemcpyHostToDevice, m->stream));
     return PGMI_OK;
 }
 
@@ -96,12 +102,8 @@ int run_tranception(pgmi_model* m, int B, int T) {
     const int M = B * T, D = c.embed_dim, F = c.ffn_dim, H = c.heads;
     hipStream_t s = m->stream;
     if (T > c.max_positions) { set_error("sequence of %d tokens exceeds the model context n_ctx=%d", T, c.max_positions); return PGMI_EINVAL; }
-    int rc = 0;
-    if (B != m->last_B || T != m->last_T) {
-        PGMI_HIP(hipMemsetAsync(m->vt16, 0, m->vt16_plane * 2 * sizeof(unsigned short), s));
-        m->last_B = B;
-        m->last_T = T;
-    }
+    int rc = reset_pad_keys(m, B, T);
+    if (rc) return rc;
     { ProfScope p(m, PGMI_K_EMBED, 0, (double)M * D * 4);
       launch_gather_rows(m->embed_tokens, m->tokens, M, D, m->x, s); }       // wte[input_ids]; no positional embedding
     const double ln_bytes = 2.0 * M * D * 4;
@@ -262,21 +264,19 @@ extern "C" {
 int pgmi_tr_token_logprobs(pgmi_model* m, const int32_t* tokens, int B, int T, float* out) {
     if (!m || !tokens || !out || B <= 0 || T <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
     if (m->cfg.arch != PGMI_ARCH_TRANCEPTION) { set_error("not a Tranception model"); return PGMI_EINVAL; }
-    for (int64_t i = 0; i < (int64_t)B * T; ++i)
-        if (tokens[i] < 0 || tokens[i] >= m->cfg.vocab) { set_error("token id %d out of range", tokens[i]); return PGMI_EINVAL; }
+    const int V = m->cfg.vocab;
+    int rc = check_vocab(tokens, B, T, V);
+    if (rc) return rc;
     if (T + 31 > m->max_rows) { set_error("T=%d exceeds workspace rows %d", T, m->max_rows); return PGMI_EINVAL; }
     PGMI_HIP(hipSetDevice(m->device));
-    const int per = std::max(1, m->max_rows / ((T + 31) / 32 * 32));
-    const int V = m->cfg.vocab;
-    for (int b0 = 0; b0 < B; b0 += per) {
-        const int bc = std::min(per, B - b0);
+    rc = for_each_chunk(m, B, T, [&](int b0, int bc) {
         PGMI_HIP(hipMemcpyAsync(m->tokens, tokens + (size_t)b0 * T, (size_t)bc * T * 4, hipMemcpyHostToDevice, m->stream));
         int rc = run_tranception(m, bc, T);
         if (rc) return rc;
         PGMI_HIP(hipMemcpyAsync(out + (size_t)b0 * T * V, m->lp, (size_t)bc * T * V * 4, hipMemcpyDeviceToHost, m->stream));
-        PGMI_HIP(hipStreamSynchronize(m->stream));
-    }
-    return check_nonfinite(m);
+        return PGMI_OK;
+    });
+    return rc ? rc : check_nonfinite(m);
 }
 
 int pgmi_tr_sequence_loglik(pgmi_model* m, const int32_t* tokens, const int32_t* lens, int B, int T,
@@ -286,12 +286,10 @@ int pgmi_tr_sequence_loglik(pgmi_model* m, const int32_t* tokens, const int32_t*
     if (m->cfg.arch != PGMI_ARCH_TRANCEPTION) { set_error("not a Tranception model"); return PGMI_EINVAL; }
     if (log_prior && (!prior_a0 || !prior_row0 || !prior_n || !prior_flip || P <= 0)) { set_error("incomplete retrieval arguments"); return PGMI_EINVAL; }
     const int V = m->cfg.vocab;
+    int rc = check_vocab(tokens, B, T, V);
+    if (rc) return rc;
     for (int b = 0; b < B; ++b) {
         if (lens[b] < 1 || lens[b] > T) { set_error("lens[%d]=%d out of range", b, lens[b]); return PGMI_EINVAL; }
-        for (int t = 0; t < T; ++t) {
-            const int tk = tokens[(size_t)b * T + t];
-            if (tk < 0 || tk >= V) { set_error("token id %d out of range at [%d,%d]", tk, b, t); return PGMI_EINVAL; }
-        }
         if (log_prior && prior_n[b] > 0 &&
             (prior_a0[b] < 0 || prior_a0[b] + prior_n[b] > T - 1 || prior_row0[b] < 0 || prior_row0[b] + prior_n[b] > P)) {
             set_error("retrieval slice of sequence %d out of range", b);
@@ -301,19 +299,9 @@ int pgmi_tr_sequence_loglik(pgmi_model* m, const int32_t* tokens, const int32_t*
     if (T + 31 > m->max_rows) { set_error("T=%d exceeds workspace rows %d", T, m->max_rows); return PGMI_EINVAL; }
     PGMI_HIP(hipSetDevice(m->device));
     hipStream_t s = m->stream;
-    if (log_prior) {
-        if (P > m->tr_prior_rows) {
-            float* np_ = nullptr;
-            int rc = dev_alloc(m->allocs, &np_, (size_t)P * V);
-            if (rc) return rc;
-            m->tr_prior = np_;
-            m->tr_prior_rows = P;
-        }
-        PGMI_HIP(hipMemcpyAsync(m->tr_prior, log_prior, (size_t)P * V * 4, hipMemcpyHostToDevice, s));
-    }
-    const int per = std::max(1, m->max_rows / ((T + 31) / 32 * 32));
-    for (int b0 = 0; b0 < B; b0 += per) {
-        const int bc = std::min(per, B - b0);
+    rc = upload_prior(m, log_prior, P);
+    if (rc) return rc;
+    rc = for_each_chunk(m, B, T, [&](int b0, int bc) {
         PGMI_HIP(hipMemcpyAsync(m->tokens, tokens + (size_t)b0 * T, (size_t)bc * T * 4, hipMemcpyHostToDevice, s));
         PGMI_HIP(hipMemcpyAsync(m->kv_len, lens + b0, (size_t)bc * 4, hipMemcpyHostToDevice, s));
         int32_t *da0 = nullptr, *dr0 = nullptr, *dn = nullptr, *dfl = nullptr;
@@ -330,9 +318,9 @@ int pgmi_tr_sequence_loglik(pgmi_model* m, const int32_t* tokens, const int32_t*
           launch_seq_loglik(m->lp, m->tokens, m->kv_len, bc, T, V, log_prior ? m->tr_prior : nullptr, da0, dr0, dn, dfl, alpha,
                             m->denom, s); }
         PGMI_HIP(hipMemcpyAsync(out + b0, m->denom, (size_t)bc * 4, hipMemcpyDeviceToHost, s));
-        PGMI_HIP(hipStreamSynchronize(s));
-    }
-    return check_nonfinite(m);
+        return PGMI_OK;
+    });
+    return rc ? rc : check_nonfinite(m);
 }
 
 int pgmi_tr_sequence_loglik_shared(pgmi_model* m, const int32_t* tokens, const int32_t* ref, int B, int T,
@@ -346,12 +334,10 @@ int pgmi_tr_sequence_loglik_shared(pgmi_model* m, const int32_t* tokens, const i
     const int V = m->cfg.vocab, D = m->cfg.embed_dim;
     const int Tpad = (T + 31) / 32 * 32;
     if (2 * Tpad > m->max_rows) { set_error("T=%d exceeds workspace rows %d", T, m->max_rows); return PGMI_EINVAL; }
+    int rc = check_vocab(tokens, B, T, V);
+    if (rc) return rc;
     for (int b = 0; b < B; ++b) {
         if (ref[b] < 0 || ref[b] >= B || ref[ref[b]] != ref[b]) { set_error("ref[%d]=%d is not a root (a sequence that is its own reference)", b, ref[b]); return PGMI_EINVAL; }
-        for (int t = 0; t < T; ++t) {
-            const int tk = tokens[(size_t)b * T + t];
-            if (tk < 0 || tk >= V) { set_error("token id %d out of range at [%d,%d]", tk, b, t); return PGMI_EINVAL; }
-        }
         if (log_prior && prior_n[b] > 0 &&
             (prior_a0[b] < 0 || prior_a0[b] + prior_n[b] > T - 1 || prior_row0[b] < 0 || prior_row0[b] + prior_n[b] > P)) {
             set_error("retrieval slice of sequence %d out of range", b);
@@ -360,16 +346,8 @@ int pgmi_tr_sequence_loglik_shared(pgmi_model* m, const int32_t* tokens, const i
     }
     PGMI_HIP(hipSetDevice(m->device));
     hipStream_t s = m->stream;
-    if (log_prior) {
-        if (P > m->tr_prior_rows) {
-            float* np_ = nullptr;
-            int rc = dev_alloc(m->allocs, &np_, (size_t)P * V);
-            if (rc) return rc;
-            m->tr_prior = np_;
-            m->tr_prior_rows = P;
-        }
-        PGMI_HIP(hipMemcpyAsync(m->tr_prior, log_prior, (size_t)P * V * 4, hipMemcpyHostToDevice, s));
-    }
+    rc = upload_prior(m, log_prior, P);
+    if (rc) return rc;
     // first own token of every sequence: its first difference from its root (a copy of the root: the last token)
     std::vector<int> a0(B, 0);
     std::vector<std::vector<int>> members(B);
@@ -424,7 +402,7 @@ int pgmi_tr_sequence_loglik_shared(pgmi_model* m, const int32_t* tokens, const i
             ck.add(b, tokens + (size_t)b * T, T, a0[b], rl, D);
         }
     }
-    int rc = flush();
+    rc = flush();
     if (rc) return rc;
     if (rows_forwarded) *rows_forwarded = forwarded;
     return check_nonfinite(m);

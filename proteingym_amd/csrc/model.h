@@ -1,10 +1,12 @@
 // Internal header of the C ABI's translation units (api_*.hip): the device-resident model / assay / library state behind the opaque
 // handles of include/pgmi.h and the host-side helpers they share.  Nothing here is part of the ABI.
-//   api_model.hip        errors, configuration check, weight upload, model create / destroy, options, profiling
-//   api_esm.hip          ESM-1b / ESM-1v / ESM2 forward (run_encoder, run_head), masked-marginals assays, pseudo-ppl libraries
-//   api_tranception.hip  Tranception forward, dense and prefix-shared; token log-probs and sequence log-likelihoods
-//   api_progen2.hip      ProGen2 forward (parallel residual, GPT-J rotary); token log-probs and sequence log-likelihoods
-//   api_msa.hip          MSA Transformer forward (tied row attention, column attention)
+//   api_model.hip        errors, configuration and token checks, weight split, model create (validation, per-arch dispatch,
+//                        workspace) / destroy, options, profiling
+//   api_esm.hip          ESM-1b / ESM-1v / ESM2 weights (create_esm) and forward (run_encoder, run_head), masked-marginals assays,
+//                        pseudo-ppl libraries
+//   api_tranception.hip  Tranception weights and forward, dense and prefix-shared; token log-probs and sequence log-likelihoods
+//   api_progen2.hip      ProGen2 weights and forward (parallel residual, GPT-J rotary); token log-probs and sequence log-likelihoods
+//   api_msa.hip          MSA Transformer weights and forward (tied row attention, column attention)
 //   api_host.hip         host-only entries: mutant parser, table -> scores, optimal window
 //   api_ops.hip          single-op and timing entries for the numerics tests and the A/B scripts
 #pragma once
@@ -68,7 +70,7 @@ struct pgmi_model {
     W16 hd16;
     float *tr_lm_head = nullptr, *tr_zero_bias = nullptr, *tr_slopes = nullptr;   // Tranception head / ALiBi slopes
     float* tr_prior = nullptr;                          // device copy of the retrieval log-prior [P,V]
-    int tr_prior_rows = 0;
+    size_t tr_prior_cap = 0;
     int32_t* tr_meta = nullptr;                         // prefix-shared scoring: the chunk's index arrays (TrChunk)
     size_t tr_meta_cap = 0;
     // ProGen2: rotary_dim, the biased 32-column head and its amino-acid rows 5..29, zero bias of the bias-free projections, zero slopes
@@ -198,14 +200,17 @@ int ensure_cap(pgmi_model* m, T** p, size_t* cap, size_t need) {
 int prof_drain(pgmi_model* m);
 int check_cfg(const pgmi_config* c);
 int check_tokens(const int32_t* tokens, int B, int T);
+int check_vocab(const int32_t* tokens, int B, int T, int V);
 int env_int(const char* name, int dflt);
 int make_w16(std::vector<void*>& pool, const float* host, size_t n, size_t K, int precision, hipStream_t s, W16* out);
 int linear(pgmi_model* m, const float* in32, const unsigned short* in16, size_t in_plane, const float* W32,
            const W16& w16, const float* bias, const float* residual, float* out32, unsigned short* out16,
            size_t out_plane, int M, int N, int K, int epi);
 int check_nonfinite(pgmi_model* m);
+int reset_pad_keys(pgmi_model* m, int B, int T);
 int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int device, pgmi_model** out, int rotary_dim);
 // api_esm.hip
+int create_esm(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights);
 int ensure_rotary(pgmi_model* m, int T);
 int run_encoder(pgmi_model* m, int B, int T, const int32_t* keep = nullptr, int n_keep = 0, bool* compacted = nullptr);
 int run_head(pgmi_model* m, int R, const int32_t* row_idx);
@@ -218,5 +223,90 @@ int create_progen2(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_
 // api_msa.hip
 int create_msa(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights);
 int run_msa(pgmi_model* m, int R, int C, int keep_col = -1, bool* compacted = nullptr);
+
+// Walks a weight blob in the order include/pgmi.h documents.  upload / w16 / linear put the next n floats on the device; their forms
+// with a host pointer upload a host re-layout instead and do not advance.  take hands the next n floats to a host re-layout.  The
+// first error sticks: every later call does nothing, and finish() returns it -- or a mismatch if the walk did not end exactly at
+// the end of the blob.
+struct BlobCursor {
+    pgmi_model* m;
+    const float *p, *end;
+    int rc = PGMI_OK;
+    BlobCursor(pgmi_model* m_, const float* w, int64_t n_weights) : m(m_), p(w), end(w + n_weights) {}
+    const float* take(size_t n) { p += n; return p - n; }
+    void upload(float** dst, const float* host, size_t n) { if (!rc) rc = dev_upload(m->allocs, dst, host, n); }
+    void upload(float** dst, size_t n) { upload(dst, take(n), n); }
+    void w16(W16* dst, const float* host, size_t n, size_t K) { if (!rc) rc = make_w16(m->allocs, host, n, K, m->cfg.precision, m->stream, dst); }
+    void w16(W16* dst, size_t n, size_t K) { w16(dst, take(n), n, K); }
+    // a Linear weight [n / K, K]: fp32 in precision fp32, 16-bit planes otherwise
+    void linear(float** w32, W16* w16_, const float* host, size_t n, size_t K) {
+        if (m->cfg.precision == PGMI_PREC_FP32) upload(w32, host, n); else w16(w16_, host, n, K);
+    }
+    void linear(float** w32, W16* w16_, size_t n, size_t K) { linear(w32, w16_, take(n), n, K); }
+    int finish() {
+        if (!rc && p != end) { set_error("internal: blob walk mismatch"); rc = PGMI_EINVAL; }
+        return rc;
+    }
+};
+
+// Fused [3 Da, D] QKV projection from the blob's q | k | v blocks (each a [D, D] weight, followed by a [D] bias when bq is
+// given): row o of block k goes to row k Da + slot(o), the q rows pre-scaled by qscale.  Rows no model dim maps to keep their
+// zeros (zero q / k / v lanes change no score and no context value).
+template <typename Slot>
+void pack_qkv_slots(const float* src, size_t D, size_t Da, Slot slot, float qscale, float* wq, float* bq = nullptr) {
+    for (size_t k = 0; k < 3; ++k) {
+        const float sc = (k == 0) ? qscale : 1.0f;
+        for (size_t o = 0; o < D; ++o) {
+            float* dst = &wq[(k * Da + slot(o)) * D];
+            for (size_t i = 0; i < D; ++i) dst[i] = src[o * D + i] * sc;
+        }
+        src += D * D;
+        if (!bq) continue;
+        for (size_t o = 0; o < D; ++o) bq[k * Da + slot(o)] = src[o] * sc;
+        src += D;
+    }
+}
+
+// Out-projection [D, D] -> [D, Da]: its input columns follow the same slot layout.
+template <typename Slot>
+void pack_out_cols(const float* src, size_t D, size_t Da, Slot slot, float* wo) {
+    for (size_t o = 0; o < D; ++o)
+        for (size_t i = 0; i < D; ++i) wo[o * Da + slot(i)] = src[o * D + i];
+}
+
+// Rotary cos / sin tables [n][groups][64] in the fused QKV epilogue's layout: slots i and 32 + i of slot group g rotate by
+// angle(t, g, i), an fp32 angle.  Angle 0 passes the pair through (cosf(0) = 1 and sinf(0) = 0 exactly).
+template <typename Angle>
+int upload_rotary(pgmi_model* m, int n, int groups, Angle angle) {
+    std::vector<float> c((size_t)n * groups * 64), s((size_t)n * groups * 64);
+    for (int t = 0; t < n; ++t)
+        for (int g = 0; g < groups; ++g)
+            for (int i = 0; i < 32; ++i) {
+                const float f = angle(t, g, i);
+                const size_t o = ((size_t)t * groups + g) * 64;
+                c[o + i] = c[o + 32 + i] = cosf(f);
+                s[o + i] = s[o + 32 + i] = sinf(f);
+            }
+    int rc = dev_upload(m->allocs, &m->rot_cos, c.data(), c.size());
+    if (!rc) rc = dev_upload(m->allocs, &m->rot_sin, s.data(), s.size());
+    if (!rc) m->rot_len = n;
+    return rc;
+}
+
+// Sequences of T tokens per workspace chunk: B * roundup(T, 32) <= max_rows, at least one.
+inline int rows_per_chunk(const pgmi_model* m, int T) { return std::max(1, m->max_rows / ((T + 31) / 32 * 32)); }
+
+// Drives a fixed-T batch through the workspace: fn(b0, bc) copies chunk [b0, b0 + bc) in, runs it and copies its results out
+// (asynchronously); the stream is synchronized after every chunk, so host buffers of the chunk outlive their copies.
+template <typename Fn>
+int for_each_chunk(pgmi_model* m, int B, int T, Fn fn) {
+    const int per = rows_per_chunk(m, T);
+    for (int b0 = 0; b0 < B; b0 += per) {
+        int rc = fn(b0, std::min(per, B - b0));
+        if (rc) return rc;
+        PGMI_HIP(hipStreamSynchronize(m->stream));
+    }
+    return PGMI_OK;
+}
 
 }  // namespace pgmi
