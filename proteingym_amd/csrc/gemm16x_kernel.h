@@ -73,6 +73,23 @@ __device__ __forceinline__ f32x16 mfma16(u32x4 a, u32x4 b, f32x16 c) {
     }
 }
 
+// the GEMM's MFMA: A = 16 weight rows, B = 16 activation rows, the whole 32-deep K tile (f16x3) or one k32 half of it (BF)
+template <bool BF>
+__device__ __forceinline__ f32x4 mfma16x16(u32x4 a, u32x4 b, f32x4 c) {
+    if constexpr (BF) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(b8, a), __builtin_bit_cast(b8, b), c, 0, 0, 0);
+    } else {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, a), __builtin_bit_cast(h8, b), c, 0, 0, 0);
+    }
+}
+
+// a store into an epilogue patch, explicitly to LDS: where the same value goes either to the patch or straight to global memory,
+// the compiler otherwise merges the two stores into one flat store through a per-lane 64-bit pointer (kept live across the epilogue)
+template <typename T>
+__device__ __forceinline__ void lds_put(unsigned char* p, T v) {
+    *(__attribute__((address_space(3))) T*)(p) = v;
+}
+
 __device__ __forceinline__ unsigned short f32_to_bf16_rne(float f) {
     unsigned int u = __builtin_bit_cast(unsigned int, f);
     u += 0x7fffu + ((u >> 16) & 1u);
@@ -82,7 +99,12 @@ __device__ __forceinline__ unsigned short f32_to_bf16_rne(float f) {
 // =================================================================================================
 // Persistent ping-pong kernel (f16x3, 256 x 256 x 32 tile, 8 waves = 2(M) x 4(N), wave tile 128 x 64).
 // One workgroup per CU walks a list of work items; per item the K loop is a ping-pong schedule: the two waves of a SIMD
-// run one phase apart, one issues its 24 MFMAs while the other reads fragments / issues the DMA of the next K tile.
+// run one phase apart, one issues its 48 MFMAs while the other reads fragments / issues the DMA of the next K tile.
+// MFMA shape v_mfma_f32_16x16x32_{f16,bf16}: one MFMA takes a whole 32-deep K tile (f16x3: hi chunks kq, lo chunks 4 + kq of the
+// row's line for lane kq = lane >> 4, row lane & 15), so a K tile's two compute phases split the wave tile by M HALF: each is
+// 4 M16 x 4 N16 tiles x 3 split products = 48 MFMAs of 16 clocks, the 768 clocks of the 24 32x32x16 MFMAs it replaces, at a
+// clock the power-capped chip holds ~15 % higher (tools/mfma_phase.hip).  Accumulator of M16 tile i, N16
+// tile j: lane l holds activation row 16 i + (l & 15), weight rows (output columns) 16 j + 4 (l >> 4) + e, e = 0..3.
 // What the persistent form adds:
 //   * no workgroup launch/retire gap between tiles; the first K tile of item i+1 is in flight (DMA into buffer 0) while
 //     the epilogue of item i runs -- the epilogues' LDS patches start at buffer 1, which is free until the next K loop;
@@ -144,8 +166,8 @@ __device__ __forceinline__ void x_tile_coords(int wgid, int tiles_m, int tiles_n
 // OUT 0: fp32 [M,N] (+ residual); 1: split fp16 planes, K-interleaved (the next GEMM's operand); 2: attention operands (QkvOut).
 // XM: the batched / strided form (XMap); false = dense operands, one batch: xm is ignored (and costs nothing).
 // BF (round 6, the un-gated bf16 throughput mode): operands are ONE bf16 plane, row-major [rows][K].  A K tile is then 64 deep -- the same 128
-// bytes per row and tile, so staging, LDS image and fragment reads are unchanged -- and a compute phase issues 16 MFMAs (k16 steps ks and
-// 2 + ks of the tile: the chunks the f16x3 form reads as the hi and the lo half of one step) instead of the 24 of the three split products.
+// bytes per row and tile, so staging, LDS image and fragment reads are unchanged -- and a compute phase issues 32 MFMAs (the tile's two
+// k32 halves: the chunks the f16x3 form reads as the hi and the lo plane) instead of the 48 of the three split products.
 template <int EPI, int OUT, bool XM = false, bool BF = false>
 __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
     const unsigned short* __restrict__ A, const unsigned short* __restrict__ W, const float* __restrict__ bias,
@@ -154,12 +176,12 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
     static_assert(!(XM && BF), "the batched / strided form is f16x3 only");
     constexpr unsigned int EB = BF ? 2u : 4u;                     // operand bytes per k element: one bf16, or the hi and the lo half
     const XMap xm = XM ? xm_arg : XMap{};                         // dense instantiations: every xm test below folds away
-    constexpr int WN = 4, TMX = 4, TN = 2, LD = 4;               // TMX: 32-row MFMA tiles per wave of a full item (a half item: 2)
+    constexpr int WN = 4, TMX = 8, TN = 4, LD = 4;               // TMX: M16 tiles per wave of a full item (a half item: 4); TN: N16 tiles
     extern __shared__ __attribute__((aligned(16))) u32x4 lds[];  // [2][X_STAGE] + patches
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);    // provably wave-uniform: scalar branches, SGPR LDS bases
     const int wm = wave / WN, wn = wave % WN;
-    const int r = lane & 31, kh = lane >> 5;
+    const int r = lane & 15, kq = lane >> 4;                      // MFMA row / K chunk (fragments), activation row / column quad (accumulators)
     const bool late = wave >= 4;                                  // the second wave of every SIMD
     // epilogue patches: from buffer 1 on (free between the last phase barrier of an item and the first memory phase of the
     // next one, which every wave enters through a barrier after its own epilogue) -- buffer 0 takes the next item's first K tile
@@ -242,24 +264,27 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
         __builtin_amdgcn_sched_barrier(0);
     };
 
-    f32x16 acc[TN][TMX];
-    u32x4 af[2][TMX], wf[2][TN], whs[TN];
-    const int fsw = (r >> 1) & 7;                                 // fragment rows are (multiple of 32) + r: the row swizzle is per lane
-    auto read_frags = [&](auto tmc, const u32x4* Ab, const u32x4* Wb, int ks) {
-        constexpr int TM = decltype(tmc)::value;
+    f32x4 acc[TN][TMX];
+    u32x4 af[2][TMX / 2], wf[2][TN], whs[TN];
+    const int fsw = (r >> 1) & 7;                                 // fragment rows are (multiple of 16) + r: the row swizzle is per lane
+    // fragments of M half h (TM / 2 M16 tiles), and in the first half the W fragments of the whole K tile: chunk kq (hi / first k32)
+    // and 4 + kq (lo / second k32); 8 consecutive lanes read 8 consecutive rows of one chunk column -- conflict-free
+    auto read_frags = [&](auto tmc, auto hc, const u32x4* Ab, const u32x4* Wb) {
+        constexpr int TM = decltype(tmc)::value, TH = TM / 2, H = decltype(hc)::value;
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
-            const int c = (p * 4 + ks * 2 + kh) ^ fsw;            // chunk p*4 + (2 ks + kh) of the row's line, swizzled
+            const int c = (p * 4 + kq) ^ fsw;
 #pragma unroll
-            for (int i = 0; i < TM; ++i) af[p][i] = Ab[((wm * TM + i) * 32 + r) * XCPR + c];
+            for (int i = 0; i < TH; ++i) af[p][i] = Ab[((wm * TM + H * TH + i) * 16 + r) * XCPR + c];
+            if constexpr (H == 0)
 #pragma unroll
-            for (int j = 0; j < TN; ++j) wf[p][j] = Wb[((wn * TN + j) * 32 + r) * XCPR + c];
+                for (int j = 0; j < TN; ++j) wf[p][j] = Wb[((wn * TN + j) * 16 + r) * XCPR + c];
         }
     };
-    // w_hi 2^-11 (exact: weights are pre-scaled to ~2^13), the third operand of the split product.  Computed at the head of
-    // the wave's own COMPUTE phase, interleaved with the first MFMAs (which do not need it): in the memory phase the partner
-    // wave holds priority and these eight VALU ops sat on the critical path to the phase barrier (measured: a memory phase
-    // with nothing but them still took 600-700 clocks).
+    // w_hi 2^-11 (exact: weights are pre-scaled to ~2^13), the third operand of the split product.  Computed once per K tile at the
+    // head of the wave's first COMPUTE phase, one per MFMA gap (a 16x16x32 leaves room for about one filler): in the memory phase the
+    // partner wave holds priority and these VALU ops sat on the critical path to the phase barrier (measured with the 32x32x16 form:
+    // a memory phase with nothing but them still took 600-700 clocks).
     auto scale_whi = [&]() {
         typedef _Float16 h2 __attribute__((ext_vector_type(2)));
         const h2 sc = {(_Float16)(1.0f / kLoScale), (_Float16)(1.0f / kLoScale)};
@@ -272,45 +297,49 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
                 whs[j][e] = __builtin_bit_cast(unsigned int, t);
             }
     };
-    auto mfmas = [&](auto tmc) {
-        constexpr int TM = decltype(tmc)::value;
-        if constexpr (BF) {                                       // two k16 steps of plain bf16 products
+    auto mfmas = [&](auto tmc, auto hc) {
+        constexpr int TM = decltype(tmc)::value, TH = TM / 2, H = decltype(hc)::value;
+        if constexpr (BF) {                                       // the two k32 halves of the 64-deep tile, plain bf16 products
 #pragma unroll
             for (int p = 0; p < 2; ++p)
 #pragma unroll
                 for (int j = 0; j < TN; ++j)
 #pragma unroll
-                    for (int i = 0; i < TM; ++i) acc[j][i] = mfma16<true>(wf[p][j], af[p][i], acc[j][i]);
+                    for (int i = 0; i < TH; ++i) acc[j][H * TH + i] = mfma16x16<true>(wf[p][j], af[p][i], acc[j][H * TH + i]);
             return;
         }
-        scale_whi();
+        if constexpr (H == 0) scale_whi();
 #pragma unroll
         for (int j = 0; j < TN; ++j)
 #pragma unroll
-            for (int i = 0; i < TM; ++i) acc[j][i] = mfma16<false>(wf[1][j], af[0][i], acc[j][i]);    // w_lo a_hi
+            for (int i = 0; i < TH; ++i) acc[j][H * TH + i] = mfma16x16<false>(wf[1][j], af[0][i], acc[j][H * TH + i]);    // w_lo a_hi
 #pragma unroll
         for (int j = 0; j < TN; ++j)
 #pragma unroll
-            for (int i = 0; i < TM; ++i) acc[j][i] = mfma16<false>(whs[j], af[1][i], acc[j][i]);      // (w_hi 2^-11)(a_lo 2^11)
+            for (int i = 0; i < TH; ++i) acc[j][H * TH + i] = mfma16x16<false>(whs[j], af[1][i], acc[j][H * TH + i]);      // (w_hi 2^-11)(a_lo 2^11)
 #pragma unroll
         for (int j = 0; j < TN; ++j)
 #pragma unroll
-            for (int i = 0; i < TM; ++i) acc[j][i] = mfma16<false>(wf[0][j], af[0][i], acc[j][i]);    // w_hi a_hi
-        // one MFMA, one VALU: the eight scalings ride in the shadow of the first eight MFMAs
+            for (int i = 0; i < TH; ++i) acc[j][H * TH + i] = mfma16x16<false>(wf[0][j], af[0][i], acc[j][H * TH + i]);    // w_hi a_hi
+        if constexpr (H == 0) {
+            // one MFMA, one VALU: the sixteen scalings ride in the shadow of the first sixteen MFMAs
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);
+            for (int k = 0; k < 4 * TN; ++k) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);
+            }
+            __builtin_amdgcn_sched_group_barrier(0x008, 3 * TN * TH - 4 * TN, 0);
         }
-        __builtin_amdgcn_sched_group_barrier(0x008, 3 * TN * TM - 8, 0);
     };
+    using H0 = std::integral_constant<int, 0>;
+    using H1 = std::integral_constant<int, 1>;
 
     // ---- this workgroup's item list: b, b + G, ... (items >= n_main are 128-row items) ----
     int item = blockIdx.x;
     if (item >= n_items) return;
     decode(item);
     issue_tile(0, 0);
-    // one item, start to finish; TM (compile time) = 32-row MFMA tiles per wave: 4, or 2 for a half item.  Returns "more items".
+    // one item, start to finish; TM (compile time) = M16 tiles per wave: 8, or 4 for a half item.  Returns "more items".
     auto run_item = [&](auto tmc) -> bool {
         constexpr int TM = decltype(tmc)::value;
         // ---- prologue: the item's first K tile has been in flight into buffer 0 since before the previous epilogue ----
@@ -320,30 +349,30 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int v = 0; v < 16; ++v) acc[j][i][v] = 0.0f;
+                for (int v = 0; v < 4; ++v) acc[j][i][v] = 0.0f;
         int cur = 0;
         if (late) phase();
         for (int kt = 0; kt < nk; ++kt) {
             const u32x4* Ab = lds + cur * X_STAGE;
             const u32x4* Wb = Ab + X_OP_CH;
             // -- memory phase 1: DMA of tile kt+1 into the other buffer (last read two phases ago by the other wave group), then
-            //    the fragments of the first k16 step.  The DMA goes first: with the fragment reads ahead of it the memory phase
-            //    outlasts the partner's 24 MFMAs (tools/mfma_phase.hip: 829 -> 797 clocks per phase on the bare loop) --
+            //    the fragments of M half 0 and the W fragments.  The DMA goes first: with the fragment reads ahead of it the memory
+            //    phase outlasts the partner's MFMAs (tools/mfma_phase.hip: 829 -> 797 clocks per phase on the bare 32x32x16 loop) --
             __builtin_amdgcn_s_setprio(0);
             if (kt + 1 < nk) issue_tile(kt + 1, cur ^ 1);
-            read_frags(tmc, Ab, Wb, 0);
+            read_frags(tmc, H0{}, Ab, Wb);
             phase();
             // -- compute phase 1 --
             __builtin_amdgcn_s_setprio(1);
-            mfmas(tmc);
+            mfmas(tmc, H0{});
             phase();
-            // -- memory phase 2: fragments of the second k16 step --
+            // -- memory phase 2: fragments of M half 1 --
             __builtin_amdgcn_s_setprio(0);
-            read_frags(tmc, Ab, Wb, 1);
+            read_frags(tmc, H1{}, Ab, Wb);
             if (late) phase_vm(); else phase();                 // late waves close tile kt here: their DMA share must have landed
             // -- compute phase 2 --
             __builtin_amdgcn_s_setprio(1);
-            mfmas(tmc);
+            mfmas(tmc, H1{});
             if (!late) phase_vm(); else phase();                // early waves close tile kt here
             cur ^= 1;
         }
@@ -370,42 +399,46 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
             const bool staged_q = which < 2;
             // the wave's bias values, once per item: a load inside the block loop is followed by a wait for EVERYTHING in
             // flight (vmcnt counts the stores of the previous block as well) -- one memory round trip per 4 values
-            f32x4 bq0[4], bq1[4];
+            // (the lane's dims: 16 g + 4 kq + e of N16 tile g and 32 + 16 g + 4 kq + e of tile g + 2 -- a rotary pair -- for g = 0, 1)
+            f32x4 bq0[2], bq1[2];
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                bq0[g] = *reinterpret_cast<const f32x4*>(bias + nb + 8 * g + 4 * kh);
-                bq1[g] = *reinterpret_cast<const f32x4*>(bias + nb + 32 + 8 * g + 4 * kh);
+            for (int g = 0; g < 2; ++g) {
+                bq0[g] = *reinterpret_cast<const f32x4*>(bias + nb + 16 * g + 4 * kq);
+                bq1[g] = *reinterpret_cast<const f32x4*>(bias + nb + 32 + 16 * g + 4 * kq);
             }
 #pragma unroll
-            for (int g = 0; g < 4; ++g) asm volatile("" :: "v"(bq0[g]), "v"(bq1[g]));      // waited for HERE, not inside the block loop
+            for (int g = 0; g < 2; ++g) asm volatile("" :: "v"(bq0[g]), "v"(bq1[g]));      // waited for HERE, not inside the block loop
+            // 32-row blocks of two M16 tiles: the staged q | k rows leave the patch as in a 32x32 layout
 #pragma unroll
-            for (int i = 0; i < TM; ++i) {
-                const int m = em0 + (wm * TM + i) * 32 + r;
+            for (int ib = 0; ib < TM / 2; ++ib) {
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const int i = 2 * ib + s, prow = 16 * s + r;   // M16 tile, row in the block's patch
+                const int m = em0 + (wm * TM + i) * 16 + r;
                 const bool row_ok = m < M;
-                if (!staged_q && !row_ok) continue;
+                if (!row_ok) continue;
                 const int bb = m / qo.T, t = m - bb * qo.T;
                 // ESM2: the row's rotary table entries for all four column groups, loaded TOGETHER before the group loop (loads inside it
                 // were waited for one group at a time, and the wait -- vmcnt counts stores too -- included the V^T stores just issued)
                 // (a table row holds every angle twice: slots i and 32 + i are the pair (j, j + dh / 2) of one frequency -- api_esm.hip ensure_rotary)
-                f32x4 rc[4], rs[4];
+                f32x4 rc[2], rs[2];
                 if (which < 2 && qo.rotary) {
                     const int tr = (min(t, qo.T - 1) * qo.rot_halves + (hh % qo.rot_halves)) * 64;
 #pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        rc[g] = *reinterpret_cast<const f32x4*>(qo.cos_t + tr + 8 * g + 4 * kh);
-                        rs[g] = *reinterpret_cast<const f32x4*>(qo.sin_t + tr + 8 * g + 4 * kh);
+                    for (int g = 0; g < 2; ++g) {
+                        rc[g] = *reinterpret_cast<const f32x4*>(qo.cos_t + tr + 16 * g + 4 * kq);
+                        rs[g] = *reinterpret_cast<const f32x4*>(qo.sin_t + tr + 16 * g + 4 * kq);
                     }
                 }
-                if (row_ok)
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int d0 = 8 * g + 4 * kh;             // dims d0..d0+3 (x0) and d0+32.. (x1) of the head
+                for (int g = 0; g < 2; ++g) {
+                    const int d0 = 16 * g + 4 * kq;            // dims d0..d0+3 (x0) and d0+32.. (x1) of the head
                     const f32x4 b0 = bq0[g], b1 = bq1[g];
                     float x0[4], x1[4];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        x0[e] = fmaf(acc[0][i][4 * g + e], out_scale, b0[e]);      // explicit fma in every epilogue: left to -ffp-contract, the full- and
-                        x1[e] = fmaf(acc[1][i][4 * g + e], out_scale, b1[e]);      // half-height instantiations could round differently
+                        x0[e] = fmaf(acc[g][i][e], out_scale, b0[e]);          // explicit fma in every epilogue: left to -ffp-contract, the full- and
+                        x1[e] = fmaf(acc[g + 2][i][e], out_scale, b1[e]);      // half-height instantiations could round differently
                     }
                     if (which == 0) {                          // attention's softmax is base 2: q carries log2(e) (common.h)
 #pragma unroll
@@ -429,11 +462,11 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
                             split_act(x0[e], a, b2); hi0[e] = a; lo0[e] = b2;
                             split_act(x1[e], a, b2); hi1[e] = a; lo1[e] = b2;
                         }
-                        unsigned char* cell = patch_q + r * SPQ + d0 * 2;
-                        *reinterpret_cast<h4*>(cell) = hi0;
-                        *reinterpret_cast<h4*>(cell + 32 * SPQ) = lo0;
-                        *reinterpret_cast<h4*>(cell + 64) = hi1;
-                        *reinterpret_cast<h4*>(cell + 32 * SPQ + 64) = lo1;
+                        unsigned char* cell = patch_q + prow * SPQ + d0 * 2;
+                        lds_put(cell, hi0);
+                        lds_put(cell + 32 * SPQ, lo0);
+                        lds_put(cell + 64, hi1);
+                        lds_put(cell + 32 * SPQ + 64, lo1);
                     } else {
                         const int tk = t & 31;
                         const int pos = (t & ~31) + ((tk & 0x13) | ((tk & 4) << 1) | ((tk & 8) >> 1));   // swap key bits 2,3
@@ -452,9 +485,10 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
                         }
                     }
                 }
+            }
                 if (staged_q) {
                     __builtin_amdgcn_wave_barrier();
-                    const int m_base = em0 + (wm * TM + i) * 32;
+                    const int m_base = em0 + (wm * TM + 2 * ib) * 16;
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
                         const int q = lane + 64 * k, row = q >> 3, cc = q & 7;
@@ -471,11 +505,11 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
             }
             }
         } else if constexpr (OUT == 0) {
-            // fp32 (+ residual) output through a per-wave LDS transpose, one 32 x 32 accumulator tile at a time.  Patch: 32 rows
-            // x 128 B, the 16-byte chunk index XORed with row & 7: the accumulator-order writes (ds_write_b128: 8 rows of one
+            // fp32 (+ residual) output through a per-wave LDS transpose, one 32 x 32 block (2 x 2 accumulator tiles) at a time.  Patch:
+            // 32 rows x 128 B, the 16-byte chunk index XORed with row & 7: the accumulator-order writes (ds_write_b128: 8 rows of one
             // chunk column per group) and the row-order reads (ds_read_b128: four rows of 4 chunks per group) are conflict-free.
             // In row order lane q holds chunk q & 7 of rows (q >> 3) + 8 k: 8 lanes cover one full 128-byte line, a load / store
-            // instruction 8 full lines (the accumulator layout gives 32 rows x 32 bytes per instruction: 4 x the line accesses).
+            // instruction 8 full lines (the accumulator layout gives 16 rows x 64 bytes per instruction: 4 x the line accesses).
             // Loads and stores are BUFFER operations whose offset is pushed out of range for rows >= M / columns >= N: no branch
             // around any of them.  A memory operation under a branch makes the compiler wait for everything in flight at the next
             // use (vmcnt(0), which counts the stores already issued as well): one store round trip per 4 values.
@@ -486,40 +520,45 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
             const long long cb = xm.tiles_per_batch ? (long long)(eb % xm.batch_inner) * xm.c_b0 + (long long)(eb / xm.batch_inner) * xm.c_b1 : 0;
             const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(Cf + cb, 0, (int)((unsigned int)M * ldc * 4u), 0x00020000);
             const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(residual ? residual : Cf) + cb, 0, (int)((unsigned int)M * ldc * 4u), 0x00020000);
-            unsigned int coff[TN];                                // byte offset of the lane's four columns inside a row, or out of range
-            f32x4 bv[TN];
+            constexpr int NB = TN / 2;                            // 32-column blocks per wave
+            unsigned int coff[NB];                                // byte offset of the lane's four columns inside a row, or out of range
+            f32x4 bv[NB];
 #pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int n = en0 + (wn * TN + j) * 32 + cc * 4;  // N % 4 == 0 is required by the launcher
+            for (int j = 0; j < NB; ++j) {
+                const int n = en0 + wn * 64 + j * 32 + cc * 4;    // N % 4 == 0 is required by the launcher
                 coff[j] = n < N ? (unsigned int)n * 4u : kOob;
                 bv[j] = (bias && n < N) ? *reinterpret_cast<const f32x4*>(bias + n) : f32x4{0.f, 0.f, 0.f, 0.f};
             }
 #pragma unroll
-            for (int j = 0; j < TN; ++j) asm volatile("" :: "v"(bv[j]));                     // waited for HERE, not inside the block loop
+            for (int j = 0; j < NB; ++j) asm volatile("" :: "v"(bv[j]));                     // waited for HERE, not inside the block loop
             auto c_off = [&](int m, int j) -> int {
                 return (int)((m < M && coff[j] != kOob) ? (unsigned int)m * ldc * 4u + coff[j] : kOob);
             };
             // residual rows of block i + 1 are loaded before block i is processed: one memory latency per item, not per block
-            u32x4 rv[2][TN][4];
-            auto load_residual = [&](int i, u32x4 (&dst)[TN][4]) {
-                const int m_base = em0 + (wm * TM + i) * 32;
+            u32x4 rv[2][NB][4];
+            auto load_residual = [&](int i, u32x4 (&dst)[NB][4]) {
+                const int m_base = em0 + (wm * TM + 2 * i) * 16;
 #pragma unroll
-                for (int j = 0; j < TN; ++j)
+                for (int j = 0; j < NB; ++j)
 #pragma unroll
                     for (int k = 0; k < 4; ++k)
                         dst[j][k] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsR, c_off(m_base + rq + 8 * k, j), 0, 0));
             };
             if (residual) load_residual(0, rv[0]);
 #pragma unroll
-            for (int i = 0; i < TM; ++i) {
-                const int m_base = em0 + (wm * TM + i) * 32;
-                if (residual && i + 1 < TM) load_residual(i + 1, rv[(i + 1) & 1]);
+            for (int i = 0; i < TM / 2; ++i) {
+                const int m_base = em0 + (wm * TM + 2 * i) * 16;
+                if (residual && i + 1 < TM / 2) load_residual(i + 1, rv[(i + 1) & 1]);
 #pragma unroll
-                for (int j = 0; j < TN; ++j) {
+                for (int j = 0; j < NB; ++j) {
+                    // accumulator tile (2 j + u, 2 i + s): block row 16 s + r, chunk 4 u + kq
 #pragma unroll
-                    for (int g = 0; g < 4; ++g)
-                        *reinterpret_cast<f32x4*>(patch + r * 128 + (((2 * g + kh) ^ (r & 7)) << 4)) =
-                            f32x4{acc[j][i][4 * g], acc[j][i][4 * g + 1], acc[j][i][4 * g + 2], acc[j][i][4 * g + 3]};
+                    for (int s = 0; s < 2; ++s)
+#pragma unroll
+                        for (int u = 0; u < 2; ++u) {
+                            const int prow = 16 * s + r;
+                            *reinterpret_cast<f32x4*>(patch + prow * 128 + (((4 * u + kq) ^ (prow & 7)) << 4)) = acc[2 * j + u][2 * i + s];
+                        }
                     __builtin_amdgcn_wave_barrier();
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
@@ -544,7 +583,7 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
                 }
             }
         } else {
-            // OUT 1.  Lane holds column m = m_base + r of C^T, rows n = (v&3) + 8(v>>2) + 4kh; split-plane output leaves through a
+            // OUT 1.  Lane holds column m = m_base + r of C^T, rows n = 16 j + 4 kq + e; split-plane output leaves through a
             // per-wave LDS transpose as full 128-byte row segments.  (Round 4 tried whole 16-byte chunks per lane -- one
             // v_permlane32_swap per dword between the lane pair (r, kh = 0 / 1), ds_write_b128 into an XOR-swizzled 256-byte row,
             // no bank conflicts: FC1 -0.8 % -- and did not keep it: the full- and the half-height instantiations then disagreed in the
@@ -554,36 +593,31 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
                 // bf16 plane out, row-major [M][N] (the next GEMM's operand): the wave's 64 columns are 128 contiguous bytes per row;
                 // through a per-wave LDS patch (32 rows x 128 B + 16 B pad) so that 8 lanes store one full line
                 constexpr int SPB = 144;
-                const bool staged = (N % 8 == 0) && (en0 + (wn * TN + TN) * 32 <= N);
+                const bool staged = (N % 8 == 0) && (en0 + (wn + 1) * 64 <= N);
                 unsigned char* patch = patches + wave * (32 * SPB);
-                f32x4 bvs[TN][4];
+                f32x4 bvs[TN];
 #pragma unroll
-                for (int j = 0; j < TN; ++j)
+                for (int j = 0; j < TN; ++j) {
+                    const int n = en0 + wn * 64 + 16 * j + 4 * kq;
+                    bvs[j] = (bias && n < N) ? *reinterpret_cast<const f32x4*>(bias + n) : f32x4{0.f, 0.f, 0.f, 0.f};
+                }
 #pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const int n = en0 + (wn * TN + j) * 32 + 8 * g + 4 * kh;
-                        bvs[j][g] = (bias && n < N) ? *reinterpret_cast<const f32x4*>(bias + n) : f32x4{0.f, 0.f, 0.f, 0.f};
-                    }
+                for (int j = 0; j < TN; ++j) asm volatile("" :: "v"(bvs[j]));
 #pragma unroll
-                for (int j = 0; j < TN; ++j)
+                for (int ib = 0; ib < TM / 2; ++ib) {
 #pragma unroll
-                    for (int g = 0; g < 4; ++g) asm volatile("" :: "v"(bvs[j][g]));
+                    for (int s = 0; s < 2; ++s) {
+                    const int i = 2 * ib + s, prow = 16 * s + r;
+                    const int m = em0 + (wm * TM + i) * 16 + r;
+                    if (m >= M) continue;
 #pragma unroll
-                for (int i = 0; i < TM; ++i) {
-                    const int m = em0 + (wm * TM + i) * 32 + r;
-                    const bool row_ok = m < M;
-                    if (!staged && !row_ok) continue;
-                    if (row_ok)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j)
-#pragma unroll
-                        for (int g = 0; g < 4; ++g) {
-                            const int n = en0 + (wn * TN + j) * 32 + 8 * g + 4 * kh;
+                    for (int j = 0; j < TN; ++j) {
+                            const int n = en0 + wn * 64 + 16 * j + 4 * kq;
                             if (n >= N) continue;
-                            const f32x4 bv = bvs[j][g];
+                            const f32x4 bv = bvs[j];
                             f32x4 val;
 #pragma unroll
-                            for (int e = 0; e < 4; ++e) val[e] = fmaf(acc[j][i][4 * g + e], out_scale, bv[e]);
+                            for (int e = 0; e < 4; ++e) val[e] = fmaf(acc[j][i][e], out_scale, bv[e]);
                             if (EPI == EPI_GELU) val = gelu_erf16(val);
                             if (EPI == EPI_GELU_TANH) val = gelu_tanh16(val);
                             if (EPI == EPI_SQRELU)
@@ -592,13 +626,14 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
                             u32x2 pk;
                             pk[0] = (unsigned int)f32_to_bf16_rne(val[0]) | ((unsigned int)f32_to_bf16_rne(val[1]) << 16);
                             pk[1] = (unsigned int)f32_to_bf16_rne(val[2]) | ((unsigned int)f32_to_bf16_rne(val[3]) << 16);
-                            if (staged) *reinterpret_cast<u32x2*>(patch + r * SPB + j * 64 + (8 * g + 4 * kh) * 2) = pk;
+                            if (staged) lds_put(patch + prow * SPB + (16 * j + 4 * kq) * 2, pk);
                             else *reinterpret_cast<u32x2*>(Ch + (size_t)m * (size_t)N + n) = pk;
                         }
+                    }
                     if (staged) {
                         __builtin_amdgcn_wave_barrier();
-                        const int m_base = em0 + (wm * TM + i) * 32;
-                        const size_t ncol0 = (size_t)en0 + (size_t)wn * TN * 32;
+                        const int m_base = em0 + (wm * TM + 2 * ib) * 16;
+                        const size_t ncol0 = (size_t)en0 + (size_t)wn * 64;
 #pragma unroll
                         for (int k = 0; k < 4; ++k) {
                             const int q = lane + 64 * k, row = q >> 3, cc = q & 7;
@@ -611,37 +646,35 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
             } else {
             // per-wave LDS patch: 32 rows x (256 B in OUTPUT order: group 0 hi | group 0 lo | group 1 hi | group 1 lo) + 16 B pad
             constexpr int SP = 272;
-            const bool staged = (N % 8 == 0) && (en0 + (wn * TN + TN) * 32 <= N);
+            const bool staged = (N % 8 == 0) && (en0 + (wn + 1) * 64 <= N);
             unsigned char* patch = patches + wave * (32 * SP);
             // the wave's bias values, once per item (see OUT 2 above)
-            f32x4 bvs[TN][4];
+            f32x4 bvs[TN];
 #pragma unroll
-            for (int j = 0; j < TN; ++j)
+            for (int j = 0; j < TN; ++j) {
+                const int n = en0 + wn * 64 + 16 * j + 4 * kq;
+                bvs[j] = (bias && n < N) ? *reinterpret_cast<const f32x4*>(bias + n) : f32x4{0.f, 0.f, 0.f, 0.f};
+            }
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int n = en0 + (wn * TN + j) * 32 + 8 * g + 4 * kh;
-                    bvs[j][g] = (bias && n < N) ? *reinterpret_cast<const f32x4*>(bias + n) : f32x4{0.f, 0.f, 0.f, 0.f};
-                }
+            for (int j = 0; j < TN; ++j) asm volatile("" :: "v"(bvs[j]));              // waited for HERE, not inside the block loop
+            // 32-row blocks of two M16 tiles (patch row 16 s + r)
 #pragma unroll
-            for (int j = 0; j < TN; ++j)
+            for (int ib = 0; ib < TM / 2; ++ib) {
 #pragma unroll
-                for (int g = 0; g < 4; ++g) asm volatile("" :: "v"(bvs[j][g]));              // waited for HERE, not inside the block loop
-#pragma unroll
-            for (int i = 0; i < TM; ++i) {
-                const int m = em0 + (wm * TM + i) * 32 + r;
-                const bool row_ok = m < M;
-                if (!staged && !row_ok) continue;
-                if (row_ok)
+                for (int s = 0; s < 2; ++s) {
+                const int i = 2 * ib + s, prow = 16 * s + r;
+                const int m = em0 + (wm * TM + i) * 16 + r;
+                if (m >= M) continue;
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const int n = en0 + (wn * TN + j) * 32 + 8 * g + 4 * kh;
+                    {
+                        const int c = 16 * j + 4 * kq;               // column inside the wave's 64
+                        const int n = en0 + wn * 64 + c;
                         if (n >= N) continue;                    // N % 4 == 0 is required by the launcher
-                        const f32x4 bv = bvs[j][g];
+                        const f32x4 bv = bvs[j];
                         f32x4 val;
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) val[e] = fmaf(acc[j][i][4 * g + e], out_scale, bv[e]);
+                        for (int e = 0; e < 4; ++e) val[e] = fmaf(acc[j][i][e], out_scale, bv[e]);
                         if (EPI == EPI_GELU) val = gelu_erf16(val);
                         if (EPI == EPI_GELU_TANH) val = gelu_tanh16(val);
                         if (EPI == EPI_SQRELU)   // tranception/activations.py:79-84
@@ -657,9 +690,9 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
                                 lo[e] = b;
                             }
                             if (staged) {
-                                unsigned char* cell = patch + r * SP + j * 128 + (8 * g + 4 * kh) * 2;
-                                *reinterpret_cast<h4*>(cell) = hi;
-                                *reinterpret_cast<h4*>(cell + 64) = lo;
+                                unsigned char* cell = patch + prow * SP + (c >> 5) * 128 + (c & 31) * 2;
+                                lds_put(cell, hi);
+                                lds_put(cell + 64, lo);
                             } else {
                                 unsigned short* dst = Ch + ki_off((size_t)m, n, N);
                                 *reinterpret_cast<h4*>(dst) = hi;
@@ -668,12 +701,13 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
                         }
                     }
                 }
+                }
                 if (staged) {
                     // K-interleaved output: the wave's 64 columns are two 32-column groups = 2 x (64 B hi | 64 B lo) = 256
                     // contiguous bytes per row: 16 lanes write one row
                     __builtin_amdgcn_wave_barrier();
-                    const int m_base = em0 + (wm * TM + i) * 32;
-                    const size_t ncol0 = (size_t)en0 + (size_t)wn * TN * 32;
+                    const int m_base = em0 + (wm * TM + 2 * ib) * 16;
+                    const size_t ncol0 = (size_t)en0 + (size_t)wn * 64;
 #pragma unroll
                     for (int k = 0; k < 8; ++k) {
                         const int q = lane + 64 * k;                 // 16-byte chunk: row q/16, chunk q%16 of the 256-byte run
