@@ -48,6 +48,11 @@ extern "C" {
 /* ProGen2: GPT-J-style causal LM, parallel residual, partial interleaved rotary, tanh-GELU
  * (proteingym/baselines/progen2/models/progen/modeling_progen.py); created with pgmi_pg2_model_create */
 #define PGMI_ARCH_PROGEN2 5
+/* Pre-LN causal decoder with a sequential residual: RITA (rotary) and ProtGPT2 = GPT-2 (learned positions); created with
+ * pgmi_gpt_model_create */
+#define PGMI_ARCH_GPT 6
+#define PGMI_GPT_POS_ROTARY 0   /* RITA (proteingym/baselines/rita/rita_modeling.py): rotate-half rotary, untied lm_head */
+#define PGMI_GPT_POS_LEARNED 1  /* GPT-2 (transformers GPT2LMHeadModel): wpe added to wte, lm_head tied to wte */
 
 /* GEMM operand precision.  Residual stream, LayerNorm statistics, softmax and every
  * accumulator are fp32 in all modes. */
@@ -313,6 +318,34 @@ int pgmi_bench_gemm_ab(int device, int precision, int M, int N, int K, int epilo
 int pgmi_pg2_model_create(const pgmi_config* cfg, int rotary_dim, const float* weights, int64_t n_weights, int device, pgmi_model** out);
 int pgmi_pg2_token_logprobs(pgmi_model* m, const int32_t* tokens, int B, int T, float* out);
 int pgmi_pg2_sequence_loglik(pgmi_model* m, const int32_t* tokens, int B, int L, float* out, int32_t* n_kept);
+
+/* ---- Causal decoder (arch PGMI_ARCH_GPT; any vocab, max_positions = n_positions / max_seq_len, precision f16x3) ----------------
+ * Per layer: x += out_proj(causal_attention(ln_1(x))); x += fc_out(gelu_tanh(fc_in(ln_2(x)))); then ln_f and the bias-free head.
+ * Scores are scaled by head_dim^-1/2; gelu_tanh(u) = 0.5 u (1 + tanh(0.79788456 (u + 0.044715 u^3))) (RITA_gelu, gelu_new).
+ * head_dim = D / heads: an even value up to 64 (zero-padded to 64 lanes) or 128 (RITA XL).  Token ids are the tokenizer's own.
+ * Weight blob order (fp32, nn.Linear layout [out,in]; GPT-2's Conv1D weights are transposed and c_attn split by the host,
+ * proteingym_amd/causal_lm.py):
+ *   wte [V,D]; (LEARNED) wpe [max_positions,D];
+ *   per layer: ln_1 w,b; Wq [D,D], bq; Wk, bk; Wv, bv; Wo [D,D], bo; ln_2 w,b; fc_in W[F,D], b[F]; fc_out W[D,F], b[D];
+ *   ln_f w,b; (ROTARY) lm_head [V,D].
+ * pos_kind ROTARY (RITA): q and k rotate by rotate-half over the whole head, pairs (j, j + head_dim/2),
+ *   inv_freq = 10000^(-2j/head_dim), angle = fp32(t) * fp32(inv_freq) (rita_modeling.py:36-62).
+ * pos_kind LEARNED (GPT-2): x = wte[id] + wpe[t]; the head is wte itself.
+ *
+ * pgmi_gpt_weight_count: the blob size for (cfg, pos_kind); <0 on a bad cfg.  (pgmi_weight_count returns -1 for this arch.)
+ * pgmi_gpt_model_create: as pgmi_model_create, with pos_kind.  Returns an ordinary model: destroy, profile, synchronize as usual.
+ * pgmi_gpt_token_logprobs: log_softmax(model(input_ids).logits) over all V columns; tokens int32 [B,T] (no padding,
+ *   T <= max_positions), out f32 [B,T,V].
+ * pgmi_gpt_sequence_loglik: B rows right-padded to T tokens (pad ids must lie in [0, V)), row b holding lens[b] >= 2 real tokens.
+ *   sum[b] = sum over t < lens[b]-1 of log p(tokens[b,t+1] | tokens[b,<=t]) and n_targets[b] = lens[b]-1 (optional); the
+ *   reference's -CE of the row is sum[b] / n_targets[b].  Pad positions are never scored and need no key mask (a causal row reads
+ *   no key to its right).  A row's result has the same bits whatever else is in the batch.
+ * Heads with V <= 64 (RITA: 26) run on one wave per row; wider ones (ProtGPT2: 50257) on the f16x3 GEMM into fp32 logits followed
+ * by a 256-thread log-softmax per row, over the target rows only when scoring. */
+int64_t pgmi_gpt_weight_count(const pgmi_config* cfg, int pos_kind);
+int pgmi_gpt_model_create(const pgmi_config* cfg, int pos_kind, const float* weights, int64_t n_weights, int device, pgmi_model** out);
+int pgmi_gpt_token_logprobs(pgmi_model* m, const int32_t* tokens, int B, int T, float* out);
+int pgmi_gpt_sequence_loglik(pgmi_model* m, const int32_t* tokens, const int32_t* lens, int B, int T, double* sum, int32_t* n_targets);
 
 /* ---- MSA Transformer (arch PGMI_ARCH_MSA; vocab 33, head_dim 64, precision f16x3) --------------------
  * Replaces MSATransformer.forward (proteingym/baselines/esm/esm/model/msa_transformer.py:146-205; tied

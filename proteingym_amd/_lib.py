@@ -14,6 +14,8 @@ LIB_PATH = os.path.join(HERE, "libpgmi.so")
 ABI_VERSION = 4
 ARCH_ESM1B, ARCH_ESM2, ARCH_TRANCEPTION = 1, 2, 3
 ARCH_PROGEN2 = 5
+ARCH_GPT = 6
+GPT_POS_ROTARY, GPT_POS_LEARNED = 0, 1
 PREC_FP32, PREC_BF16, PREC_F16X3 = 0, 1, 2
 PRECISIONS = {"fp32": PREC_FP32, "bf16": PREC_BF16, "f16x3": PREC_F16X3}
 K_NAMES = ["embed", "layernorm", "gemm_qkv", "attention", "gemm_out", "gemm_fc1", "gemm_fc2",
@@ -83,6 +85,10 @@ SIGNATURES = [
     ("pgmi_pg2_model_create", C.c_int, [C.POINTER(Config), C.c_int, _f32p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     ("pgmi_pg2_token_logprobs", C.c_int, [C.c_void_p, _i32p, C.c_int, C.c_int, _f32p]),
     ("pgmi_pg2_sequence_loglik", C.c_int, [C.c_void_p, _i32p, C.c_int, C.c_int, _f32p, _i32p]),
+    ("pgmi_gpt_weight_count", C.c_int64, [C.POINTER(Config), C.c_int]),
+    ("pgmi_gpt_model_create", C.c_int, [C.POINTER(Config), C.c_int, _f32p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
+    ("pgmi_gpt_token_logprobs", C.c_int, [C.c_void_p, _i32p, C.c_int, C.c_int, _f32p]),
+    ("pgmi_gpt_sequence_loglik", C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, C.c_int, _f64p, _i32p]),
     ("pgmi_bench_gemm", C.c_int, [C.c_int] * 9 + [_f64p]),
     ("pgmi_bench_gemm_ab", C.c_int, [C.c_int] * 7 + [_i32p, C.c_int, C.c_int, C.c_int, _f64p]),
     ("pgmi_op_attention", C.c_int, [C.c_int, C.c_int, _f32p, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),

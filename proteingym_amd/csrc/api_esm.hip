@@ -15,17 +15,7 @@ int create_esm(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_
         c.upload(&m->lnb_w, D);
         c.upload(&m->lnb_b, D);
     }
-    // head layout: every head owns 64 lanes of the attention kernels; dim j of a head sits in slot
-    // j (first half) or 32 + (j - dh/2) (second half) so that rotary pairs (j, j + dh/2) are the
-    // kernels' pairs (i, i + 32).  dh == 64 is the identity layout; smaller heads leave zero slots
-    // (zero weight rows -> q,k,v slots exactly 0 -> scores and context unchanged).
-    // head_dim 128: a head is two slot groups; group g in {0,1} holds dims 32 g + i (slots i < 32) and 64 + 32 g + i (slots 32 + i), so
-    // the rotary partners (j, j + 64) are again the kernels' pairs (i, i + 32) inside ONE 64-column wave tile of the QKV epilogue.
-    auto slot = [&](size_t col) -> size_t {
-        const size_t h = col / dh, j = col % dh;
-        if (dh > 64) return (2 * h + ((j >> 5) & 1)) * 64 + ((j >> 6) << 5) + (j & 31);
-        return h * 64 + (j < dh / 2 ? j : 32 + (j - dh / 2));
-    };
+    auto slot = [&](size_t col) -> size_t { return rotate_half_slot(col, dh); };
     const float qscale = 1.0f / sqrtf((float)dh);           // multihead_attention.py:261 (exact 1/8 for dh 64)
     m->layers.resize(cfg->layers);
     std::vector<float> wq(3 * Da * D, 0.0f), bq(3 * Da, 0.0f), wo_r(D * Da, 0.0f);
@@ -58,6 +48,10 @@ int create_esm(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_
 
 int ensure_rotary(pgmi_model* m, int T) {
     if (m->cfg.arch != PGMI_ARCH_ESM2 || T <= m->rot_len) return PGMI_OK;
+    return upload_rotate_half(m, std::max(T, 1026));
+}
+
+int upload_rotate_half(pgmi_model* m, int n) {
     // rotary_embedding.py:40,52-58: inv_freq = 1/10000^(2i/d) in f32; freqs = t * inv_freq (f32);
     // emb = cat(freqs, freqs); cos/sin taken in f32.
     const int rh = m->rot_halves;                          // table rows per token: slot-group parity for head_dim 128
@@ -65,7 +59,7 @@ int ensure_rotary(pgmi_model* m, int T) {
     const int half = m->dh / 2;                            // rotary pairs are (j, j + dh/2)
     for (int i = 0; i < half; ++i) inv[i] = 1.0f / powf(10000.0f, (float)(2 * i) / (float)m->dh);
     // slots i and 32+i of slot group g hold dims j and j + dh/2 with j = i (dh <= 64) or 32 g + i (dh 128)
-    return upload_rotary(m, std::max(T, 1026), rh, [&](int t, int g, int i) {
+    return upload_rotary(m, n, rh, [&](int t, int g, int i) {
         const int j = (rh == 1) ? i : 32 * g + i;
         return j < half ? (float)t * inv[j] : 0.0f;                        // padded slots (dh < 64): cos 1, sin 0
     });

@@ -1,0 +1,249 @@
+// Causal decoder with a sequential pre-LN residual: RITA (proteingym/baselines/rita/rita_modeling.py) and ProtGPT2, a GPT-2
+// (transformers GPT2LMHeadModel; proteingym/baselines/protgpt2/compute_fitness.py).  Model creation, the forward, the two LM heads
+// and the C entries.
+//
+// Per layer (rita_modeling.py:208-219; GPT2Block): x += out_proj(attn(ln_1(x)));  x += fc_out(gelu_tanh(fc_in(ln_2(x)))).  The
+// attention runs on the kernels the other causal LMs use: the fused QKV epilogue (RITA: ESM2's rotate-half rotary tables) and
+// attention_f16x3_v2 with all-zero ALiBi slopes (the ALiBi term is then exactly 0).  Heads: V <= 64 (RITA: 26) on one wave per row
+// (vocab_logsoftmax_kernel); wider ones (ProtGPT2: 50 257, tied to wte) on the f16x3 GEMM into fp32 logits, then one workgroup per
+// row (wide_logsoftmax_kernel).  When scoring, only the rows that have a target reach the head.
+#include "model.h"
+
+namespace pgmi {
+
+static bool wide_head(const pgmi_config& c) { return c.vocab > kWave; }
+constexpr int kWideHeadRows = 2048;        // logits rows per head GEMM: 2048 x 50 304 x 4 B = 412 MB at ProtGPT2's vocabulary
+
+int64_t gpt_weight_count(const pgmi_config* c, int pos_kind) {
+    if (pos_kind != PGMI_GPT_POS_ROTARY && pos_kind != PGMI_GPT_POS_LEARNED) return -1;
+    const int64_t D = c->embed_dim, F = c->ffn_dim, V = c->vocab, P = c->max_positions;
+    const int64_t layer = 2 * D + 3 * (D * D + D) + (D * D + D) + 2 * D + (F * D + F) + (D * F + D);
+    return V * D + (pos_kind == PGMI_GPT_POS_LEARNED ? P * D : 0) + (int64_t)c->layers * layer + 2 * D +
+           (pos_kind == PGMI_GPT_POS_ROTARY ? V * D : 0);
+}
+
+int create_gpt(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights, int pos_kind) {
+    const size_t D = cfg->embed_dim, F = cfg->ffn_dim, V = cfg->vocab, H = cfg->heads, dh = m->dh, Da = m->Da;
+    const bool rotary = pos_kind == PGMI_GPT_POS_ROTARY;
+    m->gpt_pos = pos_kind;
+    BlobCursor c(m, w, n_weights);
+    const float* wte = c.take(V * D);
+    c.upload(&m->embed_tokens, wte, V * D);
+    if (!rotary) c.upload(&m->embed_positions, (size_t)cfg->max_positions * D);
+    auto slot = [&](size_t col) -> size_t { return rotate_half_slot(col, dh); };
+    // scores * head_dim^-1/2 (rita_modeling.py:153, after the rotary; GPT2Attention): rotary is linear, so the scale folds into q
+    const float qscale = 1.0f / sqrtf((float)dh);
+    m->layers.resize(cfg->layers);
+    std::vector<float> wq(3 * Da * D, 0.0f), bq(3 * Da, 0.0f), wo_r(D * Da, 0.0f);
+    for (int l = 0; l < cfg->layers; ++l) {
+        Layer& L = m->layers[l];
+        c.upload(&L.ln1_w, D);
+        c.upload(&L.ln1_b, D);
+        pack_qkv_slots(c.take(3 * (D * D + D)), D, Da, slot, qscale, wq.data(), bq.data());
+        c.w16(&L.wqkv16, wq.data(), wq.size(), D);
+        c.upload(&L.bqkv, bq.data(), bq.size());
+        pack_out_cols(c.take(D * D), D, Da, slot, wo_r.data());
+        c.w16(&L.wo16, wo_r.data(), wo_r.size(), Da);
+        c.upload(&L.bo, D);
+        c.upload(&L.ln2_w, D);
+        c.upload(&L.ln2_b, D);
+        c.w16(&L.w116, F * D, D);
+        c.upload(&L.b1, F);
+        c.w16(&L.w216, D * F, F);
+        c.upload(&L.b2, D);
+    }
+    c.upload(&m->lna_w, D);
+    c.upload(&m->lna_b, D);
+    const float* head = rotary ? c.take(V * D) : wte;                // GPT-2: lm_head.weight is wte itself
+    const size_t Vp = (V + 63) / 64 * 64;
+    m->gpt_Vp = (int)Vp;
+    if (!wide_head(*cfg)) {
+        c.upload(&m->gpt_head_w, head, V * D);
+    } else {
+        // zero rows V .. Vp-1: whole 64-column GEMM tiles; the log-softmax excludes those columns by index
+        std::vector<float> padded(Vp * D, 0.0f);
+        memcpy(padded.data(), head, V * D * sizeof(float));
+        c.w16(&m->gpt_head16, padded.data(), padded.size(), D);
+        m->gpt_head_rows = std::min(m->max_rows, kWideHeadRows);
+    }
+    const std::vector<float> zeros(std::max(Vp, D), 0.0f), zs(H, 0.0f);
+    c.upload(&m->gpt_zero, zeros.data(), zeros.size());
+    c.upload(&m->gpt_slopes, zs.data(), zs.size());
+    int rc = c.finish();
+    if (!rc && m->gpt_head_rows) rc = dev_alloc(m->allocs, &m->gpt_logits, (size_t)m->gpt_head_rows * Vp);
+    if (!rc) rc = dev_alloc(m->allocs, &m->gpt_sum, (size_t)m->max_rows);
+    if (!rc && rotary) rc = upload_rotate_half(m, cfg->max_positions);
+    return rc;
+}
+
+// The decoder body on tokens in m->tokens [B,T]; leaves the residual stream after the last layer in m->x [B*T, D].
+static int run_gpt_body(pgmi_model* m, int B, int T) {
+    const pgmi_config& c = m->cfg;
+    const int M = B * T, D = c.embed_dim, F = c.ffn_dim, H = c.heads, Da = m->Da;
+    const bool rotary = m->gpt_pos == PGMI_GPT_POS_ROTARY;
+    hipStream_t s = m->stream;
+    int rc = reset_pad_keys(m, B, T);
+    if (rc) return rc;
+    { ProfScope p(m, PGMI_K_EMBED, 0, (double)M * D * (rotary ? 4 : 8));
+      if (rotary) launch_gather_rows(m->embed_tokens, m->tokens, M, D, m->x, s);        // rita_modeling.py:255: no positional table
+      else launch_embed_learned(m->tokens, m->embed_tokens, m->embed_positions, M, T, D, m->x, s); }
+    const double ln_bytes = 2.0 * M * D * 4;
+    for (int l = 0; l < c.layers; ++l) {
+        const Layer& L = m->layers[l];
+        { ProfScope p(m, PGMI_K_LAYERNORM, 0, ln_bytes);
+          launch_layernorm16(m->x, L.ln1_w, L.ln1_b, M, D, m->ln_eps, m->h16, m->h16_plane, 1, s); }
+        { ProfScope p(m, PGMI_K_GEMM_QKV, 2.0 * M * 3 * Da * D, 0);
+          rc = launch_gemm16_qkv(m->h16, m->h16_plane, L.wqkv16.p, L.wqkv16.plane, L.bqkv, M, Da, D, L.wqkv16.out_scale,
+                                 m->qk16, m->qk16_plane, m->vt16, m->vt16_plane, m->rot_cos, m->rot_sin, rotary, T, m->Hs,
+                                 m->gemm_variant, s, m->rot_halves, false);
+          if (rc) return rc; }
+        { ProfScope p(m, PGMI_K_ATTENTION, 2.0 * M * T * Da, 0);             // causal: half of the 4 M T Da of a dense pass
+          rc = launch_attention_f16x3_v2(nullptr, nullptr, m->rot_cos, m->rot_sin, rotary, B, T, H, m->qk16, m->qk16_plane, m->vt16,
+                                         m->vt16_plane, nullptr, m->h16, m->h16_plane, 1, s, nullptr, m->gpt_slopes, m->rot_halves * kHeadDim);
+          if (rc) return rc; }
+        { ProfScope p(m, PGMI_K_GEMM_OUT, 2.0 * M * D * Da, 0);
+          rc = linear(m, nullptr, m->h16, m->h16_plane, nullptr, L.wo16, L.bo, m->x, m->x, nullptr, 0, M, D, Da, EPI_NONE);
+          if (rc) return rc; }
+        { ProfScope p(m, PGMI_K_LAYERNORM, 0, ln_bytes);
+          launch_layernorm16(m->x, L.ln2_w, L.ln2_b, M, D, m->ln_eps, m->h16, m->h16_plane, 1, s); }
+        { ProfScope p(m, PGMI_K_GEMM_FC1, 2.0 * M * F * D, 0);
+          rc = linear(m, nullptr, m->h16, m->h16_plane, nullptr, L.w116, L.b1, nullptr, nullptr, m->g16, m->g16_plane, M, F, D, EPI_GELU_TANH);
+          if (rc) return rc; }
+        { ProfScope p(m, PGMI_K_GEMM_FC2, 2.0 * M * F * D, 0);
+          rc = linear(m, nullptr, m->g16, m->g16_plane, nullptr, L.w216, L.b2, m->x, m->x, nullptr, 0, M, D, F, EPI_NONE);
+          if (rc) return rc; }
+    }
+    return PGMI_OK;
+}
+
+// Wide head on R rows whose ln_f output is in m->h16: per chunk of gpt_head_rows, fp32 logits [rc][Vp] from the f16x3 GEMM against
+// wte (profiled as PGMI_K_HEAD), then the log-softmax (PGMI_K_SCORE).  tgt != nullptr: out[r] = log p(tgt[r]) on the device; else
+// each chunk's full rows go to host_out [R][V] (the stream is synchronized per chunk: m->lp holds one chunk).
+static int wide_head_rows(pgmi_model* m, int R, const int32_t* tgt, float* out, float* host_out) {
+    const int D = m->cfg.embed_dim, V = m->cfg.vocab, Vp = m->gpt_Vp;
+    for (int r0 = 0; r0 < R; r0 += m->gpt_head_rows) {
+        const int rc_rows = std::min(m->gpt_head_rows, R - r0);
+        { ProfScope p(m, PGMI_K_HEAD, 2.0 * rc_rows * Vp * D, 0);
+          int rc = linear(m, nullptr, m->h16 + (size_t)r0 * 2 * D, m->h16_plane, nullptr, m->gpt_head16, m->gpt_zero, nullptr,
+                          m->gpt_logits, nullptr, 0, rc_rows, Vp, D, EPI_NONE);
+          if (rc) return rc; }
+        { ProfScope p(m, PGMI_K_SCORE, 0, (double)rc_rows * V * 4 * (tgt ? 1 : 3));
+          launch_wide_logsoftmax(m->gpt_logits, Vp, rc_rows, V, tgt ? tgt + r0 : nullptr, tgt ? out + r0 : m->lp, m->nonfinite, m->stream); }
+        if (!tgt) {
+            PGMI_HIP(hipMemcpyAsync(host_out + (size_t)r0 * V, m->lp, (size_t)rc_rows * V * 4, hipMemcpyDeviceToHost, m->stream));
+            PGMI_HIP(hipStreamSynchronize(m->stream));
+        }
+    }
+    return PGMI_OK;
+}
+
+static int gpt_check(pgmi_model* m, int T) {
+    if (m->cfg.arch != PGMI_ARCH_GPT) { set_error("not a causal decoder (RITA / ProtGPT2) model"); return PGMI_EINVAL; }
+    if (T > m->cfg.max_positions) { set_error("sequence of %d tokens exceeds the model context of %d positions", T, m->cfg.max_positions); return PGMI_EINVAL; }
+    if (T + 31 > m->max_rows) { set_error("T=%d exceeds workspace rows %d", T, m->max_rows); return PGMI_EINVAL; }
+    return PGMI_OK;
+}
+
+}  // namespace pgmi
+
+extern "C" {
+
+int64_t pgmi_gpt_weight_count(const pgmi_config* cfg, int pos_kind) {
+    if (!cfg || cfg->layers <= 0 || cfg->embed_dim <= 0 || cfg->ffn_dim <= 0 || cfg->vocab <= 0 || cfg->max_positions <= 0) return -1;
+    return gpt_weight_count(cfg, pos_kind);
+}
+
+int pgmi_gpt_model_create(const pgmi_config* cfg, int pos_kind, const float* weights, int64_t n_weights, int device, pgmi_model** out) {
+    if (out) *out = nullptr;
+    if (!cfg || cfg->arch != PGMI_ARCH_GPT) { set_error("pgmi_gpt_model_create: arch must be PGMI_ARCH_GPT"); return PGMI_EINVAL; }
+    return model_create(cfg, weights, n_weights, device, out, pos_kind);
+}
+
+int pgmi_gpt_token_logprobs(pgmi_model* m, const int32_t* tokens, int B, int T, float* out) {
+    if (!m || !tokens || !out || B <= 0 || T <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
+    int rc = gpt_check(m, T);
+    if (rc) return rc;
+    const pgmi_config& c = m->cfg;
+    const int V = c.vocab, D = c.embed_dim;
+    rc = check_vocab(tokens, B, T, V);
+    if (rc) return rc;
+    PGMI_HIP(hipSetDevice(m->device));
+    hipStream_t s = m->stream;
+    rc = for_each_chunk(m, B, T, [&](int b0, int bc) {
+        const int M = bc * T;
+        PGMI_HIP(hipMemcpyAsync(m->tokens, tokens + (size_t)b0 * T, (size_t)M * 4, hipMemcpyHostToDevice, s));
+        int rc = run_gpt_body(m, bc, T);
+        if (rc) return rc;
+        float* dst = out + (size_t)b0 * T * V;
+        if (wide_head(c)) {
+            { ProfScope p(m, PGMI_K_LAYERNORM, 0, 2.0 * M * D * 4);
+              launch_layernorm16(m->x, m->lna_w, m->lna_b, M, D, m->ln_eps, m->h16, m->h16_plane, 1, s); }
+            return wide_head_rows(m, M, nullptr, nullptr, dst);
+        }
+        { ProfScope p(m, PGMI_K_HEAD, 2.0 * M * D * V, 0);
+          launch_layernorm(m->x, m->lna_w, m->lna_b, M, D, m->ln_eps, m->h, s);
+          launch_vocab_logsoftmax(m->h, m->gpt_head_w, m->gpt_zero, M, D, V, m->lp, m->nonfinite, s); }
+        PGMI_HIP(hipMemcpyAsync(dst, m->lp, (size_t)M * V * 4, hipMemcpyDeviceToHost, s));
+        return PGMI_OK;
+    });
+    return rc ? rc : check_nonfinite(m);
+}
+
+int pgmi_gpt_sequence_loglik(pgmi_model* m, const int32_t* tokens, const int32_t* lens, int B, int T, double* sum, int32_t* n_targets) {
+    if (!m || !tokens || !lens || !sum || B <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
+    if (T < 2) { set_error("rows of %d tokens: the model needs at least one input and one target token", T); return PGMI_EINVAL; }
+    const int Ti = T - 1;                                           // the model reads tokens[:, :T-1]; targets are tokens[:, 1:]
+    int rc = gpt_check(m, Ti);
+    if (!rc) rc = check_vocab(tokens, B, T, m->cfg.vocab);
+    if (rc) return rc;
+    for (int b = 0; b < B; ++b)
+        if (lens[b] < 2 || lens[b] > T) { set_error("row %d of this call: length %d outside [2, T = %d]", b, lens[b], T); return PGMI_EINVAL; }
+    const pgmi_config& c = m->cfg;
+    const int D = c.embed_dim, V = c.vocab;
+    std::vector<int32_t> in((size_t)B * Ti), idx, tgt, off;
+    for (int b = 0; b < B; ++b) memcpy(&in[(size_t)b * Ti], tokens + (size_t)b * T, (size_t)Ti * 4);
+    PGMI_HIP(hipSetDevice(m->device));
+    hipStream_t s = m->stream;
+    rc = for_each_chunk(m, B, Ti, [&](int b0, int bc) {
+        // the rows that have a target, in (sequence, position) order; sequence b owns [off[b], off[b+1])
+        idx.clear(); tgt.clear(); off.assign(1, 0);
+        for (int b = 0; b < bc; ++b) {
+            const int32_t* row = tokens + (size_t)(b0 + b) * T;
+            for (int t = 0; t + 1 < lens[b0 + b]; ++t) {
+                idx.push_back(b * Ti + t);
+                tgt.push_back(row[t + 1]);
+            }
+            off.push_back((int32_t)idx.size());
+        }
+        const int R = (int)idx.size();
+        PGMI_HIP(hipMemcpyAsync(m->tokens, in.data() + (size_t)b0 * Ti, (size_t)bc * Ti * 4, hipMemcpyHostToDevice, s));
+        PGMI_HIP(hipMemcpyAsync(m->row_idx, idx.data(), (size_t)R * 4, hipMemcpyHostToDevice, s));
+        PGMI_HIP(hipMemcpyAsync(m->aux_i, tgt.data(), (size_t)R * 4, hipMemcpyHostToDevice, s));
+        PGMI_HIP(hipMemcpyAsync(m->kv_len, off.data(), (size_t)(bc + 1) * 4, hipMemcpyHostToDevice, s));
+        int rc = run_gpt_body(m, bc, Ti);
+        if (rc) return rc;
+        { ProfScope p(m, PGMI_K_EMBED, 0, 2.0 * R * D * 4);
+          launch_gather_rows(m->x, m->row_idx, R, D, m->g, s); }                 // pad rows and last rows never reach the head
+        if (wide_head(c)) {
+            { ProfScope p(m, PGMI_K_LAYERNORM, 0, 2.0 * R * D * 4);
+              launch_layernorm16(m->g, m->lna_w, m->lna_b, R, D, m->ln_eps, m->h16, m->h16_plane, 1, s); }
+            rc = wide_head_rows(m, R, m->aux_i, m->denom, nullptr);
+            if (rc) return rc;
+        } else {
+            ProfScope p(m, PGMI_K_HEAD, 2.0 * R * D * V, 0);
+            launch_layernorm(m->g, m->lna_w, m->lna_b, R, D, m->ln_eps, m->h, s);
+            launch_vocab_logsoftmax(m->h, m->gpt_head_w, m->gpt_zero, R, D, V, m->lp, m->nonfinite, s);
+            launch_pppl_pick(m->lp, m->aux_i, R, V, m->denom, s);
+        }
+        launch_seq_sum(m->denom, m->kv_len, bc, m->gpt_sum, s);
+        PGMI_HIP(hipGetLastError());
+        PGMI_HIP(hipMemcpyAsync(sum + b0, m->gpt_sum, (size_t)bc * sizeof(double), hipMemcpyDeviceToHost, s));
+        return PGMI_OK;
+    });
+    if (rc) return rc;
+    if (n_targets)
+        for (int b = 0; b < B; ++b) n_targets[b] = lens[b] - 1;
+    return check_nonfinite(m);
+}
+
+}  // extern "C"

@@ -28,7 +28,7 @@ int check_cfg(const pgmi_config* c) {
     if (!c) { set_error("null config"); return PGMI_EINVAL; }
     if (c->abi_version != PGMI_ABI_VERSION) { set_error("ABI version mismatch: got %d, library is %d", c->abi_version, PGMI_ABI_VERSION); return PGMI_EINVAL; }
     if (c->arch != PGMI_ARCH_ESM1B && c->arch != PGMI_ARCH_ESM2 && c->arch != PGMI_ARCH_TRANCEPTION && c->arch != PGMI_ARCH_MSA &&
-        c->arch != PGMI_ARCH_PROGEN2) { set_error("unknown arch %d", c->arch); return PGMI_EINVAL; }
+        c->arch != PGMI_ARCH_PROGEN2 && c->arch != PGMI_ARCH_GPT) { set_error("unknown arch %d", c->arch); return PGMI_EINVAL; }
     if (c->layers <= 0 || c->embed_dim <= 0 || c->heads <= 0 || c->ffn_dim <= 0) { set_error("non-positive model dimension"); return PGMI_EINVAL; }
     {
         // head_dim 64 natively; smaller head dims (ESM2 8M/35M/150M: 16/24/32) run zero-padded to 64 lanes per head;
@@ -36,10 +36,11 @@ int check_cfg(const pgmi_config* c) {
         const int dh = c->embed_dim / c->heads;
         // ProGen2: any even head_dim up to 256, zero-padded to one (<= 64), two (<= 128) or four (<= 256) slot groups per head
         // (api_progen2.hip)
-        const bool esm = c->arch == PGMI_ARCH_ESM1B || c->arch == PGMI_ARCH_ESM2;
         const bool pg2 = c->arch == PGMI_ARCH_PROGEN2;
+        // causal decoder: ESM2's layout (RITA XL: head_dim 128)
+        const bool esm_layout = c->arch == PGMI_ARCH_ESM1B || c->arch == PGMI_ARCH_ESM2 || c->arch == PGMI_ARCH_GPT;
         const bool ok = c->embed_dim % c->heads == 0 &&
-                        (dh == kHeadDim || (dh < kHeadDim && dh % 2 == 0 && esm) || (dh == 2 * kHeadDim && esm) ||
+                        (dh == kHeadDim || (dh < kHeadDim && dh % 2 == 0 && esm_layout) || (dh == 2 * kHeadDim && esm_layout) ||
                          (pg2 && dh % 2 == 0 && dh <= 4 * kHeadDim));
         if (pg2 && !ok && c->embed_dim % c->heads == 0 && dh > 4 * kHeadDim) {
             set_error("unsupported head_dim %d (embed_dim %d / heads %d): ProGen2 runs even head dims up to 256", dh, c->embed_dim, c->heads);
@@ -59,6 +60,10 @@ int check_cfg(const pgmi_config* c) {
         if (c->heads % 8) { set_error("ProGen2 needs the number of heads to be a multiple of 8 (mp_num = 8), got %d", c->heads); return PGMI_EINVAL; }
         if (c->precision != PGMI_PREC_F16X3) { set_error("ProGen2 is available in precision f16x3 only"); return PGMI_EINVAL; }
         if (c->max_positions <= 0) { set_error("ProGen2 needs max_positions = n_positions"); return PGMI_EINVAL; }
+    } else if (c->arch == PGMI_ARCH_GPT) {
+        if (c->vocab < 2) { set_error("causal decoder vocab must be at least 2, got %d", c->vocab); return PGMI_EINVAL; }
+        if (c->precision != PGMI_PREC_F16X3) { set_error("the causal decoder (RITA / ProtGPT2) is available in precision f16x3 only"); return PGMI_EINVAL; }
+        if (c->max_positions <= 0) { set_error("the causal decoder needs max_positions = n_positions / max_seq_len"); return PGMI_EINVAL; }
     } else if (c->vocab != PGMI_VOCAB) { set_error("vocab must be %d", PGMI_VOCAB); return PGMI_EINVAL; }
     if (c->arch == PGMI_ARCH_ESM1B && c->max_positions <= 0) { set_error("ESM-1b arch needs max_positions"); return PGMI_EINVAL; }
     if (c->arch == PGMI_ARCH_MSA) {
@@ -189,6 +194,7 @@ int64_t pgmi_weight_count(const pgmi_config* c) {
     }
     if (c->arch == PGMI_ARCH_PROGEN2)        // include/pgmi.h: the ProGen2 blob
         return V * D + (int64_t)c->layers * (2 * D + 3 * D * D + D * D + (F * D + F) + (D * F + D)) + 2 * D + V * D + V;
+    if (c->arch == PGMI_ARCH_GPT) return -1;      // the blob depends on pos_kind: pgmi_gpt_weight_count
     if (c->arch == PGMI_ARCH_MSA) {
         const int64_t attn = 2 * D + 4 * (D * D + D);
         return V * D + (int64_t)(c->max_positions + 2) * D + 1024 * D + 2 * D +
@@ -206,6 +212,11 @@ int pgmi_model_create(const pgmi_config* cfg, const float* w, int64_t n_weights,
     if (cfg && cfg->arch == PGMI_ARCH_PROGEN2) {
         if (out) *out = nullptr;
         set_error("ProGen2 models are created with pgmi_pg2_model_create (it takes rotary_dim)");
+        return PGMI_EINVAL;
+    }
+    if (cfg && cfg->arch == PGMI_ARCH_GPT) {
+        if (out) *out = nullptr;
+        set_error("causal decoder models are created with pgmi_gpt_model_create (it takes pos_kind)");
         return PGMI_EINVAL;
     }
     return model_create(cfg, w, n_weights, device, out, 0);
@@ -245,7 +256,8 @@ static int alloc_workspace(pgmi_model* m) {
         alloc(&m->xt, R * D);
         alloc(&m->msa_kv_len, (size_t)2048);
     }
-    alloc(&m->lp, R * V);
+    // the wide causal-decoder head writes its full rows per head chunk (api_gpt.hip): R * V would be ~20 GB at V = 50 257
+    alloc(&m->lp, (c.arch == PGMI_ARCH_GPT && V > kWave ? (size_t)m->gpt_head_rows : R) * V);
     alloc(&m->denom, R);
     alloc(&m->tokens, R);
     alloc(&m->pos_idx, R);
@@ -258,14 +270,17 @@ static int alloc_workspace(pgmi_model* m) {
     return PGMI_OK;
 }
 
-// pgmi_model_create and pgmi_pg2_model_create; rotary_dim is ProGen2's (0 for every other arch)
-int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int device, pgmi_model** out, int rotary_dim) {
+// pgmi_model_create, pgmi_pg2_model_create and pgmi_gpt_model_create; arch_arg is ProGen2's rotary_dim or the causal decoder's
+// pos_kind (0 for every other arch)
+int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int device, pgmi_model** out, int arch_arg) {
     if (!out) { set_error("null out"); return PGMI_EINVAL; }
     *out = nullptr;
     int rc = check_cfg(cfg);
     if (rc) return rc;
-    if (!w || n_weights != pgmi_weight_count(cfg)) {
-        set_error("weight blob has %lld elements, config needs %lld", (long long)n_weights, (long long)pgmi_weight_count(cfg));
+    const int64_t need = cfg->arch == PGMI_ARCH_GPT ? gpt_weight_count(cfg, arch_arg) : pgmi_weight_count(cfg);
+    if (need < 0) { set_error("causal decoder pos_kind %d: must be PGMI_GPT_POS_ROTARY or PGMI_GPT_POS_LEARNED", arch_arg); return PGMI_EINVAL; }
+    if (!w || n_weights != need) {
+        set_error("weight blob has %lld elements, config needs %lld", (long long)n_weights, (long long)need);
         return PGMI_EINVAL;
     }
     const int ndev = pgmi_device_count();
@@ -285,7 +300,8 @@ int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int 
     switch (cfg->arch) {
         case PGMI_ARCH_TRANCEPTION: rc = create_tranception(m, cfg, w, n_weights); break;
         case PGMI_ARCH_MSA: rc = create_msa(m, cfg, w, n_weights); break;
-        case PGMI_ARCH_PROGEN2: rc = create_progen2(m, cfg, w, n_weights, rotary_dim); break;
+        case PGMI_ARCH_PROGEN2: rc = create_progen2(m, cfg, w, n_weights, arch_arg); break;
+        case PGMI_ARCH_GPT: rc = create_gpt(m, cfg, w, n_weights, arch_arg); break;
         default: rc = create_esm(m, cfg, w, n_weights);
     }
     if (!rc) rc = alloc_workspace(m);

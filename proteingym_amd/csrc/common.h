@@ -90,6 +90,14 @@ void launch_seq_loglik_ragged(const float* lp, const int32_t* tokens, const int3
                               const int32_t* row0, const int32_t* n, const int32_t* flip, float alpha, float* out, hipStream_t s);
 // ProGen2: out[b] = sum over t < n_kept[b] of lp[b*T + t, col[b*T + t]] (lp [B*T,V], one wave per sequence, fixed lane order)
 void launch_pg2_seq_loglik(const float* lp, const int32_t* col, const int32_t* n_kept, int B, int T, int V, float* out, hipStream_t s);
+// causal decoder (api_gpt.hip): x[row] = E[tokens[row]] + P[row % T]
+void launch_embed_learned(const int32_t* tokens, const float* E, const float* P, int rows, int T, int D, float* x, hipStream_t s);
+// log-softmax over V > 64 columns of fp32 logits [rows][ldl] (ldl % 4 == 0, pad columns excluded by index): out[r] = log p(tgt[r])
+// when tgt != nullptr, else the full rows out [rows][V]
+void launch_wide_logsoftmax(const float* logits, int ldl, int rows, int V, const int32_t* tgt, float* out, int32_t* nonfinite,
+                            hipStream_t s);
+// out[b] = sum of terms[off[b] .. off[b+1]) in double, left to right
+void launch_seq_sum(const float* terms, const int32_t* off, int B, double* out, hipStream_t s);
 void launch_score_mutants(const float* table, int V, const int32_t* sub_pos, const int32_t* sub_wt,
                           const int32_t* sub_mt, const int64_t* mut_off, int64_t n_mut,
                           double* scores, hipStream_t s);

@@ -541,4 +541,108 @@ void launch_pppl_sum(const float* terms, const int64_t* rp, const int32_t* sid, 
     hipLaunchKernelGGL(pppl_sum_kernel, dim3((J + 127) / 128), dim3(128), 0, s, terms, rp, sid, J, first, out);
 }
 
+
+// ---- causal decoder (api_gpt.hip) -----------------------------------------------------------------------------------------
+// x[row] = E[tokens[row]] + P[row % T]: GPT-2's inputs_embeds + position_embeds with position ids 0..T-1 (one wave per row)
+__global__ __launch_bounds__(256) void embed_learned_kernel(const int32_t* __restrict__ tokens, const float* __restrict__ E,
+                                                            const float* __restrict__ P, int rows, int T, int D, float* __restrict__ x) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const f32x4* e = reinterpret_cast<const f32x4*>(E + (size_t)tokens[row] * D);
+    const f32x4* p = reinterpret_cast<const f32x4*>(P + (size_t)(row % T) * D);
+    f32x4* xo = reinterpret_cast<f32x4*>(x + (size_t)row * D);
+    for (int i = lane; i < D / 4; i += 64) xo[i] = e[i] + p[i];
+}
+void launch_embed_learned(const int32_t* tokens, const float* E, const float* P, int rows, int T, int D, float* x, hipStream_t s) {
+    hipLaunchKernelGGL(embed_learned_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, tokens, E, P, rows, T, D, x);
+}
+
+// Log-softmax over a wide vocabulary (V > 64: ProtGPT2's 50 257).  One 256-thread workgroup per row of fp32 logits [rows][ldl]
+// (ldl % 4 == 0; columns V .. ldl-1 are padding, excluded by index, never by value).  The row is read once: thread i takes the
+// float4s i, i + 256, ... and keeps a running max m and s = sum exp(x - m) in double (rescaled when m grows); the 256 (m, s) pairs
+// are then combined in a fixed tree order in double.  Every order depends on V alone, so a row's bits do not depend on the other
+// rows of the launch.  tgt != nullptr: out[r] = log p(column tgt[r]) (scoring); else out[r * V + c] for every c < V.
+__device__ __forceinline__ void lse_merge(float& m, double& s, float m2, double s2) {
+    const float M = fmaxf(m, m2);
+    const double a = s == 0.0 ? 0.0 : s * exp((double)m - (double)M);
+    const double b = s2 == 0.0 ? 0.0 : s2 * exp((double)m2 - (double)M);
+    m = M;
+    s = a + b;
+}
+__global__ __launch_bounds__(256) void wide_logsoftmax_kernel(const float* __restrict__ logits, int ldl, int V,
+                                                              const int32_t* __restrict__ tgt, float* __restrict__ out,
+                                                              int32_t* __restrict__ nonfinite) {
+    __shared__ float sm[256];
+    __shared__ double ss[256];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const float* row = logits + (size_t)r * ldl;
+    const f32x4* row4 = reinterpret_cast<const f32x4*>(row);
+    float m = -INFINITY;
+    double s = 0.0;
+    for (int i = tid; i < (V + 3) / 4; i += 256) {
+        const f32x4 v = row4[i];
+        const int c0 = 4 * i;
+        float mx = m;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (c0 + k < V) mx = fmaxf(mx, v[k]);
+        if (mx > m) {
+            s = s == 0.0 ? 0.0 : s * (double)__expf(m - mx);
+            m = mx;
+        }
+        float e = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (c0 + k < V) e += __expf(v[k] - m);
+        s += (double)e;
+    }
+    sm[tid] = m;
+    ss[tid] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) {
+            float a = sm[tid];
+            double b = ss[tid];
+            lse_merge(a, b, sm[tid + o], ss[tid + o]);
+            sm[tid] = a;
+            ss[tid] = b;
+        }
+        __syncthreads();
+    }
+    const double lse = (double)sm[0] + log(ss[0]);
+    bool bad = false;
+    if (tgt) {
+        if (tid == 0) {
+            const float res = (float)((double)row[tgt[r]] - lse);
+            out[r] = res;
+            bad = !(fabsf(res) <= 3.0e38f);
+        }
+    } else {
+        for (int c = tid; c < V; c += 256) {
+            const float res = (float)((double)row[c] - lse);
+            out[(size_t)r * V + c] = res;
+            bad |= !(fabsf(res) <= 3.0e38f);
+        }
+    }
+    if (nonfinite && bad) atomicOr(nonfinite, 1);             // NaN/inf: fp16 overflow upstream
+}
+void launch_wide_logsoftmax(const float* logits, int ldl, int rows, int V, const int32_t* tgt, float* out, int32_t* nonfinite,
+                            hipStream_t s) {
+    if (rows <= 0) return;
+    hipLaunchKernelGGL(wide_logsoftmax_kernel, dim3(rows), dim3(256), 0, s, logits, ldl, V, tgt, out, nonfinite);
+}
+
+// out[b] = sum of terms[off[b] .. off[b+1]) in double, left to right: one thread per sequence, so the order is the sequence's own
+__global__ void seq_sum_kernel(const float* __restrict__ terms, const int32_t* __restrict__ off, int B, double* __restrict__ out) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double acc = 0.0;
+    for (int i = off[b]; i < off[b + 1]; ++i) acc += (double)terms[i];
+    out[b] = acc;
+}
+void launch_seq_sum(const float* terms, const int32_t* off, int B, double* out, hipStream_t s) {
+    hipLaunchKernelGGL(seq_sum_kernel, dim3((B + 127) / 128), dim3(128), 0, s, terms, off, B, out);
+}
+
 }  // namespace pgmi

@@ -6,6 +6,8 @@
 //                        pseudo-ppl libraries
 //   api_tranception.hip  Tranception weights and forward, dense and prefix-shared; token log-probs and sequence log-likelihoods
 //   api_progen2.hip      ProGen2 weights and forward (parallel residual, GPT-J rotary); token log-probs and sequence log-likelihoods
+//   api_gpt.hip          causal decoder (RITA, ProtGPT2) weights and forward, narrow and wide LM heads; token log-probs and sequence
+//                        log-likelihoods
 //   api_msa.hip          MSA Transformer weights and forward (tied row attention, column attention)
 //   api_host.hip         host-only entries: mutant parser, table -> scores, optimal window
 //   api_ops.hip          single-op and timing entries for the numerics tests and the A/B scripts
@@ -77,6 +79,12 @@ struct pgmi_model {
     int pg2_rotary = 0;
     float *pg2_head_w = nullptr, *pg2_head_b = nullptr, *pg2_aa_w = nullptr, *pg2_aa_b = nullptr;
     float *pg2_zero = nullptr, *pg2_slopes = nullptr;
+    // causal decoder (api_gpt.hip): PGMI_GPT_POS_*, the head -- fp32 lm_head [V,D] (V <= 64) or the f16x3 planes of wte zero-padded to
+    // gpt_Vp = roundup(V, 64) rows -- and the wide head's fp32 logits [gpt_head_rows][gpt_Vp]; per-sequence sums; zero bias / slopes
+    int gpt_pos = 0, gpt_Vp = 0, gpt_head_rows = 0;
+    float *gpt_head_w = nullptr, *gpt_logits = nullptr, *gpt_zero = nullptr, *gpt_slopes = nullptr;
+    W16 gpt_head16;
+    double* gpt_sum = nullptr;
     // MSA Transformer
     float* msa_pe = nullptr;                            // msa_position_embedding [1024, D]
     float* xt = nullptr;                                // residual stream in column-major token order
@@ -208,10 +216,11 @@ int linear(pgmi_model* m, const float* in32, const unsigned short* in16, size_t 
            size_t out_plane, int M, int N, int K, int epi);
 int check_nonfinite(pgmi_model* m);
 int reset_pad_keys(pgmi_model* m, int B, int T);
-int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int device, pgmi_model** out, int rotary_dim);
+int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int device, pgmi_model** out, int arch_arg);
 // api_esm.hip
 int create_esm(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights);
 int ensure_rotary(pgmi_model* m, int T);
+int upload_rotate_half(pgmi_model* m, int n);       // ESM2's rotary tables for positions 0..n-1 (rotate_half_slot layout)
 int run_encoder(pgmi_model* m, int B, int T, const int32_t* keep = nullptr, int n_keep = 0, bool* compacted = nullptr);
 int run_head(pgmi_model* m, int R, const int32_t* row_idx);
 int run_rows(pgmi_model* m, int B, int T, int R, const int32_t* row_idx);
@@ -220,6 +229,9 @@ int create_tranception(pgmi_model* m, const pgmi_config* cfg, const float* w, in
 int run_tranception(pgmi_model* m, int B, int T);
 // api_progen2.hip
 int create_progen2(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights, int rotary_dim);
+// api_gpt.hip
+int create_gpt(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights, int pos_kind);
+int64_t gpt_weight_count(const pgmi_config* c, int pos_kind);
 // api_msa.hip
 int create_msa(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights);
 int run_msa(pgmi_model* m, int R, int C, int keep_col = -1, bool* compacted = nullptr);
@@ -248,6 +260,18 @@ struct BlobCursor {
         return rc;
     }
 };
+
+// Attention slot of model dim `col` in the rotate-half layout (ESM2, RITA): every head owns 64 lanes of the attention kernels; dim j
+// of a head sits in slot j (first half) or 32 + (j - dh/2) (second half) so that rotary pairs (j, j + dh/2) are the kernels' pairs
+// (i, i + 32).  dh == 64 is the identity layout; smaller heads leave zero slots (zero weight rows -> q,k,v slots exactly 0 -> scores
+// and context unchanged).  head_dim 128: a head is two slot groups; group g in {0,1} holds dims 32 g + i (slots i < 32) and
+// 64 + 32 g + i (slots 32 + i), so the rotary partners (j, j + 64) are again the kernels' pairs (i, i + 32) inside ONE 64-column wave
+// tile of the QKV epilogue.
+inline size_t rotate_half_slot(size_t col, size_t dh) {
+    const size_t h = col / dh, j = col % dh;
+    if (dh > 64) return (2 * h + ((j >> 5) & 1)) * 64 + ((j >> 6) << 5) + (j & 31);
+    return h * 64 + (j < dh / 2 ? j : 32 + (j - dh / 2));
+}
 
 // Fused [3 Da, D] QKV projection from the blob's q | k | v blocks (each a [D, D] weight, followed by a [D] bias when bq is
 // given): row o of block k goes to row k Da + slot(o), the q rows pre-scaled by qscale.  Rows no model dim maps to keep their

@@ -1,0 +1,28 @@
+"""Drop-in for ``proteingym/baselines/protgpt2/compute_fitness.py`` on MI355X.
+
+Same flags, same assay resolution (row --DMS_index of the reference file), same output file ``<output_scores_folder>/<DMS_id>.csv``
+with the columns the reference writes (mutated_sequence, ProtGPT2_score, DMS_score).  Scores are the reference's calc_fitness: the
+sum over (chunk, direction) of -mean CE divided by 2 * n_chunks (proteingym_amd/causal_lm.py).  Additive flags: --tokenizer_path
+(the reference hard-codes its tokenizer directory; default here: the model directory), --device, --max_rows.
+"""
+from __future__ import annotations
+
+import argparse
+
+from . import causal_lm as clm
+
+
+def parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description="ProtGPT2 scoring (HIP, MI355X)")
+    clm.add_common_flags(p, "--ProtGPT2_model_name_or_path", "ProtGPT2 checkpoint directory (config.json + pytorch_model.bin / model.safetensors)")
+    return p
+
+
+def main(argv=None):
+    args = parser().parse_args(argv)
+    return clm.score_assay(args, args.ProtGPT2_model_name_or_path, "ProtGPT2", "ProtGPT2_score",
+                           ["mutated_sequence", "ProtGPT2_score", "DMS_score"])
+
+
+if __name__ == "__main__":
+    main()

@@ -403,9 +403,9 @@ def expected_keys(n_layer):
     return keys
 
 
-def load_checkpoint(checkpoint_dir: str):
-    """config.json + pytorch_model.bin / model.safetensors (score_tranception_proteingym.py:79,100).
-    Returns (cfg dict, flat fp32 blob in the ABI order of include/pgmi.h)."""
+def load_hf_directory(checkpoint_dir: str):
+    """A Hugging Face model directory: (config.json as a dict, state dict of fp32 numpy arrays from pytorch_model.bin or
+    model.safetensors)."""
     c = json.load(open(os.path.join(checkpoint_dir, "config.json")))
     bin_path = os.path.join(checkpoint_dir, "pytorch_model.bin")
     if os.path.exists(bin_path):
@@ -414,6 +414,13 @@ def load_checkpoint(checkpoint_dir: str):
     else:
         from safetensors.numpy import load_file
         sd = load_file(os.path.join(checkpoint_dir, "model.safetensors"))
+    return c, sd
+
+
+def load_checkpoint(checkpoint_dir: str):
+    """config.json + pytorch_model.bin / model.safetensors (score_tranception_proteingym.py:79,100).
+    Returns (cfg dict, flat fp32 blob in the ABI order of include/pgmi.h)."""
+    c, sd = load_hf_directory(checkpoint_dir)
     if "lm_head.weight" not in sd:                        # tied to wte (_keys_to_ignore_on_load_missing, :635)
         sd["lm_head.weight"] = sd["transformer.wte.weight"]
     n_embd, n_head, n_layer = int(c["n_embd"]), int(c["n_head"]), int(c["n_layer"])

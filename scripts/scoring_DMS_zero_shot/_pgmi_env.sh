@@ -50,3 +50,10 @@ pgmi_progen2() {
         --DMS_reference_file_path "${mapping}" --DMS_data_folder "${folder}" --DMS_index "${DMS_index:=0}" \
         --output_scores_folder "${output_scores_folder}" "$@"
 }
+# pgmi_causal_lm <module> <model flag> <model path> <mapping csv> <data folder> [more flags]: assay ${DMS_index} through the RITA /
+# ProtGPT2 scorers
+pgmi_causal_lm() {
+    local mod="$1" flag="$2" path="$3" mapping="$4" folder="$5"; shift 5
+    pgmi_run "${mod}" "${flag}" "${path}" --DMS_reference_file_path "${mapping}" --DMS_data_folder "${folder}" \
+        --DMS_index "${DMS_index:=0}" --output_scores_folder "${output_scores_folder}" "$@"
+}
