@@ -53,6 +53,9 @@ extern "C" {
 #define PGMI_ARCH_GPT 6
 #define PGMI_GPT_POS_ROTARY 0   /* RITA (proteingym/baselines/rita/rita_modeling.py): rotate-half rotary, untied lm_head */
 #define PGMI_GPT_POS_LEARNED 1  /* GPT-2 (transformers GPT2LMHeadModel): wpe added to wte, lm_head tied to wte */
+/* ESM C (ESM Cambrian, proteingym/baselines/evoscale/esm/models/esmc.py): pre-LN encoder with q/k LayerNorm, SwiGLU, scaled residual;
+ * created with pgmi_model_create, scored with pgmi_token_logprobs / pgmi_masked_logprobs (see the ESM C section below) */
+#define PGMI_ARCH_ESMC 7
 
 /* GEMM operand precision.  Residual stream, LayerNorm statistics, softmax and every
  * accumulator are fp32 in all modes. */
@@ -68,6 +71,7 @@ extern "C" {
 #define PGMI_TOK_MASK 32
 #define PGMI_VOCAB 33
 #define PGMI_PG2_VOCAB 32  /* ProGen2 (progen2/tokenizer.json) */
+#define PGMI_ESMC_VOCAB 64 /* ESM C: the ESM token ids above, 64 logits columns (33..63 untrained, inside the log-softmax) */
 
 typedef struct pgmi_config {
     int32_t abi_version;          /* = PGMI_ABI_VERSION */
@@ -238,9 +242,16 @@ int pgmi_set_option(const char* name, int64_t value);
 int pgmi_op_layernorm(int device, const float* x, const float* w, const float* b,
                       int rows, int D, float eps, float* y);               /* modules.py:80-81 */
 int pgmi_op_gemm(int device, int precision, const float* A, const float* W, const float* bias,
-                 const float* residual, int M, int N, int K, int epilogue /*0 none,1 gelu,2 squared relu,3 tanh-gelu; +256 (f16x3):
-                 the split-fp16-plane output epilogue, its planes returned rebuilt as fp32*/,
-                 float* C);          /* C = epi(A W^T + bias) + residual; modules.py:134-140 */
+                 const float* residual, int M, int N, int K, int epilogue /*0 none,1 gelu,2 squared relu,3 tanh-gelu,4 SwiGLU;
+                 +256 (f16x3): the split-fp16-plane output epilogue, its planes returned rebuilt as fp32*/,
+                 float* C);          /* C = epi(A W^T + bias) + residual; modules.py:134-140.
+                                      * SwiGLU (4 + 256 only, f16x3, N % 64 == 0): W and bias in blocks of 64 rows = 32 gate rows then
+                                      * 32 up rows; C [M, N/2] with C[:, 32 b + i] = silu(gate row 64 b + i) * (up row 64 b + 32 + i) */
+/* ESM C's QK-LayerNorm prep pass on qkv [B*T, 3D] (D = 64 H <= 2048): qk [B*T, 2D] = the attention's q | k operands rebuilt as fp32:
+ * LayerNorm(q) * q_w (no bias, eps 1e-5) rotated by rotate-half rotary (head_dim 64) and times log2(e), then the same for k without
+ * the factor; v [B*T, D] = the v operand.  Either output may be NULL.  iters > 0: *ms = mean time of that many further launches. */
+int pgmi_op_qkln_prep(int device, const float* qkv, const float* q_w, const float* k_w, int B, int T, int H, int iters, float* qk,
+                      float* v, double* ms);
 int pgmi_op_attention(int device, int precision, const float* qkv, const int32_t* kv_len,
                       int B, int T, int H, int rotary, float* ctx);
                                      /* multihead_attention.py:354-395; qkv [B*T,3*H*64], q pre-scaled */
@@ -346,6 +357,22 @@ int64_t pgmi_gpt_weight_count(const pgmi_config* cfg, int pos_kind);
 int pgmi_gpt_model_create(const pgmi_config* cfg, int pos_kind, const float* weights, int64_t n_weights, int device, pgmi_model** out);
 int pgmi_gpt_token_logprobs(pgmi_model* m, const int32_t* tokens, int B, int T, float* out);
 int pgmi_gpt_sequence_loglik(pgmi_model* m, const int32_t* tokens, const int32_t* lens, int B, int T, double* sum, int32_t* n_targets);
+
+/* ---- ESM C (arch PGMI_ARCH_ESMC; vocab 64, head_dim 64, embed_dim <= 2048, ffn_dim = the SwiGLU hidden width F, precision f16x3) --
+ * Per block: x += out_proj(attn(x)) / s; x += ffn(x) / s with s = sqrt(layers / 36) (transformer_stack.py:50, blocks.py:150-162).
+ * attn: LayerNorm (with bias) -> QKV without bias -> q, k each LayerNorm-ed over the whole width D without bias (before the head
+ * split) -> rotate-half rotary per 64-dim head (base 1e4) -> softmax(q k^T / 8) v -> out_proj without bias.  ffn: LayerNorm (with
+ * bias) -> W1 -> silu(gate) * up -> W2, both bias-free.  Then a LayerNorm without bias and the head Linear(D,D) + erf-GELU +
+ * LayerNorm + Linear(D,64); log-softmax over all 64 columns.  Token ids are ESM's (PGMI_TOK_*); <pad> keys are masked.
+ * Weight blob order (fp32, nn.Linear layout [out,in], names as in ESMC.state_dict()):
+ *   embed.weight [64,D];
+ *   per block i (transformer.blocks.i.): attn.layernorm_qkv.0.{weight,bias} [D]; attn.layernorm_qkv.1.weight [3D,D] (q | k | v rows);
+ *     attn.q_ln.weight [D]; attn.k_ln.weight [D]; attn.out_proj.weight [D,D]; ffn.0.{weight,bias} [D];
+ *     ffn.1.weight [2F,D] with its rows in SwiGLU block order: for b < F/32, the gate rows 32b .. 32b+31 (the first F rows of the
+ *     checkpoint) then the up rows F+32b .. F+32b+31 (the pgmi_op_gemm SwiGLU layout); ffn.3.weight [D,F];
+ *   transformer.norm.weight [D]; sequence_head.0.{weight [D,D], bias}; sequence_head.2.{weight,bias}; sequence_head.3.{weight [64,D], bias [64]}.
+ * pgmi_weight_count gives its size.  pgmi_masked_logprobs serves this arch (out [B,64]); ready-made rows carry their own window (ESM C's
+ * window rule differs from pgmi_optimal_window, so pgmi_assay_create refuses this arch). */
 
 /* ---- MSA Transformer (arch PGMI_ARCH_MSA; vocab 33, head_dim 64, precision f16x3) --------------------
  * Replaces MSATransformer.forward (proteingym/baselines/esm/esm/model/msa_transformer.py:146-205; tied

@@ -15,6 +15,7 @@ ABI_VERSION = 4
 ARCH_ESM1B, ARCH_ESM2, ARCH_TRANCEPTION = 1, 2, 3
 ARCH_PROGEN2 = 5
 ARCH_GPT = 6
+ARCH_ESMC = 7
 GPT_POS_ROTARY, GPT_POS_LEARNED = 0, 1
 PREC_FP32, PREC_BF16, PREC_F16X3 = 0, 1, 2
 PRECISIONS = {"fp32": PREC_FP32, "bf16": PREC_BF16, "f16x3": PREC_F16X3}
@@ -92,6 +93,7 @@ SIGNATURES = [
     ("pgmi_bench_gemm", C.c_int, [C.c_int] * 9 + [_f64p]),
     ("pgmi_bench_gemm_ab", C.c_int, [C.c_int] * 7 + [_i32p, C.c_int, C.c_int, C.c_int, _f64p]),
     ("pgmi_op_attention", C.c_int, [C.c_int, C.c_int, _f32p, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),
+    ("pgmi_op_qkln_prep", C.c_int, [C.c_int, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p, _f64p]),
     ("pgmi_msa_token_logprobs", C.c_int, [C.c_void_p, _i32p, C.c_int, C.c_int, _f32p]),
     ("pgmi_msa_masked_logprobs", C.c_int, [C.c_void_p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, _i32p, C.c_int, _f32p]),
     ("pgmi_msa_cluster_counts", C.c_int, [C.c_int, C.POINTER(C.c_int8), C.c_int64, C.c_int64, C.c_int, C.c_double, _i32p, _f64p]),

@@ -194,6 +194,7 @@ int run_head(pgmi_model* m, int R, const int32_t* row_idx) {
 
 // Encoder + LM head where only the rows row_idx [R] (device) of the [B*T] outputs are read.  Result in m->lp [R,V].
 int run_rows(pgmi_model* m, int B, int T, int R, const int32_t* row_idx) {
+    if (m->cfg.arch == PGMI_ARCH_ESMC) return run_esmc_rows(m, B, T, R, row_idx);
     bool compacted = false;
     int rc = run_encoder(m, B, T, row_idx, R, &compacted);
     if (rc) return rc;
@@ -213,8 +214,7 @@ int pgmi_token_logprobs(pgmi_model* m, const int32_t* tokens, int B, int T, floa
     const int V = m->cfg.vocab;
     rc = for_each_chunk(m, B, T, [&](int b0, int bc) {
         PGMI_HIP(hipMemcpyAsync(m->tokens, tokens + (size_t)b0 * T, (size_t)bc * T * 4, hipMemcpyHostToDevice, m->stream));
-        int rc = run_encoder(m, bc, T);
-        if (!rc) rc = run_head(m, bc * T, nullptr);
+        int rc = run_rows(m, bc, T, bc * T, nullptr);        // all rows: run_encoder, then run_head (or ESM C's forward)
         if (rc) return rc;
         PGMI_HIP(hipMemcpyAsync(out + (size_t)b0 * T * V, m->lp, (size_t)bc * T * V * 4, hipMemcpyDeviceToHost, m->stream));
         return PGMI_OK;
@@ -224,6 +224,7 @@ int pgmi_token_logprobs(pgmi_model* m, const int32_t* tokens, int B, int T, floa
 
 int pgmi_masked_logprobs(pgmi_model* m, const int32_t* tokens, const int32_t* mask_pos, int B, int T, float* out) {
     if (!m || !tokens || !mask_pos || !out || B <= 0 || T <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
+    if (m->cfg.arch == PGMI_ARCH_ESMC && T + 31 > m->max_rows) { set_error("T=%d exceeds workspace rows %d", T, m->max_rows); return PGMI_EINVAL; }
     if (T > m->max_rows) { set_error("T=%d exceeds workspace rows %d", T, m->max_rows); return PGMI_EINVAL; }
     int rc = check_tokens(tokens, B, T);
     if (rc) return rc;
@@ -253,6 +254,7 @@ int pgmi_assay_create(pgmi_model* m, const int32_t* wt_tokens, int n_tok, const 
     if (!out) { set_error("null out"); return PGMI_EINVAL; }
     *out = nullptr;
     if (!m || !wt_tokens || n_tok <= 0 || P < 0 || (P > 0 && !positions) || window <= 0 || n_mut < 0) { set_error("bad argument"); return PGMI_EINVAL; }
+    if (m->cfg.arch == PGMI_ARCH_ESMC) { set_error("ESM C assays run through pgmi_masked_logprobs (their window rule is not pgmi_optimal_window)"); return PGMI_EINVAL; }
     for (int i = 0; i < n_tok; ++i)
         if (wt_tokens[i] < 0 || wt_tokens[i] >= PGMI_VOCAB || wt_tokens[i] == PGMI_TOK_PAD) { set_error("wt token %d invalid at %d", wt_tokens[i], i); return PGMI_EINVAL; }
     const int T = std::min(n_tok, window);

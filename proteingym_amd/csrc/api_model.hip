@@ -28,8 +28,17 @@ int check_cfg(const pgmi_config* c) {
     if (!c) { set_error("null config"); return PGMI_EINVAL; }
     if (c->abi_version != PGMI_ABI_VERSION) { set_error("ABI version mismatch: got %d, library is %d", c->abi_version, PGMI_ABI_VERSION); return PGMI_EINVAL; }
     if (c->arch != PGMI_ARCH_ESM1B && c->arch != PGMI_ARCH_ESM2 && c->arch != PGMI_ARCH_TRANCEPTION && c->arch != PGMI_ARCH_MSA &&
-        c->arch != PGMI_ARCH_PROGEN2 && c->arch != PGMI_ARCH_GPT) { set_error("unknown arch %d", c->arch); return PGMI_EINVAL; }
+        c->arch != PGMI_ARCH_PROGEN2 && c->arch != PGMI_ARCH_GPT && c->arch != PGMI_ARCH_ESMC) { set_error("unknown arch %d", c->arch); return PGMI_EINVAL; }
     if (c->layers <= 0 || c->embed_dim <= 0 || c->heads <= 0 || c->ffn_dim <= 0) { set_error("non-positive model dimension"); return PGMI_EINVAL; }
+    if (c->arch == PGMI_ARCH_ESMC) {
+        // the QK-LayerNorm prep pass holds a q / k row of D <= 2048 in registers; FC1's SwiGLU epilogue pairs 32-column blocks
+        if (c->precision != PGMI_PREC_F16X3) { set_error("ESM C is available in precision f16x3 only"); return PGMI_EINVAL; }
+        if (c->embed_dim % 32 || c->embed_dim != c->heads * kHeadDim) { set_error("ESM C needs head_dim 64 and d %% 32 == 0 (embed_dim %d, heads %d)", c->embed_dim, c->heads); return PGMI_EINVAL; }
+        if (c->embed_dim > 2048) { set_error("ESM C: embed_dim %d above the 2048 this build supports", c->embed_dim); return PGMI_EINVAL; }
+        if (c->ffn_dim % 32) { set_error("ESM C: the SwiGLU hidden width %d must be a multiple of 32", c->ffn_dim); return PGMI_EINVAL; }
+        if (c->vocab != PGMI_ESMC_VOCAB) { set_error("ESM C vocab must be %d", PGMI_ESMC_VOCAB); return PGMI_EINVAL; }
+        return PGMI_OK;
+    }
     {
         // head_dim 64 natively; smaller head dims (ESM2 8M/35M/150M: 16/24/32) run zero-padded to 64 lanes per head;
         // head_dim 128 (ESM2-15B: pretrained.py:387-394) as two 64-lane slot groups per head (see pgmi_model_create)
@@ -195,6 +204,7 @@ int64_t pgmi_weight_count(const pgmi_config* c) {
     if (c->arch == PGMI_ARCH_PROGEN2)        // include/pgmi.h: the ProGen2 blob
         return V * D + (int64_t)c->layers * (2 * D + 3 * D * D + D * D + (F * D + F) + (D * F + D)) + 2 * D + V * D + V;
     if (c->arch == PGMI_ARCH_GPT) return -1;      // the blob depends on pos_kind: pgmi_gpt_weight_count
+    if (c->arch == PGMI_ARCH_ESMC) return esmc_weight_count(c);
     if (c->arch == PGMI_ARCH_MSA) {
         const int64_t attn = 2 * D + 4 * (D * D + D);
         return V * D + (int64_t)(c->max_positions + 2) * D + 1024 * D + 2 * D +
@@ -302,6 +312,7 @@ int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int 
         case PGMI_ARCH_MSA: rc = create_msa(m, cfg, w, n_weights); break;
         case PGMI_ARCH_PROGEN2: rc = create_progen2(m, cfg, w, n_weights, arch_arg); break;
         case PGMI_ARCH_GPT: rc = create_gpt(m, cfg, w, n_weights, arch_arg); break;
+        case PGMI_ARCH_ESMC: rc = create_esmc(m, cfg, w, n_weights); break;
         default: rc = create_esm(m, cfg, w, n_weights);
     }
     if (!rc) rc = alloc_workspace(m);

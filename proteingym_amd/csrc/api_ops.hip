@@ -46,6 +46,12 @@ int pgmi_op_gemm(int device, int precision, const float* A, const float* W, cons
     // planes rebuilt as fp32 (tests: a row's bits through the half- and full-height items)
     const int epi = epilogue & 255;
     const bool split_planes = (epilogue & 256) != 0;
+    // EPI_SWIGLU: f16x3 split-plane output only (N % 64 == 0); C is then [M, N / 2]
+    if (epi == EPI_SWIGLU && (!split_planes || precision != PGMI_PREC_F16X3 || (N % 64))) {
+        for (void* p : pool) hipFree(p);
+        set_error("SwiGLU GEMM op: precision f16x3 with the split-plane output (epilogue 4 + 256), N %% 64 == 0");
+        return PGMI_EINVAL;
+    }
     if (split_planes && (precision == PGMI_PREC_FP32 || residual || (N % (precision == PGMI_PREC_F16X3 ? 32 : 4)))) {
         for (void* p : pool) hipFree(p);
         set_error("16-bit-plane GEMM op: f16x3 (N %% 32 == 0) or bf16 (N %% 4 == 0), no residual");
@@ -65,8 +71,9 @@ int pgmi_op_gemm(int device, int precision, const float* A, const float* W, cons
             if (split_planes) {
                 // the split-plane epilogue (the next GEMM's operand): run it, then rebuild fp32 = hi + lo 2^-11 from the K-interleaved planes
                 unsigned short* c16 = nullptr;
+                const int No = epi == EPI_SWIGLU ? N / 2 : N;              // output columns
                 rc = dev_alloc(pool, &c16, (size_t)M * N * 2);
-                if (!rc) rc = launch_gemm16(a16, (size_t)M * K, w16.p, w16.plane, dB, nullptr, nullptr, c16, (size_t)M * N, M, N, K, epi,
+                if (!rc) rc = launch_gemm16(a16, (size_t)M * K, w16.p, w16.plane, dB, nullptr, nullptr, c16, (size_t)M * No, M, N, K, epi,
                                             w16.out_scale, planes, bf, env_int("PGMI_GEMM_VARIANT", 0), nullptr);
                 if (!rc) {
                     std::vector<unsigned short> h((size_t)M * N * 2);
@@ -78,11 +85,11 @@ int pgmi_op_gemm(int device, int precision, const float* A, const float* W, cons
                             memcpy(&C[m * N + n], &u, 4);
                         }
                     for (size_t m = 0; m < (size_t)M && !rc && !bf; ++m)
-                        for (int n = 0; n < N; ++n) {
-                            const size_t o = ki_off(m, n, N);
+                        for (int n = 0; n < No; ++n) {
+                            const size_t o = ki_off(m, n, No);
                             _Float16 hi, lo;
                             memcpy(&hi, &h[o], 2); memcpy(&lo, &h[o + 32], 2);
-                            C[m * N + n] = (float)hi + (float)lo * (1.0f / kLoScale);
+                            C[m * No + n] = (float)hi + (float)lo * (1.0f / kLoScale);
                         }
                 }
                 for (void* p : pool) hipFree(p);
@@ -184,6 +191,72 @@ int pgmi_bench_gemm_ab(int device, int precision, int M, int N, int K, int epilo
 int pgmi_bench_gemm(int device, int precision, int M, int N, int K, int epilogue, int split_out, int variant,
                     int iters, double* ms_per_launch) {
     return pgmi_bench_gemm_ab(device, precision, M, N, K, epilogue, split_out, &variant, 1, 1, iters, ms_per_launch);
+}
+
+int pgmi_op_qkln_prep(int device, const float* qkv, const float* q_w, const float* k_w, int B, int T, int H, int iters, float* qk,
+                      float* v, double* ms) {
+    if (!qkv || !q_w || !k_w || B <= 0 || T <= 0 || H <= 0 || H * kHeadDim > 2048 || iters < 0 || (iters > 0 && !ms)) { set_error("bad argument"); return PGMI_EINVAL; }
+    if (pgmi_device_count() <= 0) { set_error("no HIP device visible"); return PGMI_ENODEV; }
+    PGMI_HIP(hipSetDevice(device));
+    const size_t D = (size_t)H * kHeadDim, M = (size_t)B * T, Tp = (size_t)(T + 31) / 32 * 32;
+    std::vector<void*> pool;
+    auto cleanup = [&]() { for (void* p : pool) hipFree(p); };
+    float *dq = nullptr, *dqw = nullptr, *dkw = nullptr;
+    unsigned short *qk16 = nullptr, *vt16 = nullptr;
+    int rc = 0;
+    if ((rc = dev_upload(pool, &dq, qkv, M * 3 * D)) || (rc = dev_upload(pool, &dqw, q_w, D)) || (rc = dev_upload(pool, &dkw, k_w, D)) ||
+        (rc = dev_alloc(pool, &qk16, M * 2 * D * 2)) || (rc = dev_alloc(pool, &vt16, (size_t)B * Tp * D * 2))) {
+        cleanup();
+        return rc;
+    }
+    pgmi_model tmp;                                      // head_dim 64: ESM2's rotate-half tables
+    rc = upload_rotate_half(&tmp, T);
+    auto launch = [&]() {
+        return launch_qkln_prep(dq, dqw, dkw, 1e-5f, tmp.rot_cos, tmp.rot_sin, B, T, H, qk16, M * 2 * D, vt16, (size_t)B * Tp * D, nullptr);
+    };
+    if (!rc) rc = launch();
+    if (!rc && iters > 0) {
+        hipEvent_t e0, e1;
+        PGMI_HIP(hipEventCreate(&e0));
+        PGMI_HIP(hipEventCreate(&e1));
+        hipEventRecord(e0, nullptr);
+        for (int i = 0; i < iters && !rc; ++i) rc = launch();
+        hipEventRecord(e1, nullptr);
+        hipEventSynchronize(e1);
+        float t = 0.f;
+        hipEventElapsedTime(&t, e0, e1);
+        *ms = (double)t / iters;
+        hipEventDestroy(e0);
+        hipEventDestroy(e1);
+    }
+    hipDeviceSynchronize();
+    std::vector<unsigned short> hq(qk ? M * 2 * D * 2 : 0), hv(v ? (size_t)B * Tp * D * 2 : 0);
+    hipError_t e = hipSuccess;
+    if (!rc && qk) e = hipMemcpy(hq.data(), qk16, hq.size() * 2, hipMemcpyDeviceToHost);
+    if (!rc && v && e == hipSuccess) e = hipMemcpy(hv.data(), vt16, hv.size() * 2, hipMemcpyDeviceToHost);
+    for (void* p : tmp.allocs) hipFree(p);
+    cleanup();
+    if (rc) return rc;
+    if (e != hipSuccess) { set_error("qkln prep op failed: %s", hipGetErrorString(e)); return PGMI_EHIP; }
+    auto rebuild = [](unsigned short h, unsigned short l) {
+        _Float16 a, b;
+        memcpy(&a, &h, 2); memcpy(&b, &l, 2);
+        return (float)a + (float)b * (1.0f / kLoScale);
+    };
+    if (qk)
+        for (size_t i = 0; i < M * 2 * D; ++i) qk[i] = rebuild(hq[i], hq[M * 2 * D + i]);
+    if (v) {
+        const size_t vp = (size_t)B * Tp * D;
+        for (int b = 0; b < B; ++b)
+            for (int t = 0; t < T; ++t) {
+                const int tk = t & 31, pos = (t & ~31) + ((tk & 0x13) | ((tk & 4) << 1) | ((tk & 8) >> 1));   // keys with bits 2, 3 swapped
+                for (size_t c = 0; c < D; ++c) {
+                    const size_t o = ((size_t)b * H * kHeadDim + c) * Tp + pos;
+                    v[((size_t)b * T + t) * D + c] = rebuild(hv[o], hv[vp + o]);
+                }
+            }
+    }
+    return PGMI_OK;
 }
 
 int pgmi_op_attention(int device, int precision, const float* qkv, const int32_t* kv_len, int B, int T, int H,

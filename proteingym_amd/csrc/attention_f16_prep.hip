@@ -205,6 +205,121 @@ __global__ __launch_bounds__(256) void qkv_prep_conv_kernel(
     }
 }
 
+// ESM C (esm/layers/attention.py:45-66): the bias-free QKV projection's fp32 rows [B*T][3D] -> the planes above.  q and k are
+// LayerNorm-ed over the WHOLE width D before the head split (q_ln / k_ln: weight only, eps; the mean / variance arithmetic of
+// elementwise.hip layernorm_kernel), then rotated per 64-dim head (rotate-half, rotary.py) -- q also carries log2(e) (kQLog2e);
+// the 1/8 score scale is folded into q_w by the host -- and v is transposed as in qkv_prep_kernel.  The LayerNorm spans every head,
+// so this cannot be the QKV GEMM's epilogue (its N tiles are 256 wide).  HBM-bound: 12 D B in, 8 D B out per token.
+// Grid (ceil(T / 32), B), 256 threads: the 64 (token, q | k) rows of a 32-token tile go one wave per row; lane l holds the float4
+// columns l + 64 i, so the rotary partner (dim +- 32 of the head = float4 index ^ 8) sits in lane l ^ 8 of the same i.
+template <int NV>
+__global__ __launch_bounds__(256) void qkln_prep_kernel(
+    const float* __restrict__ qkv, const float* __restrict__ q_w, const float* __restrict__ k_w, float eps,
+    const float* __restrict__ cos_t, const float* __restrict__ sin_t, int T, int H, int Tp,
+    unsigned short* __restrict__ qk16, size_t qk_plane, unsigned short* __restrict__ vt16, size_t vt_plane) {
+    const int b = blockIdx.y, t0 = blockIdx.x * 32;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int D = H * kHeadDim, nv = D >> 2;
+    const size_t RS = (size_t)3 * D;
+    for (int u = wave; u < 64; u += 4) {                       // wave-uniform: row (token u >> 1, q | k = u & 1)
+        const int which = u & 1, t = t0 + (u >> 1);
+        if (t >= T) break;
+        const f32x4* xr = reinterpret_cast<const f32x4*>(qkv + ((size_t)b * T + t) * RS + (size_t)which * D);
+        f32x4 v[NV];
+        float sum = 0.f;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int c = lane + 64 * i;
+            v[i] = (c < nv) ? xr[c] : f32x4{0.f, 0.f, 0.f, 0.f};
+            sum += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+        const float mean = sum / (float)D;
+        float q = 0.f;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int c = lane + 64 * i;
+            if (c < nv) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float d = v[i][k] - mean;
+                    q += d * d;
+                }
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
+        const float rstd = 1.0f / sqrtf(q / (float)D + eps);
+        const f32x4* wr = reinterpret_cast<const f32x4*>(which ? k_w : q_w);
+        const int j4 = 4 * (lane & 15);                        // the lane's first dim inside its head (c & 15 == lane & 15)
+        const f32x4 cs = *reinterpret_cast<const f32x4*>(cos_t + (size_t)t * 64 + j4);
+        const f32x4 sn = *reinterpret_cast<const f32x4*>(sin_t + (size_t)t * 64 + j4);
+        const bool first_half = (lane & 8) == 0;               // dims 0..31 of the head: y = x cos - x[+32] sin; else x cos + x[-32] sin
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int c = lane + 64 * i;
+            f32x4 o;
+            const f32x4 wv = (c < nv) ? wr[c] : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) o[k] = (v[i][k] - mean) * rstd * wv[k];
+            f32x4 p;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) p[k] = __shfl_xor(o[k], 8);    // every lane takes part (nv % 16 == 0: partners agree on c < nv)
+            if (c < nv) {
+                f32x4 y;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) y[k] = first_half ? o[k] * cs[k] + (-p[k]) * sn[k] : o[k] * cs[k] + p[k] * sn[k];
+                if (which == 0) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) y[k] *= kQLog2e;
+                }
+                _Float16 hh[4], ll[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) split_act(y[k], hh[k], ll[k]);
+                unsigned short* dst = qk16 + ((size_t)b * T + t) * (2 * D) + (size_t)which * D + 4 * c;
+                *reinterpret_cast<u32x2*>(dst) = u32x2{pack_h2(hh[0], hh[1]), pack_h2(hh[2], hh[3])};
+                *reinterpret_cast<u32x2*>(dst + qk_plane) = u32x2{pack_h2(ll[0], ll[1]), pack_h2(ll[2], ll[3])};
+            }
+        }
+    }
+    // ---- v: thread (d, kq) transposes keys 8kq .. 8kq+7 of dimension d of every head (qkv_prep_kernel; keys >= T are zeros) ----
+    const int d = tid & 63, kq = tid >> 6;
+    for (int h = 0; h < H; ++h) {
+        _Float16 hh[8], ll[8];
+        const float* vsrc = qkv + ((size_t)b * T) * RS + 2 * D + h * kHeadDim + d;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int t = t0 + 8 * kq + e;
+            const float x = (t < T) ? vsrc[(size_t)t * RS] : 0.0f;
+            split_act(x, hh[e], ll[e]);
+        }
+        unsigned short* row = vt16 + (((size_t)b * H + h) * kHeadDim + d) * Tp + t0 + 16 * (kq >> 1) + 4 * (kq & 1);
+        *reinterpret_cast<u32x2*>(row) = u32x2{pack_h2(hh[0], hh[1]), pack_h2(hh[2], hh[3])};
+        *reinterpret_cast<u32x2*>(row + 8) = u32x2{pack_h2(hh[4], hh[5]), pack_h2(hh[6], hh[7])};
+        *reinterpret_cast<u32x2*>(row + vt_plane) = u32x2{pack_h2(ll[0], ll[1]), pack_h2(ll[2], ll[3])};
+        *reinterpret_cast<u32x2*>(row + vt_plane + 8) = u32x2{pack_h2(ll[4], ll[5]), pack_h2(ll[6], ll[7])};
+    }
+}
+
+int launch_qkln_prep(const float* qkv, const float* q_w, const float* k_w, float eps, const float* cos_t, const float* sin_t, int B,
+                     int T, int H, unsigned short* qk16, size_t qk_plane, unsigned short* vt16, size_t vt_plane, hipStream_t s) {
+    const int nv = H * kHeadDim / 4, Tp = (T + 31) / 32 * 32;
+    if (B <= 0 || T <= 0 || H <= 0 || nv > 512) { set_error("qkln_prep: bad shape B=%d T=%d H=%d (D = 64 H <= 2048)", B, T, H); return PGMI_EINVAL; }
+    const dim3 grid((T + 31) / 32, B);
+#define PGMI_QKLN(NV_) hipLaunchKernelGGL(qkln_prep_kernel<NV_>, grid, dim3(256), 0, s, qkv, q_w, k_w, eps, cos_t, sin_t, T, H, Tp, \
+                                          qk16, qk_plane, vt16, vt_plane)
+    if (nv <= 64) PGMI_QKLN(1);
+    else if (nv <= 128) PGMI_QKLN(2);
+    else if (nv <= 192) PGMI_QKLN(3);
+    else if (nv <= 256) PGMI_QKLN(4);
+    else if (nv <= 320) PGMI_QKLN(5);
+    else PGMI_QKLN(8);
+#undef PGMI_QKLN
+    PGMI_HIP(hipGetLastError());
+    return PGMI_OK;
+}
+
 void launch_qkv_prep(dim3 grid, hipStream_t s, const float* qkv, const float* cos_t, const float* sin_t, int rotary, int T, int H, int Tp,
                      unsigned short* qk16, size_t qk_plane, unsigned short* vt16, size_t vt_plane) {
     hipLaunchKernelGGL(qkv_prep_kernel, grid, dim3(256), 0, s, qkv, cos_t, sin_t, rotary, T, H, Tp, qk16, qk_plane, vt16, vt_plane);

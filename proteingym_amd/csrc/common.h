@@ -26,7 +26,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kWave = 64;
 constexpr int kHeadDim = 64;
 
-enum Epilogue { EPI_NONE = 0, EPI_GELU = 1, EPI_SQRELU = 2, EPI_GELU_TANH = 3 };   // erf-GELU (ESM), squared ReLU (Tranception), tanh-GELU (ProGen2)
+enum Epilogue { EPI_NONE = 0, EPI_GELU = 1, EPI_SQRELU = 2, EPI_GELU_TANH = 3,   // erf-GELU (ESM), squared ReLU (Tranception), tanh-GELU (ProGen2)
+                EPI_SWIGLU = 4 };   // ESM C's FC1: W rows in blocks of 64 = 32 gate | 32 up rows; out column 32 b + i = silu(gate) * up, N / 2 wide
 
 // f16x3 activation split: x ~= hi + lo * 2^-11 with hi = fp16(x) and lo = fp16((x - hi) * 2^11).
 // The scaled lo keeps its 11 bits for every |x| >= 2^-14 (an unscaled lo would be an fp16
@@ -146,6 +147,12 @@ int launch_gemm16_ex(const unsigned short* A, const unsigned short* W, float* Cf
 // x [n/K rows][K] fp32 -> mode 0: f16x3 weight (hi/lo of x*scale), 1: bf16 plane, 2: f16x3 activation split; the
 // f16x3 forms are written K-interleaved (ki_off)
 void launch_split16(const float* x, int64_t n, float scale, int mode, int K, unsigned short* out, hipStream_t s);
+
+// ESM C (api_esmc.hip): fp32 q | k | v rows [B*T][3D] of the bias-free QKV projection -> the split-fp16 attention operands (qk16 /
+// vt16, the layout of qkv_prep_kernel).  q and k get a weight-only LayerNorm over the full width D (q_w / k_w, eps), the rotate-half
+// rotary of 64-dim heads (cos_t / sin_t [t][64]) and q the log2(e) factor.  D = 64 H <= 2048.
+int launch_qkln_prep(const float* qkv, const float* q_w, const float* k_w, float eps, const float* cos_t, const float* sin_t, int B,
+                     int T, int H, unsigned short* qk16, size_t qk_plane, unsigned short* vt16, size_t vt_plane, hipStream_t s);
 
 // ---- attention_f32.hip -------------------------------------------------------------------
 // qkv [B*T, 3*H*64] (q pre-scaled by 1/8); kv_len[b] (nullable) = valid keys.  Output: ctx fp32

@@ -52,6 +52,16 @@ __device__ __forceinline__ f32x4 gelu_tanh16(f32x4 x) {
     return r;
 }
 
+// SiLU (ESM C's SwiGLU, blocks.py:15-30: F.silu(x1) * x2) in the logistic form x / (1 + 2^(-x log2 e)).  NaN stays NaN, +inf stays +inf
+// and -inf gives NaN (torch: -inf * 0 = NaN), so a value that left the fp16 range upstream still reaches the range guard downstream.
+__device__ __forceinline__ f32x4 silu16(f32x4 x) {
+    constexpr float c = -1.4426950408889634f;
+    f32x4 r;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) r[e] = x[e] / (1.0f + __builtin_amdgcn_exp2f(c * x[e]));
+    return r;
+}
+
 // Attention operands straight from the fused QKV projection (OUT 2): q|k as split planes qk16 [2][M][2D] (ESM2 rotary
 // applied here, rotary_embedding.py:11-20), v as the transposed, key-permuted planes vt16 [2][B*H*64][Tp] that
 // attention_f16.hip consumes.
@@ -643,6 +653,60 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
                         __builtin_amdgcn_wave_barrier();
                     }
                 }
+            } else if constexpr (EPI == EPI_SWIGLU) {
+            // SwiGLU (ESM C's FC1): the host stores W in blocks of 64 rows = 32 gate rows | 32 up rows, so the lane's N16 tiles j and
+            // j + 2 (j = 0, 1) hold gate and up of the SAME hidden units and the wave's 64 columns become the 32 output columns
+            // en0 / 2 + wn * 32 + 16 j + 4 kq + e of the N / 2 wide K-interleaved planes (N % 64 == 0: the launcher).  Through a per-wave
+            // patch of 32 rows x (64 B hi | 64 B lo) + 16 B pad, so that 8 lanes store one row's 128-byte line.
+            constexpr int SPS = 144;
+            const int Nh = N >> 1, nw = en0 + wn * 64;
+            if (nw < N) {
+            unsigned char* patch = patches + wave * (32 * SPS);
+            f32x4 bvs[TN];
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+                bvs[j] = bias ? *reinterpret_cast<const f32x4*>(bias + nw + 16 * j + 4 * kq) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int j = 0; j < TN; ++j) asm volatile("" :: "v"(bvs[j]));              // waited for HERE, not inside the block loop
+#pragma unroll
+            for (int ib = 0; ib < TM / 2; ++ib) {
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    const int i = 2 * ib + s, prow = 16 * s + r;
+                    if (em0 + (wm * TM + i) * 16 + r >= M) continue;
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        f32x4 g, u;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            g[e] = fmaf(acc[j][i][e], out_scale, bvs[j][e]);
+                            u[e] = fmaf(acc[j + 2][i][e], out_scale, bvs[j + 2][e]);
+                        }
+                        const f32x4 val = silu16(g) * u;
+                        h4 hi, lo;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            _Float16 a, b;
+                            split_act(val[e], a, b);
+                            hi[e] = a;
+                            lo[e] = b;
+                        }
+                        unsigned char* cell = patch + prow * SPS + (16 * j + 4 * kq) * 2;
+                        lds_put(cell, hi);
+                        lds_put(cell + 64, lo);
+                    }
+                }
+                __builtin_amdgcn_wave_barrier();
+                const int m_base = em0 + (wm * TM + 2 * ib) * 16;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int q = lane + 64 * k, row = q >> 3, cc = q & 7;     // 16-byte chunk cc of row `row`'s 128-byte line
+                    const u32x4 v = *reinterpret_cast<const u32x4*>(patch + row * SPS + cc * 16);
+                    if (m_base + row < M) *reinterpret_cast<u32x4*>(Ch + (size_t)(m_base + row) * (2 * (size_t)Nh) + (size_t)nw + cc * 8) = v;
+                }
+                __builtin_amdgcn_wave_barrier();
+            }
+            }
             } else {
             // per-wave LDS patch: 32 rows x (256 B in OUTPUT order: group 0 hi | group 0 lo | group 1 hi | group 1 lo) + 16 B pad
             constexpr int SP = 272;

@@ -316,6 +316,12 @@ static int launch_gemm16x_one(const unsigned short* A, const unsigned short* W,
     } while (0)
 #define PGMI_LAUNCH16X_O(EPI_) do { if (Ch) PGMI_LAUNCH16X(EPI_, 1); else PGMI_LAUNCH16X(EPI_, 0); } while (0)
     if (qkv) PGMI_LAUNCH16X(EPI_NONE, 2);
+    else if (epilogue == EPI_SWIGLU) {                   // f16x3, split-plane output only (launch_gemm16)
+        const auto kfn = gemm16x_kernel<EPI_SWIGLU, 1>;
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)X_LDS_BYTES);
+        if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PGMI_EHIP; }
+        hipLaunchKernelGGL(kfn, grid, block, X_LDS_BYTES, s, A, W, bias, residual, Cf, Ch, c_plane, M, N, K, out_scale, tp, qo, xmap);
+    }
     else if (epilogue == EPI_GELU) PGMI_LAUNCH16X_O(EPI_GELU);
     else if (epilogue == EPI_SQRELU) PGMI_LAUNCH16X_O(EPI_SQRELU);
     else if (epilogue == EPI_GELU_TANH) PGMI_LAUNCH16X_O(EPI_GELU_TANH);
@@ -397,8 +403,9 @@ static int launch_gemm16x(const unsigned short* A, const unsigned short* W,
             rc = launch_gemm16x_one(Ac, W, bias, nullptr, nullptr, Ch + (size_t)m0 * (size_t)(2 * (N / 3)), c_plane, mc, N, K, epilogue,
                                     out_scale, s, &q, bf);
         } else {
+            const size_t n_out = epilogue == EPI_SWIGLU ? (size_t)N / 2 : (size_t)N;        // SwiGLU: N / 2 output columns
             rc = launch_gemm16x_one(Ac, W, bias, residual ? residual + (size_t)m0 * N : nullptr, Cf ? Cf + (size_t)m0 * N : nullptr,
-                                    Ch ? Ch + (size_t)m0 * (size_t)((bf ? 1 : 2) * N) : nullptr, c_plane, mc, N, K, epilogue, out_scale, s, nullptr, bf);
+                                    Ch ? Ch + (size_t)m0 * (size_t)(bf ? 1 : 2) * n_out : nullptr, c_plane, mc, N, K, epilogue, out_scale, s, nullptr, bf);
         }
         if (rc) return rc;
     }
@@ -425,6 +432,10 @@ int launch_gemm16(const unsigned short* A, size_t a_plane, const unsigned short*
     const int k_step = (planes == 2 && !bf) ? 32 : 64;
     if (M <= 0 || N <= 0 || K <= 0 || (K % k_step) != 0 || (N % 4) != 0 || (!Cf && !Ch) || (Cf && Ch)) {
         set_error("gemm16: unsupported shape/args M=%d N=%d K=%d (K %% %d == 0, N %% 4 == 0 required)", M, N, K, k_step);
+        return PGMI_EINVAL;
+    }
+    if (epilogue == EPI_SWIGLU && (planes != 2 || bf || !Ch || residual || (N % 64) != 0)) {
+        set_error("gemm16: the SwiGLU epilogue is f16x3 with split-plane output, no residual and N %% 64 == 0 (N = %d)", N);
         return PGMI_EINVAL;
     }
     if (planes == 2 && !bf) {

@@ -8,6 +8,7 @@
 //   api_progen2.hip      ProGen2 weights and forward (parallel residual, GPT-J rotary); token log-probs and sequence log-likelihoods
 //   api_gpt.hip          causal decoder (RITA, ProtGPT2) weights and forward, narrow and wide LM heads; token log-probs and sequence
 //                        log-likelihoods
+//   api_esmc.hip         ESM C weights and forward (QK-LayerNorm, SwiGLU, scaled residual, untied 64-column head)
 //   api_msa.hip          MSA Transformer weights and forward (tied row attention, column attention)
 //   api_host.hip         host-only entries: mutant parser, table -> scores, optimal window
 //   api_ops.hip          single-op and timing entries for the numerics tests and the A/B scripts
@@ -43,6 +44,7 @@ struct Layer {
     // MSA Transformer: ln1/wqkv/wo = tied row attention, c_* = column attention, ln2/w1/w2 = feed forward
     float *c_ln_w = nullptr, *c_ln_b = nullptr, *c_bqkv = nullptr, *c_bo = nullptr;
     W16 c_wqkv16, c_wo16;
+    float *q_ln = nullptr, *k_ln = nullptr;       // ESM C: q_ln (times 1/8) / k_ln weights
 };
 
 struct ProfEvent {
@@ -85,6 +87,8 @@ struct pgmi_model {
     float *gpt_head_w = nullptr, *gpt_logits = nullptr, *gpt_zero = nullptr, *gpt_slopes = nullptr;
     W16 gpt_head16;
     double* gpt_sum = nullptr;
+    // ESM C (api_esmc.hip): the untied head weight [64,D] (its bias is h_bias) and the zero bias of the final LayerNorm
+    float *esmc_head_w = nullptr, *esmc_zero = nullptr;
     // MSA Transformer
     float* msa_pe = nullptr;                            // msa_position_embedding [1024, D]
     float* xt = nullptr;                                // residual stream in column-major token order
@@ -232,6 +236,10 @@ int create_progen2(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_
 // api_gpt.hip
 int create_gpt(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights, int pos_kind);
 int64_t gpt_weight_count(const pgmi_config* c, int pos_kind);
+// api_esmc.hip
+int64_t esmc_weight_count(const pgmi_config* c);
+int create_esmc(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights);
+int run_esmc_rows(pgmi_model* m, int B, int T, int R, const int32_t* row_idx);
 // api_msa.hip
 int create_msa(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights);
 int run_msa(pgmi_model* m, int R, int C, int keep_col = -1, bool* compacted = nullptr);

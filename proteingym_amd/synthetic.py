@@ -485,3 +485,37 @@ def save_causal_lm_checkpoint(path: str, cfg: dict, sd: Dict[str, np.ndarray]):
                  bos_token_id=0, eos_token_id=0)
     json.dump(c, open(os.path.join(path, "config.json"), "w"), indent=1)
     torch.save({k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in sd.items()}, os.path.join(path, "pytorch_model.bin"))
+
+
+def esmc_config(embed_dim: int = 960, layers: int = 30) -> dict:
+    """An ESM C configuration (esm/pretrained.py:65-98): head_dim 64, SwiGLU width swiglu_correction_fn(8/3, d), 64-column head."""
+    return dict(layers=layers, embed_dim=embed_dim, heads=embed_dim // 64, ffn_dim=int(((8 / 3 * embed_dim) + 255) // 256 * 256), vocab=64)
+
+
+def esmc_state_dict(cfg: dict, seed: int) -> Dict[str, np.ndarray]:
+    """Seeded random ESM C weights under ESMC.state_dict()'s keys.  Linear weights ~ N(0, 1/fan_in), LayerNorm gains 1 + N(0, 0.1^2)
+    (q_ln / k_ln and the bias-free final norm included), biases N(0, 0.02^2), embedding N(0, 1); the output layer 3x wider so that the
+    log-probabilities are far from uniform, its untrained rows 33..63 non-zero like the rest."""
+    normal = _causal_normal(seed)
+    D, F, V = cfg["embed_dim"], cfg["ffn_dim"], cfg["vocab"]
+    sd = {"embed.weight": normal((V, D), 1.0)}
+    for i in range(cfg["layers"]):
+        p = f"transformer.blocks.{i}."
+        sd[p + "attn.layernorm_qkv.0.weight"] = 1.0 + normal((D,), 0.1)
+        sd[p + "attn.layernorm_qkv.0.bias"] = normal((D,), 0.02)
+        sd[p + "attn.layernorm_qkv.1.weight"] = normal((3 * D, D), D ** -0.5)
+        sd[p + "attn.out_proj.weight"] = normal((D, D), D ** -0.5)
+        sd[p + "attn.q_ln.weight"] = 1.0 + normal((D,), 0.1)
+        sd[p + "attn.k_ln.weight"] = 1.0 + normal((D,), 0.1)
+        sd[p + "ffn.0.weight"] = 1.0 + normal((D,), 0.1)
+        sd[p + "ffn.0.bias"] = normal((D,), 0.02)
+        sd[p + "ffn.1.weight"] = normal((2 * F, D), D ** -0.5)
+        sd[p + "ffn.3.weight"] = normal((D, F), F ** -0.5)
+    sd["transformer.norm.weight"] = 1.0 + normal((D,), 0.1)
+    sd["sequence_head.0.weight"] = normal((D, D), D ** -0.5)
+    sd["sequence_head.0.bias"] = normal((D,), 0.02)
+    sd["sequence_head.2.weight"] = 1.0 + normal((D,), 0.1)
+    sd["sequence_head.2.bias"] = normal((D,), 0.02)
+    sd["sequence_head.3.weight"] = normal((V, D), 3.0 * D ** -0.5)
+    sd["sequence_head.3.bias"] = normal((V,), 0.02)
+    return sd
