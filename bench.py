@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the hot path: mutants scored per second, ESM-1v 650M masked-marginals.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision fp32] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision fp32] [--dump-outputs DIR] [--full]
 
 One *step* = one pass of the hot path over one assay-shaped batch resident in HBM:
 BASELINE.json configs[1] -- ESM-1v 650M (33 x 1280 x 20 heads x 5120), one assay shaped like
@@ -13,14 +13,18 @@ random-init weights (no network), deterministic seeds.
 N > 1 (launched by torch.distributed.run, one rank per GPU): the SAME step on every rank -- one BLAT-shaped assay per rank per
 step (its own synthetic assay), then the path's one exchange: an RCCL all_gather of the per-mutant score vectors.  Per-GPU work
 is fixed ("scaling": "weak"), value = N x 4 996 x K mutants / max-over-ranks seconds, so value(N) / (N x value(1)) is the scaling
-efficiency of the step the N = 1 line measures.  After that timed region the line gains `strong_scaling_217`: ONE pass over the
-217-assay-shaped substitution benchmark (2 465 767 mutants, the north star's workload) with the assays sharded over the ranks by
+efficiency of the step the N = 1 line measures.  With --full, after that timed region the line gains `strong_scaling_217`: ONE pass
+over the 217-assay-shaped substitution benchmark (2 465 767 mutants, the north star's workload) with the assays sharded over the ranks by
 the product planner (run_benchmark.plan_assays), inputs resident, timed with its own barriers (scripts/bench_scale.py); its
-one-GPU point is the N = 1 line's `one_gpu_same_workload_mutants_per_s`.
+one-GPU point is the N = 1 --full line's `one_gpu_same_workload_mutants_per_s`.
 
-Extra objects on the JSON line: `roofline` (dominant kernel = the FFN GEMMs, HIP-event timed
-inside the timed region, against the MFMA peak of the dtype) and `cpu_baseline` (the oracle's
-CPU restatement of the reference path timed on this box's host cores, bounded sample).
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, the
+--dump-outputs arrays, and the JSON line with `roofline` (dominant kernel = the FFN GEMMs, HIP-event
+timed inside the timed region, against the MFMA peak of the dtype) and `kernels` from that same
+region.  --full adds everything that takes work of its own after the timed region: `box` (clock and
+power during extra steps), roofline.traffic from in-run rocprofv3 --pmc passes, the end-to-end
+fields, `cpu_baseline` (the oracle's CPU restatement of the reference path timed on this box's host
+cores, bounded sample) with `parity`, the `secondary` configurations and, N > 1, `strong_scaling_217`.
 """
 import argparse
 import json
@@ -107,8 +111,7 @@ def live_traffic(precision, timeout_s=90):
                 env.pop(k, None)
             for counter in ("FETCH_SIZE", "WRITE_SIZE"):
                 cmd = [exe, "--kernel-trace", "--pmc", counter, "--output-format", "csv", "-d", os.path.join(d, counter), "-o", "p", "--",
-                       sys.executable, os.path.abspath(__file__), "--steps", "1", "--warmup", "0", "--cpu-seconds", "0", "--layers", "2",
-                       "--no-box-state", "--no-secondary", "--no-live-traffic", "--precision", precision]
+                       sys.executable, os.path.abspath(__file__), "--steps", "1", "--warmup", "0", "--layers", "2", "--precision", precision]
                 done = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout_s, env=env, cwd="/tmp")
                 if done.returncode != 0:
                     return {"unavailable": f"rocprofv3 --pmc {counter} exited {done.returncode}: {done.stderr.strip()[-200:]}"}
@@ -602,14 +605,17 @@ def main(argv=None, make_model=None, make_assay=None):
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--precision", default="f16x3", choices=["fp32", "bf16", "f16x3"],
                     help="f16x3 (default) and fp32 are parity-gated (1e-4 abs vs the reference); bf16 is not")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU-baseline time budget (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure and check everything beyond the headline (box state, in-run PMC "
+                         "traffic, end-to-end rate, CPU baseline and parity, secondary configurations, N > 1: strong_scaling_217)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: CPU-baseline time budget (0 = skip it and `secondary`)")
     ap.add_argument("--layers", type=int, default=33, help="debug only; the headline config is 33")
     ap.add_argument("--checkpoints", type=int, default=1,
                     help="score with N checkpoints per step and average (ESM-1v ensemble rate; the headline is 1)")
     ap.add_argument("--variant", type=int, default=None, help="debug: PGMI_GEMM_VARIANT tile configuration")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the `secondary` object (other configs; ~1 min after the headline)")
-    ap.add_argument("--no-live-traffic", action="store_true", help="do not run the rocprofv3 --pmc child passes for roofline.traffic (the committed file is used)")
-    ap.add_argument("--no-box-state", action="store_true", help="skip the `box` object (shader clock / socket power during ~2 s of untimed extra steps)")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the `secondary` object (other configs; minutes after the headline)")
+    ap.add_argument("--no-live-traffic", action="store_true", help="--full: do not run the rocprofv3 --pmc child passes for roofline.traffic (the committed file is used)")
+    ap.add_argument("--no-box-state", action="store_true", help="--full: skip the `box` object (shader clock / socket power during ~2 s of untimed extra steps)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step computed as DIR/<name>.npy: scores.npy, the float64 per-mutant scores "
                          "(N > 1: the all_gathered vector of every rank, written by rank 0)")
@@ -680,7 +686,7 @@ def main(argv=None, make_model=None, make_assay=None):
         if not seam:
             torch.cuda.synchronize()
 
-    # every N: W untimed steps, then exactly K timed steps between two fences; N > 1 adds the 217-assay pass AFTER this region
+    # every N: W untimed steps, then exactly K timed steps between two fences; N > 1 --full adds the 217-assay pass AFTER this region
     blat_steps = args.steps
     for _ in range(args.warmup):
         step()
@@ -705,17 +711,19 @@ def main(argv=None, make_model=None, make_assay=None):
     if world > 1:
         prof = model.profile()
         assay.close()
-        sys.path.insert(0, os.path.join(ROOT, "scripts"))
-        import bench_scale
-        strong_steps = max(1, min(args.steps, 4))
-        st = bench_scale.run(model, rank, world, strong_steps, min(args.warmup, 1), torch, dist,
-                             max_assays=int(os.environ.get("PGMI_BENCH_217_ASSAYS", "0")), make_assay=make_assay)
-        st["mutants_per_s"] = st["mutants"] / st["seconds"]
-        st["what"] = (f"ONE pass over the {st['assays']}-assay-shaped DMS substitution benchmark ({st['mutants']} mutants; real seq_len / mutant counts "
-                      "of reference_files/DMS_substitutions.csv, optimal 1024 windows), 1 checkpoint, assays sharded over the ranks by "
-                      "run_benchmark.plan_assays, inputs resident in HBM, one all_gather of the per-mutant score vectors; total work fixed; "
-                      f"timed between its own barriers as {strong_steps} consecutive slices of each rank's work list, max over ranks")
-        st["scaling_efficiency"] = "mutants_per_s / (N * one_gpu_same_workload_mutants_per_s of the N = 1 line)"
+        st = None
+        if args.full:
+            sys.path.insert(0, os.path.join(ROOT, "scripts"))
+            import bench_scale
+            strong_steps = max(1, min(args.steps, 4))
+            st = bench_scale.run(model, rank, world, strong_steps, min(args.warmup, 1), torch, dist,
+                                 max_assays=int(os.environ.get("PGMI_BENCH_217_ASSAYS", "0")), make_assay=make_assay)
+            st["mutants_per_s"] = st["mutants"] / st["seconds"]
+            st["what"] = (f"ONE pass over the {st['assays']}-assay-shaped DMS substitution benchmark ({st['mutants']} mutants; real seq_len / mutant "
+                          "counts of reference_files/DMS_substitutions.csv, optimal 1024 windows), 1 checkpoint, assays sharded over the ranks by "
+                          "run_benchmark.plan_assays, inputs resident in HBM, one all_gather of the per-mutant score vectors; total work fixed; "
+                          f"timed between its own barriers as {strong_steps} consecutive slices of each rank's work list, max over ranks")
+            st["scaling_efficiency"] = "mutants_per_s / (N * one_gpu_same_workload_mutants_per_s of the N = 1 line)"
         from proteingym_amd import dist as pdist
         rccl = pdist.collective_identity(local_rank)                  # a collective: every rank calls it
         if rank == 0:
@@ -739,10 +747,11 @@ def main(argv=None, make_model=None, make_assay=None):
                                        f"mutants, inputs resident in HBM, a different synthetic assay per rank), then ONE all_gather of the {world} score vectors "
                                        "(RCCL over xGMI); per-GPU work fixed",
                            "value_is": "all ranks' mutants / max-over-ranks seconds of the K steps; value(N) / (N * value(1)) = scaling efficiency",
-                           "north_star_workload": "strong_scaling_217 (the whole 217-assay table sharded over the ranks), timed after this region",
+                           "north_star_workload": "strong_scaling_217 (the whole 217-assay table sharded over the ranks), timed after this region "
+                                                  "with --full",
                            "precision": args.precision, "layers": args.layers},
                 "rccl": rccl,
-                "strong_scaling_217": st,
+                **({"strong_scaling_217": st} if st is not None else {}),
                 **({"REHEARSAL": "PGMI_BENCH_SHARE_GPU=1: ranks share a GPU and use gloo -- not a measurement"} if share else {}),
                 "roofline": {"bound": "mfma", "kernel": "gemm (fc1+GELU, fc2+residual), rank 0", "achieved": achieved, "peak": peak,
                              "unit": "TFLOP/s", "frac": achieved / peak, "avg_launch_ms": ffn_ms / max(ffn_n, 1), "traffic": None,
@@ -760,7 +769,7 @@ def main(argv=None, make_model=None, make_assay=None):
         return
 
     prof = model.profile()
-    box = box_state(step) if not args.no_box_state else None          # after the timed region and the profile read-out
+    box = box_state(step) if args.full and not args.no_box_state else None     # after the timed region and the profile read-out
     if rank == 0:
         ffn_ms = prof["gemm_fc1"]["ms"] + prof["gemm_fc2"]["ms"]
         ffn_fl = prof["gemm_fc1"]["flops"] + prof["gemm_fc2"]["flops"]
@@ -769,7 +778,10 @@ def main(argv=None, make_model=None, make_assay=None):
         peak = PEAK_TFLOPS[args.precision]
         passes = 3 if args.precision == "f16x3" else 1          # MFMA FLOPs executed per algorithmic FLOP
         total_fl = sum(v["flops"] for v in prof.values())
-        live = None if (args.no_live_traffic or args.layers != 33) else live_traffic(args.precision)
+        if not args.full:
+            live = {"unavailable": "the rocprofv3 --pmc passes run with --full"}
+        else:
+            live = None if (args.no_live_traffic or args.layers != 33) else live_traffic(args.precision)
         traffic, traffic_detail = ffn_traffic(args.precision, len(assay.positions) * assay.T, cfg["embed_dim"], cfg["ffn_dim"], live=live)
         kern = {k: {"ms_per_step": round(v["ms"] / args.steps, 3), "launches_per_step": v["launches"] // args.steps,
                     "tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2) if v["ms"] > 0 and v["flops"] > 0 else None,
@@ -789,10 +801,10 @@ def main(argv=None, make_model=None, make_assay=None):
                                    "BLAT_ECOLX_Stiffler_2015-shaped assay per step (BASELINE.json configs[1]: L=286, T=288, "
                                    f"{len(assay.positions)} masked positions run, {n_mut} single mutants), "
                                    f"{args.checkpoints} checkpoint{'s averaged (ensemble rate)' if args.checkpoints > 1 else ''}; "
-                                   "N > 1 runs the same step on every rank + one all_gather (weak scaling) and adds strong_scaling_217",
+                                   "N > 1 runs the same step on every rank + one all_gather (weak scaling) and, with --full, adds strong_scaling_217",
                        "value_is": "DEVICE-ONLY rate of the hot path: inputs resident in HBM when the timed region starts, scores left in HBM "
-                                   "(mutants / seconds of the K timed steps).  The metric as SURVEY 8d words it -- weights resident to CSV written -- is "
-                                   "value_end_to_end (this assay: mutant strings parsed, uploaded, scored, copied back, CSV written) and, for the whole "
+                                   "(mutants / seconds of the K timed steps).  The metric as SURVEY 8d words it -- weights resident to CSV written -- is, "
+                                   "with --full, value_end_to_end (this assay: mutant strings parsed, uploaded, scored, copied back, CSV written) and, for the whole "
                                    "217-assay table, benchmark_217_end_to_end_mutants_per_s",
                        "precision": args.precision, "layers": args.layers,
                        "last_layer": ("after its attention the last layer runs on the masked row of every sequence only -- the one row "
@@ -813,13 +825,13 @@ def main(argv=None, make_model=None, make_assay=None):
         if box is not None:
             out["box"] = box
         e2e = None
-        if world == 1 and args.layers == 33:                          # SURVEY 8d's wording of the metric on this assay (after the timed region)
+        if args.full and world == 1 and args.layers == 33:            # SURVEY 8d's wording of the metric on this assay (after the timed region)
             try:
                 e2e = end_to_end_blat(model, seq, muts)
             except Exception as e:                                    # noqa: BLE001
                 e2e = {"error": repr(e)}
             out.update(end_to_end_fields(e2e, None))
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             _, gpu_table = assay.run(want_table=True)                 # outside the timed region
             for m2, a2, _ in extra:
                 a2.close()

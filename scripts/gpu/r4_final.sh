@@ -11,8 +11,8 @@ python -c "import torch; p=torch.cuda.get_device_properties(0); print(p.name, p.
 if [ "$1" != "quick" ]; then
   timeout 2400 python -m pytest tests -q -m gpu > $O/gpu_suite.log 2>&1; echo "rc $?" >> $O/gpu_suite.log; tail -4 $O/gpu_suite.log
 fi
-timeout 900 python bench.py > $O/bench_f16x3.json 2> $O/bench_f16x3.err; echo "bench rc $?"
-timeout 400 python bench.py --gpus 1 --steps 20 --warmup 5 --no-secondary > $O/bench_driver_command_headline.json 2> $O/bench_driver.err
+timeout 900 python bench.py --full > $O/bench_f16x3.json 2> $O/bench_f16x3.err; echo "bench rc $?"
+timeout 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-secondary > $O/bench_driver_command_headline.json 2> $O/bench_driver.err
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_f16x3 -o p -- python bench.py --steps 2 --warmup 1 --cpu-seconds 0 --no-secondary --no-box-state > $O/prof_f16x3.log 2>&1
 if [ "$1" != "quick" ]; then
   bash scripts/pmc_profile.sh r4 > $O/pmc.log 2>&1; cp gpurun_out/pmc_r4/summary.txt $O/pmc_summary.txt; cp gpurun_out/pmc_r4/pmc_traffic.json $O/pmc_traffic.json
@@ -28,7 +28,7 @@ timeout 300 python scripts/bench_msa_transformer.py > $O/bench_msa_transformer.j
 timeout 300 python scripts/bench_msa_transformer.py --cols 1024 --positions 3 > $O/bench_msa_transformer_1024.json 2>> $O/bench_msa.err
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_msat -o p -- python scripts/bench_msa_transformer.py --positions 3 > $O/prof_msat.log 2>&1
 timeout 300 python scripts/bench_msa_weights.py --n 100000 --l 400 > $O/bench_msa_weights.json 2> $O/bench_msa_weights.err
-PGMI_BENCH_SHARE_GPU=1 PGMI_BENCH_217_ASSAYS=24 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 2 --steps 4 --warmup 1 > $O/rehearsal_bench_n2_shared_gpu.json 2> $O/rehearsal.err
+PGMI_BENCH_SHARE_GPU=1 PGMI_BENCH_217_ASSAYS=24 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29611 bench.py --full --gpus 2 --steps 4 --warmup 1 > $O/rehearsal_bench_n2_shared_gpu.json 2> $O/rehearsal.err
 tools/store_drain > $O/store_drain.log 2>&1
 find $O -name "*kernel_trace.csv" -delete; find $O -name "*agent_info.csv" -delete; find $O -name "*.db" -delete
 du -sh $O; ls $O

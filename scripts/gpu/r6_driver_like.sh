@@ -6,7 +6,7 @@ O=gpurun_out/r6_driver_like; rm -rf $O; mkdir -p $O
 timeout 2400 python -m pytest tests/ -x -q -m gpu --durations=15 > $O/gpu_suite.log 2>&1; echo "suite rc $?"; tail -3 $O/gpu_suite.log
 timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc $?"; tail -2 $O/smoke.log
 SECONDS=0
-timeout 1500 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc $? in $SECONDS s"
+timeout 1500 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc $? in $SECONDS s"
 python - <<PY
 import json
 d = json.loads(open("$O/bench_default.json").read().strip().splitlines()[-1])

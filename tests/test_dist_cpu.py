@@ -1056,12 +1056,12 @@ def _bench_main_entry(dump_dir):
         print("[Gloo] Rank chatter that a backend might print on stdout")        # inside bench.main: must end up on stderr
         os.system("echo chatter of a child process that inherits file descriptor 1")
         return _FakeBenchModel()
-    bench.main(["--gpus", "2", "--steps", "2", "--warmup", "1", "--dump-outputs", dump_dir], make_model=model, make_assay=_FakeBenchAssay)
+    bench.main(["--gpus", "2", "--steps", "2", "--warmup", "1", "--dump-outputs", dump_dir, "--full"], make_model=model, make_assay=_FakeBenchAssay)
 
 
 def test_bench_n_gt_1_prints_exactly_one_json_line_on_stdout(tmp_path):
     """The driver launches `bench.py --gpus N` under torch.distributed.run and reads stdout: two gloo ranks through bench.main
-    (model and assay seams, 24 assays of the table) -- rank 0's stdout is ONE line and it is the JSON object with the contract's
+    --full (model and assay seams, 24 assays of the table) -- rank 0's stdout is ONE line and it is the JSON object with the contract's
     keys, rank 1's stdout is empty; everything any library printed is on stderr.  --dump-outputs: rank 0 writes the gathered
     score vector of both ranks."""
     import json
@@ -1091,6 +1091,56 @@ def test_bench_n_gt_1_prints_exactly_one_json_line_on_stdout(tmp_path):
     assert sorted(os.listdir(tmp_path / "dump")) == ["scores.npy"]
     scores = np.load(tmp_path / "dump" / "scores.npy")
     assert scores.dtype == np.float64 and scores.shape == (2 * 4996,)           # two ranks x the BLAT-shaped assay
+
+
+def _bench_plain_entry(dump_dir):
+    """Runs in a child process (see the test below): bench.main without --full, seams for the model and the assay; everything that
+    --full adds after the timed region raises if it is reached."""
+    import sys
+    import bench
+    from proteingym_amd import synthetic
+
+    def full_only(*a, **k):
+        raise AssertionError("a plain bench run reached work that belongs to --full")
+    for name in ("box_state", "live_traffic", "end_to_end_blat", "cpu_baseline", "secondary"):
+        setattr(bench, name, full_only)
+    sys.modules["bench_scale"] = None                                            # `import bench_scale` (strong_scaling_217) fails
+    synthetic.random_weights = lambda cfg, seed, **k: np.zeros(1, np.float32)    # the seam model never reads the blob
+    world = os.environ["WORLD_SIZE"]
+    bench.main(["--gpus", world, "--steps", "2", "--warmup", "1", "--dump-outputs", dump_dir],
+               make_model=lambda cfg, blob, dev, prec: _FakeBenchModel(), make_assay=_FakeBenchAssay)
+
+
+@pytest.mark.parametrize("world", [1, 2])
+def test_plain_bench_run_ends_with_the_headline(tmp_path, world):
+    """`bench.py --gpus N --steps K --warmup W` without --full: warm-up, timed steps, --dump-outputs and ONE JSON line with the
+    contract's keys -- no box state, PMC passes, end-to-end run, CPU baseline, secondary configurations or strong-scaling pass."""
+    import json
+    import subprocess
+    import sys
+    port = _free_port()
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    procs = []
+    for r in range(world):
+        env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(world),
+                   OMP_NUM_THREADS="1")
+        code = (f"import sys; sys.path[:0] = [{root!r}, {os.path.join(root, 'tests')!r}]; import test_dist_cpu as t; "
+                f"t._bench_plain_entry({str(tmp_path / 'dump')!r})")
+        procs.append(subprocess.Popen([sys.executable, "-c", code], env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
+    outs = [p.communicate(timeout=600) for p in procs]
+    assert [p.returncode for p in procs] == [0] * world, outs
+    lines = outs[0][0].splitlines()
+    assert len(lines) == 1 and all(o[0] == "" for o in outs[1:]), outs
+    line = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config", "roofline",
+                "kernels"):
+        assert key in line, key
+    assert line["n_gpus"] == world and line["steps"] == 2 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    for key in ("box", "cpu_baseline", "parity", "secondary", "value_end_to_end", "strong_scaling_217"):
+        assert key not in line, key
+    assert ("rccl" in line) == (world > 1)
+    scores = np.load(tmp_path / "dump" / "scores.npy")
+    assert scores.dtype == np.float64 and scores.shape == (world * 4996,)
 
 
 # ---- run_indels: a job that dies is taken up where its saved slices ended -------------------------------------------------------
