@@ -56,8 +56,8 @@ def load_tokenizer(path: str):
 
 # -- scoring plan ----------------------------------------------------------------------------------------------------------
 def chunks(prot: str, model_context_len: int = MODEL_CONTEXT_LEN):
-    """compute_fitness.py:19-30: one chunk below the context length, else 1 + int(len / n) windows (the last one empty when the
-    length is a multiple of n)."""
+    """compute_fitness.py:19-30 (and progen2/compute_fitness.py:44-53): one chunk below the context length, else 1 + int(len / n)
+    windows (the last one empty when the length is a multiple of n)."""
     if len(prot) < model_context_len:
         return [prot]
     n = 1 + int(len(prot) / model_context_len)
@@ -209,24 +209,25 @@ def load_checkpoint(checkpoint_dir: str):
 
 
 # -- model -----------------------------------------------------------------------------------------------------------------
-class CausalLM:
-    """Device-resident RITA or ProtGPT2 (f16x3)."""
+class DecoderHandle:
+    """A device-resident causal decoder (f16x3) behind its libpgmi handle: the blob-size check against the library's count, create,
+    close and token_logprobs.  Subclasses (CausalLM, progen2.ProGen2Model) name their arch, C entries and weight count."""
+    ARCH: int
+    CREATE = TOKEN_LOGPROBS = ""            # pgmi_*_model_create(cfg, arch_arg, ...), pgmi_*_token_logprobs
 
-    def __init__(self, cfg: dict, weights: np.ndarray, device: int = 0, max_rows: int = 0):
+    def __init__(self, cfg: dict, weights: np.ndarray, arch_arg: int, device: int = 0, max_rows: int = 0):
         lib = _lib.load()
         self.cfg = dict(cfg)
-        self.family = cfg["family"]
-        pos = POS_KIND[self.family]
-        c = Config(abi_version=_lib.ABI_VERSION, arch=_lib.ARCH_GPT, layers=cfg["layers"], embed_dim=cfg["embed_dim"],
+        c = Config(abi_version=_lib.ABI_VERSION, arch=self.ARCH, layers=cfg["layers"], embed_dim=cfg["embed_dim"],
                    heads=cfg["heads"], ffn_dim=cfg["ffn_dim"], vocab=cfg["vocab"], max_positions=cfg["max_positions"],
                    token_dropout=0, emb_layer_norm_before=0, precision=_lib.PREC_F16X3, max_rows=max_rows,
                    ln_eps=cfg.get("ln_eps", 1e-5))
         w = _lib.as_f32(weights)
-        n = lib.pgmi_gpt_weight_count(C.byref(c), pos)
+        n = self._weight_count(lib, c, arch_arg)
         if w.size != n:
             raise PgmiError(f"weight blob has {w.size} elements, config needs {n}")
         h = C.c_void_p()
-        _lib.check(lib.pgmi_gpt_model_create(C.byref(c), pos, _lib.ptr(w, _lib._f32p), w.size, device, C.byref(h)))
+        _lib.check(getattr(lib, self.CREATE)(C.byref(c), arch_arg, _lib.ptr(w, _lib._f32p), w.size, device, C.byref(h)))
         self._h = h
 
     def close(self):
@@ -245,8 +246,21 @@ class CausalLM:
         t = _lib.as_i32(np.atleast_2d(np.asarray(input_ids)))
         B, T = t.shape
         out = np.empty((B, T, self.cfg["vocab"]), dtype=np.float32)
-        _lib.check(_lib.load().pgmi_gpt_token_logprobs(self._h, _lib.ptr(t, _lib._i32p), B, T, _lib.ptr(out, _lib._f32p)))
+        _lib.check(getattr(_lib.load(), self.TOKEN_LOGPROBS)(self._h, _lib.ptr(t, _lib._i32p), B, T, _lib.ptr(out, _lib._f32p)))
         return out
+
+
+class CausalLM(DecoderHandle):
+    """Device-resident RITA or ProtGPT2 (f16x3)."""
+    ARCH, CREATE, TOKEN_LOGPROBS = _lib.ARCH_GPT, "pgmi_gpt_model_create", "pgmi_gpt_token_logprobs"
+
+    def __init__(self, cfg: dict, weights: np.ndarray, device: int = 0, max_rows: int = 0):
+        self.family = cfg["family"]
+        super().__init__(cfg, weights, POS_KIND[self.family], device, max_rows)
+
+    @staticmethod
+    def _weight_count(lib, c, pos_kind):
+        return lib.pgmi_gpt_weight_count(C.byref(c), pos_kind)
 
     def sequence_loglik(self, rows: Sequence[np.ndarray]):
         """Whole (chunk, direction) id rows of any lengths -> (sum of log p(ids[t+1] | ids[<=t]) as float64, target count), in one
@@ -282,7 +296,7 @@ def from_pretrained(checkpoint_dir: str, device: int = 0, max_rows: int = 0) -> 
     return model
 
 
-# -- assay CLIs (score_rita_proteingym.py, score_protgpt2_proteingym.py) ---------------------------------------------------
+# -- assay CLIs (score_rita_proteingym.py, score_protgpt2_proteingym.py; the assay I/O of score_progen2_proteingym.py) -----
 def get_mutated_sequence(focus_seq, mutant, start_idx=1, AA_vocab="ACDEFGHIKLMNPQRSTVWY"):
     """compute_fitness.py:46-61: the substituted sequence (substitutions only)."""
     mutated = list(focus_seq)
@@ -308,24 +322,36 @@ def add_common_flags(p, model_flag: str, model_help: str):
     p.add_argument("--max_rows", type=int, default=0, help="workspace rows per device call (0 = library default)")
 
 
-def score_assay(args, model_path: str, name: str, score_col: str, out_cols):
-    """compute_fitness.py main() of both scorers: resolve assay --DMS_index, build mutated_sequence only when the column is missing
-    and --indel_mode is off, score, write <output_scores_folder>/<DMS_id>.csv."""
+def load_assay(args, name: str, model_path: str):
+    """compute_fitness.py main()'s assay resolution (all three causal-LM scorers): row --DMS_index of the reference file ->
+    (DMS_id, upper-case target_seq, the assay's rows), after the reference's "Computing scores for" line."""
     import pandas as pd
-    encode = load_tokenizer(args.tokenizer_path or model_path)
-    model = from_pretrained(model_path, device=args.device, max_rows=args.max_rows)
     mapping = pd.read_csv(args.DMS_reference_file_path)
     DMS_id = mapping["DMS_id"][args.DMS_index]
     print("Computing scores for: {} with {}: {}".format(DMS_id, name, model_path))
     row = mapping[mapping["DMS_id"] == DMS_id]
     DMS_file_name = row["DMS_filename"].values[0]
     target_seq = row["target_seq"].values[0].upper()
-    DMS_data = pd.read_csv(os.path.join(args.DMS_data_folder, DMS_file_name), low_memory=False)
-    if not args.indel_mode and "mutated_sequence" not in DMS_data.columns:
-        DMS_data["mutated_sequence"] = DMS_data["mutant"].apply(lambda x: get_mutated_sequence(target_seq, x))
-    DMS_data[score_col] = model.calc_fitness(list(DMS_data["mutated_sequence"]), encode)
+    return DMS_id, target_seq, pd.read_csv(os.path.join(args.DMS_data_folder, DMS_file_name), low_memory=False)
+
+
+def write_scores(args, DMS_id: str, DMS_data, out_cols) -> str:
+    """The columns out_cols of the scored assay to <output_scores_folder>/<DMS_id>.csv; returns the path."""
     os.makedirs(args.output_scores_folder, exist_ok=True)
     out = os.path.join(args.output_scores_folder, DMS_id + ".csv")
     DMS_data[out_cols].to_csv(out, index=False)
+    return out
+
+
+def score_assay(args, model_path: str, name: str, score_col: str, out_cols):
+    """compute_fitness.py main() of both scorers: resolve assay --DMS_index, build mutated_sequence only when the column is missing
+    and --indel_mode is off, score, write <output_scores_folder>/<DMS_id>.csv."""
+    encode = load_tokenizer(args.tokenizer_path or model_path)
+    model = from_pretrained(model_path, device=args.device, max_rows=args.max_rows)
+    DMS_id, target_seq, DMS_data = load_assay(args, name, model_path)
+    if not args.indel_mode and "mutated_sequence" not in DMS_data.columns:
+        DMS_data["mutated_sequence"] = DMS_data["mutant"].apply(lambda x: get_mutated_sequence(target_seq, x))
+    DMS_data[score_col] = model.calc_fitness(list(DMS_data["mutated_sequence"]), encode)
+    out = write_scores(args, DMS_id, DMS_data, out_cols)
     model.close()
     return out

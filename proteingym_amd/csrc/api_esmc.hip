@@ -55,8 +55,6 @@ int create_esmc(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n
     c.upload(&m->hln_b, D);
     c.upload(&m->esmc_head_w, V * D);
     c.upload(&m->h_bias, V);
-    const std::vector<float> zeros(D, 0.0f);
-    c.upload(&m->esmc_zero, zeros.data(), D);
     int rc = c.finish();
     if (!rc) rc = upload_rotate_half(m, 1026);
     return rc;
@@ -124,7 +122,7 @@ int run_esmc_rows(pgmi_model* m, int B, int T, int R, const int32_t* row_idx) {
             src = m->h;
         }
         // transformer_stack.py:62 (LayerNorm without bias), then regression_head.py
-        launch_layernorm16(src, m->lna_w, m->esmc_zero, R, D, 1e-5f, m->h16, m->h16_plane, 1, s);
+        launch_layernorm16(src, m->lna_w, m->zeros, R, D, 1e-5f, m->h16, m->h16_plane, 1, s);
         rc = linear(m, nullptr, m->h16, m->h16_plane, nullptr, m->hd16, m->hd_b, nullptr, m->g, nullptr, 0, R, D, D, EPI_GELU);
         if (rc) return rc;
         launch_layernorm(m->g, m->hln_w, m->hln_b, R, D, 1e-5f, m->g, s);

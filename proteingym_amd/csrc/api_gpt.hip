@@ -1,12 +1,14 @@
-// Causal decoder with a sequential pre-LN residual: RITA (proteingym/baselines/rita/rita_modeling.py) and ProtGPT2, a GPT-2
-// (transformers GPT2LMHeadModel; proteingym/baselines/protgpt2/compute_fitness.py).  Model creation, the forward, the two LM heads
-// and the C entries.
+// Causal decoder: RITA (proteingym/baselines/rita/rita_modeling.py) and ProtGPT2, a GPT-2 (transformers GPT2LMHeadModel;
+// proteingym/baselines/protgpt2/compute_fitness.py), and the body and 32-column head of ProGen2 (api_progen2.hip).  Model creation of
+// RITA / ProtGPT2, the forward, the two LM heads and the C entries.
 //
-// Per layer (rita_modeling.py:208-219; GPT2Block): x += out_proj(attn(ln_1(x)));  x += fc_out(gelu_tanh(fc_in(ln_2(x)))).  The
-// attention runs on the kernels the other causal LMs use: the fused QKV epilogue (RITA: ESM2's rotate-half rotary tables) and
-// attention_f16x3_v2 with all-zero ALiBi slopes (the ALiBi term is then exactly 0).  Heads: V <= 64 (RITA: 26) on one wave per row
-// (vocab_logsoftmax_kernel); wider ones (ProtGPT2: 50 257, tied to wte) on the f16x3 GEMM into fp32 logits, then one workgroup per
-// row (wide_logsoftmax_kernel).  When scoring, only the rows that have a target reach the head.
+// Per layer, sequential pre-LN residual (rita_modeling.py:208-219; GPT2Block): x += out_proj(attn(ln_1(x)));
+// x += fc_out(gelu_tanh(fc_in(ln_2(x)))).  Parallel residual (ProGen2, modeling_progen.py:252-283): h = ln_1(x);
+// x += out_proj(attn(h)) + fc_out(gelu_new(fc_in(h))).  The attention runs on the kernels the other causal LMs use: the fused QKV
+// epilogue (RITA: ESM2's rotate-half rotary tables; ProGen2: GPT-J's, in the same layout) and attention_f16x3_v2 with all-zero ALiBi
+// slopes (the ALiBi term is then exactly 0).  Heads: V <= 64 (RITA: 26, ProGen2: 32) on one wave per row (vocab_logsoftmax_kernel);
+// wider ones (ProtGPT2: 50 257, tied to wte) on the f16x3 GEMM into fp32 logits, then one workgroup per row (wide_logsoftmax_kernel).
+// When scoring, only the rows that have a target reach the head.
 #include "model.h"
 
 namespace pgmi {
@@ -23,7 +25,7 @@ int64_t gpt_weight_count(const pgmi_config* c, int pos_kind) {
 }
 
 int create_gpt(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights, int pos_kind) {
-    const size_t D = cfg->embed_dim, F = cfg->ffn_dim, V = cfg->vocab, H = cfg->heads, dh = m->dh, Da = m->Da;
+    const size_t D = cfg->embed_dim, F = cfg->ffn_dim, V = cfg->vocab, dh = m->dh, Da = m->Da;
     const bool rotary = pos_kind == PGMI_GPT_POS_ROTARY;
     m->gpt_pos = pos_kind;
     BlobCursor c(m, w, n_weights);
@@ -59,6 +61,7 @@ int create_gpt(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_
     m->gpt_Vp = (int)Vp;
     if (!wide_head(*cfg)) {
         c.upload(&m->gpt_head_w, head, V * D);
+        m->gpt_head_b = m->zeros;
     } else {
         // zero rows V .. Vp-1: whole 64-column GEMM tiles; the log-softmax excludes those columns by index
         std::vector<float> padded(Vp * D, 0.0f);
@@ -66,9 +69,6 @@ int create_gpt(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_
         c.w16(&m->gpt_head16, padded.data(), padded.size(), D);
         m->gpt_head_rows = std::min(m->max_rows, kWideHeadRows);
     }
-    const std::vector<float> zeros(std::max(Vp, D), 0.0f), zs(H, 0.0f);
-    c.upload(&m->gpt_zero, zeros.data(), zeros.size());
-    c.upload(&m->gpt_slopes, zs.data(), zs.size());
     int rc = c.finish();
     if (!rc && m->gpt_head_rows) rc = dev_alloc(m->allocs, &m->gpt_logits, (size_t)m->gpt_head_rows * Vp);
     if (!rc) rc = dev_alloc(m->allocs, &m->gpt_sum, (size_t)m->max_rows);
@@ -77,7 +77,7 @@ int create_gpt(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_
 }
 
 // The decoder body on tokens in m->tokens [B,T]; leaves the residual stream after the last layer in m->x [B*T, D].
-static int run_gpt_body(pgmi_model* m, int B, int T) {
+int run_decoder(pgmi_model* m, int B, int T) {
     const pgmi_config& c = m->cfg;
     const int M = B * T, D = c.embed_dim, F = c.ffn_dim, H = c.heads, Da = m->Da;
     const bool rotary = m->gpt_pos == PGMI_GPT_POS_ROTARY;
@@ -85,9 +85,16 @@ static int run_gpt_body(pgmi_model* m, int B, int T) {
     int rc = reset_pad_keys(m, B, T);
     if (rc) return rc;
     { ProfScope p(m, PGMI_K_EMBED, 0, (double)M * D * (rotary ? 4 : 8));
-      if (rotary) launch_gather_rows(m->embed_tokens, m->tokens, M, D, m->x, s);        // rita_modeling.py:255: no positional table
+      if (rotary) launch_gather_rows(m->embed_tokens, m->tokens, M, D, m->x, s);        // RITA, ProGen2: no positional table
       else launch_embed_learned(m->tokens, m->embed_tokens, m->embed_positions, M, T, D, m->x, s); }
     const double ln_bytes = 2.0 * M * D * 4;
+    auto mlp = [&](const Layer& L) {                                  // x += fc_out(gelu_tanh(fc_in(h16)))
+        { ProfScope p(m, PGMI_K_GEMM_FC1, 2.0 * M * F * D, 0);
+          int rc = linear(m, nullptr, m->h16, m->h16_plane, nullptr, L.w116, L.b1, nullptr, nullptr, m->g16, m->g16_plane, M, F, D, EPI_GELU_TANH);
+          if (rc) return rc; }
+        ProfScope p(m, PGMI_K_GEMM_FC2, 2.0 * M * F * D, 0);
+        return linear(m, nullptr, m->g16, m->g16_plane, nullptr, L.w216, L.b2, m->x, m->x, nullptr, 0, M, D, F, EPI_NONE);
+    };
     for (int l = 0; l < c.layers; ++l) {
         const Layer& L = m->layers[l];
         { ProfScope p(m, PGMI_K_LAYERNORM, 0, ln_bytes);
@@ -97,21 +104,23 @@ static int run_gpt_body(pgmi_model* m, int B, int T) {
                                  m->qk16, m->qk16_plane, m->vt16, m->vt16_plane, m->rot_cos, m->rot_sin, rotary, T, m->Hs,
                                  m->gemm_variant, s, m->rot_halves, false);
           if (rc) return rc; }
+        if (m->parallel_residual) {             // the MLP branch first: it reads ln_1's output, which the context rows then overwrite
+            rc = mlp(L);
+            if (rc) return rc;
+        }
         { ProfScope p(m, PGMI_K_ATTENTION, 2.0 * M * T * Da, 0);             // causal: half of the 4 M T Da of a dense pass
           rc = launch_attention_f16x3_v2(nullptr, nullptr, m->rot_cos, m->rot_sin, rotary, B, T, H, m->qk16, m->qk16_plane, m->vt16,
-                                         m->vt16_plane, nullptr, m->h16, m->h16_plane, 1, s, nullptr, m->gpt_slopes, m->rot_halves * kHeadDim);
+                                         m->vt16_plane, nullptr, m->h16, m->h16_plane, 1, s, nullptr, m->zeros, m->rot_halves * kHeadDim);
           if (rc) return rc; }
         { ProfScope p(m, PGMI_K_GEMM_OUT, 2.0 * M * D * Da, 0);
           rc = linear(m, nullptr, m->h16, m->h16_plane, nullptr, L.wo16, L.bo, m->x, m->x, nullptr, 0, M, D, Da, EPI_NONE);
           if (rc) return rc; }
-        { ProfScope p(m, PGMI_K_LAYERNORM, 0, ln_bytes);
-          launch_layernorm16(m->x, L.ln2_w, L.ln2_b, M, D, m->ln_eps, m->h16, m->h16_plane, 1, s); }
-        { ProfScope p(m, PGMI_K_GEMM_FC1, 2.0 * M * F * D, 0);
-          rc = linear(m, nullptr, m->h16, m->h16_plane, nullptr, L.w116, L.b1, nullptr, nullptr, m->g16, m->g16_plane, M, F, D, EPI_GELU_TANH);
-          if (rc) return rc; }
-        { ProfScope p(m, PGMI_K_GEMM_FC2, 2.0 * M * F * D, 0);
-          rc = linear(m, nullptr, m->g16, m->g16_plane, nullptr, L.w216, L.b2, m->x, m->x, nullptr, 0, M, D, F, EPI_NONE);
-          if (rc) return rc; }
+        if (!m->parallel_residual) {
+            { ProfScope p(m, PGMI_K_LAYERNORM, 0, ln_bytes);
+              launch_layernorm16(m->x, L.ln2_w, L.ln2_b, M, D, m->ln_eps, m->h16, m->h16_plane, 1, s); }
+            rc = mlp(L);
+            if (rc) return rc;
+        }
     }
     return PGMI_OK;
 }
@@ -124,7 +133,7 @@ static int wide_head_rows(pgmi_model* m, int R, const int32_t* tgt, float* out, 
     for (int r0 = 0; r0 < R; r0 += m->gpt_head_rows) {
         const int rc_rows = std::min(m->gpt_head_rows, R - r0);
         { ProfScope p(m, PGMI_K_HEAD, 2.0 * rc_rows * Vp * D, 0);
-          int rc = linear(m, nullptr, m->h16 + (size_t)r0 * 2 * D, m->h16_plane, nullptr, m->gpt_head16, m->gpt_zero, nullptr,
+          int rc = linear(m, nullptr, m->h16 + (size_t)r0 * 2 * D, m->h16_plane, nullptr, m->gpt_head16, m->zeros, nullptr,
                           m->gpt_logits, nullptr, 0, rc_rows, Vp, D, EPI_NONE);
           if (rc) return rc; }
         { ProfScope p(m, PGMI_K_SCORE, 0, (double)rc_rows * V * 4 * (tgt ? 1 : 3));
@@ -137,11 +146,49 @@ static int wide_head_rows(pgmi_model* m, int R, const int32_t* tgt, float* out, 
     return PGMI_OK;
 }
 
-static int gpt_check(pgmi_model* m, int T) {
-    if (m->cfg.arch != PGMI_ARCH_GPT) { set_error("not a causal decoder (RITA / ProtGPT2) model"); return PGMI_EINVAL; }
-    if (T > m->cfg.max_positions) { set_error("sequence of %d tokens exceeds the model context of %d positions", T, m->cfg.max_positions); return PGMI_EINVAL; }
+// Arch, context and workspace checks of a causal-decoder entry for input length T; `arch` is the entry's, the messages its own.
+int decoder_check(pgmi_model* m, int arch, int T) {
+    const bool pg2 = arch == PGMI_ARCH_PROGEN2;
+    if (m->cfg.arch != arch) { set_error(pg2 ? "not a ProGen2 model" : "not a causal decoder (RITA / ProtGPT2) model"); return PGMI_EINVAL; }
+    if (T > m->cfg.max_positions) {
+        set_error(pg2 ? "sequence of %d tokens exceeds the model context n_positions=%d"
+                      : "sequence of %d tokens exceeds the model context of %d positions", T, m->cfg.max_positions);
+        return PGMI_EINVAL;
+    }
     if (T + 31 > m->max_rows) { set_error("T=%d exceeds workspace rows %d", T, m->max_rows); return PGMI_EINVAL; }
     return PGMI_OK;
+}
+
+// pgmi_gpt_token_logprobs and pgmi_pg2_token_logprobs: log-probabilities over all V columns, [B,T,V] to out.
+int decoder_token_logprobs(pgmi_model* m, int arch, const int32_t* tokens, int B, int T, float* out) {
+    if (!m || !tokens || !out || B <= 0 || T <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
+    int rc = decoder_check(m, arch, T);
+    if (rc) return rc;
+    const pgmi_config& c = m->cfg;
+    const int V = c.vocab, D = c.embed_dim;
+    rc = check_vocab(tokens, B, T, V);
+    if (rc) return rc;
+    PGMI_HIP(hipSetDevice(m->device));
+    hipStream_t s = m->stream;
+    rc = for_each_chunk(m, B, T, [&](int b0, int bc) {
+        const int M = bc * T;
+        PGMI_HIP(hipMemcpyAsync(m->tokens, tokens + (size_t)b0 * T, (size_t)M * 4, hipMemcpyHostToDevice, s));
+        int rc = run_decoder(m, bc, T);
+        if (rc) return rc;
+        float* dst = out + (size_t)b0 * T * V;
+        if (wide_head(c)) {
+            { ProfScope p(m, PGMI_K_LAYERNORM, 0, 2.0 * M * D * 4);
+              launch_layernorm16(m->x, m->lna_w, m->lna_b, M, D, m->ln_eps, m->h16, m->h16_plane, 1, s); }
+            return wide_head_rows(m, M, nullptr, nullptr, dst);
+        }
+        { ProfScope p(m, PGMI_K_HEAD, 2.0 * M * D * V, 0);
+          launch_layernorm(m->x, m->lna_w, m->lna_b, M, D, m->ln_eps, m->h, s);
+          launch_vocab_logsoftmax(m->h, m->gpt_head_w, m->gpt_head_b, M, D, V, m->lp, m->nonfinite, s); }
+        PGMI_HIP(hipGetLastError());
+        PGMI_HIP(hipMemcpyAsync(dst, m->lp, (size_t)M * V * 4, hipMemcpyDeviceToHost, s));
+        return PGMI_OK;
+    });
+    return rc ? rc : check_nonfinite(m);
 }
 
 }  // namespace pgmi
@@ -160,40 +207,14 @@ int pgmi_gpt_model_create(const pgmi_config* cfg, int pos_kind, const float* wei
 }
 
 int pgmi_gpt_token_logprobs(pgmi_model* m, const int32_t* tokens, int B, int T, float* out) {
-    if (!m || !tokens || !out || B <= 0 || T <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
-    int rc = gpt_check(m, T);
-    if (rc) return rc;
-    const pgmi_config& c = m->cfg;
-    const int V = c.vocab, D = c.embed_dim;
-    rc = check_vocab(tokens, B, T, V);
-    if (rc) return rc;
-    PGMI_HIP(hipSetDevice(m->device));
-    hipStream_t s = m->stream;
-    rc = for_each_chunk(m, B, T, [&](int b0, int bc) {
-        const int M = bc * T;
-        PGMI_HIP(hipMemcpyAsync(m->tokens, tokens + (size_t)b0 * T, (size_t)M * 4, hipMemcpyHostToDevice, s));
-        int rc = run_gpt_body(m, bc, T);
-        if (rc) return rc;
-        float* dst = out + (size_t)b0 * T * V;
-        if (wide_head(c)) {
-            { ProfScope p(m, PGMI_K_LAYERNORM, 0, 2.0 * M * D * 4);
-              launch_layernorm16(m->x, m->lna_w, m->lna_b, M, D, m->ln_eps, m->h16, m->h16_plane, 1, s); }
-            return wide_head_rows(m, M, nullptr, nullptr, dst);
-        }
-        { ProfScope p(m, PGMI_K_HEAD, 2.0 * M * D * V, 0);
-          launch_layernorm(m->x, m->lna_w, m->lna_b, M, D, m->ln_eps, m->h, s);
-          launch_vocab_logsoftmax(m->h, m->gpt_head_w, m->gpt_zero, M, D, V, m->lp, m->nonfinite, s); }
-        PGMI_HIP(hipMemcpyAsync(dst, m->lp, (size_t)M * V * 4, hipMemcpyDeviceToHost, s));
-        return PGMI_OK;
-    });
-    return rc ? rc : check_nonfinite(m);
+    return decoder_token_logprobs(m, PGMI_ARCH_GPT, tokens, B, T, out);
 }
 
 int pgmi_gpt_sequence_loglik(pgmi_model* m, const int32_t* tokens, const int32_t* lens, int B, int T, double* sum, int32_t* n_targets) {
     if (!m || !tokens || !lens || !sum || B <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
     if (T < 2) { set_error("rows of %d tokens: the model needs at least one input and one target token", T); return PGMI_EINVAL; }
     const int Ti = T - 1;                                           // the model reads tokens[:, :T-1]; targets are tokens[:, 1:]
-    int rc = gpt_check(m, Ti);
+    int rc = decoder_check(m, PGMI_ARCH_GPT, Ti);
     if (!rc) rc = check_vocab(tokens, B, T, m->cfg.vocab);
     if (rc) return rc;
     for (int b = 0; b < B; ++b)
@@ -220,7 +241,7 @@ int pgmi_gpt_sequence_loglik(pgmi_model* m, const int32_t* tokens, const int32_t
         PGMI_HIP(hipMemcpyAsync(m->row_idx, idx.data(), (size_t)R * 4, hipMemcpyHostToDevice, s));
         PGMI_HIP(hipMemcpyAsync(m->aux_i, tgt.data(), (size_t)R * 4, hipMemcpyHostToDevice, s));
         PGMI_HIP(hipMemcpyAsync(m->kv_len, off.data(), (size_t)(bc + 1) * 4, hipMemcpyHostToDevice, s));
-        int rc = run_gpt_body(m, bc, Ti);
+        int rc = run_decoder(m, bc, Ti);
         if (rc) return rc;
         { ProfScope p(m, PGMI_K_EMBED, 0, 2.0 * R * D * 4);
           launch_gather_rows(m->x, m->row_idx, R, D, m->g, s); }                 // pad rows and last rows never reach the head
@@ -232,7 +253,7 @@ int pgmi_gpt_sequence_loglik(pgmi_model* m, const int32_t* tokens, const int32_t
         } else {
             ProfScope p(m, PGMI_K_HEAD, 2.0 * R * D * V, 0);
             launch_layernorm(m->g, m->lna_w, m->lna_b, R, D, m->ln_eps, m->h, s);
-            launch_vocab_logsoftmax(m->h, m->gpt_head_w, m->gpt_zero, R, D, V, m->lp, m->nonfinite, s);
+            launch_vocab_logsoftmax(m->h, m->gpt_head_w, m->gpt_head_b, R, D, V, m->lp, m->nonfinite, s);
             launch_pppl_pick(m->lp, m->aux_i, R, V, m->denom, s);
         }
         launch_seq_sum(m->denom, m->kv_len, bc, m->gpt_sum, s);

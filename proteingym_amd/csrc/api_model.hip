@@ -307,7 +307,10 @@ int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int 
     m->Da = m->Hs * kHeadDim;
     m->ln_eps = cfg->ln_eps > 0.f ? cfg->ln_eps : 1e-5f;
     m->max_rows = std::max(cfg->max_rows > 0 ? cfg->max_rows : 98304, 2048);
-    switch (cfg->arch) {
+    const size_t V = cfg->vocab;
+    const std::vector<float> zeros(std::max({3 * (size_t)m->Da, (V + 63) / 64 * 64, (size_t)cfg->embed_dim, V, (size_t)cfg->heads}), 0.0f);
+    rc = dev_upload(m->allocs, &m->zeros, zeros.data(), zeros.size());
+    if (!rc) switch (cfg->arch) {
         case PGMI_ARCH_TRANCEPTION: rc = create_tranception(m, cfg, w, n_weights); break;
         case PGMI_ARCH_MSA: rc = create_msa(m, cfg, w, n_weights); break;
         case PGMI_ARCH_PROGEN2: rc = create_progen2(m, cfg, w, n_weights, arch_arg); break;

@@ -1,9 +1,11 @@
-// ProGen2 (proteingym/baselines/progen2/models/progen/modeling_progen.py): model creation, the forward and its C entries.
+// ProGen2 (proteingym/baselines/progen2/models/progen/modeling_progen.py): model creation, the 25-column amino-acid head of the
+// scoring entry and the C entries.
 //
 // Per layer (ProGenBlock, :252-283): h = ln_1(x);  x = x + out_proj(attn(h)) + fc_out(gelu_new(fc_in(h))) -- one LayerNorm, two
 // branches that read it, both residual-adding into x.  The attention (:109-145, :147-224) is causal, scores in fp32 scaled by
-// head_dim^-1/2, with GPT-J rotary on the first rotary_dim dims of q and k.  It runs on the kernels the other causal LM uses: the fused
-// QKV epilogue (rotary, split planes, V^T) and attention_f16x3_v2 with all-zero ALiBi slopes (the ALiBi term is then exactly 0).
+// head_dim^-1/2, with GPT-J rotary on the first rotary_dim dims of q and k.  The forward is the causal decoder's (api_gpt.hip) in its
+// parallel-residual order: the fused QKV epilogue (rotary, split planes, V^T) and attention_f16x3_v2 with all-zero ALiBi slopes (the
+// ALiBi term is then exactly 0); the bias-free projections pass the model's zero vector as their bias.
 #include "model.h"
 
 namespace pgmi {
@@ -20,7 +22,7 @@ static int pg2_slot(int j, int rd) {
 }
 
 int create_progen2(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights, int rotary_dim) {
-    const size_t D = cfg->embed_dim, F = cfg->ffn_dim, V = cfg->vocab, H = cfg->heads;
+    const size_t D = cfg->embed_dim, F = cfg->ffn_dim, V = cfg->vocab;
     const int dh = m->dh, G = m->rot_halves;
     const size_t Da = m->Da;
     if (rotary_dim < 2 || rotary_dim > dh || rotary_dim % 2) {
@@ -28,6 +30,8 @@ int create_progen2(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_
         return PGMI_EINVAL;
     }
     m->pg2_rotary = rotary_dim;
+    m->gpt_pos = PGMI_GPT_POS_ROTARY;                              // the decoder body: no positional table, q / k rotated by the tables
+    m->parallel_residual = true;
     BlobCursor c(m, w, n_weights);
     c.upload(&m->embed_tokens, V * D);
     auto slot = [&](size_t col) -> size_t {                        // attention column of model dim `col` (head-major)
@@ -46,6 +50,7 @@ int create_progen2(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_
         c.w16(&L.wqkv16, wq.data(), wq.size(), D);
         pack_out_cols(c.take(D * D), D, Da, slot, wo_r.data());
         c.w16(&L.wo16, wo_r.data(), wo_r.size(), Da);
+        L.bqkv = L.bo = m->zeros;                                  // qkv_proj and out_proj have no bias
         c.w16(&L.w116, F * D, D);
         c.upload(&L.b1, F);
         c.w16(&L.w216, D * F, F);
@@ -54,14 +59,11 @@ int create_progen2(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_
     c.upload(&m->lna_w, D);
     c.upload(&m->lna_b, D);
     const float* head_w = c.take(V * D);
-    c.upload(&m->pg2_head_w, head_w, V * D);
+    c.upload(&m->gpt_head_w, head_w, V * D);
     c.upload(&m->pg2_aa_w, head_w + 5 * D, 25 * D);               // rows 5..29: the amino-acid columns (compute_fitness.py:67-70)
     const float* head_b = c.take(V);
-    c.upload(&m->pg2_head_b, head_b, V);
+    c.upload(&m->gpt_head_b, head_b, V);
     c.upload(&m->pg2_aa_b, head_b + 5, 25);
-    const std::vector<float> zeros(std::max(3 * Da, D), 0.0f), zs(H, 0.0f);
-    c.upload(&m->pg2_zero, zeros.data(), zeros.size());
-    c.upload(&m->pg2_slopes, zs.data(), zs.size());
     int rc = c.finish();
     if (rc) return rc;
     // cos / sin tables: slot i and 32 + i of group g hold the angle of pair position 32 g + i.  The angle is fp32(t) * inv_freq in
@@ -75,58 +77,6 @@ int create_progen2(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_
     });
 }
 
-// ProGen2 forward on tokens in m->tokens [B,T]; leaves log-probabilities in m->lp: [B*T, 32] (aa_only = false) or the log-softmax over
-// columns 5..29 only, [B*T, 25] (aa_only = true).
-static int run_progen2(pgmi_model* m, int B, int T, bool aa_only) {
-    const pgmi_config& c = m->cfg;
-    const int M = B * T, D = c.embed_dim, F = c.ffn_dim, H = c.heads, Da = m->Da;
-    hipStream_t s = m->stream;
-    if (T > c.max_positions) { set_error("sequence of %d tokens exceeds the model context n_positions=%d", T, c.max_positions); return PGMI_EINVAL; }
-    int rc = reset_pad_keys(m, B, T);
-    if (rc) return rc;
-    { ProfScope p(m, PGMI_K_EMBED, 0, (double)M * D * 4);
-      launch_gather_rows(m->embed_tokens, m->tokens, M, D, m->x, s); }       // wte[input_ids]: no positional table, no embedding LayerNorm
-    const double ln_bytes = 2.0 * M * D * 4;
-    for (int l = 0; l < c.layers; ++l) {
-        const Layer& L = m->layers[l];
-        { ProfScope p(m, PGMI_K_LAYERNORM, 0, ln_bytes);
-          launch_layernorm16(m->x, L.ln1_w, L.ln1_b, M, D, m->ln_eps, m->h16, m->h16_plane, 1, s); }
-        { ProfScope p(m, PGMI_K_GEMM_QKV, 2.0 * M * 3 * Da * D, 0);
-          rc = launch_gemm16_qkv(m->h16, m->h16_plane, L.wqkv16.p, L.wqkv16.plane, m->pg2_zero, M, Da, D, L.wqkv16.out_scale,
-                                 m->qk16, m->qk16_plane, m->vt16, m->vt16_plane, m->rot_cos, m->rot_sin, 1, T, m->Hs,
-                                 m->gemm_variant, s, m->rot_halves, false);
-          if (rc) return rc; }
-        // the MLP branch first: it reads ln_1's output, which the attention's context rows then overwrite in h16
-        { ProfScope p(m, PGMI_K_GEMM_FC1, 2.0 * M * F * D, 0);
-          rc = linear(m, nullptr, m->h16, m->h16_plane, nullptr, L.w116, L.b1, nullptr, nullptr, m->g16, m->g16_plane, M, F, D, EPI_GELU_TANH);
-          if (rc) return rc; }
-        { ProfScope p(m, PGMI_K_GEMM_FC2, 2.0 * M * F * D, 0);
-          rc = linear(m, nullptr, m->g16, m->g16_plane, nullptr, L.w216, L.b2, m->x, m->x, nullptr, 0, M, D, F, EPI_NONE);
-          if (rc) return rc; }
-        { ProfScope p(m, PGMI_K_ATTENTION, 2.0 * M * T * Da, 0);             // causal: half of the 4 M T Da of a dense pass
-          rc = launch_attention_f16x3_v2(nullptr, nullptr, m->rot_cos, m->rot_sin, 1, B, T, H, m->qk16, m->qk16_plane, m->vt16,
-                                         m->vt16_plane, nullptr, m->h16, m->h16_plane, 1, s, nullptr, m->pg2_slopes, m->rot_halves * kHeadDim);
-          if (rc) return rc; }
-        { ProfScope p(m, PGMI_K_GEMM_OUT, 2.0 * M * D * Da, 0);
-          rc = linear(m, nullptr, m->h16, m->h16_plane, nullptr, L.wo16, m->pg2_zero, m->x, m->x, nullptr, 0, M, D, Da, EPI_NONE);
-          if (rc) return rc; }
-    }
-    const int Vh = aa_only ? 25 : c.vocab;
-    { ProfScope p(m, PGMI_K_HEAD, 2.0 * M * D * Vh, 0);
-      launch_layernorm(m->x, m->lna_w, m->lna_b, M, D, m->ln_eps, m->h, s);
-      launch_vocab_logsoftmax(m->h, aa_only ? m->pg2_aa_w : m->pg2_head_w, aa_only ? m->pg2_aa_b : m->pg2_head_b, M, D, Vh, m->lp,
-                              m->nonfinite, s); }
-    PGMI_HIP(hipGetLastError());
-    return PGMI_OK;
-}
-
-static int pg2_check(pgmi_model* m, int T) {
-    if (m->cfg.arch != PGMI_ARCH_PROGEN2) { set_error("not a ProGen2 model"); return PGMI_EINVAL; }
-    if (T > m->cfg.max_positions) { set_error("sequence of %d tokens exceeds the model context n_positions=%d", T, m->cfg.max_positions); return PGMI_EINVAL; }
-    if (T + 31 > m->max_rows) { set_error("T=%d exceeds workspace rows %d", T, m->max_rows); return PGMI_EINVAL; }
-    return PGMI_OK;
-}
-
 }  // namespace pgmi
 
 extern "C" {
@@ -138,28 +88,14 @@ int pgmi_pg2_model_create(const pgmi_config* cfg, int rotary_dim, const float* w
 }
 
 int pgmi_pg2_token_logprobs(pgmi_model* m, const int32_t* tokens, int B, int T, float* out) {
-    if (!m || !tokens || !out || B <= 0 || T <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
-    int rc = pg2_check(m, T);
-    if (rc) return rc;
-    const int V = m->cfg.vocab;
-    rc = check_vocab(tokens, B, T, V);
-    if (rc) return rc;
-    PGMI_HIP(hipSetDevice(m->device));
-    rc = for_each_chunk(m, B, T, [&](int b0, int bc) {
-        PGMI_HIP(hipMemcpyAsync(m->tokens, tokens + (size_t)b0 * T, (size_t)bc * T * 4, hipMemcpyHostToDevice, m->stream));
-        int rc = run_progen2(m, bc, T, false);
-        if (rc) return rc;
-        PGMI_HIP(hipMemcpyAsync(out + (size_t)b0 * T * V, m->lp, (size_t)bc * T * V * 4, hipMemcpyDeviceToHost, m->stream));
-        return PGMI_OK;
-    });
-    return rc ? rc : check_nonfinite(m);
+    return decoder_token_logprobs(m, PGMI_ARCH_PROGEN2, tokens, B, T, out);
 }
 
 int pgmi_pg2_sequence_loglik(pgmi_model* m, const int32_t* tokens, int B, int L, float* out, int32_t* n_kept) {
     if (!m || !tokens || !out || B <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
     if (L < 2) { set_error("rows of %d tokens: the model needs at least one input and one target token", L); return PGMI_EINVAL; }
     const int T = L - 1;                                            // input = ids[:-1], targets = ids[1:]
-    int rc = pg2_check(m, T);
+    int rc = decoder_check(m, PGMI_ARCH_PROGEN2, T);
     if (!rc) rc = check_vocab(tokens, B, L, m->cfg.vocab);
     if (rc) return rc;
     std::vector<int32_t> in((size_t)B * T), col((size_t)B * T, 0), kept(B);
@@ -181,8 +117,13 @@ int pgmi_pg2_sequence_loglik(pgmi_model* m, const int32_t* tokens, int B, int L,
         PGMI_HIP(hipMemcpyAsync(m->tokens, in.data() + (size_t)b0 * T, (size_t)bc * T * 4, hipMemcpyHostToDevice, s));
         PGMI_HIP(hipMemcpyAsync(m->aux_i, col.data() + (size_t)b0 * T, (size_t)bc * T * 4, hipMemcpyHostToDevice, s));
         PGMI_HIP(hipMemcpyAsync(m->kv_len, kept.data() + b0, (size_t)bc * 4, hipMemcpyHostToDevice, s));
-        int rc = run_progen2(m, bc, T, true);
+        int rc = run_decoder(m, bc, T);
         if (rc) return rc;
+        const int M = bc * T, D = m->cfg.embed_dim;
+        { ProfScope p(m, PGMI_K_HEAD, 2.0 * M * D * 25, 0);           // ln_f, then the log-softmax over columns 5..29 only
+          launch_layernorm(m->x, m->lna_w, m->lna_b, M, D, m->ln_eps, m->h, s);
+          launch_vocab_logsoftmax(m->h, m->pg2_aa_w, m->pg2_aa_b, M, D, 25, m->lp, m->nonfinite, s); }
+        PGMI_HIP(hipGetLastError());
         { ProfScope p(m, PGMI_K_SCORE, 0, (double)bc * T * 8);
           launch_pg2_seq_loglik(m->lp, m->aux_i, m->kv_len, bc, T, 25, m->denom, s); }
         PGMI_HIP(hipMemcpyAsync(out + b0, m->denom, (size_t)bc * 4, hipMemcpyDeviceToHost, s));

@@ -77,8 +77,7 @@ int create_tranception(pgmi_model* m, const pgmi_config* cfg, const float* w, in
     c.upload(&m->lna_w, D);
     c.upload(&m->lna_b, D);
     c.upload(&m->tr_lm_head, V * D);
-    std::vector<float> zb(V, 0.0f), sl;
-    c.upload(&m->tr_zero_bias, zb.data(), zb.size());
+    std::vector<float> sl;
     std::vector<double> quarter = alibi_slopes((int)H / 4);          // grouped: slopes of n/4 heads, tiled 4x
     for (int rep = 0; rep < 4; ++rep)
         for (double v : quarter) sl.push_back((float)v);
@@ -132,7 +131,7 @@ int run_tranception(pgmi_model* m, int B, int T) {
     }
     { ProfScope p(m, PGMI_K_HEAD, 2.0 * M * D * c.vocab, 0);
       launch_layernorm(m->x, m->lna_w, m->lna_b, M, D, m->ln_eps, m->h, s);
-      launch_vocab_logsoftmax(m->h, m->tr_lm_head, m->tr_zero_bias, M, D, c.vocab, m->lp, m->nonfinite, s); }
+      launch_vocab_logsoftmax(m->h, m->tr_lm_head, m->zeros, M, D, c.vocab, m->lp, m->nonfinite, s); }
     PGMI_HIP(hipGetLastError());
     return PGMI_OK;
 }
@@ -249,7 +248,7 @@ int run_tranception_shared(pgmi_model* m, TrChunk& ck, int T, const float* prior
     }
     { ProfScope ps(m, PGMI_K_HEAD, 2.0 * M * D * V, 0);
       launch_layernorm(m->x, m->lna_w, m->lna_b, M, D, m->ln_eps, m->h, s);
-      launch_vocab_logsoftmax(m->h, m->tr_lm_head, m->tr_zero_bias, M, D, V, m->lp, m->nonfinite, s); }
+      launch_vocab_logsoftmax(m->h, m->tr_lm_head, m->zeros, M, D, V, m->lp, m->nonfinite, s); }
     { ProfScope ps(m, PGMI_K_SCORE, 0, (double)S * T * 8);
       launch_seq_loglik_ragged(m->lp, m->tokens, rg.seq_off, rg.seq_p, rg.seq_root, S, T, V, prior_dev, d_pa, d_pr, d_pc, d_pf, alpha,
                                m->denom, s); }

@@ -5,9 +5,10 @@
 //   api_esm.hip          ESM-1b / ESM-1v / ESM2 weights (create_esm) and forward (run_encoder, run_head), masked-marginals assays,
 //                        pseudo-ppl libraries
 //   api_tranception.hip  Tranception weights and forward, dense and prefix-shared; token log-probs and sequence log-likelihoods
-//   api_progen2.hip      ProGen2 weights and forward (parallel residual, GPT-J rotary); token log-probs and sequence log-likelihoods
-//   api_gpt.hip          causal decoder (RITA, ProtGPT2) weights and forward, narrow and wide LM heads; token log-probs and sequence
+//   api_progen2.hip      ProGen2 weights (GPT-J rotary, bias-free projections), its 25-column amino-acid head and sequence
 //                        log-likelihoods
+//   api_gpt.hip          causal decoder: RITA / ProtGPT2 weights, the decoder body (sequential or ProGen2's parallel residual), narrow
+//                        and wide LM heads, the checks and token log-probs of both archs; RITA / ProtGPT2 sequence log-likelihoods
 //   api_esmc.hip         ESM C weights and forward (QK-LayerNorm, SwiGLU, scaled residual, untied 64-column head)
 //   api_msa.hip          MSA Transformer weights and forward (tied row attention, column attention)
 //   api_host.hip         host-only entries: mutant parser, table -> scores, optimal window
@@ -72,23 +73,24 @@ struct pgmi_model {
     float *hd_w = nullptr, *hd_b = nullptr, *hln_w = nullptr, *hln_b = nullptr, *h_bias = nullptr;
     std::vector<Layer> layers;
     W16 hd16;
-    float *tr_lm_head = nullptr, *tr_zero_bias = nullptr, *tr_slopes = nullptr;   // Tranception head / ALiBi slopes
+    float *tr_lm_head = nullptr, *tr_slopes = nullptr;  // Tranception head / ALiBi slopes
     float* tr_prior = nullptr;                          // device copy of the retrieval log-prior [P,V]
     size_t tr_prior_cap = 0;
     int32_t* tr_meta = nullptr;                         // prefix-shared scoring: the chunk's index arrays (TrChunk)
     size_t tr_meta_cap = 0;
-    // ProGen2: rotary_dim, the biased 32-column head and its amino-acid rows 5..29, zero bias of the bias-free projections, zero slopes
+    // ProGen2: rotary_dim and the amino-acid rows 5..29 of its head
     int pg2_rotary = 0;
-    float *pg2_head_w = nullptr, *pg2_head_b = nullptr, *pg2_aa_w = nullptr, *pg2_aa_b = nullptr;
-    float *pg2_zero = nullptr, *pg2_slopes = nullptr;
-    // causal decoder (api_gpt.hip): PGMI_GPT_POS_*, the head -- fp32 lm_head [V,D] (V <= 64) or the f16x3 planes of wte zero-padded to
-    // gpt_Vp = roundup(V, 64) rows -- and the wide head's fp32 logits [gpt_head_rows][gpt_Vp]; per-sequence sums; zero bias / slopes
+    float *pg2_aa_w = nullptr, *pg2_aa_b = nullptr;
+    // causal decoder (api_gpt.hip; ProGen2 runs on it too): PGMI_GPT_POS_*, the residual order, the head -- fp32 weight [V,D] and bias
+    // [V] (V <= 64; RITA's bias is `zeros`) or the f16x3 planes of wte zero-padded to gpt_Vp = roundup(V, 64) rows -- and the wide
+    // head's fp32 logits [gpt_head_rows][gpt_Vp]; per-sequence sums
     int gpt_pos = 0, gpt_Vp = 0, gpt_head_rows = 0;
-    float *gpt_head_w = nullptr, *gpt_logits = nullptr, *gpt_zero = nullptr, *gpt_slopes = nullptr;
+    bool parallel_residual = false;     // ProGen2: attention and MLP both read ln_1's output; else ln_2 follows the attention
+    float *gpt_head_w = nullptr, *gpt_head_b = nullptr, *gpt_logits = nullptr;
     W16 gpt_head16;
     double* gpt_sum = nullptr;
-    // ESM C (api_esmc.hip): the untied head weight [64,D] (its bias is h_bias) and the zero bias of the final LayerNorm
-    float *esmc_head_w = nullptr, *esmc_zero = nullptr;
+    // ESM C (api_esmc.hip): the untied head weight [64,D] (its bias is h_bias)
+    float* esmc_head_w = nullptr;
     // MSA Transformer
     float* msa_pe = nullptr;                            // msa_position_embedding [1024, D]
     float* xt = nullptr;                                // residual stream in column-major token order
@@ -112,6 +114,9 @@ struct pgmi_model {
     int Da = 0;           // attention width = heads * 64 (== embed_dim when dh == 64)
     float *rot_cos = nullptr, *rot_sin = nullptr;
     int rot_len = 0;
+    // max(3 Da, roundup(V, 64), D, V, heads) zeros: the bias of a bias-free QKV / out-projection / wide head GEMM / LayerNorm / head,
+    // and all-zero ALiBi slopes (model_create)
+    float* zeros = nullptr;
     // workspace
     int max_rows = 0;
     float *x = nullptr, *h = nullptr, *qkv = nullptr, *g = nullptr, *lp = nullptr, *denom = nullptr;
@@ -236,6 +241,9 @@ int create_progen2(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_
 // api_gpt.hip
 int create_gpt(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights, int pos_kind);
 int64_t gpt_weight_count(const pgmi_config* c, int pos_kind);
+int decoder_check(pgmi_model* m, int arch, int T);
+int run_decoder(pgmi_model* m, int B, int T);
+int decoder_token_logprobs(pgmi_model* m, int arch, const int32_t* tokens, int B, int T, float* out);
 // api_esmc.hip
 int64_t esmc_weight_count(const pgmi_config* c);
 int create_esmc(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights);

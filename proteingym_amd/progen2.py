@@ -1,9 +1,10 @@
 """ProGen2 scoring on libpgmi (include/pgmi.h, arch PGMI_ARCH_PROGEN2).
 
 Replaces proteingym/baselines/progen2/compute_fitness.py: the checkpoint is packed into the C ABI's blob, the forward runs in
-HIP (csrc/api_progen2.hip), and ``calc_fitness`` reproduces the reference's per-sequence loop -- chunks of n_positions characters,
-each scored in both reading directions, a terminal last target dropped, log-softmax over the 25 amino-acid columns, -mean CE summed,
-halved and divided by the sequence length -- with the equal-length (chunk, direction) rows of all sequences batched together.
+HIP (csrc/api_progen2.hip on the causal decoder of csrc/api_gpt.hip), and ``calc_fitness`` reproduces the reference's per-sequence
+loop -- chunks of n_positions characters, each scored in both reading directions, a terminal last target dropped, log-softmax over
+the 25 amino-acid columns, -mean CE summed, halved and divided by the sequence length -- with the equal-length (chunk, direction) rows
+of all sequences batched together.
 """
 from __future__ import annotations
 
@@ -16,7 +17,7 @@ from typing import Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import Config, PgmiError
+from .causal_lm import DecoderHandle, chunks        # chunks: compute_fitness.py:44-53 splits as RITA's does
 
 # progen2/tokenizer.json: one id per character
 PAD, BOS, EOS = 0, 1, 2
@@ -52,14 +53,6 @@ def sequences_to_score(DMS_data, target_seq: str, indel_mode: bool):
     if not indel_mode and "mutated_sequence" not in DMS_data.columns:
         return [get_mutated_sequence(target_seq, m) for m in DMS_data["mutant"]]
     return list(DMS_data["mutated_sequence"])
-
-
-def chunks(prot: str, model_context_len: int):
-    """compute_fitness.py:44-53."""
-    if len(prot) < model_context_len:
-        return [prot]
-    n = 1 + int(len(prot) / model_context_len)
-    return [prot[i * model_context_len:(i + 1) * model_context_len] for i in range(n)]
 
 
 def scoring_plan(prots: Sequence[str], model_context_len: int):
@@ -169,43 +162,17 @@ def load_checkpoint(checkpoint_dir: str):
 
 
 # -- model -----------------------------------------------------------------------------------------------------------------
-class ProGen2Model:
+class ProGen2Model(DecoderHandle):
     """Device-resident ProGen2 (f16x3)."""
+    ARCH, CREATE, TOKEN_LOGPROBS = _lib.ARCH_PROGEN2, "pgmi_pg2_model_create", "pgmi_pg2_token_logprobs"
 
     def __init__(self, cfg: dict, weights: np.ndarray, device: int = 0, max_rows: int = 0):
-        lib = _lib.load()
-        self.cfg = dict(cfg)
-        c = Config(abi_version=_lib.ABI_VERSION, arch=_lib.ARCH_PROGEN2, layers=cfg["layers"], embed_dim=cfg["embed_dim"],
-                   heads=cfg["heads"], ffn_dim=cfg["ffn_dim"], vocab=cfg["vocab"], max_positions=cfg["max_positions"],
-                   token_dropout=0, emb_layer_norm_before=0, precision=_lib.PREC_F16X3, max_rows=max_rows,
-                   ln_eps=cfg.get("ln_eps", 1e-5))
-        w = _lib.as_f32(weights)
-        n = lib.pgmi_weight_count(C.byref(c))
-        if w.size != n:
-            raise PgmiError(f"weight blob has {w.size} elements, config needs {n}")
-        h = C.c_void_p()
-        _lib.check(lib.pgmi_pg2_model_create(C.byref(c), int(cfg["rotary_dim"]), _lib.ptr(w, _lib._f32p), w.size, device, C.byref(h)))
-        self._h = h
+        super().__init__(cfg, weights, int(cfg["rotary_dim"]), device, max_rows)
         self.n_positions = cfg["max_positions"]
 
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.load().pgmi_model_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def token_logprobs(self, input_ids) -> np.ndarray:
-        """log_softmax(model(input_ids).logits) over all 32 columns: [B,T] -> [B,T,32]."""
-        t = _lib.as_i32(np.atleast_2d(np.asarray(input_ids)))
-        B, T = t.shape
-        out = np.empty((B, T, self.cfg["vocab"]), dtype=np.float32)
-        _lib.check(_lib.load().pgmi_pg2_token_logprobs(self._h, _lib.ptr(t, _lib._i32p), B, T, _lib.ptr(out, _lib._f32p)))
-        return out
+    @staticmethod
+    def _weight_count(lib, c, rotary_dim):
+        return lib.pgmi_weight_count(C.byref(c))
 
     def sequence_loglik(self, rows):
         """rows int32 [B,L] of whole (chunk, direction) id rows -> (sum of the kept targets' 25-column log-probs, kept count)."""

@@ -12,9 +12,8 @@ import json
 import os
 
 import numpy as np
-import pandas as pd
 
-from . import progen2 as pg
+from . import causal_lm as clm, progen2 as pg
 
 # compute_fitness.py --test (:146-159): the reference's own check of a checkpoint -- one sequence and the log-likelihood each released
 # checkpoint must give it (reduction 'sum', tolerance 0.1).  These constants are part of the reference CLI's behaviour that --test
@@ -48,13 +47,7 @@ def main(argv=None):
     config = json.load(open(os.path.join(args.Progen2_model_name_or_path, "config.json")))
     print("Maximum context length: {}".format(config["n_positions"]))
     model = pg.from_pretrained(args.Progen2_model_name_or_path, device=args.device, max_rows=args.max_rows)
-    mapping = pd.read_csv(args.DMS_reference_file_path)
-    DMS_id = mapping["DMS_id"][args.DMS_index]
-    print("Computing scores for: {} with Progen2: {}".format(DMS_id, args.Progen2_model_name_or_path))
-    row = mapping[mapping["DMS_id"] == DMS_id]
-    DMS_file_name = row["DMS_filename"].values[0]
-    target_seq = row["target_seq"].values[0].upper()
-    DMS_data = pd.read_csv(os.path.join(args.DMS_data_folder, DMS_file_name), low_memory=False)
+    DMS_id, target_seq, DMS_data = clm.load_assay(args, "Progen2", args.Progen2_model_name_or_path)
     if args.test:
         model_size = args.Progen2_model_name_or_path.rstrip("/").split("/")[-1]
         seq, expected = CHECKPOINT_X_LL[model_size]
@@ -63,9 +56,7 @@ def main(argv=None):
         assert abs(score - expected) < 0.1
     prots = pg.sequences_to_score(DMS_data, target_seq, args.indel_mode)
     DMS_data["Progen2_score"] = model.calc_fitness(prots, model_context_len=int(config["n_positions"]))
-    os.makedirs(args.output_scores_folder, exist_ok=True)
-    out = os.path.join(args.output_scores_folder, DMS_id + ".csv")
-    DMS_data[["mutant", "Progen2_score", "DMS_score"]].to_csv(out, index=False)
+    out = clm.write_scores(args, DMS_id, DMS_data, ["mutant", "Progen2_score", "DMS_score"])
     model.close()
     return out
 
