@@ -134,3 +134,42 @@ def as_i32(a):
 
 def as_f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+class ModelHandle:
+    """A device-resident model behind its libpgmi handle.  __init__ builds the Config from cfg's dimensions and the fields the
+    subclass passes, checks the blob size against the library's count and creates the model through CREATE; close / __del__ destroy
+    it.  pgmi_pg2_model_create and pgmi_gpt_model_create take arch_arg (ProGen2's rotary_dim, the causal decoder's pos_kind) after
+    the config, and their subclasses name their weight count."""
+    CREATE = "pgmi_model_create"
+
+    def __init__(self, cfg: dict, weights: np.ndarray, device: int = 0, max_rows: int = 0, arch_arg=None,
+                 precision: int = PREC_F16X3, **fields):
+        lib = load()
+        self.cfg = dict(cfg)
+        self.device = device
+        c = Config(abi_version=ABI_VERSION, layers=cfg["layers"], embed_dim=cfg["embed_dim"], heads=cfg["heads"],
+                   ffn_dim=cfg["ffn_dim"], precision=precision, max_rows=max_rows, **fields)
+        w = as_f32(weights)
+        n = self._weight_count(lib, c, arch_arg)
+        if w.size != n:
+            raise PgmiError(f"weight blob has {w.size} elements, config needs {n}")
+        h = C.c_void_p()
+        head = (C.byref(c),) if arch_arg is None else (C.byref(c), arch_arg)
+        check(getattr(lib, self.CREATE)(*head, ptr(w, _f32p), w.size, device, C.byref(h)))
+        self._h = h
+
+    @staticmethod
+    def _weight_count(lib, c, arch_arg):
+        return lib.pgmi_weight_count(C.byref(c))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load().pgmi_model_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

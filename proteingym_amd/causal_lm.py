@@ -19,7 +19,6 @@ from typing import Callable, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import Config, PgmiError
 from .tranception import load_hf_directory
 
 MODEL_CONTEXT_LEN = 1023                   # compute_fitness.py:13 (both): the chunk length in characters
@@ -209,37 +208,15 @@ def load_checkpoint(checkpoint_dir: str):
 
 
 # -- model -----------------------------------------------------------------------------------------------------------------
-class DecoderHandle:
-    """A device-resident causal decoder (f16x3) behind its libpgmi handle: the blob-size check against the library's count, create,
-    close and token_logprobs.  Subclasses (CausalLM, progen2.ProGen2Model) name their arch, C entries and weight count."""
+class DecoderHandle(_lib.ModelHandle):
+    """A device-resident causal decoder (f16x3) and its token_logprobs.  Subclasses (CausalLM, progen2.ProGen2Model) name their arch
+    and C entries."""
     ARCH: int
     CREATE = TOKEN_LOGPROBS = ""            # pgmi_*_model_create(cfg, arch_arg, ...), pgmi_*_token_logprobs
 
     def __init__(self, cfg: dict, weights: np.ndarray, arch_arg: int, device: int = 0, max_rows: int = 0):
-        lib = _lib.load()
-        self.cfg = dict(cfg)
-        c = Config(abi_version=_lib.ABI_VERSION, arch=self.ARCH, layers=cfg["layers"], embed_dim=cfg["embed_dim"],
-                   heads=cfg["heads"], ffn_dim=cfg["ffn_dim"], vocab=cfg["vocab"], max_positions=cfg["max_positions"],
-                   token_dropout=0, emb_layer_norm_before=0, precision=_lib.PREC_F16X3, max_rows=max_rows,
-                   ln_eps=cfg.get("ln_eps", 1e-5))
-        w = _lib.as_f32(weights)
-        n = self._weight_count(lib, c, arch_arg)
-        if w.size != n:
-            raise PgmiError(f"weight blob has {w.size} elements, config needs {n}")
-        h = C.c_void_p()
-        _lib.check(getattr(lib, self.CREATE)(C.byref(c), arch_arg, _lib.ptr(w, _lib._f32p), w.size, device, C.byref(h)))
-        self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.load().pgmi_model_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(cfg, weights, device, max_rows, arch_arg, arch=self.ARCH, vocab=cfg["vocab"],
+                         max_positions=cfg["max_positions"], ln_eps=cfg.get("ln_eps", 1e-5))
 
     def token_logprobs(self, input_ids) -> np.ndarray:
         """log_softmax(model(input_ids).logits) over all V columns: [B,T] -> [B,T,V]."""

@@ -1,5 +1,6 @@
 // ESM-1b / ESM-1v / ESM2: the forward (esm/model/esm1.py:116-177, esm2.py:76-130, modules.py:120-142), masked-marginals assays
-// (compute_fitness.py:486-514) and pseudo-perplexity libraries (compute_fitness.py:258-279,515-529) behind include/pgmi.h.
+// (compute_fitness.py:486-514) and pseudo-perplexity libraries (compute_fitness.py:258-279,515-529) behind include/pgmi.h.  ESM C
+// (api_esmc.hip) and the MSA Transformer's head run on the same encoder and head.
 #include "model.h"
 
 namespace pgmi {
@@ -42,12 +43,13 @@ int create_esm(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_
     c.upload(&m->hd_b, D);
     c.upload(&m->hln_w, D);
     c.upload(&m->hln_b, D);
-    c.upload(&m->h_bias, V);
+    c.upload(&m->head_b, V);
+    m->head_w = m->embed_tokens;
     return c.finish();
 }
 
 int ensure_rotary(pgmi_model* m, int T) {
-    if (m->cfg.arch != PGMI_ARCH_ESM2 || T <= m->rot_len) return PGMI_OK;
+    if ((m->cfg.arch != PGMI_ARCH_ESM2 && m->cfg.arch != PGMI_ARCH_ESMC) || T <= m->rot_len) return PGMI_OK;
     return upload_rotate_half(m, std::max(T, 1026));
 }
 
@@ -72,10 +74,11 @@ int upload_rotate_half(pgmi_model* m, int n) {
 // of the attention context and of the residual stream and runs those stages on n_keep rows; m->x then holds the kept
 // rows COMPACTED (row j = keep[j]) and *compacted is set.  The kept rows are bit-identical to the full evaluation: every
 // kernel on the way computes a row from that row's inputs only, in an order that does not depend on the row count
-// (tests/test_gpu_esm.py::test_last_layer_kept_rows_bit_identical).  PGMI_KEEP_ROWS=0 turns it off.
+// (tests/test_gpu_esm.py::test_last_layer_kept_rows_bit_identical, tests/test_gpu_esmc.py).  PGMI_KEEP_ROWS=0 turns it off.
+// What differs per model is data: the embedding (embed_gather), a layer's q / k LayerNorm (L.q_ln: ESM C), FC1's epilogue and width.
 int run_encoder(pgmi_model* m, int B, int T, const int32_t* keep, int n_keep, bool* compacted) {
     const pgmi_config& c = m->cfg;
-    const int M = B * T, D = c.embed_dim, F = c.ffn_dim, H = c.heads, Da = m->Da;
+    const int M = B * T, D = c.embed_dim, F = c.ffn_dim, N1 = m->fc1_cols, H = c.heads, Da = m->Da;
     hipStream_t s = m->stream;
     if (c.arch == PGMI_ARCH_ESM1B && T > c.max_positions) {
         set_error("Sequence length %d above maximum sequence length of %d", T, c.max_positions);   // modules.py:256-260
@@ -86,9 +89,11 @@ int run_encoder(pgmi_model* m, int B, int T, const int32_t* keep, int n_keep, bo
     if (rc) return rc;
     {
         ProfScope p(m, PGMI_K_EMBED, 0, (double)M * D * 4);
-        launch_seq_stats(m->tokens, B, T, c.token_dropout, m->denom, m->pos_idx, m->kv_len, s);
-        launch_embed(m->tokens, m->denom, m->pos_idx, m->embed_tokens, m->embed_positions, c.token_dropout, M, T, D, m->x, s);
-        if (c.emb_layer_norm_before) {
+        // kv_len: keys before the first <pad>
+        launch_seq_stats(m->tokens, B, T, m->embed_gather ? 0 : c.token_dropout, m->denom, m->pos_idx, m->kv_len, s);
+        if (m->embed_gather) launch_gather_rows(m->embed_tokens, m->tokens, M, D, m->x, s);
+        else launch_embed(m->tokens, m->denom, m->pos_idx, m->embed_tokens, m->embed_positions, c.token_dropout, M, T, D, m->x, s);
+        if (m->lnb_w) {                                        // emb_layer_norm_before
             launch_layernorm(m->x, m->lnb_w, m->lnb_b, M, D, 1e-5f, m->x, s);
             launch_zero_pad_rows(m->tokens, M, D, m->x, s);
         }
@@ -102,8 +107,9 @@ int run_encoder(pgmi_model* m, int B, int T, const int32_t* keep, int n_keep, bo
           if (prec == PGMI_PREC_FP32) launch_layernorm(m->x, L.ln1_w, L.ln1_b, M, D, 1e-5f, m->h, s);
           else launch_layernorm16(m->x, L.ln1_w, L.ln1_b, M, D, 1e-5f, m->h16, m->h16_plane, mode16, s); }
         // attention operands straight from the QKV projection's epilogue -- in the bf16 mode too (round 6): the epilogue splits the fp32
-        // accumulators whatever the GEMM's operand type was, so that mode's attention runs on the 16-bit pipe as well
-        const bool fused_qkv = prec != PGMI_PREC_FP32;
+        // accumulators whatever the GEMM's operand type was, so that mode's attention runs on the 16-bit pipe as well.  A layer with a
+        // q / k LayerNorm (ESM C) writes fp32 rows for its prep pass instead.
+        const bool fused_qkv = prec != PGMI_PREC_FP32 && !L.q_ln;
         { ProfScope p(m, PGMI_K_GEMM_QKV, 2.0 * M * 3 * D * D, 0);
           if (fused_qkv)
               rc = launch_gemm16_qkv(m->h16, m->h16_plane, L.wqkv16.p, L.wqkv16.plane, L.bqkv, M, Da, D, L.wqkv16.out_scale,
@@ -112,11 +118,15 @@ int run_encoder(pgmi_model* m, int B, int T, const int32_t* keep, int n_keep, bo
           else
               rc = linear(m, m->h, m->h16, m->h16_plane, L.wqkv, L.wqkv16, L.bqkv, nullptr, m->qkv, nullptr, 0, M, 3 * Da, D, EPI_NONE);
           if (rc) return rc; }
-        { ProfScope p(m, PGMI_K_ATTENTION, 4.0 * M * T * D, 0);
+        // the q / k LayerNorm prep pass is profiled as attention (it produces the attention's operands): PGMI_K_ATTENTION counts both
+        { ProfScope p(m, PGMI_K_ATTENTION, 4.0 * M * T * D, L.q_ln ? (double)M * D * 20 : 0);
+          if (L.q_ln && (rc = launch_qkln_prep(m->qkv, L.q_ln, L.k_ln, 1e-5f, m->rot_cos, m->rot_sin, B, T, H, m->qk16, m->qk16_plane,
+                                               m->vt16, m->vt16_plane, s)))
+              return rc;
           const bool v2 = prec != PGMI_PREC_FP32;
           if (c.arch == PGMI_ARCH_ESM2 && !v2) launch_rotary(m->qkv, m->rot_cos, m->rot_sin, M, T, m->Hs, s, m->rot_halves);
           if (prec == PGMI_PREC_F16X3)
-              rc = launch_attention_f16x3_v2(fused_qkv ? nullptr : m->qkv, m->kv_len, m->rot_cos, m->rot_sin, c.arch == PGMI_ARCH_ESM2, B, T, H,
+              rc = launch_attention_f16x3_v2(nullptr, m->kv_len, m->rot_cos, m->rot_sin, c.arch == PGMI_ARCH_ESM2, B, T, H,
                                              m->qk16, m->qk16_plane, m->vt16, m->vt16_plane, nullptr, m->h16,
                                              m->h16_plane, 1, s, nullptr, nullptr, m->rot_halves * kHeadDim);
           else if (v2)         // bf16 mode: the context rows leave as one bf16 plane (the out-projection's operand)
@@ -129,7 +139,7 @@ int run_encoder(pgmi_model* m, int B, int T, const int32_t* keep, int n_keep, bo
           if (rc) return rc; }
         if (keep && m->keep_rows && l == c.layers - 1) {
             const int R = n_keep;
-            ProfScope p(m, PGMI_K_KEPT_ROWS, 2.0 * R * D * (Da + 2.0 * F), 0);
+            ProfScope p(m, PGMI_K_KEPT_ROWS, 2.0 * R * D * (Da + N1 + F), 0);
             launch_gather_rows(m->x, keep, R, D, m->qkv, s);                       // residual rows (qkv is free after attention)
             if (prec == PGMI_PREC_FP32) launch_gather_rows(m->h, keep, R, Da, m->g, s);
             else        // a 16-bit context row is one contiguous run (K-interleaved hi|lo: 4 Da bytes; bf16: 2 Da bytes)
@@ -141,7 +151,7 @@ int run_encoder(pgmi_model* m, int B, int T, const int32_t* keep, int n_keep, bo
             else launch_layernorm16(m->x, L.ln2_w, L.ln2_b, R, D, 1e-5f, m->h16, m->h16_plane, mode16, s);
             rc = linear(m, m->h, m->h16, m->h16_plane, L.w1, L.w116, L.b1, nullptr,
                         prec == PGMI_PREC_FP32 ? m->g : nullptr, prec == PGMI_PREC_FP32 ? nullptr : m->g16, m->g16_plane,
-                        R, F, D, EPI_GELU);
+                        R, N1, D, m->fc1_epi);
             if (rc) return rc;
             rc = linear(m, m->g, m->g16, m->g16_plane, L.w2, L.w216, L.b2, m->x, m->x, nullptr, 0, R, D, F, EPI_NONE);
             if (rc) return rc;
@@ -154,10 +164,10 @@ int run_encoder(pgmi_model* m, int B, int T, const int32_t* keep, int n_keep, bo
         { ProfScope p(m, PGMI_K_LAYERNORM, 0, ln_bytes);
           if (prec == PGMI_PREC_FP32) launch_layernorm(m->x, L.ln2_w, L.ln2_b, M, D, 1e-5f, m->h, s);
           else launch_layernorm16(m->x, L.ln2_w, L.ln2_b, M, D, 1e-5f, m->h16, m->h16_plane, mode16, s); }
-        { ProfScope p(m, PGMI_K_GEMM_FC1, 2.0 * M * F * D, 0);
+        { ProfScope p(m, PGMI_K_GEMM_FC1, 2.0 * M * N1 * D, 0);
           rc = linear(m, m->h, m->h16, m->h16_plane, L.w1, L.w116, L.b1, nullptr,
                       prec == PGMI_PREC_FP32 ? m->g : nullptr, prec == PGMI_PREC_FP32 ? nullptr : m->g16, m->g16_plane,
-                      M, F, D, EPI_GELU);
+                      M, N1, D, m->fc1_epi);
           if (rc) return rc; }
         { ProfScope p(m, PGMI_K_GEMM_FC2, 2.0 * M * F * D, 0);
           rc = linear(m, m->g, m->g16, m->g16_plane, L.w2, L.w216, L.b2, m->x, m->x, nullptr, 0, M, D, F, EPI_NONE);
@@ -167,9 +177,8 @@ int run_encoder(pgmi_model* m, int B, int T, const int32_t* keep, int n_keep, bo
     return PGMI_OK;
 }
 
-// LM head (modules.py:322-328) + log-softmax on R rows.  If row_idx != null the rows are
-// gathered from m->x first (masked positions only), else R must be the full M rows of m->x.
-// Result in m->lp [R,V].
+// LM head (modules.py:322-328; ESM C: transformer_stack.py:62 + regression_head.py) + log-softmax on R rows.  If row_idx != null
+// the rows are gathered from m->x first (masked positions only), else R must be the full M rows of m->x.  Result in m->lp [R,V].
 int run_head(pgmi_model* m, int R, const int32_t* row_idx) {
     const pgmi_config& c = m->cfg;
     const int D = c.embed_dim;
@@ -186,7 +195,7 @@ int run_head(pgmi_model* m, int R, const int32_t* row_idx) {
     int rc = linear(m, m->h, m->h16, m->h16_plane, m->hd_w, m->hd16, m->hd_b, nullptr, m->g, nullptr, 0, R, D, D, EPI_GELU);
     if (rc) return rc;
     launch_layernorm(m->g, m->hln_w, m->hln_b, R, D, 1e-5f, m->g, s);
-    launch_vocab_logsoftmax(m->g, m->embed_tokens, m->h_bias, R, D, c.vocab, m->lp, m->nonfinite, s);
+    launch_vocab_logsoftmax(m->g, m->head_w, m->head_b, R, D, c.vocab, m->lp, m->nonfinite, s);
     PGMI_HIP(hipGetLastError());
     return PGMI_OK;
 }
@@ -194,7 +203,6 @@ int run_head(pgmi_model* m, int R, const int32_t* row_idx) {
 
 // Encoder + LM head where only the rows row_idx [R] (device) of the [B*T] outputs are read.  Result in m->lp [R,V].
 int run_rows(pgmi_model* m, int B, int T, int R, const int32_t* row_idx) {
-    if (m->cfg.arch == PGMI_ARCH_ESMC) return run_esmc_rows(m, B, T, R, row_idx);
     bool compacted = false;
     int rc = run_encoder(m, B, T, row_idx, R, &compacted);
     if (rc) return rc;
@@ -214,7 +222,7 @@ int pgmi_token_logprobs(pgmi_model* m, const int32_t* tokens, int B, int T, floa
     const int V = m->cfg.vocab;
     rc = for_each_chunk(m, B, T, [&](int b0, int bc) {
         PGMI_HIP(hipMemcpyAsync(m->tokens, tokens + (size_t)b0 * T, (size_t)bc * T * 4, hipMemcpyHostToDevice, m->stream));
-        int rc = run_rows(m, bc, T, bc * T, nullptr);        // all rows: run_encoder, then run_head (or ESM C's forward)
+        int rc = run_rows(m, bc, T, bc * T, nullptr);        // all rows: run_encoder, then run_head
         if (rc) return rc;
         PGMI_HIP(hipMemcpyAsync(out + (size_t)b0 * T * V, m->lp, (size_t)bc * T * V * 4, hipMemcpyDeviceToHost, m->stream));
         return PGMI_OK;

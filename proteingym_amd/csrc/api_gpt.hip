@@ -1,12 +1,13 @@
 // Causal decoder: RITA (proteingym/baselines/rita/rita_modeling.py) and ProtGPT2, a GPT-2 (transformers GPT2LMHeadModel;
-// proteingym/baselines/protgpt2/compute_fitness.py), and the body and 32-column head of ProGen2 (api_progen2.hip).  Model creation of
-// RITA / ProtGPT2, the forward, the two LM heads and the C entries.
+// proteingym/baselines/protgpt2/compute_fitness.py), and the bodies of ProGen2 (api_progen2.hip) and Tranception (api_tranception.hip).
+// Model creation of RITA / ProtGPT2, the forward, the LM heads and the C entries.
 //
 // Per layer, sequential pre-LN residual (rita_modeling.py:208-219; GPT2Block): x += out_proj(attn(ln_1(x)));
 // x += fc_out(gelu_tanh(fc_in(ln_2(x)))).  Parallel residual (ProGen2, modeling_progen.py:252-283): h = ln_1(x);
-// x += out_proj(attn(h)) + fc_out(gelu_new(fc_in(h))).  The attention runs on the kernels the other causal LMs use: the fused QKV
-// epilogue (RITA: ESM2's rotate-half rotary tables; ProGen2: GPT-J's, in the same layout) and attention_f16x3_v2 with all-zero ALiBi
-// slopes (the ALiBi term is then exactly 0).  Heads: V <= 64 (RITA: 26, ProGen2: 32) on one wave per row (vocab_logsoftmax_kernel);
+// x += out_proj(attn(h)) + fc_out(gelu_new(fc_in(h))).  The attention runs on the fused QKV epilogue (RITA: ESM2's rotate-half rotary
+// tables; ProGen2: GPT-J's, in the same layout) and attention_f16x3_v2 with all-zero ALiBi slopes (the ALiBi term is then exactly 0);
+// Tranception's layers (L.conv) project into fp32 rows whose depth-wise convolution runs in the attention's prep pass, with its grouped
+// ALiBi slopes, and FC1 ends in its squared ReLU.  Heads: V <= 64 (RITA: 26, ProGen2: 32) on one wave per row (vocab_logsoftmax_kernel);
 // wider ones (ProtGPT2: 50 257, tied to wte) on the f16x3 GEMM into fp32 logits, then one workgroup per row (wide_logsoftmax_kernel).
 // When scoring, only the rows that have a target reach the head.
 #include "model.h"
@@ -27,7 +28,6 @@ int64_t gpt_weight_count(const pgmi_config* c, int pos_kind) {
 int create_gpt(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights, int pos_kind) {
     const size_t D = cfg->embed_dim, F = cfg->ffn_dim, V = cfg->vocab, dh = m->dh, Da = m->Da;
     const bool rotary = pos_kind == PGMI_GPT_POS_ROTARY;
-    m->gpt_pos = pos_kind;
     BlobCursor c(m, w, n_weights);
     const float* wte = c.take(V * D);
     c.upload(&m->embed_tokens, wte, V * D);
@@ -59,9 +59,11 @@ int create_gpt(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_
     const float* head = rotary ? c.take(V * D) : wte;                // GPT-2: lm_head.weight is wte itself
     const size_t Vp = (V + 63) / 64 * 64;
     m->gpt_Vp = (int)Vp;
+    m->slopes = m->zeros;
+    m->fc1_epi = EPI_GELU_TANH;
     if (!wide_head(*cfg)) {
-        c.upload(&m->gpt_head_w, head, V * D);
-        m->gpt_head_b = m->zeros;
+        c.upload(&m->head_w, head, V * D);
+        m->head_b = m->zeros;
     } else {
         // zero rows V .. Vp-1: whole 64-column GEMM tiles; the log-softmax excludes those columns by index
         std::vector<float> padded(Vp * D, 0.0f);
@@ -76,21 +78,25 @@ int create_gpt(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_
     return rc;
 }
 
-// The decoder body on tokens in m->tokens [B,T]; leaves the residual stream after the last layer in m->x [B*T, D].
-int run_decoder(pgmi_model* m, int B, int T) {
+// The decoder body on tokens in m->tokens; leaves the residual stream after the last layer in m->x.  Dense: B sequences of T tokens,
+// [B*T, D].  Ragged (rg != nullptr; Tranception's prefix-shared scoring, api_tranception.hip): `rows` packed suffix rows of sequences
+// of T tokens, their attention over rg (att_flops for the profile).  What differs per model is data: the position kind (rotary tables
+// rot_cos, a learned table embed_positions, or none), a layer's depth-wise convolution (L.conv), the slopes, FC1's epilogue and the
+// residual order.
+int run_decoder(pgmi_model* m, int B, int T, const AttRagged* rg, int rows, double att_flops) {
     const pgmi_config& c = m->cfg;
-    const int M = B * T, D = c.embed_dim, F = c.ffn_dim, H = c.heads, Da = m->Da;
-    const bool rotary = m->gpt_pos == PGMI_GPT_POS_ROTARY;
+    const int M = rg ? rows : B * T, D = c.embed_dim, F = c.ffn_dim, H = c.heads, Da = m->Da;
+    const bool rotary = m->rot_cos != nullptr;
     hipStream_t s = m->stream;
-    int rc = reset_pad_keys(m, B, T);
+    int rc = rg ? PGMI_OK : reset_pad_keys(m, B, T);
     if (rc) return rc;
-    { ProfScope p(m, PGMI_K_EMBED, 0, (double)M * D * (rotary ? 4 : 8));
-      if (rotary) launch_gather_rows(m->embed_tokens, m->tokens, M, D, m->x, s);        // RITA, ProGen2: no positional table
-      else launch_embed_learned(m->tokens, m->embed_tokens, m->embed_positions, M, T, D, m->x, s); }
+    { ProfScope p(m, PGMI_K_EMBED, 0, (double)M * D * (m->embed_positions ? 8 : 4));
+      if (m->embed_positions) launch_embed_learned(m->tokens, m->embed_tokens, m->embed_positions, M, T, D, m->x, s);
+      else launch_gather_rows(m->embed_tokens, m->tokens, M, D, m->x, s); }       // RITA, ProGen2, Tranception: no positional table
     const double ln_bytes = 2.0 * M * D * 4;
-    auto mlp = [&](const Layer& L) {                                  // x += fc_out(gelu_tanh(fc_in(h16)))
+    auto mlp = [&](const Layer& L) {                                  // x += fc_out(act(fc_in(h16)))
         { ProfScope p(m, PGMI_K_GEMM_FC1, 2.0 * M * F * D, 0);
-          int rc = linear(m, nullptr, m->h16, m->h16_plane, nullptr, L.w116, L.b1, nullptr, nullptr, m->g16, m->g16_plane, M, F, D, EPI_GELU_TANH);
+          int rc = linear(m, nullptr, m->h16, m->h16_plane, nullptr, L.w116, L.b1, nullptr, nullptr, m->g16, m->g16_plane, M, F, D, m->fc1_epi);
           if (rc) return rc; }
         ProfScope p(m, PGMI_K_GEMM_FC2, 2.0 * M * F * D, 0);
         return linear(m, nullptr, m->g16, m->g16_plane, nullptr, L.w216, L.b2, m->x, m->x, nullptr, 0, M, D, F, EPI_NONE);
@@ -100,17 +106,25 @@ int run_decoder(pgmi_model* m, int B, int T) {
         { ProfScope p(m, PGMI_K_LAYERNORM, 0, ln_bytes);
           launch_layernorm16(m->x, L.ln1_w, L.ln1_b, M, D, m->ln_eps, m->h16, m->h16_plane, 1, s); }
         { ProfScope p(m, PGMI_K_GEMM_QKV, 2.0 * M * 3 * Da * D, 0);
-          rc = launch_gemm16_qkv(m->h16, m->h16_plane, L.wqkv16.p, L.wqkv16.plane, L.bqkv, M, Da, D, L.wqkv16.out_scale,
-                                 m->qk16, m->qk16_plane, m->vt16, m->vt16_plane, m->rot_cos, m->rot_sin, rotary, T, m->Hs,
-                                 m->gemm_variant, s, m->rot_halves, false);
+          if (L.conv)                           // fp32 q | k | v rows: the attention's prep pass convolves and splits them
+              rc = linear(m, nullptr, m->h16, m->h16_plane, nullptr, L.wqkv16, L.bqkv, nullptr, m->qkv, nullptr, 0, M, 3 * Da, D, EPI_NONE);
+          else
+              rc = launch_gemm16_qkv(m->h16, m->h16_plane, L.wqkv16.p, L.wqkv16.plane, L.bqkv, M, Da, D, L.wqkv16.out_scale,
+                                     m->qk16, m->qk16_plane, m->vt16, m->vt16_plane, m->rot_cos, m->rot_sin, rotary, T, m->Hs,
+                                     m->gemm_variant, s, m->rot_halves, false);
           if (rc) return rc; }
         if (m->parallel_residual) {             // the MLP branch first: it reads ln_1's output, which the context rows then overwrite
             rc = mlp(L);
             if (rc) return rc;
         }
-        { ProfScope p(m, PGMI_K_ATTENTION, 2.0 * M * T * Da, 0);             // causal: half of the 4 M T Da of a dense pass
-          rc = launch_attention_f16x3_v2(nullptr, nullptr, m->rot_cos, m->rot_sin, rotary, B, T, H, m->qk16, m->qk16_plane, m->vt16,
-                                         m->vt16_plane, nullptr, m->h16, m->h16_plane, 1, s, nullptr, m->zeros, m->rot_halves * kHeadDim);
+        { ProfScope p(m, PGMI_K_ATTENTION, rg ? att_flops : 2.0 * M * T * Da, 0);     // causal: half of the 4 M T Da of a dense pass
+          const float* qkv = L.conv ? m->qkv : nullptr;
+          if (rg)
+              rc = launch_attention_tr_ragged(qkv, L.conv, m->slopes, T, H, *rg, m->qk16, m->qk16_plane, m->vt16, m->vt16_plane,
+                                              m->h16, m->h16_plane, s);
+          else
+              rc = launch_attention_f16x3_v2(qkv, nullptr, m->rot_cos, m->rot_sin, rotary, B, T, H, m->qk16, m->qk16_plane, m->vt16,
+                                             m->vt16_plane, nullptr, m->h16, m->h16_plane, 1, s, L.conv, m->slopes, m->rot_halves * kHeadDim);
           if (rc) return rc; }
         { ProfScope p(m, PGMI_K_GEMM_OUT, 2.0 * M * D * Da, 0);
           rc = linear(m, nullptr, m->h16, m->h16_plane, nullptr, L.wo16, L.bo, m->x, m->x, nullptr, 0, M, D, Da, EPI_NONE);
@@ -122,6 +136,16 @@ int run_decoder(pgmi_model* m, int B, int T) {
             if (rc) return rc;
         }
     }
+    return PGMI_OK;
+}
+
+// Narrow head (V <= 64) on the M rows of m->x: ln_f, then the log-softmax over all V columns into m->lp [M, V].
+int narrow_head(pgmi_model* m, int M) {
+    const int D = m->cfg.embed_dim, V = m->cfg.vocab;
+    { ProfScope p(m, PGMI_K_HEAD, 2.0 * M * D * V, 0);
+      launch_layernorm(m->x, m->lna_w, m->lna_b, M, D, m->ln_eps, m->h, m->stream);
+      launch_vocab_logsoftmax(m->h, m->head_w, m->head_b, M, D, V, m->lp, m->nonfinite, m->stream); }
+    PGMI_HIP(hipGetLastError());
     return PGMI_OK;
 }
 
@@ -181,10 +205,8 @@ int decoder_token_logprobs(pgmi_model* m, int arch, const int32_t* tokens, int B
               launch_layernorm16(m->x, m->lna_w, m->lna_b, M, D, m->ln_eps, m->h16, m->h16_plane, 1, s); }
             return wide_head_rows(m, M, nullptr, nullptr, dst);
         }
-        { ProfScope p(m, PGMI_K_HEAD, 2.0 * M * D * V, 0);
-          launch_layernorm(m->x, m->lna_w, m->lna_b, M, D, m->ln_eps, m->h, s);
-          launch_vocab_logsoftmax(m->h, m->gpt_head_w, m->gpt_head_b, M, D, V, m->lp, m->nonfinite, s); }
-        PGMI_HIP(hipGetLastError());
+        rc = narrow_head(m, M);
+        if (rc) return rc;
         PGMI_HIP(hipMemcpyAsync(dst, m->lp, (size_t)M * V * 4, hipMemcpyDeviceToHost, s));
         return PGMI_OK;
     });
@@ -253,7 +275,7 @@ int pgmi_gpt_sequence_loglik(pgmi_model* m, const int32_t* tokens, const int32_t
         } else {
             ProfScope p(m, PGMI_K_HEAD, 2.0 * R * D * V, 0);
             launch_layernorm(m->g, m->lna_w, m->lna_b, R, D, m->ln_eps, m->h, s);
-            launch_vocab_logsoftmax(m->h, m->gpt_head_w, m->gpt_head_b, R, D, V, m->lp, m->nonfinite, s);
+            launch_vocab_logsoftmax(m->h, m->head_w, m->head_b, R, D, V, m->lp, m->nonfinite, s);
             launch_pppl_pick(m->lp, m->aux_i, R, V, m->denom, s);
         }
         launch_seq_sum(m->denom, m->kv_len, bc, m->gpt_sum, s);

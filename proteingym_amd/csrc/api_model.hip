@@ -1,5 +1,6 @@
 // C ABI of libpgmi.so (include/pgmi.h): errors, configuration and token checks, weight split, model create / destroy, options and
-// profiling.  The per-architecture weight walks and forwards live in api_esm / api_tranception / api_progen2 / api_msa.hip.
+// profiling.  The per-architecture weight walks live in api_esm / api_esmc / api_tranception / api_progen2 / api_gpt / api_msa.hip, the
+// layer loops in api_esm.hip (encoder), api_gpt.hip (decoder) and api_msa.hip.
 #include "model.h"
 
 namespace pgmi {
@@ -310,6 +311,7 @@ int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int 
     const size_t V = cfg->vocab;
     const std::vector<float> zeros(std::max({3 * (size_t)m->Da, (V + 63) / 64 * 64, (size_t)cfg->embed_dim, V, (size_t)cfg->heads}), 0.0f);
     rc = dev_upload(m->allocs, &m->zeros, zeros.data(), zeros.size());
+    m->fc1_cols = cfg->ffn_dim;                          // ESM C's SwiGLU FC1: 2 ffn_dim (create_esmc)
     if (!rc) switch (cfg->arch) {
         case PGMI_ARCH_TRANCEPTION: rc = create_tranception(m, cfg, w, n_weights); break;
         case PGMI_ARCH_MSA: rc = create_msa(m, cfg, w, n_weights); break;

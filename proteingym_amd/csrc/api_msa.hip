@@ -45,7 +45,8 @@ int create_msa(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_
     c.upload(&m->hd_b, D);
     c.upload(&m->hln_w, D);
     c.upload(&m->hln_b, D);
-    c.upload(&m->h_bias, V);
+    c.upload(&m->head_b, V);
+    m->head_w = m->embed_tokens;                             // run_head (api_esm.hip): the tied lm_head
     return c.finish();
 }
 

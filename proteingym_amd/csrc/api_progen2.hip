@@ -30,8 +30,9 @@ int create_progen2(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_
         return PGMI_EINVAL;
     }
     m->pg2_rotary = rotary_dim;
-    m->gpt_pos = PGMI_GPT_POS_ROTARY;                              // the decoder body: no positional table, q / k rotated by the tables
-    m->parallel_residual = true;
+    m->parallel_residual = true;                                   // the decoder body: no positional table, q / k rotated by the tables
+    m->slopes = m->zeros;
+    m->fc1_epi = EPI_GELU_TANH;
     BlobCursor c(m, w, n_weights);
     c.upload(&m->embed_tokens, V * D);
     auto slot = [&](size_t col) -> size_t {                        // attention column of model dim `col` (head-major)
@@ -59,10 +60,10 @@ int create_progen2(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_
     c.upload(&m->lna_w, D);
     c.upload(&m->lna_b, D);
     const float* head_w = c.take(V * D);
-    c.upload(&m->gpt_head_w, head_w, V * D);
+    c.upload(&m->head_w, head_w, V * D);
     c.upload(&m->pg2_aa_w, head_w + 5 * D, 25 * D);               // rows 5..29: the amino-acid columns (compute_fitness.py:67-70)
     const float* head_b = c.take(V);
-    c.upload(&m->gpt_head_b, head_b, V);
+    c.upload(&m->head_b, head_b, V);
     c.upload(&m->pg2_aa_b, head_b + 5, 25);
     int rc = c.finish();
     if (rc) return rc;

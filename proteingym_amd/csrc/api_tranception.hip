@@ -1,4 +1,6 @@
-// Tranception (tranception/model_pytorch.py): model creation, the dense forward, prefix-shared scoring and their C entries.
+// Tranception (tranception/model_pytorch.py): model creation, prefix-shared scoring and the C entries.  The forward, dense and
+// prefix-shared, is the causal decoder's (api_gpt.hip run_decoder) with the layers' depth-wise convolution (L.conv), the grouped ALiBi
+// slopes and FC1's squared ReLU stored here; the head is its narrow one (narrow_head).
 #include "model.h"
 
 namespace pgmi {
@@ -76,12 +78,14 @@ int create_tranception(pgmi_model* m, const pgmi_config* cfg, const float* w, in
     }
     c.upload(&m->lna_w, D);
     c.upload(&m->lna_b, D);
-    c.upload(&m->tr_lm_head, V * D);
+    c.upload(&m->head_w, V * D);
+    m->head_b = m->zeros;
     std::vector<float> sl;
     std::vector<double> quarter = alibi_slopes((int)H / 4);          // grouped: slopes of n/4 heads, tiled 4x
     for (int rep = 0; rep < 4; ++rep)
         for (double v : quarter) sl.push_back((float)v);
-    c.upload(&m->tr_slopes, sl.data(), sl.size());
+    c.upload(&m->slopes, sl.data(), sl.size());
+    m->fc1_epi = EPI_SQRELU;
     return c.finish();
 }
 
@@ -95,45 +99,11 @@ static int upload_prior(pgmi_model* m, const float* log_prior, int P) {
     return PGMI_OK;
 }
 
-// Tranception forward on tokens in m->tokens [B,T]; leaves log-probabilities in m->lp [B*T, V].
-int run_tranception(pgmi_model* m, int B, int T) {
-    const pgmi_config& c = m->cfg;
-    const int M = B * T, D = c.embed_dim, F = c.ffn_dim, H = c.heads;
-    hipStream_t s = m->stream;
-    if (T > c.max_positions) { set_error("sequence of %d tokens exceeds the model context n_ctx=%d", T, c.max_positions); return PGMI_EINVAL; }
-    int rc = reset_pad_keys(m, B, T);
-    if (rc) return rc;
-    { ProfScope p(m, PGMI_K_EMBED, 0, (double)M * D * 4);
-      launch_gather_rows(m->embed_tokens, m->tokens, M, D, m->x, s); }       // wte[input_ids]; no positional embedding
-    const double ln_bytes = 2.0 * M * D * 4;
-    for (int l = 0; l < c.layers; ++l) {
-        const Layer& L = m->layers[l];
-        { ProfScope p(m, PGMI_K_LAYERNORM, 0, ln_bytes);
-          launch_layernorm16(m->x, L.ln1_w, L.ln1_b, M, D, m->ln_eps, m->h16, m->h16_plane, 1, s); }
-        { ProfScope p(m, PGMI_K_GEMM_QKV, 2.0 * M * 3 * D * D, 0);
-          rc = linear(m, nullptr, m->h16, m->h16_plane, nullptr, L.wqkv16, L.bqkv, nullptr, m->qkv, nullptr, 0, M, 3 * D, D, EPI_NONE);
-          if (rc) return rc; }
-        { ProfScope p(m, PGMI_K_ATTENTION, 2.0 * M * T * D, 0);
-          rc = launch_attention_f16x3_v2(m->qkv, nullptr, nullptr, nullptr, 0, B, T, H, m->qk16, m->qk16_plane, m->vt16,
-                                         m->vt16_plane, nullptr, m->h16, m->h16_plane, 1, s, L.conv, m->tr_slopes);
-          if (rc) return rc; }
-        { ProfScope p(m, PGMI_K_GEMM_OUT, 2.0 * M * D * D, 0);
-          rc = linear(m, nullptr, m->h16, m->h16_plane, nullptr, L.wo16, L.bo, m->x, m->x, nullptr, 0, M, D, D, EPI_NONE);
-          if (rc) return rc; }
-        { ProfScope p(m, PGMI_K_LAYERNORM, 0, ln_bytes);
-          launch_layernorm16(m->x, L.ln2_w, L.ln2_b, M, D, m->ln_eps, m->h16, m->h16_plane, 1, s); }
-        { ProfScope p(m, PGMI_K_GEMM_FC1, 2.0 * M * F * D, 0);
-          rc = linear(m, nullptr, m->h16, m->h16_plane, nullptr, L.w116, L.b1, nullptr, nullptr, m->g16, m->g16_plane, M, F, D, EPI_SQRELU);
-          if (rc) return rc; }
-        { ProfScope p(m, PGMI_K_GEMM_FC2, 2.0 * M * F * D, 0);
-          rc = linear(m, nullptr, m->g16, m->g16_plane, nullptr, L.w216, L.b2, m->x, m->x, nullptr, 0, M, D, F, EPI_NONE);
-          if (rc) return rc; }
-    }
-    { ProfScope p(m, PGMI_K_HEAD, 2.0 * M * D * c.vocab, 0);
-      launch_layernorm(m->x, m->lna_w, m->lna_b, M, D, m->ln_eps, m->h, s);
-      launch_vocab_logsoftmax(m->h, m->tr_lm_head, m->zeros, M, D, c.vocab, m->lp, m->nonfinite, s); }
-    PGMI_HIP(hipGetLastError());
-    return PGMI_OK;
+// The dense entries' context check (the prefix-shared entry runs the same one before its workspace check).
+static int check_ctx(const pgmi_model* m, int T) {
+    if (T <= m->cfg.max_positions) return PGMI_OK;
+    set_error("sequence of %d tokens exceeds the model context n_ctx=%d", T, m->cfg.max_positions);
+    return PGMI_EINVAL;
 }
 
 // ---- Tranception: prefix-shared scoring ------------------------------------------------------------
@@ -175,8 +145,7 @@ struct TrChunk {
 // log-probabilities in m->lp [rows, V] and the per-sequence reductions in m->denom [sequences].
 int run_tranception_shared(pgmi_model* m, TrChunk& ck, int T, const float* prior_dev, const int32_t* a0, const int32_t* r0,
                            const int32_t* pn, const int32_t* fl, float alpha) {
-    const pgmi_config& c = m->cfg;
-    const int M = ck.rows, D = c.embed_dim, F = c.ffn_dim, H = c.heads, V = c.vocab, S = (int)ck.seq.size();
+    const int M = ck.rows, V = m->cfg.vocab, S = (int)ck.seq.size();
     hipStream_t s = m->stream;
     // attention blocks with the most key tiles first: the launch's tail is made of the short ones
     {
@@ -220,35 +189,9 @@ int run_tranception_shared(pgmi_model* m, TrChunk& ck, int T, const float* prior
     PGMI_HIP(hipMemcpyAsync(m->tokens, ck.tokens.data(), (size_t)M * 4, hipMemcpyHostToDevice, s));
     PGMI_HIP(hipStreamSynchronize(s));                 // the host vectors go out of scope with the caller's chunk
     m->last_B = m->last_T = 0;                          // the V^T planes now hold another layout: the dense path clears them again
-    { ProfScope ps(m, PGMI_K_EMBED, 0, (double)M * D * 4);
-      launch_gather_rows(m->embed_tokens, m->tokens, M, D, m->x, s); }
-    const double ln_bytes = 2.0 * M * D * 4;
-    for (int l = 0; l < c.layers; ++l) {
-        const Layer& L = m->layers[l];
-        { ProfScope ps(m, PGMI_K_LAYERNORM, 0, ln_bytes);
-          launch_layernorm16(m->x, L.ln1_w, L.ln1_b, M, D, m->ln_eps, m->h16, m->h16_plane, 1, s); }
-        { ProfScope ps(m, PGMI_K_GEMM_QKV, 2.0 * M * 3 * D * D, 0);
-          rc = linear(m, nullptr, m->h16, m->h16_plane, nullptr, L.wqkv16, L.bqkv, nullptr, m->qkv, nullptr, 0, M, 3 * D, D, EPI_NONE);
-          if (rc) return rc; }
-        { ProfScope ps(m, PGMI_K_ATTENTION, ck.att_flops, 0);
-          rc = launch_attention_tr_ragged(m->qkv, L.conv, m->tr_slopes, T, H, rg, m->qk16, m->qk16_plane, m->vt16, m->vt16_plane,
-                                          m->h16, m->h16_plane, s);
-          if (rc) return rc; }
-        { ProfScope ps(m, PGMI_K_GEMM_OUT, 2.0 * M * D * D, 0);
-          rc = linear(m, nullptr, m->h16, m->h16_plane, nullptr, L.wo16, L.bo, m->x, m->x, nullptr, 0, M, D, D, EPI_NONE);
-          if (rc) return rc; }
-        { ProfScope ps(m, PGMI_K_LAYERNORM, 0, ln_bytes);
-          launch_layernorm16(m->x, L.ln2_w, L.ln2_b, M, D, m->ln_eps, m->h16, m->h16_plane, 1, s); }
-        { ProfScope ps(m, PGMI_K_GEMM_FC1, 2.0 * M * F * D, 0);
-          rc = linear(m, nullptr, m->h16, m->h16_plane, nullptr, L.w116, L.b1, nullptr, nullptr, m->g16, m->g16_plane, M, F, D, EPI_SQRELU);
-          if (rc) return rc; }
-        { ProfScope ps(m, PGMI_K_GEMM_FC2, 2.0 * M * F * D, 0);
-          rc = linear(m, nullptr, m->g16, m->g16_plane, nullptr, L.w216, L.b2, m->x, m->x, nullptr, 0, M, D, F, EPI_NONE);
-          if (rc) return rc; }
-    }
-    { ProfScope ps(m, PGMI_K_HEAD, 2.0 * M * D * V, 0);
-      launch_layernorm(m->x, m->lna_w, m->lna_b, M, D, m->ln_eps, m->h, s);
-      launch_vocab_logsoftmax(m->h, m->tr_lm_head, m->zeros, M, D, V, m->lp, m->nonfinite, s); }
+    rc = run_decoder(m, 0, T, &rg, M, ck.att_flops);
+    if (!rc) rc = narrow_head(m, M);
+    if (rc) return rc;
     { ProfScope ps(m, PGMI_K_SCORE, 0, (double)S * T * 8);
       launch_seq_loglik_ragged(m->lp, m->tokens, rg.seq_off, rg.seq_p, rg.seq_root, S, T, V, prior_dev, d_pa, d_pr, d_pc, d_pf, alpha,
                                m->denom, s); }
@@ -267,10 +210,13 @@ int pgmi_tr_token_logprobs(pgmi_model* m, const int32_t* tokens, int B, int T, f
     int rc = check_vocab(tokens, B, T, V);
     if (rc) return rc;
     if (T + 31 > m->max_rows) { set_error("T=%d exceeds workspace rows %d", T, m->max_rows); return PGMI_EINVAL; }
+    rc = check_ctx(m, T);
+    if (rc) return rc;
     PGMI_HIP(hipSetDevice(m->device));
     rc = for_each_chunk(m, B, T, [&](int b0, int bc) {
         PGMI_HIP(hipMemcpyAsync(m->tokens, tokens + (size_t)b0 * T, (size_t)bc * T * 4, hipMemcpyHostToDevice, m->stream));
-        int rc = run_tranception(m, bc, T);
+        int rc = run_decoder(m, bc, T);
+        if (!rc) rc = narrow_head(m, bc * T);
         if (rc) return rc;
         PGMI_HIP(hipMemcpyAsync(out + (size_t)b0 * T * V, m->lp, (size_t)bc * T * V * 4, hipMemcpyDeviceToHost, m->stream));
         return PGMI_OK;
@@ -296,6 +242,8 @@ int pgmi_tr_sequence_loglik(pgmi_model* m, const int32_t* tokens, const int32_t*
         }
     }
     if (T + 31 > m->max_rows) { set_error("T=%d exceeds workspace rows %d", T, m->max_rows); return PGMI_EINVAL; }
+    rc = check_ctx(m, T);
+    if (rc) return rc;
     PGMI_HIP(hipSetDevice(m->device));
     hipStream_t s = m->stream;
     rc = upload_prior(m, log_prior, P);
@@ -311,7 +259,8 @@ int pgmi_tr_sequence_loglik(pgmi_model* m, const int32_t* tokens, const int32_t*
             PGMI_HIP(hipMemcpyAsync(dn, prior_n + b0, (size_t)bc * 4, hipMemcpyHostToDevice, s));
             PGMI_HIP(hipMemcpyAsync(dfl, prior_flip + b0, (size_t)bc * 4, hipMemcpyHostToDevice, s));
         }
-        int rc = run_tranception(m, bc, T);
+        int rc = run_decoder(m, bc, T);
+        if (!rc) rc = narrow_head(m, bc * T);
         if (rc) return rc;
         { ProfScope p(m, PGMI_K_SCORE, 0, (double)bc * T * 8);
           launch_seq_loglik(m->lp, m->tokens, m->kv_len, bc, T, V, log_prior ? m->tr_prior : nullptr, da0, dr0, dn, dfl, alpha,
@@ -329,7 +278,7 @@ int pgmi_tr_sequence_loglik_shared(pgmi_model* m, const int32_t* tokens, const i
     if (!m || !tokens || !ref || !out || B <= 0 || T <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
     if (m->cfg.arch != PGMI_ARCH_TRANCEPTION) { set_error("not a Tranception model"); return PGMI_EINVAL; }
     if (log_prior && (!prior_a0 || !prior_row0 || !prior_n || !prior_flip || P <= 0)) { set_error("incomplete retrieval arguments"); return PGMI_EINVAL; }
-    if (T > m->cfg.max_positions) { set_error("sequence of %d tokens exceeds the model context n_ctx=%d", T, m->cfg.max_positions); return PGMI_EINVAL; }
+    if (check_ctx(m, T)) return PGMI_EINVAL;
     const int V = m->cfg.vocab, D = m->cfg.embed_dim;
     const int Tpad = (T + 31) / 32 * 32;
     if (2 * Tpad > m->max_rows) { set_error("T=%d exceeds workspace rows %d", T, m->max_rows); return PGMI_EINVAL; }

@@ -2,14 +2,15 @@
 // handles of include/pgmi.h and the host-side helpers they share.  Nothing here is part of the ABI.
 //   api_model.hip        errors, configuration and token checks, weight split, model create (validation, per-arch dispatch,
 //                        workspace) / destroy, options, profiling
-//   api_esm.hip          ESM-1b / ESM-1v / ESM2 weights (create_esm) and forward (run_encoder, run_head), masked-marginals assays,
-//                        pseudo-ppl libraries
-//   api_tranception.hip  Tranception weights and forward, dense and prefix-shared; token log-probs and sequence log-likelihoods
+//   api_esm.hip          ESM-1b / ESM-1v / ESM2 weights (create_esm), the encoder forward of the ESM family and ESM C (run_encoder,
+//                        run_head), masked-marginals assays, pseudo-ppl libraries
+//   api_tranception.hip  Tranception weights, prefix-shared chunks; token log-probs and sequence log-likelihoods (on run_decoder)
 //   api_progen2.hip      ProGen2 weights (GPT-J rotary, bias-free projections), its 25-column amino-acid head and sequence
 //                        log-likelihoods
-//   api_gpt.hip          causal decoder: RITA / ProtGPT2 weights, the decoder body (sequential or ProGen2's parallel residual), narrow
-//                        and wide LM heads, the checks and token log-probs of both archs; RITA / ProtGPT2 sequence log-likelihoods
-//   api_esmc.hip         ESM C weights and forward (QK-LayerNorm, SwiGLU, scaled residual, untied 64-column head)
+//   api_gpt.hip          causal decoder: RITA / ProtGPT2 weights, the decoder body of RITA / ProtGPT2 / ProGen2 / Tranception (sequential
+//                        or ProGen2's parallel residual; dense or Tranception's ragged prefix-shared rows), narrow and wide LM heads,
+//                        the checks and token log-probs of RITA / ProtGPT2 / ProGen2; RITA / ProtGPT2 sequence log-likelihoods
+//   api_esmc.hip         ESM C weights (QK-LayerNorm, SwiGLU, scaled residual, untied 64-column head); it runs on run_encoder
 //   api_msa.hip          MSA Transformer weights and forward (tied row attention, column attention)
 //   api_host.hip         host-only entries: mutant parser, table -> scores, optimal window
 //   api_ops.hip          single-op and timing entries for the numerics tests and the A/B scripts
@@ -70,10 +71,18 @@ struct pgmi_model {
     // weights
     float *embed_tokens = nullptr, *embed_positions = nullptr;
     float *lnb_w = nullptr, *lnb_b = nullptr, *lna_w = nullptr, *lna_b = nullptr;
-    float *hd_w = nullptr, *hd_b = nullptr, *hln_w = nullptr, *hln_b = nullptr, *h_bias = nullptr;
+    float *hd_w = nullptr, *hd_b = nullptr, *hln_w = nullptr, *hln_b = nullptr;
+    // the log-softmax head [V,D] and its bias [V]: embed_tokens (ESM family, MSA Transformer: tied) or an untied matrix (ESM C, and the
+    // narrow causal-decoder heads; RITA's and Tranception's bias is `zeros`)
+    float *head_w = nullptr, *head_b = nullptr;
     std::vector<Layer> layers;
     W16 hd16;
-    float *tr_lm_head = nullptr, *tr_slopes = nullptr;  // Tranception head / ALiBi slopes
+    // what the shared layer loops (run_encoder, run_decoder) read per model: FC1's epilogue (common.h Epilogue) and output columns
+    // (ffn_dim; 2 ffn_dim for ESM C's SwiGLU); the encoder's embedding as a plain table gather (ESM C: no token dropout, position
+    // table or <pad> zeroing); the causal attention's ALiBi slopes (Tranception's grouped table; `zeros` for the others)
+    int fc1_epi = EPI_GELU, fc1_cols = 0;
+    bool embed_gather = false;
+    float* slopes = nullptr;
     float* tr_prior = nullptr;                          // device copy of the retrieval log-prior [P,V]
     size_t tr_prior_cap = 0;
     int32_t* tr_meta = nullptr;                         // prefix-shared scoring: the chunk's index arrays (TrChunk)
@@ -81,16 +90,14 @@ struct pgmi_model {
     // ProGen2: rotary_dim and the amino-acid rows 5..29 of its head
     int pg2_rotary = 0;
     float *pg2_aa_w = nullptr, *pg2_aa_b = nullptr;
-    // causal decoder (api_gpt.hip; ProGen2 runs on it too): PGMI_GPT_POS_*, the residual order, the head -- fp32 weight [V,D] and bias
-    // [V] (V <= 64; RITA's bias is `zeros`) or the f16x3 planes of wte zero-padded to gpt_Vp = roundup(V, 64) rows -- and the wide
-    // head's fp32 logits [gpt_head_rows][gpt_Vp]; per-sequence sums
-    int gpt_pos = 0, gpt_Vp = 0, gpt_head_rows = 0;
+    // causal decoder (api_gpt.hip; ProGen2 and Tranception run on it too): the residual order, the wide head -- the f16x3 planes of wte
+    // zero-padded to gpt_Vp = roundup(V, 64) rows and its fp32 logits [gpt_head_rows][gpt_Vp] (V <= 64: head_w / head_b) --;
+    // per-sequence sums.  Rotary: rot_cos / rot_sin uploaded at creation (RITA, ProGen2); learned positions: embed_positions (ProtGPT2)
+    int gpt_Vp = 0, gpt_head_rows = 0;
     bool parallel_residual = false;     // ProGen2: attention and MLP both read ln_1's output; else ln_2 follows the attention
-    float *gpt_head_w = nullptr, *gpt_head_b = nullptr, *gpt_logits = nullptr;
+    float* gpt_logits = nullptr;
     W16 gpt_head16;
     double* gpt_sum = nullptr;
-    // ESM C (api_esmc.hip): the untied head weight [64,D] (its bias is h_bias)
-    float* esmc_head_w = nullptr;
     // MSA Transformer
     float* msa_pe = nullptr;                            // msa_position_embedding [1024, D]
     float* xt = nullptr;                                // residual stream in column-major token order
@@ -228,26 +235,25 @@ int reset_pad_keys(pgmi_model* m, int B, int T);
 int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int device, pgmi_model** out, int arch_arg);
 // api_esm.hip
 int create_esm(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights);
-int ensure_rotary(pgmi_model* m, int T);
+int ensure_rotary(pgmi_model* m, int T);            // ESM2 / ESM C: tables for at least T positions
 int upload_rotate_half(pgmi_model* m, int n);       // ESM2's rotary tables for positions 0..n-1 (rotate_half_slot layout)
 int run_encoder(pgmi_model* m, int B, int T, const int32_t* keep = nullptr, int n_keep = 0, bool* compacted = nullptr);
 int run_head(pgmi_model* m, int R, const int32_t* row_idx);
 int run_rows(pgmi_model* m, int B, int T, int R, const int32_t* row_idx);
 // api_tranception.hip
 int create_tranception(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights);
-int run_tranception(pgmi_model* m, int B, int T);
 // api_progen2.hip
 int create_progen2(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights, int rotary_dim);
 // api_gpt.hip
 int create_gpt(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights, int pos_kind);
 int64_t gpt_weight_count(const pgmi_config* c, int pos_kind);
 int decoder_check(pgmi_model* m, int arch, int T);
-int run_decoder(pgmi_model* m, int B, int T);
+int run_decoder(pgmi_model* m, int B, int T, const AttRagged* rg = nullptr, int rows = 0, double att_flops = 0);
+int narrow_head(pgmi_model* m, int M);
 int decoder_token_logprobs(pgmi_model* m, int arch, const int32_t* tokens, int B, int T, float* out);
 // api_esmc.hip
 int64_t esmc_weight_count(const pgmi_config* c);
 int create_esmc(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights);
-int run_esmc_rows(pgmi_model* m, int B, int T, int R, const int32_t* row_idx);
 // api_msa.hip
 int create_msa(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights);
 int run_msa(pgmi_model* m, int R, int C, int keep_col = -1, bool* compacted = nullptr);

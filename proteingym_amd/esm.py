@@ -22,7 +22,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import PgmiError, Config
+from ._lib import PgmiError
 
 # The 33 symbols of the ESM-1b / ESM2 / MSA Transformer vocabulary in index order -- the checkpoint's embedding rows ARE this order
 # (esm/constants.py:8 between the four leading specials, one filler up to a multiple of 8, and <mask>; esm/data.py:92-174).
@@ -247,7 +247,7 @@ def pack_state_dict(cfg, sd) -> np.ndarray:
     return np.concatenate(parts)
 
 
-class EsmModel:
+class EsmModel(_lib.ModelHandle):
     """Device-resident ESM-1b/1v/ESM2 masked LM.  ``model(tokens)["logits"]`` mirrors the
     reference call (compute_fitness.py:502) but returns log-probabilities, i.e. already
     ``log_softmax``-ed logits -- log_softmax is idempotent, so reference-style callers that
@@ -255,8 +255,6 @@ class EsmModel:
 
     def __init__(self, cfg: dict, weights: np.ndarray, device: int = 0, precision: str = "f16x3",
                  max_rows: int = 0):
-        lib = _lib.load()
-        self.cfg = dict(cfg)
         if precision == "bf16" and (cfg["embed_dim"] % 64 or cfg["ffn_dim"] % 64):
             # the bf16 GEMM's K tile is 64 deep (ESM2-35M has embed_dim 480): that (un-gated, throughput) mode hands such a
             # model to fp32 -- said out loud, never a silent switch.  f16x3 takes any multiple of 32.
@@ -265,31 +263,9 @@ class EsmModel:
                   f"using precision fp32 instead of {precision}", file=sys.stderr)
             precision = "fp32"
         self.precision = precision
-        c = Config(abi_version=_lib.ABI_VERSION, arch=cfg["arch"], layers=cfg["layers"],
-                   embed_dim=cfg["embed_dim"], heads=cfg["heads"], ffn_dim=cfg["ffn_dim"], vocab=33,
-                   max_positions=cfg["max_positions"], token_dropout=cfg["token_dropout"],
-                   emb_layer_norm_before=cfg["emb_layer_norm_before"],
-                   precision=_lib.PRECISIONS[precision], max_rows=max_rows, ln_eps=0.0)
-        self._c = c
-        n = lib.pgmi_weight_count(C.byref(c))
-        w = _lib.as_f32(weights)
-        if w.size != n:
-            raise PgmiError(f"weight blob has {w.size} elements, config needs {n}")
-        h = C.c_void_p()
-        _lib.check(lib.pgmi_model_create(C.byref(c), _lib.ptr(w, _lib._f32p), w.size, device, C.byref(h)))
-        self._h = h
-        self.device = device
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.load().pgmi_model_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(cfg, weights, device, max_rows, precision=_lib.PRECISIONS[precision], arch=cfg["arch"], vocab=33,
+                         max_positions=cfg["max_positions"], token_dropout=cfg["token_dropout"],
+                         emb_layer_norm_before=cfg["emb_layer_norm_before"])
 
     def eval(self):
         return self

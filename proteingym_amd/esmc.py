@@ -8,7 +8,6 @@ an assay batched into one call (they all have the same length, so nothing is pad
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 import os
 import re
@@ -17,7 +16,6 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import Config, PgmiError
 from .esm import VOCABULARY
 
 # EsmSequenceTokenizer: the ids of ESM's 33-symbol alphabet (<cls> 0, <pad> 1, <eos> 2, <unk> 3, <mask> 32); 64 logits columns
@@ -234,33 +232,11 @@ def combine(parsed: Sequence[Parsed], lp_by_pos: Dict[int, np.ndarray]) -> Dict[
 
 
 # -- model -----------------------------------------------------------------------------------------------------------------
-class ESMC:
+class ESMC(_lib.ModelHandle):
     """Device-resident ESM C (f16x3)."""
 
     def __init__(self, cfg: dict, weights: np.ndarray, device: int = 0, max_rows: int = 0):
-        lib = _lib.load()
-        self.cfg = dict(cfg)
-        c = Config(abi_version=_lib.ABI_VERSION, arch=_lib.ARCH_ESMC, layers=cfg["layers"], embed_dim=cfg["embed_dim"],
-                   heads=cfg["heads"], ffn_dim=cfg["ffn_dim"], vocab=VOCAB, max_positions=0, token_dropout=0,
-                   emb_layer_norm_before=0, precision=_lib.PREC_F16X3, max_rows=max_rows, ln_eps=1e-5)
-        w = _lib.as_f32(weights)
-        n = lib.pgmi_weight_count(C.byref(c))
-        if w.size != n:
-            raise PgmiError(f"weight blob has {w.size} elements, config needs {n}")
-        h = C.c_void_p()
-        _lib.check(lib.pgmi_model_create(C.byref(c), _lib.ptr(w, _lib._f32p), w.size, device, C.byref(h)))
-        self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.load().pgmi_model_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(cfg, weights, device, max_rows, arch=_lib.ARCH_ESMC, vocab=VOCAB, ln_eps=1e-5)
 
     def token_logprobs(self, tokens) -> np.ndarray:
         """log_softmax(model(tokens).sequence_logits) over all 64 columns: [B,T] -> [B,T,64]."""

@@ -12,7 +12,6 @@ through the C ABI (``pgmi_msa_token_logprobs`` / ``pgmi_msa_masked_logprobs``); 
 """
 from __future__ import annotations
 
-import ctypes as C
 import itertools
 import os
 import random
@@ -21,7 +20,6 @@ from typing import List, Tuple
 import numpy as np
 
 from . import _lib, alignment
-from ._lib import Config, PgmiError
 from . import esm as pesm
 
 ARCH_MSA = 4
@@ -125,39 +123,16 @@ def pack_state_dict(cfg, sd) -> np.ndarray:
     return np.concatenate(parts)
 
 
-class MsaTransformerModel:
+class MsaTransformerModel(_lib.ModelHandle):
     """Device-resident MSA Transformer.  ``model(tokens)["logits"]`` mirrors the reference call
     (compute_fitness.py:390) and returns log-probabilities [B, R, C, 33] (log_softmax is idempotent)."""
 
     def __init__(self, cfg: dict, weights: np.ndarray, device: int = 0, max_rows: int = 0):
-        lib = _lib.load()
-        self.cfg = dict(cfg)
         self.precision = "f16x3"
         if max_rows <= 0:
             max_rows = 416 * 1024                                   # 400 sampled rows x 1024 columns, padded to 32
-        c = Config(abi_version=_lib.ABI_VERSION, arch=ARCH_MSA, layers=cfg["layers"], embed_dim=cfg["embed_dim"],
-                   heads=cfg["heads"], ffn_dim=cfg["ffn_dim"], vocab=33, max_positions=cfg["max_positions"],
-                   token_dropout=0, emb_layer_norm_before=1, precision=_lib.PRECISIONS["f16x3"], max_rows=max_rows,
-                   ln_eps=0.0)
-        n = lib.pgmi_weight_count(C.byref(c))
-        w = _lib.as_f32(weights)
-        if w.size != n:
-            raise PgmiError(f"weight blob has {w.size} elements, config needs {n}")
-        h = C.c_void_p()
-        _lib.check(lib.pgmi_model_create(C.byref(c), _lib.ptr(w, _lib._f32p), w.size, device, C.byref(h)))
-        self._h = h
-        self.device = device
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.load().pgmi_model_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(cfg, weights, device, max_rows, arch=ARCH_MSA, vocab=33, max_positions=cfg["max_positions"],
+                         emb_layer_norm_before=1)
 
     def eval(self):
         return self

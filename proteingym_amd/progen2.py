@@ -8,7 +8,6 @@ of all sequences batched together.
 """
 from __future__ import annotations
 
-import ctypes as C
 import json
 import os
 from collections import defaultdict
@@ -169,10 +168,6 @@ class ProGen2Model(DecoderHandle):
     def __init__(self, cfg: dict, weights: np.ndarray, device: int = 0, max_rows: int = 0):
         super().__init__(cfg, weights, int(cfg["rotary_dim"]), device, max_rows)
         self.n_positions = cfg["max_positions"]
-
-    @staticmethod
-    def _weight_count(lib, c, rotary_dim):
-        return lib.pgmi_weight_count(C.byref(c))
 
     def sequence_loglik(self, rows):
         """rows int32 [B,L] of whole (chunk, direction) id rows -> (sum of the kept targets' 25-column log-probs, kept count)."""

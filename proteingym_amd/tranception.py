@@ -13,7 +13,6 @@ log-likelihood, prior fusion, per-sequence sum) runs in HIP kernels through the 
 """
 from __future__ import annotations
 
-import ctypes as C
 import json
 import os
 from typing import Optional, Sequence
@@ -22,7 +21,6 @@ import numpy as np
 import pandas as pd
 
 from . import _lib, alignment
-from ._lib import PgmiError, Config
 
 VOCAB = {'[UNK]': 0, '[CLS]': 1, '[SEP]': 2, '[PAD]': 3, '[MASK]': 4, 'A': 5, 'C': 6, 'D': 7, 'E': 8, 'F': 9,
          'G': 10, 'H': 11, 'I': 12, 'K': 13, 'L': 14, 'M': 15, 'N': 16, 'P': 17, 'Q': 18, 'R': 19, 'S': 20,
@@ -442,7 +440,7 @@ def load_checkpoint(checkpoint_dir: str):
     return cfg, np.concatenate(parts)
 
 
-class TranceptionModel:
+class TranceptionModel(_lib.ModelHandle):
     """Device-resident Tranception.  ``score_mutants`` mirrors the reference method of the same name."""
 
     share_prefix = True          # forward a mutated sequence from its first mutated token on (sequence_loglik)
@@ -452,35 +450,13 @@ class TranceptionModel:
 
     def __init__(self, cfg: dict, weights: np.ndarray, device: int = 0, scoring_window: str = "optimal",
                  retrieval: Optional[dict] = None, max_rows: int = 0):
-        lib = _lib.load()
-        self.cfg = dict(cfg)
-        c = Config(abi_version=_lib.ABI_VERSION, arch=_lib.ARCH_TRANCEPTION, layers=cfg["layers"], embed_dim=cfg["embed_dim"],
-                   heads=cfg["heads"], ffn_dim=cfg["ffn_dim"], vocab=cfg["vocab"], max_positions=cfg["max_positions"],
-                   token_dropout=0, emb_layer_norm_before=0, precision=_lib.PREC_F16X3, max_rows=max_rows,
-                   ln_eps=cfg.get("ln_eps", 1e-5))
-        w = _lib.as_f32(weights)
-        n = lib.pgmi_weight_count(C.byref(c))
-        if w.size != n:
-            raise PgmiError(f"weight blob has {w.size} elements, config needs {n}")
-        h = C.c_void_p()
-        _lib.check(lib.pgmi_model_create(C.byref(c), _lib.ptr(w, _lib._f32p), w.size, device, C.byref(h)))
-        self._h = h
+        super().__init__(cfg, weights, device, max_rows, arch=_lib.ARCH_TRANCEPTION, vocab=cfg["vocab"],
+                         max_positions=cfg["max_positions"], ln_eps=cfg.get("ln_eps", 1e-5))
         self.n_ctx = cfg["max_positions"]
         self.scoring_window = scoring_window
         # retrieval: dict(log_prior [L,25] float32, MSA_start (0-based), MSA_end, weight)
         self.retrieval = retrieval
         self.share_prefix = os.environ.get("PGMI_TR_SHARE_PREFIX", "1") != "0"
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.load().pgmi_model_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def eval(self):
         return self

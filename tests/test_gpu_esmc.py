@@ -34,7 +34,9 @@ def build(g, name, max_rows=0, scale_w1=None):
 
 
 @pytest.mark.parametrize("name", SHAPES)
-def test_logprobs_match_reference(lib, g, name):
+def test_logprobs_match_reference(lib, g, name, monkeypatch):
+    """... and the masked rows, whose last layer runs its row-local stages on those rows only, have the bits of the full
+    evaluation (PGMI_KEEP_ROWS=0, read at model creation)."""
     model = build(g, name)
     ids = g[f"{name}_ids"]
     lp = model.token_logprobs(ids[None])[0]
@@ -43,6 +45,10 @@ def test_logprobs_match_reference(lib, g, name):
     mlp = model.masked_logprobs(np.repeat(ids[None], len(pos), 0), pos)
     assert np.abs(mlp - g[f"{name}_mask_lp"]).max() <= TOL
     model.close()
+    monkeypatch.setenv("PGMI_KEEP_ROWS", "0")
+    full = build(g, name)
+    assert np.array_equal(full.masked_logprobs(np.repeat(ids[None], len(pos), 0), pos), mlp)
+    full.close()
 
 
 def run_cli(tmp_path, model_path, *extra):
