@@ -255,6 +255,19 @@ int pgmi_op_qkln_prep(int device, const float* qkv, const float* q_w, const floa
 int pgmi_op_attention(int device, int precision, const float* qkv, const int32_t* kv_len,
                       int B, int T, int H, int rotary, float* ctx);
                                      /* multihead_attention.py:354-395; qkv [B*T,3*H*64], q pre-scaled */
+/* The causal attention of one decoder layer in SLOT SPACE, through the launchers the decoders use.  heads of `lanes` (64 / 128 / 256) lanes,
+ * Da = heads * lanes, every head lanes / 64 slot groups of 64; slopes [heads] (ALiBi, zeros for none) selects the causal kernels.
+ * Fused form (RITA, ProtGPT2, ProGen2): X [B*T, K] (K % 32 == 0), W [3 Da, K] (rows q | k | v), bias [3 Da]; qkv = conv = NULL.  The fused
+ *   QKV projection forms X W^T + bias and rotates the pair (i, i + 32) of every slot group g of a q / k head at position t (restarting
+ *   per sequence) by rot_cos / rot_sin [T][lanes / 64][64] at [t][g][i] (both NULL: no rotary; entries i and i + 32 hold the same angle).
+ * Conv form (Tranception; lanes 64, heads % 4 == 0): qkv fp32 [B*T, 3 Da] and conv [3][4][64][8] -- per (q | k | v, head group
+ *   h / (heads / 4), lane) 7 right-aligned causal taps, tap j on token t - 6 + j (zero before the sequence), entry 7 the bias; X, W, bias,
+ *   rot_cos, rot_sin = NULL.
+ * q is taken as given (pre-scaled).  ctx [B*T, Da]: the split-plane context the out-projection consumes, rebuilt as fp32.  What a launcher
+ * refuses is PGMI_EINVAL with its message. */
+int pgmi_op_causal_attention(int device, int lanes, const float* X, const float* W, const float* bias, int K, const float* qkv,
+                             const float* conv, const float* rot_cos, const float* rot_sin, const float* slopes, int B, int T,
+                             int heads, float* ctx);
 
 /* ---- Tranception (arch PGMI_ARCH_TRANCEPTION; vocab 25, max_positions = n_ctx, precision f16x3) ------
  * Weight blob order (fp32, names as in the HF state dict, Conv1D weights as stored = [in,out]):

@@ -1,6 +1,12 @@
 // Single-op and timing entries of include/pgmi.h (numerics tests against torch ops; interleaved A/B of launch parameters).
 #include "model.h"
 
+// a value of the split fp16 planes (common.h split_act) back as fp32: hi + lo 2^-11
+static inline float rebuild_split(unsigned short h, unsigned short l) {
+    _Float16 a, b;
+    memcpy(&a, &h, 2); memcpy(&b, &l, 2);
+    return (float)a + (float)b * (1.0f / kLoScale);
+}
 
 extern "C" {
 
@@ -87,9 +93,7 @@ int pgmi_op_gemm(int device, int precision, const float* A, const float* W, cons
                     for (size_t m = 0; m < (size_t)M && !rc && !bf; ++m)
                         for (int n = 0; n < No; ++n) {
                             const size_t o = ki_off(m, n, No);
-                            _Float16 hi, lo;
-                            memcpy(&hi, &h[o], 2); memcpy(&lo, &h[o + 32], 2);
-                            C[m * No + n] = (float)hi + (float)lo * (1.0f / kLoScale);
+                            C[m * No + n] = rebuild_split(h[o], h[o + 32]);
                         }
                 }
                 for (void* p : pool) hipFree(p);
@@ -238,13 +242,8 @@ int pgmi_op_qkln_prep(int device, const float* qkv, const float* q_w, const floa
     cleanup();
     if (rc) return rc;
     if (e != hipSuccess) { set_error("qkln prep op failed: %s", hipGetErrorString(e)); return PGMI_EHIP; }
-    auto rebuild = [](unsigned short h, unsigned short l) {
-        _Float16 a, b;
-        memcpy(&a, &h, 2); memcpy(&b, &l, 2);
-        return (float)a + (float)b * (1.0f / kLoScale);
-    };
     if (qk)
-        for (size_t i = 0; i < M * 2 * D; ++i) qk[i] = rebuild(hq[i], hq[M * 2 * D + i]);
+        for (size_t i = 0; i < M * 2 * D; ++i) qk[i] = rebuild_split(hq[i], hq[M * 2 * D + i]);
     if (v) {
         const size_t vp = (size_t)B * Tp * D;
         for (int b = 0; b < B; ++b)
@@ -252,7 +251,7 @@ int pgmi_op_qkln_prep(int device, const float* qkv, const float* q_w, const floa
                 const int tk = t & 31, pos = (t & ~31) + ((tk & 0x13) | ((tk & 4) << 1) | ((tk & 8) >> 1));   // keys with bits 2, 3 swapped
                 for (size_t c = 0; c < D; ++c) {
                     const size_t o = ((size_t)b * H * kHeadDim + c) * Tp + pos;
-                    v[((size_t)b * T + t) * D + c] = rebuild(hv[o], hv[vp + o]);
+                    v[((size_t)b * T + t) * D + c] = rebuild_split(hv[o], hv[vp + o]);
                 }
             }
     }
@@ -294,6 +293,64 @@ int pgmi_op_attention(int device, int precision, const float* qkv, const int32_t
     for (void* p : pool) hipFree(p);
     if (rc) return rc;
     if (e != hipSuccess) { set_error("attention op failed: %s", hipGetErrorString(e)); return PGMI_EHIP; }
+    return PGMI_OK;
+}
+
+// The attention of one decoder layer (run_decoder, api_gpt.hip) in slot space, through the launchers and the argument pattern it uses.
+// Fused form (X, W, bias): split the activations, make the weight planes, the fused QKV projection with H = heads * lanes / 64 slot groups
+// and rot_halves = lanes / 64, then the causal attention on its operands.  Conv form (qkv, conv): fp32 rows into the attention's
+// depth-wise-convolution prep pass.  Shapes are the launchers' to refuse; only what the uploads themselves need is checked here.
+int pgmi_op_causal_attention(int device, int lanes, const float* X, const float* W, const float* bias, int K, const float* qkv,
+                             const float* conv, const float* rot_cos, const float* rot_sin, const float* slopes, int B, int T,
+                             int heads, float* ctx) {
+    const bool fused = X && W && bias && !qkv && !conv, conv_form = qkv && conv && !X && !W && !bias && !rot_cos && !rot_sin;
+    if ((!fused && !conv_form) || !slopes || !ctx || B <= 0 || T <= 0 || heads <= 0 || lanes <= 0 || !rot_cos != !rot_sin) { set_error("bad argument"); return PGMI_EINVAL; }
+    // the activation / weight split writes K-interleaved rows (ki_off) before any launcher sees K: whole groups of 32 only
+    if (fused && (K <= 0 || K % 32)) { set_error("causal attention op: K = %d is not a positive multiple of 32", K); return PGMI_EINVAL; }
+    if (pgmi_device_count() <= 0) { set_error("no HIP device visible"); return PGMI_ENODEV; }
+    PGMI_HIP(hipSetDevice(device));
+    gemm_options_from_env();
+    const size_t M = (size_t)B * T, Da = (size_t)heads * lanes, Tp = (size_t)(T + 31) / 32 * 32, Hs = Da / kHeadDim;
+    const int halves = lanes / kHeadDim, rotary = rot_cos != nullptr;
+    const size_t qk_plane = M * 2 * Da, vt_plane = (size_t)B * Tp * Da;
+    std::vector<void*> pool;
+    auto cleanup = [&]() { for (void* p : pool) hipFree(p); };
+    float *dx = nullptr, *db = nullptr, *dq = nullptr, *dconv = nullptr, *dcos = nullptr, *dsin = nullptr, *dsl = nullptr;
+    unsigned short *a16 = nullptr, *qk16 = nullptr, *vt16 = nullptr, *c16 = nullptr;
+    int rc = 0;
+    if ((rc = dev_upload(pool, &dsl, slopes, (size_t)heads)) || (rc = dev_alloc(pool, &qk16, qk_plane * 2)) ||
+        (rc = dev_alloc(pool, &vt16, vt_plane * 2)) || (rc = dev_alloc(pool, &c16, M * Da * 2)) ||
+        (fused && ((rc = dev_upload(pool, &dx, X, M * K)) || (rc = dev_upload(pool, &db, bias, 3 * Da)) || (rc = dev_alloc(pool, &a16, M * K * 2)))) ||
+        (rotary && ((rc = dev_upload(pool, &dcos, rot_cos, (size_t)T * std::max(halves, 1) * kHeadDim)) ||
+                    (rc = dev_upload(pool, &dsin, rot_sin, (size_t)T * std::max(halves, 1) * kHeadDim)))) ||
+        (conv_form && ((rc = dev_upload(pool, &dq, qkv, M * 3 * Da)) || (rc = dev_upload(pool, &dconv, conv, (size_t)3 * 4 * kHeadDim * 8))))) {
+        cleanup();
+        return rc;
+    }
+    hipError_t e = hipMemset(vt16, 0, vt_plane * 2 * sizeof(unsigned short));      // pad keys: finite (reset_pad_keys)
+    if (e != hipSuccess) { cleanup(); set_error("causal attention op failed: %s", hipGetErrorString(e)); return PGMI_EHIP; }
+    if (fused) {
+        W16 w16;
+        rc = make_w16(pool, W, 3 * Da * K, (size_t)K, PGMI_PREC_F16X3, nullptr, &w16);
+        if (!rc) {
+            launch_split16(dx, (int64_t)(M * K), 1.0f, 2, K, a16, nullptr);
+            rc = launch_gemm16_qkv(a16, M * K, w16.p, w16.plane, db, (int)M, (int)Da, K, w16.out_scale, qk16, qk_plane, vt16, vt_plane,
+                                   dcos, dsin, rotary, T, (int)Hs, env_int("PGMI_GEMM_VARIANT", 0), nullptr, halves, false);
+        }
+    }
+    if (!rc) rc = launch_attention_f16x3_v2(dq, nullptr, dcos, dsin, rotary, B, T, heads, qk16, qk_plane, vt16, vt_plane, nullptr, c16, M * Da,
+                                            1, nullptr, dconv, dsl, lanes);
+    std::vector<unsigned short> h(rc ? 0 : M * Da * 2);
+    e = hipDeviceSynchronize();
+    if (!rc && e == hipSuccess) e = hipMemcpy(h.data(), c16, h.size() * 2, hipMemcpyDeviceToHost);
+    cleanup();
+    if (rc) return rc;
+    if (e != hipSuccess) { set_error("causal attention op failed: %s", hipGetErrorString(e)); return PGMI_EHIP; }
+    for (size_t m = 0; m < M; ++m)                               // the context planes (K-interleaved rows of Da) rebuilt as fp32
+        for (size_t n = 0; n < Da; ++n) {
+            const size_t o = ki_off(m, (int)n, (int)Da);
+            ctx[m * Da + n] = rebuild_split(h[o], h[o + 32]);
+        }
     return PGMI_OK;
 }
 

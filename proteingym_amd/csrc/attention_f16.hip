@@ -528,6 +528,7 @@ int launch_attention_f16x3_v2(const float* qkv, const int32_t* kv_len, const flo
         return PGMI_OK;
     }
     if (qkv && conv && rotary) { set_error("attention_f16x3_v2: depth-wise convolution and rotary together are not a model this library knows"); return PGMI_EINVAL; }
+    if (qkv && conv && H % 4) { set_error("attention_f16x3_v2: the depth-wise convolution has four head groups, H = %d is not a multiple of 4", H); return PGMI_EINVAL; }
     if (qkv && conv)       // Tranception: LDS-staged depth-wise conv + split
         launch_qkv_prep_conv(dim3(n32, H, B), s, qkv, conv, T, H, Tp, qk16, qk_plane, vt16, vt_plane, nullptr);
     else if (qkv)          // operands not prepared by the fused QKV epilogue: run the prep pass

@@ -10,11 +10,12 @@ def _layernorm(x, w, b, eps):
     return (x - mu) / np.sqrt(var + eps) * w + b
 
 
-def numpy_forward(cfg, blob, ids):
-    """log_softmax(logits) [T, V] in float64 for one row of ids."""
+def numpy_forward(cfg, blob, ids, dtype=np.float64):
+    """log_softmax(logits) [T, V] for one row of ids, computed in `dtype`: float64 is the reference; float32 is the same forward in plain
+    fp32, whose distance from the float64 one (noise32) sizes the tolerance of long contexts."""
     D, F, V, H, L, P = cfg["embed_dim"], cfg["ffn_dim"], cfg["vocab"], cfg["heads"], cfg["layers"], cfg["max_positions"]
     dh, eps, rita = D // H, cfg["ln_eps"], cfg["family"] == "rita"
-    w = blob.astype(np.float64)
+    w = blob.astype(dtype)
     o = 0
 
     def take(*shape):
@@ -30,7 +31,7 @@ def numpy_forward(cfg, blob, ids):
     if not rita:
         x = x + take(P, D)[:T]
     inv = (1.0 / (10000 ** (np.arange(0, dh, 2, dtype=np.float32) / np.float32(dh)))).astype(np.float32)
-    ang = (np.arange(T, dtype=np.float32)[:, None] * inv[None, :]).astype(np.float64)    # fp32 angle, as the reference
+    ang = (np.arange(T, dtype=np.float32)[:, None] * inv[None, :]).astype(dtype)    # fp32 angle, as the reference
     cos, sin = np.concatenate([np.cos(ang)] * 2, -1)[:, None, :], np.concatenate([np.sin(ang)] * 2, -1)[:, None, :]
 
     def rot(t):
@@ -46,13 +47,13 @@ def numpy_forward(cfg, blob, ids):
         q, k, v = ((h @ W.T + b).reshape(T, H, dh) for W, b in ((wq, bq), (wk, bk), (wv, bv)))
         if rita:
             q, k = rot(q), rot(k)
-        s = np.einsum("thd,shd->hts", q, k) / np.sqrt(dh)
-        s = np.where(mask[None], s, -np.inf)
+        s = np.einsum("thd,shd->hts", q, k) / float(np.sqrt(dh))
+        s = np.where(mask[None], s, dtype(-np.inf))
         p = np.exp(s - s.max(-1, keepdims=True))
         p /= p.sum(-1, keepdims=True)
         x = x + np.einsum("hts,shd->thd", p, v).reshape(T, D) @ wo.T + bo
         u = _layernorm(x, ln2_w, ln2_b, eps) @ w1.T + b1
-        g = 0.5 * u * (1.0 + np.tanh(np.sqrt(2.0 / np.pi) * (u + 0.044715 * u ** 3)))
+        g = 0.5 * u * (1.0 + np.tanh(float(np.sqrt(2.0 / np.pi)) * (u + 0.044715 * u ** 3)))
         x = x + g @ w2.T + b2
     lnf_w, lnf_b = take(D), take(D)
     head = take(V, D) if rita else wte

@@ -53,6 +53,29 @@ def test_token_logprobs_toy(g_rita, g_gpt2, family, name):
         m.close()
 
 
+@pytest.mark.parametrize("T", [97, 129, 1024])
+@pytest.mark.parametrize("family,name", [("rita", "h64"), ("rita", "h128"), ("gpt2", "h64")])
+def test_token_logprobs_longer_contexts(g_gpt2, family, name, T):
+    """The toy models beyond T = 77, up to the families' real context: four and more key tiles, several query blocks per sequence, the
+    LDS ring wrapping.  Against the float64 forward over the packed blob; the bound is max(1e-4, 3 noise32), noise32 = the same forward
+    in plain fp32 against the float64 one (the rule of test_gpu_progen2.py::test_token_logprobs_real_width)."""
+    m = rita_model(name) if family == "rita" else gpt2_model(name, int(g_gpt2["vocab_size"]))
+    try:
+        cfg = m.cfg
+        D, H, seed = (RITA_TOY if family == "rita" else GPT2_TOY)[name]
+        blob = clm.pack(cfg, (S.rita_state_dict if family == "rita" else S.gpt2_state_dict)(cfg, seed))
+        ids = np.random.default_rng(T + D + H).integers(0, cfg["vocab"], (1 if T == 1024 else 2, T)).astype(np.int32)
+        lp = m.token_logprobs(ids)
+        for b, row in enumerate(ids):
+            ref = numpy_forward(cfg, blob, row)
+            noise32 = float(np.abs(numpy_forward(cfg, blob, row, np.float32) - ref).max())
+            err, tol = float(np.abs(lp[b] - ref).max()), max(1e-4, 3 * noise32)
+            print(f"causal_lm long {family} {name} T={T} row={b} err={err:.3e} noise32={noise32:.3e} tol={tol:.3e}")
+            assert err <= tol, (family, name, T, b, err, tol)
+    finally:
+        m.close()
+
+
 def test_wide_head_at_protgpt2_vocabulary():
     """V = 50 257 (pad columns up to 50 304), D = 1280, 2 layers, T = 45: full rows and scored targets against float64."""
     sh = S.PROTGPT2_SHAPE
