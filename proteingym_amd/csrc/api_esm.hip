@@ -125,17 +125,18 @@ int run_encoder(pgmi_model* m, int B, int T, const int32_t* keep, int n_keep, bo
               return rc;
           const bool v2 = prec != PGMI_PREC_FP32;
           if (c.arch == PGMI_ARCH_ESM2 && !v2) launch_rotary(m->qkv, m->rot_cos, m->rot_sin, M, T, m->Hs, s, m->rot_halves);
-          if (prec == PGMI_PREC_F16X3)
-              rc = launch_attention_f16x3_v2(nullptr, m->kv_len, m->rot_cos, m->rot_sin, c.arch == PGMI_ARCH_ESM2, B, T, H,
-                                             m->qk16, m->qk16_plane, m->vt16, m->vt16_plane, nullptr, m->h16,
-                                             m->h16_plane, 1, s, nullptr, nullptr, m->rot_halves * kHeadDim);
-          else if (v2)         // bf16 mode: the context rows leave as one bf16 plane (the out-projection's operand)
-              rc = launch_attention_f16x3_v2(nullptr, m->kv_len, m->rot_cos, m->rot_sin, c.arch == PGMI_ARCH_ESM2, B, T, H,
-                                             m->qk16, m->qk16_plane, m->vt16, m->vt16_plane, nullptr, m->h16, m->h16_plane, 2, s, nullptr, nullptr,
-                                             m->rot_halves * kHeadDim);
-          else
-              rc = launch_attention_f32(m->qkv, m->kv_len, B, T, H, m->h, m->h16, m->h16_plane,
-                                        prec == PGMI_PREC_FP32 ? 0 : mode16, s, m->rot_halves * kHeadDim);
+          if (v2) {
+              AttLaunch a;
+              a.qk16 = m->qk16, a.qk_plane = m->qk16_plane, a.vt16 = m->vt16, a.vt_plane = m->vt16_plane;
+              a.B = B, a.T = T, a.H = H, a.head_dim = m->rot_halves * kHeadDim;
+              a.kv_len = m->kv_len;
+              a.out = prec == PGMI_PREC_F16X3 ? ATT_OUT_SPLIT : ATT_OUT_BF16;      // bf16 mode: one bf16 plane (the out-projection's operand)
+              a.ctx16 = m->h16;
+              a.stream = s;
+              rc = launch_attention_f16x3_v2(a);
+          } else {
+              rc = launch_attention_f32(m->qkv, m->kv_len, B, T, H, m->h, s, m->rot_halves * kHeadDim);
+          }
           if (rc) return rc; }
         if (keep && m->keep_rows && l == c.layers - 1) {
             const int R = n_keep;

@@ -118,13 +118,14 @@ int run_decoder(pgmi_model* m, int B, int T, const AttRagged* rg, int rows, doub
             if (rc) return rc;
         }
         { ProfScope p(m, PGMI_K_ATTENTION, rg ? att_flops : 2.0 * M * T * Da, 0);     // causal: half of the 4 M T Da of a dense pass
-          const float* qkv = L.conv ? m->qkv : nullptr;
-          if (rg)
-              rc = launch_attention_tr_ragged(qkv, L.conv, m->slopes, T, H, *rg, m->qk16, m->qk16_plane, m->vt16, m->vt16_plane,
-                                              m->h16, m->h16_plane, s);
-          else
-              rc = launch_attention_f16x3_v2(qkv, nullptr, m->rot_cos, m->rot_sin, rotary, B, T, H, m->qk16, m->qk16_plane, m->vt16,
-                                             m->vt16_plane, nullptr, m->h16, m->h16_plane, 1, s, L.conv, m->slopes, m->rot_halves * kHeadDim);
+          AttLaunch a;
+          a.qk16 = m->qk16, a.qk_plane = m->qk16_plane, a.vt16 = m->vt16, a.vt_plane = m->vt16_plane;
+          a.B = B, a.T = T, a.H = H, a.head_dim = m->rot_halves * kHeadDim;
+          a.slopes = m->slopes;
+          a.out = ATT_OUT_SPLIT, a.ctx16 = m->h16;
+          a.stream = s;
+          if (L.conv) a.qkv = m->qkv, a.conv = L.conv;
+          rc = rg ? launch_attention_tr_ragged(a, *rg) : launch_attention_f16x3_v2(a);
           if (rc) return rc; }
         { ProfScope p(m, PGMI_K_GEMM_OUT, 2.0 * M * D * Da, 0);
           rc = linear(m, nullptr, m->h16, m->h16_plane, nullptr, L.wo16, L.bo, m->x, m->x, nullptr, 0, M, D, Da, EPI_NONE);

@@ -66,6 +66,16 @@ int run_msa(pgmi_model* m, int R, int C, int keep_col, bool* compacted) {
     const int Rp = (R + 31) / 32 * 32, Cp = (C + 31) / 32 * 32;
     if ((int64_t)Rp * Cp > m->max_rows) { set_error("alignment of %d x %d tokens exceeds the workspace (%d rows): create the model with max_rows >= %lld", R, C, m->max_rows, (long long)Rp * Cp); return PGMI_EINVAL; }
     int rc = 0;
+    // column attention: `columns` sequences of R rows each, operands from the fused QKV projection, split-plane context rows into h16
+    auto column_attention = [&](int columns) {
+        AttLaunch a;
+        a.qk16 = m->qk16, a.qk_plane = m->qk16_plane, a.vt16 = m->vt16, a.vt_plane = m->vt16_plane;
+        a.B = columns, a.T = R, a.H = H;
+        a.kv_len = m->msa_kv_len;
+        a.out = ATT_OUT_SPLIT, a.ctx16 = m->h16;
+        a.stream = s;
+        return a;
+    };
     // split the (r, d) contraction of the tied scores so that the launch fills the chip: S divides R, ~2 rounds of tiles at most
     const int Kp = (C + 63) / 64 * 64;                      // the update GEMM's K (columns j), zero-padded
     int S = 1;
@@ -142,8 +152,7 @@ int run_msa(pgmi_model* m, int R, int C, int keep_col, bool* compacted) {
             rc = launch_gemm16_qkv(m->h16, m->h16_plane, L.c_wqkv16.p, L.c_wqkv16.plane, L.c_bqkv, R, D, D, L.c_wqkv16.out_scale,
                                    m->qk16, m->qk16_plane, m->vt16, m->vt16_plane, nullptr, nullptr, 0, R, H, m->gemm_variant, s);
             if (rc) return rc;
-            rc = launch_attention_f16x3_v2(nullptr, m->msa_kv_len, nullptr, nullptr, 0, 1, R, H, m->qk16, m->qk16_plane, m->vt16,
-                                           m->vt16_plane, nullptr, m->h16, m->h16_plane, 1, s);
+            rc = launch_attention_f16x3_v2(column_attention(1));
             if (rc) return rc;
             rc = linear(m, nullptr, m->h16, m->h16_plane, nullptr, L.c_wo16, L.c_bo, m->xt, m->xt, nullptr, 0, R, D, D, EPI_NONE);
             if (rc) return rc;
@@ -168,8 +177,7 @@ int run_msa(pgmi_model* m, int R, int C, int keep_col, bool* compacted) {
                                  m->qk16, m->qk16_plane, m->vt16, m->vt16_plane, nullptr, nullptr, 0, R, H, m->gemm_variant, s);
           if (rc) return rc; }
         { ProfScope p(m, PGMI_K_ATTENTION, 4.0 * (double)M * R * D, 0);
-          rc = launch_attention_f16x3_v2(nullptr, m->msa_kv_len, nullptr, nullptr, 0, C, R, H, m->qk16, m->qk16_plane, m->vt16,
-                                         m->vt16_plane, nullptr, m->h16, m->h16_plane, 1, s);
+          rc = launch_attention_f16x3_v2(column_attention(C));
           if (rc) return rc; }
         { ProfScope p(m, PGMI_K_GEMM_OUT, 2.0 * M * D * D, 0);
           rc = linear(m, nullptr, m->h16, m->h16_plane, nullptr, L.c_wo16, L.c_bo, m->xt, m->xt, nullptr, 0, M, D, D, EPI_NONE);

@@ -281,11 +281,16 @@ int pgmi_op_attention(int device, int precision, const float* qkv, const int32_t
         unsigned short *qk = nullptr, *vt = nullptr;
         rc = dev_alloc(pool, &qk, (size_t)B * T * 2 * D * 2);
         if (!rc) rc = dev_alloc(pool, &vt, (size_t)B * Tp * D * 2);
-        if (!rc) rc = launch_attention_f16x3_v2(dq, dl, tmp.rot_cos, tmp.rot_sin, rotary, B, T, H, qk, (size_t)B * T * 2 * D,
-                                                vt, (size_t)B * Tp * D, dc, nullptr, 0, 0, nullptr);
+        AttLaunch a;
+        a.qk16 = qk, a.qk_plane = (size_t)B * T * 2 * D, a.vt16 = vt, a.vt_plane = (size_t)B * Tp * D;
+        a.B = B, a.T = T, a.H = H;
+        a.kv_len = dl;
+        a.out = ATT_OUT_F32, a.ctx = dc;
+        a.qkv = dq, a.cos_t = tmp.rot_cos, a.sin_t = tmp.rot_sin, a.rotary = rotary;
+        if (!rc) rc = launch_attention_f16x3_v2(a);
     } else if (!rc) {
         if (rotary) launch_rotary(dq, tmp.rot_cos, tmp.rot_sin, B * T, T, H, nullptr);
-        rc = launch_attention_f32(dq, dl, B, T, H, dc, nullptr, 0, 0, nullptr);
+        rc = launch_attention_f32(dq, dl, B, T, H, dc, nullptr);
     }
     hipDeviceSynchronize();
     for (void* p : tmp.allocs) hipFree(p);
@@ -338,8 +343,13 @@ int pgmi_op_causal_attention(int device, int lanes, const float* X, const float*
                                    dcos, dsin, rotary, T, (int)Hs, env_int("PGMI_GEMM_VARIANT", 0), nullptr, halves, false);
         }
     }
-    if (!rc) rc = launch_attention_f16x3_v2(dq, nullptr, dcos, dsin, rotary, B, T, heads, qk16, qk_plane, vt16, vt_plane, nullptr, c16, M * Da,
-                                            1, nullptr, dconv, dsl, lanes);
+    AttLaunch a;
+    a.qk16 = qk16, a.qk_plane = qk_plane, a.vt16 = vt16, a.vt_plane = vt_plane;
+    a.B = B, a.T = T, a.H = heads, a.head_dim = lanes;
+    a.slopes = dsl;
+    a.out = ATT_OUT_SPLIT, a.ctx16 = c16;
+    a.qkv = dq, a.conv = dconv;             // conv form only (the fused form's operands carry the rotary already)
+    if (!rc) rc = launch_attention_f16x3_v2(a);
     std::vector<unsigned short> h(rc ? 0 : M * Da * 2);
     e = hipDeviceSynchronize();
     if (!rc && e == hipSuccess) e = hipMemcpy(h.data(), c16, h.size() * 2, hipMemcpyDeviceToHost);

@@ -25,39 +25,33 @@ template <int WPB, int OUT, int NSTG, int DH = 64, bool RAG = false, int DO = DH
 __global__ __launch_bounds__(WPB * 64) void attention_f16x3_v2_kernel(
     const unsigned short* __restrict__ qk16, size_t qk_plane, const unsigned short* __restrict__ vt16,
     size_t vt_plane, const int32_t* __restrict__ kv_len, const float* __restrict__ slopes, int T, int H,
-    int Tp, float* __restrict__ ctx, unsigned short* __restrict__ ctx16, size_t plane, RagMap rag, int dense_nblk, int nseq) {
+    int Tp, float* __restrict__ ctx, unsigned short* __restrict__ ctx16, RagMap rag, int dense_nblk, int nseq) {
     constexpr float defer_thr = kAttDefer;
     // slopes != nullptr selects the Tranception flavour (tranception/model_pytorch.py:155-183): causal
     // mask (key <= query) and the grouped-ALiBi bias slope[h] * key added to the scaled scores.
     constexpr int NT = WPB * 64;
-    // A tile is 16 wave-instructions of 64 chunks (K hi, K lo, V^T hi, V^T lo: 1024 x 16 B).  Every
-    // wave issues the same number NDMA of them (counted vmcnt needs a per-wave constant): when
-    // 16 % WPB != 0 the surplus slots re-issue instruction (i - 16), i.e. write identical bytes twice.
+    // A tile is 16 wave-instructions of 64 chunks (K hi, K lo, V^T hi, V^T lo: 1024 x 16 B) at DH 64, 32 at DH 128, 48 at DH 256 / DO 128.
+    // Every wave issues the same number NDMA of them (counted vmcnt needs a per-wave constant).
     constexpr int KCPR = DH / 8;                        // 16-byte chunks per key row of a K plane
     constexpr int KCH = AKT * KCPR, VCH = DO * 4;       // chunks per K plane / V^T plane (the slice's DO rows) of a tile
     constexpr int NSL = DH / DO;                        // context slices per head
-    static_assert(NSL == 1 || (OUT == 1 && !RAG), "sliced context: split-plane output of dense launches only");
+    static_assert(NSL == 1 || (OUT == ATT_OUT_SPLIT && !RAG), "sliced context: split-plane output of dense launches only");
     constexpr int STG_CH = 2 * KCH + 2 * VCH;           // chunks per stage (16 KB at DH 64, 32 KB at DH 128)
     constexpr int NWI = STG_CH / 64;                    // wave-instructions per tile
-    constexpr int NDMA = (NWI + WPB - 1) / WPB;
+    static_assert(NWI % WPB == 0, "the wave-instructions of a stage divide evenly over the waves");
+    constexpr int NDMA = NWI / WPB;
     constexpr int NS = DH / 16, ND = DO / 32;
     extern __shared__ __attribute__((aligned(16))) u32x4 lds[];   // [NSTG][STG_CH]
 
-    // Dense launches (dense_nblk > 0) are ONE-dimensional in an XCD-local order (workgroup i runs on XCD i % 8): the dense_nblk query
-    // blocks of one (sequence, head) are the workgroups i, i + 8, i + 16 ... of a group of 8 dense_nblk consecutive ones -- the same
-    // XCD, dispatched together -- so that the K and V^T tiles every one of them streams reach that XCD's L2 once instead of once per
-    // query block (the (nblk, H, B) grid, dense_nblk == 0, puts them on different XCDs: 2.45 x the algorithmic bytes fetched at
-    // T = 288, profiles/r4).
+    // Dense launches with dense_nblk > 0 are one-dimensional in the XCD-local order (xcd_local_pair), else a (query block, head, sequence) grid
     int b, h, qblk_dense, hs;                   // hs: (head, slice) index, h * NSL + slice
     if (RAG) {
         b = rag.ent_seq[blockIdx.x];
         hs = blockIdx.y;
         qblk_dense = 0;
     } else if (dense_nblk > 0) {
-        const int within = (int)blockIdx.x % (8 * dense_nblk);
-        const int pair = ((int)blockIdx.x / (8 * dense_nblk)) * 8 + (within & 7);
+        const int pair = xcd_local_pair(dense_nblk, qblk_dense);
         if (pair >= nseq * H * NSL) return;
-        qblk_dense = within >> 3;
         b = pair / (H * NSL);
         hs = pair - b * (H * NSL);
     } else {
@@ -115,13 +109,11 @@ __global__ __launch_bounds__(WPB * 64) void attention_f16x3_v2_kernel(
     const size_t seq_halfs = (size_t)T * (2 * D), vt_halfs = (size_t)DH * Tp;
     const unsigned long long qk_bytes = std::min<unsigned long long>(0xFFFFFFFFull, (unsigned long long)qk_plane * 2ull + seq_halfs * 2ull);
     const unsigned long long vt_bytes = std::min<unsigned long long>(0xFFFFFFFFull, (unsigned long long)vt_plane * 2ull + vt_halfs * 2ull);
-    const __amdgpu_buffer_rsrc_t rsQK = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(qk16) + (size_t)row0 * (2 * D), 0, (int)(unsigned int)qk_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsVT = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<unsigned short*>(vt16) + (RAG ? (size_t)rag.seq_vt[b] + (size_t)h * DH * Tpo : ((size_t)b * H + h) * vt_halfs), 0, (int)(unsigned int)vt_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsQK = operand_rsrc(qk16 + (size_t)row0 * (2 * D), qk_bytes);
+    const __amdgpu_buffer_rsrc_t rsVT = operand_rsrc(vt16 + (RAG ? (size_t)rag.seq_vt[b] + (size_t)h * DH * Tpo : ((size_t)b * H + h) * vt_halfs), vt_bytes);
     // RAG: the root's planes for the key tiles before kt0 (the root owns all of its T tokens: V^T row pitch Tp)
-    const __amdgpu_buffer_rsrc_t rsQKr = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(qk16) + (size_t)rrow0 * (2 * D), 0, (int)(unsigned int)qk_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsVTr = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<unsigned short*>(vt16) + (RAG ? (size_t)rag.seq_vt[rag.seq_root[b]] + (size_t)h * DH * Tp : (size_t)0), 0, (int)(unsigned int)vt_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsQKr = operand_rsrc(qk16 + (size_t)rrow0 * (2 * D), qk_bytes);
+    const __amdgpu_buffer_rsrc_t rsVTr = operand_rsrc(vt16 + (RAG ? (size_t)rag.seq_vt[rag.seq_root[b]] + (size_t)h * DH * Tp : (size_t)0), vt_bytes);
     // causal: keys beyond the block's last query tile are never needed (uniform bound for the block)
     const bool causal = slopes != nullptr;
     const int last_q = min(T, a0 + (qblk * WPB + WPB) * 32);
@@ -132,13 +124,15 @@ __global__ __launch_bounds__(WPB * 64) void attention_f16x3_v2_kernel(
     bool is_k[NDMA];
 #pragma unroll
     for (int i = 0; i < NDMA; ++i) {
-        int wi = wave + WPB * i;                          // wave-instruction index 0 .. NWI-1 (+ duplicates)
+        int wi = wave + WPB * i;                          // wave-instruction index 0 .. NWI-1
+        // Never taken (wave < WPB and WPB divides NWI), but hipcc cannot see that `wave` is below WPB: without this line it compiles a
+        // different kernel (145 to 997 fewer instructions, every instantiation).  That is a kernel change, to be made and timed as one.
         if (wi >= NWI) wi -= NWI;
         slot0[i] = wi * 64;
         is_k[i] = wi < 2 * KCH / 64;
         if (is_k[i]) {
             const int p = wi / (KCH / 64), key = ((wi % (KCH / 64)) * 64 + lane) / KCPR;
-            const int c = (lane % KCPR) ^ (DH == 64 ? ((key >> 1) & 7) : (key & 15));
+            const int c = (lane % KCPR) ^ k_swizzle<DH>(key);
             voff[i] = voff_root[i] = key * (2 * D) * 2 + c * 16;
             voff_last[i] = min(key, T - 1 - (nkt - 1) * AKT) * (2 * D) * 2 + c * 16;
             sbase[i] = (int)((unsigned int)p * (unsigned int)qk_plane * 2u + (unsigned int)(D + h * DH) * 2u);
@@ -177,7 +171,7 @@ __global__ __launch_bounds__(WPB * 64) void attention_f16x3_v2_kernel(
 #pragma unroll
             for (int i = 0; i < NQ; ++i) {
                 const int f = i * 64 + lane, pq = f / KCH, row = (f % KCH) / KCPR;
-                const int c = (f % KCPR) ^ (DH == 64 ? ((row >> 1) & 7) : (row & 15));
+                const int c = (f % KCPR) ^ k_swizzle<DH>(row);
                 const int vo = (int)(((unsigned int)(min(q0 + row, T - 1) - a0) * (unsigned int)(2 * D) + (unsigned int)(h * DH)) * 2u + (unsigned int)c * 16u);
                 const int so = (int)((unsigned int)pq * (unsigned int)qk_plane * 2u);
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rsQK, (__attribute__((address_space(3))) void*)(qbase + i * 64), 16, vo, so, 0, 0);
@@ -187,7 +181,7 @@ __global__ __launch_bounds__(WPB * 64) void attention_f16x3_v2_kernel(
         if (active) {
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
-                const int ci = r * KCPR + ((2 * s + kh) ^ (DH == 64 ? ((r >> 1) & 7) : (r & 15)));
+                const int ci = r * KCPR + ((2 * s + kh) ^ k_swizzle<DH>(r));
                 qh[s] = qbase[ci];
                 ql[s] = qbase[KCH + ci];
             }
@@ -221,7 +215,7 @@ __global__ __launch_bounds__(WPB * 64) void attention_f16x3_v2_kernel(
         const u32x4* Kb = lds + buf * STG_CH;
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-            const int ci = r * KCPR + ((2 * s + kh) ^ (DH == 64 ? ((r >> 1) & 7) : (r & 15)));
+            const int ci = r * KCPR + ((2 * s + kh) ^ k_swizzle<DH>(r));
             const u32x4 kfh = Kb[ci], kfl = Kb[KCH + ci];
             sc = mfma_h(kfh, ql[s], s == 0 ? zero16 : sc);       // s == 0: the accumulator operand is the inline constant 0
             sc = mfma_h(kfl, qh[s], sc);
@@ -313,23 +307,14 @@ __global__ __launch_bounds__(WPB * 64) void attention_f16x3_v2_kernel(
             for (int m = 0; m < 2; ++m) {
                 u32x4 ph, pl;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {                    // hi by truncation (pkrtz), lo = (p - hi) 2^11
-                    const float p0 = st[8 * m + 2 * e], p1 = st[8 * m + 2 * e + 1];
-                    typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
-                    const fp16x2 hi2 = __builtin_amdgcn_cvt_pkrtz(p0, p1);
-                    // (p - hi) 2^11 as one mixed-precision fma on the fp16 hi (v_fma_mix_f32): p 2^11 (one packed multiply for
-                    // the pair) and the fma are both exact
-                    typedef float f32x2 __attribute__((ext_vector_type(2)));
-                    const f32x2 ps = f32x2{p0, p1} * f32x2{kLoScale, kLoScale};
-                    const float l0 = fmaf((float)hi2[0], -kLoScale, ps[0]), l1 = fmaf((float)hi2[1], -kLoScale, ps[1]);
-                    const fp16x2 lo2 = __builtin_amdgcn_cvt_pkrtz(l0, l1);
-                    ph[e] = __builtin_bit_cast(unsigned int, hi2);
-                    pl[e] = __builtin_bit_cast(unsigned int, lo2);
+                for (int e = 0; e < 4; ++e) {
+                    const u32x2 p = split_p(st[8 * m + 2 * e], st[8 * m + 2 * e + 1]);
+                    ph[e] = p[0];
+                    pl[e] = p[1];
                 }
 #pragma unroll
                 for (int dt = 0; dt < ND; ++dt) {
-                    const int d = dt * 32 + r;
-                    const int ci = d * 4 + ((2 * m + kh) ^ ((d >> 2) & 3));
+                    const int ci = v_chunk(dt * 32 + r, m, kh);
                     const u32x4 vfh = Vb[ci], vfl = Vb[VCH + ci];
                     oc[dt] = mfma_h(vfh, pl, oc[dt]);
                     oc[dt] = mfma_h(vfl, ph, oc[dt]);
@@ -342,69 +327,12 @@ __global__ __launch_bounds__(WPB * 64) void attention_f16x3_v2_kernel(
 
     if (active) {
         const float l_tot = l_run + __shfl_xor(l_run, 32);
-        if (OUT == 3) {          // one bf16 plane, row-major (attention_f16_common.h)
-            store_ctx_bf16<ND>(om, oc, 1.0f / l_tot, kInvLo, q0 + r < T && q0 + r >= p0,
-                               ctx16 + (size_t)(orow0 + max(min(q0 + r, T - 1), p0)) * (size_t)D + (size_t)h * DH, kh);
-        } else if (OUT == 1) {
-            // Split-plane output, 16-byte stores: lane (r, kh) holds columns 8g + 4kh .. + 3 of its query row for g = 0 .. 3; one
-            // v_permlane32_swap per dword hands lane (r, 0) its partner's half of an even g and lane (r, 1) its partner's half of
-            // the following odd g, so every lane owns 8 consecutive columns = one dwordx4 per plane: 8 store instructions per
-            // lane instead of 16 of half the width (a row-per-lane store touches 32-64 lines per instruction: the epilogue is bound
-            // by store issue, not by bytes).  All 64 lanes take part in the swaps; rows beyond T only skip the stores.
-            const float inv = 1.0f / l_tot;
-            const bool row_ok = q0 + r < T && q0 + r >= p0;
-            unsigned short* rowp = ctx16 + (size_t)(orow0 + max(min(q0 + r, T - 1), p0)) * (size_t)(2 * D) + (size_t)((h * DH + d0) / 32) * 64;
-#pragma unroll
-            for (int dt = 0; dt < ND; ++dt)
-#pragma unroll
-                for (int gp = 0; gp < 2; ++gp) {
-                    unsigned int w[2][4];                        // [g parity][hi0 hi1 lo0 lo1]
-#pragma unroll
-                    for (int gi = 0; gi < 2; ++gi) {
-                        const int g = 2 * gp + gi;
-                        _Float16 hh[4], ll[4];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) split_act(fmaf(oc[dt][4 * g + e], kInvLo, om[dt][4 * g + e]) * inv, hh[e], ll[e]);
-                        w[gi][0] = pack_h2(hh[0], hh[1]); w[gi][1] = pack_h2(hh[2], hh[3]);
-                        w[gi][2] = pack_h2(ll[0], ll[1]); w[gi][3] = pack_h2(ll[2], ll[3]);
-                    }
-                    unsigned int first[4], second[4];            // columns c .. c + 3 and c + 4 .. c + 7 of this lane's 8-column run
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const auto sw = __builtin_amdgcn_permlane32_swap(w[0][k], w[1][k], false, false);
-                        first[k] = sw[0];                        // kh 0: own g even          kh 1: partner's (kh 0) g odd
-                        second[k] = sw[1];                       // kh 0: partner's g even    kh 1: own g odd
-                    }
-                    if (row_ok) {
-                        unsigned short* dst = rowp + dt * 64 + 8 * (2 * gp + kh);
-                        *reinterpret_cast<u32x4*>(dst) = u32x4{first[0], first[1], second[0], second[1]};
-                        *reinterpret_cast<u32x4*>(dst + 32) = u32x4{first[2], first[3], second[2], second[3]};
-                    }
-                }
-        } else if (q0 + r < T && q0 + r >= p0) {
-            const float inv = 1.0f / l_tot;
-            const size_t off = (size_t)(orow0 + q0 + r) * D + (size_t)h * DH + 4 * kh;
-#pragma unroll
-            for (int dt = 0; dt < ND; ++dt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    float val[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) val[e] = fmaf(oc[dt][4 * g + e], kInvLo, om[dt][4 * g + e]) * inv;
-                    const size_t oo = off + dt * 32 + 8 * g;
-                    if constexpr (OUT == 0) {
-                        *reinterpret_cast<f32x4*>(ctx + oo) = f32x4{val[0], val[1], val[2], val[3]};
-                    } else {
-                        _Float16 hh[4], ll[4];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) split_act(val[e], hh[e], ll[e]);
-                        // K-interleaved GEMM operand (common.h ki_off): column h*DH + dt*32 + 8g + 4kh of a row of D
-                        unsigned short* dst = ctx16 + (size_t)(orow0 + q0 + r) * (size_t)(2 * D) + (size_t)(ND * h + dt) * 64 + 8 * g + 4 * kh;
-                        *reinterpret_cast<u32x2*>(dst) = u32x2{pack_h2(hh[0], hh[1]), pack_h2(hh[2], hh[3])};
-                        *reinterpret_cast<u32x2*>(dst + 32) = u32x2{pack_h2(ll[0], ll[1]), pack_h2(ll[2], ll[3])};
-                    }
-                }
-        }
+        const float inv = 1.0f / l_tot;
+        const bool row_ok = q0 + r < T && q0 + r >= p0;                 // rows beyond T, or before the sequence's own first token, are not written
+        const size_t orow = (size_t)(orow0 + max(min(q0 + r, T - 1), p0));
+        if (OUT == ATT_OUT_BF16) store_ctx_bf16<ND>(om, oc, inv, kInvLo, row_ok, ctx16 + orow * (size_t)D + (size_t)h * DH, kh);
+        else if (OUT == ATT_OUT_SPLIT) store_ctx_split<ND>(om, oc, inv, kInvLo, row_ok, ctx16 + orow * (size_t)(2 * D) + (size_t)((h * DH + d0) / 32) * 64, kh);
+        else if (row_ok) store_ctx_f32<ND>(om, oc, inv, kInvLo, ctx + (size_t)(orow0 + q0 + r) * D + (size_t)h * DH + 4 * kh);
     }
 }
 
@@ -416,32 +344,38 @@ __global__ __launch_bounds__(WPB * 64) void attention_f16x3_v2_kernel(
 // prefetch hides is small beside that.  The XCD-local block ORDER alone (the query blocks of one (sequence, head) on one XCD, K / V^T fetched
 // into its L2 once) is +2.5 % at T = 1024 and -2 % at T = 288 (att_ab_1_xcd_local_order.log): fetch traffic is not what bounds this kernel.
 
+// Every instantiation of the v2 family, written once: the dense, the head_dim 128 / 256 and the ragged launches all pick theirs here.
+// lds: NSTG stages of K (2 planes x 32 keys x DH / 8) + V^T (2 x DO x 4) chunks of 16 B.
+using Att16v2Kernel = decltype(&attention_f16x3_v2_kernel<4, ATT_OUT_F32, 3, 64, false, 64>);
+struct Att16v2Inst { int wpb, out, head_dim; bool rag; Att16v2Kernel fn; size_t lds_bytes; };
 template <int WPB, int OUT, int NSTG, int DH, bool RAG = false, int DO = DH>
-static int launch_att16v2_one(dim3 grid, const unsigned short* qk16, size_t qk_plane, const unsigned short* vt16, size_t vt_plane,
-                              const int32_t* kv_len, const float* slopes, int T, int H, int Tp, float* ctx, unsigned short* ctx16,
-                              size_t plane, hipStream_t s, RagMap rag = RagMap{}, int dense_nblk = 0, int nseq = 0) {
-    constexpr size_t lds_bytes = (size_t)NSTG * (8 * DH + 8 * DO) * 16;  // stage = K (2 planes x 32 keys x DH / 8) + V^T (2 x DO x 4) chunks of 16 B
-    auto kfn = attention_f16x3_v2_kernel<WPB, OUT, NSTG, DH, RAG, DO>;
-    if (lds_bytes > 65536) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PGMI_EHIP; }
-    }
-    hipLaunchKernelGGL(kfn, grid, dim3(WPB * 64), lds_bytes, s, qk16, qk_plane, vt16, vt_plane, kv_len, slopes, T, H, Tp, ctx, ctx16, plane, rag, dense_nblk, nseq);
-    return PGMI_OK;
+static constexpr Att16v2Inst att16v2_inst() {
+    return {WPB, OUT, DH, RAG, attention_f16x3_v2_kernel<WPB, OUT, NSTG, DH, RAG, DO>, (size_t)NSTG * (8 * DH + 8 * DO) * 16};
 }
+static const Att16v2Inst kAtt16v2[] = {
+    att16v2_inst<1, ATT_OUT_F32, 3, 64>(),   att16v2_inst<2, ATT_OUT_F32, 3, 64>(),   att16v2_inst<4, ATT_OUT_F32, 3, 64>(),
+    att16v2_inst<1, ATT_OUT_SPLIT, 3, 64>(), att16v2_inst<2, ATT_OUT_SPLIT, 3, 64>(), att16v2_inst<4, ATT_OUT_SPLIT, 3, 64>(),
+    att16v2_inst<1, ATT_OUT_BF16, 3, 64>(),  att16v2_inst<2, ATT_OUT_BF16, 3, 64>(),  att16v2_inst<4, ATT_OUT_BF16, 3, 64>(),
+    att16v2_inst<1, ATT_OUT_SPLIT, 3, 64, true>(), att16v2_inst<2, ATT_OUT_SPLIT, 3, 64, true>(), att16v2_inst<4, ATT_OUT_SPLIT, 3, 64, true>(),
+    att16v2_inst<4, ATT_OUT_F32, 3, 128>(),  att16v2_inst<4, ATT_OUT_SPLIT, 3, 128>(), att16v2_inst<4, ATT_OUT_BF16, 3, 128>(),
+    att16v2_inst<4, ATT_OUT_SPLIT, 2, 256, false, 128>(),
+};
 
-template <int OUT, int NSTG>
-static int launch_att16v2_mode(int wpb, dim3 grid, const unsigned short* qk16, size_t qk_plane,
-                               const unsigned short* vt16, size_t vt_plane, const int32_t* kv_len,
-                               const float* slopes, int T, int H, int Tp, float* ctx, unsigned short* ctx16,
-                               size_t plane, hipStream_t s, int dense_nblk, int nseq) {
-    const RagMap none{};
-    switch (wpb) {
-        case 1: return launch_att16v2_one<1, OUT, NSTG, 64>(grid, qk16, qk_plane, vt16, vt_plane, kv_len, slopes, T, H, Tp, ctx, ctx16, plane, s, none, dense_nblk, nseq);
-        case 2: return launch_att16v2_one<2, OUT, NSTG, 64>(grid, qk16, qk_plane, vt16, vt_plane, kv_len, slopes, T, H, Tp, ctx, ctx16, plane, s, none, dense_nblk, nseq);
-        case 3: return launch_att16v2_one<3, OUT, NSTG, 64>(grid, qk16, qk_plane, vt16, vt_plane, kv_len, slopes, T, H, Tp, ctx, ctx16, plane, s, none, dense_nblk, nseq);
-        default: return launch_att16v2_one<4, OUT, NSTG, 64>(grid, qk16, qk_plane, vt16, vt_plane, kv_len, slopes, T, H, Tp, ctx, ctx16, plane, s, none, dense_nblk, nseq);
+// The one function between a caller's descriptor and a v2 kernel.  rag != nullptr: the ragged form (grid = entries x H), else dense (dense_grid).
+static int launch_att16v2(const AttLaunch& a, int wpb, dim3 grid, const RagMap* rag, int dense_nblk) {
+    for (const Att16v2Inst& k : kAtt16v2) {
+        if (k.wpb != wpb || k.out != a.out || k.head_dim != a.head_dim || k.rag != (rag != nullptr)) continue;
+        if (k.lds_bytes > 65536) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds_bytes);
+            if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PGMI_EHIP; }
+        }
+        hipLaunchKernelGGL(k.fn, grid, dim3(wpb * 64), k.lds_bytes, a.stream, a.qk16, a.qk_plane, a.vt16, a.vt_plane, a.kv_len, a.slopes,
+                           a.T, a.H, (a.T + 31) / 32 * 32, a.ctx, a.ctx16, rag ? *rag : RagMap{}, dense_nblk, a.B);
+        PGMI_HIP(hipGetLastError());
+        return PGMI_OK;
     }
+    set_error("attention_f16x3_v2: no kernel for %d waves, output %d, head_dim %d%s", wpb, (int)a.out, a.head_dim, rag ? ", ragged" : "");
+    return PGMI_EINVAL;
 }
 
 // Launch option (pgmi_set_option "att_xcd_local", default 1): 1 = the one-dimensional XCD-local order of the dense launches, 0 = the
@@ -470,32 +404,33 @@ int att16_waves_per_block(int T) {
     return wpb == 3 ? 4 : wpb;                    // measured: a 4th (idle) wave that only helps loading beats 3-wave blocks
 }
 
-// qkv fp32 [B*T, 3D] -> (rotary) -> split planes -> attention.  Scratch: qk16 2 planes of B*T*2D
-// halfs (plane stride qk_plane), vt16 2 planes of B*H*64*Tp halfs (plane stride vt_plane), Tp = T
-// rounded up to 32.
-int launch_attention_f16x3_v2(const float* qkv, const int32_t* kv_len, const float* cos_t, const float* sin_t,
-                              int rotary, int B, int T, int H, unsigned short* qk16, size_t qk_plane,
-                              unsigned short* vt16, size_t vt_plane, float* ctx, unsigned short* ctx16, size_t plane,
-                              int out_mode, hipStream_t s, const float* conv, const float* slopes, int head_dim) {
-    if (B <= 0 || T <= 0 || H <= 0 || out_mode < 0 || out_mode > 2 || (head_dim != 64 && head_dim != 128 && head_dim != 256)) {      // out_mode 2: one bf16 plane
-        set_error("attention_f16x3_v2: bad arguments B=%d T=%d H=%d out=%d head_dim=%d", B, T, H, out_mode, head_dim);
+// The K / V^T DMA addresses both planes of ONE sequence / (sequence, head) through a buffer descriptor based there, with 32-bit
+// byte offsets: the lo plane sits one plane stride further, so plane stride + one sequence must stay below 4 GiB (the arrays
+// themselves may be larger).  Every supported model fits with room (ESM2-15B at 98 304 rows: 2.0e9 bytes per q|k plane; an MSA
+// Transformer workspace of 1024 x 1024 tokens: 3.2e9); anything beyond is refused here instead of wrapping.
+static int check_operand_range(const char* who, const AttLaunch& a) {
+    const unsigned long long Tp = (unsigned long long)(a.T + 31) / 32 * 32;
+    const unsigned long long seq_bytes = (unsigned long long)a.T * 2ull * (unsigned long long)a.H * (unsigned long long)a.head_dim * 2ull;
+    const unsigned long long vt_bytes = (unsigned long long)a.head_dim * Tp * 2ull;
+    if ((unsigned long long)a.qk_plane * 2ull + seq_bytes >= (1ull << 32) || (unsigned long long)a.vt_plane * 2ull + vt_bytes >= (1ull << 32)) {
+        set_error("%s: operand planes of %zu / %zu halfs exceed the 32-bit offset range of the K / V^T DMA "
+                  "(plane stride + one sequence must stay below 4 GiB: create the model with a smaller max_rows)", who, a.qk_plane, a.vt_plane);
+        return PGMI_EINVAL;
+    }
+    return PGMI_OK;
+}
+
+// (prep pass over a.qkv ->) split planes -> attention.  Tp = T rounded up to 32.
+int launch_attention_f16x3_v2(const AttLaunch& a) {
+    const int B = a.B, T = a.T, H = a.H, head_dim = a.head_dim;
+    if (B <= 0 || T <= 0 || H <= 0 || a.out < ATT_OUT_F32 || a.out > ATT_OUT_BF16 || (head_dim != 64 && head_dim != 128 && head_dim != 256)) {
+        set_error("attention_f16x3_v2: bad arguments B=%d T=%d H=%d out=%d head_dim=%d", B, T, H, (int)a.out, head_dim);
         return PGMI_EINVAL;
     }
     const int n32 = (T + 31) / 32, Tp = n32 * 32;
-    int rc = PGMI_OK;
-    // The K / V^T DMA addresses both planes of ONE sequence / (sequence, head) through a buffer descriptor based there, with 32-bit
-    // byte offsets: the lo plane sits one plane stride further, so plane stride + one sequence must stay below 4 GiB (the arrays
-    // themselves may be larger).  Every supported model fits with room (ESM2-15B at 98 304 rows: 2.0e9 bytes per q|k plane; an MSA
-    // Transformer workspace of 1024 x 1024 tokens: 3.2e9); anything beyond is refused here instead of wrapping.
-    {
-        const unsigned long long seq_bytes = (unsigned long long)T * 2ull * (unsigned long long)H * (unsigned long long)head_dim * 2ull;
-        const unsigned long long vt_bytes = (unsigned long long)head_dim * (unsigned long long)Tp * 2ull;
-        if ((unsigned long long)qk_plane * 2ull + seq_bytes >= (1ull << 32) || (unsigned long long)vt_plane * 2ull + vt_bytes >= (1ull << 32)) {
-            set_error("attention_f16x3_v2: operand planes of %zu / %zu halfs exceed the 32-bit offset range of the K / V^T DMA "
-                      "(plane stride + one sequence must stay below 4 GiB: create the model with a smaller max_rows)", qk_plane, vt_plane);
-            return PGMI_EINVAL;
-        }
-    }
+    int rc = check_operand_range("attention_f16x3_v2", a);
+    if (rc) return rc;
+    int dn = 0;
     if (head_dim == 256) {
         // ProGen2-xlarge: H heads of 256 = 4 H slot groups of 64; causal only, fused-QKV operands, split-plane context out.  Sizing (160 KiB
         // LDS per CU; VGPRs and AGPRs share one file of 512 per lane at one wave per SIMD): Q fragments of 256 dims are 2 x 16 x 4 = 128
@@ -503,80 +438,44 @@ int launch_attention_f16x3_v2(const float* qkv, const int32_t* kv_len, const flo
         // keeps the context of one 128-dim slice (DO = 128: 128 O registers; two slices per head, S computed by both).  A stage holds K
         // (2 planes x 32 keys x 512 B) and the slice's V^T (2 x 128 x 64 B) = 48 KiB; the ring is 2 stages (96 KiB) with Q straight from
         // the planes: the Q-via-LDS staging of the 3-stage ring would need 4 waves x 32 KiB inside stages 1 .. 2.
-        if (qkv || conv || !slopes || out_mode != 1) { set_error("attention_f16x3_v2: head_dim 256 is the causal, fused-QKV, split-plane-output flavour only"); return PGMI_EINVAL; }
-        const int nblk = (n32 + 3) / 4;
-        int dn = 0;
-        const dim3 grid = dense_grid(nblk, 2 * H, B, &dn);       // (sequence, head, slice) pairs
-        rc = launch_att16v2_one<4, 1, 2, 256, false, 128>(grid, qk16, qk_plane, vt16, vt_plane, kv_len, slopes, T, H, Tp, ctx, ctx16, plane, s, RagMap{}, dn, B);
-        if (rc) return rc;
-        PGMI_HIP(hipGetLastError());
-        return PGMI_OK;
+        if (a.qkv || a.conv || !a.slopes || a.out != ATT_OUT_SPLIT) { set_error("attention_f16x3_v2: head_dim 256 is the causal, fused-QKV, split-plane-output flavour only"); return PGMI_EINVAL; }
+        const dim3 grid = dense_grid((n32 + 3) / 4, 2 * H, B, &dn);       // (sequence, head, slice) pairs
+        return launch_att16v2(a, 4, grid, nullptr, dn);
     }
     if (head_dim == 128) {
         // ESM2-15B class: H heads of 128 = 2 H slot groups of 64 in the operand planes; only the fused-QKV operand path
         // (no prep pass), no depth-wise convolution; 3-stage ring (3 x 32 KB).  slopes != nullptr: the causal flavour (ProGen2, head
         // dims 80 / 96 / 128 zero-padded into the 128-lane layout; its all-zero slopes make the ALiBi term exactly 0)
-        if (qkv || conv) { set_error("attention_f16x3_v2: head_dim 128 needs operands from the fused QKV projection"); return PGMI_EINVAL; }
-        const int nblk = (n32 + 3) / 4;
-        int dn = 0;
-        const dim3 grid = dense_grid(nblk, H, B, &dn);
-        if (out_mode == 0) rc = launch_att16v2_one<4, 0, 3, 128>(grid, qk16, qk_plane, vt16, vt_plane, kv_len, slopes, T, H, Tp, ctx, ctx16, plane, s, RagMap{}, dn, B);
-        else if (out_mode == 2) rc = launch_att16v2_one<4, 3, 3, 128>(grid, qk16, qk_plane, vt16, vt_plane, kv_len, slopes, T, H, Tp, ctx, ctx16, plane, s, RagMap{}, dn, B);
-        else rc = launch_att16v2_one<4, 1, 3, 128>(grid, qk16, qk_plane, vt16, vt_plane, kv_len, slopes, T, H, Tp, ctx, ctx16, plane, s, RagMap{}, dn, B);
-        if (rc) return rc;
-        PGMI_HIP(hipGetLastError());
-        return PGMI_OK;
+        if (a.qkv || a.conv) { set_error("attention_f16x3_v2: head_dim 128 needs operands from the fused QKV projection"); return PGMI_EINVAL; }
+        const dim3 grid = dense_grid((n32 + 3) / 4, H, B, &dn);
+        return launch_att16v2(a, 4, grid, nullptr, dn);
     }
-    if (qkv && conv && rotary) { set_error("attention_f16x3_v2: depth-wise convolution and rotary together are not a model this library knows"); return PGMI_EINVAL; }
-    if (qkv && conv && H % 4) { set_error("attention_f16x3_v2: the depth-wise convolution has four head groups, H = %d is not a multiple of 4", H); return PGMI_EINVAL; }
-    if (qkv && conv)       // Tranception: LDS-staged depth-wise conv + split
-        launch_qkv_prep_conv(dim3(n32, H, B), s, qkv, conv, T, H, Tp, qk16, qk_plane, vt16, vt_plane, nullptr);
-    else if (qkv)          // operands not prepared by the fused QKV epilogue: run the prep pass
-        launch_qkv_prep(dim3(n32, H, B), s, qkv, cos_t, sin_t, rotary, T, H, Tp, qk16, qk_plane, vt16, vt_plane);
-    const int wpb = att16_waves_per_block(T), nblk = (n32 + wpb - 1) / wpb;
-    int dn = 0;
-    const dim3 grid = dense_grid(nblk, H, B, &dn);
-    if (att_v3_serves(T, conv, slopes, head_dim)) rc = launch_att16v3(out_mode, wpb, grid, qk16, qk_plane, vt16, vt_plane, kv_len, T, H, Tp, ctx, ctx16, s, dn, B);
-    else if (out_mode == 0) rc = launch_att16v2_mode<0, 3>(wpb, grid, qk16, qk_plane, vt16, vt_plane, kv_len, slopes, T, H, Tp, ctx, ctx16, plane, s, dn, B);
-    else if (out_mode == 2) rc = launch_att16v2_mode<3, 3>(wpb, grid, qk16, qk_plane, vt16, vt_plane, kv_len, slopes, T, H, Tp, ctx, ctx16, plane, s, dn, B);
-    else rc = launch_att16v2_mode<1, 3>(wpb, grid, qk16, qk_plane, vt16, vt_plane, kv_len, slopes, T, H, Tp, ctx, ctx16, plane, s, dn, B);
-    if (rc) return rc;
-    PGMI_HIP(hipGetLastError());
-    return PGMI_OK;
+    if (a.qkv && a.conv && a.rotary) { set_error("attention_f16x3_v2: depth-wise convolution and rotary together are not a model this library knows"); return PGMI_EINVAL; }
+    if (a.qkv && a.conv && H % 4) { set_error("attention_f16x3_v2: the depth-wise convolution has four head groups, H = %d is not a multiple of 4", H); return PGMI_EINVAL; }
+    if (a.qkv && a.conv)   // Tranception: LDS-staged depth-wise conv + split
+        launch_qkv_prep_conv(dim3(n32, H, B), a.stream, a.qkv, a.conv, T, H, Tp, a.qk16, a.qk_plane, a.vt16, a.vt_plane, nullptr);
+    else if (a.qkv)        // operands not prepared by the fused QKV epilogue: run the prep pass
+        launch_qkv_prep(dim3(n32, H, B), a.stream, a.qkv, a.cos_t, a.sin_t, a.rotary, T, H, Tp, a.qk16, a.qk_plane, a.vt16, a.vt_plane);
+    const int wpb = att16_waves_per_block(T);
+    const dim3 grid = dense_grid((n32 + wpb - 1) / wpb, H, B, &dn);
+    return att_v3_serves(a) ? launch_att16v3(a, wpb, grid, dn) : launch_att16v2(a, wpb, grid, nullptr, dn);
 }
 
 // Tranception prefix-shared scoring (RagMap): depth-wise conv prep over a list of n_tiles (sequence, 32-token tile) entries, then causal
 // grouped-ALiBi attention over a list of n_blocks (sequence, block of att16_waves_per_block(T) query tiles) entries; split-plane context rows out (packed rows).
-int launch_attention_tr_ragged(const float* qkv, const float* conv, const float* slopes, int T, int H, const AttRagged& rg,
-                               unsigned short* qk16, size_t qk_plane, unsigned short* vt16, size_t vt_plane, unsigned short* ctx16,
-                               size_t plane, hipStream_t s) {
-    if (T <= 0 || H <= 0 || !qkv || !conv || !slopes || rg.n_tiles <= 0 || rg.n_blocks <= 0) {
+int launch_attention_tr_ragged(const AttLaunch& a, const AttRagged& rg) {
+    const int T = a.T, H = a.H;
+    if (T <= 0 || H <= 0 || !a.qkv || !a.conv || !a.slopes || a.head_dim != 64 || a.out != ATT_OUT_SPLIT || rg.n_tiles <= 0 || rg.n_blocks <= 0) {
         set_error("attention_tr_ragged: bad arguments T=%d H=%d tiles=%d blocks=%d", T, H, rg.n_tiles, rg.n_blocks);
         return PGMI_EINVAL;
     }
-    const int Tp = (T + 31) / 32 * 32;
-    {
-        const unsigned long long seq_bytes = (unsigned long long)T * 2ull * (unsigned long long)H * 64ull * 2ull;
-        const unsigned long long vt_bytes = 64ull * (unsigned long long)Tp * 2ull;
-        if ((unsigned long long)qk_plane * 2ull + seq_bytes >= (1ull << 32) || (unsigned long long)vt_plane * 2ull + vt_bytes >= (1ull << 32)) {
-            set_error("attention_tr_ragged: operand planes exceed the 32-bit offset range of the K / V^T DMA (create the model with a smaller max_rows)");
-            return PGMI_EINVAL;
-        }
-    }
+    const int rc = check_operand_range("attention_tr_ragged", a);
+    if (rc) return rc;
     const RagMap tiles{rg.seq_off, rg.seq_p, rg.seq_q, rg.seq_root, rg.seq_vt, rg.tile_seq, rg.tile_j};
-    launch_qkv_prep_conv(dim3(rg.n_tiles, H, 1), s, qkv, conv, T, H, Tp, qk16, qk_plane, vt16, vt_plane, &tiles);
+    launch_qkv_prep_conv(dim3(rg.n_tiles, H, 1), a.stream, a.qkv, a.conv, T, H, (T + 31) / 32 * 32, a.qk16, a.qk_plane, a.vt16, a.vt_plane, &tiles);
     // the same instantiation (waves per block) as the dense launch of T tokens: a row is computed by the same code
     const RagMap rag{rg.seq_off, rg.seq_p, rg.seq_q, rg.seq_root, rg.seq_vt, rg.blk_seq, rg.blk_j};
-    const dim3 grid(rg.n_blocks, H, 1);
-    int rc;
-    switch (att16_waves_per_block(T)) {
-        case 1: rc = launch_att16v2_one<1, 1, 3, 64, true>(grid, qk16, qk_plane, vt16, vt_plane, nullptr, slopes, T, H, Tp, nullptr, ctx16, plane, s, rag); break;
-        case 2: rc = launch_att16v2_one<2, 1, 3, 64, true>(grid, qk16, qk_plane, vt16, vt_plane, nullptr, slopes, T, H, Tp, nullptr, ctx16, plane, s, rag); break;
-        default: rc = launch_att16v2_one<4, 1, 3, 64, true>(grid, qk16, qk_plane, vt16, vt_plane, nullptr, slopes, T, H, Tp, nullptr, ctx16, plane, s, rag); break;
-    }
-    if (rc) return rc;
-    PGMI_HIP(hipGetLastError());
-    return PGMI_OK;
+    return launch_att16v2(a, att16_waves_per_block(T), dim3(rg.n_blocks, H, 1), &rag, 0);
 }
 
 }  // namespace pgmi

@@ -33,11 +33,9 @@ __global__ __launch_bounds__(WPB * 64, 2) void attention_f16x3_v3_kernel(
     constexpr int NWI = STG_CH / 64, NDMA = (NWI + WPB - 1) / WPB, NS = 4, ND = 2;
     extern __shared__ __attribute__((aligned(16))) u32x4 lds[];   // [NSTG][STG_CH]
     int b, h, qblk;
-    if (dense_nblk > 0) {                                         // XCD-local order (see the v2 kernel)
-        const int within = (int)blockIdx.x % (8 * dense_nblk);
-        const int pair = ((int)blockIdx.x / (8 * dense_nblk)) * 8 + (within & 7);
+    if (dense_nblk > 0) {                                         // XCD-local order
+        const int pair = xcd_local_pair(dense_nblk, qblk);
         if (pair >= nseq * H) return;
-        qblk = within >> 3;
         b = pair / H;
         h = pair - b * H;
     } else {
@@ -56,8 +54,8 @@ __global__ __launch_bounds__(WPB * 64, 2) void attention_f16x3_v3_kernel(
     const size_t seq_halfs = (size_t)T * (2 * D), vt_halfs = (size_t)DH * Tp;
     const unsigned long long qk_bytes = std::min<unsigned long long>(0xFFFFFFFFull, (unsigned long long)qk_plane * 2ull + seq_halfs * 2ull);
     const unsigned long long vt_bytes = std::min<unsigned long long>(0xFFFFFFFFull, (unsigned long long)vt_plane * 2ull + vt_halfs * 2ull);
-    const __amdgpu_buffer_rsrc_t rsQK = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(qk16) + (size_t)b * seq_halfs, 0, (int)(unsigned int)qk_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsVT = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(vt16) + ((size_t)b * H + h) * vt_halfs, 0, (int)(unsigned int)vt_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsQK = operand_rsrc(qk16 + (size_t)b * seq_halfs, qk_bytes);
+    const __amdgpu_buffer_rsrc_t rsVT = operand_rsrc(vt16 + ((size_t)b * H + h) * vt_halfs, vt_bytes);
 
     // DMA map of a stage: the v2 kernel's (K hi | K lo | V^T hi | V^T lo, 16 wave-instructions of 1 KiB over WPB waves).  Instruction i
     // of wave w is wave-instruction w + WPB i: with WPB in {1, 2, 4} its tensor and plane are compile-time (i < 8 / WPB: K), only the
@@ -71,7 +69,7 @@ __global__ __launch_bounds__(WPB * 64, 2) void attention_f16x3_v3_kernel(
         const int q4 = (wave + WPB * i) & 3;                       // quarter of the K plane: keys 8 q4 .. 8 q4 + 7
         const int key = q4 * 8 + (lane >> 3);
         krow[i] = key;
-        kvoff[i] = ((lane & 7) ^ ((key >> 1) & 7)) * 16;
+        kvoff[i] = ((lane & 7) ^ k_swizzle<DH>(key)) * 16;
     }
 #pragma unroll
     for (int i = 0; i < NDMA - NK; ++i) {
@@ -116,7 +114,7 @@ __global__ __launch_bounds__(WPB * 64, 2) void attention_f16x3_v3_kernel(
 #pragma unroll
             for (int i = 0; i < NQ; ++i) {
                 const int f = i * 64 + lane, pq = f / KCH, row = (f % KCH) / KCPR;
-                const int c = (f % KCPR) ^ ((row >> 1) & 7);
+                const int c = (f % KCPR) ^ k_swizzle<DH>(row);
                 const int vo = (int)(((unsigned int)min(q0 + row, T - 1) * (unsigned int)(2 * D) + (unsigned int)(h * DH)) * 2u + (unsigned int)c * 16u);
                 const int so = (int)((unsigned int)pq * (unsigned int)qk_plane * 2u);
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rsQK, (__attribute__((address_space(3))) void*)(qbase + i * 64), 16, vo, so, 0, 0);
@@ -126,7 +124,7 @@ __global__ __launch_bounds__(WPB * 64, 2) void attention_f16x3_v3_kernel(
         if (active) {
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
-                const int ci = r * KCPR + ((2 * s + kh) ^ ((r >> 1) & 7));
+                const int ci = r * KCPR + ((2 * s + kh) ^ k_swizzle<DH>(r));
                 qh[s] = qbase[ci];
                 ql[s] = qbase[KCH + ci];
             }
@@ -168,14 +166,13 @@ __global__ __launch_bounds__(WPB * 64, 2) void attention_f16x3_v3_kernel(
     auto vfrag = [&](const u32x4* Vb, int m, u32x4 (&fh)[ND], u32x4 (&fl)[ND]) {
 #pragma unroll
         for (int dt = 0; dt < ND; ++dt) {
-            const int d = dt * 32 + r;
-            const int ci = d * 4 + ((2 * m + kh) ^ ((d >> 2) & 3));
+            const int ci = v_chunk(dt * 32 + r, m, kh);
             fh[dt] = Vb[ci];
             fl[dt] = Vb[VCH + ci];
         }
     };
     auto kfrag = [&](const u32x4* Kb, int s, u32x4& kh_, u32x4& kl_) {
-        const int ci = r * KCPR + ((2 * s + kh) ^ ((r >> 1) & 7));
+        const int ci = r * KCPR + ((2 * s + kh) ^ k_swizzle<DH>(r));
         kh_ = Kb[ci];
         kl_ = Kb[KCH + ci];
     };
@@ -187,15 +184,10 @@ __global__ __launch_bounds__(WPB * 64, 2) void attention_f16x3_v3_kernel(
             om[dt] = mfma_h(fh[dt], ph[m], om[dt]);
         }
     };
-    auto split_p = [&](const float (&st)[16], int m, int e) {        // P -> hi by truncation, lo = (p - hi) 2^11 (the v2 kernel's)
-        const float p0 = st[8 * m + 2 * e], p1 = st[8 * m + 2 * e + 1];
-        typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
-        const fp16x2 hi2 = __builtin_amdgcn_cvt_pkrtz(p0, p1);
-        const f32x2 ps = f32x2{p0, p1} * f32x2{kLoScale, kLoScale};
-        const float l0 = fmaf((float)hi2[0], -kLoScale, ps[0]), l1 = fmaf((float)hi2[1], -kLoScale, ps[1]);
-        const fp16x2 lo2 = __builtin_amdgcn_cvt_pkrtz(l0, l1);
-        ph[m][e] = __builtin_bit_cast(unsigned int, hi2);
-        pl[m][e] = __builtin_bit_cast(unsigned int, lo2);
+    auto split_pm = [&](const float (&st)[16], int m, int e) {
+        const u32x2 p = split_p(st[8 * m + 2 * e], st[8 * m + 2 * e + 1]);
+        ph[m][e] = p[0];
+        pl[m][e] = p[1];
     };
     // The rescale of O by alpha(kt) -- decided in step kt, due after P V (kt - 1) and before P V (kt) -- is applied at the HEAD of step
     // kt + 1 (and of the closing P V): a branch in the middle of a step would cut its straight-line block, and hipcc then sinks the exp2 /
@@ -295,32 +287,32 @@ __global__ __launch_bounds__(WPB * 64, 2) void attention_f16x3_v3_kernel(
         l_run += sa + (((st[8] + st[9]) + (st[10] + st[11])) + ((st[12] + st[13]) + (st[14] + st[15])));
         PGMI_SLOT();
         oc[1] = mfma_h(vb_h[1], pl[1], oc[1]);
-        split_p(st, 0, 0);                                           // (P of m = 0 may be overwritten: its six MFMAs have issued)
+        split_pm(st, 0, 0);                                           // (P of m = 0 may be overwritten: its six MFMAs have issued)
         PGMI_SLOT();
         oc[1] = mfma_h(vb_l[1], ph[1], oc[1]);
-        split_p(st, 0, 1);
+        split_pm(st, 0, 1);
         PGMI_SLOT();
         om[1] = mfma_h(vb_h[1], ph[1], om[1]);
         kfrag(Kb, 1, k1h, k1l);
-        split_p(st, 0, 2);
+        split_pm(st, 0, 2);
         PGMI_SLOT();
         // ---- slots 12-23: scores of tile kt + 1, one k16 slice per three slots; the vector work ends in slot 16, the DMA of bundle
         //      kt + 3 (into the stage of bundle kt, free since this step's barrier) rides in the slots after it ----
         sc = mfma_h(k0h, ql[0], zero16);
-        split_p(st, 0, 3);
+        split_pm(st, 0, 3);
         PGMI_SLOT();
         sc = mfma_h(k0l, qh[0], sc);
-        split_p(st, 1, 0);
+        split_pm(st, 1, 0);
         PGMI_SLOT();
         sm = mfma_h(k0h, qh[0], zero16);
         kfrag(Kb, 2, k0h, k0l);
-        split_p(st, 1, 1);
+        split_pm(st, 1, 1);
         PGMI_SLOT();
         sc = mfma_h(k1h, ql[1], sc);
-        split_p(st, 1, 2);
+        split_pm(st, 1, 2);
         PGMI_SLOT();
         sc = mfma_h(k1l, qh[1], sc);
-        split_p(st, 1, 3);
+        split_pm(st, 1, 3);
         PGMI_SLOT();
         sm = mfma_h(k1h, qh[1], sm);
         kfrag(Kb, 3, k1h, k1l);
@@ -365,7 +357,7 @@ __global__ __launch_bounds__(WPB * 64, 2) void attention_f16x3_v3_kernel(
     if (active && nkt > 0) {
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-            const int ci = r * KCPR + ((2 * s + kh) ^ ((r >> 1) & 7));
+            const int ci = r * KCPR + ((2 * s + kh) ^ k_swizzle<DH>(r));
             const u32x4 kfh = lds[ci], kfl = lds[KCH + ci];
             sc = mfma_h(kfh, ql[s], s == 0 ? zero16 : sc);
             sc = mfma_h(kfl, qh[s], sc);
@@ -406,50 +398,11 @@ __global__ __launch_bounds__(WPB * 64, 2) void attention_f16x3_v3_kernel(
     if (active) {
         const float l_tot = l_run + __shfl_xor(l_run, 32);
         const float inv = 1.0f / l_tot;
-        if (OUT == 3) {
-            store_ctx_bf16<ND>(om, oc, inv, kInvLo, q0 + r < T, ctx16 + (size_t)(b * T + min(q0 + r, T - 1)) * (size_t)D + (size_t)h * DH, kh);
-        } else if (OUT == 1) {
-            const bool row_ok = q0 + r < T;
-            unsigned short* rowp = ctx16 + (size_t)(b * T + min(q0 + r, T - 1)) * (size_t)(2 * D) + (size_t)(ND * h) * 64;
-#pragma unroll
-            for (int dt = 0; dt < ND; ++dt)
-#pragma unroll
-                for (int gp = 0; gp < 2; ++gp) {
-                    unsigned int w[2][4];
-#pragma unroll
-                    for (int gi = 0; gi < 2; ++gi) {
-                        const int g = 2 * gp + gi;
-                        _Float16 hh[4], ll[4];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) split_act(fmaf(oc[dt][4 * g + e], kInvLo, om[dt][4 * g + e]) * inv, hh[e], ll[e]);
-                        w[gi][0] = pack_h2(hh[0], hh[1]); w[gi][1] = pack_h2(hh[2], hh[3]);
-                        w[gi][2] = pack_h2(ll[0], ll[1]); w[gi][3] = pack_h2(ll[2], ll[3]);
-                    }
-                    unsigned int first[4], second[4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const auto sw = __builtin_amdgcn_permlane32_swap(w[0][k], w[1][k], false, false);
-                        first[k] = sw[0];
-                        second[k] = sw[1];
-                    }
-                    if (row_ok) {
-                        unsigned short* dst = rowp + dt * 64 + 8 * (2 * gp + kh);
-                        *reinterpret_cast<u32x4*>(dst) = u32x4{first[0], first[1], second[0], second[1]};
-                        *reinterpret_cast<u32x4*>(dst + 32) = u32x4{first[2], first[3], second[2], second[3]};
-                    }
-                }
-        } else if (q0 + r < T) {
-            const size_t off = (size_t)(b * T + q0 + r) * D + (size_t)h * DH + 4 * kh;
-#pragma unroll
-            for (int dt = 0; dt < ND; ++dt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    float val[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) val[e] = fmaf(oc[dt][4 * g + e], kInvLo, om[dt][4 * g + e]) * inv;
-                    *reinterpret_cast<f32x4*>(ctx + off + dt * 32 + 8 * g) = f32x4{val[0], val[1], val[2], val[3]};
-                }
-        }
+        const bool row_ok = q0 + r < T;
+        const size_t orow = (size_t)(b * T + min(q0 + r, T - 1));
+        if (OUT == ATT_OUT_BF16) store_ctx_bf16<ND>(om, oc, inv, kInvLo, row_ok, ctx16 + orow * (size_t)D + (size_t)h * DH, kh);
+        else if (OUT == ATT_OUT_SPLIT) store_ctx_split<ND>(om, oc, inv, kInvLo, row_ok, ctx16 + orow * (size_t)(2 * D) + (size_t)(ND * h) * 64, kh);
+        else if (row_ok) store_ctx_f32<ND>(om, oc, inv, kInvLo, ctx + (size_t)(b * T + q0 + r) * D + (size_t)h * DH + 4 * kh);
     }
 }
 
@@ -458,35 +411,33 @@ __global__ __launch_bounds__(WPB * 64, 2) void attention_f16x3_v3_kernel(
 // 1 = wherever the kernel is defined (dense, head_dim 64, no causal / ALiBi flavour).  Same bits either way.
 static int g_att_v3 = -1;
 void att_v3_set_option(int value) { g_att_v3 = value; }
-bool att_v3_serves(int T, const float* conv, const float* slopes, int head_dim) {
-    if (g_att_v3 == 0 || conv || slopes || head_dim != 64) return false;
-    return g_att_v3 > 0 || (T + 31) / 32 >= 7;
+bool att_v3_serves(const AttLaunch& a) {
+    if (g_att_v3 == 0 || a.conv || a.slopes || a.head_dim != 64) return false;
+    return g_att_v3 > 0 || (a.T + 31) / 32 >= 7;
 }
 
+// Every instantiation of the v3 kernel: the waves per block att16_waves_per_block gives x the output kinds
+using Att16v3Kernel = decltype(&attention_f16x3_v3_kernel<4, ATT_OUT_F32>);
+struct Att16v3Inst { int wpb, out; Att16v3Kernel fn; };
 template <int WPB, int OUT>
-static void launch_att16v3_one(dim3 grid, const unsigned short* qk16, size_t qk_plane, const unsigned short* vt16, size_t vt_plane, const int32_t* kv_len,
-                               int T, int H, int Tp, float* ctx, unsigned short* ctx16, hipStream_t s, int dense_nblk, int nseq) {
-    constexpr size_t lds_bytes = (size_t)3 * A_STAGE * 16;
-    auto kfn = attention_f16x3_v3_kernel<WPB, OUT>;
-    if (lds_bytes > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    hipLaunchKernelGGL((attention_f16x3_v3_kernel<WPB, OUT>), grid, dim3(WPB * 64), lds_bytes, s, qk16, qk_plane, vt16, vt_plane, kv_len, T, H, Tp, ctx, ctx16,
-                       dense_nblk, nseq);
-}
-int launch_att16v3(int out_mode, int wpb, dim3 grid, const unsigned short* qk16, size_t qk_plane, const unsigned short* vt16, size_t vt_plane,
-                          const int32_t* kv_len, int T, int H, int Tp, float* ctx, unsigned short* ctx16, hipStream_t s, int dense_nblk, int nseq) {
-#define PGMI_V3(W)                                                                                                                          \
-    do {                                                                                                                                    \
-        if (out_mode == 2) launch_att16v3_one<W, 3>(grid, qk16, qk_plane, vt16, vt_plane, kv_len, T, H, Tp, ctx, ctx16, s, dense_nblk, nseq); \
-        else if (out_mode) launch_att16v3_one<W, 1>(grid, qk16, qk_plane, vt16, vt_plane, kv_len, T, H, Tp, ctx, ctx16, s, dense_nblk, nseq);   \
-        else launch_att16v3_one<W, 0>(grid, qk16, qk_plane, vt16, vt_plane, kv_len, T, H, Tp, ctx, ctx16, s, dense_nblk, nseq);            \
-    } while (0)
-    switch (wpb) {
-        case 1: PGMI_V3(1); break;
-        case 2: PGMI_V3(2); break;
-        default: PGMI_V3(4); break;
+static constexpr Att16v3Inst att16v3_inst() { return {WPB, OUT, attention_f16x3_v3_kernel<WPB, OUT>}; }
+static const Att16v3Inst kAtt16v3[] = {
+    att16v3_inst<1, ATT_OUT_F32>(),   att16v3_inst<2, ATT_OUT_F32>(),   att16v3_inst<4, ATT_OUT_F32>(),
+    att16v3_inst<1, ATT_OUT_SPLIT>(), att16v3_inst<2, ATT_OUT_SPLIT>(), att16v3_inst<4, ATT_OUT_SPLIT>(),
+    att16v3_inst<1, ATT_OUT_BF16>(),  att16v3_inst<2, ATT_OUT_BF16>(),  att16v3_inst<4, ATT_OUT_BF16>(),
+};
+
+int launch_att16v3(const AttLaunch& a, int wpb, dim3 grid, int dense_nblk) {
+    constexpr size_t lds_bytes = (size_t)3 * (2 * AKT * 8 + 2 * 64 * 4) * 16;      // the kernel's NSTG stages of STG_CH chunks: 48 KiB
+    for (const Att16v3Inst& k : kAtt16v3) {
+        if (k.wpb != wpb || k.out != a.out) continue;
+        hipLaunchKernelGGL(k.fn, grid, dim3(wpb * 64), lds_bytes, a.stream, a.qk16, a.qk_plane, a.vt16, a.vt_plane, a.kv_len, a.T, a.H, (a.T + 31) / 32 * 32,
+                           a.ctx, a.ctx16, dense_nblk, a.B);
+        PGMI_HIP(hipGetLastError());
+        return PGMI_OK;
     }
-#undef PGMI_V3
-    return PGMI_OK;
+    set_error("attention_f16x3_v3: no kernel for %d waves, output %d", wpb, (int)a.out);
+    return PGMI_EINVAL;
 }
 
 }  // namespace pgmi

@@ -27,10 +27,9 @@ constexpr int KT = 32;          // keys per tile
 
 // DH = 64 (heads of <= 64 dims, zero-padded slots) or 128 (ESM2-15B: a head is two adjacent 64-lane slot groups of the
 // projection; pretrained.py:387-394): the S^T contraction runs over DH / 8 fragments, O^T has DH / 32 column tiles.
-template <int WPB, int OUT, int DH = 64>
+template <int WPB, int DH = 64>
 __global__ __launch_bounds__(WPB * 64) void attention_f32_kernel(
-    const float* __restrict__ qkv, const int32_t* __restrict__ kv_len, int T, int H,
-    float* __restrict__ ctx, unsigned short* __restrict__ ctx16, size_t plane) {
+    const float* __restrict__ qkv, const int32_t* __restrict__ kv_len, int T, int H, float* __restrict__ ctx) {
     constexpr int NT = WPB * 64;
     constexpr int KS_STRIDE = DH + 4;         // K tile row stride (floats): conflict-free ds_read_b128
     constexpr int VS_STRIDE = DH;
@@ -173,90 +172,44 @@ __global__ __launch_bounds__(WPB * 64) void attention_f32_kernel(
                     f32x4 val;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) val[e] = o[dt][4 * g + e] * inv;
-                    const size_t oo = off + dt * 32 + 8 * g;
-                    if constexpr (OUT == 0) {
-                        *reinterpret_cast<f32x4*>(ctx + oo) = val;
-                    } else if constexpr (OUT == 1) {      // fp16 hi/lo planes for the f16x3 out-projection
-                        typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-                        h4 hi, lo;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            _Float16 a, b2;
-                            split_act(val[e], a, b2);
-                            hi[e] = a;
-                            lo[e] = b2;
-                        }
-                        // K-interleaved GEMM operand (common.h ki_off): column h*DH + dt*32 + 8g + 4kh of a row of D
-                        unsigned short* dst = ctx16 + ((size_t)b * T + q0 + r) * (size_t)(2 * D) + (size_t)(ND * h + dt) * 64 + 8 * g + 4 * kh;
-                        *reinterpret_cast<h4*>(dst) = hi;
-                        *reinterpret_cast<h4*>(dst + 32) = lo;
-                    } else {                              // bf16
-                        typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-                        unsigned short bb[4];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const float ve = val[e];   // copy first: bit_cast of a vector-element lvalue reads element 0
-                            unsigned int u = __builtin_bit_cast(unsigned int, ve);
-                            u += 0x7fffu + ((u >> 16) & 1u);
-                            bb[e] = (unsigned short)(u >> 16);
-                        }
-                        u32x2 pk;
-                        pk[0] = bb[0] | ((unsigned)bb[1] << 16);
-                        pk[1] = bb[2] | ((unsigned)bb[3] << 16);
-                        *reinterpret_cast<u32x2*>(ctx16 + oo) = pk;
-                    }
+                    *reinterpret_cast<f32x4*>(ctx + off + dt * 32 + 8 * g) = val;
                 }
         }
     }
 }
 
-template <int WPB, int OUT, int DH>
-static int launch_att_one(dim3 grid, const float* qkv, const int32_t* kv_len, int T, int H, float* ctx, unsigned short* ctx16,
-                          size_t plane, hipStream_t s) {
-    constexpr size_t lds_bytes = (size_t)(2 * KT * (DH + 4) + 2 * KT * DH) * sizeof(float);      // 33 KB at DH 64, 66.6 KB at DH 128
-    auto kfn = attention_f32_kernel<WPB, OUT, DH>;
-    if (lds_bytes > 65536) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PGMI_EHIP; }
-    }
-    hipLaunchKernelGGL(kfn, grid, dim3(WPB * 64), lds_bytes, s, qkv, kv_len, T, H, ctx, ctx16, plane);
-    return PGMI_OK;
-}
+// Every instantiation: the 1 .. 4 waves per block the launcher's even spread gives x the two head widths.
+// lds: 33 KB at DH 64, 66.6 KB at DH 128
+using AttF32Kernel = decltype(&attention_f32_kernel<4, 64>);
+struct AttF32Inst { int wpb, head_dim; AttF32Kernel fn; };
+template <int WPB, int DH>
+static constexpr AttF32Inst att_f32_inst() { return {WPB, DH, attention_f32_kernel<WPB, DH>}; }
+static const AttF32Inst kAttF32[] = {
+    att_f32_inst<1, 64>(),  att_f32_inst<2, 64>(),  att_f32_inst<3, 64>(),  att_f32_inst<4, 64>(),
+    att_f32_inst<1, 128>(), att_f32_inst<2, 128>(), att_f32_inst<3, 128>(), att_f32_inst<4, 128>(),
+};
 
-template <int OUT, int DH>
-static int launch_att_mode(int wpb, dim3 grid, const float* qkv, const int32_t* kv_len, int T, int H,
-                           float* ctx, unsigned short* ctx16, size_t plane, hipStream_t s) {
-    switch (wpb) {
-        case 1: return launch_att_one<1, OUT, DH>(grid, qkv, kv_len, T, H, ctx, ctx16, plane, s);
-        case 2: return launch_att_one<2, OUT, DH>(grid, qkv, kv_len, T, H, ctx, ctx16, plane, s);
-        case 3: return launch_att_one<3, OUT, DH>(grid, qkv, kv_len, T, H, ctx, ctx16, plane, s);
-        default: return launch_att_one<4, OUT, DH>(grid, qkv, kv_len, T, H, ctx, ctx16, plane, s);
-    }
-}
-
-int launch_attention_f32(const float* qkv, const int32_t* kv_len, int B, int T, int H, float* ctx,
-                         unsigned short* ctx16, size_t plane, int out_mode, hipStream_t s, int head_dim) {
-    if (B <= 0 || T <= 0 || H <= 0 || (head_dim != 64 && head_dim != 128) || out_mode < 0 || out_mode > 2) {
-        set_error("attention_f32: bad arguments B=%d T=%d H=%d head_dim=%d out=%d", B, T, H, head_dim, out_mode);
+int launch_attention_f32(const float* qkv, const int32_t* kv_len, int B, int T, int H, float* ctx, hipStream_t s, int head_dim) {
+    if (B <= 0 || T <= 0 || H <= 0 || (head_dim != 64 && head_dim != 128)) {
+        set_error("attention_f32: bad arguments B=%d T=%d H=%d head_dim=%d", B, T, H, head_dim);
         return PGMI_EINVAL;
     }
     const int n32 = (T + 31) / 32;
     const int nblk = (n32 + 3) / 4;
     const int wpb = (n32 + nblk - 1) / nblk;
-    const dim3 grid(nblk, H, B);
-    int rc;
-    if (head_dim == 128) {
-        if (out_mode == 0) rc = launch_att_mode<0, 128>(wpb, grid, qkv, kv_len, T, H, ctx, ctx16, plane, s);
-        else if (out_mode == 1) rc = launch_att_mode<1, 128>(wpb, grid, qkv, kv_len, T, H, ctx, ctx16, plane, s);
-        else rc = launch_att_mode<2, 128>(wpb, grid, qkv, kv_len, T, H, ctx, ctx16, plane, s);
-    } else {
-        if (out_mode == 0) rc = launch_att_mode<0, 64>(wpb, grid, qkv, kv_len, T, H, ctx, ctx16, plane, s);
-        else if (out_mode == 1) rc = launch_att_mode<1, 64>(wpb, grid, qkv, kv_len, T, H, ctx, ctx16, plane, s);
-        else rc = launch_att_mode<2, 64>(wpb, grid, qkv, kv_len, T, H, ctx, ctx16, plane, s);
+    const size_t lds_bytes = (size_t)(2 * KT * (head_dim + 4) + 2 * KT * head_dim) * sizeof(float);
+    for (const AttF32Inst& k : kAttF32) {
+        if (k.wpb != wpb || k.head_dim != head_dim) continue;
+        if (lds_bytes > 65536) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+            if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PGMI_EHIP; }
+        }
+        hipLaunchKernelGGL(k.fn, dim3(nblk, H, B), dim3(wpb * 64), lds_bytes, s, qkv, kv_len, T, H, ctx);
+        PGMI_HIP(hipGetLastError());
+        return PGMI_OK;
     }
-    if (rc) return rc;
-    PGMI_HIP(hipGetLastError());
-    return PGMI_OK;
+    set_error("attention_f32: no kernel for %d waves, head_dim %d", wpb, head_dim);
+    return PGMI_EINVAL;
 }
 
 }  // namespace pgmi

@@ -155,20 +155,44 @@ int launch_qkln_prep(const float* qkv, const float* q_w, const float* k_w, float
                      int T, int H, unsigned short* qk16, size_t qk_plane, unsigned short* vt16, size_t vt_plane, hipStream_t s);
 
 // ---- attention_f32.hip -------------------------------------------------------------------
-// qkv [B*T, 3*H*64] (q pre-scaled by 1/8); kv_len[b] (nullable) = valid keys.  Output: ctx fp32
-// [B*T, H*64] (out_mode 0), or fp16 hi/lo planes (1) / one bf16 plane (2) in ctx16.
-int launch_attention_f32(const float* qkv, const int32_t* kv_len, int B, int T, int H, float* ctx,
-                         unsigned short* ctx16, size_t plane, int out_mode, hipStream_t s, int head_dim = 64);   // 128: heads of two adjacent slot groups
+// qkv [B*T, 3*H*head_dim] (q pre-scaled by head_dim^-1/2); kv_len[b] (nullable) = valid keys.  Output: ctx fp32 [B*T, H*head_dim].
+int launch_attention_f32(const float* qkv, const int32_t* kv_len, int B, int T, int H, float* ctx, hipStream_t s,
+                         int head_dim = 64);   // 128: heads of two adjacent slot groups
 
 // ---- attention_f16.hip -------------------------------------------------------------------
+// What an attention launch writes its context rows as: the value is also the kernels' OUT template argument.
+enum AttOut {
+    ATT_OUT_F32 = 0,      // fp32 rows [rows][H * head_dim] in ctx
+    ATT_OUT_SPLIT = 1,    // split fp16 hi | lo, K-interleaved rows (ki_off) in ctx16: the f16x3 out-projection's operand
+    ATT_OUT_BF16 = 2      // one bf16 plane, row-major, in ctx16: the bf16 mode's out-projection operand
+};
 // Split-fp16 (f16x3) attention on the 16-bit MFMA pipe: operands as attention-ready fp16 planes (from the fused QKV projection, or
-// from a prep pass over qkv != nullptr: rotary / Tranception depth-wise conv fused), tiles moved with direct-to-LDS loads.  Scratch: qk16 (2 planes, stride qk_plane >= B*T*2*H*64 halfs) and vt16
-// (2 planes, stride vt_plane >= B*H*64*roundup(T,32) halfs).
-int launch_attention_f16x3_v2(const float* qkv, const int32_t* kv_len, const float* cos_t, const float* sin_t,
-                              int rotary, int B, int T, int H, unsigned short* qk16, size_t qk_plane,
-                              unsigned short* vt16, size_t vt_plane, float* ctx, unsigned short* ctx16, size_t plane,
-                              int out_mode, hipStream_t s, const float* conv = nullptr, const float* slopes = nullptr,
-                              int head_dim = 64);     // 128: H heads of two 64-lane slot groups (ESM2-15B), fused-QKV operands only
+// from a prep pass over qkv != nullptr: rotary / Tranception depth-wise conv fused), tiles moved with direct-to-LDS loads.  One launch,
+// fields assigned by name; what a caller does not need keeps its default.
+struct AttLaunch {
+    // operand planes (scratch when qkv != nullptr): qk16 2 planes of q | k rows, stride qk_plane >= B*T*2*H*head_dim halfs; vt16 2 planes of
+    // V^T per (sequence, head), stride vt_plane >= B*H*head_dim*roundup(T,32) halfs
+    unsigned short* qk16 = nullptr;
+    size_t qk_plane = 0;
+    unsigned short* vt16 = nullptr;
+    size_t vt_plane = 0;
+    int B = 1, T = 0, H = 0;
+    int head_dim = 64;                  // 128: H heads of two 64-lane slot groups (ESM2-15B), 256: of four (ProGen2-xlarge); fused-QKV operands only
+    const int32_t* kv_len = nullptr;    // [B] valid keys per sequence; nullptr: T
+    const float* slopes = nullptr;      // [H] != nullptr: the causal flavour, slopes[h] * key added to the scores (grouped ALiBi; all zero: causal only)
+    AttOut out = ATT_OUT_F32;
+    float* ctx = nullptr;               // ATT_OUT_F32
+    unsigned short* ctx16 = nullptr;    // ATT_OUT_SPLIT / ATT_OUT_BF16
+    hipStream_t stream = nullptr;
+    // optional prep pass: fp32 q | k | v rows [B*T][3*H*64] -> the operand planes, through the depth-wise convolution (conv != nullptr,
+    // Tranception) or else the rotary tables (rotary != 0)
+    const float* qkv = nullptr;
+    const float* conv = nullptr;
+    const float* cos_t = nullptr;
+    const float* sin_t = nullptr;
+    int rotary = 0;
+};
+int launch_attention_f16x3_v2(const AttLaunch& a);
 
 // Tranception prefix-shared scoring: device arrays that describe a launch over SUFFIXES of sequences (attention_f16.hip RagMap).
 struct AttRagged {
@@ -185,8 +209,7 @@ struct AttRagged {
 };
 int att16_waves_per_block(int T);
 int att_set_option(const char* name, long long value);      // "att_xcd_local": block order of the dense attention launches (A/B only)
-int launch_attention_tr_ragged(const float* qkv, const float* conv, const float* slopes, int T, int H, const AttRagged& rg,
-                               unsigned short* qk16, size_t qk_plane, unsigned short* vt16, size_t vt_plane, unsigned short* ctx16,
-                               size_t plane, hipStream_t s);
+// a: qkv, conv, slopes, T, H, the operand planes, ctx16 (ATT_OUT_SPLIT, packed rows) and the stream; B and kv_len are not read
+int launch_attention_tr_ragged(const AttLaunch& a, const AttRagged& rg);
 
 }  // namespace pgmi

@@ -46,11 +46,7 @@ def main():
                     _lib.check(_lib.load().pgmi_set_option(name.encode(), int(val)))
                 model.profile_reset()
                 model.profile_enable(True)
-                try:
-                    assay.run_device_only()
-                except _lib.PgmiError as e:                 # the timing probes of the two-role kernel (att_pp > 1) compute garbage: the range
-                    if e.code != _lib.EOVERFLOW:            # guard at the end of the forward trips, the launches have run and been timed
-                        raise
+                assay.run_device_only()
                 model.profile_enable(False)
                 pr = model.profile()["attention"]
                 res[v].append((pr["ms"] / pr["launches"], pr["flops"] / (pr["ms"] * 1e-3) / 1e12))
