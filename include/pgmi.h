@@ -56,6 +56,9 @@ extern "C" {
 /* ESM C (ESM Cambrian, proteingym/baselines/evoscale/esm/models/esmc.py): pre-LN encoder with q/k LayerNorm, SwiGLU, scaled residual;
  * created with pgmi_model_create, scored with pgmi_token_logprobs / pgmi_masked_logprobs (see the ESM C section below) */
 #define PGMI_ARCH_ESMC 7
+/* SaProt (proteingym/baselines/saprot/compute_fitness.py, HF EsmForMaskedLM): ESM2 over a 446-token structure-aware vocabulary;
+ * created with pgmi_saprot_model_create, scored with pgmi_saprot_* (see the SaProt section below) */
+#define PGMI_ARCH_SAPROT 8
 
 /* GEMM operand precision.  Residual stream, LayerNorm statistics, softmax and every
  * accumulator are fp32 in all modes. */
@@ -72,6 +75,8 @@ extern "C" {
 #define PGMI_VOCAB 33
 #define PGMI_PG2_VOCAB 32  /* ProGen2 (progen2/tokenizer.json) */
 #define PGMI_ESMC_VOCAB 64 /* ESM C: the ESM token ids above, 64 logits columns (33..63 untrained, inside the log-softmax) */
+#define PGMI_SAPROT_VOCAB 446 /* SaProt: 5 specials + 21 amino-acid letters x 21 structure letters */
+#define PGMI_SAPROT_GROUPS 21 /* amino-acid letters ACDEFGHIKLMNPQRSTVWY# = columns of the group table */
 
 typedef struct pgmi_config {
     int32_t abi_version;          /* = PGMI_ABI_VERSION */
@@ -80,7 +85,7 @@ typedef struct pgmi_config {
     int32_t embed_dim;            /* D  (encoder_embed_dim) */
     int32_t heads;                /* H  (encoder_attention_heads); head_dim D/H: 64, an even value below 64 (ESM2 8M/35M/150M: 16/24/32), or 128 (ESM2-15B) */
     int32_t ffn_dim;              /* F  (encoder_ffn_embed_dim; 4*D for ESM2, esm2.py:52) */
-    int32_t vocab;                /* = 33 */
+    int32_t vocab;                /* = 33 (other families: their section below) */
     int32_t max_positions;        /* ESM-1b learned positions (table has max_positions+2 rows, modules.py:246-251); 0 for ESM2 */
     int32_t token_dropout;        /* esm1.py:125-131 / esm2.py:85-91 */
     int32_t emb_layer_norm_before;/* pretrained.py:80-82,98 */
@@ -386,6 +391,28 @@ int pgmi_gpt_sequence_loglik(pgmi_model* m, const int32_t* tokens, const int32_t
  *   transformer.norm.weight [D]; sequence_head.0.{weight [D,D], bias}; sequence_head.2.{weight,bias}; sequence_head.3.{weight [64,D], bias [64]}.
  * pgmi_weight_count gives its size.  pgmi_masked_logprobs serves this arch (out [B,64]); ready-made rows carry their own window (ESM C's
  * window rule differs from pgmi_optimal_window, so pgmi_assay_create refuses this arch). */
+
+/* ---- SaProt (arch PGMI_ARCH_SAPROT; vocab 446, max_positions 0, every precision) ---------------------------------------------
+ * The model is ESM2 (rotary, erf-GELU, tied LM head; head dims as for ESM2) and its weight blob is ESM2's in pgmi_weight_count's order
+ * with V = 446 (HF names -> ESM names: proteingym_amd/saprot.py).  Token ids are the tokenizer's: <cls> 0, <pad> 1, <eos> 2, <unk> 3,
+ * <mask> 4, then for a in "ACDEFGHIKLMNPQRSTVWY#" and s in "pynwrqhgdlvtmfsaeikc#" the token a+s at 5 + 21 index(a) + index(s).
+ * Id 32 is an ordinary residue token here: the <mask> id is the model's own (mask_id, the config's mask_token_id = 4), and with
+ * token_dropout the embedding is scaled by 0.88 / (1 - #mask / #tokens) as in ESM2.  <pad> is honoured as in pgmi_token_logprobs.
+ *
+ * pgmi_saprot_model_create: as pgmi_model_create, with mask_id.  Returns an ordinary model: destroy, profile, synchronize as usual.
+ * pgmi_saprot_token_logprobs: log_softmax(model(input_ids).logits) over all 446 columns; tokens int32 [B,T], out f32 [B,T,446].
+ * pgmi_saprot_group_logprobs: the forwards of compute_fitness.py:17-55 for one structure chunk, one per DISTINCT set of mutated
+ *   positions (the masked input depends on nothing else).  wt_tokens int32 [T]: <cls> + the chunk's tokens + <eos>; position set s is
+ *   set_pos[set_off[s] .. set_off[s+1]) (CSR; token positions, <cls> = 0, ascending, on residue tokens).  The forward of set s
+ *   replaces every token of the set by '#' + its structure letter (the amino-acid half masked).  out f32 [set_off[n_sets]][21]:
+ *   for entry e = (set, position), out[e][a] = log sum_s p(a+s) = logsumexp(logits[5 + 21 a .. + 21)) - logsumexp(logits[0 .. 446))
+ *   at that position; the reference's per-sub-mutation term log(sum probs[mt] / sum probs[wt]) is out[e][mt] - out[e][wt], so
+ *   pgmi_score_mutants(out, n_entries, 21, sub_pos = e, sub_wt, sub_mt, ...) gives its scores.  An entry's bits do not depend on
+ *   the other sets of the call.  T + 31 > max_rows is PGMI_EINVAL: the reference does not window, neither does this path. */
+int pgmi_saprot_model_create(const pgmi_config* cfg, int mask_id, const float* weights, int64_t n_weights, int device, pgmi_model** out);
+int pgmi_saprot_token_logprobs(pgmi_model* m, const int32_t* tokens, int B, int T, float* out);
+int pgmi_saprot_group_logprobs(pgmi_model* m, const int32_t* wt_tokens, int T, const int32_t* set_off, const int32_t* set_pos,
+                               int n_sets, float* out);
 
 /* ---- MSA Transformer (arch PGMI_ARCH_MSA; vocab 33, head_dim 64, precision f16x3) --------------------
  * Replaces MSATransformer.forward (proteingym/baselines/esm/esm/model/msa_transformer.py:146-205; tied

@@ -16,6 +16,7 @@ ARCH_ESM1B, ARCH_ESM2, ARCH_TRANCEPTION = 1, 2, 3
 ARCH_PROGEN2 = 5
 ARCH_GPT = 6
 ARCH_ESMC = 7
+ARCH_SAPROT = 8
 GPT_POS_ROTARY, GPT_POS_LEARNED = 0, 1
 PREC_FP32, PREC_BF16, PREC_F16X3 = 0, 1, 2
 PRECISIONS = {"fp32": PREC_FP32, "bf16": PREC_BF16, "f16x3": PREC_F16X3}
@@ -90,6 +91,9 @@ SIGNATURES = [
     ("pgmi_gpt_model_create", C.c_int, [C.POINTER(Config), C.c_int, _f32p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     ("pgmi_gpt_token_logprobs", C.c_int, [C.c_void_p, _i32p, C.c_int, C.c_int, _f32p]),
     ("pgmi_gpt_sequence_loglik", C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, C.c_int, _f64p, _i32p]),
+    ("pgmi_saprot_model_create", C.c_int, [C.POINTER(Config), C.c_int, _f32p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
+    ("pgmi_saprot_token_logprobs", C.c_int, [C.c_void_p, _i32p, C.c_int, C.c_int, _f32p]),
+    ("pgmi_saprot_group_logprobs", C.c_int, [C.c_void_p, _i32p, C.c_int, _i32p, _i32p, C.c_int, _f32p]),
     ("pgmi_bench_gemm", C.c_int, [C.c_int] * 9 + [_f64p]),
     ("pgmi_bench_gemm_ab", C.c_int, [C.c_int] * 7 + [_i32p, C.c_int, C.c_int, C.c_int, _f64p]),
     ("pgmi_op_attention", C.c_int, [C.c_int, C.c_int, _f32p, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),
@@ -141,7 +145,8 @@ def as_f32(a):
 class ModelHandle:
     """A device-resident model behind its libpgmi handle.  __init__ builds the Config from cfg's dimensions and the fields the
     subclass passes, checks the blob size against the library's count and creates the model through CREATE; close / __del__ destroy
-    it.  pgmi_pg2_model_create and pgmi_gpt_model_create take arch_arg (ProGen2's rotary_dim, the causal decoder's pos_kind) after
+    it.  pgmi_pg2_model_create, pgmi_gpt_model_create and pgmi_saprot_model_create take arch_arg (ProGen2's rotary_dim, the causal
+    decoder's pos_kind, SaProt's <mask> id) after
     the config, and their subclasses name their weight count."""
     CREATE = "pgmi_model_create"
 

@@ -1,6 +1,6 @@
 // ESM-1b / ESM-1v / ESM2: the forward (esm/model/esm1.py:116-177, esm2.py:76-130, modules.py:120-142), masked-marginals assays
 // (compute_fitness.py:486-514) and pseudo-perplexity libraries (compute_fitness.py:258-279,515-529) behind include/pgmi.h.  ESM C
-// (api_esmc.hip) and the MSA Transformer's head run on the same encoder and head.
+// (api_esmc.hip), SaProt (api_saprot.hip) and the MSA Transformer's head run on the same encoder and head.
 #include "model.h"
 
 namespace pgmi {
@@ -49,7 +49,7 @@ int create_esm(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_
 }
 
 int ensure_rotary(pgmi_model* m, int T) {
-    if ((m->cfg.arch != PGMI_ARCH_ESM2 && m->cfg.arch != PGMI_ARCH_ESMC) || T <= m->rot_len) return PGMI_OK;
+    if ((!esm2_rotary(m->cfg.arch) && m->cfg.arch != PGMI_ARCH_ESMC) || T <= m->rot_len) return PGMI_OK;
     return upload_rotate_half(m, std::max(T, 1026));
 }
 
@@ -90,9 +90,9 @@ int run_encoder(pgmi_model* m, int B, int T, const int32_t* keep, int n_keep, bo
     {
         ProfScope p(m, PGMI_K_EMBED, 0, (double)M * D * 4);
         // kv_len: keys before the first <pad>
-        launch_seq_stats(m->tokens, B, T, m->embed_gather ? 0 : c.token_dropout, m->denom, m->pos_idx, m->kv_len, s);
+        launch_seq_stats(m->tokens, B, T, m->embed_gather ? 0 : c.token_dropout, m->denom, m->pos_idx, m->kv_len, s, m->mask_id);
         if (m->embed_gather) launch_gather_rows(m->embed_tokens, m->tokens, M, D, m->x, s);
-        else launch_embed(m->tokens, m->denom, m->pos_idx, m->embed_tokens, m->embed_positions, c.token_dropout, M, T, D, m->x, s);
+        else launch_embed(m->tokens, m->denom, m->pos_idx, m->embed_tokens, m->embed_positions, c.token_dropout, M, T, D, m->x, s, m->mask_id);
         if (m->lnb_w) {                                        // emb_layer_norm_before
             launch_layernorm(m->x, m->lnb_w, m->lnb_b, M, D, 1e-5f, m->x, s);
             launch_zero_pad_rows(m->tokens, M, D, m->x, s);
@@ -114,7 +114,7 @@ int run_encoder(pgmi_model* m, int B, int T, const int32_t* keep, int n_keep, bo
           if (fused_qkv)
               rc = launch_gemm16_qkv(m->h16, m->h16_plane, L.wqkv16.p, L.wqkv16.plane, L.bqkv, M, Da, D, L.wqkv16.out_scale,
                                      m->qk16, m->qk16_plane, m->vt16, m->vt16_plane, m->rot_cos, m->rot_sin,
-                                     c.arch == PGMI_ARCH_ESM2, T, m->Hs, m->gemm_variant, s, m->rot_halves, prec == PGMI_PREC_BF16);
+                                     esm2_rotary(c.arch), T, m->Hs, m->gemm_variant, s, m->rot_halves, prec == PGMI_PREC_BF16);
           else
               rc = linear(m, m->h, m->h16, m->h16_plane, L.wqkv, L.wqkv16, L.bqkv, nullptr, m->qkv, nullptr, 0, M, 3 * Da, D, EPI_NONE);
           if (rc) return rc; }
@@ -124,7 +124,7 @@ int run_encoder(pgmi_model* m, int B, int T, const int32_t* keep, int n_keep, bo
                                                m->vt16, m->vt16_plane, s)))
               return rc;
           const bool v2 = prec != PGMI_PREC_FP32;
-          if (c.arch == PGMI_ARCH_ESM2 && !v2) launch_rotary(m->qkv, m->rot_cos, m->rot_sin, M, T, m->Hs, s, m->rot_halves);
+          if (esm2_rotary(c.arch) && !v2) launch_rotary(m->qkv, m->rot_cos, m->rot_sin, M, T, m->Hs, s, m->rot_halves);
           if (v2) {
               AttLaunch a;
               a.qk16 = m->qk16, a.qk_plane = m->qk16_plane, a.vt16 = m->vt16, a.vt_plane = m->vt16_plane;
@@ -182,9 +182,19 @@ int run_encoder(pgmi_model* m, int B, int T, const int32_t* keep, int n_keep, bo
 // the rows are gathered from m->x first (masked positions only), else R must be the full M rows of m->x.  Result in m->lp [R,V].
 int run_head(pgmi_model* m, int R, const int32_t* row_idx) {
     const pgmi_config& c = m->cfg;
+    ProfScope p(m, PGMI_K_HEAD, 2.0 * R * c.embed_dim * (c.embed_dim + c.vocab), 0);
+    int rc = head_hidden(m, R, row_idx);
+    if (rc) return rc;
+    launch_vocab_logsoftmax(m->g, m->head_w, m->head_b, R, c.embed_dim, c.vocab, m->lp, m->nonfinite, m->stream);
+    PGMI_HIP(hipGetLastError());
+    return PGMI_OK;
+}
+
+// The head up to its LayerNorm: (gather) -> final LayerNorm -> dense + erf-GELU -> LayerNorm, in m->g [R,D].
+int head_hidden(pgmi_model* m, int R, const int32_t* row_idx) {
+    const pgmi_config& c = m->cfg;
     const int D = c.embed_dim;
     hipStream_t s = m->stream;
-    ProfScope p(m, PGMI_K_HEAD, 2.0 * R * D * (D + c.vocab), 0);
     const int prec = c.precision;
     const float* src = m->x;
     if (row_idx) {
@@ -196,8 +206,6 @@ int run_head(pgmi_model* m, int R, const int32_t* row_idx) {
     int rc = linear(m, m->h, m->h16, m->h16_plane, m->hd_w, m->hd16, m->hd_b, nullptr, m->g, nullptr, 0, R, D, D, EPI_GELU);
     if (rc) return rc;
     launch_layernorm(m->g, m->hln_w, m->hln_b, R, D, 1e-5f, m->g, s);
-    launch_vocab_logsoftmax(m->g, m->head_w, m->head_b, R, D, c.vocab, m->lp, m->nonfinite, s);
-    PGMI_HIP(hipGetLastError());
     return PGMI_OK;
 }
 
@@ -216,6 +224,7 @@ extern "C" {
 
 int pgmi_token_logprobs(pgmi_model* m, const int32_t* tokens, int B, int T, float* out) {
     if (!m || !tokens || !out || B <= 0 || T <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
+    if (m->cfg.arch == PGMI_ARCH_SAPROT) { set_error("SaProt models are scored with pgmi_saprot_token_logprobs / pgmi_saprot_group_logprobs"); return PGMI_EINVAL; }
     if (T + 31 > m->max_rows) { set_error("T=%d exceeds workspace rows %d", T, m->max_rows); return PGMI_EINVAL; }
     int rc = check_tokens(tokens, B, T);
     if (rc) return rc;
@@ -233,6 +242,7 @@ int pgmi_token_logprobs(pgmi_model* m, const int32_t* tokens, int B, int T, floa
 
 int pgmi_masked_logprobs(pgmi_model* m, const int32_t* tokens, const int32_t* mask_pos, int B, int T, float* out) {
     if (!m || !tokens || !mask_pos || !out || B <= 0 || T <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
+    if (m->cfg.arch == PGMI_ARCH_SAPROT) { set_error("SaProt models are scored with pgmi_saprot_token_logprobs / pgmi_saprot_group_logprobs"); return PGMI_EINVAL; }
     if (m->cfg.arch == PGMI_ARCH_ESMC && T + 31 > m->max_rows) { set_error("T=%d exceeds workspace rows %d", T, m->max_rows); return PGMI_EINVAL; }
     if (T > m->max_rows) { set_error("T=%d exceeds workspace rows %d", T, m->max_rows); return PGMI_EINVAL; }
     int rc = check_tokens(tokens, B, T);
@@ -264,6 +274,7 @@ int pgmi_assay_create(pgmi_model* m, const int32_t* wt_tokens, int n_tok, const 
     *out = nullptr;
     if (!m || !wt_tokens || n_tok <= 0 || P < 0 || (P > 0 && !positions) || window <= 0 || n_mut < 0) { set_error("bad argument"); return PGMI_EINVAL; }
     if (m->cfg.arch == PGMI_ARCH_ESMC) { set_error("ESM C assays run through pgmi_masked_logprobs (their window rule is not pgmi_optimal_window)"); return PGMI_EINVAL; }
+    if (m->cfg.arch == PGMI_ARCH_SAPROT) { set_error("SaProt assays run through pgmi_saprot_group_logprobs (position sets, no window)"); return PGMI_EINVAL; }
     for (int i = 0; i < n_tok; ++i)
         if (wt_tokens[i] < 0 || wt_tokens[i] >= PGMI_VOCAB || wt_tokens[i] == PGMI_TOK_PAD) { set_error("wt token %d invalid at %d", wt_tokens[i], i); return PGMI_EINVAL; }
     const int T = std::min(n_tok, window);

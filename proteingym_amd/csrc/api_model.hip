@@ -1,6 +1,6 @@
 // C ABI of libpgmi.so (include/pgmi.h): errors, configuration and token checks, weight split, model create / destroy, options and
-// profiling.  The per-architecture weight walks live in api_esm / api_esmc / api_tranception / api_progen2 / api_gpt / api_msa.hip, the
-// layer loops in api_esm.hip (encoder), api_gpt.hip (decoder) and api_msa.hip.
+// profiling.  The per-architecture weight walks live in api_esm / api_esmc / api_saprot / api_tranception / api_progen2 / api_gpt / api_msa.hip, the
+// layer loops in api_esm.hip (encoder; SaProt's entries on it in api_saprot.hip), api_gpt.hip (decoder) and api_msa.hip.
 #include "model.h"
 
 namespace pgmi {
@@ -29,7 +29,7 @@ int check_cfg(const pgmi_config* c) {
     if (!c) { set_error("null config"); return PGMI_EINVAL; }
     if (c->abi_version != PGMI_ABI_VERSION) { set_error("ABI version mismatch: got %d, library is %d", c->abi_version, PGMI_ABI_VERSION); return PGMI_EINVAL; }
     if (c->arch != PGMI_ARCH_ESM1B && c->arch != PGMI_ARCH_ESM2 && c->arch != PGMI_ARCH_TRANCEPTION && c->arch != PGMI_ARCH_MSA &&
-        c->arch != PGMI_ARCH_PROGEN2 && c->arch != PGMI_ARCH_GPT && c->arch != PGMI_ARCH_ESMC) { set_error("unknown arch %d", c->arch); return PGMI_EINVAL; }
+        c->arch != PGMI_ARCH_PROGEN2 && c->arch != PGMI_ARCH_GPT && c->arch != PGMI_ARCH_ESMC && c->arch != PGMI_ARCH_SAPROT) { set_error("unknown arch %d", c->arch); return PGMI_EINVAL; }
     if (c->layers <= 0 || c->embed_dim <= 0 || c->heads <= 0 || c->ffn_dim <= 0) { set_error("non-positive model dimension"); return PGMI_EINVAL; }
     if (c->arch == PGMI_ARCH_ESMC) {
         // the QK-LayerNorm prep pass holds a q / k row of D <= 2048 in registers; FC1's SwiGLU epilogue pairs 32-column blocks
@@ -48,7 +48,7 @@ int check_cfg(const pgmi_config* c) {
         // (api_progen2.hip)
         const bool pg2 = c->arch == PGMI_ARCH_PROGEN2;
         // causal decoder: ESM2's layout (RITA XL: head_dim 128)
-        const bool esm_layout = c->arch == PGMI_ARCH_ESM1B || c->arch == PGMI_ARCH_ESM2 || c->arch == PGMI_ARCH_GPT;
+        const bool esm_layout = c->arch == PGMI_ARCH_ESM1B || c->arch == PGMI_ARCH_ESM2 || c->arch == PGMI_ARCH_GPT || c->arch == PGMI_ARCH_SAPROT;
         const bool ok = c->embed_dim % c->heads == 0 &&
                         (dh == kHeadDim || (dh < kHeadDim && dh % 2 == 0 && esm_layout) || (dh == 2 * kHeadDim && esm_layout) ||
                          (pg2 && dh % 2 == 0 && dh <= 4 * kHeadDim));
@@ -74,6 +74,9 @@ int check_cfg(const pgmi_config* c) {
         if (c->vocab < 2) { set_error("causal decoder vocab must be at least 2, got %d", c->vocab); return PGMI_EINVAL; }
         if (c->precision != PGMI_PREC_F16X3) { set_error("the causal decoder (RITA / ProtGPT2) is available in precision f16x3 only"); return PGMI_EINVAL; }
         if (c->max_positions <= 0) { set_error("the causal decoder needs max_positions = n_positions / max_seq_len"); return PGMI_EINVAL; }
+    } else if (c->arch == PGMI_ARCH_SAPROT) {
+        if (c->vocab != PGMI_SAPROT_VOCAB) { set_error("SaProt vocab must be %d (5 specials + 21 x 21 residue tokens)", PGMI_SAPROT_VOCAB); return PGMI_EINVAL; }
+        if (c->max_positions != 0) { set_error("SaProt has rotary positions: max_positions must be 0"); return PGMI_EINVAL; }
     } else if (c->vocab != PGMI_VOCAB) { set_error("vocab must be %d", PGMI_VOCAB); return PGMI_EINVAL; }
     if (c->arch == PGMI_ARCH_ESM1B && c->max_positions <= 0) { set_error("ESM-1b arch needs max_positions"); return PGMI_EINVAL; }
     if (c->arch == PGMI_ARCH_MSA) {
@@ -88,13 +91,13 @@ int check_cfg(const pgmi_config* c) {
 }
 
 // trailing-only padding, at least one real token per sequence
-int check_tokens(const int32_t* tokens, int B, int T) {
+int check_tokens(const int32_t* tokens, int B, int T, int n_ids) {
     for (int b = 0; b < B; ++b) {
         const int32_t* t = tokens + (size_t)b * T;
         bool seen_pad = false;
         if (t[0] == PGMI_TOK_PAD) { set_error("sequence %d is empty (all <pad>)", b); return PGMI_EINVAL; }
         for (int i = 0; i < T; ++i) {
-            if (t[i] < 0 || t[i] >= PGMI_VOCAB) { set_error("token id %d out of range at [%d,%d]", t[i], b, i); return PGMI_EINVAL; }
+            if (t[i] < 0 || t[i] >= n_ids) { set_error("token id %d out of range at [%d,%d]", t[i], b, i); return PGMI_EINVAL; }
             if (t[i] == PGMI_TOK_PAD) seen_pad = true;
             else if (seen_pad) { set_error("interior <pad> at [%d,%d]: only trailing padding is supported", b, i); return PGMI_EINVAL; }
         }
@@ -230,6 +233,11 @@ int pgmi_model_create(const pgmi_config* cfg, const float* w, int64_t n_weights,
         set_error("causal decoder models are created with pgmi_gpt_model_create (it takes pos_kind)");
         return PGMI_EINVAL;
     }
+    if (cfg && cfg->arch == PGMI_ARCH_SAPROT) {
+        if (out) *out = nullptr;
+        set_error("SaProt models are created with pgmi_saprot_model_create (it takes the tokenizer's <mask> id)");
+        return PGMI_EINVAL;
+    }
     return model_create(cfg, w, n_weights, device, out, 0);
 }
 
@@ -282,7 +290,7 @@ static int alloc_workspace(pgmi_model* m) {
 }
 
 // pgmi_model_create, pgmi_pg2_model_create and pgmi_gpt_model_create; arch_arg is ProGen2's rotary_dim or the causal decoder's
-// pos_kind (0 for every other arch)
+// pos_kind, SaProt's <mask> id (0 for every other arch)
 int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int device, pgmi_model** out, int arch_arg) {
     if (!out) { set_error("null out"); return PGMI_EINVAL; }
     *out = nullptr;
@@ -318,6 +326,7 @@ int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int 
         case PGMI_ARCH_PROGEN2: rc = create_progen2(m, cfg, w, n_weights, arch_arg); break;
         case PGMI_ARCH_GPT: rc = create_gpt(m, cfg, w, n_weights, arch_arg); break;
         case PGMI_ARCH_ESMC: rc = create_esmc(m, cfg, w, n_weights); break;
+        case PGMI_ARCH_SAPROT: rc = create_saprot(m, cfg, w, n_weights, arch_arg); break;
         default: rc = create_esm(m, cfg, w, n_weights);
     }
     if (!rc) rc = alloc_workspace(m);

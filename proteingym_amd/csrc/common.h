@@ -58,13 +58,13 @@ void launch_make_masked_windows(const int32_t* wt, const int32_t* win_start, con
                                 int B, int T, int32_t* tokens_out, hipStream_t s);
 // tokens[b, mask_pos[b]] = <mask> (in place)
 void launch_apply_mask(int32_t* tokens, const int32_t* mask_pos, int B, int T, hipStream_t s);
-// per sequence: scale[b] (token-dropout rescale), pos_idx[b,t] (learned-position index), kv_len[b]
+// per sequence: scale[b] (token-dropout rescale), pos_idx[b,t] (learned-position index), kv_len[b]; mask_id = the model's <mask> id
 void launch_seq_stats(const int32_t* tokens, int B, int T, int token_dropout, float* scale,
-                      int32_t* pos_idx, int32_t* kv_len, hipStream_t s);
+                      int32_t* pos_idx, int32_t* kv_len, hipStream_t s, int mask_id = PGMI_TOK_MASK);
 void launch_zero_pad_rows(const int32_t* tokens, int rows, int D, float* x, hipStream_t s);
 void launch_embed(const int32_t* tokens, const float* scale, const int32_t* pos_idx,
                   const float* embed_tokens, const float* embed_positions, int token_dropout,
-                  int rows, int T, int D, float* x, hipStream_t s);
+                  int rows, int T, int D, float* x, hipStream_t s, int mask_id = PGMI_TOK_MASK);
 void launch_layernorm(const float* x, const float* w, const float* b, int rows, int D, float eps,
                       float* y, hipStream_t s);
 // y[i,:] = x[row_idx[i],:]
@@ -110,6 +110,14 @@ void launch_make_pppl_rows(const uint8_t* tok8, const int64_t* seq_off, const in
                            int64_t g0, int bc, int T, int32_t* tokens, int32_t* row_idx, int32_t* target, hipStream_t s);
 void launch_pppl_pick(const float* lp, const int32_t* target, int bc, int V, float* terms, hipStream_t s);
 void launch_pppl_sum(const float* terms, const int64_t* rp, const int32_t* sid, int J, int64_t first, double* out, hipStream_t s);
+// SaProt (api_saprot.hip): token rows [bc][T] of the position sets [s0, s0 + bc) (CSR set_off / set_pos, positions ascending inside a
+// set) with the masked ids, and keep[e - set_off[s0]] = the flat row of entry e
+void launch_saprot_rows(const int32_t* wt, const int32_t* set_off, const int32_t* set_pos, int s0, int bc, int T, int first, int groups,
+                        int width, int32_t* tokens, int32_t* keep, hipStream_t s);
+// per row of h [rows][D] against E [V][D] (V <= 512), in double: full [rows][V] = log-softmax (nullable); group [rows][groups] =
+// lse(logits[first + g width .. + width)) - lse(row) (nullable)
+int launch_group_logsoftmax(const float* h, const float* E, const float* bias, int rows, int D, int V, int first, int groups, int width,
+                            float* full, float* group, int32_t* nonfinite, hipStream_t s);
 
 // ---- gemm_f32.hip ------------------------------------------------------------------------
 // C[M,N] = epi(A[M,K] W[N,K]^T + bias[N]) (+ residual[M,N]); K % 32 == 0.

@@ -58,7 +58,8 @@ void launch_apply_mask(int32_t* tokens, const int32_t* mask_pos, int B, int T, h
 // pos_idx[b,t] = cumsum(tok != pad)*(tok != pad) + pad_idx          (modules.py:261-262)
 // kv_len[b]    = index of the last non-pad token + 1 (the host only admits trailing padding, so
 //                this is the number of valid keys for the attention mask).
-__global__ void seq_stats_kernel(const int32_t* __restrict__ tokens, int B, int T, int token_dropout,
+// mask_id: the model's <mask> token id (PGMI_TOK_MASK for the ESM alphabet; SaProt's tokenizer has it at 4 and an ordinary residue at 32).
+__global__ void seq_stats_kernel(const int32_t* __restrict__ tokens, int B, int T, int token_dropout, int mask_id,
                                  float* __restrict__ denom, int32_t* __restrict__ pos_idx,
                                  int32_t* __restrict__ kv_len) {
     const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -76,7 +77,7 @@ __global__ void seq_stats_kernel(const int32_t* __restrict__ tokens, int B, int 
         const int incl = __popcll(below);
         if (t < T) pos_idx[(int64_t)b * T + t] = valid ? (running + incl + PGMI_TOK_PAD) : PGMI_TOK_PAD;
         running += __popcll(bal);
-        n_mask += __popcll(__ballot((t < T) && tok == PGMI_TOK_MASK));
+        n_mask += __popcll(__ballot((t < T) && tok == mask_id));
         if (bal) last_valid = t0 + 63 - __clzll(bal);
     }
     if (lane == 0) {
@@ -87,8 +88,8 @@ __global__ void seq_stats_kernel(const int32_t* __restrict__ tokens, int B, int 
     }
 }
 void launch_seq_stats(const int32_t* tokens, int B, int T, int token_dropout, float* denom,
-                      int32_t* pos_idx, int32_t* kv_len, hipStream_t s) {
-    hipLaunchKernelGGL(seq_stats_kernel, dim3((B + 3) / 4), dim3(256), 0, s, tokens, B, T, token_dropout,
+                      int32_t* pos_idx, int32_t* kv_len, hipStream_t s, int mask_id) {
+    hipLaunchKernelGGL(seq_stats_kernel, dim3((B + 3) / 4), dim3(256), 0, s, tokens, B, T, token_dropout, mask_id,
                        denom, pos_idx, kv_len);
 }
 
@@ -96,7 +97,7 @@ void launch_seq_stats(const int32_t* tokens, int B, int T, int token_dropout, fl
 // x = E[tok] (zero for <mask> under token dropout) * 0.88 / denom[b] + Wpos[pos_idx]; pad rows -> 0.
 __global__ void embed_kernel(const int32_t* __restrict__ tokens, const float* __restrict__ denom,
                              const int32_t* __restrict__ pos_idx, const float* __restrict__ E,
-                             const float* __restrict__ P, int token_dropout, int rows, int T, int D,
+                             const float* __restrict__ P, int token_dropout, int mask_id, int rows, int T, int D,
                              float* __restrict__ x) {
     const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -108,7 +109,7 @@ __global__ void embed_kernel(const int32_t* __restrict__ tokens, const float* __
     const f32x4* p = P ? reinterpret_cast<const f32x4*>(P + (size_t)pos_idx[row] * D) : nullptr;
     f32x4* xo = reinterpret_cast<f32x4*>(x + (size_t)row * D);
     const bool is_pad = tok == PGMI_TOK_PAD;
-    const bool zero_emb = token_dropout && tok == PGMI_TOK_MASK;
+    const bool zero_emb = token_dropout && tok == mask_id;
     for (int i = lane; i < D / 4; i += 64) {
         f32x4 v = zero_emb ? f32x4{0.f, 0.f, 0.f, 0.f} : e[i];
         if (token_dropout) {
@@ -125,9 +126,9 @@ __global__ void embed_kernel(const int32_t* __restrict__ tokens, const float* __
     }
 }
 void launch_embed(const int32_t* tokens, const float* denom, const int32_t* pos_idx, const float* E,
-                  const float* P, int token_dropout, int rows, int T, int D, float* x, hipStream_t s) {
+                  const float* P, int token_dropout, int rows, int T, int D, float* x, hipStream_t s, int mask_id) {
     hipLaunchKernelGGL(embed_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, tokens, denom, pos_idx, E, P,
-                       token_dropout, rows, T, D, x);
+                       token_dropout, mask_id, rows, T, D, x);
 }
 
 // zero the rows of <pad> tokens (esm1.py:138-139), needed after emb_layer_norm_before
@@ -643,6 +644,143 @@ __global__ void seq_sum_kernel(const float* __restrict__ terms, const int32_t* _
 }
 void launch_seq_sum(const float* terms, const int32_t* off, int B, double* out, hipStream_t s) {
     hipLaunchKernelGGL(seq_sum_kernel, dim3((B + 127) / 128), dim3(128), 0, s, terms, off, B, out);
+}
+
+// ---- SaProt (api_saprot.hip) ----------------------------------------------------------------------------------------------
+// Token rows of the position sets [s0, s0 + bc) of an assay chunk (baselines/saprot/compute_fitness.py:30-36): row b is the wild type wt [T]
+// with the tokens at the set's positions set_pos[set_off[s] .. set_off[s + 1]) (ascending) replaced by their masked ids -- the '#'
+// amino-acid group with the same structure letter: first + (groups - 1) * width + (id - first) % width; a special token (id < first)
+// stays.  keep[e - set_off[s0]] = flat row of entry e: the rows the head reads.  One wave per set; a token looks itself up in the
+// set by bisection, so every element of `tokens` is written once.
+__global__ __launch_bounds__(256) void saprot_rows_kernel(const int32_t* __restrict__ wt, const int32_t* __restrict__ set_off,
+                                                          const int32_t* __restrict__ set_pos, int s0, int bc, int T, int first,
+                                                          int groups, int width, int32_t* __restrict__ tokens,
+                                                          int32_t* __restrict__ keep) {
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (b >= bc) return;
+    const int e0 = set_off[s0], lo0 = set_off[s0 + b], hi0 = set_off[s0 + b + 1];
+    int32_t* out = tokens + (int64_t)b * T;
+    for (int t = lane; t < T; t += 64) {
+        int lo = lo0, hi = hi0;                              // first entry with set_pos >= t
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (set_pos[mid] < t) lo = mid + 1; else hi = mid;
+        }
+        const int id = wt[t];
+        const bool masked = lo < hi0 && set_pos[lo] == t && id >= first;
+        out[t] = masked ? first + (groups - 1) * width + (id - first) % width : id;
+    }
+    for (int e = lo0 + lane; e < hi0; e += 64) keep[e - e0] = b * T + set_pos[e];
+}
+void launch_saprot_rows(const int32_t* wt, const int32_t* set_off, const int32_t* set_pos, int s0, int bc, int T, int first, int groups,
+                        int width, int32_t* tokens, int32_t* keep, hipStream_t s) {
+    hipLaunchKernelGGL(saprot_rows_kernel, dim3((bc + 3) / 4), dim3(256), 0, s, wt, set_off, set_pos, s0, bc, T, first, groups, width,
+                       tokens, keep);
+}
+
+// Vocabulary projection + grouped log-softmax (compute_fitness.py:42-53).  One wave per row of h [rows][D] (D % 4 == 0), V <= 512 logits
+// against the tied table E [V][D]:
+//   full  [row][V]      (nullable) = logit - lse(row)                                    the log-softmax of all V columns
+//   group [row][groups] (nullable) = lse(logits[first + g width .. + width)) - lse(row)  log of the summed probability of group g
+// so that group[mt] - group[wt] is the reference's log(sum probs[mt group] / sum probs[wt group]).  The logits and every log-sum-exp
+// are accumulated in double and rounded to fp32 once, for the reason given at vocab_logsoftmax_kernel.  The lane holds its share of
+// the hidden row in registers (128-bit loads; NV float4 per lane); logit v ends up in slot v / 64 of lane v % 64.  Every sum runs
+// over the same lanes in the same order whatever else is in the launch: a row's bits depend on V and D alone.
+constexpr int kGroupSlots = 8;
+template <int NV>
+__global__ __launch_bounds__(256) void group_logsoftmax_kernel(const float* __restrict__ h, const float* __restrict__ E,
+                                                               const float* __restrict__ bias, int rows, int D, int V, int first,
+                                                               int groups, int width, float* __restrict__ full,
+                                                               float* __restrict__ group, int32_t* __restrict__ nonfinite) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const int nv = D >> 2;
+    const f32x4* hr = reinterpret_cast<const f32x4*>(h + (size_t)row * D);
+    f32x4 x[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = lane + 64 * i;
+        x[i] = (c < nv) ? hr[c] : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    double lg[kGroupSlots];
+#pragma unroll
+    for (int j = 0; j < kGroupSlots; ++j) {
+        lg[j] = -INFINITY;
+        for (int l = 0; l < 64; ++l) {
+            const int v = 64 * j + l;
+            if (v >= V) break;                                // uniform over the wave
+            const f32x4* ev = reinterpret_cast<const f32x4*>(E + (size_t)v * D);
+            double acc = 0.0;
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const int c = lane + 64 * i;
+                if (c < nv) {
+                    const f32x4 e = ev[c];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) acc = fma((double)x[i][k], (double)e[k], acc);
+                }
+            }
+            acc = wave_sum_d(acc);
+            if (lane == l) lg[j] = acc + (double)bias[v];
+        }
+    }
+    float mx = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < kGroupSlots; ++j) mx = fmaxf(mx, (float)lg[j]);
+    mx = wave_max(mx);
+    double ex = 0.0;
+#pragma unroll
+    for (int j = 0; j < kGroupSlots; ++j) ex += (64 * j + lane < V) ? exp(lg[j] - (double)mx) : 0.0;
+    const double lse = (double)mx + log(wave_sum_d(ex));
+    bool bad = false;
+    if (full) {
+#pragma unroll
+        for (int j = 0; j < kGroupSlots; ++j) {
+            const int v = 64 * j + lane;
+            if (v < V) {
+                const float res = (float)(lg[j] - lse);
+                full[(size_t)row * V + v] = res;
+                bad |= !(fabsf(res) <= 3.0e38f);
+            }
+        }
+    }
+    if (group) {
+        float mine = 0.f;
+        for (int g = 0; g < groups; ++g) {
+            const int c0 = first + g * width;
+            double val = -INFINITY;                           // this lane's logit inside the group (width <= 64: at most one)
+#pragma unroll
+            for (int j = 0; j < kGroupSlots; ++j) {
+                const int v = 64 * j + lane;
+                if (v >= c0 && v < c0 + width && v < V) val = lg[j];
+            }
+            const float gm = wave_max((float)val);
+            const double gs = wave_sum_d(val == -INFINITY ? 0.0 : exp(val - (double)gm));
+            const float res = (float)(((double)gm + log(gs)) - lse);
+            if (lane == g) mine = res;
+        }
+        if (lane < groups) {
+            group[(size_t)row * groups + lane] = mine;
+            bad |= !(fabsf(mine) <= 3.0e38f);
+        }
+    }
+    if (nonfinite && bad) atomicOr(nonfinite, 1);             // NaN/inf: fp16 overflow upstream
+}
+int launch_group_logsoftmax(const float* h, const float* E, const float* bias, int rows, int D, int V, int first, int groups, int width,
+                            float* full, float* group, int32_t* nonfinite, hipStream_t s) {
+    if (rows <= 0) return PGMI_OK;
+    const int nv = (D / 4 + 63) / 64;
+    if (D % 4 || nv > 10 || V > 64 * kGroupSlots || groups > 64 || width > 64 || first + groups * width > V) {
+        set_error("grouped log-softmax: unsupported shape (D %d, V %d, %d groups of %d from column %d)", D, V, groups, width, first);
+        return PGMI_EINVAL;
+    }
+    const dim3 grid((rows + 3) / 4), block(256);
+#define PGMI_GLS(N) hipLaunchKernelGGL((group_logsoftmax_kernel<N>), grid, block, 0, s, h, E, bias, rows, D, V, first, groups, width, full, group, nonfinite)
+    if (nv <= 1) PGMI_GLS(1); else if (nv <= 2) PGMI_GLS(2); else if (nv <= 5) PGMI_GLS(5); else PGMI_GLS(10);
+#undef PGMI_GLS
+    return PGMI_OK;
 }
 
 }  // namespace pgmi

@@ -11,6 +11,7 @@
 //                        or ProGen2's parallel residual; dense or Tranception's ragged prefix-shared rows), narrow and wide LM heads,
 //                        the checks and token log-probs of RITA / ProtGPT2 / ProGen2; RITA / ProtGPT2 sequence log-likelihoods
 //   api_esmc.hip         ESM C weights (QK-LayerNorm, SwiGLU, scaled residual, untied 64-column head); it runs on run_encoder
+//   api_saprot.hip       SaProt: ESM2's weights and encoder with a 446-token vocabulary; position-set rows and the grouped log-softmax head
 //   api_msa.hip          MSA Transformer weights and forward (tied row attention, column attention)
 //   api_host.hip         host-only entries: mutant parser, table -> scores, optimal window
 //   api_ops.hip          single-op and timing entries for the numerics tests and the A/B scripts
@@ -82,6 +83,9 @@ struct pgmi_model {
     // table or <pad> zeroing); the causal attention's ALiBi slopes (Tranception's grouped table; `zeros` for the others)
     int fc1_epi = EPI_GELU, fc1_cols = 0;
     bool embed_gather = false;
+    // what the token checks and the embedding read per model: the <mask> id and the number of token ids (the ESM alphabet's 32 / 33;
+    // SaProt's tokenizer has <mask> at 4, 446 ids, and an ordinary residue token at 32)
+    int mask_id = PGMI_TOK_MASK, n_token_ids = PGMI_VOCAB;
     float* slopes = nullptr;
     float* tr_prior = nullptr;                          // device copy of the retrieval log-prior [P,V]
     size_t tr_prior_cap = 0;
@@ -223,7 +227,7 @@ int ensure_cap(pgmi_model* m, T** p, size_t* cap, size_t need) {
 // ---- shared helpers (api_model.hip unless noted) ----
 int prof_drain(pgmi_model* m);
 int check_cfg(const pgmi_config* c);
-int check_tokens(const int32_t* tokens, int B, int T);
+int check_tokens(const int32_t* tokens, int B, int T, int n_ids = PGMI_VOCAB);
 int check_vocab(const int32_t* tokens, int B, int T, int V);
 int env_int(const char* name, int dflt);
 int make_w16(std::vector<void*>& pool, const float* host, size_t n, size_t K, int precision, hipStream_t s, W16* out);
@@ -238,6 +242,7 @@ int create_esm(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_
 int ensure_rotary(pgmi_model* m, int T);            // ESM2 / ESM C: tables for at least T positions
 int upload_rotate_half(pgmi_model* m, int n);       // ESM2's rotary tables for positions 0..n-1 (rotate_half_slot layout)
 int run_encoder(pgmi_model* m, int B, int T, const int32_t* keep = nullptr, int n_keep = 0, bool* compacted = nullptr);
+int head_hidden(pgmi_model* m, int R, const int32_t* row_idx);   // run_head up to the LM head's LayerNorm: m->g [R,D]
 int run_head(pgmi_model* m, int R, const int32_t* row_idx);
 int run_rows(pgmi_model* m, int B, int T, int R, const int32_t* row_idx);
 // api_tranception.hip
@@ -254,9 +259,14 @@ int decoder_token_logprobs(pgmi_model* m, int arch, const int32_t* tokens, int B
 // api_esmc.hip
 int64_t esmc_weight_count(const pgmi_config* c);
 int create_esmc(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights);
+// api_saprot.hip
+int create_saprot(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights, int mask_id);
 // api_msa.hip
 int create_msa(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights);
 int run_msa(pgmi_model* m, int R, int C, int keep_col = -1, bool* compacted = nullptr);
+
+// ESM2's rotate-half rotary on q and k (SaProt is ESM2 with another vocabulary)
+inline bool esm2_rotary(int arch) { return arch == PGMI_ARCH_ESM2 || arch == PGMI_ARCH_SAPROT; }
 
 // Walks a weight blob in the order include/pgmi.h documents.  upload / w16 / linear put the next n floats on the device; their forms
 // with a host pointer upload a host re-layout instead and do not advance.  take hands the next n floats to a host re-layout.  The

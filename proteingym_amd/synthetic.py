@@ -519,3 +519,43 @@ def esmc_state_dict(cfg: dict, seed: int) -> Dict[str, np.ndarray]:
     sd["sequence_head.3.weight"] = normal((V, D), 3.0 * D ** -0.5)
     sd["sequence_head.3.bias"] = normal((V,), 0.02)
     return sd
+
+
+def saprot_config(embed_dim: int = 1280, heads: int = 20, layers: int = 33, ffn_dim: int = 0) -> dict:
+    """A SaProt configuration (SaProt-650M by default; SaProt-35M: 480, 20, 12): ESM2's shape with the 446-token vocabulary, token
+    dropout, rotary positions, no LayerNorm before the encoder, <mask> at id 4."""
+    return dict(arch=_lib.ARCH_SAPROT, layers=layers, embed_dim=embed_dim, heads=heads, ffn_dim=ffn_dim or 4 * embed_dim, vocab=446,
+                max_positions=0, token_dropout=1, emb_layer_norm_before=0, mask_token_id=4)
+
+
+def saprot_state_dict(cfg: dict, seed: int, embed_std: float = 0.15) -> Dict[str, np.ndarray]:
+    """Seeded random SaProt weights under Hugging Face EsmForMaskedLM's keys (the tied lm_head.decoder.weight is not stored).  Linear
+    weights ~ N(0, 1/fan_in), LayerNorm gains 1 + N(0, 0.1^2), biases N(0, 0.02^2); the tied embedding N(0, embed_std^2) so that the
+    log-ratios stay in the range real checkpoints produce."""
+    normal = _causal_normal(seed)
+    D, F, V = cfg["embed_dim"], cfg["ffn_dim"], cfg["vocab"]
+    sd = {"esm.embeddings.word_embeddings.weight": normal((V, D), embed_std)}
+
+    def ln(p):
+        sd[p + ".weight"] = 1.0 + normal((D,), 0.1)
+        sd[p + ".bias"] = normal((D,), 0.02)
+
+    def linear(p, n_out, n_in):
+        sd[p + ".weight"] = normal((n_out, n_in), n_in ** -0.5)
+        sd[p + ".bias"] = normal((n_out,), 0.02)
+    if cfg["emb_layer_norm_before"]:
+        ln("esm.embeddings.layer_norm")
+    for i in range(cfg["layers"]):
+        p = f"esm.encoder.layer.{i}."
+        ln(p + "attention.LayerNorm")
+        for n in ("query", "key", "value"):
+            linear(p + "attention.self." + n, D, D)
+        linear(p + "attention.output.dense", D, D)
+        ln(p + "LayerNorm")
+        linear(p + "intermediate.dense", F, D)
+        linear(p + "output.dense", D, F)
+    ln("esm.encoder.emb_layer_norm_after")
+    linear("lm_head.dense", D, D)
+    ln("lm_head.layer_norm")
+    sd["lm_head.bias"] = normal((V,), 0.02)
+    return sd
