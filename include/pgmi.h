@@ -414,6 +414,89 @@ int pgmi_saprot_token_logprobs(pgmi_model* m, const int32_t* tokens, int B, int 
 int pgmi_saprot_group_logprobs(pgmi_model* m, const int32_t* wt_tokens, int T, const int32_t* set_off, const int32_t* set_pos,
                                int n_sets, float* out);
 
+/* ---- EVE / DeepSequence (Bayesian alignment VAE; its own handle and config, precision fp32) ------------------------------------
+ * Replaces VAE_model.all_likelihood_components and the sampling loop of compute_evol_indices_chunk
+ * (proteingym/baselines/EVE/EVE/VAE_model.py:165-181, :466-481; VAE_encoder.py:69-88; VAE_decoder.py:112-167) as
+ * compute_evol_indices_DMS.py runs them: the model is never put in eval mode, so the decoder's dropout is part of the estimator.
+ * ELBO[m, j] = -(BCE + KLD) of row m under noise sample j; DESIGN.md 4.6f has the estimator, the generator and the divergences
+ * (one set of decoder weights per sample, shared by all rows of the assay).
+ *
+ * Weight blob: fp32, the tensors of VAE_model.state_dict() in its own order, each flattened row-major:
+ *   encoder.hidden_layers.{i}.weight [E_i, in_i], .bias [E_i]   i = 0 .. n_enc-1 (in_0 = 20 L)
+ *   encoder.fc_mean.weight [z, E_last], .bias [z]; encoder.fc_log_var.weight [z, E_last], .bias [z]
+ *   decoder.sparsity_weight_mean, decoder.sparsity_weight_log_var [H / tiles, L]          (sparsity_tiles > 0 only)
+ *   decoder.last_hidden_layer_weight_mean, _log_var [C L, H]     (C = conv_depth, or 20 without the convolution; H = D_last)
+ *   decoder.last_hidden_layer_bias_mean, _log_var [20 L]
+ *   decoder.temperature_scaler_mean, _log_var [1]                                        (temperature != 0 only)
+ *   decoder.hidden_layers_mean.{i}.weight [D_i, in_i], .bias [D_i]   i = 0 .. n_dec-1 (in_0 = z), then the same of
+ *   decoder.hidden_layers_log_var.{i}
+ *   decoder.output_convolution_mean.weight, decoder.output_convolution_log_var.weight [20, C, 1]     (conv_depth > 0 only)
+ * Residues: uint8 [M][L], the letter's index in "ACDEFGHIKLMNPQRSTVWY"; 255 (any value >= 20) = no letter: an all-zero one-hot row,
+ * which adds nothing to the encoder's first layer and has no target term in the BCE.
+ * Limits: alphabet 20; encoder without dropout and input convolution (both parameter files); conv_depth % 4 == 0;
+ * H % sparsity_tiles == 0; at most PGMI_EVE_MAX_LAYERS layers per stack. */
+#define PGMI_EVE_MAX_LAYERS 8
+#define PGMI_EVE_ACT_RELU 0
+#define PGMI_EVE_ACT_TANH 1
+#define PGMI_EVE_ACT_SIGMOID 2
+#define PGMI_EVE_ACT_ELU 3
+#define PGMI_EVE_ACT_LINEAR 4
+typedef struct pgmi_eve_config {
+    int32_t abi_version;                          /* = PGMI_ABI_VERSION */
+    int32_t seq_len;                              /* L: focus columns */
+    int32_t alphabet;                             /* = 20 */
+    int32_t z_dim;
+    int32_t n_enc, enc_sizes[PGMI_EVE_MAX_LAYERS];   /* encoder_parameters.hidden_layers_sizes */
+    int32_t n_dec, dec_sizes[PGMI_EVE_MAX_LAYERS];   /* decoder_parameters.hidden_layers_sizes */
+    int32_t conv_depth;                           /* convolution_output_depth when convolve_output, else 0 */
+    int32_t temperature;                          /* include_temperature_scaler */
+    int32_t sparsity_tiles;                       /* num_tiles_sparsity when include_sparsity, else 0 */
+    int32_t enc_act, dec_first_act, dec_last_act; /* PGMI_EVE_ACT_* */
+    int32_t precision;                            /* PGMI_PREC_FP32 (the only mode so far) */
+    float dropout_p;                              /* decoder_parameters.dropout_proba */
+} pgmi_eve_config;
+typedef struct pgmi_eve pgmi_eve;
+/* One sample's noise, host buffers, in the order the reference draws it (VAE_model.py:170, VAE_decoder.py:120-161): eps tensors are
+ * the randn_like draws, keep tensors the dropout layer's Bernoulli(1 - p) masks (1 = kept; read only when dropout_p > 0). */
+typedef struct pgmi_eve_noise {
+    float* z_eps;                                 /* [M][z] */
+    uint8_t* keep[PGMI_EVE_MAX_LAYERS + 1];       /* keep[0] [M][z] on z; keep[i + 1] [M][D_i] after hidden layer i */
+    float* w_eps[PGMI_EVE_MAX_LAYERS];            /* [D_i][in_i] */
+    float* b_eps[PGMI_EVE_MAX_LAYERS];            /* [D_i] */
+    float* wout_eps;                              /* [C L][H] */
+    float* bout_eps;                              /* [20 L] */
+    float* conv_eps;                              /* [20][C]; conv_depth > 0 */
+    float* sparsity_eps;                          /* [H / tiles][L]; sparsity_tiles > 0 */
+    float* temp_eps;                              /* [1]; temperature != 0 */
+} pgmi_eve_noise;
+/* pgmi_eve_weight_count: size of the blob above; -1 for a config the library refuses (pgmi_last_error).
+ * pgmi_eve_create / pgmi_eve_destroy: the device-resident model (one HIP stream).
+ * pgmi_eve_profile_model: the handle's profiling view for pgmi_profile_enable / _get / _reset / pgmi_synchronize (owned by the handle,
+ *   never destroyed by the caller).  Classes: PGMI_K_EMBED = the weight sampler, PGMI_K_GEMM_FC1 = latent + hidden layers,
+ *   PGMI_K_GEMM_FC2 = the final GEMM, PGMI_K_SCORE = the ELBO reduction, PGMI_K_HEAD = the encoder.
+ * pgmi_eve_encode: mu, log_var f32 [M][z] of the (deterministic) encoder.
+ * pgmi_eve_elbo: one sample.  Row i of the call is row row_base + i of the assay (what the generator's per-row noise is indexed by).
+ *   injected != NULL: every noise tensor comes from the caller (seed and sample are not read); NULL: from the device generator
+ *   (Philox4x32-10 keyed by seed, counter = (element / 4, sample, tensor)).  elbo / bce / kld: f32 [M], each nullable.  A row's
+ *   values depend on its residues, its global index, seed and sample only -- not on M, the other rows or the row chunking.
+ * pgmi_eve_noise_fill: writes the generator's noise of (seed, sample, rows row_base .. row_base + M) into out's non-NULL buffers.
+ * pgmi_eve_evol_indices: the production loop: samples 0 .. num_samples-1, per-row sum and sum of squares (of the ELBO minus the
+ *   row's first sample) in fp64 on the device.  mean_elbo, std_elbo: f64 [M], std with the n - 1 denominator (torch.std); row 0 is
+ *   the wild type, so evol_index[m] = -(mean_elbo[m] - mean_elbo[0]).
+ * pgmi_set_option("eve_max_rows", n): rows per chunk of the hidden layers / logits (0: what fits 256 MB of logits; test hook,
+ *   bit-neutral).  pgmi_set_option("eve_fixed_sample", j): pgmi_eve_evol_indices draws every sample with index j (-1: off; test hook
+ *   of the accumulators). */
+int64_t pgmi_eve_weight_count(const pgmi_eve_config* cfg);
+int pgmi_eve_create(const pgmi_eve_config* cfg, const float* weights, int64_t n_weights, int device, pgmi_eve** out);
+void pgmi_eve_destroy(pgmi_eve* m);
+pgmi_model* pgmi_eve_profile_model(pgmi_eve* m);
+int pgmi_eve_encode(pgmi_eve* m, const uint8_t* residues, int M, float* mu, float* log_var);
+int pgmi_eve_elbo(pgmi_eve* m, const uint8_t* residues, int M, int64_t row_base, uint64_t seed, int sample,
+                  const pgmi_eve_noise* injected, float* elbo, float* bce, float* kld);
+int pgmi_eve_noise_fill(pgmi_eve* m, uint64_t seed, int sample, int64_t row_base, int M, pgmi_eve_noise* out);
+int pgmi_eve_evol_indices(pgmi_eve* m, const uint8_t* residues, int M, int num_samples, uint64_t seed, double* mean_elbo,
+                          double* std_elbo);
+
 /* ---- MSA Transformer (arch PGMI_ARCH_MSA; vocab 33, head_dim 64, precision f16x3) --------------------
  * Replaces MSATransformer.forward (proteingym/baselines/esm/esm/model/msa_transformer.py:146-205; tied
  * row attention esm/axial_attention.py:33-168, column attention :171-297) and the masked-marginals loop

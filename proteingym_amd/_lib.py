@@ -47,6 +47,7 @@ _i32p = C.POINTER(C.c_int32)
 _i64p = C.POINTER(C.c_int64)
 _f32p = C.POINTER(C.c_float)
 _f64p = C.POINTER(C.c_double)
+_u8p = C.POINTER(C.c_uint8)
 
 # (name, restype, argtypes) -- must list every symbol include/pgmi.h declares
 SIGNATURES = [
@@ -94,6 +95,14 @@ SIGNATURES = [
     ("pgmi_saprot_model_create", C.c_int, [C.POINTER(Config), C.c_int, _f32p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     ("pgmi_saprot_token_logprobs", C.c_int, [C.c_void_p, _i32p, C.c_int, C.c_int, _f32p]),
     ("pgmi_saprot_group_logprobs", C.c_int, [C.c_void_p, _i32p, C.c_int, _i32p, _i32p, C.c_int, _f32p]),
+    ("pgmi_eve_weight_count", C.c_int64, [C.c_void_p]),
+    ("pgmi_eve_create", C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
+    ("pgmi_eve_destroy", None, [C.c_void_p]),
+    ("pgmi_eve_profile_model", C.c_void_p, [C.c_void_p]),
+    ("pgmi_eve_encode", C.c_int, [C.c_void_p, _u8p, C.c_int, _f32p, _f32p]),
+    ("pgmi_eve_elbo", C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int64, C.c_uint64, C.c_int, C.c_void_p, _f32p, _f32p, _f32p]),
+    ("pgmi_eve_noise_fill", C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int64, C.c_int, C.c_void_p]),
+    ("pgmi_eve_evol_indices", C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, C.c_uint64, _f64p, _f64p]),
     ("pgmi_bench_gemm", C.c_int, [C.c_int] * 9 + [_f64p]),
     ("pgmi_bench_gemm_ab", C.c_int, [C.c_int] * 7 + [_i32p, C.c_int, C.c_int, C.c_int, _f64p]),
     ("pgmi_op_attention", C.c_int, [C.c_int, C.c_int, _f32p, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),

@@ -370,7 +370,8 @@ int pgmi_set_option(const char* name, int64_t value) {
     if (!name) { set_error("null option name"); return PGMI_EINVAL; }
     int rc = gemm_set_option(name, (long long)value);
     if (rc) rc = att_set_option(name, (long long)value);
-    if (rc) set_error("unknown option '%s' (gemm_half_tail, gemm_max_rows, att_xcd_local, att_v3)", name);
+    if (rc) rc = eve_set_option(name, (long long)value);
+    if (rc) set_error("unknown option '%s' (gemm_half_tail, gemm_max_rows, att_xcd_local, att_v3, eve_max_rows, eve_fixed_sample)", name);
     return rc;
 }
 

@@ -119,6 +119,28 @@ void launch_saprot_rows(const int32_t* wt, const int32_t* set_off, const int32_t
 int launch_group_logsoftmax(const float* h, const float* E, const float* bias, int rows, int D, int V, int first, int groups, int width,
                             float* full, float* group, int32_t* nonfinite, hipStream_t s);
 
+// ---- eve.hip (EVE / DeepSequence; the kernels are described there) ------------------------------------------------------------
+// Noise tensor ids of the Philox counter (include/pgmi.h pgmi_eve_noise names the tensors): z eps; dropout keeps 0 .. n_dec; hidden
+// weight / bias eps per layer; W_out, b_out, conv, sparsity, temperature eps.
+enum EveTensor { PGMI_EVE_T_Z = 0, PGMI_EVE_T_KEEP = 1, PGMI_EVE_T_W = 16, PGMI_EVE_T_B = 32, PGMI_EVE_T_WOUT = 48, PGMI_EVE_T_BOUT = 49,
+                 PGMI_EVE_T_CONV = 50, PGMI_EVE_T_SPARSITY = 51, PGMI_EVE_T_TEMP = 52 };
+void launch_eve_gather(const uint8_t* res, const float* W0t, const float* b, int rows, int L, int ld, int act, float* out, hipStream_t s);
+void launch_eve_act(float* x, int rows, int n, int ld, int act, uint32_t keep24, float scale, uint64_t seed, uint32_t sample, int tensor,
+                    int64_t row_base, const uint8_t* inj, int64_t inj_row0, hipStream_t s);
+void launch_eve_latent(const float* mulv, int ldz, int64_t mulv_row0, int rows, int z, int ld, uint32_t keep24, float scale, uint64_t seed,
+                       uint32_t sample, int64_t row_base, const float* inj_eps, const uint8_t* inj_keep, int64_t inj_row0, float* h,
+                       hipStream_t s);
+void launch_eve_sample(const float* mean, const float* sd, int64_t n, int K, int Kp, uint64_t seed, uint32_t sample, int tensor,
+                       const float* inj, float* out, hipStream_t s);
+void launch_eve_sample_final(const float* w_mean, const float* w_sd, const float* c_mean, const float* c_sd, const float* s_mean,
+                             const float* s_sd, int L, int H, int Hp, int C, int Ht, bool conv, uint64_t seed, uint32_t sample,
+                             const float* inj_w, const float* inj_c, const float* inj_s, float* out, hipStream_t s);
+void launch_eve_elbo(const float* logits, const uint8_t* res, const float* mulv, int ldz, int z, const float* temp, int rows, int L,
+                     int64_t loc0, float* elbo, float* bce, float* kld, double* acc, int first, hipStream_t s);
+void launch_eve_fill_normal(uint64_t seed, uint32_t sample, int tensor, uint64_t e0, int64_t n, float* out, hipStream_t s);
+void launch_eve_fill_keep(uint64_t seed, uint32_t sample, int tensor, uint64_t e0, int64_t n, uint32_t keep24, uint8_t* out, hipStream_t s);
+int eve_set_option(const char* name, long long value);   // api_eve.hip: "eve_max_rows", "eve_fixed_sample"
+
 // ---- gemm_f32.hip ------------------------------------------------------------------------
 // C[M,N] = epi(A[M,K] W[N,K]^T + bias[N]) (+ residual[M,N]); K % 32 == 0.
 // ---- msa_transformer.hip ------------------------------------------------------------------
