@@ -310,6 +310,21 @@ int pgmi_tr_sequence_loglik_shared(pgmi_model* m, const int32_t* tokens, const i
                                    const float* log_prior, int P, const int32_t* prior_a0, const int32_t* prior_row0,
                                    const int32_t* prior_n, const int32_t* prior_flip, float alpha, float* out,
                                    float* token_logprobs, int64_t* rows_forwarded);
+/* pgmi_tr_sequence_loglik_eve / pgmi_tr_sequence_loglik_shared_eve: the two calls above with TranceptEVE's second prior
+ *   (trancepteve/model_pytorch.py:1113-1133).  eve_log_prior f32 [P,V] (host, nullable; needs log_prior) is indexed and flipped exactly
+ *   like log_prior (prior_row0, prior_n, prior_flip).  For a fused position with network log-probability lp, retrieval row m and EVE
+ *   row e at the target token, in fp32 and in this order: (1-beta)*((1-alpha)*lp + alpha*m) + beta*e; where e is -inf (a column outside
+ *   EVE's focus columns) and eve_fallback != 0: (1-alpha)*lp + alpha*m; with eve_fallback == 0 the -inf goes through the arithmetic as
+ *   in the reference.  eve_log_prior == NULL: the two calls above, bit for bit (they are these calls with NULL); the _shared_eve
+ *   output has the bits of the _eve output. */
+int pgmi_tr_sequence_loglik_eve(pgmi_model* m, const int32_t* tokens, const int32_t* lens, int B, int T,
+                                const float* log_prior, int P, const int32_t* prior_a0, const int32_t* prior_row0,
+                                const int32_t* prior_n, const int32_t* prior_flip, float alpha, const float* eve_log_prior, float beta,
+                                int eve_fallback, float* out);
+int pgmi_tr_sequence_loglik_shared_eve(pgmi_model* m, const int32_t* tokens, const int32_t* ref, int B, int T,
+                                       const float* log_prior, int P, const int32_t* prior_a0, const int32_t* prior_row0,
+                                       const int32_t* prior_n, const int32_t* prior_flip, float alpha, const float* eve_log_prior,
+                                       float beta, int eve_fallback, float* out, float* token_logprobs, int64_t* rows_forwarded);
 
 /* Tuning utility: times `iters` launches of the production GEMM (device-resident random operands,
  * HIP events) for one shape; variant selects the launch parameters (negative or below 1000 = library default;
@@ -496,6 +511,19 @@ int pgmi_eve_elbo(pgmi_eve* m, const uint8_t* residues, int M, int64_t row_base,
 int pgmi_eve_noise_fill(pgmi_eve* m, uint64_t seed, int sample, int64_t row_base, int M, pgmi_eve_noise* out);
 int pgmi_eve_evol_indices(pgmi_eve* m, const uint8_t* residues, int M, int num_samples, uint64_t seed, double* mean_elbo,
                           double* std_elbo);
+/* pgmi_eve_log_prior: TranceptEVE's EVE log-prior of ONE row (get_EVE_log_prior_single, trancepteve/model_pytorch.py:975-1001; decoder
+ *   trancepteve/EVE/VAE_decoder.py): the mean over num_samples Monte-Carlo samples of log_softmax(decoder(z)) over the 20 letters of
+ *   every position, each sample with freshly drawn decoder weights and latent.  The reference's model is in eval(): cfg.dropout_p is
+ *   ignored here and the keep masks of an injected struct are not read.  residues uint8 [L].  Sample j draws with the counters of
+ *   pgmi_eve_elbo(row_base = 0, sample = j): pgmi_eve_noise_fill(seed, j, 0, 1, ..) hands out its noise, and num_samples such structs
+ *   as `injected` (seed is then not read) give the generator path's bits.  The final layer is fused with its sampler (the sampled
+ *   [20 L][H] matrix never exists in memory) and a launch serves several samples from one read of the means and standard deviations.
+ *   Per (position, letter): fp64 sum and sum of squares of (logp - the first sample's logp), added in sample order on the device;
+ *   mean_logp, std_logp (nullable): f64 [L][20], std with the n - 1 denominator.  Limits: last hidden size >= 20, conv_depth <= 612.
+ * pgmi_set_option("eve_prior_batch", n): samples per batch of that call (0: default; a batch runs in launches of at most 4 samples).
+ *   Bit-neutral: no sum's order depends on it. */
+int pgmi_eve_log_prior(pgmi_eve* m, const uint8_t* residues, int num_samples, uint64_t seed, const pgmi_eve_noise* injected,
+                       double* mean_logp, double* std_logp);
 
 /* ---- MSA Transformer (arch PGMI_ARCH_MSA; vocab 33, head_dim 64, precision f16x3) --------------------
  * Replaces MSATransformer.forward (proteingym/baselines/esm/esm/model/msa_transformer.py:146-205; tied

@@ -85,6 +85,11 @@ SIGNATURES = [
                                           _i32p, _i32p, _i32p, _i32p, C.c_float, _f32p]),
     ("pgmi_tr_sequence_loglik_shared", C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, C.c_int, _f32p, C.c_int,
                                                  _i32p, _i32p, _i32p, _i32p, C.c_float, _f32p, _f32p, _i64p]),
+    ("pgmi_tr_sequence_loglik_eve", C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, C.c_int, _f32p, C.c_int,
+                                              _i32p, _i32p, _i32p, _i32p, C.c_float, _f32p, C.c_float, C.c_int, _f32p]),
+    ("pgmi_tr_sequence_loglik_shared_eve", C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, C.c_int, _f32p, C.c_int,
+                                                     _i32p, _i32p, _i32p, _i32p, C.c_float, _f32p, C.c_float, C.c_int, _f32p, _f32p,
+                                                     _i64p]),
     ("pgmi_pg2_model_create", C.c_int, [C.POINTER(Config), C.c_int, _f32p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     ("pgmi_pg2_token_logprobs", C.c_int, [C.c_void_p, _i32p, C.c_int, C.c_int, _f32p]),
     ("pgmi_pg2_sequence_loglik", C.c_int, [C.c_void_p, _i32p, C.c_int, C.c_int, _f32p, _i32p]),
@@ -103,6 +108,7 @@ SIGNATURES = [
     ("pgmi_eve_elbo", C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int64, C.c_uint64, C.c_int, C.c_void_p, _f32p, _f32p, _f32p]),
     ("pgmi_eve_noise_fill", C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int64, C.c_int, C.c_void_p]),
     ("pgmi_eve_evol_indices", C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, C.c_uint64, _f64p, _f64p]),
+    ("pgmi_eve_log_prior", C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_uint64, C.c_void_p, _f64p, _f64p]),
     ("pgmi_bench_gemm", C.c_int, [C.c_int] * 9 + [_f64p]),
     ("pgmi_bench_gemm_ab", C.c_int, [C.c_int] * 7 + [_i32p, C.c_int, C.c_int, C.c_int, _f64p]),
     ("pgmi_op_attention", C.c_int, [C.c_int, C.c_int, _f32p, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),

@@ -7,11 +7,12 @@
 
 namespace pgmi {
 
-static long long g_eve_max_rows = 0, g_eve_fixed_sample = -1;
+static long long g_eve_max_rows = 0, g_eve_fixed_sample = -1, g_eve_prior_batch = 0;
 
 int eve_set_option(const char* name, long long value) {
     if (!strcmp(name, "eve_max_rows")) { g_eve_max_rows = value > 0 ? value : 0; return PGMI_OK; }
     if (!strcmp(name, "eve_fixed_sample")) { g_eve_fixed_sample = value; return PGMI_OK; }
+    if (!strcmp(name, "eve_prior_batch")) { g_eve_prior_batch = value > 0 ? value : 0; return PGMI_OK; }
     return PGMI_EINVAL;
 }
 
@@ -55,6 +56,10 @@ struct pgmi_eve {
     float* logits = nullptr;  size_t logits_cap = 0;
     float* out3 = nullptr;    size_t out3_cap = 0;   // elbo | bce | kld, [3][M]
     double* acc = nullptr;    size_t acc_cap = 0;    // [M][3]
+    // pgmi_eve_log_prior: hidden vectors [2][EVE_PRIOR_S][wmax], the final kernel's partial sums, accumulators [20 L][3]
+    float* pr_h = nullptr;       size_t pr_h_cap = 0;
+    float* pr_partial = nullptr; size_t pr_partial_cap = 0;
+    double* pr_acc = nullptr;    size_t pr_acc_cap = 0;
 };
 
 namespace pgmi {
@@ -331,9 +336,9 @@ static int inj_upload(std::vector<void*>& pool, const T** dst, const T* host, si
     return rc;
 }
 
-static int eve_upload_noise(pgmi_eve* m, const pgmi_eve_noise* nz, int M, std::vector<void*>& pool, EveInj* inj) {
+static int eve_upload_noise(pgmi_eve* m, const pgmi_eve_noise* nz, int M, std::vector<void*>& pool, EveInj* inj, bool keeps = true) {
     const pgmi_eve_config& c = m->cfg;
-    const bool drop = m->keep24 != 0;
+    const bool drop = keeps && m->keep24 != 0;
     int rc = inj_upload(pool, &inj->z_eps, (const float*)nz->z_eps, (size_t)M * m->z, "z_eps");
     if (!rc && drop) rc = inj_upload(pool, &inj->keep[0], (const uint8_t*)nz->keep[0], (size_t)M * m->z, "keep[0]");
     for (int i = 0; i < c.n_dec && !rc; ++i) {
@@ -504,3 +509,98 @@ int pgmi_eve_evol_indices(pgmi_eve* m, const uint8_t* residues, int M, int num_s
 }
 
 }  // extern "C"
+
+namespace pgmi {
+
+// samples [j0, j0 + S) of a log-prior call: latent -> sampled hidden layers -> fused final layer -> log-softmax into the accumulators
+static int eve_prior_group(pgmi_eve* m, uint64_t seed, int j0, int S, const EveInj* inj /* S structs or nullptr */) {
+    pgmi_model* pm = &m->pm;
+    hipStream_t st = pm->stream;
+    const pgmi_eve_config& c = m->cfg;
+    auto ptrs = [&](auto field) {
+        EvePriorPtrs p;
+        for (int s = 0; s < S && inj; ++s) p.p[s] = field(inj[s]);
+        return p;
+    };
+    float *cur = m->pr_h, *nxt = m->pr_h + (size_t)EVE_PRIOR_S * m->wmax;
+    {
+        double fl = 0;
+        for (const EveBayes& l : m->dec) fl += 2.0 * S * l.N * l.K;
+        ProfScope p(pm, PGMI_K_GEMM_FC1, fl, 0);
+        launch_eve_prior_latent(m->mulv, m->z, m->wmax, seed, (uint32_t)j0, ptrs([](const EveInj& i) { return i.z_eps; }), S, cur, st);
+        for (size_t i = 0; i < m->dec.size(); ++i) {
+            const EveBayes& l = m->dec[i];
+            launch_eve_prior_hidden(l.w_mean, l.w_sd, l.b_mean, l.b_sd, l.N, l.K, seed, (uint32_t)j0, PGMI_EVE_T_W + (int)i, PGMI_EVE_T_B + (int)i,
+                                    ptrs([i](const EveInj& x) { return x.w_eps[i]; }), ptrs([i](const EveInj& x) { return x.b_eps[i]; }), S, cur,
+                                    m->wmax, i + 1 == m->dec.size() ? c.dec_last_act : c.dec_first_act, nxt, m->wmax, st);
+            std::swap(cur, nxt);
+        }
+    }
+    {
+        ProfScope p(pm, PGMI_K_GEMM_FC2, 2.0 * S * m->N * m->H, (double)m->C * m->L * m->H * 8);
+        launch_eve_prior_final(m->wout_mean, m->wout_sd, m->conv_mean, m->conv_sd, m->sp_mean, m->sp_sd, m->L, m->H, m->C, m->Ht,
+                               c.conv_depth != 0, seed, (uint32_t)j0, ptrs([](const EveInj& i) { return i.wout; }),
+                               ptrs([](const EveInj& i) { return i.conv; }), ptrs([](const EveInj& i) { return i.sparsity; }), S, cur, m->wmax,
+                               m->pr_partial, st);
+    }
+    {
+        ProfScope p(pm, PGMI_K_SCORE, 0, 0);
+        launch_eve_prior_finish(m->pr_partial, S, m->bout_mean, m->bout_sd, c.temperature ? m->t_mean : nullptr, m->t_sd, seed, (uint32_t)j0,
+                                ptrs([](const EveInj& i) { return i.bout; }), ptrs([](const EveInj& i) { return i.temp; }), m->L, m->H, j0,
+                                m->pr_acc, st);
+    }
+    PGMI_HIP(hipGetLastError());
+    return PGMI_OK;
+}
+
+}  // namespace pgmi
+
+extern "C" int pgmi_eve_log_prior(pgmi_eve* m, const uint8_t* residues, int num_samples, uint64_t seed, const pgmi_eve_noise* injected,
+                                  double* mean_logp, double* std_logp) {
+    using namespace pgmi;
+    int rc = eve_check_call(m, residues, 1);
+    if (rc) return rc;
+    if (num_samples <= 0 || !mean_logp) { set_error("bad argument"); return PGMI_EINVAL; }
+    if (m->H < 20) { set_error("EVE log-prior: the last hidden size must be at least 20, got %d", m->H); return PGMI_EINVAL; }
+    const int smax = eve_prior_max_samples(m->C, m->cfg.conv_depth != 0);
+    if (smax < 1) { set_error("EVE log-prior: conv_depth %d does not fit the final kernel's LDS", m->C); return PGMI_EINVAL; }
+    pgmi_model* pm = &m->pm;
+    hipStream_t st = pm->stream;
+    rc = eve_encode(m, residues, 1);
+    if (!rc) rc = ensure_cap(pm, &m->pr_h, &m->pr_h_cap, (size_t)2 * EVE_PRIOR_S * m->wmax);
+    if (!rc) rc = ensure_cap(pm, &m->pr_partial, &m->pr_partial_cap, (size_t)EVE_PRIOR_S * eve_prior_blocks(m->L, m->H) * eve_prior_kmax(m->H));
+    if (!rc) rc = ensure_cap(pm, &m->pr_acc, &m->pr_acc_cap, (size_t)3 * m->N);
+    if (rc) return rc;
+    // "eve_prior_batch" samples at a time (default: what one launch serves), each batch in launches of at most smax samples
+    const int batch = g_eve_prior_batch > 0 ? (int)std::min<long long>(g_eve_prior_batch, num_samples) : smax;
+    int groups = 0;
+    for (int j0 = 0; j0 < num_samples && !rc; j0 += batch) {
+        const int j1 = std::min(num_samples, j0 + batch);
+        for (int k0 = j0; k0 < j1 && !rc; k0 += smax) {
+            const int S = std::min(smax, j1 - k0);
+            if (injected) {
+                std::vector<void*> pool;
+                EveInj inj[EVE_PRIOR_S];
+                for (int s = 0; s < S && !rc; ++s) rc = eve_upload_noise(m, injected + k0 + s, 1, pool, &inj[s], false);
+                if (!rc) rc = eve_prior_group(m, seed, k0, S, inj);
+                const hipError_t e = hipStreamSynchronize(st);
+                for (void* p : pool) hipFree(p);
+                if (!rc && e != hipSuccess) { set_error("EVE log-prior failed: %s", hipGetErrorString(e)); rc = PGMI_EHIP; }
+            } else {
+                rc = eve_prior_group(m, seed, k0, S, nullptr);
+            }
+            if (!rc && pm->prof && (++groups & 63) == 63) rc = prof_drain(pm);
+        }
+    }
+    if (rc) { hipStreamSynchronize(st); return rc; }
+    std::vector<double> a((size_t)3 * m->N);
+    PGMI_HIP(hipMemcpyAsync(a.data(), m->pr_acc, a.size() * 8, hipMemcpyDeviceToHost, st));
+    PGMI_HIP(hipStreamSynchronize(st));
+    const double n = num_samples;
+    for (int i = 0; i < m->N; ++i) {
+        const double shift = a[3 * (size_t)i], s = a[3 * (size_t)i + 1], ss = a[3 * (size_t)i + 2];
+        mean_logp[i] = shift + s / n;
+        if (std_logp) std_logp[i] = num_samples > 1 ? sqrt(std::max(0.0, (ss - s * s / n) / (n - 1))) : 0.0;
+    }
+    return PGMI_OK;
+}

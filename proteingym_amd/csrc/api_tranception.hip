@@ -89,13 +89,27 @@ int create_tranception(pgmi_model* m, const pgmi_config* cfg, const float* w, in
     return c.finish();
 }
 
-// Device copy of the retrieval log-prior [P, V] (none: no retrieval), grown as needed.
-static int upload_prior(pgmi_model* m, const float* log_prior, int P) {
+// TranceptEVE's second prior: host table [P, V] indexed like the retrieval prior, its weight and the fallback switch; dev is set by
+// upload_prior
+struct TrEve {
+    const float* host = nullptr;
+    float beta = 0.0f;
+    int fallback = 0;
+    const float* dev = nullptr;
+};
+
+// Device copy of the retrieval log-prior [P, V] (none: no retrieval), grown as needed; the EVE table, when given, sits behind it.
+static int upload_prior(pgmi_model* m, const float* log_prior, int P, TrEve* eve = nullptr) {
     if (!log_prior) return PGMI_OK;
     const size_t n = (size_t)P * m->cfg.vocab;
-    int rc = ensure_cap(m, &m->tr_prior, &m->tr_prior_cap, n);
+    const bool two = eve && eve->host;
+    int rc = ensure_cap(m, &m->tr_prior, &m->tr_prior_cap, two ? 2 * n : n);
     if (rc) return rc;
     PGMI_HIP(hipMemcpyAsync(m->tr_prior, log_prior, n * 4, hipMemcpyHostToDevice, m->stream));
+    if (two) {
+        PGMI_HIP(hipMemcpyAsync(m->tr_prior + n, eve->host, n * 4, hipMemcpyHostToDevice, m->stream));
+        eve->dev = m->tr_prior + n;
+    }
     return PGMI_OK;
 }
 
@@ -144,7 +158,7 @@ struct TrChunk {
 // Runs one chunk: tokens (packed), index arrays and the retrieval arguments are uploaded, the forward leaves the suffix rows'
 // log-probabilities in m->lp [rows, V] and the per-sequence reductions in m->denom [sequences].
 int run_tranception_shared(pgmi_model* m, TrChunk& ck, int T, const float* prior_dev, const int32_t* a0, const int32_t* r0,
-                           const int32_t* pn, const int32_t* fl, float alpha) {
+                           const int32_t* pn, const int32_t* fl, float alpha, const TrEve& eve) {
     const int M = ck.rows, V = m->cfg.vocab, S = (int)ck.seq.size();
     hipStream_t s = m->stream;
     // attention blocks with the most key tiles first: the launch's tail is made of the short ones
@@ -194,7 +208,7 @@ int run_tranception_shared(pgmi_model* m, TrChunk& ck, int T, const float* prior
     if (rc) return rc;
     { ProfScope ps(m, PGMI_K_SCORE, 0, (double)S * T * 8);
       launch_seq_loglik_ragged(m->lp, m->tokens, rg.seq_off, rg.seq_p, rg.seq_root, S, T, V, prior_dev, d_pa, d_pr, d_pc, d_pf, alpha,
-                               m->denom, s); }
+                               prior_dev ? eve.dev : nullptr, eve.beta, eve.fallback, m->denom, s); }
     PGMI_HIP(hipGetLastError());
     return PGMI_OK;
 }
@@ -227,7 +241,17 @@ int pgmi_tr_token_logprobs(pgmi_model* m, const int32_t* tokens, int B, int T, f
 int pgmi_tr_sequence_loglik(pgmi_model* m, const int32_t* tokens, const int32_t* lens, int B, int T,
                             const float* log_prior, int P, const int32_t* prior_a0, const int32_t* prior_row0,
                             const int32_t* prior_n, const int32_t* prior_flip, float alpha, float* out) {
+    return pgmi_tr_sequence_loglik_eve(m, tokens, lens, B, T, log_prior, P, prior_a0, prior_row0, prior_n, prior_flip, alpha, nullptr, 0.0f,
+                                       0, out);
+}
+
+int pgmi_tr_sequence_loglik_eve(pgmi_model* m, const int32_t* tokens, const int32_t* lens, int B, int T,
+                                const float* log_prior, int P, const int32_t* prior_a0, const int32_t* prior_row0,
+                                const int32_t* prior_n, const int32_t* prior_flip, float alpha, const float* eve_log_prior, float beta,
+                                int eve_fallback, float* out) {
     if (!m || !tokens || !lens || !out || B <= 0 || T <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
+    if (eve_log_prior && !log_prior) { set_error("the EVE prior is fused on the retrieval prior's rows: log_prior is NULL"); return PGMI_EINVAL; }
+    TrEve eve{eve_log_prior, beta, eve_fallback, nullptr};
     if (m->cfg.arch != PGMI_ARCH_TRANCEPTION) { set_error("not a Tranception model"); return PGMI_EINVAL; }
     if (log_prior && (!prior_a0 || !prior_row0 || !prior_n || !prior_flip || P <= 0)) { set_error("incomplete retrieval arguments"); return PGMI_EINVAL; }
     const int V = m->cfg.vocab;
@@ -246,7 +270,7 @@ int pgmi_tr_sequence_loglik(pgmi_model* m, const int32_t* tokens, const int32_t*
     if (rc) return rc;
     PGMI_HIP(hipSetDevice(m->device));
     hipStream_t s = m->stream;
-    rc = upload_prior(m, log_prior, P);
+    rc = upload_prior(m, log_prior, P, &eve);
     if (rc) return rc;
     rc = for_each_chunk(m, B, T, [&](int b0, int bc) {
         PGMI_HIP(hipMemcpyAsync(m->tokens, tokens + (size_t)b0 * T, (size_t)bc * T * 4, hipMemcpyHostToDevice, s));
@@ -264,7 +288,7 @@ int pgmi_tr_sequence_loglik(pgmi_model* m, const int32_t* tokens, const int32_t*
         if (rc) return rc;
         { ProfScope p(m, PGMI_K_SCORE, 0, (double)bc * T * 8);
           launch_seq_loglik(m->lp, m->tokens, m->kv_len, bc, T, V, log_prior ? m->tr_prior : nullptr, da0, dr0, dn, dfl, alpha,
-                            m->denom, s); }
+                            eve.dev, eve.beta, eve.fallback, m->denom, s); }
         PGMI_HIP(hipMemcpyAsync(out + b0, m->denom, (size_t)bc * 4, hipMemcpyDeviceToHost, s));
         return PGMI_OK;
     });
@@ -275,7 +299,17 @@ int pgmi_tr_sequence_loglik_shared(pgmi_model* m, const int32_t* tokens, const i
                                    const float* log_prior, int P, const int32_t* prior_a0, const int32_t* prior_row0,
                                    const int32_t* prior_n, const int32_t* prior_flip, float alpha, float* out, float* token_logprobs,
                                    int64_t* rows_forwarded) {
+    return pgmi_tr_sequence_loglik_shared_eve(m, tokens, ref, B, T, log_prior, P, prior_a0, prior_row0, prior_n, prior_flip, alpha, nullptr,
+                                              0.0f, 0, out, token_logprobs, rows_forwarded);
+}
+
+int pgmi_tr_sequence_loglik_shared_eve(pgmi_model* m, const int32_t* tokens, const int32_t* ref, int B, int T,
+                                       const float* log_prior, int P, const int32_t* prior_a0, const int32_t* prior_row0,
+                                       const int32_t* prior_n, const int32_t* prior_flip, float alpha, const float* eve_log_prior,
+                                       float beta, int eve_fallback, float* out, float* token_logprobs, int64_t* rows_forwarded) {
     if (!m || !tokens || !ref || !out || B <= 0 || T <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
+    if (eve_log_prior && !log_prior) { set_error("the EVE prior is fused on the retrieval prior's rows: log_prior is NULL"); return PGMI_EINVAL; }
+    TrEve eve{eve_log_prior, beta, eve_fallback, nullptr};
     if (m->cfg.arch != PGMI_ARCH_TRANCEPTION) { set_error("not a Tranception model"); return PGMI_EINVAL; }
     if (log_prior && (!prior_a0 || !prior_row0 || !prior_n || !prior_flip || P <= 0)) { set_error("incomplete retrieval arguments"); return PGMI_EINVAL; }
     if (check_ctx(m, T)) return PGMI_EINVAL;
@@ -294,7 +328,7 @@ int pgmi_tr_sequence_loglik_shared(pgmi_model* m, const int32_t* tokens, const i
     }
     PGMI_HIP(hipSetDevice(m->device));
     hipStream_t s = m->stream;
-    rc = upload_prior(m, log_prior, P);
+    rc = upload_prior(m, log_prior, P, &eve);
     if (rc) return rc;
     // first own token of every sequence: its first difference from its root (a copy of the root: the last token)
     std::vector<int> a0(B, 0);
@@ -314,7 +348,7 @@ int pgmi_tr_sequence_loglik_shared(pgmi_model* m, const int32_t* tokens, const i
     TrChunk ck;
     auto flush = [&]() -> int {
         if (ck.seq.empty()) return PGMI_OK;
-        int rc = run_tranception_shared(m, ck, T, log_prior ? m->tr_prior : nullptr, prior_a0, prior_row0, prior_n, prior_flip, alpha);
+        int rc = run_tranception_shared(m, ck, T, log_prior ? m->tr_prior : nullptr, prior_a0, prior_row0, prior_n, prior_flip, alpha, eve);
         if (rc) return rc;
         const int S = (int)ck.seq.size();
         std::vector<float> res(S);

@@ -82,13 +82,16 @@ void launch_row_index(const int32_t* mask_rel, int B, int T, int32_t* out, hipSt
 void launch_fill_f32(float* p, int64_t n, float v, hipStream_t s);
 // Tranception: per-sequence sum over t < len-1 of log p(tok[t+1] | tok[<=t]) from lp [B*T,V]
 // (scoring_utils.py:118-128), with the retrieval fusion (model_pytorch.py:806-830) on rows
-// [a0, a0+n) when prior != nullptr: value = (1-alpha)*lp + alpha*prior[row0 +/- i].
+// [a0, a0+n) when prior != nullptr: value = (1-alpha)*lp + alpha*prior[row0 +/- i]; eve != nullptr (TranceptEVE,
+// trancepteve/model_pytorch.py:1113-1133; same rows as prior): value = (1-beta)*value + beta*eve[row], except that an eve entry of
+// -inf leaves the value alone when eve_fallback != 0.
 void launch_seq_loglik(const float* lp, const int32_t* tokens, const int32_t* lens, int B, int T, int V,
                        const float* prior, const int32_t* a0, const int32_t* row0, const int32_t* n,
-                       const int32_t* flip, float alpha, float* out, hipStream_t s);
+                       const int32_t* flip, float alpha, const float* eve, float beta, int eve_fallback, float* out, hipStream_t s);
 void launch_seq_loglik_ragged(const float* lp, const int32_t* tokens, const int32_t* seq_off, const int32_t* seq_p,
                               const int32_t* seq_root, int B, int T, int V, const float* prior, const int32_t* a0,
-                              const int32_t* row0, const int32_t* n, const int32_t* flip, float alpha, float* out, hipStream_t s);
+                              const int32_t* row0, const int32_t* n, const int32_t* flip, float alpha, const float* eve, float beta,
+                              int eve_fallback, float* out, hipStream_t s);
 // ProGen2: out[b] = sum over t < n_kept[b] of lp[b*T + t, col[b*T + t]] (lp [B*T,V], one wave per sequence, fixed lane order)
 void launch_pg2_seq_loglik(const float* lp, const int32_t* col, const int32_t* n_kept, int B, int T, int V, float* out, hipStream_t s);
 // causal decoder (api_gpt.hip): x[row] = E[tokens[row]] + P[row % T]
@@ -139,7 +142,25 @@ void launch_eve_elbo(const float* logits, const uint8_t* res, const float* mulv,
                      int64_t loc0, float* elbo, float* bce, float* kld, double* acc, int first, hipStream_t s);
 void launch_eve_fill_normal(uint64_t seed, uint32_t sample, int tensor, uint64_t e0, int64_t n, float* out, hipStream_t s);
 void launch_eve_fill_keep(uint64_t seed, uint32_t sample, int tensor, uint64_t e0, int64_t n, uint32_t keep24, uint8_t* out, hipStream_t s);
-int eve_set_option(const char* name, long long value);   // api_eve.hip: "eve_max_rows", "eve_fixed_sample"
+// the log-prior of one row (pgmi_eve_log_prior): up to EVE_PRIOR_S samples per launch; p[s] = sample s's injected tensor (nullptr: generator)
+constexpr int EVE_PRIOR_S = 4;
+struct EvePriorPtrs { const float* p[EVE_PRIOR_S] = {nullptr, nullptr, nullptr, nullptr}; };
+void launch_eve_prior_latent(const float* mulv, int z, int ld, uint64_t seed, uint32_t sample, const EvePriorPtrs& inj, int S, float* h,
+                             hipStream_t s);
+void launch_eve_prior_hidden(const float* w_mean, const float* w_sd, const float* b_mean, const float* b_sd, int N, int K, uint64_t seed,
+                             uint32_t sample, int tw, int tb, const EvePriorPtrs& inj_w, const EvePriorPtrs& inj_b, int S, const float* x,
+                             int ldx, int act, float* y, int ldy, hipStream_t s);
+int eve_prior_blocks(int L, int H);                      // blocks of the final kernel = rows of its partial sums per sample
+int eve_prior_kmax(int H);                               // logits a block can touch = row pitch of the partial sums
+int eve_prior_max_samples(int C, bool conv);
+void launch_eve_prior_final(const float* w_mean, const float* w_sd, const float* c_mean, const float* c_sd, const float* s_mean,
+                            const float* s_sd, int L, int H, int C, int Ht, bool conv, uint64_t seed, uint32_t sample,
+                            const EvePriorPtrs& inj_w, const EvePriorPtrs& inj_c, const EvePriorPtrs& inj_s, int S, const float* h, int ldh,
+                            float* partial, hipStream_t s);
+void launch_eve_prior_finish(const float* partial, int S, const float* b_mean, const float* b_sd, const float* t_mean, const float* t_sd,
+                             uint64_t seed, uint32_t sample, const EvePriorPtrs& inj_b, const EvePriorPtrs& inj_t, int L, int H, int sample0,
+                             double* acc, hipStream_t s);
+int eve_set_option(const char* name, long long value);   // api_eve.hip: "eve_max_rows", "eve_fixed_sample", "eve_prior_batch"
 
 // ---- gemm_f32.hip ------------------------------------------------------------------------
 // C[M,N] = epi(A[M,K] W[N,K]^T + bias[N]) (+ residual[M,N]); K % 32 == 0.

@@ -367,11 +367,19 @@ void launch_vocab_logsoftmax(const float* h, const float* E, const float* bias, 
 }
 
 // ---- Tranception sequence log-likelihood (one wave per sequence) ------------------------------
+// TranceptEVE's second prior (trancepteve/model_pytorch.py:1113-1133): two = (1 - alpha) lp + alpha msa is fused with the EVE row e as
+// (1 - beta) two + beta e; a column EVE does not model holds -inf, which either hands the position back to `two` (eve_fallback) or
+// goes through the arithmetic as in the reference.
+__device__ __forceinline__ float fuse_eve(float two, float e, float beta, int eve_fallback) {
+    if (eve_fallback && e == -INFINITY) return two;
+    return (1.0f - beta) * two + beta * e;
+}
 __global__ __launch_bounds__(256) void seq_loglik_kernel(const float* __restrict__ lp, const int32_t* __restrict__ tokens,
                                                          const int32_t* __restrict__ lens, int B, int T, int V,
                                                          const float* __restrict__ prior, const int32_t* __restrict__ a0,
                                                          const int32_t* __restrict__ row0, const int32_t* __restrict__ n,
                                                          const int32_t* __restrict__ flip, float alpha,
+                                                         const float* __restrict__ eve, float beta, int eve_fallback,
                                                          float* __restrict__ out) {
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -385,6 +393,7 @@ __global__ __launch_bounds__(256) void seq_loglik_kernel(const float* __restrict
             const int i = t - a0[b];
             const int row = flip[b] ? row0[b] + (n[b] - 1 - i) : row0[b] + i;
             v = (1.0f - alpha) * v + alpha * prior[(size_t)row * V + tgt];
+            if (eve) v = fuse_eve(v, eve[(size_t)row * V + tgt], beta, eve_fallback);
         }
         acc += v;
     }
@@ -401,6 +410,7 @@ __global__ __launch_bounds__(256) void seq_loglik_ragged_kernel(const float* __r
                                                                 const float* __restrict__ prior, const int32_t* __restrict__ a0,
                                                                 const int32_t* __restrict__ row0, const int32_t* __restrict__ n,
                                                                 const int32_t* __restrict__ flip, float alpha,
+                                                                const float* __restrict__ eve, float beta, int eve_fallback,
                                                                 float* __restrict__ out) {
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -414,6 +424,7 @@ __global__ __launch_bounds__(256) void seq_loglik_ragged_kernel(const float* __r
             const int i = t - a0[b];
             const int row = flip[b] ? row0[b] + (n[b] - 1 - i) : row0[b] + i;
             v = (1.0f - alpha) * v + alpha * prior[(size_t)row * V + tgt];
+            if (eve) v = fuse_eve(v, eve[(size_t)row * V + tgt], beta, eve_fallback);
         }
         acc += v;
     }
@@ -422,15 +433,16 @@ __global__ __launch_bounds__(256) void seq_loglik_ragged_kernel(const float* __r
 }
 void launch_seq_loglik_ragged(const float* lp, const int32_t* tokens, const int32_t* seq_off, const int32_t* seq_p,
                               const int32_t* seq_root, int B, int T, int V, const float* prior, const int32_t* a0,
-                              const int32_t* row0, const int32_t* n, const int32_t* flip, float alpha, float* out, hipStream_t s) {
+                              const int32_t* row0, const int32_t* n, const int32_t* flip, float alpha, const float* eve, float beta,
+                              int eve_fallback, float* out, hipStream_t s) {
     hipLaunchKernelGGL(seq_loglik_ragged_kernel, dim3((B + 3) / 4), dim3(256), 0, s, lp, tokens, seq_off, seq_p, seq_root, B, T, V,
-                       prior, a0, row0, n, flip, alpha, out);
+                       prior, a0, row0, n, flip, alpha, eve, beta, eve_fallback, out);
 }
 void launch_seq_loglik(const float* lp, const int32_t* tokens, const int32_t* lens, int B, int T, int V,
                        const float* prior, const int32_t* a0, const int32_t* row0, const int32_t* n,
-                       const int32_t* flip, float alpha, float* out, hipStream_t s) {
+                       const int32_t* flip, float alpha, const float* eve, float beta, int eve_fallback, float* out, hipStream_t s) {
     hipLaunchKernelGGL(seq_loglik_kernel, dim3((B + 3) / 4), dim3(256), 0, s, lp, tokens, lens, B, T, V, prior, a0, row0, n,
-                       flip, alpha, out);
+                       flip, alpha, eve, beta, eve_fallback, out);
 }
 
 // ---- ProGen2 sequence log-likelihood (one wave per sequence) ---------------------------------

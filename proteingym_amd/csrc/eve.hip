@@ -10,6 +10,10 @@
 //                            reference's flat views ([C L, H] read as [L H, C]; [L H, 20] read as [H, L, 20] and as [20 L, H])
 //   eve_elbo_kernel          per row: 20-way log-sum-exp per position, BCE-with-logits of the log-probabilities, KLD, fp64 sums
 //   eve_fill_*_kernel        the generator's noise as tensors (pgmi_eve_noise_fill)
+//   eve_prior_*_kernel       the log-prior of ONE row over many samples (pgmi_eve_log_prior): latent, sampled hidden layers as
+//                            matrix-vector products, the final layer fused with its sampler (W_final never exists in memory), and the
+//                            log-softmax with its fp64 accumulators; up to EVE_PRIOR_S samples per launch share one read of the means
+//                            and standard deviations
 // Noise: counter-based Philox4x32-10.  key = seed; counter = (element / 4 low, element / 4 high, sample j, tensor id); the four
 // outputs of a counter serve elements 4 b .. 4 b + 3 of the tensor: normals by Box-Muller in fp32 (outputs 0,1 -> elements 0,1;
 // outputs 2,3 -> elements 2,3), dropout keeps by output < (1 - p) 2^24 on the top 24 bits.  Per-row tensors are indexed by the row's
@@ -310,6 +314,240 @@ __global__ __launch_bounds__(256) void eve_elbo_kernel(const float* __restrict__
     }
 }
 
+// ---- log-prior of one row (pgmi_eve_log_prior) ------------------------------------------------------------------------------------
+// A launch serves S <= EVE_PRIOR_S consecutive samples: sample s of the launch draws with the counter's sample word g.sample + s (the
+// words pgmi_eve_elbo(row_base = 0, sample) uses), or reads the injected tensor inj.p[s].  No dropout: the reference's model is in eval().
+// Every sum below has one order, set by the shapes alone: a sample's bits do not depend on S or on its place in the launch.
+static __device__ __forceinline__ EveRng eve_rng_plus(EveRng g, int s) { g.sample += (uint32_t)s; return g; }
+
+// h[s][c] = exp(lv / 2) eps + mu for c < z (row 0 of mulv), 0 up to ld
+__global__ __launch_bounds__(256) void eve_prior_latent_kernel(const float* __restrict__ mulv, int z, int ld, EveRng g, EvePriorPtrs inj, int S,
+                                                               float* __restrict__ h) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= S * ld) return;
+    const int s = i / ld, c = i % ld;
+    float v = 0.0f;
+    if (c < z) {
+        const float eps = inj.p[s] ? inj.p[s][c] : eve_normal(eve_rng_plus(g, s), PGMI_EVE_T_Z, (uint64_t)c);
+        v = expf(0.5f * mulv[z + c]) * eps + mulv[c];
+    }
+    h[i] = v;
+}
+
+// y[s][n] = act(sum_k (sd eps + mean)[n][k] x[s][k] + (sd eps + mean)[n]): one wave per output n, grid (ceil(N / 4), S).  A lane owns
+// the Philox counters b_lo + lane, b_lo + lane + 64, ... of the row's elements [n K, (n + 1) K) (a counter's elements outside the row
+// belong to its neighbours) and adds its terms in that order; the 64 lane sums go through one xor butterfly.
+__global__ __launch_bounds__(256) void eve_prior_hidden_kernel(const float* __restrict__ w_mean, const float* __restrict__ w_sd,
+                                                               const float* __restrict__ b_mean, const float* __restrict__ b_sd, int N, int K,
+                                                               EveRng g, int tw, int tb, EvePriorPtrs inj_w, EvePriorPtrs inj_b,
+                                                               const float* __restrict__ x, int ldx, int act, float* __restrict__ y, int ldy) {
+    const int lane = threadIdx.x & 63, s = blockIdx.y;
+    const int n = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (n >= N) return;
+    const EveRng gs = eve_rng_plus(g, s);
+    const float* iw = inj_w.p[s];
+    const float* xs = x + (size_t)s * ldx;
+    const int64_t e0 = (int64_t)n * K, e1 = e0 + K;
+    float part = 0.0f;
+    for (int64_t b = (e0 >> 2) + lane; b <= ((e1 - 1) >> 2); b += 64) {
+        float eps[4];
+        if (!iw) eve_normal4(gs, tw, (uint64_t)b, eps);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int64_t e = b * 4 + i;
+            if (e >= e0 && e < e1) {
+                const float ev = iw ? iw[e] : eps[i];
+                part += (w_sd[e] * ev + w_mean[e]) * xs[e - e0];
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
+    if (lane == 0) {
+        const float ev = inj_b.p[s] ? inj_b.p[s][n] : eve_normal(gs, tb, (uint64_t)n);
+        y[(size_t)s * ldy + n] = eve_act(part + (b_sd[n] * ev + b_mean[n]), act);
+    }
+}
+
+// The final layer of one row, fused with its sampler.  Thread t < 256 of sample group gi (threads 256 gi + t; samples S gi .. S gi + S - 1
+// of the launch's ns) owns row r = 256 block + t < L H of W_out's flat [L H][C] view exactly as in eve_sample_final_kernel (same draws,
+// same contraction, same gate).  The groups of a block walk the same rows' means and standard deviations together, so one read from
+// memory serves the launch's samples; each sample has its own conv weight (LDS), gate and hidden vector h[s].  The 20 values are flat
+// elements f = 20 r + a of W_final read as [20 L][H]: they meet h[s][f % H] and belong to logit f / H.  With H >= 20 a thread's
+// elements touch at most two logits: s0 sums those of logit (20 r) / H, s1 those after the wrap.  Per block (256 rows = 5120 flat
+// elements) and logit n, one wave adds the threads' sums of [max(n H, F0), min((n + 1) H, F1)) -- lane i takes threads t_lo + i, + 64,
+// ... in order, then one xor butterfly -- into partial[s][block][n - n0], n0 = F0 / H: a logit whose terms straddle blocks is
+// finished, in block order, by eve_prior_finish_kernel.  No atomics.
+template <bool CONV, int S>
+__global__ __launch_bounds__(512) void eve_prior_final_kernel(const float* __restrict__ w_mean, const float* __restrict__ w_sd,
+                                                              const float* __restrict__ c_mean, const float* __restrict__ c_sd,
+                                                              const float* __restrict__ s_mean, const float* __restrict__ s_sd, int L, int H,
+                                                              int C, int Ht, EveRng g, EvePriorPtrs inj_w, EvePriorPtrs inj_c,
+                                                              EvePriorPtrs inj_s, int ns, const float* __restrict__ h, int ldh,
+                                                              float* __restrict__ partial, int kmax) {
+    constexpr int A = 20;
+    extern __shared__ float prior_lds[];
+    float* conv_s = prior_lds;                                  // [ns][C][20] (CONV)
+    float* red = prior_lds + (CONV ? ns * A * C : 0);           // [ns][256][2]
+    const int tid = threadIdx.x & 255, sb = (threadIdx.x >> 8) * S;
+    if (CONV) {
+        for (int i = threadIdx.x; i < ns * A * C; i += blockDim.x) {
+            const int s = i / (A * C), e = i % (A * C);
+            const float ev = inj_c.p[s] ? inj_c.p[s][e] : eve_normal(eve_rng_plus(g, s), PGMI_EVE_T_CONV, (uint64_t)e);
+            conv_s[i] = c_sd[e] * ev + c_mean[e];
+        }
+        __syncthreads();
+    }
+    const int64_t LH = (int64_t)L * H, rb = (int64_t)blockIdx.x * 256, r = rb + tid;
+    float s0[S], s1[S];
+#pragma unroll
+    for (int s = 0; s < S; ++s) s0[s] = s1[s] = 0.0f;
+    if (r < LH) {
+        float acc[S][A];
+#pragma unroll
+        for (int s = 0; s < S; ++s)
+#pragma unroll
+            for (int a = 0; a < A; ++a) acc[s][a] = 0.0f;
+        const int64_t base = r * C;
+        if (CONV) {
+            // the next counter's mean / sd are in flight while this one's draws are computed
+            f32x4 mu = *reinterpret_cast<const f32x4*>(w_mean + base), sg = *reinterpret_cast<const f32x4*>(w_sd + base);
+            for (int c = 0; c < C; c += 4) {
+                const int cn = c + 4 < C ? c + 4 : c;
+                const f32x4 mu_n = *reinterpret_cast<const f32x4*>(w_mean + base + cn);
+                const f32x4 sg_n = *reinterpret_cast<const f32x4*>(w_sd + base + cn);
+#pragma unroll
+                for (int s = 0; s < S; ++s) {
+                    if (sb + s >= ns) continue;
+                    const float* iw = inj_w.p[sb + s];
+                    float eps[4];
+                    if (iw) { const f32x4 t = *reinterpret_cast<const f32x4*>(iw + base + c); eps[0] = t[0]; eps[1] = t[1]; eps[2] = t[2]; eps[3] = t[3]; }
+                    else eve_normal4(eve_rng_plus(g, sb + s), PGMI_EVE_T_WOUT, (uint64_t)(base + c) >> 2, eps);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const float v = sg[i] * eps[i] + mu[i];
+                        const float* cv = conv_s + (sb + s) * A * C + (c + i) * A;
+#pragma unroll
+                        for (int a = 0; a < A; ++a) acc[s][a] += v * cv[a];
+                    }
+                }
+                mu = mu_n; sg = sg_n;
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < A; c += 4) {
+                const f32x4 mu = *reinterpret_cast<const f32x4*>(w_mean + base + c);
+                const f32x4 sg = *reinterpret_cast<const f32x4*>(w_sd + base + c);
+#pragma unroll
+                for (int s = 0; s < S; ++s) {
+                    if (sb + s >= ns) continue;
+                    const float* iw = inj_w.p[sb + s];
+                    float eps[4];
+                    if (iw) { const f32x4 t = *reinterpret_cast<const f32x4*>(iw + base + c); eps[0] = t[0]; eps[1] = t[1]; eps[2] = t[2]; eps[3] = t[3]; }
+                    else eve_normal4(eve_rng_plus(g, sb + s), PGMI_EVE_T_WOUT, (uint64_t)(base + c) >> 2, eps);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) acc[s][c + i] = sg[i] * eps[i] + mu[i];
+                }
+            }
+        }
+        if (Ht > 0) {
+            const int hq = (int)(r / L), l = (int)(r % L);
+            const int64_t e = (int64_t)(hq % Ht) * L + l;
+            const float sm = s_mean[e], ss = s_sd[e];
+#pragma unroll
+            for (int s = 0; s < S; ++s) {
+                if (sb + s >= ns) continue;
+                const float ev = inj_s.p[sb + s] ? inj_s.p[sb + s][e] : eve_normal(eve_rng_plus(g, sb + s), PGMI_EVE_T_SPARSITY, (uint64_t)e);
+                const float gate = 1.0f / (1.0f + expf(-(ss * ev + sm)));
+#pragma unroll
+                for (int a = 0; a < A; ++a) acc[s][a] *= gate;
+            }
+        }
+        const int k0 = (int)((r * A) % H);
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            if (sb + s >= ns) continue;
+            const float* hs = h + (size_t)(sb + s) * ldh;
+#pragma unroll
+            for (int a = 0; a < A; ++a) {
+                const int k = k0 + a;
+                const bool wrap = k >= H;
+                const float p = acc[s][a] * hs[wrap ? k - H : k];
+                if (wrap) s1[s] += p; else s0[s] += p;
+            }
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+        if (sb + s >= ns) continue;
+        red[((sb + s) * 256 + tid) * 2] = s0[s];
+        red[((sb + s) * 256 + tid) * 2 + 1] = s1[s];
+    }
+    __syncthreads();
+    const int64_t nrows = LH - rb < 256 ? LH - rb : 256;
+    const int64_t F0 = rb * A, F1 = F0 + nrows * A, n0 = F0 / H;
+    const int cnt = (int)((F1 - 1) / H - n0) + 1;
+    const int lane = threadIdx.x & 63;
+    for (int q = threadIdx.x >> 6; q < cnt; q += blockDim.x >> 6) {
+        const int64_t n = n0 + q;
+        const int64_t lo = n * H > F0 ? n * H : F0, hi = ((n + 1) * H < F1 ? (n + 1) * H : F1) - 1;
+        const int t_lo = (int)(lo / A - rb), t_hi = (int)(hi / A - rb);
+        for (int s = 0; s < ns; ++s) {
+            float v = 0.0f;
+            for (int t = t_lo + lane; t <= t_hi; t += 64) v += red[(s * 256 + t) * 2 + (((rb + t) * A) / H == n ? 0 : 1)];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+            if (lane == 0) partial[((size_t)s * gridDim.x + blockIdx.x) * kmax + q] = v;
+        }
+    }
+}
+
+// Thread l < L finishes position l for the S samples in order: logit 20 l + a = its blocks' partial sums in block order + the sampled
+// bias, times log(1 + exp(temperature)); log-softmax over the 20 letters as in eve_elbo_kernel; acc [20 L][3] doubles: the first
+// sample's value, sum and sum of squares of (logp - that), added in sample order (sample0 + s == 0 starts them).
+__global__ __launch_bounds__(64) void eve_prior_finish_kernel(const float* __restrict__ partial, int nblocks, int kmax, int S,
+                                                              const float* __restrict__ b_mean, const float* __restrict__ b_sd,
+                                                              const float* __restrict__ t_mean, const float* __restrict__ t_sd, EveRng g,
+                                                              EvePriorPtrs inj_b, EvePriorPtrs inj_t, int L, int H, int sample0,
+                                                              double* __restrict__ acc) {
+    constexpr int A = 20;
+    const int l = blockIdx.x * blockDim.x + threadIdx.x;
+    if (l >= L) return;
+    for (int s = 0; s < S; ++s) {
+        const EveRng gs = eve_rng_plus(g, s);
+        float t = 1.0f;
+        if (t_mean) {
+            const float ev = inj_t.p[s] ? inj_t.p[s][0] : eve_normal(gs, PGMI_EVE_T_TEMP, 0);
+            t = logf(1.0f + expf(t_sd[0] * ev + t_mean[0]));
+        }
+        float x[A];
+#pragma unroll
+        for (int a = 0; a < A; ++a) {
+            const int64_t n = (int64_t)l * A + a;
+            const int64_t b_lo = n * H / (256 * A), b_hi = ((n + 1) * H - 1) / (256 * A);
+            float sum = 0.0f;
+            for (int64_t b = b_lo; b <= b_hi; ++b) sum += partial[((size_t)s * nblocks + b) * kmax + (n - b * (256 * A) / H)];
+            const float ev = inj_b.p[s] ? inj_b.p[s][n] : eve_normal(gs, PGMI_EVE_T_BOUT, (uint64_t)n);
+            x[a] = sum + (b_sd[n] * ev + b_mean[n]);
+            if (t_mean) x[a] *= t;
+        }
+        float mx = x[0];
+#pragma unroll
+        for (int a = 1; a < A; ++a) mx = fmaxf(mx, x[a]);
+        float se = 0.0f;
+#pragma unroll
+        for (int a = 0; a < A; ++a) se += expf(x[a] - mx);
+        const float lse = mx + logf(se);
+#pragma unroll
+        for (int a = 0; a < A; ++a) {
+            double* a3 = acc + ((size_t)l * A + a) * 3;
+            const double lp = (double)(x[a] - lse);
+            if (sample0 + s == 0) { a3[0] = lp; a3[1] = 0.0; a3[2] = 0.0; }
+            else { const double d = lp - a3[0]; a3[1] += d; a3[2] += d * d; }
+        }
+    }
+}
+
 // ---- the generator's noise as tensors -------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void eve_fill_normal_kernel(EveRng g, int tensor, uint64_t e0, int64_t n, float* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -372,6 +610,51 @@ void launch_eve_fill_normal(uint64_t seed, uint32_t sample, int tensor, uint64_t
 
 void launch_eve_fill_keep(uint64_t seed, uint32_t sample, int tensor, uint64_t e0, int64_t n, uint32_t keep24, uint8_t* out, hipStream_t s) {
     if (n > 0) hipLaunchKernelGGL(eve_fill_keep_kernel, dim3(eve_blocks(n)), dim3(256), 0, s, eve_rng(seed, sample), tensor, e0, n, keep24, out);
+}
+
+void launch_eve_prior_latent(const float* mulv, int z, int ld, uint64_t seed, uint32_t sample, const EvePriorPtrs& inj, int S, float* h,
+                             hipStream_t s) {
+    hipLaunchKernelGGL(eve_prior_latent_kernel, dim3(eve_blocks((int64_t)S * ld)), dim3(256), 0, s, mulv, z, ld, eve_rng(seed, sample), inj, S, h);
+}
+
+void launch_eve_prior_hidden(const float* w_mean, const float* w_sd, const float* b_mean, const float* b_sd, int N, int K, uint64_t seed,
+                             uint32_t sample, int tw, int tb, const EvePriorPtrs& inj_w, const EvePriorPtrs& inj_b, int S, const float* x,
+                             int ldx, int act, float* y, int ldy, hipStream_t s) {
+    hipLaunchKernelGGL(eve_prior_hidden_kernel, dim3((N + 3) / 4, S), dim3(256), 0, s, w_mean, w_sd, b_mean, b_sd, N, K, eve_rng(seed, sample),
+                       tw, tb, inj_w, inj_b, x, ldx, act, y, ldy);
+}
+
+int eve_prior_blocks(int L, int H) { return (int)eve_blocks((int64_t)L * H); }
+int eve_prior_kmax(int H) { return (256 * 20 - 1) / H + 2; }
+// samples one launch of the final kernel can serve: per sample its conv weight (20 C floats) and its reduction buffer (512 floats)
+// take dynamic LDS, kept within 48 KB per block; 0 = none
+int eve_prior_max_samples(int C, bool conv) {
+    const int fit = conv ? (48 * 1024 / 4) / (20 * C + 512) : EVE_PRIOR_S;
+    return fit < EVE_PRIOR_S ? fit : EVE_PRIOR_S;
+}
+
+void launch_eve_prior_final(const float* w_mean, const float* w_sd, const float* c_mean, const float* c_sd, const float* s_mean,
+                            const float* s_sd, int L, int H, int C, int Ht, bool conv, uint64_t seed, uint32_t sample,
+                            const EvePriorPtrs& inj_w, const EvePriorPtrs& inj_c, const EvePriorPtrs& inj_s, int S, const float* h, int ldh,
+                            float* partial, hipStream_t s) {
+    // 1 or 2 samples: one group of 256 threads; 3 or 4: two groups of two samples (the second sample of the last group may be absent)
+    const dim3 grid(eve_prior_blocks(L, H)), block(S > 2 ? 512 : 256);
+    const size_t lds = ((conv ? (size_t)S * 20 * C : 0) + (size_t)S * 512) * sizeof(float);
+    const EveRng g = eve_rng(seed, sample);
+    const int kmax = eve_prior_kmax(H);
+#define PGMI_EVE_PRIOR_LAUNCH(CONV, N)                                                                                                   \
+    hipLaunchKernelGGL((eve_prior_final_kernel<CONV, N>), grid, block, lds, s, w_mean, w_sd, c_mean, c_sd, s_mean, s_sd, L, H, C, Ht, g, \
+                       inj_w, inj_c, inj_s, S, h, ldh, partial, kmax)
+    if (conv) { if (S == 1) PGMI_EVE_PRIOR_LAUNCH(true, 1); else PGMI_EVE_PRIOR_LAUNCH(true, 2); }
+    else { if (S == 1) PGMI_EVE_PRIOR_LAUNCH(false, 1); else PGMI_EVE_PRIOR_LAUNCH(false, 2); }
+#undef PGMI_EVE_PRIOR_LAUNCH
+}
+
+void launch_eve_prior_finish(const float* partial, int S, const float* b_mean, const float* b_sd, const float* t_mean, const float* t_sd,
+                             uint64_t seed, uint32_t sample, const EvePriorPtrs& inj_b, const EvePriorPtrs& inj_t, int L, int H, int sample0,
+                             double* acc, hipStream_t s) {
+    hipLaunchKernelGGL(eve_prior_finish_kernel, dim3((L + 63) / 64), dim3(64), 0, s, partial, eve_prior_blocks(L, H), eve_prior_kmax(H), S,
+                       b_mean, b_sd, t_mean, t_sd, eve_rng(seed, sample), inj_b, inj_t, L, H, sample0, acc);
 }
 
 }  // namespace pgmi

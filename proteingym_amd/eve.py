@@ -320,6 +320,28 @@ class EveModel:
                                                      _lib.ptr(std, _lib._f64p)))
         return mean, std
 
+    def log_prior(self, residues, num_samples: int, seed: int = 0, noise: Sequence[Dict[str, np.ndarray]] = None):
+        """(mean, std) f64 [L, 20] of log_softmax(decoder(z)) of one row over num_samples samples, without dropout (TranceptEVE's
+        get_EVE_log_prior_single).  ``noise``: one dict per sample (noise_shapes(1) without the keep masks) instead of the generator."""
+        r = self._res(np.asarray(residues).reshape(1, -1))
+        mean, std = np.empty((self.L, 20), np.float64), np.empty((self.L, 20), np.float64)
+        inj, alive = None, []
+        if noise is not None:
+            if len(noise) != num_samples:
+                raise _lib.PgmiError(f"{len(noise)} noise dicts for {num_samples} samples")
+            need = {n for n in self.noise_shapes(1) if not n.startswith("keep")}
+            arr = (EveNoise * num_samples)()
+            for j, nz in enumerate(noise):
+                if need - set(nz):
+                    raise _lib.PgmiError(f"injected noise of sample {j} lacks {sorted(need - set(nz))}")
+                s, keep = self._noise_struct({k: v for k, v in nz.items() if k in need}, 1)
+                arr[j] = s
+                alive.append(keep)
+            inj = C.cast(arr, C.c_void_p)
+        _lib.check(_lib.load().pgmi_eve_log_prior(self._h, _u8p(r), num_samples, seed, inj, _lib.ptr(mean, _lib._f64p),
+                                                  _lib.ptr(std, _lib._f64p)))
+        return mean, std
+
 
 def from_checkpoint(path: str, params_path: str, seq_len: int, device: int = 0) -> EveModel:
     with open(params_path) as f:

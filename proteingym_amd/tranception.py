@@ -224,13 +224,16 @@ def compute_sequence_weights(enc: np.ndarray, theta: float, device: int = 0) -> 
 
 def get_msa_prior(MSA_data_file, MSA_weight_file_name, MSA_start, MSA_end, len_target_seq, vocab=VOCAB,
                   retrieval_aggregation_mode="aggregate_substitution", filter_MSA=True, seq_name_to_weight=None,
-                  block_bytes=64 << 20):
+                  block_bytes=64 << 20, threshold_sequence_frac_gaps=None, return_depth=False):
     """Per-position amino-acid distribution of the retrieved alignment with 1e-5 pseudo-counts, [len_target_seq, V],
     zero outside [MSA_start, MSA_end) -- the quantity msa_utils.py:63-138 builds.  Sequences sharing less than 20 %
     of the query's symbols are dropped (:83-91); with ``MSA_weight_file_name`` the EVE weights come from
     ``MSA_processing`` and sequences without a weight are dropped (:100-115); ``seq_name_to_weight`` injects weights
     directly (additive, like ``block_bytes``: the size of the float64 working set).  The float expression of the reference
-    is kept term by term so the result is bit-identical."""
+    is kept term by term so the result is bit-identical.  TranceptEVE's version (trancepteve/utils/msa_utils.py:63-139) passes its
+    sequence gap threshold to the weights' alignment (``threshold_sequence_frac_gaps``; None: the default 0.5; the focus-column
+    threshold of that alignment is always 1.0) and also returns the number of sequences kept: ``return_depth`` makes the result
+    (prior, processed_MSA_depth)."""
     V = len(vocab)
     records = process_msa_data(MSA_data_file)
     names = list(records)
@@ -258,15 +261,18 @@ def get_msa_prior(MSA_data_file, MSA_weight_file_name, MSA_start, MSA_end, len_t
         keep &= ~(((codes == query) & (query >= 0)).sum(axis=1) / n_query < 0.2)
     if MSA_weight_file_name is not None and seq_name_to_weight is None:
         assert os.path.exists(MSA_weight_file_name), "Weights file not located on disk."
-        seq_name_to_weight = MSA_processing(MSA_location=MSA_data_file, use_weights=True,
-                                            weights_location=MSA_weight_file_name).seq_name_to_weight
+        extra = {} if threshold_sequence_frac_gaps is None else dict(threshold_sequence_frac_gaps=threshold_sequence_frac_gaps)
+        seq_name_to_weight = MSA_processing(MSA_location=MSA_data_file, use_weights=True, threshold_focus_cols_frac_gaps=1.0,
+                                            weights_location=MSA_weight_file_name, **extra).seq_name_to_weight
     if seq_name_to_weight is not None:
         keep &= np.array([n in seq_name_to_weight for n in names], dtype=bool)
         weights = np.array([seq_name_to_weight[n] for n, k in zip(names, keep) if k])
     else:
         weights = np.array([1] * int(keep.sum()))
+    depth = int(keep.sum())
     if retrieval_aggregation_mode not in ("aggregate_substitution", "aggregate_indel"):
-        return np.ones((len_target_seq, V)) / V
+        uniform = np.ones((len_target_seq, V)) / V
+        return (uniform, depth) if return_depth else uniform
     codes = codes[keep]
     if codes.shape[1] > width:
         if (codes[:, width:] >= 0).any():
@@ -292,7 +298,7 @@ def get_msa_prior(MSA_data_file, MSA_weight_file_name, MSA_start, MSA_end, len_t
         acc = np.add.reduce(counts if first else np.concatenate([acc[None], counts]), axis=0)
     prior = np.zeros((len_target_seq, V))
     prior[MSA_start:MSA_end, :] = acc / np.tile(total.reshape(-1, 1), (1, V))
-    return prior
+    return (prior, depth) if return_depth else prior
 
 
 # ---- indel scoring with retrieval: one re-alignment per scored sequence (msa_utils.py:141-192) ------
@@ -454,7 +460,8 @@ class TranceptionModel(_lib.ModelHandle):
                          max_positions=cfg["max_positions"], ln_eps=cfg.get("ln_eps", 1e-5))
         self.n_ctx = cfg["max_positions"]
         self.scoring_window = scoring_window
-        # retrieval: dict(log_prior [L,25] float32, MSA_start (0-based), MSA_end, weight)
+        # retrieval: dict(log_prior [L,25] float32, MSA_start (0-based), MSA_end, weight); TranceptEVE adds eve_log_prior [L,25]
+        # float32 (-inf outside EVE's focus columns), eve_weight and eve_fallback (trancepteve.py)
         self.retrieval = retrieval
         self.share_prefix = os.environ.get("PGMI_TR_SHARE_PREFIX", "1") != "0"
 
@@ -507,6 +514,12 @@ class TranceptionModel(_lib.ModelHandle):
         lengths = np.array([len(s) for s in seqs], dtype=np.int64)
         order = np.argsort(lengths, kind="stable")
         r = self.retrieval
+        eve = None                                                    # TranceptEVE: the second prior rides on the first one's rows
+        if r is not None and r.get("eve_log_prior") is not None:
+            elp = _lib.as_f32(r["eve_log_prior"])
+            if elp.shape != np.shape(r["log_prior"]):
+                raise ValueError(f"eve_log_prior {elp.shape} and log_prior {np.shape(r['log_prior'])} differ in shape")
+            eve = (_lib.ptr(elp, _lib._f32p), float(r["eve_weight"]), int(bool(r.get("eve_fallback", False))))
         share = reference is not None and getattr(self, "share_prefix", True)
         if share:
             reference = np.asarray(reference, dtype=np.int64)
@@ -554,13 +567,22 @@ class TranceptionModel(_lib.ModelHandle):
                     ref_c = ref_c.copy()
                     ref_c[B:] = np.arange(B, Bc)                  # (ref_c[B:] held the wild-type row each new root was made from)
                 rows = np.zeros(1, dtype=np.int64)
-                _lib.check(lib.pgmi_tr_sequence_loglik_shared(self._h, _lib.ptr(ids_c, _lib._i32p), _lib.ptr(ref_c, _lib._i32p), Bc, T,
-                                                              *prior_c, _lib.ptr(res_c, _lib._f32p), None, _lib.ptr(rows, _lib._i64p)))
+                if eve is not None:
+                    _lib.check(lib.pgmi_tr_sequence_loglik_shared_eve(self._h, _lib.ptr(ids_c, _lib._i32p), _lib.ptr(ref_c, _lib._i32p), Bc, T,
+                                                                      *prior_c, *eve, _lib.ptr(res_c, _lib._f32p), None,
+                                                                      _lib.ptr(rows, _lib._i64p)))
+                else:
+                    _lib.check(lib.pgmi_tr_sequence_loglik_shared(self._h, _lib.ptr(ids_c, _lib._i32p), _lib.ptr(ref_c, _lib._i32p), Bc, T,
+                                                                  *prior_c, _lib.ptr(res_c, _lib._f32p), None, _lib.ptr(rows, _lib._i64p)))
                 res = res_c[:B]
                 self.rows_forwarded += int(rows[0])
             else:
-                _lib.check(lib.pgmi_tr_sequence_loglik(self._h, _lib.ptr(ids, _lib._i32p), _lib.ptr(lens, _lib._i32p), B, T,
-                                                       *prior, _lib.ptr(res, _lib._f32p)))
+                if eve is not None:
+                    _lib.check(lib.pgmi_tr_sequence_loglik_eve(self._h, _lib.ptr(ids, _lib._i32p), _lib.ptr(lens, _lib._i32p), B, T,
+                                                               *prior, *eve, _lib.ptr(res, _lib._f32p)))
+                else:
+                    _lib.check(lib.pgmi_tr_sequence_loglik(self._h, _lib.ptr(ids, _lib._i32p), _lib.ptr(lens, _lib._i32p), B, T,
+                                                           *prior, _lib.ptr(res, _lib._f32p)))
                 self.rows_forwarded += B * T
             self.rows_full += B * T
             out[idx] = res
@@ -677,10 +699,16 @@ class TranceptionModel(_lib.ModelHandle):
         flip = np.zeros(B, dtype=np.int32)
         res = np.empty(B, dtype=np.float32)
         lp = _lib.as_f32(prior)
-        _lib.check(_lib.load().pgmi_tr_sequence_loglik(self._h, _lib.ptr(ids, _lib._i32p), _lib.ptr(lens, _lib._i32p), B, T,
-                                                       _lib.ptr(lp, _lib._f32p), lp.shape[0], _lib.ptr(a0, _lib._i32p), _lib.ptr(row0, _lib._i32p),
-                                                       _lib.ptr(count, _lib._i32p), _lib.ptr(flip, _lib._i32p), float(r["weight"]),
-                                                       _lib.ptr(res, _lib._f32p)))
+        args = (self._h, _lib.ptr(ids, _lib._i32p), _lib.ptr(lens, _lib._i32p), B, T, _lib.ptr(lp, _lib._f32p), lp.shape[0],
+                _lib.ptr(a0, _lib._i32p), _lib.ptr(row0, _lib._i32p), _lib.ptr(count, _lib._i32p), _lib.ptr(flip, _lib._i32p), float(r["weight"]))
+        if r.get("eve_log_prior") is not None:                           # TranceptEVE: the EVE table goes through the same alignment rows
+            eprior = np.zeros_like(prior)
+            eprior[:len(window)][has_prior] = np.asarray(r["eve_log_prior"], dtype=np.float32)[window[has_prior]]
+            elp = _lib.as_f32(eprior)
+            _lib.check(_lib.load().pgmi_tr_sequence_loglik_eve(*args, _lib.ptr(elp, _lib._f32p), float(r["eve_weight"]),
+                                                               int(bool(r.get("eve_fallback", False))), _lib.ptr(res, _lib._f32p)))
+        else:
+            _lib.check(_lib.load().pgmi_tr_sequence_loglik(*args, _lib.ptr(res, _lib._f32p)))
         plain = float(res[-1])
         return float(np.sum(res[:-1], dtype=np.float64) - (len(runs) - 1) * plain) if runs else plain
 
