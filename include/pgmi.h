@@ -273,6 +273,26 @@ int pgmi_op_attention(int device, int precision, const float* qkv, const int32_t
 int pgmi_op_causal_attention(int device, int lanes, const float* X, const float* W, const float* bias, int K, const float* qkv,
                              const float* conv, const float* rot_cos, const float* rot_sin, const float* slopes, int B, int T,
                              int heads, float* ctx);
+/* The MSA Transformer's two axial attentions (axial_attention.py:108-168, :232-275), through the launchers and the argument pattern of the
+ * model's forward.  Heads of 64 lanes, D = 64 H; q is taken as given (pre-scaled by 1/8).
+ * pgmi_op_tied_row_attention: qkv [R*C, 3 D] (q | k | v), token order (r, c).  s[h,i,j] = sum_{r,d} q[r,i,h,d] k[r,j,h,d] / sqrt(R) is ONE
+ *   score matrix per head, P = softmax_j, ctx[r,i,h,:] = sum_j P[h,i,j] v[r,j,h,:].  splits: the K splits S of the scores GEMM (0: the
+ *   forward's rule, pgmi_op_tied_row_splits; else S must divide R, 1 .. 16).  ctx [R*C, D]: the split-plane context the out-projection
+ *   consumes, rebuilt as fp32; probs (nullable) [H, C, Kp], Kp = C rounded up to 64: the P planes of the update GEMM rebuilt as fp32,
+ *   padding columns included (exact zeros).  The q planes and the context planes are one buffer, as in the forward; the partial scores,
+ *   P, V^T and that buffer start as 0xFF bytes (NaN): a score, probability or V^T element the kernels neither write nor ignore shows as
+ *   NaN.  (Not so a context row: the q operand overwrites the shared buffer first, so an unwritten context row holds finite q values
+ *   and only the comparison of values finds it.)  PGMI_EINVAL with the launcher's message, before anything is allocated, for a bad
+ *   `splits`, C > 1024 and operands beyond the 32-bit offset range.
+ * pgmi_op_tied_row_splits: a test-only entry beside the two ops, so that a test reads the S the forward's rule picks for (R, C, H)
+ *   instead of trusting its own copy of the rule.  Host only.  Returns S (1 .. 16), or PGMI_EINVAL (negative) for a non-positive argument.
+ * pgmi_op_column_attention: X [C*R, K] (K % 32 == 0), token order (c, r), W [3 D, K] (rows q | k | v), bias [3 D]: the fused QKV
+ *   projection (no rotary) forms X W^T + bias, then every column is one sequence of R rows of the dense attention (B = C, T = R, kv_len = R,
+ *   pad keys zeroed); honours the "att_v3" option.  ctx [C*R, D], order (c, r): the split-plane context (0xFF bytes before the launch)
+ *   rebuilt as fp32. */
+int pgmi_op_tied_row_attention(int device, const float* qkv, int R, int C, int H, int splits, float* ctx, float* probs);
+int pgmi_op_tied_row_splits(int R, int C, int H);
+int pgmi_op_column_attention(int device, const float* X, const float* W, const float* bias, int K, int R, int C, int H, float* ctx);
 
 /* ---- Tranception (arch PGMI_ARCH_TRANCEPTION; vocab 25, max_positions = n_ctx, precision f16x3) ------
  * Weight blob order (fp32, names as in the HF state dict, Conv1D weights as stored = [in,out]):

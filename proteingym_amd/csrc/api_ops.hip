@@ -364,4 +364,117 @@ int pgmi_op_causal_attention(int device, int lanes, const float* X, const float*
     return PGMI_OK;
 }
 
+// The K splits run_msa's rule picks for an alignment of R x C tokens and H heads (host only: no device is touched).
+int pgmi_op_tied_row_splits(int R, int C, int H) {
+    if (R <= 0 || C <= 0 || H <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
+    return tied_row_splits(R, C, H);
+}
+
+// The tied row attention of one MSA Transformer layer (run_msa, api_msa.hip) through launch_tied_row_attention with run_msa's aliasing:
+// the q planes and the context planes are one buffer.  Every buffer the kernels write or are meant to ignore starts as 0xFF bytes (NaN in
+// fp32 and in fp16): the stale workspace of an earlier, wider alignment.  What the launcher refuses is refused before any allocation.
+int pgmi_op_tied_row_attention(int device, const float* qkv, int R, int C, int H, int splits, float* ctx, float* probs) {
+    if (!qkv || !ctx || R <= 0 || C <= 0 || H <= 0 || splits < 0) { set_error("bad argument"); return PGMI_EINVAL; }
+    const int S = splits ? splits : tied_row_splits(R, C, H);
+    int rc = tied_row_check(R, C, H, S);
+    if (rc) return rc;
+    if (pgmi_device_count() <= 0) { set_error("no HIP device visible"); return PGMI_ENODEV; }
+    PGMI_HIP(hipSetDevice(device));
+    const size_t M = (size_t)R * C, D = (size_t)H * kHeadDim, Kp = (size_t)tied_row_kp(C);
+    const size_t n_part = (size_t)H * S * C * Kp, n_p = (size_t)H * C * Kp, n_vt = (size_t)H * R * kHeadDim * Kp;
+    std::vector<void*> pool;
+    auto cleanup = [&]() { for (void* p : pool) hipFree(p); };
+    float *dq = nullptr, *part = nullptr, *pp = nullptr, *vt = nullptr;
+    unsigned short *qctx16 = nullptr, *k16 = nullptr;
+    if ((rc = dev_upload(pool, &dq, qkv, M * 3 * D)) || (rc = dev_alloc(pool, &qctx16, M * D * 2)) || (rc = dev_alloc(pool, &k16, M * D * 2)) ||
+        (rc = dev_alloc(pool, &part, n_part)) || (rc = dev_alloc(pool, &pp, n_p)) || (rc = dev_alloc(pool, &vt, n_vt))) {
+        cleanup();
+        return rc;
+    }
+    hipError_t e = hipMemset(part, 0xFF, n_part * 4);
+    if (e == hipSuccess) e = hipMemset(pp, 0xFF, n_p * 4);
+    if (e == hipSuccess) e = hipMemset(vt, 0xFF, n_vt * 4);
+    if (e == hipSuccess) e = hipMemset(qctx16, 0xFF, M * D * 2 * sizeof(unsigned short));
+    if (e != hipSuccess) { cleanup(); set_error("tied row attention op failed: %s", hipGetErrorString(e)); return PGMI_EHIP; }
+    TiedRowLaunch t;
+    t.qkv = dq, t.R = R, t.C = C, t.H = H, t.S = S;
+    t.qctx16 = qctx16, t.k16 = k16;
+    t.part = part, t.p = pp, t.vt = vt;
+    rc = launch_tied_row_attention(t);
+    std::vector<unsigned short> h(rc ? 0 : M * D * 2), hp(rc || !probs ? 0 : n_p * 2);
+    e = hipDeviceSynchronize();
+    if (!rc && e == hipSuccess) e = hipMemcpy(h.data(), qctx16, h.size() * 2, hipMemcpyDeviceToHost);
+    if (!rc && probs && e == hipSuccess) e = hipMemcpy(hp.data(), pp, hp.size() * 2, hipMemcpyDeviceToHost);
+    cleanup();
+    if (rc) return rc;
+    if (e != hipSuccess) { set_error("tied row attention op failed: %s", hipGetErrorString(e)); return PGMI_EHIP; }
+    for (size_t m = 0; m < M; ++m)                               // the context planes (K-interleaved rows of D) rebuilt as fp32
+        for (size_t n = 0; n < D; ++n) {
+            const size_t o = ki_off(m, (int)n, (int)D);
+            ctx[m * D + n] = rebuild_split(h[o], h[o + 32]);
+        }
+    if (probs)                                                   // the P planes: rows (h, i) of Kp columns
+        for (size_t r = 0; r < (size_t)H * C; ++r)
+            for (size_t j = 0; j < Kp; ++j) {
+                const size_t o = ki_off(r, (int)j, (int)Kp);
+                probs[r * Kp + j] = rebuild_split(hp[o], hp[o + 32]);
+            }
+    return PGMI_OK;
+}
+
+// The column attention of one MSA Transformer layer (run_msa's column block): the activation split, the fused QKV projection without
+// rotary on sequences of R rows, V^T planes zeroed first (pad keys must be finite), then the dense attention with B = C, T = R, a device
+// kv_len of C entries equal to R and the split-plane context, which starts as 0xFF bytes.
+int pgmi_op_column_attention(int device, const float* X, const float* W, const float* bias, int K, int R, int C, int H, float* ctx) {
+    if (!X || !W || !bias || !ctx || R <= 0 || C <= 0 || H <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
+    // the activation / weight split writes K-interleaved rows (ki_off) before any launcher sees K: whole groups of 32 only
+    if (K <= 0 || K % 32) { set_error("column attention op: K = %d is not a positive multiple of 32", K); return PGMI_EINVAL; }
+    if (pgmi_device_count() <= 0) { set_error("no HIP device visible"); return PGMI_ENODEV; }
+    PGMI_HIP(hipSetDevice(device));
+    gemm_options_from_env();
+    const size_t M = (size_t)C * R, D = (size_t)H * kHeadDim, Tp = (size_t)(R + 31) / 32 * 32;
+    const size_t qk_plane = M * 2 * D, vt_plane = (size_t)C * Tp * D;
+    std::vector<void*> pool;
+    auto cleanup = [&]() { for (void* p : pool) hipFree(p); };
+    const std::vector<int32_t> kv((size_t)C, R);
+    float *dx = nullptr, *db = nullptr;
+    int32_t* dl = nullptr;
+    unsigned short *a16 = nullptr, *qk16 = nullptr, *vt16 = nullptr, *c16 = nullptr;
+    int rc = 0;
+    if ((rc = dev_upload(pool, &dx, X, M * K)) || (rc = dev_upload(pool, &db, bias, 3 * D)) || (rc = dev_upload(pool, &dl, kv.data(), kv.size())) ||
+        (rc = dev_alloc(pool, &a16, M * K * 2)) || (rc = dev_alloc(pool, &qk16, qk_plane * 2)) || (rc = dev_alloc(pool, &vt16, vt_plane * 2)) ||
+        (rc = dev_alloc(pool, &c16, M * D * 2))) {
+        cleanup();
+        return rc;
+    }
+    hipError_t e = hipMemset(vt16, 0, vt_plane * 2 * sizeof(unsigned short));
+    if (e == hipSuccess) e = hipMemset(c16, 0xFF, M * D * 2 * sizeof(unsigned short));
+    if (e != hipSuccess) { cleanup(); set_error("column attention op failed: %s", hipGetErrorString(e)); return PGMI_EHIP; }
+    W16 w16;
+    rc = make_w16(pool, W, 3 * D * K, (size_t)K, PGMI_PREC_F16X3, nullptr, &w16);
+    if (!rc) {
+        launch_split16(dx, (int64_t)(M * K), 1.0f, 2, K, a16, nullptr);
+        rc = launch_gemm16_qkv(a16, M * K, w16.p, w16.plane, db, (int)M, (int)D, K, w16.out_scale, qk16, qk_plane, vt16, vt_plane,
+                               nullptr, nullptr, 0, R, H, env_int("PGMI_GEMM_VARIANT", 0), nullptr);
+    }
+    AttLaunch a;
+    a.qk16 = qk16, a.qk_plane = qk_plane, a.vt16 = vt16, a.vt_plane = vt_plane;
+    a.B = C, a.T = R, a.H = H;
+    a.kv_len = dl;
+    a.out = ATT_OUT_SPLIT, a.ctx16 = c16;
+    if (!rc) rc = launch_attention_f16x3_v2(a);
+    std::vector<unsigned short> h(rc ? 0 : M * D * 2);
+    e = hipDeviceSynchronize();
+    if (!rc && e == hipSuccess) e = hipMemcpy(h.data(), c16, h.size() * 2, hipMemcpyDeviceToHost);
+    cleanup();
+    if (rc) return rc;
+    if (e != hipSuccess) { set_error("column attention op failed: %s", hipGetErrorString(e)); return PGMI_EHIP; }
+    for (size_t m = 0; m < M; ++m)
+        for (size_t n = 0; n < D; ++n) {
+            const size_t o = ki_off(m, (int)n, (int)D);
+            ctx[m * D + n] = rebuild_split(h[o], h[o + 32]);
+        }
+    return PGMI_OK;
+}
+
 }  // extern "C"

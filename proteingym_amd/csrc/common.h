@@ -173,6 +173,23 @@ void launch_tied_prep_qk(const float* qkv, int64_t M, int D, unsigned short* q16
 void launch_pack_vt16(const float* qkv, int R, int C, int Kp, int H, unsigned short* Vt, hipStream_t s);
 int launch_tied_softmax16(const float* part, int H, int S, int C, int Kp, float scale, unsigned short* P, hipStream_t s);
 float tied_w_scale();
+// The tied row attention of one alignment, from the fp32 q | k | v rows of its projection to the split-plane context rows: operand
+// prep, split-K scores GEMM, softmax, update GEMM (launch_gemm16_ex).  One launch, fields assigned by name.
+struct TiedRowLaunch {
+    const float* qkv = nullptr;         // fp32 [R*C][3*H*64], token order (r, c), q pre-scaled by head_dim^-1/2
+    int R = 0, C = 0, H = 0;
+    int S = 0;                          // K splits of the scores GEMM: divides R, 1 .. 16 (tied_row_splits: the product's choice)
+    unsigned short* qctx16 = nullptr;   // 2 planes x R*C*H*64 halfs, K-interleaved rows: the q operand, then overwritten by the context rows
+    unsigned short* k16 = nullptr;      // the same size: the k operand
+    float* part = nullptr;              // H * S * C * tied_row_kp(C): split-K partial scores
+    float* p = nullptr;                 // H * C * tied_row_kp(C): the probabilities as split planes (4 bytes per element like fp32)
+    float* vt = nullptr;                // H * R * 64 * tied_row_kp(C): V^T as split planes
+    hipStream_t stream = nullptr;
+};
+int tied_row_kp(int C);                              // the update GEMM's K: columns j, zero-padded to a multiple of 64
+int tied_row_splits(int R, int C, int H);            // S: divides R, ~2 rounds of score tiles at most
+int tied_row_check(int R, int C, int H, int S);      // PGMI_EINVAL with a message for what launch_tied_row_attention refuses
+int launch_tied_row_attention(const TiedRowLaunch& t);
 
 int launch_gemm_f32(const float* A, const float* W, const float* bias, const float* residual,
                     float* C, int M, int N, int K, int epilogue, hipStream_t s);

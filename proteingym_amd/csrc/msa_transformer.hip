@@ -14,6 +14,7 @@
 //     + DMA-ring kernel) runs with batch = C, T = R.
 // All kernels here are HBM-bound data movement or tiny reductions.
 #include "common.h"
+#include "gemm16x_kernel.h"          // XMap: the operand maps of the two batched GEMMs; no kernel is instantiated here
 
 namespace pgmi {
 
@@ -196,6 +197,62 @@ int launch_tied_softmax16(const float* part, int H, int S, int C, int Kp, float 
     if (C > 1024 || Kp > 1024 || (Kp % 64)) { set_error("tied row attention supports at most 1024 columns, got %d", C); return PGMI_EINVAL; }
     hipLaunchKernelGGL(tied_softmax16_kernel, dim3((H * C + 3) / 4), dim3(256), 0, s, part, H, S, C, Kp, scale, P);
     return PGMI_OK;
+}
+
+// ---- the tied row attention as one launch sequence ---------------------------------------------------
+int tied_row_kp(int C) { return (C + 63) / 64 * 64; }
+
+// split the (r, d) contraction of the tied scores so that the launch fills the chip: S divides R, ~2 rounds of tiles at most
+int tied_row_splits(int R, int C, int H) {
+    const int rows_last = C % 256, tm = (rows_last > 0 && rows_last <= 128) ? (C + 127) / 128 : (C + 255) / 256;
+    const int tiles = tm * ((C + 255) / 256) * H;
+    int S = 1;
+    for (int cand = 1; cand <= 16; ++cand) if (R % cand == 0 && tiles * cand <= 640) S = cand;
+    return S;
+}
+
+int tied_row_check(int R, int C, int H, int S) {
+    if (R <= 0 || C <= 0 || H <= 0) { set_error("tied row attention: bad shape %d x %d tokens, %d heads", R, C, H); return PGMI_EINVAL; }
+    if (S < 1 || S > 16 || R % S) { set_error("tied row attention: %d K splits do not divide %d rows into 1 .. 16 parts", S, R); return PGMI_EINVAL; }
+    if (C > 1024) { set_error("tied row attention supports at most 1024 columns, got %d", C); return PGMI_EINVAL; }
+    const unsigned long long M = (unsigned long long)R * C, D = (unsigned long long)H * 64, Kp = tied_row_kp(C);
+    if (M * D * 4ull >= (1ull << 32) || (unsigned long long)H * R * 64 * Kp * 4ull >= (1ull << 32)) {
+        set_error("alignment of %d x %d tokens exceeds the 32-bit offset range of the tied row attention's operands", R, C);
+        return PGMI_EINVAL;
+    }
+    return PGMI_OK;
+}
+
+int launch_tied_row_attention(const TiedRowLaunch& t) {
+    int rc = tied_row_check(t.R, t.C, t.H, t.S);
+    if (rc) return rc;
+    const int R = t.R, C = t.C, H = t.H, S = t.S, M = R * C, D = H * 64, Kp = tied_row_kp(C);
+    hipStream_t s = t.stream;
+    // operands for the 16-bit pipe: q -> qctx16, k -> k16, V^T
+    unsigned short* q16 = t.qctx16;
+    unsigned short* k16 = t.k16;
+    unsigned short* vt16 = reinterpret_cast<unsigned short*>(t.vt);
+    unsigned short* p16 = reinterpret_cast<unsigned short*>(t.p);
+    launch_tied_prep_qk(t.qkv, M, D, q16, k16, s);
+    launch_pack_vt16(t.qkv, R, C, Kp, H, vt16, s);
+    XMap g1{};                                       // scores: batch = (head, K split); K walks (r, d): runs of 64 d a row of tokens apart
+    g1.a_row_bytes = g1.w_row_bytes = (unsigned int)D * 4u;
+    g1.a_bytes = g1.w_bytes = (unsigned int)((size_t)M * D * 4);
+    g1.k_run_log2 = 1; g1.a_run_bytes = g1.w_run_bytes = (unsigned int)((size_t)C * D * 4);
+    g1.batch_inner = S;
+    g1.a_b0 = g1.w_b0 = (unsigned int)((size_t)(R / S) * C * D * 4); g1.a_b1 = g1.w_b1 = 64u * 4u;
+    g1.c_b0 = (long long)C * Kp; g1.c_b1 = (long long)S * C * Kp; g1.ldc = Kp;
+    rc = launch_gemm16_ex(q16, k16, t.part, nullptr, C, (C + 3) / 4 * 4, (R / S) * 64, 1.0f / tied_w_scale(), g1, H * S, s);
+    if (rc) return rc;
+    rc = launch_tied_softmax16(t.part, H, S, C, Kp, 1.0f / sqrtf((float)R), p16, s);
+    if (rc) return rc;
+    XMap g2{};                                       // update: batch = head, output scattered to the context rows [r, i] x columns [h, d]
+    g2.a_row_bytes = g2.w_row_bytes = (unsigned int)Kp * 4u;
+    g2.a_bytes = (unsigned int)((size_t)H * C * Kp * 4); g2.w_bytes = (unsigned int)((size_t)H * R * 64 * Kp * 4);
+    g2.batch_inner = H;
+    g2.a_b0 = (unsigned int)((size_t)C * Kp * 4); g2.w_b0 = (unsigned int)((size_t)R * 64 * Kp * 4);
+    g2.o_ld = D; g2.o_rows_per_n64 = C; g2.o_col_per_batch = 64;
+    return launch_gemm16_ex(p16, vt16, nullptr, t.qctx16, C, R * 64, Kp, 1.0f / tied_w_scale(), g2, H, s);
 }
 
 }  // namespace pgmi

@@ -696,3 +696,21 @@ def test_tranception_slices_agree_with_the_oracle_on_drawn_libraries():
         assert list(a.columns) == list(b.columns), (mode, list(a.columns), list(b.columns))
         assert len(a) == len(b) and all(list(a[c]) == list(b[c]) for c in cols), (seed, mode, L, ctx)
     check()
+
+
+def test_tied_row_attention_split_rule_and_refusals_need_no_device(lib):
+    """pgmi_op_tied_row_splits is run_msa's rule (the values tests/test_gpu_axial_attention.py relies on; axial_ref.py mirrors it), and
+    pgmi_op_tied_row_attention refuses what the launcher refuses before it looks for a device or allocates."""
+    import axial_ref as ax
+    for case, want in list(zip(ax.TIED_ROW_EDGES, ax.TIED_ROW_EDGE_SPLITS)) + [((18, 300, 12), 6), ((400, 287, 12), 8), ((400, 1024, 12), 2)]:
+        assert lib.pgmi_op_tied_row_splits(*case) == want == ax.tied_splits(*case), case
+    for R in range(1, 50):
+        for Cc, H in ((1, 1), (45, 2), (129, 12), (300, 12), (1024, 20)):
+            assert lib.pgmi_op_tied_row_splits(R, Cc, H) == ax.tied_splits(R, Cc, H), (R, Cc, H)
+    assert lib.pgmi_op_tied_row_splits(0, 5, 1) == _lib.EINVAL
+    buf = np.zeros(16, np.float32)
+    p = buf.ctypes.data_as(_lib._f32p)
+    for args, msg in (((12, 70, 2, 5), "K splits"), ((12, 70, 2, 24), "K splits"), ((12, 70, 2, -1), "bad argument"),
+                      ((2, 1025, 1, 0), "at most 1024 columns"), ((1024, 1024, 20, 0), "32-bit offset range")):
+        assert lib.pgmi_op_tied_row_attention(0, p, *args, p, None) == _lib.EINVAL, args
+        assert msg in lib.pgmi_last_error().decode(), (args, lib.pgmi_last_error())
