@@ -105,18 +105,19 @@ int run_encoder(pgmi_model* m, int B, int T, const int32_t* keep, int n_keep, bo
         const Layer& L = m->layers[l];
         { ProfScope p(m, PGMI_K_LAYERNORM, 0, ln_bytes);
           if (prec == PGMI_PREC_FP32) launch_layernorm(m->x, L.ln1_w, L.ln1_b, M, D, 1e-5f, m->h, s);
-          else launch_layernorm16(m->x, L.ln1_w, L.ln1_b, M, D, 1e-5f, m->h16, m->h16_plane, mode16, s); }
+          else launch_layernorm16(m->x, L.ln1_w, L.ln1_b, M, D, 1e-5f, m->h16, mode16, s); }
         // attention operands straight from the QKV projection's epilogue -- in the bf16 mode too (round 6): the epilogue splits the fp32
         // accumulators whatever the GEMM's operand type was, so that mode's attention runs on the 16-bit pipe as well.  A layer with a
         // q / k LayerNorm (ESM C) writes fp32 rows for its prep pass instead.
         const bool fused_qkv = prec != PGMI_PREC_FP32 && !L.q_ln;
         { ProfScope p(m, PGMI_K_GEMM_QKV, 2.0 * M * 3 * D * D, 0);
-          if (fused_qkv)
-              rc = launch_gemm16_qkv(m->h16, m->h16_plane, L.wqkv16.p, L.wqkv16.plane, L.bqkv, M, Da, D, L.wqkv16.out_scale,
-                                     m->qk16, m->qk16_plane, m->vt16, m->vt16_plane, m->rot_cos, m->rot_sin,
-                                     esm2_rotary(c.arch), T, m->Hs, m->gemm_variant, s, m->rot_halves, prec == PGMI_PREC_BF16);
-          else
-              rc = linear(m, m->h, m->h16, m->h16_plane, L.wqkv, L.wqkv16, L.bqkv, nullptr, m->qkv, nullptr, 0, M, 3 * Da, D, EPI_NONE);
+          if (fused_qkv) {
+              GemmLaunch g = qkv_launch(m, L.wqkv16, L.bqkv, M, Da, D, T, m->Hs);
+              g.bf = prec == PGMI_PREC_BF16;
+              g.qkv.cos_t = m->rot_cos; g.qkv.sin_t = m->rot_sin; g.qkv.rotary = esm2_rotary(c.arch); g.qkv.rot_halves = m->rot_halves;
+              rc = launch_gemm16(g);
+          } else
+              rc = linear(m, m->h, m->h16, L.wqkv, L.wqkv16, L.bqkv, nullptr, m->qkv, nullptr, M, 3 * Da, D, EPI_NONE);
           if (rc) return rc; }
         // the q / k LayerNorm prep pass is profiled as attention (it produces the attention's operands): PGMI_K_ATTENTION counts both
         { ProfScope p(m, PGMI_K_ATTENTION, 4.0 * M * T * D, L.q_ln ? (double)M * D * 20 : 0);
@@ -146,32 +147,32 @@ int run_encoder(pgmi_model* m, int B, int T, const int32_t* keep, int n_keep, bo
             else        // a 16-bit context row is one contiguous run (K-interleaved hi|lo: 4 Da bytes; bf16: 2 Da bytes)
                 launch_gather_rows(reinterpret_cast<const float*>(m->h16), keep, R, prec == PGMI_PREC_F16X3 ? Da : Da / 2,
                                    reinterpret_cast<float*>(m->g16), s);
-            rc = linear(m, m->g, m->g16, m->g16_plane, L.wo, L.wo16, L.bo, m->qkv, m->x, nullptr, 0, R, D, Da, EPI_NONE);
+            rc = linear(m, m->g, m->g16, L.wo, L.wo16, L.bo, m->qkv, m->x, nullptr, R, D, Da, EPI_NONE);
             if (rc) return rc;
             if (prec == PGMI_PREC_FP32) launch_layernorm(m->x, L.ln2_w, L.ln2_b, R, D, 1e-5f, m->h, s);
-            else launch_layernorm16(m->x, L.ln2_w, L.ln2_b, R, D, 1e-5f, m->h16, m->h16_plane, mode16, s);
-            rc = linear(m, m->h, m->h16, m->h16_plane, L.w1, L.w116, L.b1, nullptr,
-                        prec == PGMI_PREC_FP32 ? m->g : nullptr, prec == PGMI_PREC_FP32 ? nullptr : m->g16, m->g16_plane,
+            else launch_layernorm16(m->x, L.ln2_w, L.ln2_b, R, D, 1e-5f, m->h16, mode16, s);
+            rc = linear(m, m->h, m->h16, L.w1, L.w116, L.b1, nullptr,
+                        prec == PGMI_PREC_FP32 ? m->g : nullptr, prec == PGMI_PREC_FP32 ? nullptr : m->g16,
                         R, N1, D, m->fc1_epi);
             if (rc) return rc;
-            rc = linear(m, m->g, m->g16, m->g16_plane, L.w2, L.w216, L.b2, m->x, m->x, nullptr, 0, R, D, F, EPI_NONE);
+            rc = linear(m, m->g, m->g16, L.w2, L.w216, L.b2, m->x, m->x, nullptr, R, D, F, EPI_NONE);
             if (rc) return rc;
             if (compacted) *compacted = true;
             break;
         }
         { ProfScope p(m, PGMI_K_GEMM_OUT, 2.0 * M * D * D, 0);
-          rc = linear(m, m->h, m->h16, m->h16_plane, L.wo, L.wo16, L.bo, m->x, m->x, nullptr, 0, M, D, Da, EPI_NONE);
+          rc = linear(m, m->h, m->h16, L.wo, L.wo16, L.bo, m->x, m->x, nullptr, M, D, Da, EPI_NONE);
           if (rc) return rc; }
         { ProfScope p(m, PGMI_K_LAYERNORM, 0, ln_bytes);
           if (prec == PGMI_PREC_FP32) launch_layernorm(m->x, L.ln2_w, L.ln2_b, M, D, 1e-5f, m->h, s);
-          else launch_layernorm16(m->x, L.ln2_w, L.ln2_b, M, D, 1e-5f, m->h16, m->h16_plane, mode16, s); }
+          else launch_layernorm16(m->x, L.ln2_w, L.ln2_b, M, D, 1e-5f, m->h16, mode16, s); }
         { ProfScope p(m, PGMI_K_GEMM_FC1, 2.0 * M * N1 * D, 0);
-          rc = linear(m, m->h, m->h16, m->h16_plane, L.w1, L.w116, L.b1, nullptr,
-                      prec == PGMI_PREC_FP32 ? m->g : nullptr, prec == PGMI_PREC_FP32 ? nullptr : m->g16, m->g16_plane,
+          rc = linear(m, m->h, m->h16, L.w1, L.w116, L.b1, nullptr,
+                      prec == PGMI_PREC_FP32 ? m->g : nullptr, prec == PGMI_PREC_FP32 ? nullptr : m->g16,
                       M, N1, D, m->fc1_epi);
           if (rc) return rc; }
         { ProfScope p(m, PGMI_K_GEMM_FC2, 2.0 * M * F * D, 0);
-          rc = linear(m, m->g, m->g16, m->g16_plane, L.w2, L.w216, L.b2, m->x, m->x, nullptr, 0, M, D, F, EPI_NONE);
+          rc = linear(m, m->g, m->g16, L.w2, L.w216, L.b2, m->x, m->x, nullptr, M, D, F, EPI_NONE);
           if (rc) return rc; }
     }
     PGMI_HIP(hipGetLastError());
@@ -202,8 +203,8 @@ int head_hidden(pgmi_model* m, int R, const int32_t* row_idx) {
         src = m->h;
     }
     if (prec == PGMI_PREC_FP32) launch_layernorm(src, m->lna_w, m->lna_b, R, D, 1e-5f, m->h, s);
-    else launch_layernorm16(src, m->lna_w, m->lna_b, R, D, 1e-5f, m->h16, m->h16_plane, prec == PGMI_PREC_F16X3 ? 1 : 2, s);
-    int rc = linear(m, m->h, m->h16, m->h16_plane, m->hd_w, m->hd16, m->hd_b, nullptr, m->g, nullptr, 0, R, D, D, EPI_GELU);
+    else launch_layernorm16(src, m->lna_w, m->lna_b, R, D, 1e-5f, m->h16, prec == PGMI_PREC_F16X3 ? 1 : 2, s);
+    int rc = linear(m, m->h, m->h16, m->hd_w, m->hd16, m->hd_b, nullptr, m->g, nullptr, R, D, D, EPI_GELU);
     if (rc) return rc;
     launch_layernorm(m->g, m->hln_w, m->hln_b, R, D, 1e-5f, m->g, s);
     return PGMI_OK;

@@ -96,22 +96,23 @@ int run_decoder(pgmi_model* m, int B, int T, const AttRagged* rg, int rows, doub
     const double ln_bytes = 2.0 * M * D * 4;
     auto mlp = [&](const Layer& L) {                                  // x += fc_out(act(fc_in(h16)))
         { ProfScope p(m, PGMI_K_GEMM_FC1, 2.0 * M * F * D, 0);
-          int rc = linear(m, nullptr, m->h16, m->h16_plane, nullptr, L.w116, L.b1, nullptr, nullptr, m->g16, m->g16_plane, M, F, D, m->fc1_epi);
+          int rc = linear(m, nullptr, m->h16, nullptr, L.w116, L.b1, nullptr, nullptr, m->g16, M, F, D, m->fc1_epi);
           if (rc) return rc; }
         ProfScope p(m, PGMI_K_GEMM_FC2, 2.0 * M * F * D, 0);
-        return linear(m, nullptr, m->g16, m->g16_plane, nullptr, L.w216, L.b2, m->x, m->x, nullptr, 0, M, D, F, EPI_NONE);
+        return linear(m, nullptr, m->g16, nullptr, L.w216, L.b2, m->x, m->x, nullptr, M, D, F, EPI_NONE);
     };
     for (int l = 0; l < c.layers; ++l) {
         const Layer& L = m->layers[l];
         { ProfScope p(m, PGMI_K_LAYERNORM, 0, ln_bytes);
-          launch_layernorm16(m->x, L.ln1_w, L.ln1_b, M, D, m->ln_eps, m->h16, m->h16_plane, 1, s); }
+          launch_layernorm16(m->x, L.ln1_w, L.ln1_b, M, D, m->ln_eps, m->h16, 1, s); }
         { ProfScope p(m, PGMI_K_GEMM_QKV, 2.0 * M * 3 * Da * D, 0);
           if (L.conv)                           // fp32 q | k | v rows: the attention's prep pass convolves and splits them
-              rc = linear(m, nullptr, m->h16, m->h16_plane, nullptr, L.wqkv16, L.bqkv, nullptr, m->qkv, nullptr, 0, M, 3 * Da, D, EPI_NONE);
-          else
-              rc = launch_gemm16_qkv(m->h16, m->h16_plane, L.wqkv16.p, L.wqkv16.plane, L.bqkv, M, Da, D, L.wqkv16.out_scale,
-                                     m->qk16, m->qk16_plane, m->vt16, m->vt16_plane, m->rot_cos, m->rot_sin, rotary, T, m->Hs,
-                                     m->gemm_variant, s, m->rot_halves, false);
+              rc = linear(m, nullptr, m->h16, nullptr, L.wqkv16, L.bqkv, nullptr, m->qkv, nullptr, M, 3 * Da, D, EPI_NONE);
+          else {
+              GemmLaunch g = qkv_launch(m, L.wqkv16, L.bqkv, M, Da, D, T, m->Hs);
+              g.qkv.cos_t = m->rot_cos; g.qkv.sin_t = m->rot_sin; g.qkv.rotary = rotary; g.qkv.rot_halves = m->rot_halves;
+              rc = launch_gemm16(g);
+          }
           if (rc) return rc; }
         if (m->parallel_residual) {             // the MLP branch first: it reads ln_1's output, which the context rows then overwrite
             rc = mlp(L);
@@ -128,11 +129,11 @@ int run_decoder(pgmi_model* m, int B, int T, const AttRagged* rg, int rows, doub
           rc = rg ? launch_attention_tr_ragged(a, *rg) : launch_attention_f16x3_v2(a);
           if (rc) return rc; }
         { ProfScope p(m, PGMI_K_GEMM_OUT, 2.0 * M * D * Da, 0);
-          rc = linear(m, nullptr, m->h16, m->h16_plane, nullptr, L.wo16, L.bo, m->x, m->x, nullptr, 0, M, D, Da, EPI_NONE);
+          rc = linear(m, nullptr, m->h16, nullptr, L.wo16, L.bo, m->x, m->x, nullptr, M, D, Da, EPI_NONE);
           if (rc) return rc; }
         if (!m->parallel_residual) {
             { ProfScope p(m, PGMI_K_LAYERNORM, 0, ln_bytes);
-              launch_layernorm16(m->x, L.ln2_w, L.ln2_b, M, D, m->ln_eps, m->h16, m->h16_plane, 1, s); }
+              launch_layernorm16(m->x, L.ln2_w, L.ln2_b, M, D, m->ln_eps, m->h16, 1, s); }
             rc = mlp(L);
             if (rc) return rc;
         }
@@ -158,8 +159,8 @@ static int wide_head_rows(pgmi_model* m, int R, const int32_t* tgt, float* out, 
     for (int r0 = 0; r0 < R; r0 += m->gpt_head_rows) {
         const int rc_rows = std::min(m->gpt_head_rows, R - r0);
         { ProfScope p(m, PGMI_K_HEAD, 2.0 * rc_rows * Vp * D, 0);
-          int rc = linear(m, nullptr, m->h16 + (size_t)r0 * 2 * D, m->h16_plane, nullptr, m->gpt_head16, m->zeros, nullptr,
-                          m->gpt_logits, nullptr, 0, rc_rows, Vp, D, EPI_NONE);
+          int rc = linear(m, nullptr, m->h16 + (size_t)r0 * 2 * D, nullptr, m->gpt_head16, m->zeros, nullptr,
+                          m->gpt_logits, nullptr, rc_rows, Vp, D, EPI_NONE);
           if (rc) return rc; }
         { ProfScope p(m, PGMI_K_SCORE, 0, (double)rc_rows * V * 4 * (tgt ? 1 : 3));
           launch_wide_logsoftmax(m->gpt_logits, Vp, rc_rows, V, tgt ? tgt + r0 : nullptr, tgt ? out + r0 : m->lp, m->nonfinite, m->stream); }
@@ -203,7 +204,7 @@ int decoder_token_logprobs(pgmi_model* m, int arch, const int32_t* tokens, int B
         float* dst = out + (size_t)b0 * T * V;
         if (wide_head(c)) {
             { ProfScope p(m, PGMI_K_LAYERNORM, 0, 2.0 * M * D * 4);
-              launch_layernorm16(m->x, m->lna_w, m->lna_b, M, D, m->ln_eps, m->h16, m->h16_plane, 1, s); }
+              launch_layernorm16(m->x, m->lna_w, m->lna_b, M, D, m->ln_eps, m->h16, 1, s); }
             return wide_head_rows(m, M, nullptr, nullptr, dst);
         }
         rc = narrow_head(m, M);
@@ -270,7 +271,7 @@ int pgmi_gpt_sequence_loglik(pgmi_model* m, const int32_t* tokens, const int32_t
           launch_gather_rows(m->x, m->row_idx, R, D, m->g, s); }                 // pad rows and last rows never reach the head
         if (wide_head(c)) {
             { ProfScope p(m, PGMI_K_LAYERNORM, 0, 2.0 * R * D * 4);
-              launch_layernorm16(m->g, m->lna_w, m->lna_b, R, D, m->ln_eps, m->h16, m->h16_plane, 1, s); }
+              launch_layernorm16(m->g, m->lna_w, m->lna_b, R, D, m->ln_eps, m->h16, 1, s); }
             rc = wide_head_rows(m, R, m->aux_i, m->denom, nullptr);
             if (rc) return rc;
         } else {

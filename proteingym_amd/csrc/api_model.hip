@@ -141,21 +141,37 @@ int make_w16(std::vector<void*>& pool, const float* host, size_t n, size_t K, in
     }
     hipFree(tmp);
     if (e != hipSuccess) { set_error("weight split failed: %s", hipGetErrorString(e)); return PGMI_EHIP; }
-    out->plane = n;
     out->out_scale = 1.0f / scale;
     return PGMI_OK;
 }
 
 // y = epi(in W^T + b) (+ residual).  fp32 mode: in32 -> fp32 out.  16-bit modes: in16 planes ->
 // either fp32 out (out32) or 16-bit planes (out16).
-int linear(pgmi_model* m, const float* in32, const unsigned short* in16, size_t in_plane, const float* W32,
-           const W16& w16, const float* bias, const float* residual, float* out32, unsigned short* out16,
-           size_t out_plane, int M, int N, int K, int epi) {
+int linear(pgmi_model* m, const float* in32, const unsigned short* in16, const float* W32, const W16& w16, const float* bias,
+           const float* residual, float* out32, unsigned short* out16, int M, int N, int K, int epi) {
     if (m->cfg.precision == PGMI_PREC_FP32)
         return launch_gemm_f32(in32, W32, bias, residual, out32, M, N, K, epi, m->stream);
-    const bool bf = m->cfg.precision == PGMI_PREC_BF16;
-    return launch_gemm16(in16, in_plane, w16.p, w16.plane, bias, residual, out32, out16, out_plane, M, N, K, epi,
-                         w16.out_scale, bf ? 1 : 2, bf, m->gemm_variant, m->stream);
+    GemmLaunch g;
+    g.A = in16; g.W = w16.p; g.out_scale = w16.out_scale;
+    g.bias = bias; g.residual = residual;
+    g.out32 = out32; g.out16 = out16;
+    g.M = M; g.N = N; g.K = K;
+    g.epilogue = epi; g.bf = m->cfg.precision == PGMI_PREC_BF16; g.variant = m->gemm_variant; g.stream = m->stream;
+    return launch_gemm16(g);
+}
+
+// The fused QKV projection of m->h16 (M rows, sequences of T) into the attention operands m->qk16 / m->vt16: f16x3, no rotary; the
+// caller sets what differs (bf, the rotary tables).  Da = H * 64 attention lanes.
+GemmLaunch qkv_launch(pgmi_model* m, const W16& w16, const float* bias, int M, int Da, int K, int T, int H) {
+    GemmLaunch g;
+    g.A = m->h16; g.W = w16.p; g.out_scale = w16.out_scale;
+    g.bias = bias;
+    g.out16 = m->qk16;
+    g.M = M; g.N = 3 * Da; g.K = K;
+    g.variant = m->gemm_variant; g.stream = m->stream;
+    g.qkv.vt16 = m->vt16; g.qkv.vt_plane = m->vt16_plane; g.qkv.qk_plane = m->qk16_plane;
+    g.qkv.T = T; g.qkv.H = H;
+    return g;
 }
 
 // fp16 range check for the 16-bit modes: the vocabulary kernel raises the flag when a computed
@@ -333,7 +349,7 @@ int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int 
     if (rc) { pgmi_model_destroy(m); return rc; }
     m->keep_rows = env_int("PGMI_KEEP_ROWS", 1);
     gemm_options_from_env();                             // the GEMM launchers' test hooks: read here, not per launch
-    m->gemm_variant = env_int("PGMI_GEMM_VARIANT", 0);   // tuning only (gemm_f16.hip set_tune); below 1000 = the product configuration
+    m->gemm_variant = env_int("PGMI_GEMM_VARIANT", 0);   // tuning only (gemm_f16.hip gemm_group_m); below 1000 = the product configuration
     *out = m;
     return PGMI_OK;
 }

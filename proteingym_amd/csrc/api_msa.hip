@@ -101,9 +101,9 @@ int run_msa(pgmi_model* m, int R, int C, int keep_col, bool* compacted) {
         const Layer& L = m->layers[l];
         // ---- tied row attention (axial_attention.py:108-168) ----
         { ProfScope p(m, PGMI_K_LAYERNORM, 0, ln_bytes);
-          launch_layernorm16(m->x, L.ln1_w, L.ln1_b, M, D, 1e-5f, m->h16, m->h16_plane, 1, s); }
+          launch_layernorm16(m->x, L.ln1_w, L.ln1_b, M, D, 1e-5f, m->h16, 1, s); }
         { ProfScope p(m, PGMI_K_GEMM_QKV, 2.0 * M * 3 * D * D, 0);
-          rc = linear(m, nullptr, m->h16, m->h16_plane, nullptr, L.wqkv16, L.bqkv, nullptr, m->qkv, nullptr, 0, M, 3 * D, D, EPI_NONE);
+          rc = linear(m, nullptr, m->h16, nullptr, L.wqkv16, L.bqkv, nullptr, m->qkv, nullptr, M, 3 * D, D, EPI_NONE);
           if (rc) return rc; }
         { ProfScope p(m, PGMI_K_ATTENTION, 4.0 * (double)C * C * R * D, 0);
           // q -> m->h16 (free once the projection has read it; the context rows overwrite it there), k -> m->g16
@@ -120,52 +120,50 @@ int run_msa(pgmi_model* m, int R, int C, int keep_col, bool* compacted) {
             launch_strided_index(keep_col, C, R, m->row_idx, s);
             launch_gather_rows(m->x, m->row_idx, R, D, m->qkv, s);                                     // residual rows
             launch_gather_rows(reinterpret_cast<const float*>(m->h16), m->row_idx, R, D, reinterpret_cast<float*>(m->g16), s);   // context rows (K-interleaved: 4 D bytes)
-            rc = linear(m, nullptr, m->g16, m->g16_plane, nullptr, L.wo16, L.bo, m->qkv, m->xt, nullptr, 0, R, D, D, EPI_NONE);
+            rc = linear(m, nullptr, m->g16, nullptr, L.wo16, L.bo, m->qkv, m->xt, nullptr, R, D, D, EPI_NONE);
             if (rc) return rc;
             // column attention of this one column: a sequence of R rows (m->xt rows 0 .. R-1)
-            launch_layernorm16(m->xt, L.c_ln_w, L.c_ln_b, R, D, 1e-5f, m->h16, m->h16_plane, 1, s);
-            rc = launch_gemm16_qkv(m->h16, m->h16_plane, L.c_wqkv16.p, L.c_wqkv16.plane, L.c_bqkv, R, D, D, L.c_wqkv16.out_scale,
-                                   m->qk16, m->qk16_plane, m->vt16, m->vt16_plane, nullptr, nullptr, 0, R, H, m->gemm_variant, s);
+            launch_layernorm16(m->xt, L.c_ln_w, L.c_ln_b, R, D, 1e-5f, m->h16, 1, s);
+            rc = launch_gemm16(qkv_launch(m, L.c_wqkv16, L.c_bqkv, R, D, D, R, H));
             if (rc) return rc;
             rc = launch_attention_f16x3_v2(column_attention(1));
             if (rc) return rc;
-            rc = linear(m, nullptr, m->h16, m->h16_plane, nullptr, L.c_wo16, L.c_bo, m->xt, m->xt, nullptr, 0, R, D, D, EPI_NONE);
+            rc = linear(m, nullptr, m->h16, nullptr, L.c_wo16, L.c_bo, m->xt, m->xt, nullptr, R, D, D, EPI_NONE);
             if (rc) return rc;
             // feed-forward for token (0, keep_col) = row 0 of the column
-            launch_layernorm16(m->xt, L.ln2_w, L.ln2_b, 1, D, 1e-5f, m->h16, m->h16_plane, 1, s);
-            rc = linear(m, nullptr, m->h16, m->h16_plane, nullptr, L.w116, L.b1, nullptr, nullptr, m->g16, m->g16_plane, 1, F, D, EPI_GELU);
+            launch_layernorm16(m->xt, L.ln2_w, L.ln2_b, 1, D, 1e-5f, m->h16, 1, s);
+            rc = linear(m, nullptr, m->h16, nullptr, L.w116, L.b1, nullptr, nullptr, m->g16, 1, F, D, EPI_GELU);
             if (rc) return rc;
-            rc = linear(m, nullptr, m->g16, m->g16_plane, nullptr, L.w216, L.b2, m->xt, m->x, nullptr, 0, 1, D, F, EPI_NONE);
+            rc = linear(m, nullptr, m->g16, nullptr, L.w216, L.b2, m->xt, m->x, nullptr, 1, D, F, EPI_NONE);
             if (rc) return rc;
             if (compacted) *compacted = true;
             break;
         }
         { ProfScope p(m, PGMI_K_GEMM_OUT, 2.0 * M * D * D, 0);
-          rc = linear(m, nullptr, m->h16, m->h16_plane, nullptr, L.wo16, L.bo, m->x, m->x, nullptr, 0, M, D, D, EPI_NONE);
+          rc = linear(m, nullptr, m->h16, nullptr, L.wo16, L.bo, m->x, m->x, nullptr, M, D, D, EPI_NONE);
           if (rc) return rc; }
         // ---- column attention (axial_attention.py:232-275): ordinary attention over the R rows of a column ----
         { ProfScope p(m, PGMI_K_LAYERNORM, 0, 2 * ln_bytes);
           launch_permute_rows(m->x, m->xt, R, C, D, s);                       // -> token order (c, r)
-          launch_layernorm16(m->xt, L.c_ln_w, L.c_ln_b, M, D, 1e-5f, m->h16, m->h16_plane, 1, s); }
+          launch_layernorm16(m->xt, L.c_ln_w, L.c_ln_b, M, D, 1e-5f, m->h16, 1, s); }
         { ProfScope p(m, PGMI_K_GEMM_QKV, 2.0 * M * 3 * D * D, 0);
-          rc = launch_gemm16_qkv(m->h16, m->h16_plane, L.c_wqkv16.p, L.c_wqkv16.plane, L.c_bqkv, M, D, D, L.c_wqkv16.out_scale,
-                                 m->qk16, m->qk16_plane, m->vt16, m->vt16_plane, nullptr, nullptr, 0, R, H, m->gemm_variant, s);
+          rc = launch_gemm16(qkv_launch(m, L.c_wqkv16, L.c_bqkv, M, D, D, R, H));
           if (rc) return rc; }
         { ProfScope p(m, PGMI_K_ATTENTION, 4.0 * (double)M * R * D, 0);
           rc = launch_attention_f16x3_v2(column_attention(C));
           if (rc) return rc; }
         { ProfScope p(m, PGMI_K_GEMM_OUT, 2.0 * M * D * D, 0);
-          rc = linear(m, nullptr, m->h16, m->h16_plane, nullptr, L.c_wo16, L.c_bo, m->xt, m->xt, nullptr, 0, M, D, D, EPI_NONE);
+          rc = linear(m, nullptr, m->h16, nullptr, L.c_wo16, L.c_bo, m->xt, m->xt, nullptr, M, D, D, EPI_NONE);
           if (rc) return rc; }
         { ProfScope p(m, PGMI_K_LAYERNORM, 0, 2 * ln_bytes);
           launch_permute_rows(m->xt, m->x, C, R, D, s);                       // back to (r, c)
-          launch_layernorm16(m->x, L.ln2_w, L.ln2_b, M, D, 1e-5f, m->h16, m->h16_plane, 1, s); }
+          launch_layernorm16(m->x, L.ln2_w, L.ln2_b, M, D, 1e-5f, m->h16, 1, s); }
         // ---- feed forward (modules.py:409-432) ----
         { ProfScope p(m, PGMI_K_GEMM_FC1, 2.0 * M * F * D, 0);
-          rc = linear(m, nullptr, m->h16, m->h16_plane, nullptr, L.w116, L.b1, nullptr, nullptr, m->g16, m->g16_plane, M, F, D, EPI_GELU);
+          rc = linear(m, nullptr, m->h16, nullptr, L.w116, L.b1, nullptr, nullptr, m->g16, M, F, D, EPI_GELU);
           if (rc) return rc; }
         { ProfScope p(m, PGMI_K_GEMM_FC2, 2.0 * M * F * D, 0);
-          rc = linear(m, nullptr, m->g16, m->g16_plane, nullptr, L.w216, L.b2, m->x, m->x, nullptr, 0, M, D, F, EPI_NONE);
+          rc = linear(m, nullptr, m->g16, nullptr, L.w216, L.b2, m->x, m->x, nullptr, M, D, F, EPI_NONE);
           if (rc) return rc; }
     }
     PGMI_HIP(hipGetLastError());

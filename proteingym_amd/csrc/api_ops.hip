@@ -30,6 +30,16 @@ int pgmi_op_layernorm(int device, const float* x, const float* w, const float* b
     return PGMI_OK;
 }
 
+// The op entries' GEMMs on their own buffers: f16x3, no epilogue, no output yet -- the caller sets what differs
+static GemmLaunch op_gemm(const unsigned short* a16, const W16& w16, const float* bias, int M, int N, int K, int variant) {
+    GemmLaunch g;
+    g.A = a16; g.W = w16.p; g.out_scale = w16.out_scale;
+    g.bias = bias;
+    g.M = M; g.N = N; g.K = K;
+    g.variant = variant;
+    return g;
+}
+
 int pgmi_op_gemm(int device, int precision, const float* A, const float* W, const float* bias, const float* residual,
                  int M, int N, int K, int epilogue, float* C) {
     if (!A || !W || !C || M <= 0 || N <= 0 || K <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
@@ -74,13 +84,15 @@ int pgmi_op_gemm(int device, int precision, const float* A, const float* W, cons
         if (!rc) rc = dev_alloc(pool, &a16, (size_t)M * K * planes);
         if (!rc) {
             launch_split16(dA, (int64_t)M * K, 1.0f, bf ? 1 : 2, K, a16, nullptr);
+            GemmLaunch g = op_gemm(a16, w16, dB, M, N, K, env_int("PGMI_GEMM_VARIANT", 0));
+            g.epilogue = epi; g.bf = bf;
             if (split_planes) {
                 // the split-plane epilogue (the next GEMM's operand): run it, then rebuild fp32 = hi + lo 2^-11 from the K-interleaved planes
                 unsigned short* c16 = nullptr;
                 const int No = epi == EPI_SWIGLU ? N / 2 : N;              // output columns
                 rc = dev_alloc(pool, &c16, (size_t)M * N * 2);
-                if (!rc) rc = launch_gemm16(a16, (size_t)M * K, w16.p, w16.plane, dB, nullptr, nullptr, c16, (size_t)M * No, M, N, K, epi,
-                                            w16.out_scale, planes, bf, env_int("PGMI_GEMM_VARIANT", 0), nullptr);
+                g.out16 = c16;
+                if (!rc) rc = launch_gemm16(g);
                 if (!rc) {
                     std::vector<unsigned short> h((size_t)M * N * 2);
                     hipError_t e2 = hipMemcpy(h.data(), c16, h.size() * 2, hipMemcpyDeviceToHost);
@@ -99,8 +111,8 @@ int pgmi_op_gemm(int device, int precision, const float* A, const float* W, cons
                 for (void* p : pool) hipFree(p);
                 return rc;
             }
-            rc = launch_gemm16(a16, (size_t)M * K, w16.p, w16.plane, dB, dR, dC, nullptr, 0, M, N, K, epi,
-                               w16.out_scale, planes, bf, env_int("PGMI_GEMM_VARIANT", 0), nullptr);
+            g.residual = dR; g.out32 = dC;
+            rc = launch_gemm16(g);
         }
     }
     hipError_t e = hipMemcpy(C, dC, (size_t)M * N * 4, hipMemcpyDeviceToHost);
@@ -160,12 +172,17 @@ int pgmi_bench_gemm_ab(int device, int precision, int M, int N, int K, int epilo
     }
     auto run = [&](int var) -> int {
         if (f32) return launch_gemm_f32(dA, dW, dB, split_out == 2 ? dC : nullptr, dC, M, N, K, epilogue, nullptr);
-        if (fused_qkv)
-            return launch_gemm16_qkv(a16, (size_t)M * K, w16.p, w16.plane, dB, M, N / 3, K, w16.out_scale, qk16, qk_plane, vt16, vt_plane,
-                                     nullptr, nullptr, 0, Tq, N / 3 / kHeadDim, var, nullptr);
-        const bool planes_out = split_out == 1;
-        return launch_gemm16(a16, (size_t)M * K, w16.p, w16.plane, dB, split_out == 2 ? dC : nullptr, planes_out ? nullptr : dC,
-                             planes_out ? c16 : nullptr, (size_t)M * N, M, N, K, epilogue, w16.out_scale, planes, bf, var, nullptr);
+        GemmLaunch g = op_gemm(a16, w16, dB, M, N, K, var);
+        if (fused_qkv) {
+            g.out16 = qk16;
+            g.qkv.vt16 = vt16; g.qkv.vt_plane = vt_plane; g.qkv.qk_plane = qk_plane;
+            g.qkv.T = Tq; g.qkv.H = N / 3 / kHeadDim;
+            return launch_gemm16(g);
+        }
+        g.epilogue = epilogue; g.bf = bf;
+        if (split_out == 2) g.residual = dC;
+        if (split_out == 1) g.out16 = c16; else g.out32 = dC;
+        return launch_gemm16(g);
     };
     std::vector<std::vector<double>> samples(n_variants);
     for (int v = 0; v < n_variants && !rc; ++v) rc = run(variants[v] >= 0 ? variants[v] : env_int("PGMI_GEMM_VARIANT", 0));   // warm-up
@@ -339,8 +356,12 @@ int pgmi_op_causal_attention(int device, int lanes, const float* X, const float*
         rc = make_w16(pool, W, 3 * Da * K, (size_t)K, PGMI_PREC_F16X3, nullptr, &w16);
         if (!rc) {
             launch_split16(dx, (int64_t)(M * K), 1.0f, 2, K, a16, nullptr);
-            rc = launch_gemm16_qkv(a16, M * K, w16.p, w16.plane, db, (int)M, (int)Da, K, w16.out_scale, qk16, qk_plane, vt16, vt_plane,
-                                   dcos, dsin, rotary, T, (int)Hs, env_int("PGMI_GEMM_VARIANT", 0), nullptr, halves, false);
+            GemmLaunch g = op_gemm(a16, w16, db, (int)M, 3 * (int)Da, K, env_int("PGMI_GEMM_VARIANT", 0));
+            g.out16 = qk16;
+            g.qkv.vt16 = vt16; g.qkv.vt_plane = vt_plane; g.qkv.qk_plane = qk_plane;
+            g.qkv.cos_t = dcos; g.qkv.sin_t = dsin; g.qkv.rotary = rotary;
+            g.qkv.T = T; g.qkv.H = (int)Hs; g.qkv.rot_halves = halves;
+            rc = launch_gemm16(g);
         }
     }
     AttLaunch a;
@@ -454,8 +475,11 @@ int pgmi_op_column_attention(int device, const float* X, const float* W, const f
     rc = make_w16(pool, W, 3 * D * K, (size_t)K, PGMI_PREC_F16X3, nullptr, &w16);
     if (!rc) {
         launch_split16(dx, (int64_t)(M * K), 1.0f, 2, K, a16, nullptr);
-        rc = launch_gemm16_qkv(a16, M * K, w16.p, w16.plane, db, (int)M, (int)D, K, w16.out_scale, qk16, qk_plane, vt16, vt_plane,
-                               nullptr, nullptr, 0, R, H, env_int("PGMI_GEMM_VARIANT", 0), nullptr);
+        GemmLaunch g = op_gemm(a16, w16, db, (int)M, 3 * (int)D, K, env_int("PGMI_GEMM_VARIANT", 0));
+        g.out16 = qk16;
+        g.qkv.vt16 = vt16; g.qkv.vt_plane = vt_plane; g.qkv.qk_plane = qk_plane;
+        g.qkv.T = R; g.qkv.H = H;
+        rc = launch_gemm16(g);
     }
     AttLaunch a;
     a.qk16 = qk16, a.qk_plane = qk_plane, a.vt16 = vt16, a.vt_plane = vt_plane;

@@ -75,7 +75,7 @@ void launch_strided_index(int first, int stride, int n, int32_t* idx, hipStream_
 void launch_vocab_logsoftmax(const float* h, const float* E, const float* bias, int rows, int D,
                              int V, float* out, int32_t* nonfinite, hipStream_t s);
 void launch_layernorm16(const float* x, const float* w, const float* b, int rows, int D, float eps,
-                        unsigned short* y16, size_t plane, int mode, hipStream_t s);
+                        unsigned short* y16, int mode, hipStream_t s);
 void launch_scatter_rows(const float* src, const int32_t* dst_row, int n, int V, float* table,
                          hipStream_t s);
 void launch_row_index(const int32_t* mask_rel, int B, int T, int32_t* out, hipStream_t s);
@@ -197,18 +197,37 @@ int launch_gemm_f32(const float* A, const float* W, const float* bias, const flo
 // ---- gemm_f16.hip ------------------------------------------------------------------------
 void gemm_options_from_env();                      // PGMI_GEMM_HALF_TAIL / PGMI_GEMM_MAX_ROWS (test hooks): at model creation, never per launch
 int gemm_set_option(const char* name, long long value);
-// 16-bit-plane GEMM: C = epi(A W^T * out_scale + bias) (+ residual).  A/W: `planes` planes of
-// fp16 (hi, lo) or one bf16 plane, K-contiguous rows.  Exactly one of Cf (fp32) / Ch (planes).
-int launch_gemm16(const unsigned short* A, size_t a_plane, const unsigned short* W, size_t w_plane,
-                  const float* bias, const float* residual, float* Cf, unsigned short* Ch, size_t c_plane,
-                  int M, int N, int K, int epilogue, float out_scale, int planes, bool bf, int variant,
-                  hipStream_t s);
-// H = number of 64-lane slot groups per token (= heads, or 2 x heads for head_dim 128); rot_halves = rotary table rows per
-// token (1, or 2 for head_dim 128: slot group parity selects the frequencies)
-int launch_gemm16_qkv(const unsigned short* A, size_t a_plane, const unsigned short* W, size_t w_plane,
-                      const float* bias, int M, int D, int K, float out_scale, unsigned short* qk16, size_t qk_plane,
-                      unsigned short* vt16, size_t vt_plane, const float* cos_t, const float* sin_t, int rotary,
-                      int T, int H, int variant, hipStream_t s, int rot_halves = 1, bool bf = false);
+// The 16-bit GEMM: C = epi(A W^T * out_scale + bias) (+ residual) on the persistent kernel (gemm16x_kernel.h).  f16x3 (bf = false):
+// A / W are fp16 hi | lo halfs in K-interleaved rows (ki_off), K % 32 == 0; bf16 (bf = true): one row-major plane each, K % 64 == 0,
+// out_scale 1.  One launch, fields assigned by name; what a caller does not need keeps its default.
+struct GemmLaunch {
+    const unsigned short* A = nullptr;  // activations [M][K]
+    const unsigned short* W = nullptr;  // weight [N][K] (model.h W16::p)
+    float out_scale = 1.0f;             // W16::out_scale
+    const float* bias = nullptr;        // [N]
+    const float* residual = nullptr;    // fp32 [M][N]; may be out32 (in place)
+    // exactly one output: fp32 rows [M][N], or the next GEMM's 16-bit operand (f16x3: K-interleaved split rows, N % 32 == 0 -- with
+    // EPI_SWIGLU N / 2 columns wide, N % 64 == 0, no residual; bf16: one plane [M][N])
+    float* out32 = nullptr;
+    unsigned short* out16 = nullptr;
+    int M = 0, N = 0, K = 0;
+    int epilogue = EPI_NONE;
+    bool bf = false;
+    int variant = 0;                    // PGMI_GEMM_VARIANT (tuning, bit-neutral): gemm_f16.hip gemm_group_m
+    hipStream_t stream = nullptr;
+    // The fused QKV projection (vt16 != nullptr): N = 3 D, D % 64 == 0, M % T == 0; out16 takes the q | k rows [M][2 D] as two planes
+    // qk_plane halfs apart and vt16 the transposed, key-permuted V planes -- the attention kernels' operands (AttLaunch) instead of an
+    // fp32 [M][3 D] tensor; rotary applied to q, k if set.  H = 64-lane slot groups per token (heads, or 2 x heads for head_dim 128);
+    // rot_halves = rotary table rows per token (1, or 2 for head_dim 128: the slot group's parity selects the frequencies).
+    struct Qkv {
+        unsigned short* vt16 = nullptr;
+        size_t vt_plane = 0, qk_plane = 0;
+        const float* cos_t = nullptr;
+        const float* sin_t = nullptr;
+        int rotary = 0, T = 0, H = 0, rot_halves = 1;
+    } qkv;
+};
+int launch_gemm16(const GemmLaunch& g);
 struct XMap;                                       // gemm16x_kernel.h: batched / strided operand and output maps
 int launch_gemm16_ex(const unsigned short* A, const unsigned short* W, float* Cf, unsigned short* Ch, int M, int N, int K,
                      float out_scale, XMap xm, int nbatch, hipStream_t s);

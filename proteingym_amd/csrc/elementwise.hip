@@ -145,13 +145,12 @@ void launch_zero_pad_rows(const int32_t* tokens, int rows, int D, float* x, hipS
 // ---- LayerNorm (torch.nn.LayerNorm, modules.py:80-81): biased variance, eps inside sqrt ----
 // One wave per row, the row held in registers (D <= 64*4*NV), two-pass mean / variance.
 // Algorithmic bytes: 2*D*4 per row (read + write); HBM-bound.
-// OUTMODE 0: fp32 y;  1: fp16 hi/lo, K-interleaved (f16x3 GEMM operand; `plane` unused);  2: bf16 plane
+// OUTMODE 0: fp32 y;  1: fp16 hi/lo, K-interleaved (f16x3 GEMM operand);  2: bf16 plane
 template <int NV, int OUTMODE>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* x,   // may alias y (in place)
                                                         const float* __restrict__ w,
                                                         const float* __restrict__ bsh, int rows, int D,
-                                                        float eps, float* y, unsigned short* y16,
-                                                        size_t plane) {
+                                                        float eps, float* y, unsigned short* y16) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= rows) return;
@@ -233,24 +232,24 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* x,   // may
 }
 template <int OUTMODE>
 static void launch_ln_mode(const float* x, const float* w, const float* b, int rows, int D, float eps,
-                           float* y, unsigned short* y16, size_t plane, hipStream_t s) {
+                           float* y, unsigned short* y16, hipStream_t s) {
     const dim3 grid((rows + 3) / 4), block(256);
     const int nv = (D / 4 + 63) / 64;
-    if (nv <= 1) hipLaunchKernelGGL((layernorm_kernel<1, OUTMODE>), grid, block, 0, s, x, w, b, rows, D, eps, y, y16, plane);
-    else if (nv <= 2) hipLaunchKernelGGL((layernorm_kernel<2, OUTMODE>), grid, block, 0, s, x, w, b, rows, D, eps, y, y16, plane);
-    else if (nv <= 5) hipLaunchKernelGGL((layernorm_kernel<5, OUTMODE>), grid, block, 0, s, x, w, b, rows, D, eps, y, y16, plane);
-    else if (nv <= 10) hipLaunchKernelGGL((layernorm_kernel<10, OUTMODE>), grid, block, 0, s, x, w, b, rows, D, eps, y, y16, plane);
-    else hipLaunchKernelGGL((layernorm_kernel<20, OUTMODE>), grid, block, 0, s, x, w, b, rows, D, eps, y, y16, plane);
+    if (nv <= 1) hipLaunchKernelGGL((layernorm_kernel<1, OUTMODE>), grid, block, 0, s, x, w, b, rows, D, eps, y, y16);
+    else if (nv <= 2) hipLaunchKernelGGL((layernorm_kernel<2, OUTMODE>), grid, block, 0, s, x, w, b, rows, D, eps, y, y16);
+    else if (nv <= 5) hipLaunchKernelGGL((layernorm_kernel<5, OUTMODE>), grid, block, 0, s, x, w, b, rows, D, eps, y, y16);
+    else if (nv <= 10) hipLaunchKernelGGL((layernorm_kernel<10, OUTMODE>), grid, block, 0, s, x, w, b, rows, D, eps, y, y16);
+    else hipLaunchKernelGGL((layernorm_kernel<20, OUTMODE>), grid, block, 0, s, x, w, b, rows, D, eps, y, y16);
 }
 void launch_layernorm(const float* x, const float* w, const float* b, int rows, int D, float eps,
                       float* y, hipStream_t s) {
-    launch_ln_mode<0>(x, w, b, rows, D, eps, y, nullptr, 0, s);
+    launch_ln_mode<0>(x, w, b, rows, D, eps, y, nullptr, s);
 }
 // mode 1: fp16 hi/lo planes, mode 2: bf16
 void launch_layernorm16(const float* x, const float* w, const float* b, int rows, int D, float eps,
-                        unsigned short* y16, size_t plane, int mode, hipStream_t s) {
-    if (mode == 1) launch_ln_mode<1>(x, w, b, rows, D, eps, nullptr, y16, plane, s);
-    else launch_ln_mode<2>(x, w, b, rows, D, eps, nullptr, y16, plane, s);
+                        unsigned short* y16, int mode, hipStream_t s) {
+    if (mode == 1) launch_ln_mode<1>(x, w, b, rows, D, eps, nullptr, y16, s);
+    else launch_ln_mode<2>(x, w, b, rows, D, eps, nullptr, y16, s);
 }
 
 // ---- rotary (rotary_embedding.py:11-20,47-69): half-split rotation of q (already scaled) and k

@@ -15,200 +15,27 @@
 //
 // Operand layout in HBM ("K-interleaved planes", common.h ki_off): a row of K elements is stored as K/32 groups of
 // 128 bytes = 32 hi halfs followed by the 32 lo halfs of the same k.  One row's share of a 32-deep K tile is then ONE
-// full 128-byte line: 8 consecutive lanes fetch it with one dwordx4 each.  With two separate planes (round 1) the same
-// data was two 64-byte half lines, every line was requested twice (the other half one K tile later, long evicted from
-// the 32 KB L1) and the texture-address unit handled twice the lines: measured with the phase-timing instantiation,
+// full 128-byte line: 8 consecutive lanes fetch it with one dwordx4 each.  With two separate planes the same data was
+// two 64-byte half lines, every line was requested twice (the other half one K tile later, long evicted from the 32 KB
+// L1) and the texture-address unit handled twice the lines: measured with the phase-timing instantiation,
 // 288 -> 325 TFLOP/s on the FC2 shape from the access pattern alone.
 //
+// bf16: one row-major bf16 plane per operand, no scaling, one MFMA per product block, on the same kernel (gemm16x_kernel.h BF).
+//
+// Launch path: a caller fills a GemmLaunch (common.h) and calls launch_gemm16 -- argument checks, launch_gemm16x (row chunks under
+// the 32-bit offset range), launch_gemm16x_one (the TilePlan), launch_x (the instantiation table kGemmInst; set-attribute, launch,
+// error).  launch_gemm16_ex (the batched / strided form, XMap) makes its own TilePlan and ends in launch_x too.
+//
 // Roofline: MFMA-bound; peak 2.5 PFLOP/s of 16-bit MFMA = 833 TFLOP/s of fp32-equivalent algorithmic FLOPs in f16x3.
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
 #include <mutex>
-#include <type_traits>
-#include <vector>
 
 #include "common.h"
 #include "gemm16x_kernel.h"            // typedefs, gelu_erf16, QkvOut, TilePlan, gemm16x_kernel (the persistent ping-pong kernel)
 
 namespace pgmi {
-
-// ---- bf16 (throughput mode, NOT parity-gated): plain bf16 operands, one MFMA per product block ----------------------
-// Tiling (wave64): workgroup (WM*TM*32) x (WN*TN*32) x 32, WM*WN waves, each wave TM x TN MFMA tiles of 32x32
-// (v_mfma_f32_32x32x16_bf16).  Operands are swapped (MFMA "A" = weight rows, "B" = activation rows) so that the
-// accumulator puts 4 consecutive output columns in a lane: epilogue loads/stores are 8/16-byte vectors.  LDS tiles are
-// K-contiguous 64-byte rows with an XOR swizzle on the 16-byte chunk (conflict-free ds_read_b128), double buffered,
-// global -> VGPR -> LDS staging with the loads of tile t+1 in flight during the MFMAs of tile t; one barrier per K tile.
-// OUT: 0 = fp32 [M,N]; 1 = one bf16 plane [M,N].
-template <int WM, int WN, int TM, int TN, int EPI, int OUT>
-__global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(
-    const unsigned short* __restrict__ A, const unsigned short* __restrict__ W, const float* __restrict__ bias,
-    const float* residual, float* Cf, unsigned short* Ch, int M, int N, int K, int tiles_m, int tiles_n) {
-    constexpr int BK = 32, CPR = 4;
-    constexpr int NT = WM * WN * 64;
-    constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-    constexpr int A_CH = BM * CPR, W_CH = BN * CPR;
-    constexpr int A_LD = (A_CH + NT - 1) / NT, W_LD = (W_CH + NT - 1) / NT;
-    constexpr int STAGE = A_CH + W_CH;
-    extern __shared__ __attribute__((aligned(16))) u32x4 lds[];  // [2][STAGE]
-
-    // XCD-aware grouped tile order (see gemm_f32.hip)
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, q = nwg >> 3, r8 = nwg & 7;
-    const int wgid = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + (bid >> 3);
-    constexpr int GROUP_M = 8;
-    const int width = GROUP_M * tiles_n;
-    const int group = wgid / width, first_m = group * GROUP_M;
-    const int gsz = min(tiles_m - first_m, GROUP_M);
-    const int tm = first_m + (wgid % width) % gsz, tn = (wgid % width) / gsz;
-    const int m0 = tm * BM, n0 = tn * BN;
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave / WN, wn = wave % WN;
-    const int r = lane & 31, kh = lane >> 5;
-    auto swz = [](int row, int c) -> int { return c ^ ((row >> 2) & 3); };
-
-    const u32x4* a_src[A_LD];
-    const u32x4* w_src[W_LD];
-    int a_dst[A_LD], w_dst[W_LD];
-#pragma unroll
-    for (int i = 0; i < A_LD; ++i) {
-        const int f = tid + NT * i, row = (f % A_CH) / CPR, c = f % CPR;
-        a_src[i] = reinterpret_cast<const u32x4*>(A + (size_t)min(m0 + row, M - 1) * K) + c;
-        a_dst[i] = row * CPR + swz(row, c);
-    }
-#pragma unroll
-    for (int i = 0; i < W_LD; ++i) {
-        const int f = tid + NT * i, row = (f % W_CH) / CPR, c = f % CPR;
-        w_src[i] = reinterpret_cast<const u32x4*>(W + (size_t)min(n0 + row, N - 1) * K) + c;
-        w_dst[i] = A_CH + row * CPR + swz(row, c);
-    }
-    u32x4 a_st[A_LD], w_st[W_LD];
-    auto stage_load = [&](int kt) {
-#pragma unroll
-        for (int i = 0; i < A_LD; ++i)
-            if (A_CH % NT == 0 || tid + NT * i < A_CH) a_st[i] = a_src[i][kt * CPR];
-#pragma unroll
-        for (int i = 0; i < W_LD; ++i)
-            if (W_CH % NT == 0 || tid + NT * i < W_CH) w_st[i] = w_src[i][kt * CPR];
-    };
-    auto stage_store = [&](int buf) {
-        u32x4* base = lds + buf * STAGE;
-#pragma unroll
-        for (int i = 0; i < A_LD; ++i)
-            if (A_CH % NT == 0 || tid + NT * i < A_CH) base[a_dst[i]] = a_st[i];
-#pragma unroll
-        for (int i = 0; i < W_LD; ++i)
-            if (W_CH % NT == 0 || tid + NT * i < W_CH) base[w_dst[i]] = w_st[i];
-    };
-    stage_load(0);
-    stage_store(0);
-    __syncthreads();
-
-    f32x16 acc[TN][TM];
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) acc[j][i][v] = 0.0f;
-
-    const int nk = K / BK;
-    int cur = 0;
-    for (int kt = 0; kt < nk; ++kt) {
-        const bool more = kt + 1 < nk;
-        if (more) stage_load(kt + 1);
-        const u32x4* Ab = lds + cur * STAGE;
-        const u32x4* Wb = Ab + A_CH;
-#pragma unroll
-        for (int ks = 0; ks < BK / 16; ++ks) {
-            const int c = ks * 2 + kh;
-            u32x4 af[TM], wf[TN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) {
-                const int row = (wm * TM + i) * 32 + r;
-                af[i] = Ab[row * CPR + swz(row, c)];
-            }
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int row = (wn * TN + j) * 32 + r;
-                wf[j] = Wb[row * CPR + swz(row, c)];
-            }
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int i = 0; i < TM; ++i) acc[j][i] = mfma16<true>(wf[j], af[i], acc[j][i]);
-        }
-        if (more) stage_store(cur ^ 1);
-        __syncthreads();
-        cur ^= 1;
-    }
-    // ---- epilogue: lane holds column m = m_base + r of C^T, rows n = (v&3) + 8(v>>2) + 4kh ----
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-        const int m = m0 + (wm * TM + i) * 32 + r;
-        if (m >= M) continue;
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int n = n0 + (wn * TN + j) * 32 + 8 * g + 4 * kh;
-                if (n >= N) continue;                    // N % 4 == 0 is required by the launcher
-                const f32x4 bv = bias ? *reinterpret_cast<const f32x4*>(bias + n) : f32x4{0.f, 0.f, 0.f, 0.f};
-                f32x4 val;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) val[e] = acc[j][i][4 * g + e] + bv[e];
-                if (EPI == EPI_GELU) val = gelu_erf16(val);
-                if (EPI == EPI_GELU_TANH) val = gelu_tanh16(val);
-                if (EPI == EPI_SQRELU)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) { const float t = fmaxf(val[e], 0.0f); val[e] = t * t; }
-                const size_t o = (size_t)m * N + n;
-                if (residual) {
-                    const f32x4 rv = *reinterpret_cast<const f32x4*>(residual + o);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) val[e] = rv[e] + val[e];
-                }
-                if constexpr (OUT == 0) {
-                    *reinterpret_cast<f32x4*>(Cf + o) = val;
-                } else {
-                    u32x2 pk;
-                    pk[0] = f32_to_bf16_rne(val[0]) | ((unsigned)f32_to_bf16_rne(val[1]) << 16);
-                    pk[1] = f32_to_bf16_rne(val[2]) | ((unsigned)f32_to_bf16_rne(val[3]) << 16);
-                    *reinterpret_cast<u32x2*>(Ch + o) = pk;
-                }
-            }
-        }
-    }
-}
-
-template <int WM, int WN, int TM, int TN>
-static int launch_bf16_cfg(const unsigned short* A, const unsigned short* W, const float* bias, const float* residual, float* Cf,
-                           unsigned short* Ch, int M, int N, int K, int epilogue, hipStream_t s) {
-    constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-    constexpr size_t lds_bytes = (size_t)2 * (BM + BN) * 4 * 16;
-    const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
-    const dim3 grid(tiles_m * tiles_n), block(WM * WN * 64);
-#define PGMI_LAUNCH_BF16(EPI_, OUT_)                                                                     \
-    do {                                                                                                 \
-        auto kfn = gemm_bf16_kernel<WM, WN, TM, TN, EPI_, OUT_>;                                          \
-        if (lds_bytes > 65536) {                                                                         \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),                       \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); \
-            if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PGMI_EHIP; } \
-        }                                                                                                \
-        hipLaunchKernelGGL(kfn, grid, block, lds_bytes, s, A, W, bias, residual, Cf, Ch, M, N, K, tiles_m, tiles_n); \
-    } while (0)
-    const int out = Ch ? 1 : 0;
-    if (epilogue == EPI_GELU) { if (out) PGMI_LAUNCH_BF16(EPI_GELU, 1); else PGMI_LAUNCH_BF16(EPI_GELU, 0); }
-    else if (epilogue == EPI_SQRELU) { if (out) PGMI_LAUNCH_BF16(EPI_SQRELU, 1); else PGMI_LAUNCH_BF16(EPI_SQRELU, 0); }
-    else if (epilogue == EPI_GELU_TANH) { if (out) PGMI_LAUNCH_BF16(EPI_GELU_TANH, 1); else PGMI_LAUNCH_BF16(EPI_GELU_TANH, 0); }
-    else { if (out) PGMI_LAUNCH_BF16(EPI_NONE, 1); else PGMI_LAUNCH_BF16(EPI_NONE, 0); }
-#undef PGMI_LAUNCH_BF16
-    PGMI_HIP(hipGetLastError());
-    return PGMI_OK;
-}
 
 // Per-device launch state (a process may drive several devices through distinct model handles: nothing here is shared
 // between devices).  Indexed by the current HIP device of the calling thread; written under a mutex because two handles on two
@@ -268,24 +95,62 @@ int gemm_set_option(const char* name, long long value) {
     return PGMI_EINVAL;
 }
 
-// Launch parameters: variants >= 1000 of launch_gemm16 override the row panels per group for the interleaved A/B of
-// scripts/gemm_ab.py (tile order does not touch a row's arithmetic: same bits).
-struct GemmTune { int group_m = 0; };
-static thread_local GemmTune g_tune;
+// PGMI_GEMM_VARIANT (tuning; GemmLaunch::variant) -> the row panels per group of the grouped tile order; 0 = by shape.  Everything below
+// 1000 is the product's configuration; 1000 + t takes the low four bits of t (the interleaved A/B of scripts/gemm_ab.py).  Tile order
+// does not touch a row's arithmetic: same bits at every value.  No value is refused: 2000, which once selected the first bf16 kernel,
+// decodes like any other value of 1000 or above (1000 & 15 = 8 row panels).
+static int gemm_group_m(int variant) { return variant >= 1000 ? (variant - 1000) & 15 : 0; }
 
-static int launch_gemm16x_one(const unsigned short* A, const unsigned short* W,
-                              const float* bias, const float* residual, float* Cf, unsigned short* Ch, size_t c_plane,
-                              int M, int N, int K, int epilogue, float out_scale, hipStream_t s, const QkvOut* qkv, bool bf = false) {
-    const unsigned long long eb = bf ? 2ull : 4ull;                  // operand bytes per k element (gemm16x_kernel.h: BF)
-    const GemmTune tune = g_tune;
+// Every gemm16x_kernel instantiation of the library, keyed by (epilogue, output kind = the kernel's OUT, XM, BF).
+enum { X_OUT_F32 = 0, X_OUT_16 = 1, X_OUT_QKV = 2 };
+using GemmKernel = decltype(&gemm16x_kernel<EPI_NONE, X_OUT_F32>);
+struct GemmInst { int epi, out; bool xm, bf; GemmKernel fn; };
+template <int EPI, int OUT, bool XM = false, bool BF = false>
+static GemmInst inst() { return {EPI, OUT, XM, BF, gemm16x_kernel<EPI, OUT, XM, BF>}; }
+static const GemmInst kGemmInst[] = {
+    inst<EPI_NONE, X_OUT_F32>(),                   inst<EPI_NONE, X_OUT_16>(),                   inst<EPI_NONE, X_OUT_QKV>(),
+    inst<EPI_GELU, X_OUT_F32>(),                   inst<EPI_GELU, X_OUT_16>(),
+    inst<EPI_SQRELU, X_OUT_F32>(),                 inst<EPI_SQRELU, X_OUT_16>(),
+    inst<EPI_GELU_TANH, X_OUT_F32>(),              inst<EPI_GELU_TANH, X_OUT_16>(),
+    inst<EPI_SWIGLU, X_OUT_16>(),                                                                // f16x3, split-plane output only
+    inst<EPI_NONE, X_OUT_F32, false, true>(),      inst<EPI_NONE, X_OUT_16, false, true>(),      inst<EPI_NONE, X_OUT_QKV, false, true>(),
+    inst<EPI_GELU, X_OUT_F32, false, true>(),      inst<EPI_GELU, X_OUT_16, false, true>(),
+    inst<EPI_SQRELU, X_OUT_F32, false, true>(),    inst<EPI_SQRELU, X_OUT_16, false, true>(),
+    inst<EPI_GELU_TANH, X_OUT_F32, false, true>(), inst<EPI_GELU_TANH, X_OUT_16, false, true>(),
+    inst<EPI_NONE, X_OUT_F32, true>(),             inst<EPI_NONE, X_OUT_16, true>(),             // launch_gemm16_ex
+};
+
+// One launch of one instantiation on min(G, n_items) workgroups: table lookup, set-attribute (per launch), launch, error.  c_plane is
+// the fused QKV's q | k plane stride and 0 for every other output kind.
+static int launch_x(const GemmLaunch& g, int out, bool xm, size_t c_plane, int G, int n_items, const TilePlan& tp, const QkvOut& qo,
+                    const XMap& xmap) {
+    const GemmInst* k = nullptr;
+    for (const GemmInst& i : kGemmInst)
+        if (i.epi == g.epilogue && i.out == out && i.xm == xm && i.bf == g.bf) { k = &i; break; }
+    if (!k) {
+        set_error("gemm16: no kernel for epilogue %d, output kind %d, xmap %d, bf16 %d", g.epilogue, out, (int)xm, (int)g.bf);
+        return PGMI_EINVAL;
+    }
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k->fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)X_LDS_BYTES);
+    if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PGMI_EHIP; }
+    hipLaunchKernelGGL(k->fn, dim3(std::min(G, n_items)), dim3(XNT), X_LDS_BYTES, g.stream, g.A, g.W, g.bias, g.residual, g.out32, g.out16,
+                       c_plane, g.M, g.N, g.K, g.out_scale, tp, qo, xmap);
+    PGMI_HIP(hipGetLastError());
+    return PGMI_OK;
+}
+
+static int launch_gemm16x_one(const GemmLaunch& g, int group_m) {
+    const int M = g.M, N = g.N, K = g.K;
+    const bool qkv = g.qkv.vt16 != nullptr;
+    const unsigned long long eb = g.bf ? 2ull : 4ull;                // operand bytes per k element (gemm16x_kernel.h: BF)
     TilePlan tp{};
-    tp.group_m = tune.group_m > 0 ? tune.group_m : ((N + XBN - 1) / XBN >= kWideTilesN ? kGroupMWide : kGroupM);
+    tp.group_m = group_m > 0 ? group_m : ((N + XBN - 1) / XBN >= kWideTilesN ? kGroupMWide : kGroupM);
     tp.tiles_m = (M + XBM - 1) / XBM;
     tp.tiles_n = (N + XBN - 1) / XBN;
     const int T = tp.tiles_m * tp.tiles_n, G = x_num_cus();
     tp.n_main = T;
     if ((unsigned long long)std::max(M, N) * (unsigned long long)K * eb >= (1ull << 32) ||
-        (Cf && (unsigned long long)M * (unsigned long long)N * 4ull >= (1ull << 31))) {      // launch_gemm16x chunks M below this
+        (g.out32 && (unsigned long long)M * (unsigned long long)N * 4ull >= (1ull << 31))) {      // launch_gemm16x chunks M below this
         set_error("gemm16x: operand of %d x %d split elements (or %d x %d outputs) exceeds the 32-bit offset range", std::max(M, N), K, M, N);
         return PGMI_EINVAL;
     }
@@ -295,41 +160,12 @@ static int launch_gemm16x_one(const unsigned short* A, const unsigned short* W,
     // items on two CUs, each over the full K range in the same order, so every output element is computed exactly as in a
     // full tile (bit-identical: a row's bits must not depend on how many rows travel with it, tests/test_gpu_cli.py) -- when
     // all the halves still fit one round.
-    const int want_half = g_opt.half_tail;
-    if (want_half && !qkv && rem > 0 && 2 * rem <= G) {
+    if (g_opt.half_tail && !qkv && rem > 0 && 2 * rem <= G) {
         tp.n_main = T - rem; tp.half = 1; tp.n_tail = 2 * rem;
     }
-    const int n_items = tp.n_main + tp.n_tail;
-    const dim3 grid(std::min(G, n_items)), block(XNT);
     QkvOut qo{};
-    if (qkv) qo = *qkv;
-    const XMap xmap{};
-#define PGMI_LAUNCH16X(EPI_, OUT_)                                                                        \
-    do {                                                                                                 \
-        auto kfn = bf ? gemm16x_kernel<EPI_, OUT_, false, true> : gemm16x_kernel<EPI_, OUT_>;             \
-        const size_t lds_bytes = X_LDS_BYTES;                                                            \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),                           \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);  \
-        if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PGMI_EHIP; } \
-        hipLaunchKernelGGL(kfn, grid, block, lds_bytes, s, A, W, bias, residual, Cf, Ch, c_plane, M, N, K,  \
-                           out_scale, tp, qo, xmap);                                                     \
-    } while (0)
-#define PGMI_LAUNCH16X_O(EPI_) do { if (Ch) PGMI_LAUNCH16X(EPI_, 1); else PGMI_LAUNCH16X(EPI_, 0); } while (0)
-    if (qkv) PGMI_LAUNCH16X(EPI_NONE, 2);
-    else if (epilogue == EPI_SWIGLU) {                   // f16x3, split-plane output only (launch_gemm16)
-        const auto kfn = gemm16x_kernel<EPI_SWIGLU, 1>;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)X_LDS_BYTES);
-        if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PGMI_EHIP; }
-        hipLaunchKernelGGL(kfn, grid, block, X_LDS_BYTES, s, A, W, bias, residual, Cf, Ch, c_plane, M, N, K, out_scale, tp, qo, xmap);
-    }
-    else if (epilogue == EPI_GELU) PGMI_LAUNCH16X_O(EPI_GELU);
-    else if (epilogue == EPI_SQRELU) PGMI_LAUNCH16X_O(EPI_SQRELU);
-    else if (epilogue == EPI_GELU_TANH) PGMI_LAUNCH16X_O(EPI_GELU_TANH);
-    else PGMI_LAUNCH16X_O(EPI_NONE);
-#undef PGMI_LAUNCH16X_O
-#undef PGMI_LAUNCH16X
-    PGMI_HIP(hipGetLastError());
-    return PGMI_OK;
+    if (qkv) qo = QkvOut{g.qkv.vt16, g.qkv.vt_plane, g.qkv.cos_t, g.qkv.sin_t, g.qkv.T, g.qkv.H, (g.qkv.T + 31) / 32 * 32, g.qkv.rotary, g.qkv.rot_halves};
+    return launch_x(g, qkv ? X_OUT_QKV : g.out16 ? X_OUT_16 : X_OUT_F32, false, qkv ? g.qkv.qk_plane : 0, G, tp.n_main + tp.n_tail, tp, qo, XMap{});
 }
 
 // Batched / strided form (XMap, gemm16x_kernel.h): the MSA Transformer's tied row attention.  M, N, K are ONE batch's; nbatch batches
@@ -352,23 +188,12 @@ int launch_gemm16_ex(const unsigned short* A, const unsigned short* W, float* Cf
     xm.tiles_per_batch = per;
     if (xm.batch_inner < 1) xm.batch_inner = 1;
     if (all_half) { tp.half = 2; tp.n_main = 0; tp.n_tail = T; } else { tp.n_main = T; }
-    const dim3 grid(std::min(G, T)), block(XNT);
-    QkvOut qo{};
-    const float* nobias = nullptr;
-    const size_t lds_bytes = X_LDS_BYTES;
-#define PGMI_LAUNCH16X_EX(OUT_)                                                                           \
-    do {                                                                                                 \
-        auto kfn = gemm16x_kernel<EPI_NONE, OUT_, true>;                                                  \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),                           \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);  \
-        if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PGMI_EHIP; } \
-        hipLaunchKernelGGL(kfn, grid, block, lds_bytes, s, A, W, nobias, nobias, Cf, Ch, (size_t)0, M, N, K,  \
-                           out_scale, tp, qo, xm);                                                       \
-    } while (0)
-    if (Ch) PGMI_LAUNCH16X_EX(1); else PGMI_LAUNCH16X_EX(0);
-#undef PGMI_LAUNCH16X_EX
-    PGMI_HIP(hipGetLastError());
-    return PGMI_OK;
+    GemmLaunch g;
+    g.A = A; g.W = W; g.out_scale = out_scale;
+    g.out32 = Cf; g.out16 = Ch;
+    g.M = M; g.N = N; g.K = K;
+    g.stream = s;
+    return launch_x(g, Ch ? X_OUT_16 : X_OUT_F32, true, 0, G, T, tp, QkvOut{}, xm);
 }
 
 // The kernel addresses its operands with 32-bit byte offsets from a buffer descriptor (no 64-bit address arithmetic in the
@@ -376,109 +201,67 @@ int launch_gemm16_ex(const unsigned short* A, const unsigned short* W, float* Cf
 // K = 20480 allows 52 428 rows; an MSA Transformer alignment of 400 x 1024 tokens at K = 3072) are cut into row chunks --
 // rows are independent and every row is computed exactly as in one launch (bit-identical), the chunks run back to back on the
 // stream.  Fused QKV output: chunks are whole sequences (the V^T scatter is per (sequence, head)).
-static int launch_gemm16x(const unsigned short* A, const unsigned short* W,
-                          const float* bias, const float* residual, float* Cf, unsigned short* Ch, size_t c_plane,
-                          int M, int N, int K, int epilogue, float out_scale, hipStream_t s, const QkvOut* qkv = nullptr, bool bf = false) {
+static int launch_gemm16x(const GemmLaunch& g) {
+    const int M = g.M, N = g.N, K = g.K, group_m = gemm_group_m(g.variant);
+    const bool qkv = g.qkv.vt16 != nullptr;
     const unsigned long long lim = (1ull << 32) - 1;
-    const unsigned long long eb = bf ? 2ull : 4ull;
+    const unsigned long long eb = g.bf ? 2ull : 4ull;
     if ((unsigned long long)N * (unsigned long long)K * eb > lim) {
         set_error("gemm16x: weight of %d x %d split elements exceeds the 32-bit offset range", N, K);
         return PGMI_EINVAL;
     }
     const long long test_rows = g_opt.max_rows;                          // tests: force chunking at small shapes
     long long max_rows = (long long)(lim / ((unsigned long long)K * eb));
-    if (Cf) max_rows = std::min(max_rows, (long long)(((1ull << 31) - 1) / ((unsigned long long)N * 4ull)));   // the fp32 epilogue's buffer offsets
+    if (g.out32) max_rows = std::min(max_rows, (long long)(((1ull << 31) - 1) / ((unsigned long long)N * 4ull)));   // the fp32 epilogue's buffer offsets
     if (test_rows > 0) max_rows = std::min(max_rows, test_rows);
-    if (M <= max_rows) return launch_gemm16x_one(A, W, bias, residual, Cf, Ch, c_plane, M, N, K, epilogue, out_scale, s, qkv, bf);
-    long long per = qkv ? (max_rows / qkv->T) * qkv->T : (max_rows / XBM) * XBM;
+    if (M <= max_rows) return launch_gemm16x_one(g, group_m);
+    long long per = qkv ? (max_rows / g.qkv.T) * g.qkv.T : (max_rows / XBM) * XBM;
     if (per <= 0) per = qkv ? 0 : max_rows;
-    if (per <= 0) { set_error("gemm16x: one sequence of %d tokens x K = %d exceeds the 32-bit offset range", qkv->T, K); return PGMI_EINVAL; }
+    if (per <= 0) { set_error("gemm16x: one sequence of %d tokens x K = %d exceeds the 32-bit offset range", g.qkv.T, K); return PGMI_EINVAL; }
+    // halfs per output row: the q | k rows of the fused QKV; SwiGLU: N / 2 output columns
+    const size_t n_out16 = qkv ? (size_t)(2 * (N / 3)) : (size_t)(g.bf ? 1 : 2) * (g.epilogue == EPI_SWIGLU ? (size_t)N / 2 : (size_t)N);
     for (long long m0 = 0; m0 < M; m0 += per) {
-        const int mc = (int)std::min<long long>(per, M - m0);
-        const unsigned short* Ac = A + (size_t)m0 * (size_t)K * (bf ? 1 : 2);          // K-interleaved rows: 2 K halfs each (bf16: K)
-        int rc;
-        if (qkv) {
-            QkvOut q = *qkv;                                                           // rows m0.. are sequences m0 / T ..
-            q.vt16 = qkv->vt16 + (size_t)(m0 / qkv->T) * (size_t)qkv->H * kHeadDim * (size_t)qkv->Tp;
-            rc = launch_gemm16x_one(Ac, W, bias, nullptr, nullptr, Ch + (size_t)m0 * (size_t)(2 * (N / 3)), c_plane, mc, N, K, epilogue,
-                                    out_scale, s, &q, bf);
-        } else {
-            const size_t n_out = epilogue == EPI_SWIGLU ? (size_t)N / 2 : (size_t)N;        // SwiGLU: N / 2 output columns
-            rc = launch_gemm16x_one(Ac, W, bias, residual ? residual + (size_t)m0 * N : nullptr, Cf ? Cf + (size_t)m0 * N : nullptr,
-                                    Ch ? Ch + (size_t)m0 * (size_t)(bf ? 1 : 2) * n_out : nullptr, c_plane, mc, N, K, epilogue, out_scale, s, nullptr, bf);
-        }
+        GemmLaunch c = g;
+        c.M = (int)std::min<long long>(per, M - m0);
+        c.A = g.A + (size_t)m0 * (size_t)K * (g.bf ? 1 : 2);                           // K-interleaved rows: 2 K halfs each (bf16: K)
+        if (g.residual) c.residual = g.residual + (size_t)m0 * N;
+        if (g.out32) c.out32 = g.out32 + (size_t)m0 * N;
+        if (g.out16) c.out16 = g.out16 + (size_t)m0 * n_out16;
+        if (qkv) c.qkv.vt16 = g.qkv.vt16 + (size_t)(m0 / g.qkv.T) * (size_t)g.qkv.H * kHeadDim * (size_t)((g.qkv.T + 31) / 32 * 32);   // rows m0.. are sequences m0 / T ..
+        const int rc = launch_gemm16x_one(c, group_m);
         if (rc) return rc;
     }
     return PGMI_OK;
 }
 
-// variant (tuning; everything below 1000 is the product's configuration): 1000 + t sets the round-4 launch parameters for the
-// interleaved A/B of scripts/gemm_ab.py -- t bits 0-3: row panels per group (0: by shape).
-static void set_tune(int variant) {
-    g_tune = GemmTune{};
-    if (variant >= 1000) {
-        const int t = variant - 1000;
-        g_tune.group_m = t & 15;
+int launch_gemm16(const GemmLaunch& g) {
+    const int M = g.M, N = g.N, K = g.K;
+    // K: whole 32-deep K tiles for the f16x3 form (one 128-byte line per row and tile; an odd tile count is fine: ESM2-35M has
+    // K = 480 = 15 tiles), 64 for the bf16 form's K tile
+    const int k_step = g.bf ? 64 : 32;
+    if (g.qkv.vt16) {                                      // the fused QKV projection: N = 3 D
+        const int D = N / 3, T = g.qkv.T;
+        if (M <= 0 || K <= 0 || D <= 0 || N != 3 * D || (K % k_step) || (D % 64) || T <= 0 || M % T || g.qkv.rot_halves < 1 || !g.out16 || g.out32 ||
+            g.residual || g.epilogue != EPI_NONE) {
+            set_error("gemm16_qkv: unsupported shape M=%d D=%d K=%d T=%d", M, D, K, T);
+            return PGMI_EINVAL;
+        }
+        return launch_gemm16x(g);
     }
-}
-
-int launch_gemm16(const unsigned short* A, size_t a_plane, const unsigned short* W, size_t w_plane,
-                  const float* bias, const float* residual, float* Cf, unsigned short* Ch, size_t c_plane,
-                  int M, int N, int K, int epilogue, float out_scale, int planes, bool bf, int variant,
-                  hipStream_t s) {
-    (void)a_plane; (void)w_plane;                 // f16x3 operands are K-interleaved (no plane stride); bf16 has one plane
-    // K: whole 32-deep K tiles for the f16x3 kernel (one 128-byte line per row and tile; an odd tile count is fine: ESM2-35M has
-    // K = 480 = 15 tiles), 64 for the bf16 kernel's K tile
-    const int k_step = (planes == 2 && !bf) ? 32 : 64;
-    if (M <= 0 || N <= 0 || K <= 0 || (K % k_step) != 0 || (N % 4) != 0 || (!Cf && !Ch) || (Cf && Ch)) {
+    if (M <= 0 || N <= 0 || K <= 0 || (K % k_step) != 0 || (N % 4) != 0 || (!g.out32 && !g.out16) || (g.out32 && g.out16)) {
         set_error("gemm16: unsupported shape/args M=%d N=%d K=%d (K %% %d == 0, N %% 4 == 0 required)", M, N, K, k_step);
         return PGMI_EINVAL;
     }
-    if (epilogue == EPI_SWIGLU && (planes != 2 || bf || !Ch || residual || (N % 64) != 0)) {
+    if (g.epilogue == EPI_SWIGLU && (g.bf || !g.out16 || g.residual || (N % 64) != 0)) {
         set_error("gemm16: the SwiGLU epilogue is f16x3 with split-plane output, no residual and N %% 64 == 0 (N = %d)", N);
         return PGMI_EINVAL;
     }
-    if (planes == 2 && !bf) {
-        if (Ch && (N % 32) != 0) { set_error("gemm16: split output needs N %% 32 == 0 (K-interleaved operand of the next GEMM), got %d", N); return PGMI_EINVAL; }
-        set_tune(variant);
-        const int rc = launch_gemm16x(A, W, bias, residual, Cf, Ch, c_plane, M, N, K, epilogue, out_scale, s);
-        g_tune = GemmTune{};
-        return rc;
-    }
-    if (planes == 1 && bf) {
-        if (out_scale != 1.0f) { set_error("gemm16: bf16 weights are not pre-scaled"); return PGMI_EINVAL; }
-        if (Ch && (N % 4) != 0) { set_error("gemm16: bf16 plane output needs N %% 4 == 0, got %d", N); return PGMI_EINVAL; }
-        // round 6: the persistent ping-pong kernel in its one-plane form (gemm16x_kernel.h BF); the round-1 kernel is kept for the A/B
-        // (variant 2000: scripts/gemm_ab.py)
-        if (variant != 2000) {
-            set_tune(variant);
-            const int rc = launch_gemm16x(A, W, bias, residual, Cf, Ch, c_plane, M, N, K, epilogue, 1.0f, s, nullptr, true);
-            g_tune = GemmTune{};
-            return rc;
-        }
-        if ((long long)M * N >= 1 << 22) return launch_bf16_cfg<2, 4, 4, 2>(A, W, bias, residual, Cf, Ch, M, N, K, epilogue, s);
-        return launch_bf16_cfg<2, 2, 2, 2>(A, W, bias, residual, Cf, Ch, M, N, K, epilogue, s);
-    }
-    set_error("gemm16: unsupported mode planes=%d bf=%d", planes, (int)bf);
-    return PGMI_EINVAL;
-}
-
-// Fused QKV projection for the f16x3 attention: writes qk16 (q|k split planes, [M][2D]) and vt16
-// (transposed key-permuted V planes) instead of an fp32 [M,3D] tensor; rotary applied to q,k if set.
-int launch_gemm16_qkv(const unsigned short* A, size_t a_plane, const unsigned short* W, size_t w_plane,
-                      const float* bias, int M, int D, int K, float out_scale, unsigned short* qk16, size_t qk_plane,
-                      unsigned short* vt16, size_t vt_plane, const float* cos_t, const float* sin_t, int rotary,
-                      int T, int H, int variant, hipStream_t s, int rot_halves, bool bf) {
-    (void)a_plane; (void)w_plane;
-    if (M <= 0 || D <= 0 || (K % (bf ? 64 : 32)) || (D % 64) || M % T || rot_halves < 1) {
-        set_error("gemm16_qkv: unsupported shape M=%d D=%d K=%d T=%d", M, D, K, T);
+    if (!g.bf && g.out16 && (N % 32) != 0) {
+        set_error("gemm16: split output needs N %% 32 == 0 (K-interleaved operand of the next GEMM), got %d", N);
         return PGMI_EINVAL;
     }
-    QkvOut qo{vt16, vt_plane, cos_t, sin_t, T, H, (T + 31) / 32 * 32, rotary, rot_halves};
-    set_tune(variant);
-    const int rc = launch_gemm16x(A, W, bias, nullptr, nullptr, qk16, qk_plane, M, 3 * D, K, EPI_NONE, out_scale, s, &qo, bf);
-    g_tune = GemmTune{};
-    return rc;
+    if (g.bf && g.out_scale != 1.0f) { set_error("gemm16: bf16 weights are not pre-scaled"); return PGMI_EINVAL; }
+    return launch_gemm16x(g);
 }
 
 // ---- fp32 -> 16-bit operands (weights at load time; activations in the op-level tests and the MSA tied-attention path) ----

@@ -1,7 +1,7 @@
 // Internal header of the C ABI's translation units (api_*.hip): the device-resident model / assay / library state behind the opaque
 // handles of include/pgmi.h and the host-side helpers they share.  Nothing here is part of the ABI.
-//   api_model.hip        errors, configuration and token checks, weight split, model create (validation, per-arch dispatch,
-//                        workspace) / destroy, options, profiling
+//   api_model.hip        errors, configuration and token checks, weight split, linear() / qkv_launch() (a model's GEMMs as a
+//                        GemmLaunch), model create (validation, per-arch dispatch, workspace) / destroy, options, profiling
 //   api_esm.hip          ESM-1b / ESM-1v / ESM2 weights (create_esm), the encoder forward of the ESM family and ESM C (run_encoder,
 //                        run_head), masked-marginals assays, pseudo-ppl libraries
 //   api_tranception.hip  Tranception weights, prefix-shared chunks; token log-probs and sequence log-likelihoods (on run_decoder)
@@ -35,9 +35,9 @@ namespace pgmi {
 
 // 16-bit operand of one Linear weight [N,K]: f16x3 = fp16 (hi, lo) of W*2^s in the K-interleaved layout (common.h
 // ki_off: per row, groups of 32 hi halfs + 32 lo halfs), bf16 = one plane; out_scale = 2^-s is applied in the GEMM epilogue.
+// They are GemmLaunch's W and out_scale (common.h).
 struct W16 {
     unsigned short* p = nullptr;
-    size_t plane = 0;
     float out_scale = 1.0f;
 };
 
@@ -112,7 +112,9 @@ struct pgmi_model {
     size_t tied_part_cap = 0, tied_p_cap = 0, tied_vt_cap = 0;
     int msa_kv_R = 0, msa_kv_C = 0;
     float ln_eps = 1e-5f;
-    unsigned short *h16 = nullptr, *g16 = nullptr;     // activation planes [planes][R*D], [planes][R*F]
+    // 16-bit activations: h16_plane = R*D and g16_plane = R*F elements (f16x3: K-interleaved hi | lo rows, 2 halfs per element; bf16: 1
+    // half).  They are allocation sizes; no launcher takes them as a stride.
+    unsigned short *h16 = nullptr, *g16 = nullptr;
     size_t h16_plane = 0, g16_plane = 0;
     unsigned short *qk16 = nullptr, *vt16 = nullptr;   // attention operands (f16x3): [2][R*2D], [2][R*D]
     size_t qk16_plane = 0, vt16_plane = 0;
@@ -232,9 +234,9 @@ int check_tokens(const int32_t* tokens, int B, int T, int n_ids = PGMI_VOCAB);
 int check_vocab(const int32_t* tokens, int B, int T, int V);
 int env_int(const char* name, int dflt);
 int make_w16(std::vector<void*>& pool, const float* host, size_t n, size_t K, int precision, hipStream_t s, W16* out);
-int linear(pgmi_model* m, const float* in32, const unsigned short* in16, size_t in_plane, const float* W32,
-           const W16& w16, const float* bias, const float* residual, float* out32, unsigned short* out16,
-           size_t out_plane, int M, int N, int K, int epi);
+int linear(pgmi_model* m, const float* in32, const unsigned short* in16, const float* W32, const W16& w16, const float* bias,
+           const float* residual, float* out32, unsigned short* out16, int M, int N, int K, int epi);
+GemmLaunch qkv_launch(pgmi_model* m, const W16& w16, const float* bias, int M, int Da, int K, int T, int H);
 int check_nonfinite(pgmi_model* m);
 int reset_pad_keys(pgmi_model* m, int B, int T);
 int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int device, pgmi_model** out, int arch_arg);
