@@ -545,6 +545,60 @@ int pgmi_eve_evol_indices(pgmi_eve* m, const uint8_t* residues, int M, int num_s
 int pgmi_eve_log_prior(pgmi_eve* m, const uint8_t* residues, int num_samples, uint64_t seed, const pgmi_eve_noise* injected,
                        double* mean_logp, double* std_logp);
 
+/* ---- ProteinMPNN (message passing on a k-nearest-neighbour backbone graph; its own handle and config, precision fp32) ------------
+ * Replaces ProteinMPNN.forward and _scores (proteingym/baselines/protein_mpnn/protein_mpnn_utils.py:920-1100, :39-47) as
+ * compute_fitness.py runs them: one forward per mutant under a random decoding order, pmpnn_ll = -(masked mean NLL).  Everything that
+ * depends only on the structure (graph, edge features, the three encoder layers, the mutant-independent part of every decoder
+ * layer's first Linear) is computed once by pgmi_mpnn_set_structure; a mutant costs the decoder only.  DESIGN.md 4.6h has the
+ * restatement, the factorisation and the kernels.
+ *
+ * Weight blob: fp32, the tensors of ProteinMPNN(ca_only=False).state_dict() in its own order, each flattened row-major:
+ *   features.embeddings.linear.weight [16, 66], .bias [16]; features.edge_embedding.weight [128, 416];
+ *   features.norm_edges.weight, .bias [128]; W_e.weight [128, 128], .bias [128]; W_s.weight [21, 128];
+ *   encoder_layers.{i}: norm1, norm2, norm3 (.weight, .bias [128] each); W1 [128, 384], W2 [128, 128], W3 [128, 128], W11 [128, 384],
+ *     W12 [128, 128], W13 [128, 128], dense.W_in [512, 128], dense.W_out [128, 512] (.weight then .bias each)
+ *   decoder_layers.{i}: norm1, norm2; W1 [128, 512], W2 [128, 128], W3 [128, 128], dense.W_in [512, 128], dense.W_out [128, 512]
+ *   W_out.weight [21, 128], .bias [21]
+ * Letters: the index in "ACDEFGHIKLMNPQRSTVWYX" (0 .. 20).
+ * Limits: hidden width 128; num_edges 1 .. 48 (the v_48_* checkpoints' value); L <= 8192; at most PGMI_MPNN_MAX_LAYERS layers per stack; backbone_noise 0. */
+#define PGMI_MPNN_MAX_LAYERS 8
+typedef struct pgmi_mpnn_config {
+    int32_t abi_version;                          /* = PGMI_ABI_VERSION */
+    int32_t hidden;                               /* = 128 */
+    int32_t num_edges;                            /* the checkpoint's num_edges (48); K = min(num_edges, L) */
+    int32_t enc_layers, dec_layers;               /* 3, 3 */
+    int32_t precision;                            /* PGMI_PREC_FP32 (the only mode) */
+} pgmi_mpnn_config;
+typedef struct pgmi_mpnn pgmi_mpnn;
+/* pgmi_mpnn_weight_count: size of the blob above; -1 for a config the library refuses (pgmi_last_error).
+ * pgmi_mpnn_create / pgmi_mpnn_destroy: the device-resident model (one HIP stream).
+ * pgmi_mpnn_profile_model: the handle's profiling view for pgmi_profile_enable / _get / _reset / pgmi_synchronize (owned by the handle).
+ *   Classes: PGMI_K_EMBED = the whole structure pass (one launch per pgmi_mpnn_set_structure; its GEMMs and LayerNorms are counted
+ *   here and under no other class); of the decoder: PGMI_K_ATTENTION = the edge kernel, PGMI_K_GEMM_OUT = W3, PGMI_K_LAYERNORM = the
+ *   two LayerNorm stages, PGMI_K_GEMM_FC1 / _FC2 = the FFN, PGMI_K_GEMM_QKV = the next layer's [A | P] projection, PGMI_K_HEAD =
+ *   W_out + log-softmax, PGMI_K_SCORE = the per-mutant mean.
+ * pgmi_mpnn_set_structure: X f32 [L][4][3] (N, CA, C, O; missing atoms 0), mask f32 [L] (0 where any of the four is missing, else 1),
+ *   residue_idx i32 [L] (+100 per chain), chain_label i32 [L].  Neighbours: the K = min(num_edges, L) smallest adjusted CA distances
+ *   of a row, ties broken by ascending distance, then ascending index (torch.topk leaves the order of ties open; the edges of a node
+ *   are summed, so only the set matters).  Replaces the previous structure of the handle.
+ * pgmi_mpnn_graph (test view): E_idx i32 [L][K], E f32 [L][K][128] (ProteinFeatures' output, after norm_edges); each nullable.
+ * pgmi_mpnn_encoder (test view): h_V f32 [L][128], h_E f32 [L][K][128] after the last encoder layer; each nullable.
+ * pgmi_mpnn_log_probs: S u8 [B][L], rank i32 [B][L] (rank[b][i] = position of residue i in mutant b's decoding order; edge (i, j) sees
+ *   the sequence at j iff mask_i and rank_i > rank_j), out f32 [B][L][21].
+ * pgmi_mpnn_scores: the production call: out f64 [B], out[b] = -(sum_i mask_i (-log p_i[S_i])) / sum_i mask_i, summed in fp64 in a
+ *   fixed order; no log-probability leaves the device.  A mutant's result has the same bits whatever else is in the call.
+ * pgmi_set_option("mpnn_max_rows", n): (mutant, residue) rows per chunk (0: 32768; clamped to 1 << 20; test hook, bit-neutral). */
+int64_t pgmi_mpnn_weight_count(const pgmi_mpnn_config* cfg);
+int pgmi_mpnn_create(const pgmi_mpnn_config* cfg, const float* weights, int64_t n_weights, int device, pgmi_mpnn** out);
+void pgmi_mpnn_destroy(pgmi_mpnn* m);
+pgmi_model* pgmi_mpnn_profile_model(pgmi_mpnn* m);
+int pgmi_mpnn_set_structure(pgmi_mpnn* m, const float* X, const float* mask, const int32_t* residue_idx, const int32_t* chain_label,
+                            int L);
+int pgmi_mpnn_graph(pgmi_mpnn* m, int32_t* E_idx, float* E);
+int pgmi_mpnn_encoder(pgmi_mpnn* m, float* h_V, float* h_E);
+int pgmi_mpnn_log_probs(pgmi_mpnn* m, const uint8_t* S, const int32_t* rank, int B, float* out);
+int pgmi_mpnn_scores(pgmi_mpnn* m, const uint8_t* S, const int32_t* rank, int B, double* out);
+
 /* ---- MSA Transformer (arch PGMI_ARCH_MSA; vocab 33, head_dim 64, precision f16x3) --------------------
  * Replaces MSATransformer.forward (proteingym/baselines/esm/esm/model/msa_transformer.py:146-205; tied
  * row attention esm/axial_attention.py:33-168, column attention :171-297) and the masked-marginals loop

@@ -109,6 +109,15 @@ SIGNATURES = [
     ("pgmi_eve_noise_fill", C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int64, C.c_int, C.c_void_p]),
     ("pgmi_eve_evol_indices", C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, C.c_uint64, _f64p, _f64p]),
     ("pgmi_eve_log_prior", C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_uint64, C.c_void_p, _f64p, _f64p]),
+    ("pgmi_mpnn_weight_count", C.c_int64, [C.c_void_p]),
+    ("pgmi_mpnn_create", C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
+    ("pgmi_mpnn_destroy", None, [C.c_void_p]),
+    ("pgmi_mpnn_profile_model", C.c_void_p, [C.c_void_p]),
+    ("pgmi_mpnn_set_structure", C.c_int, [C.c_void_p, _f32p, _f32p, _i32p, _i32p, C.c_int]),
+    ("pgmi_mpnn_graph", C.c_int, [C.c_void_p, _i32p, _f32p]),
+    ("pgmi_mpnn_encoder", C.c_int, [C.c_void_p, _f32p, _f32p]),
+    ("pgmi_mpnn_log_probs", C.c_int, [C.c_void_p, _u8p, _i32p, C.c_int, _f32p]),
+    ("pgmi_mpnn_scores", C.c_int, [C.c_void_p, _u8p, _i32p, C.c_int, _f64p]),
     ("pgmi_bench_gemm", C.c_int, [C.c_int] * 9 + [_f64p]),
     ("pgmi_bench_gemm_ab", C.c_int, [C.c_int] * 7 + [_i32p, C.c_int, C.c_int, C.c_int, _f64p]),
     ("pgmi_op_attention", C.c_int, [C.c_int, C.c_int, _f32p, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),

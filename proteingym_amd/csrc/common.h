@@ -162,6 +162,25 @@ void launch_eve_prior_finish(const float* partial, int S, const float* b_mean, c
                              double* acc, hipStream_t s);
 int eve_set_option(const char* name, long long value);   // api_eve.hip: "eve_max_rows", "eve_fixed_sample", "eve_prior_batch"
 
+// ---- mpnn.hip (ProteinMPNN; the kernels are described there) -------------------------------------------------------------------
+void launch_mpnn_graph(const float* X, const float* mask, int L, int K, int32_t* E_idx, float* D_nb, hipStream_t s);
+void launch_mpnn_edge_feat(const float* X, const int32_t* ridx, const int32_t* chain, const int32_t* E_idx, const float* D_nb,
+                           const float* Wpos, const float* bpos, const float* Wt, const float* ln_w, const float* ln_b, int L, int K, float* E,
+                           hipStream_t s);
+void launch_mpnn_concat(const float* hV, const float* hE, const int32_t* E_idx, int L, int K, float* out, hipStream_t s);
+void launch_mpnn_edge_sum(const float* msg, const float* mask, const int32_t* E_idx, int L, int K, float* out, hipStream_t s);
+// out[r] = LayerNorm(a[r % a_rows] + (b[r] + kb bias) / div) * rowmask[r % L]; b, bias, rowmask nullable; 128 columns
+void launch_mpnn_add_ln(const float* a, int64_t a_rows, const float* b, const float* bias, float kb, float div, const float* ln_w,
+                        const float* ln_b, const float* rowmask, int L, int64_t rows, float* out, hipStream_t s);
+// out [B][L][128] = sum over a node's K edges of GELU(W2 GELU(pre) + b2); AP = [A | P] rows of 256, ap_bstride 0 when shared by the batch
+int launch_mpnn_dec_edge(const float* Ep, const float* T, const float* Penc, const float* AP, int64_t ap_bstride, const float* W2,
+                         const float* b2, const int32_t* E_idx, const float* mask, const uint8_t* S, const int32_t* rank, int B, int L, int K,
+                         float* out, hipStream_t s);
+void launch_mpnn_head(const float* h, const float* W, const float* bias, const uint8_t* S, int64_t rows, float* lp, float* nll,
+                      hipStream_t s);
+void launch_mpnn_score(const float* nll, const float* mask, int B, int L, double* out, hipStream_t s);
+int mpnn_set_option(const char* name, long long value);   // api_mpnn.hip: "mpnn_max_rows"
+
 // ---- gemm_f32.hip ------------------------------------------------------------------------
 // C[M,N] = epi(A[M,K] W[N,K]^T + bias[N]) (+ residual[M,N]); K % 32 == 0.
 // ---- msa_transformer.hip ------------------------------------------------------------------

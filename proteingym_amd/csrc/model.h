@@ -13,6 +13,8 @@
 //   api_esmc.hip         ESM C weights (QK-LayerNorm, SwiGLU, scaled residual, untied 64-column head); it runs on run_encoder
 //   api_saprot.hip       SaProt: ESM2's weights and encoder with a 446-token vocabulary; position-set rows and the grouped log-softmax head
 //   api_eve.hip          EVE / DeepSequence: its own handle (pgmi_eve), blob walk, encoder, one ELBO sample, noise seam, the sampling loop
+//   api_mpnn.hip         ProteinMPNN: its own handle (pgmi_mpnn), blob walk, the per-structure pass (graph, features, encoder, hoisted
+//                        decoder tables), the per-batch decoder and head
 //   api_msa.hip          MSA Transformer weights and forward (tied row attention, column attention)
 //   api_host.hip         host-only entries: mutant parser, table -> scores, optimal window
 //   api_ops.hip          single-op and timing entries for the numerics tests and the A/B scripts
