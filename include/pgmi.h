@@ -59,6 +59,9 @@ extern "C" {
 /* SaProt (proteingym/baselines/saprot/compute_fitness.py, HF EsmForMaskedLM): ESM2 over a 446-token structure-aware vocabulary;
  * created with pgmi_saprot_model_create, scored with pgmi_saprot_* (see the SaProt section below) */
 #define PGMI_ARCH_SAPROT 8
+/* PoET (proteingym/baselines/PoET/poet/models/poet.py): tiered causal decoder over a sequence-of-sequences, scored against a cached
+ * prompt; created with pgmi_poet_model_create, scored with pgmi_poet_* (see the PoET section below) */
+#define PGMI_ARCH_POET 9
 
 /* GEMM operand precision.  Residual stream, LayerNorm statistics, softmax and every
  * accumulator are fp32 in all modes. */
@@ -290,6 +293,13 @@ int pgmi_op_causal_attention(int device, int lanes, const float* X, const float*
  *   projection (no rotary) forms X W^T + bias, then every column is one sequence of R rows of the dense attention (B = C, T = R, kv_len = R,
  *   pad keys zeroed); honours the "att_v3" option.  ctx [C*R, D], order (c, r): the split-plane context (0xFF bytes before the launch)
  *   rebuilt as fp32. */
+/* PoET's segment-causal attention over a shared prefix (attention_prefix.hip) in SLOT SPACE, through the prep pass and the launcher the
+ * model uses; heads of 64 lanes, Da = 64 heads, no rotary, q taken as given (pre-scaled).  qkv fp32 [seg_off[n_seg]][3 Da]: the packed
+ * rows of n_seg segments (segment b = rows seg_off[b] .. seg_off[b+1]-1, every segment non-empty); prefix_kv fp32 [P][2 Da] (k | v; NULL
+ * when P = 0).  A query at position t of its segment sees the P prefix keys and the keys 0 .. t of its segment.  ctx [rows][Da]:
+ * split != 0: the split-plane context the out-projection consumes, rebuilt as fp32; 0: the kernel's fp32 rows. */
+int pgmi_op_prefix_attention(int device, const float* qkv, const int32_t* seg_off, int n_seg, const float* prefix_kv, int P, int heads,
+                             int split, float* ctx);
 int pgmi_op_tied_row_attention(int device, const float* qkv, int R, int C, int H, int splits, float* ctx, float* probs);
 int pgmi_op_tied_row_splits(int R, int C, int H);
 int pgmi_op_column_attention(int device, const float* X, const float* W, const float* bias, int K, int R, int C, int H, float* ctx);
@@ -448,6 +458,45 @@ int pgmi_saprot_model_create(const pgmi_config* cfg, int mask_id, const float* w
 int pgmi_saprot_token_logprobs(pgmi_model* m, const int32_t* tokens, int B, int T, float* out);
 int pgmi_saprot_group_logprobs(pgmi_model* m, const int32_t* wt_tokens, int T, const int32_t* set_off, const int32_t* set_pos,
                                int n_sets, float* out);
+
+/* ---- PoET (arch PGMI_ARCH_POET; vocab 24 .. 64, head_dim an even value up to 64, precision f16x3) ------------------------------
+ * Tokens (poet/alphabets.py Uniprot21 with gap and distinct start / stop): "ARNDCQEGHILKMFPSTWYV" 0..19, gap 20, start 21, stop 22,
+ * mask 23 (also X, B, Z; O = 11, U = 4).  No position table: both attentions of a layer rotate q and k by the position inside the
+ * sequence (interleaved pairs (2i, 2i+1), inv_freq = 10000^(-2i/head_dim), angle = fp32(t) * fp32(inv_freq)), q scaled by head_dim^-1/2.
+ * Per layer: x += out_proj(self_attn(norm1(x))) within each sequence; x += out_proj(multihead_attn(norm2(x))) causally over the
+ * sequence-of-sequences; x += linear2(gelu_erf(linear1(norm3(x)))).  Then `norm` (final_norm != 0) and linear [V,D] + bias.
+ * Config: max_positions = the largest prompt in tokens the caller will set (the per-layer prefix cache is allocated for it; 0: none);
+ * max_rows >= the prompt's tokens with every prompt sequence rounded up to 32.
+ * Weight blob order (fp32, nn.Linear layout [out,in], state-dict names without their leading component):
+ *   token_embed.weight [V,D];
+ *   per layer decoder.layers.{i}: norm1 w,b; self_attn.{q_proj, k_proj, v_proj}.weight [D,D] each; self_attn.out_proj W[D,D], b;
+ *        norm2 w,b; multihead_attn.{q_proj, k_proj, v_proj}.weight; multihead_attn.out_proj W, b; norm3 w,b;
+ *        linear1 W[F,D], b[F]; linear2 W[D,F], b[D];
+ *   (final_norm) norm w,b; linear W[V,D], b[V].
+ *
+ * pgmi_poet_weight_count: the blob size for (cfg, final_norm); <0 on a bad cfg.  (pgmi_weight_count returns -1 for this arch.)
+ * pgmi_poet_model_create: as pgmi_model_create, with final_norm.  Returns an ordinary model: destroy, profile, synchronize as usual.
+ * pgmi_poet_set_prompt: the tiered forward (PoET.embed) over a prompt of n_seg sequences, tokens int32 [sum seg_len] concatenated, each
+ *   with its start and stop token; fills the per-layer prefix cache with the tier-2 keys (rotated) and values.  n_seg = 0 clears the
+ *   cache (the reference's memory=None).  A prompt of more than max_positions tokens is PGMI_EINVAL (the cache never grows mid-assay);
+ *   after any failure no prompt is set.
+ * pgmi_poet_prompt_logprobs: out f32 [sum seg_len][V] = log_softmax(PoET.forward(prompt)) of the prompt last set.
+ * pgmi_poet_token_logprobs: variants int32 [B,T] right-padded with the mask token, lens[b] >= 1 real tokens (start / stop counted);
+ *   out f32 [B,T,V], row (b,t) = log p(. | prompt, tokens[b, <= t]) for t < lens[b]; rows beyond lens[b] are NaN.
+ * pgmi_poet_sequence_loglik: out f64 [B], out[b] = sum over t < lens[b]-1 of log p(tokens[b,t+1] | prompt, tokens[b, <= t]), targets
+ *   equal to the mask token skipped (scripts/score.py: CrossEntropyLoss(ignore_index=mask_token)); fp32 terms summed left to right in
+ *   fp64.  Only rows that have a target reach the head.  A variant's result has the same bits whatever else is in the call and however
+ *   the call is chunked. */
+#define PGMI_POET_TOK_GAP 20
+#define PGMI_POET_TOK_START 21
+#define PGMI_POET_TOK_STOP 22
+#define PGMI_POET_TOK_MASK 23
+int64_t pgmi_poet_weight_count(const pgmi_config* cfg, int final_norm);
+int pgmi_poet_model_create(const pgmi_config* cfg, int final_norm, const float* weights, int64_t n_weights, int device, pgmi_model** out);
+int pgmi_poet_set_prompt(pgmi_model* m, const int32_t* tokens, const int32_t* seg_len, int n_seg);
+int pgmi_poet_prompt_logprobs(pgmi_model* m, float* out);
+int pgmi_poet_token_logprobs(pgmi_model* m, const int32_t* tokens, const int32_t* lens, int B, int T, float* out);
+int pgmi_poet_sequence_loglik(pgmi_model* m, const int32_t* tokens, const int32_t* lens, int B, int T, double* out);
 
 /* ---- EVE / DeepSequence (Bayesian alignment VAE; its own handle and config, precision fp32) ------------------------------------
  * Replaces VAE_model.all_likelihood_components and the sampling loop of compute_evol_indices_chunk
@@ -639,6 +688,13 @@ int pgmi_msa_masked_logprobs(pgmi_model* m, const int32_t* tokens, int R, int T,
  * host, integer compares on the device): results are bit-identical to the reference's counts. */
 int pgmi_msa_cluster_counts(int device, const int8_t* matrix, int64_t N, int64_t L, int invalid_value,
                             double identity_threshold, int32_t* counts_out, double* kernel_ms);
+/* Neighbour counts of PoET's homology weights (proteingym/baselines/PoET/poet/msa/sampling.py _compute_homology_weights, numpy path):
+ * the same pair kernel with the predicate
+ *   counts_out[i] = #{j : 1 - matches(i,j) / nongap(i) <= theta}, self included, in the reference's float64 arithmetic
+ * (evaluated on the host once per non-gap length, integer compares on the device: counts equal the reference's exactly).  A gap never
+ * matches anything.  A row with no non-gap symbol is PGMI_EINVAL (the reference divides by zero there).  theta in [0, 1]. */
+int pgmi_msa_neighbor_counts(int device, const int8_t* matrix, int64_t N, int64_t L, int invalid_value,
+                             double theta, int32_t* counts_out, double* kernel_ms);
 
 #ifdef __cplusplus
 }

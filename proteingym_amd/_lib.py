@@ -17,6 +17,7 @@ ARCH_PROGEN2 = 5
 ARCH_GPT = 6
 ARCH_ESMC = 7
 ARCH_SAPROT = 8
+ARCH_POET = 9
 GPT_POS_ROTARY, GPT_POS_LEARNED = 0, 1
 PREC_FP32, PREC_BF16, PREC_F16X3 = 0, 1, 2
 PRECISIONS = {"fp32": PREC_FP32, "bf16": PREC_BF16, "f16x3": PREC_F16X3}
@@ -100,6 +101,12 @@ SIGNATURES = [
     ("pgmi_saprot_model_create", C.c_int, [C.POINTER(Config), C.c_int, _f32p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     ("pgmi_saprot_token_logprobs", C.c_int, [C.c_void_p, _i32p, C.c_int, C.c_int, _f32p]),
     ("pgmi_saprot_group_logprobs", C.c_int, [C.c_void_p, _i32p, C.c_int, _i32p, _i32p, C.c_int, _f32p]),
+    ("pgmi_poet_weight_count", C.c_int64, [C.POINTER(Config), C.c_int]),
+    ("pgmi_poet_model_create", C.c_int, [C.POINTER(Config), C.c_int, _f32p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
+    ("pgmi_poet_set_prompt", C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int]),
+    ("pgmi_poet_prompt_logprobs", C.c_int, [C.c_void_p, _f32p]),
+    ("pgmi_poet_token_logprobs", C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, C.c_int, _f32p]),
+    ("pgmi_poet_sequence_loglik", C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, C.c_int, _f64p]),
     ("pgmi_eve_weight_count", C.c_int64, [C.c_void_p]),
     ("pgmi_eve_create", C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     ("pgmi_eve_destroy", None, [C.c_void_p]),
@@ -124,12 +131,14 @@ SIGNATURES = [
     ("pgmi_op_qkln_prep", C.c_int, [C.c_int, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p, _f64p]),
     ("pgmi_op_causal_attention", C.c_int, [C.c_int, C.c_int, _f32p, _f32p, _f32p, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p,
                                            C.c_int, C.c_int, C.c_int, _f32p]),
+    ("pgmi_op_prefix_attention", C.c_int, [C.c_int, _f32p, _i32p, C.c_int, _f32p, C.c_int, C.c_int, C.c_int, _f32p]),
     ("pgmi_op_tied_row_attention", C.c_int, [C.c_int, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p]),
     ("pgmi_op_tied_row_splits", C.c_int, [C.c_int, C.c_int, C.c_int]),
     ("pgmi_op_column_attention", C.c_int, [C.c_int, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),
     ("pgmi_msa_token_logprobs", C.c_int, [C.c_void_p, _i32p, C.c_int, C.c_int, _f32p]),
     ("pgmi_msa_masked_logprobs", C.c_int, [C.c_void_p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, _i32p, C.c_int, _f32p]),
     ("pgmi_msa_cluster_counts", C.c_int, [C.c_int, C.POINTER(C.c_int8), C.c_int64, C.c_int64, C.c_int, C.c_double, _i32p, _f64p]),
+    ("pgmi_msa_neighbor_counts", C.c_int, [C.c_int, C.POINTER(C.c_int8), C.c_int64, C.c_int64, C.c_int, C.c_double, _i32p, _f64p]),
 ]
 
 

@@ -17,13 +17,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libpgmi.so")
 BUILD = os.path.join(HERE, "csrc", "_build")
-SOURCES = ["api_model.hip", "api_esm.hip", "api_tranception.hip", "api_progen2.hip", "api_gpt.hip", "api_esmc.hip", "api_saprot.hip", "api_eve.hip", "api_mpnn.hip", "api_msa.hip", "api_host.hip", "api_ops.hip", "elementwise.hip", "eve.hip", "mpnn.hip", "gemm_f32.hip", "gemm_f16.hip", "attention_f32.hip", "attention_f16.hip", "attention_f16_v3.hip", "attention_f16_prep.hip", "msa_weights.hip", "msa_transformer.hip"]
+SOURCES = ["api_model.hip", "api_esm.hip", "api_tranception.hip", "api_progen2.hip", "api_gpt.hip", "api_esmc.hip", "api_saprot.hip", "api_poet.hip", "api_eve.hip", "api_mpnn.hip", "api_msa.hip", "api_host.hip", "api_ops.hip", "elementwise.hip", "eve.hip", "mpnn.hip", "gemm_f32.hip", "gemm_f16.hip", "attention_f32.hip", "attention_f16.hip", "attention_f16_v3.hip", "attention_f16_prep.hip", "attention_prefix.hip", "msa_weights.hip", "msa_transformer.hip"]
 # attention_f16.hip: keep the MFMA accumulators in ArchVGPRs.  hipcc put the running O / S accumulators into AGPRs and then
 # paid 64 v_accvgpr_read + 64 v_accvgpr_write around every online-softmax rescale and around the S -> P conversion (VALU work
 # on accumulator data); the kernel fits 184 VGPRs at the same occupancy without them.
 # eve.hip: no FMA contraction, so that a noise draw and the arithmetic on it round the same way at every call site (the generator's
 # tensors fed back as injected noise give the generator path's bits)
 EXTRA_FLAGS = {"attention_f16.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "attention_f16_v3.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+               "attention_prefix.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "eve.hip": ["-ffp-contract=off"]}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
 

@@ -29,7 +29,8 @@ int check_cfg(const pgmi_config* c) {
     if (!c) { set_error("null config"); return PGMI_EINVAL; }
     if (c->abi_version != PGMI_ABI_VERSION) { set_error("ABI version mismatch: got %d, library is %d", c->abi_version, PGMI_ABI_VERSION); return PGMI_EINVAL; }
     if (c->arch != PGMI_ARCH_ESM1B && c->arch != PGMI_ARCH_ESM2 && c->arch != PGMI_ARCH_TRANCEPTION && c->arch != PGMI_ARCH_MSA &&
-        c->arch != PGMI_ARCH_PROGEN2 && c->arch != PGMI_ARCH_GPT && c->arch != PGMI_ARCH_ESMC && c->arch != PGMI_ARCH_SAPROT) { set_error("unknown arch %d", c->arch); return PGMI_EINVAL; }
+        c->arch != PGMI_ARCH_PROGEN2 && c->arch != PGMI_ARCH_GPT && c->arch != PGMI_ARCH_ESMC && c->arch != PGMI_ARCH_SAPROT &&
+        c->arch != PGMI_ARCH_POET) { set_error("unknown arch %d", c->arch); return PGMI_EINVAL; }
     if (c->layers <= 0 || c->embed_dim <= 0 || c->heads <= 0 || c->ffn_dim <= 0) { set_error("non-positive model dimension"); return PGMI_EINVAL; }
     if (c->arch == PGMI_ARCH_ESMC) {
         // the QK-LayerNorm prep pass holds a q / k row of D <= 2048 in registers; FC1's SwiGLU epilogue pairs 32-column blocks
@@ -49,8 +50,13 @@ int check_cfg(const pgmi_config* c) {
         const bool pg2 = c->arch == PGMI_ARCH_PROGEN2;
         // causal decoder: ESM2's layout (RITA XL: head_dim 128)
         const bool esm_layout = c->arch == PGMI_ARCH_ESM1B || c->arch == PGMI_ARCH_ESM2 || c->arch == PGMI_ARCH_GPT || c->arch == PGMI_ARCH_SAPROT;
+        const bool poet = c->arch == PGMI_ARCH_POET;          // interleaved rotary pairs in one slot group: even head dims up to 64
+        if (poet && c->embed_dim % c->heads == 0 && dh > kHeadDim) {
+            set_error("unsupported head_dim %d (embed_dim %d / heads %d): PoET's prefix attention runs even head dims up to 64", dh, c->embed_dim, c->heads);
+            return PGMI_EINVAL;
+        }
         const bool ok = c->embed_dim % c->heads == 0 &&
-                        (dh == kHeadDim || (dh < kHeadDim && dh % 2 == 0 && esm_layout) || (dh == 2 * kHeadDim && esm_layout) ||
+                        (dh == kHeadDim || (dh < kHeadDim && dh % 2 == 0 && (esm_layout || poet)) || (dh == 2 * kHeadDim && esm_layout) ||
                          (pg2 && dh % 2 == 0 && dh <= 4 * kHeadDim));
         if (pg2 && !ok && c->embed_dim % c->heads == 0 && dh > 4 * kHeadDim) {
             set_error("unsupported head_dim %d (embed_dim %d / heads %d): ProGen2 runs even head dims up to 256", dh, c->embed_dim, c->heads);
@@ -77,6 +83,10 @@ int check_cfg(const pgmi_config* c) {
     } else if (c->arch == PGMI_ARCH_SAPROT) {
         if (c->vocab != PGMI_SAPROT_VOCAB) { set_error("SaProt vocab must be %d (5 specials + 21 x 21 residue tokens)", PGMI_SAPROT_VOCAB); return PGMI_EINVAL; }
         if (c->max_positions != 0) { set_error("SaProt has rotary positions: max_positions must be 0"); return PGMI_EINVAL; }
+    } else if (c->arch == PGMI_ARCH_POET) {
+        if (c->vocab <= PGMI_POET_TOK_MASK || c->vocab > kWave) { set_error("PoET vocab must be in [%d, 64], got %d", PGMI_POET_TOK_MASK + 1, c->vocab); return PGMI_EINVAL; }
+        if (c->precision != PGMI_PREC_F16X3) { set_error("PoET is available in precision f16x3 only"); return PGMI_EINVAL; }
+        if (c->max_positions < 0) { set_error("PoET: max_positions is the largest prompt in tokens (0: no prompt)"); return PGMI_EINVAL; }
     } else if (c->vocab != PGMI_VOCAB) { set_error("vocab must be %d", PGMI_VOCAB); return PGMI_EINVAL; }
     if (c->arch == PGMI_ARCH_ESM1B && c->max_positions <= 0) { set_error("ESM-1b arch needs max_positions"); return PGMI_EINVAL; }
     if (c->arch == PGMI_ARCH_MSA) {
@@ -224,6 +234,7 @@ int64_t pgmi_weight_count(const pgmi_config* c) {
     if (c->arch == PGMI_ARCH_PROGEN2)        // include/pgmi.h: the ProGen2 blob
         return V * D + (int64_t)c->layers * (2 * D + 3 * D * D + D * D + (F * D + F) + (D * F + D)) + 2 * D + V * D + V;
     if (c->arch == PGMI_ARCH_GPT) return -1;      // the blob depends on pos_kind: pgmi_gpt_weight_count
+    if (c->arch == PGMI_ARCH_POET) return -1;     // the blob depends on final_norm: pgmi_poet_weight_count
     if (c->arch == PGMI_ARCH_ESMC) return esmc_weight_count(c);
     if (c->arch == PGMI_ARCH_MSA) {
         const int64_t attn = 2 * D + 4 * (D * D + D);
@@ -252,6 +263,11 @@ int pgmi_model_create(const pgmi_config* cfg, const float* w, int64_t n_weights,
     if (cfg && cfg->arch == PGMI_ARCH_SAPROT) {
         if (out) *out = nullptr;
         set_error("SaProt models are created with pgmi_saprot_model_create (it takes the tokenizer's <mask> id)");
+        return PGMI_EINVAL;
+    }
+    if (cfg && cfg->arch == PGMI_ARCH_POET) {
+        if (out) *out = nullptr;
+        set_error("PoET models are created with pgmi_poet_model_create (it takes final_norm)");
         return PGMI_EINVAL;
     }
     return model_create(cfg, w, n_weights, device, out, 0);
@@ -306,13 +322,14 @@ static int alloc_workspace(pgmi_model* m) {
 }
 
 // pgmi_model_create, pgmi_pg2_model_create and pgmi_gpt_model_create; arch_arg is ProGen2's rotary_dim or the causal decoder's
-// pos_kind, SaProt's <mask> id (0 for every other arch)
+// pos_kind, SaProt's <mask> id, PoET's final_norm (0 for every other arch)
 int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int device, pgmi_model** out, int arch_arg) {
     if (!out) { set_error("null out"); return PGMI_EINVAL; }
     *out = nullptr;
     int rc = check_cfg(cfg);
     if (rc) return rc;
-    const int64_t need = cfg->arch == PGMI_ARCH_GPT ? gpt_weight_count(cfg, arch_arg) : pgmi_weight_count(cfg);
+    const int64_t need = cfg->arch == PGMI_ARCH_GPT ? gpt_weight_count(cfg, arch_arg)
+                         : cfg->arch == PGMI_ARCH_POET ? poet_weight_count(cfg, arch_arg) : pgmi_weight_count(cfg);
     if (need < 0) { set_error("causal decoder pos_kind %d: must be PGMI_GPT_POS_ROTARY or PGMI_GPT_POS_LEARNED", arch_arg); return PGMI_EINVAL; }
     if (!w || n_weights != need) {
         set_error("weight blob has %lld elements, config needs %lld", (long long)n_weights, (long long)need);
@@ -343,6 +360,7 @@ int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int 
         case PGMI_ARCH_GPT: rc = create_gpt(m, cfg, w, n_weights, arch_arg); break;
         case PGMI_ARCH_ESMC: rc = create_esmc(m, cfg, w, n_weights); break;
         case PGMI_ARCH_SAPROT: rc = create_saprot(m, cfg, w, n_weights, arch_arg); break;
+        case PGMI_ARCH_POET: rc = create_poet(m, cfg, w, n_weights, arch_arg); break;
         default: rc = create_esm(m, cfg, w, n_weights);
     }
     if (!rc) rc = alloc_workspace(m);

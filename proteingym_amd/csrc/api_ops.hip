@@ -385,6 +385,76 @@ int pgmi_op_causal_attention(int device, int lanes, const float* X, const float*
     return PGMI_OK;
 }
 
+// PoET's prefix attention through launch_prefix_prep / launch_prefix_attention (attention_prefix.hip): the prefix planes are filled by the
+// prep pass over one segment of P rows (as pgmi_poet_set_prompt fills the cache), the own planes by the prep pass over the segments.
+int pgmi_op_prefix_attention(int device, const float* qkv, const int32_t* seg_off, int n_seg, const float* prefix_kv, int P, int heads,
+                             int split, float* ctx) {
+    if (!qkv || !seg_off || !ctx || n_seg <= 0 || heads <= 0 || P < 0 || (P > 0 && !prefix_kv) || seg_off[0] != 0) { set_error("bad argument"); return PGMI_EINVAL; }
+    std::vector<int32_t> ent_seg, ent_tile, pseg{0, P}, pent_seg, pent_tile;
+    for (int b = 0; b < n_seg; ++b) {
+        const int len = seg_off[b + 1] - seg_off[b];
+        if (len <= 0) { set_error("segment %d is empty", b); return PGMI_EINVAL; }
+        for (int j = 0; j * 32 < len; ++j) { ent_seg.push_back(b); ent_tile.push_back(j); }
+    }
+    for (int j = 0; j * 32 < P; ++j) { pent_seg.push_back(0); pent_tile.push_back(j); }
+    if (pgmi_device_count() <= 0) { set_error("no HIP device visible"); return PGMI_ENODEV; }
+    PGMI_HIP(hipSetDevice(device));
+    const size_t R = (size_t)seg_off[n_seg], Da = (size_t)heads * kHeadDim, pitch = ent_seg.size() * 32, ppitch = pent_seg.size() * 32;
+    std::vector<float> pq((size_t)P * 3 * Da, 0.0f);            // the prefix rows as q | k | v with a zero q block
+    for (size_t t = 0; t < (size_t)P; ++t) memcpy(&pq[t * 3 * Da + Da], prefix_kv + t * 2 * Da, 2 * Da * sizeof(float));
+    std::vector<void*> pool;
+    auto cleanup = [&]() { for (void* p : pool) hipFree(p); };
+    float *dq = nullptr, *dpq = nullptr, *dctx = nullptr;
+    int32_t *d_off = nullptr, *d_es = nullptr, *d_et = nullptr, *dp_off = nullptr, *dp_es = nullptr, *dp_et = nullptr;
+    unsigned short *q16 = nullptr, *k16 = nullptr, *vt16 = nullptr, *pq16 = nullptr, *pk16 = nullptr, *pvt16 = nullptr, *c16 = nullptr;
+    int rc = 0;
+    if ((rc = dev_upload(pool, &dq, qkv, R * 3 * Da)) || (rc = dev_upload(pool, &d_off, seg_off, (size_t)n_seg + 1)) ||
+        (rc = dev_upload(pool, &d_es, ent_seg.data(), ent_seg.size())) || (rc = dev_upload(pool, &d_et, ent_tile.data(), ent_tile.size())) ||
+        (rc = dev_alloc(pool, &q16, 2 * R * Da)) || (rc = dev_alloc(pool, &k16, 2 * Da * pitch)) || (rc = dev_alloc(pool, &vt16, 2 * Da * pitch)) ||
+        (rc = dev_alloc(pool, &c16, 2 * R * Da)) || (rc = dev_alloc(pool, &dctx, R * Da)) ||
+        (P > 0 && ((rc = dev_upload(pool, &dpq, pq.data(), pq.size())) || (rc = dev_upload(pool, &dp_off, pseg.data(), pseg.size())) ||
+                   (rc = dev_upload(pool, &dp_es, pent_seg.data(), pent_seg.size())) || (rc = dev_upload(pool, &dp_et, pent_tile.data(), pent_tile.size())) ||
+                   (rc = dev_alloc(pool, &pq16, 2 * (size_t)P * Da)) || (rc = dev_alloc(pool, &pk16, 2 * Da * ppitch)) ||
+                   (rc = dev_alloc(pool, &pvt16, 2 * Da * ppitch))))) {
+        cleanup();
+        return rc;
+    }
+    // what the kernels must write themselves starts as 0xFF bytes (NaN): an operand element or a context row they skip shows
+    hipError_t e = hipMemset(k16, 0xFF, 2 * Da * pitch * 2);
+    if (e == hipSuccess) e = hipMemset(vt16, 0xFF, 2 * Da * pitch * 2);
+    if (e == hipSuccess) e = hipMemset(c16, 0xFF, 2 * R * Da * 2);
+    if (e == hipSuccess) e = hipMemset(dctx, 0xFF, R * Da * 4);
+    if (e == hipSuccess && P > 0) e = hipMemset(pk16, 0xFF, 2 * Da * ppitch * 2);
+    if (e == hipSuccess && P > 0) e = hipMemset(pvt16, 0xFF, 2 * Da * ppitch * 2);
+    if (e != hipSuccess) { cleanup(); set_error("prefix attention op failed: %s", hipGetErrorString(e)); return PGMI_EHIP; }
+    if (P > 0) {
+        PrefixAttLaunch p;
+        p.qkv = dpq; p.seg_off = dp_off; p.ent_seg = dp_es; p.ent_tile = dp_et; p.n_seg = 1; p.n_ent = (int)pent_seg.size(); p.H = heads;
+        p.q16 = pq16; p.q_plane = (size_t)P * Da; p.k16 = pk16; p.vt16 = pvt16; p.pitch = ppitch;
+        rc = launch_prefix_prep(p);
+    }
+    PrefixAttLaunch a;
+    a.qkv = dq; a.seg_off = d_off; a.ent_seg = d_es; a.ent_tile = d_et; a.n_seg = n_seg; a.n_ent = (int)ent_seg.size(); a.H = heads;
+    a.q16 = q16; a.q_plane = R * Da; a.k16 = k16; a.vt16 = vt16; a.pitch = pitch;
+    a.pk16 = pk16; a.pvt16 = pvt16; a.ppitch = ppitch; a.P = P;
+    a.out = split ? ATT_OUT_SPLIT : ATT_OUT_F32; a.ctx = dctx; a.ctx16 = c16;
+    if (!rc) rc = launch_prefix_prep(a);
+    if (!rc) rc = launch_prefix_attention(a);
+    std::vector<unsigned short> h(rc || !split ? 0 : R * Da * 2);
+    e = hipDeviceSynchronize();
+    if (!rc && e == hipSuccess) e = split ? hipMemcpy(h.data(), c16, h.size() * 2, hipMemcpyDeviceToHost) : hipMemcpy(ctx, dctx, R * Da * 4, hipMemcpyDeviceToHost);
+    cleanup();
+    if (rc) return rc;
+    if (e != hipSuccess) { set_error("prefix attention op failed: %s", hipGetErrorString(e)); return PGMI_EHIP; }
+    if (split)
+        for (size_t m = 0; m < R; ++m)
+            for (size_t n = 0; n < Da; ++n) {
+                const size_t o = ki_off(m, (int)n, (int)Da);
+                ctx[m * Da + n] = rebuild_split(h[o], h[o + 32]);
+            }
+    return PGMI_OK;
+}
+
 // The K splits run_msa's rule picks for an alignment of R x C tokens and H heads (host only: no device is touched).
 int pgmi_op_tied_row_splits(int R, int C, int H) {
     if (R <= 0 || C <= 0 || H <= 0) { set_error("bad argument"); return PGMI_EINVAL; }

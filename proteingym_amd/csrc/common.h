@@ -313,6 +313,37 @@ struct AttRagged {
     const int32_t* blk_j;
     int n_tiles, n_blocks;
 };
+// ---- attention_prefix.hip (PoET) ------------------------------------------------------------
+// Segment-causal attention over a shared prefix: n_seg segments of packed rows, each causal within itself, all seeing the P prefix keys
+// unmasked.  The launch's query tiles are a device list of n_ent (segment, 32-position tile) entries in (segment, tile) order; entry e
+// owns the padded rows 32 e .. 32 e + 31 of the own-segment K / V^T planes.  One descriptor serves the prep pass (fp32 q | k | v rows ->
+// planes) and the attention; fields assigned by name.
+struct PrefixAttLaunch {
+    const float* qkv = nullptr;         // prep: fp32 [rows][3 H 64], q pre-scaled by head_dim^-1/2
+    const int32_t* pos = nullptr;       // prep: [rows] rotary position of every packed row (nullptr: no rotary)
+    const float* cos_t = nullptr;       // prep: rotary tables [positions][64] (model.h upload_rotary, one slot group)
+    const float* sin_t = nullptr;
+    const int32_t* seg_off = nullptr;   // [n_seg + 1] first packed row of every segment
+    const int32_t* ent_seg = nullptr;   // [n_ent]
+    const int32_t* ent_tile = nullptr;  // [n_ent]
+    int n_seg = 0, n_ent = 0, H = 0;
+    unsigned short* q16 = nullptr;      // [2][rows][H 64], planes q_plane halfs apart
+    size_t q_plane = 0;
+    unsigned short* k16 = nullptr;      // own segments: [2][H][pitch][64] and [2][H][64][pitch], planes H * pitch * 64 halfs apart
+    unsigned short* vt16 = nullptr;
+    size_t pitch = 0;                   // padded rows the planes are allocated for (multiple of 32, >= 32 n_ent)
+    const unsigned short* pk16 = nullptr;   // the prefix, same layout with pitch ppitch; read when P > 0
+    const unsigned short* pvt16 = nullptr;
+    size_t ppitch = 0;
+    int P = 0;
+    AttOut out = ATT_OUT_SPLIT;         // ATT_OUT_F32 (ctx) or ATT_OUT_SPLIT (ctx16), packed rows of H 64 columns
+    float* ctx = nullptr;
+    unsigned short* ctx16 = nullptr;
+    hipStream_t stream = nullptr;
+};
+int launch_prefix_prep(const PrefixAttLaunch& p);
+int launch_prefix_attention(const PrefixAttLaunch& p);
+
 int att16_waves_per_block(int T);
 int att_set_option(const char* name, long long value);      // "att_xcd_local": block order of the dense attention launches (A/B only)
 // a: qkv, conv, slopes, T, H, the operand planes, ctx16 (ATT_OUT_SPLIT, packed rows) and the stream; B and kv_len are not read

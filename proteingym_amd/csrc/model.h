@@ -10,6 +10,8 @@
 //   api_gpt.hip          causal decoder: RITA / ProtGPT2 weights, the decoder body of RITA / ProtGPT2 / ProGen2 / Tranception (sequential
 //                        or ProGen2's parallel residual; dense or Tranception's ragged prefix-shared rows), narrow and wide LM heads,
 //                        the checks and token log-probs of RITA / ProtGPT2 / ProGen2; RITA / ProtGPT2 sequence log-likelihoods
+//   api_poet.hip         PoET: tiered (within-sequence, then sequence-of-sequences) causal decoder on attention_prefix.hip, the
+//                        per-layer prefix cache of a prompt, variant log-probs and log-likelihoods
 //   api_esmc.hip         ESM C weights (QK-LayerNorm, SwiGLU, scaled residual, untied 64-column head); it runs on run_encoder
 //   api_saprot.hip       SaProt: ESM2's weights and encoder with a 446-token vocabulary; position-set rows and the grouped log-softmax head
 //   api_eve.hip          EVE / DeepSequence: its own handle (pgmi_eve), blob walk, encoder, one ELBO sample, noise seam, the sampling loop
@@ -114,6 +116,15 @@ struct pgmi_model {
     size_t tied_part_cap = 0, tied_p_cap = 0, tied_vt_cap = 0;
     int msa_kv_R = 0, msa_kv_C = 0;
     float ln_eps = 1e-5f;
+    // PoET (api_poet.hip): the per-layer prefix cache -- the prompt's tier-2 K (rotated) and V^T in the operand layout of
+    // attention_prefix.hip, [layers][K | V^T][2 planes][H * poet_pitch * 64] -- for a prompt of at most poet_pitch tokens, the prompt's
+    // length (0: none) and its own log-probability rows; the (segment, tile) lists of the two tiers
+    bool poet_final_norm = false;
+    unsigned short* poet_cache = nullptr;
+    size_t poet_pitch = 0;
+    int poet_P = 0;
+    std::vector<float> poet_prompt_lp;
+    int32_t* poet_meta = nullptr;
     // 16-bit activations: h16_plane = R*D and g16_plane = R*F elements (f16x3: K-interleaved hi | lo rows, 2 halfs per element; bf16: 1
     // half).  They are allocation sizes; no launcher takes them as a stride.
     unsigned short *h16 = nullptr, *g16 = nullptr;
@@ -261,6 +272,9 @@ int decoder_check(pgmi_model* m, int arch, int T);
 int run_decoder(pgmi_model* m, int B, int T, const AttRagged* rg = nullptr, int rows = 0, double att_flops = 0);
 int narrow_head(pgmi_model* m, int M);
 int decoder_token_logprobs(pgmi_model* m, int arch, const int32_t* tokens, int B, int T, float* out);
+// api_poet.hip
+int64_t poet_weight_count(const pgmi_config* c, int final_norm);
+int create_poet(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights, int final_norm);
 // api_esmc.hip
 int64_t esmc_weight_count(const pgmi_config* c);
 int create_esmc(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights);

@@ -25,6 +25,7 @@
 #include "common.h"
 
 #include <stdlib.h>
+#include <algorithm>
 #include <vector>
 
 namespace pgmi {
@@ -181,10 +182,13 @@ __global__ __launch_bounds__(256, 2) void msa_count_kernel(const uint32_t* __res
 
 using namespace pgmi;
 
-extern "C" int pgmi_msa_cluster_counts(int device, const int8_t* matrix, int64_t N, int64_t L, int invalid_value,
-                                       double identity_threshold, int32_t* counts_out, double* kernel_ms) {
-    if (!matrix || !counts_out || N <= 0 || L <= 0) { set_error("pgmi_msa_cluster_counts: null pointer or empty alignment"); return PGMI_EINVAL; }
-    if (!(identity_threshold >= 0.0 && identity_threshold < 1.0)) { set_error("identity_threshold must be in [0, 1), got %g", identity_threshold); return PGMI_EINVAL; }
+// The pair count with one of two predicates on (matches, nongap(i)): the cluster sizes' matches / nongap > identity_threshold, or
+// (neighbors) PoET's 1 - matches / nongap <= identity_threshold (= theta).
+static int pair_counts(int device, const int8_t* matrix, int64_t N, int64_t L, int invalid_value, double identity_threshold, bool neighbors,
+                       int32_t* counts_out, double* kernel_ms) {
+    if (!matrix || !counts_out || N <= 0 || L <= 0) { set_error("%s: null pointer or empty alignment", neighbors ? "pgmi_msa_neighbor_counts" : "pgmi_msa_cluster_counts"); return PGMI_EINVAL; }
+    if (neighbors && !(identity_threshold >= 0.0 && identity_threshold <= 1.0)) { set_error("theta must be in [0, 1], got %g", identity_threshold); return PGMI_EINVAL; }
+    if (!neighbors && !(identity_threshold >= 0.0 && identity_threshold < 1.0)) { set_error("identity_threshold must be in [0, 1), got %g", identity_threshold); return PGMI_EINVAL; }
     if (L > (1 << 24) || N > (int64_t)1 << 30) { set_error("alignment too large (N=%lld, L=%lld)", (long long)N, (long long)L); return PGMI_EINVAL; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device"); return PGMI_ENODEV; }
@@ -230,7 +234,20 @@ extern "C" int pgmi_msa_cluster_counts(int device, const int8_t* matrix, int64_t
     if (flag) { set_error("alignment holds a symbol outside 0..29 that is not invalid_value (%d)", invalid_value); cleanup(); return PGMI_EINVAL; }
     // smallest match count m with (double)m / (double)nongap > threshold, per non-gap length (the
     // reference's own predicate, weights.py:207 / msa_utils.py:345); max mismatches = L - m
-    for (int64_t g = 1; g <= L; ++g) {
+    if (neighbors)
+        for (int64_t i = 0; i < N; ++i)
+            if (ng[(size_t)i] == 0) { set_error("sequence %lld has no non-gap symbol (the reference divides by zero there)", (long long)i); cleanup(); return PGMI_EINVAL; }
+    // neighbours: the smallest match count m with 1.0 - (double)m / (double)nongap <= theta (sampling.py: sim / count, d = 1 - sim,
+    // d <= theta, all float64); the expression is monotone in m, and m = nongap always passes
+    for (int64_t g = 1; neighbors && g <= L; ++g) {
+        auto pass = [&](int64_t m) { return 1.0 - (double)m / (double)g <= identity_threshold; };
+        int64_t m = (int64_t)((1.0 - identity_threshold) * (double)g);
+        m = std::min(std::max(m, (int64_t)0), g);
+        while (m > 0 && pass(m - 1)) --m;
+        while (m < g && !pass(m)) ++m;
+        thr_of[(size_t)g] = (int32_t)(L - m);
+    }
+    for (int64_t g = 1; !neighbors && g <= L; ++g) {
         int64_t m = (int64_t)(identity_threshold * (double)g);
         if (m < 0) m = 0;
         while (m > 0 && (double)(m - 1) / (double)g > identity_threshold) --m;
@@ -252,8 +269,22 @@ extern "C" int pgmi_msa_cluster_counts(int device, const int8_t* matrix, int64_t
     MSA_HIP(hipMemcpyAsync(counts_out, d_cnt, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     MSA_HIP(hipStreamSynchronize(s));
     MSA_HIP(hipGetLastError());
+    // A padding sequence (all gaps, rows N .. Npad-1) mismatches every row in all L columns.  The cluster predicate needs at least one
+    // match, so its bound is below L; the neighbour predicate at theta = 1 accepts zero matches (bound L): the padding is taken out here.
+    for (int64_t i = 0; i < N; ++i)
+        if (mm[(size_t)i] >= (int32_t)L) counts_out[i] -= (int32_t)(Npad - N);
     if (kernel_ms) { float ms = 0; hipEventElapsedTime(&ms, e0, e1); *kernel_ms = ms; }
 #undef MSA_HIP
     cleanup();
     return rc;
+}
+
+extern "C" int pgmi_msa_cluster_counts(int device, const int8_t* matrix, int64_t N, int64_t L, int invalid_value,
+                                       double identity_threshold, int32_t* counts_out, double* kernel_ms) {
+    return pair_counts(device, matrix, N, L, invalid_value, identity_threshold, false, counts_out, kernel_ms);
+}
+
+extern "C" int pgmi_msa_neighbor_counts(int device, const int8_t* matrix, int64_t N, int64_t L, int invalid_value, double theta,
+                                        int32_t* counts_out, double* kernel_ms) {
+    return pair_counts(device, matrix, N, L, invalid_value, theta, true, counts_out, kernel_ms);
 }
