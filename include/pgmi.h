@@ -62,6 +62,10 @@ extern "C" {
 /* PoET (proteingym/baselines/PoET/poet/models/poet.py): tiered causal decoder over a sequence-of-sequences, scored against a cached
  * prompt; created with pgmi_poet_model_create, scored with pgmi_poet_* (see the PoET section below) */
 #define PGMI_ARCH_POET 9
+/* ProGen3 (proteingym/baselines/progen3/progen3/modeling.py): pre-RMSNorm causal decoder with grouped-query attention, rotate-half
+ * rotary and a routed mixture-of-experts feed-forward block; created with pgmi_pg3_model_create, scored with pgmi_pg3_* (see the
+ * ProGen3 section below) */
+#define PGMI_ARCH_PROGEN3 10
 
 /* GEMM operand precision.  Residual stream, LayerNorm statistics, softmax and every
  * accumulator are fp32 in all modes. */
@@ -225,7 +229,8 @@ void pgmi_optimal_window(int position, int seq_len_with_special, int model_windo
 #define PGMI_K_HEAD 7
 #define PGMI_K_SCORE 8
 #define PGMI_K_KEPT_ROWS 9   /* last layer after attention, on the kept (masked) rows only: gathers + out-projection + LN + FFN */
-#define PGMI_K_COUNT 10
+#define PGMI_K_MOE_ROUTE 10  /* ProGen3: permutation, gather and weighted combine around the expert GEMMs (the router rides in PGMI_K_LAYERNORM) */
+#define PGMI_K_COUNT 11
 /* on != 0: every launch of the classes above is bracketed by hipEventRecord on the stream. */
 int pgmi_profile_enable(pgmi_model* m, int on);
 /* Sum of event-measured milliseconds, launch count and algorithmic FLOPs / bytes for a class
@@ -300,6 +305,15 @@ int pgmi_op_causal_attention(int device, int lanes, const float* X, const float*
  * split != 0: the split-plane context the out-projection consumes, rebuilt as fp32; 0: the kernel's fp32 rows. */
 int pgmi_op_prefix_attention(int device, const float* qkv, const int32_t* seg_off, int n_seg, const float* prefix_kv, int P, int heads,
                              int split, float* ctx);
+/* ProGen3's pieces (elementwise.hip rmsnorm16_kernel, moe.hip, api_progen3.hip moe_ffn) on their own buffers.
+ * pgmi_op_rmsnorm: y [rows][D] = the split operand launch_rmsnorm16 writes, rebuilt as fp32 (hi + lo 2^-11); D % 32 == 0, D <= 5120.
+ * pgmi_op_moe: the routed block on fp32 rows h [M][D] taken as they are (no norm): gate [E][D] (ignored when E == 1); w1 [E][F][D],
+ *   w3 [E][F][D] (gated != 0, else ignored), w2 [E][D][F].  out [M][D] = sum_k weight_k * expert_k(h) (fp32); ids int32 [M][top_k] and
+ *   weights f32 [M][top_k] (nullable; E == 1: not written).  The experts run through the model's own path: router, permutation,
+ *   gather, one launch_gemm16 pair per non-empty expert, combine. */
+int pgmi_op_rmsnorm(int device, const float* x, const float* w, int rows, int D, float eps, float* y);
+int pgmi_op_moe(int device, const float* h, const float* gate, const float* w1, const float* w3, const float* w2, int M, int D, int F,
+                int E, int top_k, int gated, float* out, int32_t* ids, float* weights);
 int pgmi_op_tied_row_attention(int device, const float* qkv, int R, int C, int H, int splits, float* ctx, float* probs);
 int pgmi_op_tied_row_splits(int R, int C, int H);
 int pgmi_op_column_attention(int device, const float* X, const float* W, const float* bias, int K, int R, int C, int H, float* ctx);
@@ -420,6 +434,49 @@ int64_t pgmi_gpt_weight_count(const pgmi_config* cfg, int pos_kind);
 int pgmi_gpt_model_create(const pgmi_config* cfg, int pos_kind, const float* weights, int64_t n_weights, int device, pgmi_model** out);
 int pgmi_gpt_token_logprobs(pgmi_model* m, const int32_t* tokens, int B, int T, float* out);
 int pgmi_gpt_sequence_loglik(pgmi_model* m, const int32_t* tokens, const int32_t* lens, int B, int T, double* sum, int32_t* n_targets);
+
+/* ---- ProGen3 (arch PGMI_ARCH_PROGEN3; vocab > 64, max_positions = rotary table rows, precision f16x3) ----------------------------
+ * Tokens (progen3/tokenizer.json): <pad> 0, <bos> 1, <eos> 2, "1" 6, "2" 7, letters A 8 .. Y 32; a sequence is <bos> 1 SEQ 2 <eos>.
+ * Embedding: embed_tokens[id] + embed_seq_id[0] (one sequence per row: sequence_ids are all zero), folded into one table at creation.
+ * Per layer: x += o_proj(attn(rmsnorm(x))); x += moe(rmsnorm(x)); no bias anywhere; rmsnorm(x) = x * rsqrt(mean(x^2) + ln_eps) * w.
+ * Attention: heads query heads on kv_heads key / value heads (heads % kv_heads == 0; query head h reads K/V head h / (heads / kv_heads)),
+ *   rotate-half rotary over the whole head, inv_freq = rope_theta^(-2j/head_dim), angle = fp32(t) * fp32(inv_freq), causal, scores
+ *   scaled by head_dim^-1/2.  head_dim = D / heads in {64, 80, 96, 128, 256}.  The K/V projection rows are replicated to their query heads
+ *   when the fused QKV weight is packed, so the attention kernels see heads full heads.  clip_qkv must be 0 (unset): the clamp sits
+ *   between the projection and the rotary, inside the fused epilogue.
+ * MoE (model/moe.py SparseMoeBlock): p = softmax_fp32(gate h); the top_k largest p (ties: lower index), divided by their sum, weigh
+ *   w2(silu(w1 h) * w3 h) (gated) or w2(silu(w1 h)) of the chosen experts.  n_experts == 1: the plain MLP, no gate.  2 <= n_experts <= 64
+ *   otherwise.  Rows whose token is <pad> are not routed.
+ * Then the final rmsnorm and the untied lm_head [V,D]; log-softmax over all V columns.
+ * Weight blob order (fp32, nn.Linear layout [out,in]):
+ *   model.embed_tokens [V,D]; model.embed_seq_id row 0 [D];
+ *   per layer: input_layernorm w [D]; q_proj [D,D]; k_proj [kv_heads * head_dim, D]; v_proj (same); o_proj [D,D];
+ *        post_attention_layernorm w [D]; (n_experts > 1) gate [E,D]; per expert: w1 [F,D]; (gated) w3 [F,D]; w2 [D,F];
+ *   model.norm w [D]; lm_head [V,D].
+ *
+ * pgmi_pg3_weight_count: the blob size for (cfg, params); <0 on a bad cfg.  (pgmi_weight_count returns -1 for this arch.)
+ * pgmi_pg3_model_create: as pgmi_model_create, with params.  Returns an ordinary model: destroy, profile, synchronize as usual.
+ * pgmi_pg3_token_logprobs: tokens int32 [B,T] right-padded with <pad> (0), T <= max_positions; out f32 [B,T,V] = log_softmax(logits);
+ *   rows of <pad> tokens hold values nobody should read.
+ * pgmi_pg3_sequence_loglik: the signature and meaning of pgmi_gpt_sequence_loglik: B rows right-padded to T, row b holding lens[b] >= 2
+ *   real tokens (none of them <pad>); sum[b] = sum over t < lens[b]-1 of log p(tokens[b,t+1] | tokens[b,<=t]), fp32 terms summed in
+ *   double left to right; n_targets[b] = lens[b]-1.  A row's result has the same bits whatever else is in the batch.
+ * pgmi_pg3_routing: the experts and weights the last forward chose in `layer` for its first `rows` token rows (row = b * T_in + t of
+ *   the last device chunk; T_in = T - 1 after pgmi_pg3_sequence_loglik): ids int32 [rows][top_k] (-1: a <pad> row), weights f32. */
+typedef struct pgmi_pg3_params {
+    int32_t kv_heads;             /* num_key_value_heads */
+    int32_t n_experts;            /* num_experts */
+    int32_t top_k;                /* num_experts_per_tok (<= n_experts) */
+    int32_t gated;                /* gated_mlp */
+    float rope_theta;
+    float clip_qkv;               /* 0 = unset; anything else is refused */
+} pgmi_pg3_params;
+int64_t pgmi_pg3_weight_count(const pgmi_config* cfg, const pgmi_pg3_params* params);
+int pgmi_pg3_model_create(const pgmi_config* cfg, const pgmi_pg3_params* params, const float* weights, int64_t n_weights, int device,
+                          pgmi_model** out);
+int pgmi_pg3_token_logprobs(pgmi_model* m, const int32_t* tokens, int B, int T, float* out);
+int pgmi_pg3_sequence_loglik(pgmi_model* m, const int32_t* tokens, const int32_t* lens, int B, int T, double* sum, int32_t* n_targets);
+int pgmi_pg3_routing(pgmi_model* m, int layer, int rows, int32_t* ids, float* weights);
 
 /* ---- ESM C (arch PGMI_ARCH_ESMC; vocab 64, head_dim 64, embed_dim <= 2048, ffn_dim = the SwiGLU hidden width F, precision f16x3) --
  * Per block: x += out_proj(attn(x)) / s; x += ffn(x) / s with s = sqrt(layers / 36) (transformer_stack.py:50, blocks.py:150-162).

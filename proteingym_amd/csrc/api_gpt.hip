@@ -9,7 +9,8 @@
 // Tranception's layers (L.conv) project into fp32 rows whose depth-wise convolution runs in the attention's prep pass, with its grouped
 // ALiBi slopes, and FC1 ends in its squared ReLU.  Heads: V <= 64 (RITA: 26, ProGen2: 32) on one wave per row (vocab_logsoftmax_kernel);
 // wider ones (ProtGPT2: 50 257, tied to wte) on the f16x3 GEMM into fp32 logits, then one workgroup per row (wide_logsoftmax_kernel).
-// When scoring, only the rows that have a target reach the head.
+// When scoring, only the rows that have a target reach the head.  ProGen3 (api_progen3.hip) runs on the same body with RMSNorm in place
+// of LayerNorm and its routed expert block in place of the dense MLP, and on the wide head.
 #include "model.h"
 
 namespace pgmi {
@@ -78,11 +79,19 @@ int create_gpt(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_
     return rc;
 }
 
+// A layer's or the head's norm of fp32 rows into the f16x3 split operand: LayerNorm, or ProGen3's weight-only RMSNorm (m->rms_norm)
+static int norm16(pgmi_model* m, const float* x, const float* w, const float* b, int rows, unsigned short* y16) {
+    if (m->rms_norm) return launch_rmsnorm16(x, w, rows, m->cfg.embed_dim, m->ln_eps, y16, m->stream);
+    launch_layernorm16(x, w, b, rows, m->cfg.embed_dim, m->ln_eps, y16, 1, m->stream);
+    return PGMI_OK;
+}
+
 // The decoder body on tokens in m->tokens; leaves the residual stream after the last layer in m->x.  Dense: B sequences of T tokens,
 // [B*T, D].  Ragged (rg != nullptr; Tranception's prefix-shared scoring, api_tranception.hip): `rows` packed suffix rows of sequences
 // of T tokens, their attention over rg (att_flops for the profile).  What differs per model is data: the position kind (rotary tables
 // rot_cos, a learned table embed_positions, or none), a layer's depth-wise convolution (L.conv), the slopes, FC1's epilogue and the
-// residual order.
+// residual order, the norm (LayerNorm, or ProGen3's RMSNorm) and the feed-forward block (dense, or ProGen3's routed experts: pg3_ffn,
+// which runs the layer's second norm itself, fused with its router).
 int run_decoder(pgmi_model* m, int B, int T, const AttRagged* rg, int rows, double att_flops) {
     const pgmi_config& c = m->cfg;
     const int M = rg ? rows : B * T, D = c.embed_dim, F = c.ffn_dim, H = c.heads, Da = m->Da;
@@ -104,7 +113,8 @@ int run_decoder(pgmi_model* m, int B, int T, const AttRagged* rg, int rows, doub
     for (int l = 0; l < c.layers; ++l) {
         const Layer& L = m->layers[l];
         { ProfScope p(m, PGMI_K_LAYERNORM, 0, ln_bytes);
-          launch_layernorm16(m->x, L.ln1_w, L.ln1_b, M, D, m->ln_eps, m->h16, 1, s); }
+          rc = norm16(m, m->x, L.ln1_w, L.ln1_b, M, m->h16);
+          if (rc) return rc; }
         { ProfScope p(m, PGMI_K_GEMM_QKV, 2.0 * M * 3 * Da * D, 0);
           if (L.conv)                           // fp32 q | k | v rows: the attention's prep pass convolves and splits them
               rc = linear(m, nullptr, m->h16, nullptr, L.wqkv16, L.bqkv, nullptr, m->qkv, nullptr, M, 3 * Da, D, EPI_NONE);
@@ -131,7 +141,10 @@ int run_decoder(pgmi_model* m, int B, int T, const AttRagged* rg, int rows, doub
         { ProfScope p(m, PGMI_K_GEMM_OUT, 2.0 * M * D * Da, 0);
           rc = linear(m, nullptr, m->h16, nullptr, L.wo16, L.bo, m->x, m->x, nullptr, M, D, Da, EPI_NONE);
           if (rc) return rc; }
-        if (!m->parallel_residual) {
+        if (c.arch == PGMI_ARCH_PROGEN3) {
+            rc = pg3_ffn(m, L, l, M);
+            if (rc) return rc;
+        } else if (!m->parallel_residual) {
             { ProfScope p(m, PGMI_K_LAYERNORM, 0, ln_bytes);
               launch_layernorm16(m->x, L.ln2_w, L.ln2_b, M, D, m->ln_eps, m->h16, 1, s); }
             rc = mlp(L);
@@ -174,10 +187,11 @@ static int wide_head_rows(pgmi_model* m, int R, const int32_t* tgt, float* out, 
 
 // Arch, context and workspace checks of a causal-decoder entry for input length T; `arch` is the entry's, the messages its own.
 int decoder_check(pgmi_model* m, int arch, int T) {
-    const bool pg2 = arch == PGMI_ARCH_PROGEN2;
-    if (m->cfg.arch != arch) { set_error(pg2 ? "not a ProGen2 model" : "not a causal decoder (RITA / ProtGPT2) model"); return PGMI_EINVAL; }
+    const bool pg2 = arch == PGMI_ARCH_PROGEN2, pg3 = arch == PGMI_ARCH_PROGEN3;
+    if (m->cfg.arch != arch) { set_error(pg2 ? "not a ProGen2 model" : pg3 ? "not a ProGen3 model" : "not a causal decoder (RITA / ProtGPT2) model"); return PGMI_EINVAL; }
     if (T > m->cfg.max_positions) {
         set_error(pg2 ? "sequence of %d tokens exceeds the model context n_positions=%d"
+                  : pg3 ? "sequence of %d tokens exceeds the rotary table of max_positions=%d rows"
                       : "sequence of %d tokens exceeds the model context of %d positions", T, m->cfg.max_positions);
         return PGMI_EINVAL;
     }
@@ -204,7 +218,8 @@ int decoder_token_logprobs(pgmi_model* m, int arch, const int32_t* tokens, int B
         float* dst = out + (size_t)b0 * T * V;
         if (wide_head(c)) {
             { ProfScope p(m, PGMI_K_LAYERNORM, 0, 2.0 * M * D * 4);
-              launch_layernorm16(m->x, m->lna_w, m->lna_b, M, D, m->ln_eps, m->h16, 1, s); }
+              rc = norm16(m, m->x, m->lna_w, m->lna_b, M, m->h16);
+              if (rc) return rc; }
             return wide_head_rows(m, M, nullptr, nullptr, dst);
         }
         rc = narrow_head(m, M);
@@ -215,30 +230,13 @@ int decoder_token_logprobs(pgmi_model* m, int arch, const int32_t* tokens, int B
     return rc ? rc : check_nonfinite(m);
 }
 
-}  // namespace pgmi
-
-extern "C" {
-
-int64_t pgmi_gpt_weight_count(const pgmi_config* cfg, int pos_kind) {
-    if (!cfg || cfg->layers <= 0 || cfg->embed_dim <= 0 || cfg->ffn_dim <= 0 || cfg->vocab <= 0 || cfg->max_positions <= 0) return -1;
-    return gpt_weight_count(cfg, pos_kind);
-}
-
-int pgmi_gpt_model_create(const pgmi_config* cfg, int pos_kind, const float* weights, int64_t n_weights, int device, pgmi_model** out) {
-    if (out) *out = nullptr;
-    if (!cfg || cfg->arch != PGMI_ARCH_GPT) { set_error("pgmi_gpt_model_create: arch must be PGMI_ARCH_GPT"); return PGMI_EINVAL; }
-    return model_create(cfg, weights, n_weights, device, out, pos_kind);
-}
-
-int pgmi_gpt_token_logprobs(pgmi_model* m, const int32_t* tokens, int B, int T, float* out) {
-    return decoder_token_logprobs(m, PGMI_ARCH_GPT, tokens, B, T, out);
-}
-
-int pgmi_gpt_sequence_loglik(pgmi_model* m, const int32_t* tokens, const int32_t* lens, int B, int T, double* sum, int32_t* n_targets) {
+// pgmi_gpt_sequence_loglik and pgmi_pg3_sequence_loglik.  ProGen3: the positions beyond a row's length go in as <pad> (0), which its
+// router leaves out; a <pad> among a row's real tokens is refused.
+int decoder_sequence_loglik(pgmi_model* m, int arch, const int32_t* tokens, const int32_t* lens, int B, int T, double* sum, int32_t* n_targets) {
     if (!m || !tokens || !lens || !sum || B <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
     if (T < 2) { set_error("rows of %d tokens: the model needs at least one input and one target token", T); return PGMI_EINVAL; }
     const int Ti = T - 1;                                           // the model reads tokens[:, :T-1]; targets are tokens[:, 1:]
-    int rc = decoder_check(m, PGMI_ARCH_GPT, Ti);
+    int rc = decoder_check(m, arch, Ti);
     if (!rc) rc = check_vocab(tokens, B, T, m->cfg.vocab);
     if (rc) return rc;
     for (int b = 0; b < B; ++b)
@@ -247,6 +245,12 @@ int pgmi_gpt_sequence_loglik(pgmi_model* m, const int32_t* tokens, const int32_t
     const int D = c.embed_dim, V = c.vocab;
     std::vector<int32_t> in((size_t)B * Ti), idx, tgt, off;
     for (int b = 0; b < B; ++b) memcpy(&in[(size_t)b * Ti], tokens + (size_t)b * T, (size_t)Ti * 4);
+    if (arch == PGMI_ARCH_PROGEN3)
+        for (int b = 0; b < B; ++b) {
+            for (int t = 0; t < lens[b]; ++t)
+                if (tokens[(size_t)b * T + t] == 0) { set_error("row %d of this call: <pad> at position %d, inside its %d tokens", b, t, lens[b]); return PGMI_EINVAL; }
+            for (int t = lens[b]; t < Ti; ++t) in[(size_t)b * Ti + t] = 0;
+        }
     PGMI_HIP(hipSetDevice(m->device));
     hipStream_t s = m->stream;
     rc = for_each_chunk(m, B, Ti, [&](int b0, int bc) {
@@ -271,7 +275,8 @@ int pgmi_gpt_sequence_loglik(pgmi_model* m, const int32_t* tokens, const int32_t
           launch_gather_rows(m->x, m->row_idx, R, D, m->g, s); }                 // pad rows and last rows never reach the head
         if (wide_head(c)) {
             { ProfScope p(m, PGMI_K_LAYERNORM, 0, 2.0 * R * D * 4);
-              launch_layernorm16(m->g, m->lna_w, m->lna_b, R, D, m->ln_eps, m->h16, 1, s); }
+              rc = norm16(m, m->g, m->lna_w, m->lna_b, R, m->h16);
+              if (rc) return rc; }
             rc = wide_head_rows(m, R, m->aux_i, m->denom, nullptr);
             if (rc) return rc;
         } else {
@@ -289,6 +294,29 @@ int pgmi_gpt_sequence_loglik(pgmi_model* m, const int32_t* tokens, const int32_t
     if (n_targets)
         for (int b = 0; b < B; ++b) n_targets[b] = lens[b] - 1;
     return check_nonfinite(m);
+}
+
+}  // namespace pgmi
+
+extern "C" {
+
+int64_t pgmi_gpt_weight_count(const pgmi_config* cfg, int pos_kind) {
+    if (!cfg || cfg->layers <= 0 || cfg->embed_dim <= 0 || cfg->ffn_dim <= 0 || cfg->vocab <= 0 || cfg->max_positions <= 0) return -1;
+    return gpt_weight_count(cfg, pos_kind);
+}
+
+int pgmi_gpt_model_create(const pgmi_config* cfg, int pos_kind, const float* weights, int64_t n_weights, int device, pgmi_model** out) {
+    if (out) *out = nullptr;
+    if (!cfg || cfg->arch != PGMI_ARCH_GPT) { set_error("pgmi_gpt_model_create: arch must be PGMI_ARCH_GPT"); return PGMI_EINVAL; }
+    return model_create(cfg, weights, n_weights, device, out, pos_kind);
+}
+
+int pgmi_gpt_token_logprobs(pgmi_model* m, const int32_t* tokens, int B, int T, float* out) {
+    return decoder_token_logprobs(m, PGMI_ARCH_GPT, tokens, B, T, out);
+}
+
+int pgmi_gpt_sequence_loglik(pgmi_model* m, const int32_t* tokens, const int32_t* lens, int B, int T, double* sum, int32_t* n_targets) {
+    return decoder_sequence_loglik(m, PGMI_ARCH_GPT, tokens, lens, B, T, sum, n_targets);
 }
 
 }  // extern "C"

@@ -30,7 +30,7 @@ int check_cfg(const pgmi_config* c) {
     if (c->abi_version != PGMI_ABI_VERSION) { set_error("ABI version mismatch: got %d, library is %d", c->abi_version, PGMI_ABI_VERSION); return PGMI_EINVAL; }
     if (c->arch != PGMI_ARCH_ESM1B && c->arch != PGMI_ARCH_ESM2 && c->arch != PGMI_ARCH_TRANCEPTION && c->arch != PGMI_ARCH_MSA &&
         c->arch != PGMI_ARCH_PROGEN2 && c->arch != PGMI_ARCH_GPT && c->arch != PGMI_ARCH_ESMC && c->arch != PGMI_ARCH_SAPROT &&
-        c->arch != PGMI_ARCH_POET) { set_error("unknown arch %d", c->arch); return PGMI_EINVAL; }
+        c->arch != PGMI_ARCH_POET && c->arch != PGMI_ARCH_PROGEN3) { set_error("unknown arch %d", c->arch); return PGMI_EINVAL; }
     if (c->layers <= 0 || c->embed_dim <= 0 || c->heads <= 0 || c->ffn_dim <= 0) { set_error("non-positive model dimension"); return PGMI_EINVAL; }
     if (c->arch == PGMI_ARCH_ESMC) {
         // the QK-LayerNorm prep pass holds a q / k row of D <= 2048 in registers; FC1's SwiGLU epilogue pairs 32-column blocks
@@ -50,6 +50,11 @@ int check_cfg(const pgmi_config* c) {
         const bool pg2 = c->arch == PGMI_ARCH_PROGEN2;
         // causal decoder: ESM2's layout (RITA XL: head_dim 128)
         const bool esm_layout = c->arch == PGMI_ARCH_ESM1B || c->arch == PGMI_ARCH_ESM2 || c->arch == PGMI_ARCH_GPT || c->arch == PGMI_ARCH_SAPROT;
+        const bool pg3 = c->arch == PGMI_ARCH_PROGEN3;        // what the causal attention runs: 64, 128 and ProGen2's padded 80 / 96 / 256
+        if (pg3 && (c->embed_dim % c->heads || (dh != 64 && dh != 80 && dh != 96 && dh != 128 && dh != 256))) {
+            set_error("unsupported head_dim %d (embed_dim %d / heads %d): ProGen3 runs head dims 64, 80, 96, 128 and 256", dh, c->embed_dim, c->heads);
+            return PGMI_EINVAL;
+        }
         const bool poet = c->arch == PGMI_ARCH_POET;          // interleaved rotary pairs in one slot group: even head dims up to 64
         if (poet && c->embed_dim % c->heads == 0 && dh > kHeadDim) {
             set_error("unsupported head_dim %d (embed_dim %d / heads %d): PoET's prefix attention runs even head dims up to 64", dh, c->embed_dim, c->heads);
@@ -57,7 +62,7 @@ int check_cfg(const pgmi_config* c) {
         }
         const bool ok = c->embed_dim % c->heads == 0 &&
                         (dh == kHeadDim || (dh < kHeadDim && dh % 2 == 0 && (esm_layout || poet)) || (dh == 2 * kHeadDim && esm_layout) ||
-                         (pg2 && dh % 2 == 0 && dh <= 4 * kHeadDim));
+                         (pg2 && dh % 2 == 0 && dh <= 4 * kHeadDim) || pg3);
         if (pg2 && !ok && c->embed_dim % c->heads == 0 && dh > 4 * kHeadDim) {
             set_error("unsupported head_dim %d (embed_dim %d / heads %d): ProGen2 runs even head dims up to 256", dh, c->embed_dim, c->heads);
             return PGMI_EINVAL;
@@ -87,6 +92,10 @@ int check_cfg(const pgmi_config* c) {
         if (c->vocab <= PGMI_POET_TOK_MASK || c->vocab > kWave) { set_error("PoET vocab must be in [%d, 64], got %d", PGMI_POET_TOK_MASK + 1, c->vocab); return PGMI_EINVAL; }
         if (c->precision != PGMI_PREC_F16X3) { set_error("PoET is available in precision f16x3 only"); return PGMI_EINVAL; }
         if (c->max_positions < 0) { set_error("PoET: max_positions is the largest prompt in tokens (0: no prompt)"); return PGMI_EINVAL; }
+    } else if (c->arch == PGMI_ARCH_PROGEN3) {
+        if (c->vocab <= kWave) { set_error("ProGen3 vocab must be above 64 (the wide LM head), got %d", c->vocab); return PGMI_EINVAL; }
+        if (c->precision != PGMI_PREC_F16X3) { set_error("ProGen3 is available in precision f16x3 only"); return PGMI_EINVAL; }
+        if (c->max_positions <= 0) { set_error("ProGen3 needs max_positions = the rotary table's rows"); return PGMI_EINVAL; }
     } else if (c->vocab != PGMI_VOCAB) { set_error("vocab must be %d", PGMI_VOCAB); return PGMI_EINVAL; }
     if (c->arch == PGMI_ARCH_ESM1B && c->max_positions <= 0) { set_error("ESM-1b arch needs max_positions"); return PGMI_EINVAL; }
     if (c->arch == PGMI_ARCH_MSA) {
@@ -235,6 +244,7 @@ int64_t pgmi_weight_count(const pgmi_config* c) {
         return V * D + (int64_t)c->layers * (2 * D + 3 * D * D + D * D + (F * D + F) + (D * F + D)) + 2 * D + V * D + V;
     if (c->arch == PGMI_ARCH_GPT) return -1;      // the blob depends on pos_kind: pgmi_gpt_weight_count
     if (c->arch == PGMI_ARCH_POET) return -1;     // the blob depends on final_norm: pgmi_poet_weight_count
+    if (c->arch == PGMI_ARCH_PROGEN3) return -1;  // the blob depends on pgmi_pg3_params: pgmi_pg3_weight_count
     if (c->arch == PGMI_ARCH_ESMC) return esmc_weight_count(c);
     if (c->arch == PGMI_ARCH_MSA) {
         const int64_t attn = 2 * D + 4 * (D * D + D);
@@ -268,6 +278,11 @@ int pgmi_model_create(const pgmi_config* cfg, const float* w, int64_t n_weights,
     if (cfg && cfg->arch == PGMI_ARCH_POET) {
         if (out) *out = nullptr;
         set_error("PoET models are created with pgmi_poet_model_create (it takes final_norm)");
+        return PGMI_EINVAL;
+    }
+    if (cfg && cfg->arch == PGMI_ARCH_PROGEN3) {
+        if (out) *out = nullptr;
+        set_error("ProGen3 models are created with pgmi_pg3_model_create (it takes pgmi_pg3_params)");
         return PGMI_EINVAL;
     }
     return model_create(cfg, w, n_weights, device, out, 0);
@@ -308,7 +323,7 @@ static int alloc_workspace(pgmi_model* m) {
         alloc(&m->msa_kv_len, (size_t)2048);
     }
     // the wide causal-decoder head writes its full rows per head chunk (api_gpt.hip): R * V would be ~20 GB at V = 50 257
-    alloc(&m->lp, (c.arch == PGMI_ARCH_GPT && V > kWave ? (size_t)m->gpt_head_rows : R) * V);
+    alloc(&m->lp, ((c.arch == PGMI_ARCH_GPT || c.arch == PGMI_ARCH_PROGEN3) && V > kWave ? (size_t)m->gpt_head_rows : R) * V);
     alloc(&m->denom, R);
     alloc(&m->tokens, R);
     alloc(&m->pos_idx, R);
@@ -322,13 +337,16 @@ static int alloc_workspace(pgmi_model* m) {
 }
 
 // pgmi_model_create, pgmi_pg2_model_create and pgmi_gpt_model_create; arch_arg is ProGen2's rotary_dim or the causal decoder's
-// pos_kind, SaProt's <mask> id, PoET's final_norm (0 for every other arch)
-int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int device, pgmi_model** out, int arch_arg) {
+// pos_kind, SaProt's <mask> id, PoET's final_norm (0 for every other arch); pg3: ProGen3's parameters
+int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int device, pgmi_model** out, int arch_arg,
+                 const pgmi_pg3_params* pg3) {
     if (!out) { set_error("null out"); return PGMI_EINVAL; }
     *out = nullptr;
     int rc = check_cfg(cfg);
     if (rc) return rc;
+    if (cfg->arch == PGMI_ARCH_PROGEN3 && (rc = pg3_check(cfg, pg3))) return rc;
     const int64_t need = cfg->arch == PGMI_ARCH_GPT ? gpt_weight_count(cfg, arch_arg)
+                         : cfg->arch == PGMI_ARCH_PROGEN3 ? pg3_weight_count(cfg, pg3)
                          : cfg->arch == PGMI_ARCH_POET ? poet_weight_count(cfg, arch_arg) : pgmi_weight_count(cfg);
     if (need < 0) { set_error("causal decoder pos_kind %d: must be PGMI_GPT_POS_ROTARY or PGMI_GPT_POS_LEARNED", arch_arg); return PGMI_EINVAL; }
     if (!w || n_weights != need) {
@@ -361,6 +379,7 @@ int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int 
         case PGMI_ARCH_ESMC: rc = create_esmc(m, cfg, w, n_weights); break;
         case PGMI_ARCH_SAPROT: rc = create_saprot(m, cfg, w, n_weights, arch_arg); break;
         case PGMI_ARCH_POET: rc = create_poet(m, cfg, w, n_weights, arch_arg); break;
+        case PGMI_ARCH_PROGEN3: rc = create_progen3(m, cfg, w, n_weights, pg3); break;
         default: rc = create_esm(m, cfg, w, n_weights);
     }
     if (!rc) rc = alloc_workspace(m);
@@ -393,6 +412,7 @@ void pgmi_model_destroy(pgmi_model* m) {
     }
     m->pppls.clear();
     for (auto& e : m->events) { hipEventDestroy(e.start); hipEventDestroy(e.stop); }
+    if (m->moe.counts_host) hipHostFree(m->moe.counts_host);
     for (void* p : m->allocs) hipFree(p);
     if (m->stream) hipStreamDestroy(m->stream);
     delete m;

@@ -30,6 +30,92 @@ int pgmi_op_layernorm(int device, const float* x, const float* w, const float* b
     return PGMI_OK;
 }
 
+int pgmi_op_rmsnorm(int device, const float* x, const float* w, int rows, int D, float eps, float* y) {
+    if (!x || !w || !y || rows <= 0 || D <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
+    if (D % 32) { set_error("rmsnorm op: D = %d is not a multiple of 32 (the K-interleaved operand)", D); return PGMI_EINVAL; }
+    if (pgmi_device_count() <= 0) { set_error("no HIP device visible"); return PGMI_ENODEV; }
+    PGMI_HIP(hipSetDevice(device));
+    std::vector<void*> pool;
+    auto cleanup = [&]() { for (void* p : pool) hipFree(p); };
+    float *dx = nullptr, *dw = nullptr;
+    unsigned short* y16 = nullptr;
+    int rc = 0;
+    if ((rc = dev_upload(pool, &dx, x, (size_t)rows * D)) || (rc = dev_upload(pool, &dw, w, (size_t)D)) ||
+        (rc = dev_alloc(pool, &y16, (size_t)rows * D * 2))) {
+        cleanup();
+        return rc;
+    }
+    hipError_t e = hipMemset(y16, 0xFF, (size_t)rows * D * 2 * sizeof(unsigned short));     // an element the kernel skips shows as NaN
+    if (e == hipSuccess) rc = launch_rmsnorm16(dx, dw, rows, D, eps, y16, nullptr);
+    std::vector<unsigned short> h(rc ? 0 : (size_t)rows * D * 2);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (!rc && e == hipSuccess) e = hipMemcpy(h.data(), y16, h.size() * 2, hipMemcpyDeviceToHost);
+    cleanup();
+    if (rc) return rc;
+    if (e != hipSuccess) { set_error("rmsnorm op failed: %s", hipGetErrorString(e)); return PGMI_EHIP; }
+    for (size_t m = 0; m < (size_t)rows; ++m)
+        for (int n = 0; n < D; ++n) {
+            const size_t o = ki_off(m, n, D);
+            y[m * D + n] = rebuild_split(h[o], h[o + 32]);
+        }
+    return PGMI_OK;
+}
+
+// ProGen3's feed-forward block (api_progen3.hip pg3_ffn without the norm) on rows taken as they are: the router kernel splits them and
+// routes them, then moe_ffn (or, for one expert, dense_ffn) adds the block's output into a zeroed x.
+int pgmi_op_moe(int device, const float* h, const float* gate, const float* w1, const float* w3, const float* w2, int M, int D, int F,
+                int E, int top_k, int gated, float* out, int32_t* ids, float* weights) {
+    if (!h || !w1 || !w2 || !out || (gated && !w3) || (E > 1 && !gate) || M <= 0 || D <= 0 || F <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
+    if (D % 32 || F % 32) { set_error("moe op: D = %d and F = %d must be multiples of 32", D, F); return PGMI_EINVAL; }
+    if (E < 1 || E > kWave || top_k < 1 || top_k > E) { set_error("moe op: %d experts, top-%d: 1 .. 64 experts, 1 <= top_k <= experts", E, top_k); return PGMI_EINVAL; }
+    if (pgmi_device_count() <= 0) { set_error("no HIP device visible"); return PGMI_ENODEV; }
+    PGMI_HIP(hipSetDevice(device));
+    gemm_options_from_env();
+    pgmi_model tmp;                                              // the stream (default), the GEMM variant and no profile
+    tmp.gemm_variant = env_int("PGMI_GEMM_VARIANT", 0);
+    std::vector<void*>& pool = tmp.allocs;
+    auto cleanup = [&]() {
+        if (tmp.moe.counts_host) hipHostFree(tmp.moe.counts_host);
+        for (void* p : pool) hipFree(p);
+        pool.clear();
+    };
+    float *dh = nullptr, *dg = nullptr, *dx = nullptr;
+    unsigned short *h16 = nullptr, *g16 = nullptr;
+    const size_t FD = (size_t)F * D;
+    int rc = 0;
+    if ((rc = dev_upload(pool, &dh, h, (size_t)M * D)) || (E > 1 && (rc = dev_upload(pool, &dg, gate, (size_t)E * D))) ||
+        (rc = dev_alloc(pool, &dx, (size_t)M * D)) || (rc = dev_alloc(pool, &h16, (size_t)M * D * 2)) ||
+        (E == 1 && (rc = dev_alloc(pool, &g16, (size_t)M * F * 2))) || (rc = moe_ws_alloc(pool, &tmp.moe, (size_t)M, 1, D, F, E, top_k, gated))) {
+        cleanup();
+        return rc;
+    }
+    std::vector<W16> ew1(E), ew2(E);
+    std::vector<float> fc1(gated ? 2 * FD : 0);
+    for (int e = 0; e < E && !rc; ++e) {
+        if (gated) {
+            pack_swiglu(w1 + e * FD, w3 + e * FD, (size_t)F, (size_t)D, fc1.data());
+            rc = make_w16(pool, fc1.data(), fc1.size(), (size_t)D, PGMI_PREC_F16X3, nullptr, &ew1[e]);
+        } else rc = make_w16(pool, w1 + e * FD, FD, (size_t)D, PGMI_PREC_F16X3, nullptr, &ew1[e]);
+        if (!rc) rc = make_w16(pool, w2 + e * FD, FD, (size_t)F, PGMI_PREC_F16X3, nullptr, &ew2[e]);
+    }
+    hipError_t er = rc ? hipSuccess : hipMemset(dx, 0, (size_t)M * D * 4);
+    if (!rc && er == hipSuccess) {
+        MoeRoute r;
+        if (E > 1) { r.gate = dg; r.E = E; r.top_k = top_k; r.ids = tmp.moe.ids; r.wts = tmp.moe.wts; }
+        rc = launch_rmsnorm_route(dh, nullptr, M, D, 0.0f, h16, r, nullptr);
+        if (!rc) rc = E == 1 ? dense_ffn(&tmp, tmp.moe, ew1[0], ew2[0], h16, g16, M, D, F, gated, dx)
+                             : moe_ffn(&tmp, tmp.moe, ew1, ew2, h16, tmp.moe.ids, tmp.moe.wts, M, D, F, E, top_k, gated, dx);
+    }
+    if (er == hipSuccess) er = hipDeviceSynchronize();
+    if (!rc && er == hipSuccess) er = hipMemcpy(out, dx, (size_t)M * D * 4, hipMemcpyDeviceToHost);
+    if (!rc && er == hipSuccess && E > 1 && ids) er = hipMemcpy(ids, tmp.moe.ids, (size_t)M * top_k * 4, hipMemcpyDeviceToHost);
+    if (!rc && er == hipSuccess && E > 1 && weights) er = hipMemcpy(weights, tmp.moe.wts, (size_t)M * top_k * 4, hipMemcpyDeviceToHost);
+    cleanup();
+    if (rc) return rc;
+    if (er != hipSuccess) { set_error("moe op failed: %s", hipGetErrorString(er)); return PGMI_EHIP; }
+    return PGMI_OK;
+}
+
 // The op entries' GEMMs on their own buffers: f16x3, no epilogue, no output yet -- the caller sets what differs
 static GemmLaunch op_gemm(const unsigned short* a16, const W16& w16, const float* bias, int M, int N, int K, int variant) {
     GemmLaunch g;

@@ -50,6 +50,29 @@ __device__ __forceinline__ void split_act(float x, _Float16& hi, _Float16& lo) {
     hi = (fabsf(x) < 6.103515625e-05f) ? (_Float16)0.0f : (_Float16)x;
     lo = (_Float16)((x - (float)hi) * kLoScale);
 }
+// The columns 4 c .. 4 c + 3 of `row` (D columns, D % 8 == 0) into the K-interleaved split operand, for kernels whose lane `lane` of a wave
+// holds the f32x4 group c = lane + 64 i: lanes (2m, 2m+1) hold one group of 8 columns; the even lane stores the 16 bytes of hi values, the
+// odd lane the 16 bytes of lo values (one exchange of 8 bytes with the neighbour), so 8 lanes write one 128-byte line with one store each.
+// Both lanes of a pair must call it together.
+__device__ __forceinline__ void store_split4(f32x4 o, unsigned short* y16, size_t row, int c, int lane, int D) {
+    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    h4 hi, lo;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        _Float16 a, b;
+        split_act(o[k], a, b);
+        hi[k] = a;
+        lo[k] = b;
+    }
+    const u32x2 H = __builtin_bit_cast(u32x2, hi), L = __builtin_bit_cast(u32x2, lo);
+    const bool odd = lane & 1;
+    const unsigned int s0 = odd ? H[0] : L[0], s1 = odd ? H[1] : L[1];
+    const unsigned int r0 = __shfl_xor(s0, 1), r1 = __shfl_xor(s1, 1);
+    const u32x4 out = odd ? u32x4{r0, r1, L[0], L[1]} : u32x4{H[0], H[1], r0, r1};
+    *reinterpret_cast<u32x4*>(y16 + ki_off(row, 4 * (c & ~1), D) + (odd ? 32 : 0)) = out;
+}
 #endif
 
 // ---- elementwise.hip ---------------------------------------------------------------------
@@ -76,6 +99,9 @@ void launch_vocab_logsoftmax(const float* h, const float* E, const float* bias, 
                              int V, float* out, int32_t* nonfinite, hipStream_t s);
 void launch_layernorm16(const float* x, const float* w, const float* b, int rows, int D, float eps,
                         unsigned short* y16, int mode, hipStream_t s);
+// Weight-only RMSNorm (ProGen3): y16[r] = split(x[r] * rsqrt(mean(x[r]^2) + eps) * w), the K-interleaved f16x3 operand that
+// launch_layernorm16 mode 1 writes; D % 32 == 0, D <= 5120
+int launch_rmsnorm16(const float* x, const float* w, int rows, int D, float eps, unsigned short* y16, hipStream_t s);
 void launch_scatter_rows(const float* src, const int32_t* dst_row, int n, int V, float* table,
                          hipStream_t s);
 void launch_row_index(const int32_t* mask_rel, int B, int T, int32_t* out, hipStream_t s);
@@ -121,6 +147,34 @@ void launch_saprot_rows(const int32_t* wt, const int32_t* set_off, const int32_t
 // lse(logits[first + g width .. + width)) - lse(row) (nullable)
 int launch_group_logsoftmax(const float* h, const float* E, const float* bias, int rows, int D, int V, int first, int groups, int width,
                             float* full, float* group, int32_t* nonfinite, hipStream_t s);
+
+// ---- moe.hip (ProGen3's routed expert block; the kernels are described there) -------------------------------------------------
+// The router of launch_rmsnorm_route: gate fp32 [E][D] (nullptr: no routing), 2 <= E <= 64, 1 <= top_k <= E; tokens / pad_id (nullable):
+// rows whose token is pad_id are routed nowhere (expert -1, weight 0); ids / wts [rows][top_k]: the chosen experts, best first, and their
+// weights divided by their sum.
+struct MoeRoute {
+    const float* gate = nullptr;
+    int E = 0, top_k = 0;
+    const int32_t* tokens = nullptr;
+    int pad_id = 0;
+    int32_t* ids = nullptr;
+    float* wts = nullptr;
+};
+// launch_rmsnorm16 with the router on the normalised row while it is in registers.  w == nullptr: the rows are taken as they are;
+// y16 == nullptr: no operand is written.
+int launch_rmsnorm_route(const float* x, const float* w, int rows, int D, float eps, unsigned short* y16, const MoeRoute& r, hipStream_t s);
+// The token -> expert permutation of n_entries = rows * top_k entries (ids, -1 = unrouted): counts_seg [2 E + 1] = per-expert counts,
+// then the first slot of every expert's segment (multiples of `tile`) and the padded total; slot [n_entries] (-1 = unrouted), in the
+// entries' own order inside a segment.  blk_cnt / blk_base: scratch of moe_perm_blocks(n_entries) * E each.
+int moe_perm_blocks(int n_entries);
+void launch_moe_permute(const int32_t* ids, int n_entries, int E, int tile, int32_t* blk_cnt, int32_t* blk_base, int32_t* counts_seg,
+                        int32_t* slot, hipStream_t s);
+// a16[slot[j]] = h16[j / top_k]: split rows of D columns
+void launch_moe_gather(const unsigned short* h16, const int32_t* slot, int n_entries, int top_k, int D, unsigned short* a16, hipStream_t s);
+// x[row] += sum over k = 0 .. top_k-1 of wts[row][k] * y[slot[row][k]] (fp32 rows of D columns); unrouted rows keep x
+void launch_moe_combine(const float* y, const int32_t* slot, const float* wts, int rows, int top_k, int D, float* x, hipStream_t s);
+// g16 = split(silu(t)): fp32 rows of F columns (F % 32 == 0) -> the K-interleaved operand
+void launch_silu_split(const float* t, int rows, int F, unsigned short* g16, hipStream_t s);
 
 // ---- eve.hip (EVE / DeepSequence; the kernels are described there) ------------------------------------------------------------
 // Noise tensor ids of the Philox counter (include/pgmi.h pgmi_eve_noise names the tensors): z eps; dropout keeps 0 .. n_dec; hidden

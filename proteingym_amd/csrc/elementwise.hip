@@ -252,6 +252,50 @@ void launch_layernorm16(const float* x, const float* w, const float* b, int rows
     else launch_ln_mode<2>(x, w, b, rows, D, eps, nullptr, y16, s);
 }
 
+// ---- RMSNorm (ProGen3: x * rsqrt(mean(x^2) + eps) * w, fp32, no bias) into the K-interleaved f16x3 operand; one wave per row ----
+template <int NV>
+__global__ __launch_bounds__(256) void rmsnorm16_kernel(const float* __restrict__ x, const float* __restrict__ w, int rows, int D,
+                                                        float eps, unsigned short* __restrict__ y16) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const int nv = D >> 2;
+    const f32x4* xr = reinterpret_cast<const f32x4*>(x + (size_t)row * D);
+    f32x4 v[NV];
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = lane + 64 * i;
+        v[i] = (c < nv) ? xr[c] : f32x4{0.f, 0.f, 0.f, 0.f};
+        q += (v[i][0] * v[i][0] + v[i][1] * v[i][1]) + (v[i][2] * v[i][2] + v[i][3] * v[i][3]);
+    }
+    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + eps);
+    const f32x4* wr = reinterpret_cast<const f32x4*>(w);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = lane + 64 * i;
+        if (c < nv) {
+            const f32x4 wv = wr[c];
+            f32x4 o;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) o[k] = v[i][k] * rstd * wv[k];
+            store_split4(o, y16, (size_t)row, c, lane, D);
+        }
+    }
+}
+int launch_rmsnorm16(const float* x, const float* w, int rows, int D, float eps, unsigned short* y16, hipStream_t s) {
+    // a lane holds at most 20 f32x4 groups; pairs of lanes write 8-column groups of whole 32-column K tiles
+    if (rows <= 0 || D <= 0 || D % 32 || D > 5120) { set_error("rmsnorm: D = %d must be a multiple of 32, at most 5120", D); return PGMI_EINVAL; }
+    const dim3 grid((rows + 3) / 4), block(256);
+    const int nv = (D / 4 + 63) / 64;
+    if (nv <= 1) hipLaunchKernelGGL((rmsnorm16_kernel<1>), grid, block, 0, s, x, w, rows, D, eps, y16);
+    else if (nv <= 2) hipLaunchKernelGGL((rmsnorm16_kernel<2>), grid, block, 0, s, x, w, rows, D, eps, y16);
+    else if (nv <= 5) hipLaunchKernelGGL((rmsnorm16_kernel<5>), grid, block, 0, s, x, w, rows, D, eps, y16);
+    else if (nv <= 10) hipLaunchKernelGGL((rmsnorm16_kernel<10>), grid, block, 0, s, x, w, rows, D, eps, y16);
+    else hipLaunchKernelGGL((rmsnorm16_kernel<20>), grid, block, 0, s, x, w, rows, D, eps, y16);
+    return PGMI_OK;
+}
+
 // ---- rotary (rotary_embedding.py:11-20,47-69): half-split rotation of q (already scaled) and k
 // qkv [rows, 3*H*64]; tables cos/sin [T, 64] (emb = cat(freqs,freqs)) built on the host in f32
 // exactly as the reference does.  One thread handles the pair (d, d+32) of one head.

@@ -12,6 +12,8 @@
 //                        the checks and token log-probs of RITA / ProtGPT2 / ProGen2; RITA / ProtGPT2 sequence log-likelihoods
 //   api_poet.hip         PoET: tiered (within-sequence, then sequence-of-sequences) causal decoder on attention_prefix.hip, the
 //                        per-layer prefix cache of a prompt, variant log-probs and log-likelihoods
+//   api_progen3.hip      ProGen3 weights (RMSNorm, grouped-query attention as replicated K/V projection rows, per-expert FC1 / FC2), its
+//                        feed-forward block on moe.hip (pg3_ffn, moe_ffn), the C entries; it runs on run_decoder
 //   api_esmc.hip         ESM C weights (QK-LayerNorm, SwiGLU, scaled residual, untied 64-column head); it runs on run_encoder
 //   api_saprot.hip       SaProt: ESM2's weights and encoder with a 446-token vocabulary; position-set rows and the grouped log-softmax head
 //   api_eve.hip          EVE / DeepSequence: its own handle (pgmi_eve), blob walk, encoder, one ELBO sample, noise seam, the sampling loop
@@ -53,6 +55,10 @@ struct Layer {
     float *c_ln_w = nullptr, *c_ln_b = nullptr, *c_bqkv = nullptr, *c_bo = nullptr;
     W16 c_wqkv16, c_wo16;
     float *q_ln = nullptr, *k_ln = nullptr;       // ESM C: q_ln (times 1/8) / k_ln weights
+    // ProGen3 with more than one expert: the router's fp32 gate [E,D]; per expert FC1 (gated: w1 | w3 in EPI_SWIGLU's 32 gate | 32 up
+    // row blocks, [2F,D]; else w1 [F,D]) and FC2 [D,F].  One expert: w116 / w216 as for every other model.
+    float* gate = nullptr;
+    std::vector<W16> ew1, ew2;
 };
 
 struct ProfEvent {
@@ -107,6 +113,17 @@ struct pgmi_model {
     float* gpt_logits = nullptr;
     W16 gpt_head16;
     double* gpt_sum = nullptr;
+    // ProGen3 (api_progen3.hip): RMSNorm in place of LayerNorm in the decoder loop and the head; the expert block's dimensions and
+    // workspace (MoeWs: slots = max_rows * top_k + n_experts * the GEMM's row tile); the routing of the last forward per layer
+    bool rms_norm = false;
+    int pg3_E = 0, pg3_k = 0, pg3_gated = 0;
+    struct MoeWs {
+        int32_t *ids = nullptr, *slot = nullptr, *blk_cnt = nullptr, *blk_base = nullptr, *counts_seg = nullptr;   // ids: [layers][max_rows * top_k]
+        float *wts = nullptr, *y = nullptr, *t32 = nullptr;       // wts: [layers][max_rows * top_k]; y [slots][D]; t32 [slots][F] (non-gated; one expert: [max_rows][F])
+        unsigned short *a16 = nullptr, *g16 = nullptr;            // [slots][2 D], [slots][2 F] halfs
+        int32_t* counts_host = nullptr;                           // pinned [2 E + 1]
+        size_t layer_stride = 0;
+    } moe;
     // MSA Transformer
     float* msa_pe = nullptr;                            // msa_position_embedding [1024, D]
     float* xt = nullptr;                                // residual stream in column-major token order
@@ -252,7 +269,8 @@ int linear(pgmi_model* m, const float* in32, const unsigned short* in16, const f
 GemmLaunch qkv_launch(pgmi_model* m, const W16& w16, const float* bias, int M, int Da, int K, int T, int H);
 int check_nonfinite(pgmi_model* m);
 int reset_pad_keys(pgmi_model* m, int B, int T);
-int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int device, pgmi_model** out, int arch_arg);
+int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int device, pgmi_model** out, int arch_arg,
+                 const pgmi_pg3_params* pg3 = nullptr);
 // api_esm.hip
 int create_esm(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights);
 int ensure_rotary(pgmi_model* m, int T);            // ESM2 / ESM C: tables for at least T positions
@@ -272,6 +290,21 @@ int decoder_check(pgmi_model* m, int arch, int T);
 int run_decoder(pgmi_model* m, int B, int T, const AttRagged* rg = nullptr, int rows = 0, double att_flops = 0);
 int narrow_head(pgmi_model* m, int M);
 int decoder_token_logprobs(pgmi_model* m, int arch, const int32_t* tokens, int B, int T, float* out);
+int decoder_sequence_loglik(pgmi_model* m, int arch, const int32_t* tokens, const int32_t* lens, int B, int T, double* sum, int32_t* n_targets);
+// api_progen3.hip
+int pg3_check(const pgmi_config* c, const pgmi_pg3_params* p);
+int64_t pg3_weight_count(const pgmi_config* c, const pgmi_pg3_params* p);
+int create_progen3(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights, const pgmi_pg3_params* p);
+void pack_swiglu(const float* w1, const float* w3, size_t F, size_t D, float* dst);   // w1 | w3 -> EPI_SWIGLU's 32 gate | 32 up row blocks
+int moe_ws_alloc(std::vector<void*>& pool, pgmi_model::MoeWs* ws, size_t rows, size_t layers, int D, int F, int E, int top_k, int gated);
+// x += w2(act(w1 h16)) on the M rows themselves (one expert): g16 [M][2 F] halfs of scratch
+int dense_ffn(pgmi_model* m, const pgmi_model::MoeWs& ws, const W16& w1, const W16& w2, const unsigned short* h16, unsigned short* g16,
+              int M, int D, int F, int gated, float* x);
+int pg3_ffn(pgmi_model* m, const Layer& L, int layer, int M);       // x += moe(h16) of one layer (run_decoder)
+// The expert block on split rows h16 [M][D] whose routing (ids / wts [M][top_k]) is known: permutation, gather, per-expert GEMMs, combine
+// into x.  m gives the stream, the GEMM variant and the profile; ws the workspace.
+int moe_ffn(pgmi_model* m, const pgmi_model::MoeWs& ws, const std::vector<W16>& ew1, const std::vector<W16>& ew2,
+            const unsigned short* h16, const int32_t* ids, const float* wts, int M, int D, int F, int E, int top_k, int gated, float* x);
 // api_poet.hip
 int64_t poet_weight_count(const pgmi_config* c, int final_norm);
 int create_poet(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights, int final_norm);

@@ -5,11 +5,13 @@ publishes.
     python scripts/accept_real_weights.py --proteingym /path/to/ProteinGym --dms-folder DMS_ProteinGym_substitutions \\
         --esm1v esm1v_t33_650M_UR90S_{1,2,3,4,5}.pt [--esm2 esm2_t33_650M_UR50D.pt esm2_t36_3B_UR50D.pt] \\
         [--tranception Tranception_Large [--msa-folder MSA_files --msa-weights-folder MSA_weights]] \\
+        [--progen3 progen3-339m ...] \\
         [--assays BLAT_ECOLX_Stiffler_2015] --out accept_out
 
 What it does, with nothing of its own between the scorer and the verdict:
   1. cuts ``<proteingym>/reference_files/DMS_substitutions.csv`` down to ``--assays``;
-  2. scores them with this package's runners (``run_benchmark`` for ESM-1v / ESM2, the single-assay Tranception CLI), writing the CSVs
+  2. scores them with this package's runners (``run_benchmark`` for ESM-1v / ESM2, the single-assay Tranception and ProGen3 CLIs -- for
+     ProGen3 this is also the first proof of the megablocks expert-layout mapping of proteingym_amd/progen3.py, which no toy can give), writing the CSVs
      where ``<proteingym>/config.json`` says each model's scores live;
   3. runs the checkout's OWN ``proteingym/merge.py`` and ``proteingym/performance_DMS_benchmarks.py`` on them (the latter's summary
      tables need every taxon / alignment-depth class and may stop on a one-assay subset: its per-assay table is written first and is all
@@ -48,6 +50,8 @@ def create_parser():
     ap.add_argument("--tranception", default=None, help="Tranception checkpoint directory (config.json + weights)")
     ap.add_argument("--msa-folder", default=None, help="with --tranception: alignments -> 'Tranception L' (inference-time retrieval); without: 'Tranception L no retrieval'")
     ap.add_argument("--msa-weights-folder", default=None)
+    ap.add_argument("--progen3", nargs="*", default=[], help="ProGen3 checkpoint directories; the size in the directory's name (112m, 219m, 339m, 762m, 1b, 3b) "
+                                                             "picks the registry row Progen3_<size>")
     ap.add_argument("--assays", nargs="+", default=["BLAT_ECOLX_Stiffler_2015"], help="DMS_id values")
     ap.add_argument("--out", default="accept_out")
     ap.add_argument("--device", type=int, default=0)
@@ -109,8 +113,11 @@ def missing_inputs(args, reference, subset):
         for fn in subset["MSA_filename"]:
             if not os.path.exists(os.path.join(args.msa_folder, str(fn))):
                 gone.append(os.path.join(args.msa_folder, str(fn)))
-    if not (args.esm1v or args.esm2 or args.tranception):
-        gone.append("no model given: --esm1v / --esm2 / --tranception")
+    for d in args.progen3:
+        if not os.path.exists(os.path.join(d, "config.json")):
+            gone.append(os.path.join(d, "config.json"))
+    if not (args.esm1v or args.esm2 or args.tranception or args.progen3):
+        gone.append("no model given: --esm1v / --esm2 / --tranception / --progen3")
     return gone
 
 
@@ -167,6 +174,17 @@ def main(argv=None, make_model=None, make_tranception=None, patch_performance=No
                 make_tranception(cli, cli.create_parser().parse_args(targv))
             else:
                 cli.main(cli.create_parser().parse_args(targv))
+    for d in args.progen3:
+        from proteingym_amd import score_progen3_proteingym as pg3_cli
+        name = os.path.basename(os.path.normpath(d)).lower()
+        key = next((k for k in registry if k.startswith("Progen3_") and name.endswith(k.split("_", 1)[1].lower())), None)
+        if key is None:
+            print(f"accept_real_weights: {d}: no Progen3_<size> entry of config.json matches the directory name", file=sys.stderr)
+            return 2
+        models[key] = dict(registry[key])
+        for i in range(len(subset)):
+            pg3_cli.main(["--Progen3_model_name_or_path", d, "--DMS_reference_file_path", sub_csv, "--DMS_data_folder", args.dms_folder, "--DMS_index", str(i),
+                          "--output_scores_folder", os.path.join(scores, registry[key]["location"]), "--device", str(args.device)])
     cfg_path = os.path.join(args.out, "config.json")
     json.dump({FIELD: models}, open(cfg_path, "w"), indent=1)
 

@@ -50,6 +50,13 @@ pgmi_progen2() {
         --DMS_reference_file_path "${mapping}" --DMS_data_folder "${folder}" --DMS_index "${DMS_index:=0}" \
         --output_scores_folder "${output_scores_folder}" "$@"
 }
+# pgmi_progen3 <mapping csv> <data folder> [more flags]: assay ${DMS_index} through score_progen3_proteingym with ${Progen3_model_name_or_path}
+pgmi_progen3() {
+    local mapping="$1" folder="$2"; shift 2
+    pgmi_run proteingym_amd.score_progen3_proteingym --Progen3_model_name_or_path "${Progen3_model_name_or_path:=/path/to/progen3-339m}" \
+        --DMS_reference_file_path "${mapping}" --DMS_data_folder "${folder}" --DMS_index "${DMS_index:=0}" \
+        --output_scores_folder "${output_scores_folder}" --max_batch_tokens "${max_batch_tokens:=65536}" "$@"
+}
 # pgmi_causal_lm <module> <model flag> <model path> <mapping csv> <data folder> [more flags]: assay ${DMS_index} through the RITA /
 # ProtGPT2 scorers
 pgmi_causal_lm() {
