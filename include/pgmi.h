@@ -66,6 +66,10 @@ extern "C" {
  * rotary and a routed mixture-of-experts feed-forward block; created with pgmi_pg3_model_create, scored with pgmi_pg3_* (see the
  * ProGen3 section below) */
 #define PGMI_ARCH_PROGEN3 10
+/* ESM3 (proteingym/baselines/evoscale/esm/models/esm3.py): ESM C's blocks under a multi-track input embedding, block 0 with the
+ * geometric attention branch over per-token backbone frames; created with pgmi_esm3_model_create, a window's structure bound with
+ * pgmi_esm3_set_structure, scored with pgmi_token_logprobs / pgmi_masked_logprobs (see the ESM3 section below) */
+#define PGMI_ARCH_ESM3 11
 
 /* GEMM operand precision.  Residual stream, LayerNorm statistics, softmax and every
  * accumulator are fp32 in all modes. */
@@ -230,7 +234,8 @@ void pgmi_optimal_window(int position, int seq_len_with_special, int model_windo
 #define PGMI_K_SCORE 8
 #define PGMI_K_KEPT_ROWS 9   /* last layer after attention, on the kept (masked) rows only: gathers + out-projection + LN + FFN */
 #define PGMI_K_MOE_ROUTE 10  /* ProGen3: permutation, gather and weighted combine around the expert GEMMs (the router rides in PGMI_K_LAYERNORM) */
-#define PGMI_K_COUNT 11
+#define PGMI_K_GEOM 11       /* ESM3: block 0's geometric attention kernel (its LayerNorm and two GEMMs ride in their own classes) */
+#define PGMI_K_COUNT 12
 /* on != 0: every launch of the classes above is bracketed by hipEventRecord on the stream. */
 int pgmi_profile_enable(pgmi_model* m, int on);
 /* Sum of event-measured milliseconds, launch count and algorithmic FLOPs / bytes for a class
@@ -312,6 +317,15 @@ int pgmi_op_prefix_attention(int device, const float* qkv, const int32_t* seg_of
  *   weights f32 [M][top_k] (nullable; E == 1: not written).  The experts run through the model's own path: router, permutation,
  *   gather, one launch_gemm16 pair per non-empty expert, combine. */
 int pgmi_op_rmsnorm(int device, const float* x, const float* w, int rows, int D, float eps, float* y);
+/* ESM3's geometric attention (geom_attention.hip; geom_attention.py forward between its proj and out_proj), fp32 in and out.
+ * proj [B*S][15 H]: per token q_rot | k_rot | v | q_dist | k_dist, H x 3 each.  rot [n][S][9], trans [n][S][3], frame_mask int32 [n][S]
+ * with n = B (per_row_frames != 0) or 1 (every row shares the frames).  w_rot / w_dist [H]: softplus of rotation_scale_per_head /
+ * distance_scale_per_head.  For head h: score(i,j) = (R_i q_rot_i . R_j k_rot_j) / sqrt(3) w_rot[h] - |T_i q_dist_i - T_j k_dist_j| /
+ * sqrt(3) w_dist[h]; softmax over the framed keys j; out[i] = R_i^T sum_j p_ij R_j v_j; rows of frameless queries are zero.
+ * out [B*S][3 H].  pgmi_op_geom_key_tile: the keys per LDS tile the launch uses for S (16, 64 or 256). */
+int pgmi_op_geom_attention(int device, const float* proj, const float* rot, const float* trans, const int32_t* frame_mask,
+                           int per_row_frames, const float* w_rot, const float* w_dist, int B, int S, int H, float* out);
+int pgmi_op_geom_key_tile(int S);
 int pgmi_op_moe(int device, const float* h, const float* gate, const float* w1, const float* w3, const float* w2, int M, int D, int F,
                 int E, int top_k, int gated, float* out, int32_t* ids, float* weights);
 int pgmi_op_tied_row_attention(int device, const float* qkv, int R, int C, int H, int splits, float* ctx, float* probs);
@@ -493,6 +507,39 @@ int pgmi_pg3_routing(pgmi_model* m, int layer, int rows, int32_t* ids, float* we
  *   transformer.norm.weight [D]; sequence_head.0.{weight [D,D], bias}; sequence_head.2.{weight,bias}; sequence_head.3.{weight [64,D], bias [64]}.
  * pgmi_weight_count gives its size.  pgmi_masked_logprobs serves this arch (out [B,64]); ready-made rows carry their own window (ESM C's
  * window rule differs from pgmi_optimal_window, so pgmi_assay_create refuses this arch). */
+
+/* ---- ESM3 (arch PGMI_ARCH_ESM3; vocab 64, head_dim 64, embed_dim <= 2048, ffn_dim = the SwiGLU hidden width F, precision f16x3) ----
+ * The blocks are ESM C's (above), with the same scaled residual, final LayerNorm and 64-column sequence head.  What differs:
+ * Input embedding (esm3.py EncodeInputs with the defaults of ESM3.forward / ESM3.logits): x = sequence_embed[id] +
+ *   structure_tokens_embed[structure token] + c[p], where c[p] = plddt_projection(rbf16(1)) + structure_per_res_plddt_projection(
+ *   rbf16(p)) + ss8_embed[0] + sasa_embed[0] is folded at creation in fp32 (rbf16: 16 centres on [0,1], width 1/16) and p = 1 where
+ *   the token has finite coordinates, else 0.  The function and residue-annotation tracks are at their padding rows: zero.
+ * Block 0 (blocks.py:150-162): x += attn(x) / s; x += geom_attn(x) / s; x += ffn(x) / s.  geom_attn (geom_attention.py, v_heads = Hv):
+ *   LayerNorm without bias -> Linear(D, 15 Hv) -> the geometric attention of pgmi_op_geom_attention over the bound frames ->
+ *   Linear(3 Hv, D), both bias-free.  When no token of the bound window has a frame the branch is exactly zero and is not launched.
+ * Limits: Hv % 4 == 0, 15 Hv <= 3 D, roundup(3 Hv, 32) <= min(D, F).
+ * Weight blob order (fp32, nn.Linear layout [out,in], names as in ESM3.state_dict()):
+ *   encoder.sequence_embed.weight [64,D]; encoder.plddt_projection.{weight [D,16], bias [D]};
+ *   encoder.structure_per_res_plddt_projection.{weight [D,16], bias [D]}; encoder.structure_tokens_embed.weight [4101,D];
+ *   encoder.ss8_embed.weight [11,D]; encoder.sasa_embed.weight [19,D];
+ *   per block i (transformer.blocks.i.): ESM C's ten tensors in ESM C's order; block 0 has, between attn.out_proj.weight and ffn.0.weight,
+ *     geom_attn.distance_scale_per_head [Hv]; geom_attn.rotation_scale_per_head [Hv]; geom_attn.s_norm.weight [D];
+ *     geom_attn.proj.weight [15 Hv, D]; geom_attn.out_proj.weight [D, 3 Hv];
+ *   transformer.norm.weight [D]; output_heads.sequence_head.{0.weight [D,D], 0.bias, 2.weight, 2.bias, 3.weight [64,D], 3.bias [64]}.
+ * The other five output heads are not part of the blob.
+ *
+ * pgmi_esm3_weight_count: the blob size for (cfg, v_heads); <0 on a bad cfg.  (pgmi_weight_count returns -1 for this arch.)
+ * pgmi_esm3_model_create: as pgmi_model_create, with v_heads.  Returns an ordinary model: destroy, profile, synchronize as usual.
+ * pgmi_esm3_set_structure: binds one window of T tokens (<cls> + residues + <eos>); every later pgmi_token_logprobs /
+ *   pgmi_masked_logprobs call must have this T, and all its rows share the structure (masking changes the sequence id only).
+ *   structure_tokens int32 [T] in [0, 4101) (4096 mask, 4097 eos, 4098 bos); plddt int32 [T]: p above; rot f32 [T][9] row-major
+ *   3x3 and trans f32 [T][3]: the frames of build_affine3d_from_coordinates (Gram-Schmidt on (C, CA, N); frameless tokens carry the
+ *   frame of the window's mean N / CA / C, or the identity); frame_mask int32 [T]: non-zero = the token has a frame.
+ *   Without a bound window the forward entries return PGMI_EINVAL. */
+int64_t pgmi_esm3_weight_count(const pgmi_config* cfg, int v_heads);
+int pgmi_esm3_model_create(const pgmi_config* cfg, int v_heads, const float* weights, int64_t n_weights, int device, pgmi_model** out);
+int pgmi_esm3_set_structure(pgmi_model* m, const int32_t* structure_tokens, const int32_t* plddt, const float* rot, const float* trans,
+                            const int32_t* frame_mask, int T);
 
 /* ---- SaProt (arch PGMI_ARCH_SAPROT; vocab 446, max_positions 0, every precision) ---------------------------------------------
  * The model is ESM2 (rotary, erf-GELU, tied LM head; head dims as for ESM2) and its weight blob is ESM2's in pgmi_weight_count's order

@@ -19,11 +19,12 @@ ARCH_ESMC = 7
 ARCH_SAPROT = 8
 ARCH_POET = 9
 ARCH_PROGEN3 = 10
+ARCH_ESM3 = 11
 GPT_POS_ROTARY, GPT_POS_LEARNED = 0, 1
 PREC_FP32, PREC_BF16, PREC_F16X3 = 0, 1, 2
 PRECISIONS = {"fp32": PREC_FP32, "bf16": PREC_BF16, "f16x3": PREC_F16X3}
 K_NAMES = ["embed", "layernorm", "gemm_qkv", "attention", "gemm_out", "gemm_fc1", "gemm_fc2",
-           "head", "score", "kept_rows", "moe_route"]
+           "head", "score", "kept_rows", "moe_route", "geom"]
 
 
 EINVAL, ENOMEM, EHIP, ENODEV, EPARSE, EOVERFLOW = -1, -2, -3, -4, -5, -6          # include/pgmi.h PGMI_E*
@@ -117,6 +118,9 @@ SIGNATURES = [
     ("pgmi_pg3_token_logprobs", C.c_int, [C.c_void_p, _i32p, C.c_int, C.c_int, _f32p]),
     ("pgmi_pg3_sequence_loglik", C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, C.c_int, _f64p, _i32p]),
     ("pgmi_pg3_routing", C.c_int, [C.c_void_p, C.c_int, C.c_int, _i32p, _f32p]),
+    ("pgmi_esm3_weight_count", C.c_int64, [C.POINTER(Config), C.c_int]),
+    ("pgmi_esm3_model_create", C.c_int, [C.POINTER(Config), C.c_int, _f32p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
+    ("pgmi_esm3_set_structure", C.c_int, [C.c_void_p, _i32p, _i32p, _f32p, _f32p, _i32p, C.c_int]),
     ("pgmi_eve_weight_count", C.c_int64, [C.c_void_p]),
     ("pgmi_eve_create", C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     ("pgmi_eve_destroy", None, [C.c_void_p]),
@@ -143,6 +147,8 @@ SIGNATURES = [
                                            C.c_int, C.c_int, C.c_int, _f32p]),
     ("pgmi_op_prefix_attention", C.c_int, [C.c_int, _f32p, _i32p, C.c_int, _f32p, C.c_int, C.c_int, C.c_int, _f32p]),
     ("pgmi_op_rmsnorm", C.c_int, [C.c_int, _f32p, _f32p, C.c_int, C.c_int, C.c_float, _f32p]),
+    ("pgmi_op_geom_attention", C.c_int, [C.c_int, _f32p, _f32p, _f32p, _i32p, C.c_int, _f32p, _f32p, C.c_int, C.c_int, C.c_int, _f32p]),
+    ("pgmi_op_geom_key_tile", C.c_int, [C.c_int]),
     ("pgmi_op_moe", C.c_int, [C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p,
                               _i32p, _f32p]),
     ("pgmi_op_tied_row_attention", C.c_int, [C.c_int, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p]),

@@ -49,7 +49,7 @@ int create_esm(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_
 }
 
 int ensure_rotary(pgmi_model* m, int T) {
-    if ((!esm2_rotary(m->cfg.arch) && m->cfg.arch != PGMI_ARCH_ESMC) || T <= m->rot_len) return PGMI_OK;
+    if ((!esm2_rotary(m->cfg.arch) && !esmc_blocks(m->cfg.arch)) || T <= m->rot_len) return PGMI_OK;
     return upload_rotate_half(m, std::max(T, 1026));
 }
 
@@ -91,7 +91,8 @@ int run_encoder(pgmi_model* m, int B, int T, const int32_t* keep, int n_keep, bo
         ProfScope p(m, PGMI_K_EMBED, 0, (double)M * D * 4);
         // kv_len: keys before the first <pad>
         launch_seq_stats(m->tokens, B, T, m->embed_gather ? 0 : c.token_dropout, m->denom, m->pos_idx, m->kv_len, s, m->mask_id);
-        if (m->embed_gather) launch_gather_rows(m->embed_tokens, m->tokens, M, D, m->x, s);
+        if (c.arch == PGMI_ARCH_ESM3) { if ((rc = esm3_embed(m, B, T))) return rc; }
+        else if (m->embed_gather) launch_gather_rows(m->embed_tokens, m->tokens, M, D, m->x, s);
         else launch_embed(m->tokens, m->denom, m->pos_idx, m->embed_tokens, m->embed_positions, c.token_dropout, M, T, D, m->x, s, m->mask_id);
         if (m->lnb_w) {                                        // emb_layer_norm_before
             launch_layernorm(m->x, m->lnb_w, m->lnb_b, M, D, 1e-5f, m->x, s);
@@ -139,7 +140,8 @@ int run_encoder(pgmi_model* m, int B, int T, const int32_t* keep, int n_keep, bo
               rc = launch_attention_f32(m->qkv, m->kv_len, B, T, H, m->h, s, m->rot_halves * kHeadDim);
           }
           if (rc) return rc; }
-        if (keep && m->keep_rows && l == c.layers - 1) {
+        // (a block with the geometric branch is not row-local after its attention: a one-block ESM3 takes the full path)
+        if (keep && m->keep_rows && l == c.layers - 1 && !L.g_norm_w) {
             const int R = n_keep;
             ProfScope p(m, PGMI_K_KEPT_ROWS, 2.0 * R * D * (Da + N1 + F), 0);
             launch_gather_rows(m->x, keep, R, D, m->qkv, s);                       // residual rows (qkv is free after attention)
@@ -163,6 +165,8 @@ int run_encoder(pgmi_model* m, int B, int T, const int32_t* keep, int n_keep, bo
         { ProfScope p(m, PGMI_K_GEMM_OUT, 2.0 * M * D * D, 0);
           rc = linear(m, m->h, m->h16, L.wo, L.wo16, L.bo, m->x, m->x, nullptr, M, D, Da, EPI_NONE);
           if (rc) return rc; }
+        // ESM3 block 0: the geometric attention branch; exactly zero, and not launched, when no token of the window has a frame
+        if (L.g_norm_w && m->e3_framed && (rc = geom_branch(m, L, B, T))) return rc;
         { ProfScope p(m, PGMI_K_LAYERNORM, 0, ln_bytes);
           if (prec == PGMI_PREC_FP32) launch_layernorm(m->x, L.ln2_w, L.ln2_b, M, D, 1e-5f, m->h, s);
           else launch_layernorm16(m->x, L.ln2_w, L.ln2_b, M, D, 1e-5f, m->h16, mode16, s); }
@@ -244,7 +248,7 @@ int pgmi_token_logprobs(pgmi_model* m, const int32_t* tokens, int B, int T, floa
 int pgmi_masked_logprobs(pgmi_model* m, const int32_t* tokens, const int32_t* mask_pos, int B, int T, float* out) {
     if (!m || !tokens || !mask_pos || !out || B <= 0 || T <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
     if (m->cfg.arch == PGMI_ARCH_SAPROT) { set_error("SaProt models are scored with pgmi_saprot_token_logprobs / pgmi_saprot_group_logprobs"); return PGMI_EINVAL; }
-    if (m->cfg.arch == PGMI_ARCH_ESMC && T + 31 > m->max_rows) { set_error("T=%d exceeds workspace rows %d", T, m->max_rows); return PGMI_EINVAL; }
+    if (esmc_blocks(m->cfg.arch) && T + 31 > m->max_rows) { set_error("T=%d exceeds workspace rows %d", T, m->max_rows); return PGMI_EINVAL; }
     if (T > m->max_rows) { set_error("T=%d exceeds workspace rows %d", T, m->max_rows); return PGMI_EINVAL; }
     int rc = check_tokens(tokens, B, T);
     if (rc) return rc;
@@ -274,7 +278,7 @@ int pgmi_assay_create(pgmi_model* m, const int32_t* wt_tokens, int n_tok, const 
     if (!out) { set_error("null out"); return PGMI_EINVAL; }
     *out = nullptr;
     if (!m || !wt_tokens || n_tok <= 0 || P < 0 || (P > 0 && !positions) || window <= 0 || n_mut < 0) { set_error("bad argument"); return PGMI_EINVAL; }
-    if (m->cfg.arch == PGMI_ARCH_ESMC) { set_error("ESM C assays run through pgmi_masked_logprobs (their window rule is not pgmi_optimal_window)"); return PGMI_EINVAL; }
+    if (esmc_blocks(m->cfg.arch)) { set_error("ESM C / ESM3 assays run through pgmi_masked_logprobs (their window rule is not pgmi_optimal_window)"); return PGMI_EINVAL; }
     if (m->cfg.arch == PGMI_ARCH_SAPROT) { set_error("SaProt assays run through pgmi_saprot_group_logprobs (position sets, no window)"); return PGMI_EINVAL; }
     for (int i = 0; i < n_tok; ++i)
         if (wt_tokens[i] < 0 || wt_tokens[i] >= PGMI_VOCAB || wt_tokens[i] == PGMI_TOK_PAD) { set_error("wt token %d invalid at %d", wt_tokens[i], i); return PGMI_EINVAL; }

@@ -657,4 +657,40 @@ int pgmi_op_column_attention(int device, const float* X, const float* W, const f
     return PGMI_OK;
 }
 
+// ESM3's geometric attention kernel (geom_attention.hip) through the launcher the model and the structure tokenizer use.
+int pgmi_op_geom_attention(int device, const float* proj, const float* rot, const float* trans, const int32_t* frame_mask,
+                           int per_row_frames, const float* w_rot, const float* w_dist, int B, int S, int H, float* out) {
+    if (!proj || !rot || !trans || !frame_mask || !w_rot || !w_dist || !out || B <= 0 || S <= 0 || H <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
+    if (pgmi_device_count() <= 0) { set_error("no HIP device visible"); return PGMI_ENODEV; }
+    PGMI_HIP(hipSetDevice(device));
+    const size_t rows = (size_t)B * S, nf = per_row_frames ? rows : (size_t)S;
+    std::vector<void*> pool;
+    auto cleanup = [&]() { for (void* p : pool) hipFree(p); };
+    float *dp = nullptr, *dr = nullptr, *dt = nullptr, *dwr = nullptr, *dwd = nullptr, *dout = nullptr;
+    int32_t* dm = nullptr;
+    int rc = 0;
+    if ((rc = dev_upload(pool, &dp, proj, rows * 15 * H)) || (rc = dev_upload(pool, &dr, rot, nf * 9)) || (rc = dev_upload(pool, &dt, trans, nf * 3)) ||
+        (rc = dev_upload(pool, &dm, frame_mask, nf)) || (rc = dev_upload(pool, &dwr, w_rot, (size_t)H)) || (rc = dev_upload(pool, &dwd, w_dist, (size_t)H)) ||
+        (rc = dev_alloc(pool, &dout, rows * 3 * H))) {
+        cleanup();
+        return rc;
+    }
+    hipError_t e = hipMemset(dout, 0xFF, rows * 3 * H * sizeof(float));         // an element the kernel skips shows as NaN
+    GeomAttLaunch g;
+    g.proj = dp, g.pitch = 15 * H;
+    g.rot = dr, g.trans = dt, g.mask = dm, g.per_row_frames = per_row_frames != 0;
+    g.w_rot = dwr, g.w_dist = dwd;
+    g.B = B, g.S = S, g.H = H;
+    g.out = dout, g.opitch = 3 * H;
+    if (e == hipSuccess) rc = launch_geom_attention(g);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (!rc && e == hipSuccess) e = hipMemcpy(out, dout, rows * 3 * H * sizeof(float), hipMemcpyDeviceToHost);
+    cleanup();
+    if (rc) return rc;
+    if (e != hipSuccess) { set_error("geometric attention op failed: %s", hipGetErrorString(e)); return PGMI_EHIP; }
+    return PGMI_OK;
+}
+
+int pgmi_op_geom_key_tile(int S) { return geom_key_tile(S); }
+
 }  // extern "C"

@@ -314,6 +314,29 @@ void launch_split16(const float* x, int64_t n, float scale, int mode, int K, uns
 int launch_qkln_prep(const float* qkv, const float* q_w, const float* k_w, float eps, const float* cos_t, const float* sin_t, int B,
                      int T, int H, unsigned short* qk16, size_t qk_plane, unsigned short* vt16, size_t vt_plane, hipStream_t s);
 
+// ---- geom_attention.hip ------------------------------------------------------------------
+// ESM3's geometric attention (the file's header has the formula), fp32 in and out.  proj [B*S][pitch]: per token q_rot | k_rot | v |
+// q_dist | k_dist, H x 3 each (pitch >= 15 H).  Frames rot [n][S][9] (row-major 3x3), trans [n][S][3], mask [n][S] (non-zero = framed)
+// with n = 1 shared by the B rows, or n = B (per_row_frames).  w_rot / w_dist [H]: softplus of the per-head scales.  out [B*S][opitch]:
+// column 3 h + c; the columns 3 H .. opitch are written as zeros (the K padding of the out-projection that follows).
+struct GeomAttLaunch {
+    const float* proj = nullptr;
+    int pitch = 0;
+    const float *rot = nullptr, *trans = nullptr;
+    const int32_t* mask = nullptr;
+    bool per_row_frames = false;
+    const float *w_rot = nullptr, *w_dist = nullptr;
+    int B = 0, S = 0, H = 0;
+    float* out = nullptr;
+    int opitch = 0;
+    hipStream_t stream = nullptr;
+};
+int launch_geom_attention(const GeomAttLaunch& g);
+int geom_key_tile(int S);                              // keys per LDS tile (= queries per block) the launch picks for S: 16, 64 or 256
+// ESM3's input embedding: x[r] = seq_embed[tokens[r]] + struct_embed[stok[r % T]] + cst[plddt[r % T]]  (cst [2][D])
+void launch_esm3_embed(const int32_t* tokens, const int32_t* stok, const int32_t* plddt, const float* seq_embed, const float* struct_embed,
+                       const float* cst, int rows, int T, int D, float* x, hipStream_t s);
+
 // ---- attention_f32.hip -------------------------------------------------------------------
 // qkv [B*T, 3*H*head_dim] (q pre-scaled by head_dim^-1/2); kv_len[b] (nullable) = valid keys.  Output: ctx fp32 [B*T, H*head_dim].
 int launch_attention_f32(const float* qkv, const int32_t* kv_len, int B, int T, int H, float* ctx, hipStream_t s,

@@ -337,6 +337,25 @@ void launch_gather_rows(const float* x, const int32_t* idx, int n, int D, float*
     hipLaunchKernelGGL(gather_rows_kernel, dim3((n + 3) / 4), dim3(256), 0, s, x, idx, n, D, y);
 }
 
+// ESM3 (api_esm3.hip): the sequence row plus the window's structure-token row plus the folded per-token constant; D % 4 == 0
+__global__ void esm3_embed_kernel(const int32_t* __restrict__ tokens, const int32_t* __restrict__ stok, const int32_t* __restrict__ plddt,
+                                  const float* __restrict__ seq_embed, const float* __restrict__ struct_embed, const float* __restrict__ cst,
+                                  int n, int T, int D, float* __restrict__ x) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= n) return;
+    const int t = row % T;
+    const f32x4* a = reinterpret_cast<const f32x4*>(seq_embed + (size_t)tokens[row] * D);
+    const f32x4* b = reinterpret_cast<const f32x4*>(struct_embed + (size_t)stok[t] * D);
+    const f32x4* c = reinterpret_cast<const f32x4*>(cst + (size_t)(plddt[t] != 0) * D);
+    f32x4* dst = reinterpret_cast<f32x4*>(x + (size_t)row * D);
+    for (int i = lane; i < D / 4; i += 64) dst[i] = (a[i] + b[i]) + c[i];
+}
+void launch_esm3_embed(const int32_t* tokens, const int32_t* stok, const int32_t* plddt, const float* seq_embed, const float* struct_embed,
+                       const float* cst, int rows, int T, int D, float* x, hipStream_t s) {
+    hipLaunchKernelGGL(esm3_embed_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, tokens, stok, plddt, seq_embed, struct_embed, cst, rows, T, D, x);
+}
+
 __global__ void strided_index_kernel(int first, int stride, int n, int32_t* __restrict__ idx) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) idx[i] = first + i * stride;

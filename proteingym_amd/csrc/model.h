@@ -15,6 +15,8 @@
 //   api_progen3.hip      ProGen3 weights (RMSNorm, grouped-query attention as replicated K/V projection rows, per-expert FC1 / FC2), its
 //                        feed-forward block on moe.hip (pg3_ffn, moe_ffn), the C entries; it runs on run_decoder
 //   api_esmc.hip         ESM C weights (QK-LayerNorm, SwiGLU, scaled residual, untied 64-column head); it runs on run_encoder
+//   api_esm3.hip         ESM3 weights (ESM C's blocks, the folded multi-track embedding, block 0's geometric attention branch), the
+//                        bound window structure, geom_branch (run_encoder calls it after block 0's attention); it runs on run_encoder
 //   api_saprot.hip       SaProt: ESM2's weights and encoder with a 446-token vocabulary; position-set rows and the grouped log-softmax head
 //   api_eve.hip          EVE / DeepSequence: its own handle (pgmi_eve), blob walk, encoder, one ELBO sample, noise seam, the sampling loop
 //   api_mpnn.hip         ProteinMPNN: its own handle (pgmi_mpnn), blob walk, the per-structure pass (graph, features, encoder, hoisted
@@ -59,6 +61,10 @@ struct Layer {
     // row blocks, [2F,D]; else w1 [F,D]) and FC2 [D,F].  One expert: w116 / w216 as for every other model.
     float* gate = nullptr;
     std::vector<W16> ew1, ew2;
+    // ESM3 block 0: the geometric attention branch -- s_norm's weight, proj [15 Hv, D], out_proj [D, Kp] (its 3 Hv input columns
+    // zero-padded to Kp = roundup(3 Hv, 32); 1/s on its out_scale), softplus of the two per-head scales
+    float *g_norm_w = nullptr, *g_wrot = nullptr, *g_wdist = nullptr;
+    W16 g_proj16, g_out16;
 };
 
 struct ProfEvent {
@@ -142,6 +148,15 @@ struct pgmi_model {
     int poet_P = 0;
     std::vector<float> poet_prompt_lp;
     int32_t* poet_meta = nullptr;
+    // ESM3 (api_esm3.hip): v_heads and the out-projection's padded K; the structure-token table and the two folded constant rows; the
+    // bound window (pgmi_esm3_set_structure): structure tokens, plddt flags, frames and frame mask of e3_T tokens, e3_framed = any frame
+    int e3_vheads = 0, e3_Kp = 0;
+    float *e3_struct_embed = nullptr, *e3_const = nullptr;
+    int32_t *e3_stok = nullptr, *e3_plddt = nullptr, *e3_mask = nullptr;
+    float *e3_rot = nullptr, *e3_trans = nullptr;
+    size_t e3_cap = 0;
+    int e3_T = 0;
+    bool e3_framed = false;
     // 16-bit activations: h16_plane = R*D and g16_plane = R*F elements (f16x3: K-interleaved hi | lo rows, 2 halfs per element; bf16: 1
     // half).  They are allocation sizes; no launcher takes them as a stride.
     unsigned short *h16 = nullptr, *g16 = nullptr;
@@ -311,6 +326,12 @@ int create_poet(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n
 // api_esmc.hip
 int64_t esmc_weight_count(const pgmi_config* c);
 int create_esmc(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights);
+// api_esm3.hip
+int esm3_check(const pgmi_config* c, int v_heads);
+int64_t esm3_weight_count(const pgmi_config* c, int v_heads);
+int create_esm3(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights, int v_heads);
+int esm3_embed(pgmi_model* m, int B, int T);                        // m->tokens [B,T] -> m->x, over the bound window
+int geom_branch(pgmi_model* m, const Layer& L, int B, int T);       // x += out_proj(geom_attn(s_norm(x))) / s on the M = B T rows of m->x
 // api_saprot.hip
 int create_saprot(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights, int mask_id);
 // api_msa.hip
@@ -319,6 +340,8 @@ int run_msa(pgmi_model* m, int R, int C, int keep_col = -1, bool* compacted = nu
 
 // ESM2's rotate-half rotary on q and k (SaProt is ESM2 with another vocabulary)
 inline bool esm2_rotary(int arch) { return arch == PGMI_ARCH_ESM2 || arch == PGMI_ARCH_SAPROT; }
+// ESM C's blocks (q / k LayerNorm, SwiGLU, scaled residual, 64-column head): ESM C itself and ESM3
+inline bool esmc_blocks(int arch) { return arch == PGMI_ARCH_ESMC || arch == PGMI_ARCH_ESM3; }
 
 // Walks a weight blob in the order include/pgmi.h documents.  upload / w16 / linear put the next n floats on the device; their forms
 // with a host pointer upload a host re-layout instead and do not advance.  take hands the next n floats to a host re-layout.  The

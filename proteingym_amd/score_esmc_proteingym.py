@@ -5,7 +5,7 @@ with a warning), ``<output_dir>/<DMS_id>.csv`` = the assay's columns plus ``<mod
 skips), written after the Spearman step, and ``correlation_summary_<model_type>.csv`` appended to (header only when it is created).
 A failing assay -- a mutant letter outside the 20 standard amino acids is the reference's KeyError -- gets a NaN summary row and no
 CSV.  The model is loaded once from --model_path (a .pth state dict or a snapshot directory); nothing is downloaded.  esm3_open and
---use_structure are not supported on this path.  Additive flags: --device, --max_rows.
+--use_structure are not supported on this path (score_esm3_proteingym scores them).  Additive flags: --device, --max_rows.
 """
 from __future__ import annotations
 
@@ -73,7 +73,8 @@ def score_csv(model: esmc.ESMC, csv_path: str, sequence: str, model_type: str, o
 def main(argv=None):
     args = parser().parse_args(argv)
     if args.model_type == "esm3_open" or args.use_structure:
-        print("esm3_open / --use_structure (ESM3 with structure tracks) is not supported on this path", file=sys.stderr)
+        print("esm3_open / --use_structure (ESM3 with structure tracks) is not supported on this path: "
+              "use proteingym_amd.score_esm3_proteingym", file=sys.stderr)
         return 2
     if not args.model_path:
         print("--model_path is required: give the ESMC state dict (.pth) or its snapshot directory (this path never downloads)",

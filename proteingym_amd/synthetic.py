@@ -559,3 +559,101 @@ def saprot_state_dict(cfg: dict, seed: int, embed_std: float = 0.15) -> Dict[str
     ln("lm_head.layer_norm")
     sd["lm_head.bias"] = normal((V,), 0.02)
     return sd
+
+
+def esm3_config(embed_dim: int = 1536, layers: int = 48, v_heads: int = 256) -> dict:
+    """An ESM3 configuration (esm/pretrained.py:101-117 by default): ESM C's block shape plus the geometric attention's v_heads."""
+    return dict(esmc_config(embed_dim, layers), v_heads=v_heads)
+
+
+ESM3_HEADS = (("sequence_head", 64), ("structure_head", 4096), ("ss8_head", 11), ("sasa_head", 19), ("function_head", 260 * 8),
+              ("residue_head", 1478))
+
+
+def esm3_state_dict(cfg: dict, seed: int) -> Dict[str, np.ndarray]:
+    """Seeded random ESM3 weights under every key of ESM3.state_dict() (the five output heads this project does not pack included, so
+    that the reference loads it strictly).  Blocks as esmc_state_dict; the track embeddings N(0, 0.3^2 .. 1), the padding rows of the
+    function and residue tables zero as nn.Embedding(padding_idx=0) leaves them; both per-head scales of the geometric attention
+    N(0, 1), so non-zero: the rotation and the distance term both carry weight."""
+    normal = _causal_normal(seed)
+    D, F, Hv = cfg["embed_dim"], cfg["ffn_dim"], cfg["v_heads"]
+    sd = {"encoder.sequence_embed.weight": normal((64, D), 1.0)}
+    for n in ("plddt_projection", "structure_per_res_plddt_projection"):
+        sd[f"encoder.{n}.weight"] = normal((D, 16), 0.25)
+        sd[f"encoder.{n}.bias"] = normal((D,), 0.02)
+    sd["encoder.structure_tokens_embed.weight"] = normal((4096 + 5, D), 0.5)
+    sd["encoder.ss8_embed.weight"] = normal((11, D), 0.3)
+    sd["encoder.sasa_embed.weight"] = normal((19, D), 0.3)
+    for k in range(8):
+        w = normal((260, D // 8), 0.3)
+        w[0] = 0.0
+        sd[f"encoder.function_embed.{k}.weight"] = w
+    w = normal((1478, D), 0.3)
+    w[0] = 0.0
+    sd["encoder.residue_embed.weight"] = w
+    for i in range(cfg["layers"]):
+        p = f"transformer.blocks.{i}."
+        sd[p + "attn.layernorm_qkv.0.weight"] = 1.0 + normal((D,), 0.1)
+        sd[p + "attn.layernorm_qkv.0.bias"] = normal((D,), 0.02)
+        sd[p + "attn.layernorm_qkv.1.weight"] = normal((3 * D, D), D ** -0.5)
+        sd[p + "attn.out_proj.weight"] = normal((D, D), D ** -0.5)
+        sd[p + "attn.q_ln.weight"] = 1.0 + normal((D,), 0.1)
+        sd[p + "attn.k_ln.weight"] = 1.0 + normal((D,), 0.1)
+        if i == 0:
+            sd[p + "geom_attn.distance_scale_per_head"] = normal((Hv,), 1.0)
+            sd[p + "geom_attn.rotation_scale_per_head"] = normal((Hv,), 1.0)
+            sd[p + "geom_attn.s_norm.weight"] = 1.0 + normal((D,), 0.1)
+            sd[p + "geom_attn.proj.weight"] = normal((15 * Hv, D), D ** -0.5)
+            sd[p + "geom_attn.out_proj.weight"] = normal((D, 3 * Hv), (3 * Hv) ** -0.5)
+        sd[p + "ffn.0.weight"] = 1.0 + normal((D,), 0.1)
+        sd[p + "ffn.0.bias"] = normal((D,), 0.02)
+        sd[p + "ffn.1.weight"] = normal((2 * F, D), D ** -0.5)
+        sd[p + "ffn.3.weight"] = normal((D, F), F ** -0.5)
+    sd["transformer.norm.weight"] = 1.0 + normal((D,), 0.1)
+    for name, n_out in ESM3_HEADS:
+        p = f"output_heads.{name}."
+        sd[p + "0.weight"] = normal((D, D), D ** -0.5)
+        sd[p + "0.bias"] = normal((D,), 0.02)
+        sd[p + "2.weight"] = 1.0 + normal((D,), 0.1)
+        sd[p + "2.bias"] = normal((D,), 0.02)
+        sd[p + "3.weight"] = normal((n_out, D), 3.0 * D ** -0.5)
+        sd[p + "3.bias"] = normal((n_out,), 0.02)
+    return sd
+
+
+def esm3_encoder_config(d_model: int = 1024, v_heads: int = 128, layers: int = 2, d_out: int = 128, n_codes: int = 4096) -> dict:
+    """A StructureTokenEncoder configuration (esm/pretrained.py:30-34 by default; n_heads is unused: its blocks have no plain
+    attention)."""
+    return dict(d_model=d_model, v_heads=v_heads, layers=layers, d_out=d_out, n_codes=n_codes, ffn_dim=int(((4 * d_model) + 255) // 256 * 256))
+
+
+def esm3_encoder_state_dict(cfg: dict, seed: int) -> Dict[str, np.ndarray]:
+    """Seeded random StructureTokenEncoder weights under its state-dict keys (vqvae.py:182-194; the codebook's three buffers
+    included).  Every Linear and LayerNorm has a bias (bias=True blocks); the relative-position table N(0, 1) rather than the 0.02 of
+    its initialiser, so that neighbourhoods differ visibly; both per-head scales N(0, 1)."""
+    normal = _causal_normal(seed)
+    D, F, Hv, O, K = cfg["d_model"], cfg["ffn_dim"], cfg["v_heads"], cfg["d_out"], cfg["n_codes"]
+    sd = {}
+    for i in range(cfg["layers"]):
+        p = f"transformer.blocks.{i}."
+        sd[p + "geom_attn.distance_scale_per_head"] = normal((Hv,), 1.0)
+        sd[p + "geom_attn.rotation_scale_per_head"] = normal((Hv,), 1.0)
+        sd[p + "geom_attn.s_norm.weight"] = 1.0 + normal((D,), 0.1)
+        sd[p + "geom_attn.s_norm.bias"] = normal((D,), 0.02)
+        sd[p + "geom_attn.proj.weight"] = normal((15 * Hv, D), D ** -0.5)
+        sd[p + "geom_attn.proj.bias"] = normal((15 * Hv,), 0.02)
+        sd[p + "geom_attn.out_proj.weight"] = normal((D, 3 * Hv), (3 * Hv) ** -0.5)
+        sd[p + "geom_attn.out_proj.bias"] = normal((D,), 0.02)
+        sd[p + "ffn.0.weight"] = 1.0 + normal((D,), 0.1)
+        sd[p + "ffn.0.bias"] = normal((D,), 0.02)
+        sd[p + "ffn.1.weight"] = normal((2 * F, D), D ** -0.5)
+        sd[p + "ffn.1.bias"] = normal((2 * F,), 0.02)
+        sd[p + "ffn.3.weight"] = normal((D, F), F ** -0.5)
+        sd[p + "ffn.3.bias"] = normal((D,), 0.02)
+    sd["pre_vq_proj.weight"] = normal((O, D), D ** -0.5)
+    sd["pre_vq_proj.bias"] = normal((O,), 0.02)
+    sd["codebook.embeddings"] = normal((K, O), 1.0)
+    sd["codebook.N"] = np.zeros((K,), np.float32)
+    sd["codebook.z_avg"] = sd["codebook.embeddings"].copy()
+    sd["relative_positional_embedding.embedding.weight"] = normal((2 * 32 + 2, D), 1.0)
+    return sd
