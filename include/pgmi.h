@@ -70,6 +70,10 @@ extern "C" {
  * geometric attention branch over per-token backbone frames; created with pgmi_esm3_model_create, a window's structure bound with
  * pgmi_esm3_set_structure, scored with pgmi_token_logprobs / pgmi_masked_logprobs (see the ESM3 section below) */
 #define PGMI_ARCH_ESM3 11
+/* ESM-IF1 (proteingym/baselines/esm/esm/inverse_folding/gvp_transformer.py): the autoregressive decoder of the GVP-Transformer, every
+ * layer cross-attending to one encoded backbone; created with pgmi_esmif1_model_create, the backbone's encoder output bound with
+ * pgmi_esmif1_set_memory, scored with pgmi_esmif1_* (see the ESM-IF1 section below) */
+#define PGMI_ARCH_ESMIF1 12
 
 /* GEMM operand precision.  Residual stream, LayerNorm statistics, softmax and every
  * accumulator are fp32 in all modes. */
@@ -235,7 +239,8 @@ void pgmi_optimal_window(int position, int seq_len_with_special, int model_windo
 #define PGMI_K_KEPT_ROWS 9   /* last layer after attention, on the kept (masked) rows only: gathers + out-projection + LN + FFN */
 #define PGMI_K_MOE_ROUTE 10  /* ProGen3: permutation, gather and weighted combine around the expert GEMMs (the router rides in PGMI_K_LAYERNORM) */
 #define PGMI_K_GEOM 11       /* ESM3: block 0's geometric attention kernel (its LayerNorm and two GEMMs ride in their own classes) */
-#define PGMI_K_COUNT 12
+#define PGMI_K_CROSS_ATTENTION 12 /* ESM-IF1: the cross-attention over the encoder memory (its q prep and kernel; in set_memory the plane prep) */
+#define PGMI_K_COUNT 13
 /* on != 0: every launch of the classes above is bracketed by hipEventRecord on the stream. */
 int pgmi_profile_enable(pgmi_model* m, int on);
 /* Sum of event-measured milliseconds, launch count and algorithmic FLOPs / bytes for a class
@@ -260,7 +265,7 @@ int pgmi_set_option(const char* name, int64_t value);
 int pgmi_op_layernorm(int device, const float* x, const float* w, const float* b,
                       int rows, int D, float eps, float* y);               /* modules.py:80-81 */
 int pgmi_op_gemm(int device, int precision, const float* A, const float* W, const float* bias,
-                 const float* residual, int M, int N, int K, int epilogue /*0 none,1 gelu,2 squared relu,3 tanh-gelu,4 SwiGLU;
+                 const float* residual, int M, int N, int K, int epilogue /*0 none,1 gelu,2 squared relu,3 tanh-gelu,4 SwiGLU,5 relu (f16x3 only);
                  +256 (f16x3): the split-fp16-plane output epilogue, its planes returned rebuilt as fp32*/,
                  float* C);          /* C = epi(A W^T + bias) + residual; modules.py:134-140.
                                       * SwiGLU (4 + 256 only, f16x3, N % 64 == 0): W and bias in blocks of 64 rows = 32 gate rows then
@@ -310,6 +315,14 @@ int pgmi_op_causal_attention(int device, int lanes, const float* X, const float*
  * split != 0: the split-plane context the out-projection consumes, rebuilt as fp32; 0: the kernel's fp32 rows. */
 int pgmi_op_prefix_attention(int device, const float* qkv, const int32_t* seg_off, int n_seg, const float* prefix_kv, int P, int heads,
                              int split, float* ctx);
+/* ESM-IF1's cross-attention (attention_prefix.hip, the prefix-only instantiation) in SLOT SPACE, through the prep passes and the launcher
+ * the model uses; heads of 64 lanes, Da = 64 heads, q taken as given (pre-scaled).  q fp32 [seg_off[n_seg]][Da]: the packed query rows
+ * of n_seg non-empty segments; mem_kv fp32 [S][2 Da] (k | v), S >= 1.  Every query row sees the S memory keys, unmasked, and nothing
+ * else; the memory planes are written once by the prep pass over one segment of S rows (as pgmi_esmif1_set_memory fills a layer's
+ * planes) and start as 0xFF bytes (NaN), as does the context.  ctx [rows][Da]: split != 0: the split-plane context the out-projection
+ * consumes, rebuilt as fp32; 0: the kernel's fp32 rows.  S <= 0, an empty segment or a NULL pointer is PGMI_EINVAL. */
+int pgmi_op_cross_attention(int device, const float* q, const int32_t* seg_off, int n_seg, const float* mem_kv, int S, int heads,
+                            int split, float* ctx);
 /* ProGen3's pieces (elementwise.hip rmsnorm16_kernel, moe.hip, api_progen3.hip moe_ffn) on their own buffers.
  * pgmi_op_rmsnorm: y [rows][D] = the split operand launch_rmsnorm16 writes, rebuilt as fp32 (hi + lo 2^-11); D % 32 == 0, D <= 5120.
  * pgmi_op_moe: the routed block on fp32 rows h [M][D] taken as they are (no norm): gate [E][D] (ignored when E == 1); w1 [E][F][D],
@@ -601,6 +614,39 @@ int pgmi_poet_set_prompt(pgmi_model* m, const int32_t* tokens, const int32_t* se
 int pgmi_poet_prompt_logprobs(pgmi_model* m, float* out);
 int pgmi_poet_token_logprobs(pgmi_model* m, const int32_t* tokens, const int32_t* lens, int B, int T, float* out);
 int pgmi_poet_sequence_loglik(pgmi_model* m, const int32_t* tokens, const int32_t* lens, int B, int T, double* out);
+
+/* ---- ESM-IF1 (arch PGMI_ARCH_ESMIF1; the decoder; vocab <= 64, head_dim 64, precision f16x3) -------------------------------------
+ * Tokens (esm/data.py Alphabet.from_architecture("invariant_gvp"), 35 ids): <pad> 1, "LAGVSERTIDPKQNFYMHWCXBUZO.-" 4..30, <mask> 32,
+ * <cath> 33.  A sequence of L residues is <cath> + its L ids (no eos): the model reads the first L tokens and predicts the L residues.
+ * x = sqrt(D) embed_tokens[tok] + sinusoidal(2 + t) (esm/modules.py SinusoidalPositionalEmbedding, sin | cos halves; the table is built
+ * at creation for min(16384, max_rows) positions); per layer, pre-LN: causal self-attention, cross-attention over the S rows of the
+ * encoder output (q from the decoder row; k / v from the memory; all with biases, q scaled by head_dim^-1/2), fc2(relu(fc1 x)); then
+ * layer_norm and output_projection [V,D] without bias.  The encoder runs outside the library, once per structure.
+ * Config: layers / embed_dim / heads / ffn_dim = decoder_*; max_positions = the largest memory in rows (residues + 2) the caller will
+ * set (the per-layer K / V^T planes are allocated for it).  Decoder length and memory length are independent.
+ * Weight blob order (fp32, nn.Linear layout [out,in], names under `decoder.`):
+ *   embed_tokens.weight [V,D];
+ *   per layer layers.{i}: self_attn_layer_norm w,b; self_attn.{q,k,v}_proj W[D,D],b each; self_attn.out_proj W,b;
+ *        encoder_attn_layer_norm w,b; encoder_attn.q_proj W[D,D],b; encoder_attn.{k,v}_proj W[D,E],b each (E = enc_dim);
+ *        encoder_attn.out_proj W,b; final_layer_norm w,b; fc1 W[F,D],b[F]; fc2 W[D,F],b[D];
+ *   layer_norm w,b; output_projection.weight [V,D].
+ *
+ * pgmi_esmif1_weight_count: the blob size for (cfg, enc_dim); <0 on a bad cfg.  (pgmi_weight_count returns -1 for this arch.)
+ * pgmi_esmif1_model_create: as pgmi_model_create, with enc_dim = encoder_embed_dim (a multiple of 32).  A head_dim other than 64 is
+ *   PGMI_EINVAL.  Returns an ordinary model: destroy, profile, synchronize as usual.
+ * pgmi_esmif1_set_memory: enc_out f32 [S][enc_dim], the encoder's output rows of one backbone (the two end rows the reference pads with
+ *   included).  Every layer's k_proj / v_proj (with bias) of it goes into that layer's planes; scoring never re-packs them.
+ *   S > max_positions (or the workspace rows), S <= 0 and a non-finite value are PGMI_EINVAL; after any failure no memory is set.
+ * pgmi_esmif1_token_logprobs: sequences int32 [B,T] right-padded (pad values are not read), lens[b] >= 1 tokens; out f32 [B,T,V],
+ *   row (b,t) = log p(. | memory, tokens[b, <= t]) for t < lens[b]; rows beyond lens[b] are NaN.
+ * pgmi_esmif1_sequence_loglik: lens[b] >= 2; out f64 [B], out[b] = mean over t < lens[b]-1 of log p(tokens[b,t+1] | memory,
+ *   tokens[b, <= t]) = the reference's -mean(cross_entropy): fp32 terms summed left to right in fp64 on the device, divided by the
+ *   count.  A sequence's result has the same bits whatever else is in the call and however the call is chunked. */
+int64_t pgmi_esmif1_weight_count(const pgmi_config* cfg, int enc_dim);
+int pgmi_esmif1_model_create(const pgmi_config* cfg, int enc_dim, const float* weights, int64_t n_weights, int device, pgmi_model** out);
+int pgmi_esmif1_set_memory(pgmi_model* m, const float* enc_out, int S);
+int pgmi_esmif1_token_logprobs(pgmi_model* m, const int32_t* tokens, const int32_t* lens, int B, int T, float* out);
+int pgmi_esmif1_sequence_loglik(pgmi_model* m, const int32_t* tokens, const int32_t* lens, int B, int T, double* out);
 
 /* ---- EVE / DeepSequence (Bayesian alignment VAE; its own handle and config, precision fp32) ------------------------------------
  * Replaces VAE_model.all_likelihood_components and the sampling loop of compute_evol_indices_chunk

@@ -20,11 +20,12 @@ ARCH_SAPROT = 8
 ARCH_POET = 9
 ARCH_PROGEN3 = 10
 ARCH_ESM3 = 11
+ARCH_ESMIF1 = 12
 GPT_POS_ROTARY, GPT_POS_LEARNED = 0, 1
 PREC_FP32, PREC_BF16, PREC_F16X3 = 0, 1, 2
 PRECISIONS = {"fp32": PREC_FP32, "bf16": PREC_BF16, "f16x3": PREC_F16X3}
 K_NAMES = ["embed", "layernorm", "gemm_qkv", "attention", "gemm_out", "gemm_fc1", "gemm_fc2",
-           "head", "score", "kept_rows", "moe_route", "geom"]
+           "head", "score", "kept_rows", "moe_route", "geom", "cross_attention"]
 
 
 EINVAL, ENOMEM, EHIP, ENODEV, EPARSE, EOVERFLOW = -1, -2, -3, -4, -5, -6          # include/pgmi.h PGMI_E*
@@ -113,6 +114,11 @@ SIGNATURES = [
     ("pgmi_poet_prompt_logprobs", C.c_int, [C.c_void_p, _f32p]),
     ("pgmi_poet_token_logprobs", C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, C.c_int, _f32p]),
     ("pgmi_poet_sequence_loglik", C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, C.c_int, _f64p]),
+    ("pgmi_esmif1_weight_count", C.c_int64, [C.POINTER(Config), C.c_int]),
+    ("pgmi_esmif1_model_create", C.c_int, [C.POINTER(Config), C.c_int, _f32p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
+    ("pgmi_esmif1_set_memory", C.c_int, [C.c_void_p, _f32p, C.c_int]),
+    ("pgmi_esmif1_token_logprobs", C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, C.c_int, _f32p]),
+    ("pgmi_esmif1_sequence_loglik", C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, C.c_int, _f64p]),
     ("pgmi_pg3_weight_count", C.c_int64, [C.POINTER(Config), C.POINTER(Pg3Params)]),
     ("pgmi_pg3_model_create", C.c_int, [C.POINTER(Config), C.POINTER(Pg3Params), _f32p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     ("pgmi_pg3_token_logprobs", C.c_int, [C.c_void_p, _i32p, C.c_int, C.c_int, _f32p]),
@@ -146,6 +152,7 @@ SIGNATURES = [
     ("pgmi_op_causal_attention", C.c_int, [C.c_int, C.c_int, _f32p, _f32p, _f32p, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p,
                                            C.c_int, C.c_int, C.c_int, _f32p]),
     ("pgmi_op_prefix_attention", C.c_int, [C.c_int, _f32p, _i32p, C.c_int, _f32p, C.c_int, C.c_int, C.c_int, _f32p]),
+    ("pgmi_op_cross_attention", C.c_int, [C.c_int, _f32p, _i32p, C.c_int, _f32p, C.c_int, C.c_int, C.c_int, _f32p]),
     ("pgmi_op_rmsnorm", C.c_int, [C.c_int, _f32p, _f32p, C.c_int, C.c_int, C.c_float, _f32p]),
     ("pgmi_op_geom_attention", C.c_int, [C.c_int, _f32p, _f32p, _f32p, _i32p, C.c_int, _f32p, _f32p, C.c_int, C.c_int, C.c_int, _f32p]),
     ("pgmi_op_geom_key_tile", C.c_int, [C.c_int]),

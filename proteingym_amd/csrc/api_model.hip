@@ -30,8 +30,9 @@ int check_cfg(const pgmi_config* c) {
     if (c->abi_version != PGMI_ABI_VERSION) { set_error("ABI version mismatch: got %d, library is %d", c->abi_version, PGMI_ABI_VERSION); return PGMI_EINVAL; }
     if (c->arch != PGMI_ARCH_ESM1B && c->arch != PGMI_ARCH_ESM2 && c->arch != PGMI_ARCH_TRANCEPTION && c->arch != PGMI_ARCH_MSA &&
         c->arch != PGMI_ARCH_PROGEN2 && c->arch != PGMI_ARCH_GPT && c->arch != PGMI_ARCH_ESMC && c->arch != PGMI_ARCH_SAPROT &&
-        c->arch != PGMI_ARCH_POET && c->arch != PGMI_ARCH_PROGEN3 && c->arch != PGMI_ARCH_ESM3) { set_error("unknown arch %d", c->arch); return PGMI_EINVAL; }
+        c->arch != PGMI_ARCH_POET && c->arch != PGMI_ARCH_PROGEN3 && c->arch != PGMI_ARCH_ESM3 && c->arch != PGMI_ARCH_ESMIF1) { set_error("unknown arch %d", c->arch); return PGMI_EINVAL; }
     if (c->layers <= 0 || c->embed_dim <= 0 || c->heads <= 0 || c->ffn_dim <= 0) { set_error("non-positive model dimension"); return PGMI_EINVAL; }
+    if (c->arch == PGMI_ARCH_ESMIF1) return if1_check(c, c->embed_dim);      // the encoder width is checked at creation
     if (esmc_blocks(c->arch)) {
         // the QK-LayerNorm prep pass holds a q / k row of D <= 2048 in registers; FC1's SwiGLU epilogue pairs 32-column blocks
         if (c->precision != PGMI_PREC_F16X3) { set_error("ESM C is available in precision f16x3 only"); return PGMI_EINVAL; }
@@ -246,6 +247,7 @@ int64_t pgmi_weight_count(const pgmi_config* c) {
     if (c->arch == PGMI_ARCH_POET) return -1;     // the blob depends on final_norm: pgmi_poet_weight_count
     if (c->arch == PGMI_ARCH_PROGEN3) return -1;  // the blob depends on pgmi_pg3_params: pgmi_pg3_weight_count
     if (c->arch == PGMI_ARCH_ESM3) return -1;     // the blob depends on v_heads: pgmi_esm3_weight_count
+    if (c->arch == PGMI_ARCH_ESMIF1) return -1;   // the blob depends on the encoder width: pgmi_esmif1_weight_count
     if (c->arch == PGMI_ARCH_ESMC) return esmc_weight_count(c);
     if (c->arch == PGMI_ARCH_MSA) {
         const int64_t attn = 2 * D + 4 * (D * D + D);
@@ -289,6 +291,11 @@ int pgmi_model_create(const pgmi_config* cfg, const float* w, int64_t n_weights,
     if (cfg && cfg->arch == PGMI_ARCH_ESM3) {
         if (out) *out = nullptr;
         set_error("ESM3 models are created with pgmi_esm3_model_create (it takes v_heads)");
+        return PGMI_EINVAL;
+    }
+    if (cfg && cfg->arch == PGMI_ARCH_ESMIF1) {
+        if (out) *out = nullptr;
+        set_error("ESM-IF1 decoders are created with pgmi_esmif1_model_create (it takes the encoder width)");
         return PGMI_EINVAL;
     }
     return model_create(cfg, w, n_weights, device, out, 0);
@@ -343,7 +350,7 @@ static int alloc_workspace(pgmi_model* m) {
 }
 
 // pgmi_model_create, pgmi_pg2_model_create and pgmi_gpt_model_create; arch_arg is ProGen2's rotary_dim or the causal decoder's
-// pos_kind, SaProt's <mask> id, PoET's final_norm, ESM3's v_heads (0 for every other arch); pg3: ProGen3's parameters
+// pos_kind, SaProt's <mask> id, PoET's final_norm, ESM3's v_heads, ESM-IF1's encoder width (0 for every other arch); pg3: ProGen3's parameters
 int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int device, pgmi_model** out, int arch_arg,
                  const pgmi_pg3_params* pg3) {
     if (!out) { set_error("null out"); return PGMI_EINVAL; }
@@ -352,10 +359,12 @@ int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int 
     if (rc) return rc;
     if (cfg->arch == PGMI_ARCH_PROGEN3 && (rc = pg3_check(cfg, pg3))) return rc;
     if (cfg->arch == PGMI_ARCH_ESM3 && (rc = esm3_check(cfg, arch_arg))) return rc;
+    if (cfg->arch == PGMI_ARCH_ESMIF1 && (rc = if1_check(cfg, arch_arg))) return rc;
     const int64_t need = cfg->arch == PGMI_ARCH_GPT ? gpt_weight_count(cfg, arch_arg)
                          : cfg->arch == PGMI_ARCH_PROGEN3 ? pg3_weight_count(cfg, pg3)
                          : cfg->arch == PGMI_ARCH_POET ? poet_weight_count(cfg, arch_arg)
-                         : cfg->arch == PGMI_ARCH_ESM3 ? esm3_weight_count(cfg, arch_arg) : pgmi_weight_count(cfg);
+                         : cfg->arch == PGMI_ARCH_ESM3 ? esm3_weight_count(cfg, arch_arg)
+                         : cfg->arch == PGMI_ARCH_ESMIF1 ? if1_weight_count(cfg, arch_arg) : pgmi_weight_count(cfg);
     if (need < 0) { set_error("causal decoder pos_kind %d: must be PGMI_GPT_POS_ROTARY or PGMI_GPT_POS_LEARNED", arch_arg); return PGMI_EINVAL; }
     if (!w || n_weights != need) {
         set_error("weight blob has %lld elements, config needs %lld", (long long)n_weights, (long long)need);
@@ -389,6 +398,7 @@ int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int 
         case PGMI_ARCH_POET: rc = create_poet(m, cfg, w, n_weights, arch_arg); break;
         case PGMI_ARCH_PROGEN3: rc = create_progen3(m, cfg, w, n_weights, pg3); break;
         case PGMI_ARCH_ESM3: rc = create_esm3(m, cfg, w, n_weights, arch_arg); break;
+        case PGMI_ARCH_ESMIF1: rc = create_esmif1(m, cfg, w, n_weights, arch_arg); break;
         default: rc = create_esm(m, cfg, w, n_weights);
     }
     if (!rc) rc = alloc_workspace(m);

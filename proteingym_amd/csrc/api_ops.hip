@@ -154,6 +154,11 @@ int pgmi_op_gemm(int device, int precision, const float* A, const float* W, cons
         set_error("SwiGLU GEMM op: precision f16x3 with the split-plane output (epilogue 4 + 256), N %% 64 == 0");
         return PGMI_EINVAL;
     }
+    if (epi == EPI_RELU && precision != PGMI_PREC_F16X3) {       // the ReLU epilogue exists in the f16x3 kernels only (ESM-IF1's decoder)
+        for (void* p : pool) hipFree(p);
+        set_error("ReLU GEMM op: precision f16x3 only");
+        return PGMI_EINVAL;
+    }
     if (split_planes && (precision == PGMI_PREC_FP32 || residual || (N % (precision == PGMI_PREC_F16X3 ? 32 : 4)))) {
         for (void* p : pool) hipFree(p);
         set_error("16-bit-plane GEMM op: f16x3 (N %% 32 == 0) or bf16 (N %% 4 == 0), no residual");
@@ -532,6 +537,72 @@ int pgmi_op_prefix_attention(int device, const float* qkv, const int32_t* seg_of
     cleanup();
     if (rc) return rc;
     if (e != hipSuccess) { set_error("prefix attention op failed: %s", hipGetErrorString(e)); return PGMI_EHIP; }
+    if (split)
+        for (size_t m = 0; m < R; ++m)
+            for (size_t n = 0; n < Da; ++n) {
+                const size_t o = ki_off(m, (int)n, (int)Da);
+                ctx[m * Da + n] = rebuild_split(h[o], h[o + 32]);
+            }
+    return PGMI_OK;
+}
+
+// ESM-IF1's cross-attention through launch_cross_q_prep / launch_cross_attention (attention_prefix.hip): the memory planes are filled by
+// the prep pass over one segment of S rows (as pgmi_esmif1_set_memory fills a layer's planes).
+int pgmi_op_cross_attention(int device, const float* q, const int32_t* seg_off, int n_seg, const float* mem_kv, int S, int heads,
+                            int split, float* ctx) {
+    if (!q || !seg_off || !ctx || !mem_kv || n_seg <= 0 || heads <= 0 || S <= 0 || seg_off[0] != 0) { set_error("bad argument"); return PGMI_EINVAL; }
+    std::vector<int32_t> ent_seg, ent_tile, pseg{0, S}, pent_seg, pent_tile;
+    for (int b = 0; b < n_seg; ++b) {
+        const int len = seg_off[b + 1] - seg_off[b];
+        if (len <= 0) { set_error("segment %d is empty", b); return PGMI_EINVAL; }
+        for (int j = 0; j * 32 < len; ++j) { ent_seg.push_back(b); ent_tile.push_back(j); }
+    }
+    for (int j = 0; j * 32 < S; ++j) { pent_seg.push_back(0); pent_tile.push_back(j); }
+    if (pgmi_device_count() <= 0) { set_error("no HIP device visible"); return PGMI_ENODEV; }
+    PGMI_HIP(hipSetDevice(device));
+    const size_t R = (size_t)seg_off[n_seg], Da = (size_t)heads * kHeadDim, ppitch = pent_seg.size() * 32;
+    std::vector<float> pq((size_t)S * 3 * Da, 0.0f);            // the memory rows as q | k | v with a zero q block
+    for (size_t t = 0; t < (size_t)S; ++t) memcpy(&pq[t * 3 * Da + Da], mem_kv + t * 2 * Da, 2 * Da * sizeof(float));
+    std::vector<void*> pool;
+    auto cleanup = [&]() { for (void* p : pool) hipFree(p); };
+    float *dq = nullptr, *dpq = nullptr, *dctx = nullptr;
+    int32_t *d_off = nullptr, *d_es = nullptr, *d_et = nullptr, *dp_off = nullptr, *dp_es = nullptr, *dp_et = nullptr;
+    unsigned short *q16 = nullptr, *pq16 = nullptr, *pk16 = nullptr, *pvt16 = nullptr, *c16 = nullptr;
+    int rc = 0;
+    if ((rc = dev_upload(pool, &dq, q, R * Da)) || (rc = dev_upload(pool, &d_off, seg_off, (size_t)n_seg + 1)) ||
+        (rc = dev_upload(pool, &d_es, ent_seg.data(), ent_seg.size())) || (rc = dev_upload(pool, &d_et, ent_tile.data(), ent_tile.size())) ||
+        (rc = dev_alloc(pool, &q16, 2 * R * Da)) || (rc = dev_alloc(pool, &c16, 2 * R * Da)) || (rc = dev_alloc(pool, &dctx, R * Da)) ||
+        (rc = dev_upload(pool, &dpq, pq.data(), pq.size())) || (rc = dev_upload(pool, &dp_off, pseg.data(), pseg.size())) ||
+        (rc = dev_upload(pool, &dp_es, pent_seg.data(), pent_seg.size())) || (rc = dev_upload(pool, &dp_et, pent_tile.data(), pent_tile.size())) ||
+        (rc = dev_alloc(pool, &pq16, 2 * (size_t)S * Da)) || (rc = dev_alloc(pool, &pk16, 2 * Da * ppitch)) ||
+        (rc = dev_alloc(pool, &pvt16, 2 * Da * ppitch))) {
+        cleanup();
+        return rc;
+    }
+    // what the kernels must write themselves starts as 0xFF bytes (NaN): an operand element or a context row they skip shows
+    hipError_t e = hipMemset(q16, 0xFF, 2 * R * Da * 2);
+    if (e == hipSuccess) e = hipMemset(c16, 0xFF, 2 * R * Da * 2);
+    if (e == hipSuccess) e = hipMemset(dctx, 0xFF, R * Da * 4);
+    if (e == hipSuccess) e = hipMemset(pk16, 0xFF, 2 * Da * ppitch * 2);
+    if (e == hipSuccess) e = hipMemset(pvt16, 0xFF, 2 * Da * ppitch * 2);
+    if (e != hipSuccess) { cleanup(); set_error("cross attention op failed: %s", hipGetErrorString(e)); return PGMI_EHIP; }
+    PrefixAttLaunch p;
+    p.qkv = dpq; p.seg_off = dp_off; p.ent_seg = dp_es; p.ent_tile = dp_et; p.n_seg = 1; p.n_ent = (int)pent_seg.size(); p.H = heads;
+    p.q16 = pq16; p.q_plane = (size_t)S * Da; p.k16 = pk16; p.vt16 = pvt16; p.pitch = ppitch;
+    rc = launch_prefix_prep(p);
+    PrefixAttLaunch a;
+    a.seg_off = d_off; a.ent_seg = d_es; a.ent_tile = d_et; a.n_seg = n_seg; a.n_ent = (int)ent_seg.size(); a.H = heads;
+    a.q16 = q16; a.q_plane = R * Da;
+    a.pk16 = pk16; a.pvt16 = pvt16; a.ppitch = ppitch; a.P = S;
+    a.out = split ? ATT_OUT_SPLIT : ATT_OUT_F32; a.ctx = dctx; a.ctx16 = c16;
+    if (!rc) rc = launch_cross_q_prep(dq, R, heads, q16, R * Da, nullptr);
+    if (!rc) rc = launch_cross_attention(a);
+    std::vector<unsigned short> h(rc || !split ? 0 : R * Da * 2);
+    e = hipDeviceSynchronize();
+    if (!rc && e == hipSuccess) e = split ? hipMemcpy(h.data(), c16, h.size() * 2, hipMemcpyDeviceToHost) : hipMemcpy(ctx, dctx, R * Da * 4, hipMemcpyDeviceToHost);
+    cleanup();
+    if (rc) return rc;
+    if (e != hipSuccess) { set_error("cross attention op failed: %s", hipGetErrorString(e)); return PGMI_EHIP; }
     if (split)
         for (size_t m = 0; m < R; ++m)
             for (size_t n = 0; n < Da; ++n) {

@@ -84,33 +84,6 @@ int create_poet(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n
     return rc;
 }
 
-// The (segment, tile) lists of a launch, on the host and (slot 0 / 1 of m->poet_meta) on the device.
-struct PoetPlan {
-    std::vector<int32_t> seg_off, ent_seg, ent_tile;
-    int32_t *d_seg_off = nullptr, *d_ent_seg = nullptr, *d_ent_tile = nullptr;
-    int n_seg() const { return (int)seg_off.size() - 1; }
-    int n_ent() const { return (int)ent_seg.size(); }
-    void add(int len) {
-        if (seg_off.empty()) seg_off.push_back(0);
-        const int b = n_seg();
-        for (int j = 0; j * 32 < len; ++j) { ent_seg.push_back(b); ent_tile.push_back(j); }
-        seg_off.push_back(seg_off.back() + len);
-    }
-};
-
-static size_t own_pitch(const pgmi_model* m) { return (size_t)m->max_rows / 32 * 32; }
-
-static int upload_plan(pgmi_model* m, PoetPlan& p, int slot) {
-    const size_t cap = (size_t)m->max_rows;
-    p.d_seg_off = m->poet_meta + (size_t)slot * (3 * cap + 2);
-    p.d_ent_seg = p.d_seg_off + cap + 2;
-    p.d_ent_tile = p.d_ent_seg + cap;
-    PGMI_HIP(hipMemcpyAsync(p.d_seg_off, p.seg_off.data(), p.seg_off.size() * 4, hipMemcpyHostToDevice, m->stream));
-    PGMI_HIP(hipMemcpyAsync(p.d_ent_seg, p.ent_seg.data(), p.ent_seg.size() * 4, hipMemcpyHostToDevice, m->stream));
-    PGMI_HIP(hipMemcpyAsync(p.d_ent_tile, p.ent_tile.data(), p.ent_tile.size() * 4, hipMemcpyHostToDevice, m->stream));
-    return PGMI_OK;
-}
-
 // The tiered forward over R packed rows (tokens in m->tokens, within-sequence positions in m->pos_idx); leaves the residual stream in
 // m->x.  p1: the sequences.  Prompt (p2 != nullptr): tier 2 runs over p2 (one segment, the whole prompt) and its K / V^T planes are the
 // cache of the layer.  Variants (p2 == nullptr): tier 2 runs over p1 with the first P cache rows as the shared prefix.

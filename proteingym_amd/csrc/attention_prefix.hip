@@ -31,6 +31,11 @@
 // keys are ~2 % of a 24 k prefix; the prompt's tier 2 (once per prompt and layer) runs entirely in this phase.
 // LDS budget: 2 stages x 16 KiB = 32 KiB per workgroup, 4 waves: up to 4 workgroups per CU fit the 160 KiB, registers (one wave per
 // SIMD per workgroup at ~200 VGPRs) allow 2.
+//
+// Cross-attention (ESM-IF1's encoder_attn, api_esmif1.hip) is the OWN = false instantiation: the prefix phase alone, the planes of the
+// encoded backbone as the prefix (P = S memory keys, the last S % 32 pad keys masked to P = 0 exactly by the same `lim` test), no
+// own-segment planes.  Its budget is the prefix phase's: the same 32 KiB of LDS and the same registers less the own-phase fragments.
+// The q planes come from cross_q_prep_kernel (no k / v of the decoder rows exist).  The OWN = true code is what it was.
 #include "attention_f16_common.h"
 
 namespace pgmi {
@@ -133,7 +138,7 @@ struct PrefixAttArgs {
     float* ctx; unsigned short* ctx16;
 };
 
-template <int OUT>
+template <int OUT, bool OWN = true>
 __global__ __launch_bounds__(PFX_WPB * 64) void prefix_attention_kernel(const PrefixAttArgs a) {
     __shared__ __attribute__((aligned(16))) u32x4 lds[2 * PFX_STG];
     // XCD-local order: workgroup i runs on XCD i % 8; head 8 s + i % 8 keeps all its workgroups (and its prefix planes) on one XCD
@@ -290,7 +295,7 @@ __global__ __launch_bounds__(PFX_WPB * 64) void prefix_attention_kernel(const Pr
     if (!active) return;                                        // no barrier below
 
     // ---- the wave's own segment: causal, tiles 0 .. jt, fragments straight from global memory ----
-    {
+    if constexpr (OWN) {
         const unsigned short* kb = a.k16 + ((size_t)h * a.pitch + prow0 + r) * 64 + kh * 8;
         const unsigned short* vb = a.vt16 + ((size_t)h * 64 + r) * a.pitch + prow0 + kh * 8;
         for (int kt = 0; kt <= jt; ++kt) {
@@ -362,6 +367,61 @@ int launch_prefix_attention(const PrefixAttLaunch& p) {
     if (blocks > 0x7fffffffll) { set_error("prefix attention: launch of %lld workgroups", blocks); return PGMI_EINVAL; }
     if (p.out == ATT_OUT_SPLIT) hipLaunchKernelGGL(prefix_attention_kernel<ATT_OUT_SPLIT>, dim3((unsigned)blocks), dim3(PFX_WPB * 64), 0, p.stream, a);
     else hipLaunchKernelGGL(prefix_attention_kernel<ATT_OUT_F32>, dim3((unsigned)blocks), dim3(PFX_WPB * 64), 0, p.stream, a);
+    PGMI_HIP(hipGetLastError());
+    return PGMI_OK;
+}
+
+// fp32 q rows [rows][H 64] -> the two q16 planes, times log2(e): what prefix_prep_kernel does to its q block without rotary.
+// One thread per 8-column chunk.
+__global__ __launch_bounds__(256) void cross_q_prep_kernel(const float* __restrict__ q, size_t n_chunks, unsigned short* __restrict__ q16,
+                                                           size_t q_plane) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_chunks) return;
+    const f32x4 a0 = *reinterpret_cast<const f32x4*>(q + i * 8), a1 = *reinterpret_cast<const f32x4*>(q + i * 8 + 4);
+    _Float16 hh[8], ll[8];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { split_act(a0[k] * kQLog2e, hh[k], ll[k]); split_act(a1[k] * kQLog2e, hh[4 + k], ll[4 + k]); }
+    const u32x4 vh = {pack_h2(hh[0], hh[1]), pack_h2(hh[2], hh[3]), pack_h2(hh[4], hh[5]), pack_h2(hh[6], hh[7])};
+    const u32x4 vl = {pack_h2(ll[0], ll[1]), pack_h2(ll[2], ll[3]), pack_h2(ll[4], ll[5]), pack_h2(ll[6], ll[7])};
+    *reinterpret_cast<u32x4*>(q16 + i * 8) = vh;
+    *reinterpret_cast<u32x4*>(q16 + q_plane + i * 8) = vl;
+}
+
+int launch_cross_q_prep(const float* q, size_t rows, int H, unsigned short* q16, size_t q_plane, hipStream_t s) {
+    const size_t n_chunks = rows * (size_t)H * 8, blocks = (n_chunks + 255) / 256;
+    if (!q || !q16 || rows == 0 || H <= 0 || q_plane < rows * (size_t)H * 64 || blocks > 0x7fffffffull) {
+        set_error("cross attention prep: bad arguments rows=%zu H=%d", rows, H);
+        return PGMI_EINVAL;
+    }
+    hipLaunchKernelGGL(cross_q_prep_kernel, dim3((unsigned)blocks), dim3(256), 0, s, q, n_chunks, q16, q_plane);
+    PGMI_HIP(hipGetLastError());
+    return PGMI_OK;
+}
+
+int launch_cross_attention(const PrefixAttLaunch& p) {
+    if (p.H <= 0 || p.n_seg <= 0 || p.n_ent <= 0 || p.P <= 0 || !p.seg_off || !p.ent_seg || !p.ent_tile || !p.q16 || !p.pk16 || !p.pvt16) {
+        set_error("cross attention: bad arguments H=%d segments=%d tiles=%d S=%d", p.H, p.n_seg, p.n_ent, p.P);
+        return PGMI_EINVAL;
+    }
+    if (p.ppitch % 32 || (size_t)(p.P + 31) / 32 * 32 > p.ppitch) {
+        set_error("cross attention: %d memory keys do not fit the operand pitch %zu", p.P, p.ppitch);
+        return PGMI_EINVAL;
+    }
+    if ((p.out == ATT_OUT_F32 && !p.ctx) || (p.out == ATT_OUT_SPLIT && !p.ctx16) || (p.out != ATT_OUT_F32 && p.out != ATT_OUT_SPLIT)) {
+        set_error("cross attention: fp32 or split-plane context rows only");
+        return PGMI_EINVAL;
+    }
+    PrefixAttArgs a;
+    a.q16 = p.q16; a.q_plane = p.q_plane;
+    a.k16 = nullptr; a.vt16 = nullptr; a.pitch = 0;
+    a.pk16 = p.pk16; a.pvt16 = p.pvt16; a.ppitch = p.ppitch; a.P = p.P;
+    a.seg_off = p.seg_off; a.ent_seg = p.ent_seg; a.ent_tile = p.ent_tile;
+    a.n_ent = p.n_ent; a.n_grp = (p.n_ent + PFX_WPB - 1) / PFX_WPB; a.H = p.H;
+    a.ctx = p.ctx; a.ctx16 = p.ctx16;
+    const long long blocks = 8ll * ((p.H + 7) / 8) * a.n_grp;
+    if (blocks > 0x7fffffffll) { set_error("cross attention: launch of %lld workgroups", blocks); return PGMI_EINVAL; }
+    if (p.out == ATT_OUT_SPLIT) hipLaunchKernelGGL((prefix_attention_kernel<ATT_OUT_SPLIT, false>), dim3((unsigned)blocks), dim3(PFX_WPB * 64), 0, p.stream, a);
+    else hipLaunchKernelGGL((prefix_attention_kernel<ATT_OUT_F32, false>), dim3((unsigned)blocks), dim3(PFX_WPB * 64), 0, p.stream, a);
     PGMI_HIP(hipGetLastError());
     return PGMI_OK;
 }

@@ -27,7 +27,8 @@ constexpr int kWave = 64;
 constexpr int kHeadDim = 64;
 
 enum Epilogue { EPI_NONE = 0, EPI_GELU = 1, EPI_SQRELU = 2, EPI_GELU_TANH = 3,   // erf-GELU (ESM), squared ReLU (Tranception), tanh-GELU (ProGen2)
-                EPI_SWIGLU = 4 };   // ESM C's FC1: W rows in blocks of 64 = 32 gate | 32 up rows; out column 32 b + i = silu(gate) * up, N / 2 wide
+                EPI_SWIGLU = 4,     // ESM C's FC1: W rows in blocks of 64 = 32 gate | 32 up rows; out column 32 b + i = silu(gate) * up, N / 2 wide
+                EPI_RELU = 5 };     // ESM-IF1's decoder FC1 (f16x3 only)
 
 // f16x3 activation split: x ~= hi + lo * 2^-11 with hi = fp16(x) and lo = fp16((x - hi) * 2^11).
 // The scaled lo keeps its 11 bits for every |x| >= 2^-14 (an unscaled lo would be an fp16
@@ -122,6 +123,9 @@ void launch_seq_loglik_ragged(const float* lp, const int32_t* tokens, const int3
 void launch_pg2_seq_loglik(const float* lp, const int32_t* col, const int32_t* n_kept, int B, int T, int V, float* out, hipStream_t s);
 // causal decoder (api_gpt.hip): x[row] = E[tokens[row]] + P[row % T]
 void launch_embed_learned(const int32_t* tokens, const float* E, const float* P, int rows, int T, int D, float* x, hipStream_t s);
+// ESM-IF1's decoder (api_esmif1.hip): x[row] = scale * E[tokens[row]] + P[pos[row]] (P: the sinusoidal table built at creation)
+void launch_embed_scaled_pos(const int32_t* tokens, const int32_t* pos, const float* E, const float* P, float scale, int rows, int D,
+                             float* x, hipStream_t s);
 // log-softmax over V > 64 columns of fp32 logits [rows][ldl] (ldl % 4 == 0, pad columns excluded by index): out[r] = log p(tgt[r])
 // when tgt != nullptr, else the full rows out [rows][V]
 void launch_wide_logsoftmax(const float* logits, int ldl, int rows, int V, const int32_t* tgt, float* out, int32_t* nonfinite,
@@ -420,6 +424,11 @@ struct PrefixAttLaunch {
 };
 int launch_prefix_prep(const PrefixAttLaunch& p);
 int launch_prefix_attention(const PrefixAttLaunch& p);
+// Cross-attention (ESM-IF1's encoder_attn): the prefix phase alone.  Every query row of every segment sees the P keys of the pk16 / pvt16
+// planes, unmasked, and nothing else; k16 / vt16 / pitch / qkv / pos are not read.  launch_cross_q_prep: fp32 q rows [rows][H 64]
+// (pre-scaled by head_dim^-1/2) -> the q16 planes (times log2 e); launch_cross_attention: q16 -> ctx / ctx16.
+int launch_cross_q_prep(const float* q, size_t rows, int H, unsigned short* q16, size_t q_plane, hipStream_t s);
+int launch_cross_attention(const PrefixAttLaunch& p);
 
 int att16_waves_per_block(int T);
 int att_set_option(const char* name, long long value);      // "att_xcd_local": block order of the dense attention launches (A/B only)

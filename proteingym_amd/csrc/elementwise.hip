@@ -633,6 +633,29 @@ void launch_embed_learned(const int32_t* tokens, const float* E, const float* P,
     hipLaunchKernelGGL(embed_learned_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, tokens, E, P, rows, T, D, x);
 }
 
+// ESM-IF1's decoder embedding: x[row] = scale * E[tokens[row]] + P[pos[row]] (one wave per row, D % 4 == 0)
+__global__ __launch_bounds__(256) void embed_scaled_pos_kernel(const int32_t* __restrict__ tokens, const int32_t* __restrict__ pos,
+                                                               const float* __restrict__ E, const float* __restrict__ P, float scale,
+                                                               int rows, int D, float* __restrict__ x) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const f32x4* e = reinterpret_cast<const f32x4*>(E + (size_t)tokens[row] * D);
+    const f32x4* p = reinterpret_cast<const f32x4*>(P + (size_t)pos[row] * D);
+    f32x4* xo = reinterpret_cast<f32x4*>(x + (size_t)row * D);
+    for (int i = lane; i < D / 4; i += 64) {
+        const f32x4 ev = e[i], pv = p[i];
+        f32x4 o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = fmaf(scale, ev[k], pv[k]);
+        xo[i] = o;
+    }
+}
+void launch_embed_scaled_pos(const int32_t* tokens, const int32_t* pos, const float* E, const float* P, float scale, int rows, int D,
+                             float* x, hipStream_t s) {
+    hipLaunchKernelGGL(embed_scaled_pos_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, tokens, pos, E, P, scale, rows, D, x);
+}
+
 // Log-softmax over a wide vocabulary (V > 64: ProtGPT2's 50 257).  One 256-thread workgroup per row of fp32 logits [rows][ldl]
 // (ldl % 4 == 0; columns V .. ldl-1 are padding, excluded by index, never by value).  The row is read once: thread i takes the
 // float4s i, i + 256, ... and keeps a running max m and s = sum exp(x - m) in double (rescaled when m grows); the 256 (m, s) pairs

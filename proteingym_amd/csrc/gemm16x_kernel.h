@@ -582,6 +582,9 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
                         if (EPI == EPI_SQRELU)   // tranception/activations.py:79-84
 #pragma unroll
                         for (int e = 0; e < 4; ++e) { const float t = fmaxf(val[e], 0.0f); val[e] = t * t; }
+                        if (EPI == EPI_RELU)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) val[e] = fmaxf(val[e], 0.0f);
                         if (residual) {
                             const f32x4 rr = __builtin_bit_cast(f32x4, rv[i & 1][j][k]);
 #pragma unroll
@@ -633,6 +636,9 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
                             if (EPI == EPI_SQRELU)
 #pragma unroll
                             for (int e = 0; e < 4; ++e) { const float t = fmaxf(val[e], 0.0f); val[e] = t * t; }
+                            if (EPI == EPI_RELU)
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) val[e] = fmaxf(val[e], 0.0f);
                             u32x2 pk;
                             pk[0] = (unsigned int)f32_to_bf16_rne(val[0]) | ((unsigned int)f32_to_bf16_rne(val[1]) << 16);
                             pk[1] = (unsigned int)f32_to_bf16_rne(val[2]) | ((unsigned int)f32_to_bf16_rne(val[3]) << 16);
@@ -744,6 +750,9 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
                         if (EPI == EPI_SQRELU)   // tranception/activations.py:79-84
 #pragma unroll
                         for (int e = 0; e < 4; ++e) { const float t = fmaxf(val[e], 0.0f); val[e] = t * t; }
+                        if (EPI == EPI_RELU)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) val[e] = fmaxf(val[e], 0.0f);
                         {
                             h4 hi, lo;
 #pragma unroll

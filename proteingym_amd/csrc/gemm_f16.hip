@@ -113,6 +113,7 @@ static const GemmInst kGemmInst[] = {
     inst<EPI_SQRELU, X_OUT_F32>(),                 inst<EPI_SQRELU, X_OUT_16>(),
     inst<EPI_GELU_TANH, X_OUT_F32>(),              inst<EPI_GELU_TANH, X_OUT_16>(),
     inst<EPI_SWIGLU, X_OUT_16>(),                                                                // f16x3, split-plane output only
+    inst<EPI_RELU, X_OUT_F32>(),                   inst<EPI_RELU, X_OUT_16>(),                   // f16x3 only (ESM-IF1's decoder)
     inst<EPI_NONE, X_OUT_F32, false, true>(),      inst<EPI_NONE, X_OUT_16, false, true>(),      inst<EPI_NONE, X_OUT_QKV, false, true>(),
     inst<EPI_GELU, X_OUT_F32, false, true>(),      inst<EPI_GELU, X_OUT_16, false, true>(),
     inst<EPI_SQRELU, X_OUT_F32, false, true>(),    inst<EPI_SQRELU, X_OUT_16, false, true>(),

@@ -12,6 +12,8 @@
 //                        the checks and token log-probs of RITA / ProtGPT2 / ProGen2; RITA / ProtGPT2 sequence log-likelihoods
 //   api_poet.hip         PoET: tiered (within-sequence, then sequence-of-sequences) causal decoder on attention_prefix.hip, the
 //                        per-layer prefix cache of a prompt, variant log-probs and log-likelihoods
+//   api_esmif1.hip       ESM-IF1's decoder: causal self-attention and cross-attention over the cached K / V^T planes of one encoded
+//                        backbone (attention_prefix.hip), token log-probs and per-sequence mean log-likelihoods
 //   api_progen3.hip      ProGen3 weights (RMSNorm, grouped-query attention as replicated K/V projection rows, per-expert FC1 / FC2), its
 //                        feed-forward block on moe.hip (pg3_ffn, moe_ffn), the C entries; it runs on run_decoder
 //   api_esmc.hip         ESM C weights (QK-LayerNorm, SwiGLU, scaled residual, untied 64-column head); it runs on run_encoder
@@ -56,6 +58,10 @@ struct Layer {
     // MSA Transformer: ln1/wqkv/wo = tied row attention, c_* = column attention, ln2/w1/w2 = feed forward
     float *c_ln_w = nullptr, *c_ln_b = nullptr, *c_bqkv = nullptr, *c_bo = nullptr;
     W16 c_wqkv16, c_wo16;
+    // ESM-IF1 decoder: ln1/wqkv/wo = causal self-attention, c_ln / c_wq16 + c_bq (q, from the decoder rows) / c_wqkv16 + c_bqkv (zero q
+    // block | k | v, from the encoder rows: [3 Da, D_enc]) / c_wo16 = encoder_attn, ln2/w1/w2 = feed forward
+    float* c_bq = nullptr;
+    W16 c_wq16;
     float *q_ln = nullptr, *k_ln = nullptr;       // ESM C: q_ln (times 1/8) / k_ln weights
     // ProGen3 with more than one expert: the router's fp32 gate [E,D]; per expert FC1 (gated: w1 | w3 in EPI_SWIGLU's 32 gate | 32 up
     // row blocks, [2F,D]; else w1 [F,D]) and FC2 [D,F].  One expert: w116 / w216 as for every other model.
@@ -148,6 +154,13 @@ struct pgmi_model {
     int poet_P = 0;
     std::vector<float> poet_prompt_lp;
     int32_t* poet_meta = nullptr;
+    // ESM-IF1 (api_esmif1.hip): the decoder.  The prefix cache above holds the encoded backbone's per-layer K / V^T planes (poet_P = S
+    // memory rows, 0: none set; poet_pitch = roundup(max_positions, 32)); if1_enc = the encoder width, if1_mem / if1_mem16 the staging
+    // of one encoder output [max_positions][if1_enc] (fp32, split), if1_pos the sinusoidal table [if1_pos_len][D] (row t = position
+    // padding_idx + 1 + t)
+    int if1_enc = 0, if1_pos_len = 0;
+    float *if1_mem = nullptr, *if1_pos = nullptr;
+    unsigned short* if1_mem16 = nullptr;
     // ESM3 (api_esm3.hip): v_heads and the out-projection's padded K; the structure-token table and the two folded constant rows; the
     // bound window (pgmi_esm3_set_structure): structure tokens, plddt flags, frames and frame mask of e3_T tokens, e3_framed = any frame
     int e3_vheads = 0, e3_Kp = 0;
@@ -323,6 +336,10 @@ int moe_ffn(pgmi_model* m, const pgmi_model::MoeWs& ws, const std::vector<W16>& 
 // api_poet.hip
 int64_t poet_weight_count(const pgmi_config* c, int final_norm);
 int create_poet(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights, int final_norm);
+// api_esmif1.hip
+int if1_check(const pgmi_config* c, int enc_dim);
+int64_t if1_weight_count(const pgmi_config* c, int enc_dim);
+int create_esmif1(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights, int enc_dim);
 // api_esmc.hip
 int64_t esmc_weight_count(const pgmi_config* c);
 int create_esmc(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights);
@@ -422,6 +439,34 @@ int upload_rotary(pgmi_model* m, int n, int groups, Angle angle) {
     if (!rc) rc = dev_upload(m->allocs, &m->rot_sin, s.data(), s.size());
     if (!rc) m->rot_len = n;
     return rc;
+}
+
+// attention_prefix.hip's launches (PoET, ESM-IF1): the (segment, tile) lists of a launch, on the host and (slot 0 / 1 of m->poet_meta)
+// on the device; own_pitch = the padded key rows the workspace's own-segment planes hold.
+struct PoetPlan {
+    std::vector<int32_t> seg_off, ent_seg, ent_tile;
+    int32_t *d_seg_off = nullptr, *d_ent_seg = nullptr, *d_ent_tile = nullptr;
+    int n_seg() const { return (int)seg_off.size() - 1; }
+    int n_ent() const { return (int)ent_seg.size(); }
+    void add(int len) {
+        if (seg_off.empty()) seg_off.push_back(0);
+        const int b = n_seg();
+        for (int j = 0; j * 32 < len; ++j) { ent_seg.push_back(b); ent_tile.push_back(j); }
+        seg_off.push_back(seg_off.back() + len);
+    }
+};
+
+inline size_t own_pitch(const pgmi_model* m) { return (size_t)m->max_rows / 32 * 32; }
+
+inline int upload_plan(pgmi_model* m, PoetPlan& p, int slot) {
+    const size_t cap = (size_t)m->max_rows;
+    p.d_seg_off = m->poet_meta + (size_t)slot * (3 * cap + 2);
+    p.d_ent_seg = p.d_seg_off + cap + 2;
+    p.d_ent_tile = p.d_ent_seg + cap;
+    PGMI_HIP(hipMemcpyAsync(p.d_seg_off, p.seg_off.data(), p.seg_off.size() * 4, hipMemcpyHostToDevice, m->stream));
+    PGMI_HIP(hipMemcpyAsync(p.d_ent_seg, p.ent_seg.data(), p.ent_seg.size() * 4, hipMemcpyHostToDevice, m->stream));
+    PGMI_HIP(hipMemcpyAsync(p.d_ent_tile, p.ent_tile.data(), p.ent_tile.size() * 4, hipMemcpyHostToDevice, m->stream));
+    return PGMI_OK;
 }
 
 // Sequences of T tokens per workspace chunk: B * roundup(T, 32) <= max_rows, at least one.
