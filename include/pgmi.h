@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define PGMI_ABI_VERSION 4
+#define PGMI_ABI_VERSION 5
 
 /* error codes */
 #define PGMI_OK 0
@@ -797,6 +797,56 @@ int pgmi_mpnn_graph(pgmi_mpnn* m, int32_t* E_idx, float* E);
 int pgmi_mpnn_encoder(pgmi_mpnn* m, float* h_V, float* h_E);
 int pgmi_mpnn_log_probs(pgmi_mpnn* m, const uint8_t* S, const int32_t* rank, int B, float* out);
 int pgmi_mpnn_scores(pgmi_mpnn* m, const uint8_t* S, const int32_t* rank, int B, double* out);
+
+/* ---- UniRep (the 1900-unit multiplicative LSTM; its own handle and config, precision f16x3 or fp32) ---------------------------------
+ * Replaces babbler1900's graph (proteingym/baselines/unirep/unirep.py:318-408: embedding, mLSTMCell1900.call :81-132 under
+ * tf.nn.dynamic_rnn, Dense(25), tfa.seq2seq.sequence_loss) as unirep_inference.py:48-57 runs it.  DESIGN.md 4.6m has the restatement,
+ * the folding and the step's structure.
+ * Tokens (utils/data_utils.py:16-45): pad 0, M 1 .. L 21, O 22, X/Z/B/J 23, start 24, stop 25.  A formatted sequence is start + its
+ * residues (format_seq(stop=False)): n + 1 tokens for n residues; the model reads the first n and predicts the last n (classes
+ * target - 1; a target of 0 is masked out of the mean).
+ * Weight blob: fp32, what the host folds from the checkpoint's arrays in float64 (proteingym_amd/unirep.py fold): with w' = w *
+ * rsqrt(max(sum over rows of w^2, 1e-12)) * g per column (tf.nn.l2_normalize(axis=0) * g, unirep.py:119-122) and E the embedding,
+ *   Tmx [26][H] = E wmx';  Tx [26][4 H] = E wx' + b;  wmh' [H][H];  wh' [H][4 H] (columns i | f | o | u);  Dense kernel [H][25];
+ *   Dense bias [25].
+ * H is padded to a multiple of 32 inside the library (zero weights and table entries: the padded units stay at c = h = 0).
+ *
+ * pgmi_unirep_weight_count: size of the blob above; -1 for a config the library refuses (pgmi_last_error): bf16 is refused.
+ * pgmi_unirep_model_create / pgmi_unirep_destroy: the device-resident model (one HIP stream).
+ * pgmi_unirep_profile_model: the handle's profiling view (owned by the handle).  Classes: PGMI_K_GEMM_FC1 = h_prev wmh, PGMI_K_LAYERNORM
+ *   = the multiply by Tmx[token], PGMI_K_GEMM_FC2 = m wh, PGMI_K_ATTENTION = the gates, PGMI_K_HEAD = Dense + log-softmax, PGMI_K_EMBED
+ *   = the rows' initial state, PGMI_K_SCORE = the per-sequence mean.
+ * pgmi_unirep_set_target: tokens int32 [L + 1], the formatted target sequence.  Runs its L steps once and keeps, on the device, the
+ *   state (c, h) after every step and the [L][25] log-probability rows.  L = 0 clears the target; after a failure no target is set.
+ * pgmi_unirep_sequence_nll: n formatted sequences packed in tokens, sequence i = tokens[offsets[i] .. offsets[i+1]) (at least 2
+ *   tokens).  out f64 [n]: the mean negative log-likelihood sum(xent * mask) / (sum(mask) + 1e-12), fp32 terms added in double, left to
+ *   right.  With a target set and from_scratch == 0, a sequence's join step is the number of residues it shares with the target from
+ *   the left (0 when its first token differs): it runs the steps join .. n_i - 1 from the target's state after `join` steps, and its
+ *   terms before the join are read from the target's rows.  from_scratch != 0, or no target: every sequence runs from the zero state.
+ *   Both give the same bits.  Internally the sequences are grouped by length, ordered by join step and cut into chunks of at most
+ *   max_rows rows.  out_rowsteps (nullable): the (row, step) cell evaluations executed = sum of n_i - join_i.
+ * pgmi_unirep_token_logprobs: tokens int32 [L] = the inputs; out f32 [L][25], row t = log_softmax(Dense(h_t)) after tokens[0 .. t].
+ * pgmi_op_mlstm_step: one cell step of `rows` rows on caller-supplied state: h_prev, c_prev f32 [rows][H], tokens int32 [rows];
+ *   h, c f32 [rows][Hp] and the pre-activations z f32 [rows][4][Hp] (i, f, o, u), Hp = H rounded up to 32, padding included.
+ * pgmi_set_option("unirep_max_rows", n): rows per chunk (0: the config's max_rows, or 8192; test hook, bit-neutral). */
+typedef struct pgmi_unirep_config {
+    int32_t abi_version;                          /* = PGMI_ABI_VERSION */
+    int32_t hidden;                               /* H: 1900 for the released model */
+    int32_t vocab;                                /* = 26 */
+    int32_t precision;                            /* PGMI_PREC_F16X3 or PGMI_PREC_FP32 */
+    int32_t max_rows;                             /* rows per chunk; 0 = 8192 */
+} pgmi_unirep_config;
+typedef struct pgmi_unirep pgmi_unirep;
+int64_t pgmi_unirep_weight_count(const pgmi_unirep_config* cfg);
+int pgmi_unirep_model_create(const pgmi_unirep_config* cfg, const float* weights, int64_t n_weights, int device, pgmi_unirep** out);
+void pgmi_unirep_destroy(pgmi_unirep* m);
+pgmi_model* pgmi_unirep_profile_model(pgmi_unirep* m);
+int pgmi_unirep_set_target(pgmi_unirep* m, const int32_t* tokens, int L);
+int pgmi_unirep_sequence_nll(pgmi_unirep* m, const int32_t* tokens, const int64_t* offsets, int64_t n, int from_scratch, double* out,
+                             int64_t* out_rowsteps);
+int pgmi_unirep_token_logprobs(pgmi_unirep* m, const int32_t* tokens, int L, float* out);
+int pgmi_op_mlstm_step(pgmi_unirep* m, const float* h_prev, const float* c_prev, const int32_t* tokens, int rows, float* h, float* c,
+                       float* z);
 
 /* ---- MSA Transformer (arch PGMI_ARCH_MSA; vocab 33, head_dim 64, precision f16x3) --------------------
  * Replaces MSATransformer.forward (proteingym/baselines/esm/esm/model/msa_transformer.py:146-205; tied

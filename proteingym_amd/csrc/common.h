@@ -239,6 +239,32 @@ void launch_mpnn_head(const float* h, const float* W, const float* bias, const u
 void launch_mpnn_score(const float* nll, const float* mask, int B, int L, double* out, hipStream_t s);
 int mpnn_set_option(const char* name, long long value);   // api_mpnn.hip: "mpnn_max_rows"
 
+// ---- mlstm.hip (UniRep's mLSTM step around the two GEMMs; the kernels are described there) -------------------------------------
+// m = Tmx[tok[row * tok_stride]] * g1 [rows][Hp] -> the second product's operand: split rows m16, or fp32 m32 (exactly one)
+void launch_mlstm_m(const float* g1, const float* Tmx, const int32_t* tok, int tok_stride, int rows, int Hp, unsigned short* m16,
+                    float* m32, hipStream_t s);
+struct MlstmGate {
+    const float* z = nullptr;           // [rows][4 Hp]: m wh, gate g in columns g Hp ..
+    const float* Tx = nullptr;          // [26][4 Hp]: x wx + b per token
+    const int32_t* tok = nullptr;       // token of row r at tok[r * tok_stride]
+    int tok_stride = 0;
+    float* c = nullptr;                 // [rows][Hp] fp32, updated in place
+    unsigned short* h16 = nullptr;      // the next step's operand: split rows, or
+    float* h32 = nullptr;               // fp32 rows (exactly one)
+    float* hwin = nullptr;              // nullable: fp32 h rows for the head
+    float* z_out = nullptr;             // nullable: the pre-activations z + Tx [rows][4 Hp]
+    int rows = 0, Hp = 0;
+};
+void launch_mlstm_gate(const MlstmGate& a, hipStream_t s);
+// c / h of row r = entry join[r] of the target's table; terms[r][t < join[r]] from the target's log-probability rows (tlp nullable)
+void launch_mlstm_init(const float* ctab, const uint32_t* htab, const float* tlp, const int32_t* tgt, const int32_t* join, int rows,
+                       int Hp, int Lc, float* c, uint32_t* h, float* terms, hipStream_t s);
+// the Dense(25) head + log-softmax over the window's steps t0 .. t0 + nw - 1 (slot t % W of hwin), rows with join <= t
+void launch_mlstm_head(const float* hwin, size_t slot_stride, int W, const float* Wd, const float* bd, const int32_t* tgt,
+                       const int32_t* join, int Lc, int t0, int nw, int rows, int Hp, float* terms, float* lp, hipStream_t s);
+void launch_mlstm_score(const float* terms, const int32_t* tgt, int rows, int Lc, double* out, hipStream_t s);
+int unirep_set_option(const char* name, long long value);   // api_unirep.hip: "unirep_max_rows"
+
 // ---- gemm_f32.hip ------------------------------------------------------------------------
 // C[M,N] = epi(A[M,K] W[N,K]^T + bias[N]) (+ residual[M,N]); K % 32 == 0.
 // ---- msa_transformer.hip ------------------------------------------------------------------

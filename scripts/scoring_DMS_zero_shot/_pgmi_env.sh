@@ -57,6 +57,13 @@ pgmi_progen3() {
         --DMS_reference_file_path "${mapping}" --DMS_data_folder "${folder}" --DMS_index "${DMS_index:=0}" \
         --output_scores_folder "${output_scores_folder}" --max_batch_tokens "${max_batch_tokens:=65536}" "$@"
 }
+# pgmi_unirep <mapping csv> <data folder> <output folder> [more flags]: assay ${DMS_index} through score_unirep_proteingym with ${model_path}
+# (the reference launchers' variable: the checkpoint's .npy directory, or the folder of per-MSA evotuned directories with --evotune)
+pgmi_unirep() {
+    local mapping="$1" folder="$2" out="$3"; shift 3
+    pgmi_run proteingym_amd.score_unirep_proteingym --model_path "${model_path:=/path/to/unirep_weights}" --data_path "${folder}" \
+        --output_dir "${output_dir:=${out}}" --mapping_path "${mapping}" --DMS_index "${DMS_index:=0}" --batch_size "${batch_size:=32}" "$@"
+}
 # pgmi_causal_lm <module> <model flag> <model path> <mapping csv> <data folder> [more flags]: assay ${DMS_index} through the RITA /
 # ProtGPT2 scorers
 pgmi_causal_lm() {
