@@ -344,6 +344,34 @@ int pgmi_op_moe(int device, const float* h, const float* gate, const float* w1, 
 int pgmi_op_tied_row_attention(int device, const float* qkv, int R, int C, int H, int splits, float* ctx, float* probs);
 int pgmi_op_tied_row_splits(int R, int C, int H);
 int pgmi_op_column_attention(int device, const float* X, const float* W, const float* bias, int K, int R, int C, int H, float* ctx);
+/* The scoring tail (elementwise.hip) through the production launchers, on the entry's own buffers: host pointers in and out.  Every output
+ * buffer starts as 0xFF bytes (an element the kernel skips comes back as NaN) and carries 64 guard values behind it; a guard value the
+ * kernel touched fails the call with PGMI_EHIP.  *nonfinite: the device flag after the launch (zero before it).  Every refusal below is
+ * PGMI_EINVAL with a message, made before the device is looked for or anything is allocated, as is a NULL pointer or a non-positive size.
+ * pgmi_op_vocab_logsoftmax: h [rows][D], E [V][D], bias [V]; out [rows][V] = log_softmax(h E^T + bias).  One lane per logit: V outside
+ *   1 .. 64 is refused.
+ * pgmi_op_wide_logsoftmax: logits [rows][ldl], ldl % 4 == 0, ldl >= V; the columns V .. ldl-1 are padding whose values must not matter.
+ *   tgt NULL: out [rows][V]; else out [rows] = log p(column tgt[r]), every tgt[r] in [0, V).
+ * pgmi_op_group_logsoftmax: the grouped head; full [rows][V] and group [rows][groups] (either may be NULL, not both), groups of `width`
+ *   columns from column `first`.  What launch_group_logsoftmax refuses (D % 4, D > 2560, V > 512, more than 64 groups or columns per
+ *   group, groups past column V) comes back with its message.
+ * pgmi_op_seq_loglik: out [B] = sum over the targets of a sequence of the fused log-probability.  Dense form (lens != NULL): lp [B*T][V],
+ *   tokens [B*T], n_lp_rows = B T, lens[b] in [0, T]; target t of sequence b is tokens[b T + t + 1], read from row b T + t, t < lens[b] - 1.
+ *   Ragged form (lens == NULL): sequence b owns the T - seq_p[b] packed rows from seq_off[b] on (its tokens seq_p[b] .. T-1) and takes
+ *   the rows of the tokens before seq_p[b] from sequence seq_root[b], which must own all its T rows (seq_p == 0); every sequence sums
+ *   T - 1 targets.  prior (nullable) [n_prior_rows][V] with the windows a0 / row0 / n / flip [B]: target t in [a0, a0 + n) takes prior row
+ *   row0 + (t - a0), or row0 + n - 1 - (t - a0) when flip, as (1 - alpha) lp + alpha prior; eve (nullable, needs prior; same rows):
+ *   (1 - beta) that + beta eve, or `that` alone where eve is -inf and eve_fallback != 0.  Refused: a token outside [0, V), a window
+ *   with a0 + n > T - 1 or row0 + n > n_prior_rows, ragged rows outside [0, n_lp_rows). */
+int pgmi_op_vocab_logsoftmax(int device, const float* h, const float* E, const float* bias, int rows, int D, int V, float* out,
+                             int32_t* nonfinite);
+int pgmi_op_wide_logsoftmax(int device, const float* logits, int ldl, int rows, int V, const int32_t* tgt, float* out, int32_t* nonfinite);
+int pgmi_op_group_logsoftmax(int device, const float* h, const float* E, const float* bias, int rows, int D, int V, int first, int groups,
+                             int width, float* full, float* group, int32_t* nonfinite);
+int pgmi_op_seq_loglik(int device, const float* lp, const int32_t* tokens, int B, int T, int V, const int32_t* lens, const int32_t* seq_off,
+                       const int32_t* seq_p, const int32_t* seq_root, int n_lp_rows, const float* prior, int n_prior_rows,
+                       const int32_t* a0, const int32_t* row0, const int32_t* n, const int32_t* flip, float alpha, const float* eve,
+                       float beta, int eve_fallback, float* out);
 
 /* ---- Tranception (arch PGMI_ARCH_TRANCEPTION; vocab 25, max_positions = n_ctx, precision f16x3) ------
  * Weight blob order (fp32, names as in the HF state dict, Conv1D weights as stored = [in,out]):

@@ -169,6 +169,12 @@ SIGNATURES = [
     ("pgmi_op_tied_row_attention", C.c_int, [C.c_int, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p]),
     ("pgmi_op_tied_row_splits", C.c_int, [C.c_int, C.c_int, C.c_int]),
     ("pgmi_op_column_attention", C.c_int, [C.c_int, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),
+    ("pgmi_op_vocab_logsoftmax", C.c_int, [C.c_int, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _i32p]),
+    ("pgmi_op_wide_logsoftmax", C.c_int, [C.c_int, _f32p, C.c_int, C.c_int, C.c_int, _i32p, _f32p, _i32p]),
+    ("pgmi_op_group_logsoftmax", C.c_int, [C.c_int, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p,
+                                           _f32p, _i32p]),
+    ("pgmi_op_seq_loglik", C.c_int, [C.c_int, _f32p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _i32p, C.c_int, _f32p, C.c_int,
+                                     _i32p, _i32p, _i32p, _i32p, C.c_float, _f32p, C.c_float, C.c_int, _f32p]),
     ("pgmi_msa_token_logprobs", C.c_int, [C.c_void_p, _i32p, C.c_int, C.c_int, _f32p]),
     ("pgmi_msa_masked_logprobs", C.c_int, [C.c_void_p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, _i32p, C.c_int, _f32p]),
     ("pgmi_msa_cluster_counts", C.c_int, [C.c_int, C.POINTER(C.c_int8), C.c_int64, C.c_int64, C.c_int, C.c_double, _i32p, _f64p]),

@@ -764,4 +764,173 @@ int pgmi_op_geom_attention(int device, const float* proj, const float* rot, cons
 
 int pgmi_op_geom_key_tile(int S) { return geom_key_tile(S); }
 
+// ---- the scoring tail (elementwise.hip): log-softmax heads and per-sequence sums on their own buffers ----------------------------------
+// Every output is allocated with kOutGuard spare values behind it and starts as 0xFF bytes (NaN): an element the kernel skips shows as
+// NaN on the host, and a guard value the kernel touched fails the call.  *nonfinite is the device flag after the launch (zero before).
+static constexpr size_t kOutGuard = 64;                          // one row of the narrow head at its widest
+static int out_alloc(std::vector<void*>& pool, float** p, size_t n) {
+    int rc = dev_alloc(pool, p, n + kOutGuard);
+    if (rc) return rc;
+    PGMI_HIP(hipMemset(*p, 0xFF, (n + kOutGuard) * sizeof(float)));
+    return PGMI_OK;
+}
+static int out_fetch(const float* d, size_t n, float* host, const char* what) {
+    uint32_t guard[kOutGuard];
+    PGMI_HIP(hipMemcpy(host, d, n * sizeof(float), hipMemcpyDeviceToHost));
+    PGMI_HIP(hipMemcpy(guard, d + n, sizeof(guard), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < kOutGuard; ++i)
+        if (guard[i] != 0xFFFFFFFFu) { set_error("%s op: the kernel wrote %zu values past the end of its output", what, i + 1); return PGMI_EHIP; }
+    return PGMI_OK;
+}
+static int flag_alloc(std::vector<void*>& pool, int32_t** p) {
+    int rc = dev_alloc(pool, p, (size_t)1);
+    if (rc) return rc;
+    PGMI_HIP(hipMemset(*p, 0, 4));
+    return PGMI_OK;
+}
+static int op_finish(hipError_t e, const char* what) {
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) { set_error("%s op failed: %s", what, hipGetErrorString(e)); return PGMI_EHIP; }
+    return PGMI_OK;
+}
+
+int pgmi_op_vocab_logsoftmax(int device, const float* h, const float* E, const float* bias, int rows, int D, int V, float* out,
+                             int32_t* nonfinite) {
+    if (!h || !E || !bias || !out || !nonfinite || rows <= 0 || D <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
+    if (V < 1 || V > 64) { set_error("narrow log-softmax op: V = %d is outside 1 .. 64 (lane v owns logit v)", V); return PGMI_EINVAL; }
+    if (pgmi_device_count() <= 0) { set_error("no HIP device visible"); return PGMI_ENODEV; }
+    PGMI_HIP(hipSetDevice(device));
+    std::vector<void*> pool;
+    auto cleanup = [&]() { for (void* p : pool) hipFree(p); };
+    float *dh = nullptr, *dE = nullptr, *db = nullptr, *dout = nullptr;
+    int32_t* dflag = nullptr;
+    const size_t n_out = (size_t)rows * V;
+    int rc = 0;
+    if ((rc = dev_upload(pool, &dh, h, (size_t)rows * D)) || (rc = dev_upload(pool, &dE, E, (size_t)V * D)) ||
+        (rc = dev_upload(pool, &db, bias, (size_t)V)) || (rc = out_alloc(pool, &dout, n_out)) || (rc = flag_alloc(pool, &dflag))) {
+        cleanup();
+        return rc;
+    }
+    launch_vocab_logsoftmax(dh, dE, db, rows, D, V, dout, dflag, nullptr);
+    rc = op_finish(hipDeviceSynchronize(), "narrow log-softmax");
+    if (!rc) rc = out_fetch(dout, n_out, out, "narrow log-softmax");
+    if (!rc) rc = op_finish(hipMemcpy(nonfinite, dflag, 4, hipMemcpyDeviceToHost), "narrow log-softmax");
+    cleanup();
+    return rc;
+}
+
+int pgmi_op_wide_logsoftmax(int device, const float* logits, int ldl, int rows, int V, const int32_t* tgt, float* out,
+                            int32_t* nonfinite) {
+    if (!logits || !out || !nonfinite || rows <= 0 || V <= 0 || ldl <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
+    if (ldl % 4 || ldl < V) { set_error("wide log-softmax op: ldl = %d must be a multiple of 4 and at least V = %d", ldl, V); return PGMI_EINVAL; }
+    for (int r = 0; tgt && r < rows; ++r)
+        if (tgt[r] < 0 || tgt[r] >= V) { set_error("wide log-softmax op: tgt[%d] = %d is outside [0, %d)", r, tgt[r], V); return PGMI_EINVAL; }
+    if (pgmi_device_count() <= 0) { set_error("no HIP device visible"); return PGMI_ENODEV; }
+    PGMI_HIP(hipSetDevice(device));
+    std::vector<void*> pool;
+    auto cleanup = [&]() { for (void* p : pool) hipFree(p); };
+    float *dl = nullptr, *dout = nullptr;
+    int32_t *dt = nullptr, *dflag = nullptr;
+    const size_t n_out = tgt ? (size_t)rows : (size_t)rows * V;
+    int rc = 0;
+    if ((rc = dev_upload(pool, &dl, logits, (size_t)rows * ldl)) || (tgt && (rc = dev_upload(pool, &dt, tgt, (size_t)rows))) ||
+        (rc = out_alloc(pool, &dout, n_out)) || (rc = flag_alloc(pool, &dflag))) {
+        cleanup();
+        return rc;
+    }
+    launch_wide_logsoftmax(dl, ldl, rows, V, dt, dout, dflag, nullptr);
+    rc = op_finish(hipDeviceSynchronize(), "wide log-softmax");
+    if (!rc) rc = out_fetch(dout, n_out, out, "wide log-softmax");
+    if (!rc) rc = op_finish(hipMemcpy(nonfinite, dflag, 4, hipMemcpyDeviceToHost), "wide log-softmax");
+    cleanup();
+    return rc;
+}
+
+int pgmi_op_group_logsoftmax(int device, const float* h, const float* E, const float* bias, int rows, int D, int V, int first, int groups,
+                             int width, float* full, float* group, int32_t* nonfinite) {
+    if (!h || !E || !bias || !nonfinite || rows <= 0 || D <= 0 || V <= 0 || first < 0 || groups <= 0 || width <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
+    if (!full && !group) { set_error("grouped log-softmax op: neither `full` nor `group` is asked for"); return PGMI_EINVAL; }
+    int rc = group_logsoftmax_check(D, V, first, groups, width);
+    if (rc) return rc;
+    if (pgmi_device_count() <= 0) { set_error("no HIP device visible"); return PGMI_ENODEV; }
+    PGMI_HIP(hipSetDevice(device));
+    std::vector<void*> pool;
+    auto cleanup = [&]() { for (void* p : pool) hipFree(p); };
+    float *dh = nullptr, *dE = nullptr, *db = nullptr, *dfull = nullptr, *dgroup = nullptr;
+    int32_t* dflag = nullptr;
+    const size_t n_full = (size_t)rows * V, n_group = (size_t)rows * groups;
+    if ((rc = dev_upload(pool, &dh, h, (size_t)rows * D)) || (rc = dev_upload(pool, &dE, E, (size_t)V * D)) ||
+        (rc = dev_upload(pool, &db, bias, (size_t)V)) || (full && (rc = out_alloc(pool, &dfull, n_full))) ||
+        (group && (rc = out_alloc(pool, &dgroup, n_group))) || (rc = flag_alloc(pool, &dflag))) {
+        cleanup();
+        return rc;
+    }
+    rc = launch_group_logsoftmax(dh, dE, db, rows, D, V, first, groups, width, dfull, dgroup, dflag, nullptr);
+    if (!rc) rc = op_finish(hipDeviceSynchronize(), "grouped log-softmax");
+    if (!rc && full) rc = out_fetch(dfull, n_full, full, "grouped log-softmax");
+    if (!rc && group) rc = out_fetch(dgroup, n_group, group, "grouped log-softmax");
+    if (!rc) rc = op_finish(hipMemcpy(nonfinite, dflag, 4, hipMemcpyDeviceToHost), "grouped log-softmax");
+    cleanup();
+    return rc;
+}
+
+// The range checks of every index the two kernels form are made here, on the host, so that no input can make a kernel read outside the
+// buffers this entry allocates.  Dense form: sequence b owns the rows b T .. b T + T - 1.  Ragged form: sequence b owns the T - seq_p[b]
+// packed rows from seq_off[b] on and reads the first seq_p[b] rows of its root, a sequence that owns all its T rows.
+int pgmi_op_seq_loglik(int device, const float* lp, const int32_t* tokens, int B, int T, int V, const int32_t* lens, const int32_t* seq_off,
+                       const int32_t* seq_p, const int32_t* seq_root, int n_lp_rows, const float* prior, int n_prior_rows,
+                       const int32_t* a0, const int32_t* row0, const int32_t* n, const int32_t* flip, float alpha, const float* eve,
+                       float beta, int eve_fallback, float* out) {
+    if (!lp || !tokens || !out || B <= 0 || T <= 0 || V <= 0 || n_lp_rows <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
+    if (!lens && (!seq_off || !seq_p || !seq_root)) { set_error("sequence sum op: neither `lens` (dense) nor seq_off / seq_p / seq_root (ragged)"); return PGMI_EINVAL; }
+    if (eve && !prior) { set_error("sequence sum op: an EVE table without a retrieval prior"); return PGMI_EINVAL; }
+    if (prior && (!a0 || !row0 || !n || !flip || n_prior_rows <= 0)) { set_error("bad argument"); return PGMI_EINVAL; }
+    for (int i = 0; i < n_lp_rows; ++i)
+        if (tokens[i] < 0 || tokens[i] >= V) { set_error("sequence sum op: token %d = %d is outside [0, %d)", i, tokens[i], V); return PGMI_EINVAL; }
+    if (lens) {
+        if ((int64_t)B * T != n_lp_rows) { set_error("sequence sum op: dense form with %d rows for B = %d, T = %d", n_lp_rows, B, T); return PGMI_EINVAL; }
+        for (int b = 0; b < B; ++b)
+            if (lens[b] < 0 || lens[b] > T) { set_error("sequence sum op: lens[%d] = %d is outside [0, %d]", b, lens[b], T); return PGMI_EINVAL; }
+    } else {
+        for (int b = 0; b < B; ++b) {
+            const int64_t p = seq_p[b], off = seq_off[b], root = seq_root[b];
+            const bool ok = p >= 0 && p <= T && off >= 0 && off + (T - p) <= n_lp_rows && root >= 0 && root < B && seq_p[root] == 0 &&
+                            seq_off[root] >= 0 && (int64_t)seq_off[root] + T <= n_lp_rows;
+            if (!ok) { set_error("sequence sum op: ragged sequence %d (offset %d, first own token %d, root %d) leaves the %d packed rows", b, seq_off[b], seq_p[b], seq_root[b], n_lp_rows); return PGMI_EINVAL; }
+        }
+    }
+    for (int b = 0; prior && b < B; ++b) {
+        if (n[b] < 0) { set_error("sequence sum op: prior window %d has n = %d", b, n[b]); return PGMI_EINVAL; }
+        if (n[b] == 0) continue;
+        if (a0[b] < 0 || row0[b] < 0 || (int64_t)a0[b] + n[b] > T - 1 || (int64_t)row0[b] + n[b] > n_prior_rows) {
+            set_error("sequence sum op: prior window %d (a0 %d, row0 %d, n %d) leaves the %d targets or the %d prior rows", b, a0[b], row0[b], n[b], T - 1, n_prior_rows);
+            return PGMI_EINVAL;
+        }
+    }
+    if (pgmi_device_count() <= 0) { set_error("no HIP device visible"); return PGMI_ENODEV; }
+    PGMI_HIP(hipSetDevice(device));
+    std::vector<void*> pool;
+    auto cleanup = [&]() { for (void* p : pool) hipFree(p); };
+    float *dlp = nullptr, *dprior = nullptr, *deve = nullptr, *dout = nullptr;
+    int32_t *dtok = nullptr, *dlens = nullptr, *doff = nullptr, *dp = nullptr, *droot = nullptr, *da0 = nullptr, *drow0 = nullptr, *dn = nullptr, *dflip = nullptr;
+    const size_t nB = (size_t)B;
+    int rc = 0;
+    if ((rc = dev_upload(pool, &dlp, lp, (size_t)n_lp_rows * V)) || (rc = dev_upload(pool, &dtok, tokens, (size_t)n_lp_rows)) ||
+        (lens && (rc = dev_upload(pool, &dlens, lens, nB))) ||
+        (!lens && ((rc = dev_upload(pool, &doff, seq_off, nB)) || (rc = dev_upload(pool, &dp, seq_p, nB)) || (rc = dev_upload(pool, &droot, seq_root, nB)))) ||
+        (prior && ((rc = dev_upload(pool, &dprior, prior, (size_t)n_prior_rows * V)) || (rc = dev_upload(pool, &da0, a0, nB)) ||
+                   (rc = dev_upload(pool, &drow0, row0, nB)) || (rc = dev_upload(pool, &dn, n, nB)) || (rc = dev_upload(pool, &dflip, flip, nB)))) ||
+        (eve && (rc = dev_upload(pool, &deve, eve, (size_t)n_prior_rows * V))) || (rc = out_alloc(pool, &dout, nB))) {
+        cleanup();
+        return rc;
+    }
+    if (lens) launch_seq_loglik(dlp, dtok, dlens, B, T, V, dprior, da0, drow0, dn, dflip, alpha, deve, beta, eve_fallback, dout, nullptr);
+    else launch_seq_loglik_ragged(dlp, dtok, doff, dp, droot, B, T, V, dprior, da0, drow0, dn, dflip, alpha, deve, beta, eve_fallback, dout, nullptr);
+    rc = op_finish(hipDeviceSynchronize(), "sequence sum");
+    if (!rc) rc = out_fetch(dout, nB, out, "sequence sum");
+    cleanup();
+    return rc;
+}
+
+
 }  // extern "C"

@@ -151,6 +151,8 @@ void launch_saprot_rows(const int32_t* wt, const int32_t* set_off, const int32_t
 // lse(logits[first + g width .. + width)) - lse(row) (nullable)
 int launch_group_logsoftmax(const float* h, const float* E, const float* bias, int rows, int D, int V, int first, int groups, int width,
                             float* full, float* group, int32_t* nonfinite, hipStream_t s);
+// what launch_group_logsoftmax refuses (PGMI_EINVAL and its message), for a caller that must know before it allocates
+int group_logsoftmax_check(int D, int V, int first, int groups, int width);
 
 // ---- moe.hip (ProGen3's routed expert block; the kernels are described there) -------------------------------------------------
 // The router of launch_rmsnorm_route: gate fp32 [E][D] (nullptr: no routing), 2 <= E <= 64, 1 <= top_k <= E; tokens / pad_id (nullable):

@@ -661,6 +661,8 @@ void launch_embed_scaled_pos(const int32_t* tokens, const int32_t* pos, const fl
 // float4s i, i + 256, ... and keeps a running max m and s = sum exp(x - m) in double (rescaled when m grows); the 256 (m, s) pairs
 // are then combined in a fixed tree order in double.  Every order depends on V alone, so a row's bits do not depend on the other
 // rows of the launch.  tgt != nullptr: out[r] = log p(column tgt[r]) (scoring); else out[r * V + c] for every c < V.
+// -inf logits follow torch.log_softmax: their columns are -inf, the others what they would be without them; a row of nothing but -inf
+// is NaN.  A pair whose m is still -inf has s == 0 (or NaN, from a NaN logit), so lse_merge never forms exp(-inf - -inf).
 __device__ __forceinline__ void lse_merge(float& m, double& s, float m2, double s2) {
     const float M = fmaxf(m, m2);
     const double a = s == 0.0 ? 0.0 : s * exp((double)m - (double)M);
@@ -689,10 +691,12 @@ __global__ __launch_bounds__(256) void wide_logsoftmax_kernel(const float* __res
             s = s == 0.0 ? 0.0 : s * (double)__expf(m - mx);
             m = mx;
         }
+        // a -inf logit has probability 0 and adds nothing -- also while m is still -inf, where exp(-inf - m) would be NaN.  (A NaN or
+        // +inf logit still makes its term, and so the row, NaN.)  For a finite logit the term is the same instruction on the same operands.
         float e = 0.0f;
 #pragma unroll
         for (int k = 0; k < 4; ++k)
-            if (c0 + k < V) e += __expf(v[k] - m);
+            if (c0 + k < V) e += v[k] == -INFINITY ? 0.0f : __expf(v[k] - m);
         s += (double)e;
     }
     sm[tid] = m;
@@ -865,14 +869,19 @@ __global__ __launch_bounds__(256) void group_logsoftmax_kernel(const float* __re
     }
     if (nonfinite && bad) atomicOr(nonfinite, 1);             // NaN/inf: fp16 overflow upstream
 }
-int launch_group_logsoftmax(const float* h, const float* E, const float* bias, int rows, int D, int V, int first, int groups, int width,
-                            float* full, float* group, int32_t* nonfinite, hipStream_t s) {
-    if (rows <= 0) return PGMI_OK;
+int group_logsoftmax_check(int D, int V, int first, int groups, int width) {
     const int nv = (D / 4 + 63) / 64;
     if (D % 4 || nv > 10 || V > 64 * kGroupSlots || groups > 64 || width > 64 || first + groups * width > V) {
         set_error("grouped log-softmax: unsupported shape (D %d, V %d, %d groups of %d from column %d)", D, V, groups, width, first);
         return PGMI_EINVAL;
     }
+    return PGMI_OK;
+}
+int launch_group_logsoftmax(const float* h, const float* E, const float* bias, int rows, int D, int V, int first, int groups, int width,
+                            float* full, float* group, int32_t* nonfinite, hipStream_t s) {
+    if (rows <= 0) return PGMI_OK;
+    const int nv = (D / 4 + 63) / 64;
+    if (int rc = group_logsoftmax_check(D, V, first, groups, width)) return rc;
     const dim3 grid((rows + 3) / 4), block(256);
 #define PGMI_GLS(N) hipLaunchKernelGGL((group_logsoftmax_kernel<N>), grid, block, 0, s, h, E, bias, rows, D, V, first, groups, width, full, group, nonfinite)
     if (nv <= 1) PGMI_GLS(1); else if (nv <= 2) PGMI_GLS(2); else if (nv <= 5) PGMI_GLS(5); else PGMI_GLS(10);

@@ -714,3 +714,68 @@ def test_tied_row_attention_split_rule_and_refusals_need_no_device(lib):
                       ((2, 1025, 1, 0), "at most 1024 columns"), ((1024, 1024, 20, 0), "32-bit offset range")):
         assert lib.pgmi_op_tied_row_attention(0, p, *args, p, None) == _lib.EINVAL, args
         assert msg in lib.pgmi_last_error().decode(), (args, lib.pgmi_last_error())
+
+
+def test_scoring_op_entries_refuse_bad_arguments_before_they_look_for_a_device(lib):
+    """The four entries of the scoring tail own the range checks of every index their kernels form: each refusal is PGMI_EINVAL with a
+    message, made on the host (with no device in sight the same calls would otherwise end in PGMI_ENODEV)."""
+    f = np.zeros(4096, np.float32)
+    fp, i32 = f.ctypes.data_as(_lib._f32p), lambda *v: np.array(v, np.int32)
+    ip = lambda a: a.ctypes.data_as(_lib._i32p)                      # noqa: E731
+    flag = i32(0)
+
+    def refused(rc, msg):
+        assert rc == _lib.EINVAL, (rc, msg, lib.pgmi_last_error())
+        assert msg in lib.pgmi_last_error().decode(), (msg, lib.pgmi_last_error())
+
+    # narrow: lane v owns logit v
+    for V in (0, -1, 65, 446):
+        refused(lib.pgmi_op_vocab_logsoftmax(0, fp, fp, fp, 2, 8, V, fp, ip(flag)), "outside 1 .. 64")
+    refused(lib.pgmi_op_vocab_logsoftmax(0, None, fp, fp, 2, 8, 33, fp, ip(flag)), "bad argument")
+    refused(lib.pgmi_op_vocab_logsoftmax(0, fp, fp, fp, 0, 8, 33, fp, ip(flag)), "bad argument")
+    refused(lib.pgmi_op_vocab_logsoftmax(0, fp, fp, fp, 2, 0, 33, fp, ip(flag)), "bad argument")
+    refused(lib.pgmi_op_vocab_logsoftmax(0, fp, fp, fp, 2, 8, 33, fp, None), "bad argument")
+    # wide: the row pitch and the targets
+    refused(lib.pgmi_op_wide_logsoftmax(0, fp, 70, 2, 66, None, fp, ip(flag)), "multiple of 4")
+    refused(lib.pgmi_op_wide_logsoftmax(0, fp, 64, 2, 66, None, fp, ip(flag)), "at least V")
+    refused(lib.pgmi_op_wide_logsoftmax(0, fp, 68, 2, 66, ip(i32(0, 66)), fp, ip(flag)), "tgt[1] = 66")
+    refused(lib.pgmi_op_wide_logsoftmax(0, fp, 68, 2, 66, ip(i32(-1, 5)), fp, ip(flag)), "tgt[0] = -1")
+    refused(lib.pgmi_op_wide_logsoftmax(0, fp, 68, 0, 66, None, fp, ip(flag)), "bad argument")
+    refused(lib.pgmi_op_wide_logsoftmax(0, fp, 68, 2, 66, None, None, ip(flag)), "bad argument")
+    # grouped: an output, and what the launcher refuses in the launcher's words
+    refused(lib.pgmi_op_group_logsoftmax(0, fp, fp, fp, 1, 8, 446, 5, 21, 21, None, None, ip(flag)), "neither")
+    for D, V, first, groups, width in ((6, 446, 5, 21, 21), (2564, 446, 5, 21, 21), (8, 513, 5, 21, 21), (8, 446, 5, 65, 1), (8, 446, 5, 1, 65),
+                                       (8, 446, 6, 21, 21)):
+        refused(lib.pgmi_op_group_logsoftmax(0, fp, fp, fp, 1, D, V, first, groups, width, fp, fp, ip(flag)), "grouped log-softmax: unsupported shape")
+    refused(lib.pgmi_op_group_logsoftmax(0, fp, fp, fp, 1, 8, 446, -1, 21, 21, fp, fp, ip(flag)), "bad argument")
+    # sequence sums: B = 2, T = 4, V = 5
+    tok, lens = i32(0, 1, 2, 3, 4, 3, 2, 1), i32(4, 2)
+    z, one = i32(0, 0), i32(1, 1)
+
+    def seq(tokens=tok, lens=lens, off=None, p=None, root=None, rows=8, prior=None, n_prior=0, a0=None, row0=None, n=None, flip=None, eve=None):
+        g = lambda a: None if a is None else ip(a)                   # noqa: E731
+        return lib.pgmi_op_seq_loglik(0, fp, ip(tokens), 2, 4, 5, g(lens), g(off), g(p), g(root), rows, prior, n_prior, g(a0), g(row0), g(n),
+                                      g(flip), 0.5, eve, 0.5, 0, fp)
+
+    refused(seq(tokens=i32(0, 1, 2, 3, 5, 3, 2, 1)), "token 4 = 5")
+    refused(seq(tokens=i32(0, 1, 2, 3, 4, 3, 2, -1)), "token 7 = -1")
+    refused(seq(lens=i32(4, 5)), "lens[1] = 5")
+    refused(seq(lens=i32(-1, 4)), "lens[0] = -1")
+    refused(seq(rows=7), "dense form")
+    refused(seq(lens=None), "neither")
+    refused(seq(eve=fp), "EVE table without")
+    refused(seq(prior=fp, n_prior=3, a0=z, row0=z, n=i32(3, 4), flip=z), "prior window 1")      # a0 + n > T - 1
+    refused(seq(prior=fp, n_prior=3, a0=one, row0=z, n=i32(2, 3), flip=z), "prior window 1")    # a0 + n > T - 1 through a0
+    refused(seq(prior=fp, n_prior=3, a0=z, row0=i32(0, 1), n=i32(3, 3), flip=z), "prior window 1")   # row0 + n > n_prior_rows
+    refused(seq(prior=fp, n_prior=3, a0=z, row0=z, n=i32(3, -1), flip=z), "n = -1")
+    refused(seq(prior=fp, n_prior=3, a0=z, row0=z, n=one, flip=None), "bad argument")
+    # ragged: sequence 0 the root with its 4 rows, sequence 1 owning tokens 2..3 -> 6 packed rows
+    rtok = i32(0, 1, 2, 3, 4, 3)
+    refused(seq(tokens=rtok, lens=None, off=i32(0, 5), p=i32(0, 2), root=z, rows=6), "ragged sequence 1")      # own rows end at 7
+    refused(seq(tokens=rtok, lens=None, off=i32(0, -1), p=i32(0, 2), root=z, rows=6), "ragged sequence 1")
+    refused(seq(tokens=rtok, lens=None, off=i32(0, 4), p=i32(0, 5), root=z, rows=6), "ragged sequence 1")      # seq_p > T
+    refused(seq(tokens=rtok, lens=None, off=i32(0, 4), p=i32(0, 2), root=i32(0, 2), rows=6), "ragged sequence 1")   # no such root
+    refused(seq(tokens=rtok, lens=None, off=i32(0, 4), p=i32(1, 2), root=z, rows=6), "ragged sequence 0")      # a root that owns no row 0
+    refused(seq(tokens=rtok, lens=None, off=i32(3, 0), p=i32(0, 2), root=z, rows=6), "ragged sequence 0")      # the root's rows end at 7
+    # what passes every check ends at the device (or, with one, succeeds)
+    assert seq() in (0, _lib.ENODEV) and seq(tokens=rtok, lens=None, off=i32(0, 4), p=i32(0, 2), root=z, rows=6) in (0, _lib.ENODEV)
