@@ -323,6 +323,14 @@ int pgmi_op_prefix_attention(int device, const float* qkv, const int32_t* seg_of
  * consumes, rebuilt as fp32; 0: the kernel's fp32 rows.  S <= 0, an empty segment or a NULL pointer is PGMI_EINVAL. */
 int pgmi_op_cross_attention(int device, const float* q, const int32_t* seg_off, int n_seg, const float* mem_kv, int S, int heads,
                             int split, float* ctx);
+/* A test-only entry beside them, host only: how the PoET / ESM-IF1 entries cut a call of B sequences of lens[b] tokens into packed
+ * chunks for a workspace of max_rows rows, so that a test reads the rule the entries run.  drop_last != 0: the model reads
+ * lens[b] - 1 tokens (a log-likelihood); same_length != 0: a chunk is a run of sequences of one length (ESM-IF1).  A chunk takes
+ * sequences while its packed rows stay within max_rows and its key rows, every sequence padded to a multiple of 32, within
+ * max_rows rounded down to a multiple of 32.  out_b1 [B]: the end b1 of each successive chunk [b0, b1); *out_n: their number.
+ * PGMI_EINVAL with the entries' own message at the first sequence that fits no chunk alone; a length below 1 (2 with drop_last), a
+ * NULL pointer or a non-positive size is PGMI_EINVAL too. */
+int pgmi_op_packed_chunks(const int32_t* lens, int B, int drop_last, int same_length, int max_rows, int32_t* out_b1, int32_t* out_n);
 /* ProGen3's pieces (elementwise.hip rmsnorm16_kernel, moe.hip, api_progen3.hip moe_ffn) on their own buffers.
  * pgmi_op_rmsnorm: y [rows][D] = the split operand launch_rmsnorm16 writes, rebuilt as fp32 (hi + lo 2^-11); D % 32 == 0, D <= 5120.
  * pgmi_op_moe: the routed block on fp32 rows h [M][D] taken as they are (no norm): gate [E][D] (ignored when E == 1); w1 [E][F][D],

@@ -161,6 +161,7 @@ SIGNATURES = [
                                            C.c_int, C.c_int, C.c_int, _f32p]),
     ("pgmi_op_prefix_attention", C.c_int, [C.c_int, _f32p, _i32p, C.c_int, _f32p, C.c_int, C.c_int, C.c_int, _f32p]),
     ("pgmi_op_cross_attention", C.c_int, [C.c_int, _f32p, _i32p, C.c_int, _f32p, C.c_int, C.c_int, C.c_int, _f32p]),
+    ("pgmi_op_packed_chunks", C.c_int, [_i32p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p]),
     ("pgmi_op_rmsnorm", C.c_int, [C.c_int, _f32p, _f32p, C.c_int, C.c_int, C.c_float, _f32p]),
     ("pgmi_op_geom_attention", C.c_int, [C.c_int, _f32p, _f32p, _f32p, _i32p, C.c_int, _f32p, _f32p, C.c_int, C.c_int, C.c_int, _f32p]),
     ("pgmi_op_geom_key_tile", C.c_int, [C.c_int]),

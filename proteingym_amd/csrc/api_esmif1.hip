@@ -45,7 +45,8 @@ int64_t if1_weight_count(const pgmi_config* c, int enc_dim) {
 int create_esmif1(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights, int enc_dim) {
     const size_t D = cfg->embed_dim, F = cfg->ffn_dim, V = cfg->vocab, Da = m->Da, E = enc_dim;
     m->if1_enc = enc_dim;
-    m->poet_final_norm = true;
+    m->final_norm = true;
+    m->slopes = m->zeros;                                       // the causal self-attention's ALiBi term is exactly 0
     m->fc1_epi = EPI_RELU;
     BlobCursor c(m, w, n_weights);
     c.upload(&m->embed_tokens, V * D);
@@ -111,86 +112,42 @@ int create_esmif1(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t
         rc = dev_upload(m->allocs, &m->if1_pos, tab.data(), tab.size());
         if (rc) return rc;
     }
-    m->poet_pitch = ((size_t)cfg->max_positions + 31) / 32 * 32;
-    const size_t n = (size_t)cfg->layers * 2 * 2 * Da * m->poet_pitch;
-    rc = dev_alloc(m->allocs, &m->poet_cache, n);
-    if (!rc) PGMI_HIP(hipMemset(m->poet_cache, 0, n * sizeof(unsigned short)));
+    rc = alloc_prefix_cache(m);
     if (!rc) rc = dev_alloc(m->allocs, &m->if1_mem, (size_t)cfg->max_positions * E);
     if (!rc) rc = dev_alloc(m->allocs, &m->if1_mem16, (size_t)cfg->max_positions * E * 2);
-    if (!rc) rc = dev_alloc(m->allocs, &m->poet_meta, (size_t)7 * m->max_rows + 8);
-    if (!rc) rc = dev_alloc(m->allocs, &m->gpt_sum, (size_t)m->max_rows);
     return rc;
 }
 
 // The decoder over B sequences of T rows each, packed (tokens in m->tokens, positions in m->pos_idx, the segments again in pl for the
 // cross-attention's query tiles); leaves the residual stream in m->x.
-static int if1_forward(pgmi_model* m, int B, int T, const PoetPlan& pl) {
+static int if1_forward(pgmi_model* m, int B, int T, const SegPlan& pl) {
     const pgmi_config& c = m->cfg;
-    const int M = B * T, D = c.embed_dim, F = c.ffn_dim, H = c.heads, Da = m->Da, S = m->poet_P;
+    const int M = B * T, D = c.embed_dim, Da = m->Da, S = m->pfx.rows;
     hipStream_t s = m->stream;
     int rc = reset_pad_keys(m, B, T);
     if (rc) return rc;
     { ProfScope p(m, PGMI_K_EMBED, 0, 2.0 * M * D * 4);
       launch_embed_scaled_pos(m->tokens, m->pos_idx, m->embed_tokens, m->if1_pos, sqrtf((float)D), M, D, m->x, s); }
-    const double ln_bytes = 2.0 * M * D * 4;
-    const size_t cap = (size_t)m->max_rows, cache_plane = (size_t)Da * m->poet_pitch;
-    PrefixAttLaunch a;
-    a.seg_off = pl.d_seg_off; a.ent_seg = pl.d_ent_seg; a.ent_tile = pl.d_ent_tile;
-    a.n_seg = pl.n_seg(); a.n_ent = pl.n_ent(); a.H = H;
-    a.q16 = m->qk16; a.q_plane = cap * Da;
-    a.out = ATT_OUT_SPLIT; a.ctx16 = m->h16; a.stream = s;
+    PrefixAttLaunch ca = prefix_launch(m, pl);                   // cross-attention over a layer's memory planes
+    ca.ppitch = m->pfx.pitch; ca.P = S;
     for (int l = 0; l < c.layers; ++l) {
         const Layer& L = m->layers[l];
-        { ProfScope p(m, PGMI_K_LAYERNORM, 0, ln_bytes);
-          launch_layernorm16(m->x, L.ln1_w, L.ln1_b, M, D, m->ln_eps, m->h16, 1, s); }
-        { ProfScope p(m, PGMI_K_GEMM_QKV, 2.0 * M * 3 * Da * D, 0);        // fused QKV: the epilogue writes the attention's operand planes
-          rc = launch_gemm16(qkv_launch(m, L.wqkv16, L.bqkv, M, Da, D, T, H));
-          if (rc) return rc; }
-        { ProfScope p(m, PGMI_K_ATTENTION, 2.0 * M * T * Da, 0);            // causal self-attention (api_gpt.hip's launch, zero ALiBi slopes)
-          AttLaunch sa;
-          sa.qk16 = m->qk16, sa.qk_plane = m->qk16_plane, sa.vt16 = m->vt16, sa.vt_plane = m->vt16_plane;
-          sa.B = B, sa.T = T, sa.H = H;
-          sa.slopes = m->zeros;
-          sa.out = ATT_OUT_SPLIT, sa.ctx16 = m->h16;
-          sa.stream = s;
-          rc = launch_attention_f16x3_v2(sa);
-          if (rc) return rc; }
-        { ProfScope p(m, PGMI_K_GEMM_OUT, 2.0 * M * D * Da, 0);
-          rc = linear(m, nullptr, m->h16, nullptr, L.wo16, L.bo, m->x, m->x, nullptr, M, D, Da, EPI_NONE);
-          if (rc) return rc; }
-        { ProfScope p(m, PGMI_K_LAYERNORM, 0, ln_bytes);
+        rc = self_attention(m, L, B, T);                         // the causal decoder's, with zero ALiBi slopes and no rotary
+        if (rc) return rc;
+        { ProfScope p(m, PGMI_K_LAYERNORM, 0, 2.0 * M * D * 4);
           launch_layernorm16(m->x, L.c_ln_w, L.c_ln_b, M, D, m->ln_eps, m->h16, 1, s); }
         { ProfScope p(m, PGMI_K_GEMM_QKV, 2.0 * M * Da * D, 0);
           rc = linear(m, nullptr, m->h16, nullptr, L.c_wq16, L.c_bq, nullptr, m->qkv, nullptr, M, Da, D, EPI_NONE);
           if (rc) return rc; }
-        { PrefixAttLaunch ca = a;                                // cross-attention over the layer's memory planes
-          ca.pk16 = m->poet_cache + (size_t)l * 4 * cache_plane; ca.pvt16 = ca.pk16 + 2 * cache_plane; ca.ppitch = m->poet_pitch; ca.P = S;
+        { ca.pk16 = m->pfx.k(l); ca.pvt16 = m->pfx.vt(l);
           ProfScope p(m, PGMI_K_CROSS_ATTENTION, 4.0 * (double)M * S * Da, 0);
-          rc = launch_cross_q_prep(m->qkv, (size_t)M, H, m->qk16, cap * Da, s);
+          rc = launch_cross_q_prep(m->qkv, (size_t)M, ca.H, ca.q16, ca.q_plane, s);
           if (!rc) rc = launch_cross_attention(ca);
           if (rc) return rc; }
-        { ProfScope p(m, PGMI_K_GEMM_OUT, 2.0 * M * D * Da, 0);
-          rc = linear(m, nullptr, m->h16, nullptr, L.c_wo16, L.c_bo, m->x, m->x, nullptr, M, D, Da, EPI_NONE);
-          if (rc) return rc; }
-        { ProfScope p(m, PGMI_K_LAYERNORM, 0, ln_bytes);
-          launch_layernorm16(m->x, L.ln2_w, L.ln2_b, M, D, m->ln_eps, m->h16, 1, s); }
-        { ProfScope p(m, PGMI_K_GEMM_FC1, 2.0 * M * F * D, 0);
-          rc = linear(m, nullptr, m->h16, nullptr, L.w116, L.b1, nullptr, nullptr, m->g16, M, F, D, EPI_RELU);
-          if (rc) return rc; }
-        { ProfScope p(m, PGMI_K_GEMM_FC2, 2.0 * M * F * D, 0);
-          rc = linear(m, nullptr, m->g16, nullptr, L.w216, L.b2, m->x, m->x, nullptr, M, D, F, EPI_NONE);
-          if (rc) return rc; }
+        rc = out_proj(m, L.c_wo16, L.c_bo, M);
+        if (!rc) rc = ffn(m, L, M);
+        if (rc) return rc;
     }
-    PGMI_HIP(hipGetLastError());
-    return PGMI_OK;
-}
-
-// decoder.layer_norm and the log-softmax head on n rows of src -> m->lp [n, V]
-static int if1_head(pgmi_model* m, const float* src, int n) {
-    const int D = m->cfg.embed_dim, V = m->cfg.vocab;
-    ProfScope p(m, PGMI_K_HEAD, 2.0 * n * D * V, 0);
-    launch_layernorm(src, m->lna_w, m->lna_b, n, D, m->ln_eps, m->h, m->stream);
-    launch_vocab_logsoftmax(m->h, m->head_w, m->head_b, n, D, V, m->lp, m->nonfinite, m->stream);
     PGMI_HIP(hipGetLastError());
     return PGMI_OK;
 }
@@ -201,75 +158,19 @@ static int if1_model_check(pgmi_model* m) {
     return PGMI_OK;
 }
 
-// Sequences [B][T] right-padded (the pad value is not read), lens[b] tokens each, the prepended <cath> counted.  loglik: the model reads
-// tokens[b, :lens[b] - 1] and mean[b] = mean of log p(tokens[b, t + 1]) over all lens[b] - 1 targets; else the model reads all lens[b]
-// tokens and every row's log-probabilities go to out [B][T][V] (rows beyond lens[b]: NaN).
+// Sequences right-padded (the pad value is not read), the prepended <cath> counted in lens[b]; the log-likelihood is the mean over all
+// lens[b] - 1 targets.  A chunk is a run of sequences of ONE length (the dense causal attention takes B x T): a sequence goes through
+// the same kernels at the same T whatever surrounds it.
 static int if1_sequences(pgmi_model* m, const int32_t* tokens, const int32_t* lens, int B, int T, bool loglik, float* out, double* mean) {
     int rc = if1_model_check(m);
     if (rc) return rc;
-    if (!tokens || !lens || B <= 0 || T <= 0 || (loglik ? !mean : !out)) { set_error("bad argument"); return PGMI_EINVAL; }
-    if (m->poet_P <= 0) { set_error("no encoder memory is set (pgmi_esmif1_set_memory)"); return PGMI_EINVAL; }
-    const int V = m->cfg.vocab, lo = loglik ? 2 : 1;
-    for (int b = 0; b < B; ++b) {
-        if (lens[b] < lo || lens[b] > T) { set_error("row %d of this call: length %d outside [%d, T = %d]", b, lens[b], lo, T); return PGMI_EINVAL; }
-        if (lens[b] > m->if1_pos_len) { set_error("row %d of this call: %d tokens exceed the %d positions / workspace rows", b, lens[b], m->if1_pos_len); return PGMI_EINVAL; }
-        rc = check_vocab(tokens + (size_t)b * T, 1, lens[b], V);
-        if (rc) return rc;
-    }
-    PGMI_HIP(hipSetDevice(m->device));
-    hipStream_t s = m->stream;
-    const size_t pitch = own_pitch(m);
-    if (!loglik) std::fill(out, out + (size_t)B * T * V, NAN);
-    std::vector<int32_t> tok, pos, tgt, off;
-    for (int b0 = 0; b0 < B;) {
-        // the chunk: a run of sequences of ONE length (the dense causal attention takes B x T), as many as the packed rows and the
-        // padded key rows of the workspace take.  A sequence goes through the same kernels at the same T whatever surrounds it.
-        PoetPlan pl;
-        tok.clear(); pos.clear(); tgt.clear(); off.assign(1, 0);
-        int b1 = b0;
-        size_t rows = 0, padded = 0;
-        for (; b1 < B; ++b1) {
-            const int n = lens[b1] - (loglik ? 1 : 0);
-            if (b1 > b0 && lens[b1] != lens[b0]) break;
-            if (rows + n > (size_t)m->max_rows || padded + (size_t)(n + 31) / 32 * 32 > pitch) break;
-            const int32_t* row = tokens + (size_t)b1 * T;
-            for (int t = 0; t < n; ++t) {
-                tok.push_back(row[t]);
-                pos.push_back(t);
-                if (loglik) tgt.push_back(row[t + 1]);
-            }
-            pl.add(n);
-            rows += n; padded += (size_t)(n + 31) / 32 * 32;
-            off.push_back((int32_t)rows);
-        }
-        if (b1 == b0) { set_error("row %d of this call: %d tokens exceed the workspace of %d rows", b0, lens[b0], m->max_rows); return PGMI_EINVAL; }
-        const int R = (int)rows, bc = b1 - b0;
-        PGMI_HIP(hipMemcpyAsync(m->tokens, tok.data(), (size_t)R * 4, hipMemcpyHostToDevice, s));
-        PGMI_HIP(hipMemcpyAsync(m->pos_idx, pos.data(), (size_t)R * 4, hipMemcpyHostToDevice, s));
-        rc = upload_plan(m, pl, 0);
-        if (!rc) rc = if1_forward(m, bc, R / bc, pl);
-        if (!rc) rc = if1_head(m, m->x, R);
-        if (rc) return rc;
-        if (loglik) {
-            int32_t* d_off = m->poet_meta + (size_t)2 * (3 * (size_t)m->max_rows + 2);
-            PGMI_HIP(hipMemcpyAsync(d_off, off.data(), off.size() * 4, hipMemcpyHostToDevice, s));
-            PGMI_HIP(hipMemcpyAsync(m->aux_i, tgt.data(), (size_t)R * 4, hipMemcpyHostToDevice, s));
-            { ProfScope p(m, PGMI_K_SCORE, 0, (double)R * 8);
-              launch_pppl_pick(m->lp, m->aux_i, R, V, m->denom, s);
-              launch_seq_sum(m->denom, d_off, bc, m->gpt_sum, s); }
-            PGMI_HIP(hipGetLastError());
-            PGMI_HIP(hipMemcpyAsync(mean + b0, m->gpt_sum, (size_t)bc * sizeof(double), hipMemcpyDeviceToHost, s));
-        } else {
-            for (int b = 0; b < bc; ++b)
-                PGMI_HIP(hipMemcpyAsync(out + (size_t)(b0 + b) * T * V, m->lp + (size_t)pl.seg_off[b] * V,
-                                        (size_t)lens[b0 + b] * V * 4, hipMemcpyDeviceToHost, s));
-        }
-        PGMI_HIP(hipStreamSynchronize(s));                      // the chunk's host buffers outlive their copies
-        if (loglik)
-            for (int b = b0; b < b1; ++b) mean[b] /= (double)(lens[b] - 1);
-        b0 = b1;
-    }
-    return check_nonfinite(m);
+    PackedScorer e = {};
+    e.forward = [](pgmi_model* m, int bc, int R, const SegPlan& pl) { return if1_forward(m, bc, R / bc, pl); };
+    e.pos_len = m->if1_pos_len; e.pos_what = "positions";
+    e.not_ready = m->pfx.rows > 0 ? nullptr : "no encoder memory is set (pgmi_esmif1_set_memory)";
+    e.same_length = e.vocab_per_row = e.mean = true;
+    e.skip_target = -1;
+    return score_packed(m, e, tokens, lens, B, T, loglik, out, mean);
 }
 
 }  // namespace pgmi
@@ -290,17 +191,17 @@ int pgmi_esmif1_model_create(const pgmi_config* cfg, int enc_dim, const float* w
 int pgmi_esmif1_set_memory(pgmi_model* m, const float* enc_out, int S) {
     int rc = if1_model_check(m);
     if (rc) return rc;
-    m->poet_P = 0;                                              // whatever happens below, stale planes are never read
+    m->pfx.rows = 0;                                              // whatever happens below, stale planes are never read
     if (!enc_out || S <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
     if (S > m->cfg.max_positions) {
         set_error("encoder memory of %d rows: the planes were created for max_positions = %d", S, m->cfg.max_positions);
         return PGMI_EINVAL;
     }
     if (S > m->max_rows) { set_error("encoder memory of %d rows exceeds the workspace of %d rows", S, m->max_rows); return PGMI_EINVAL; }
-    const size_t E = m->if1_enc, Da = m->Da, cache_plane = Da * m->poet_pitch;
+    const size_t E = m->if1_enc, Da = m->Da;
     for (size_t i = 0; i < (size_t)S * E; ++i)
         if (!std::isfinite(enc_out[i])) { set_error("encoder memory: non-finite value at row %zu", i / E); return PGMI_EINVAL; }
-    PoetPlan pl;
+    SegPlan pl;
     pl.add(S);
     PGMI_HIP(hipSetDevice(m->device));
     hipStream_t s = m->stream;
@@ -313,19 +214,15 @@ int pgmi_esmif1_set_memory(pgmi_model* m, const float* enc_out, int S) {
         { ProfScope p(m, PGMI_K_GEMM_QKV, 2.0 * S * 3 * Da * E, 0);
           rc = linear(m, nullptr, m->if1_mem16, nullptr, L.c_wqkv16, L.c_bqkv, nullptr, m->qkv, nullptr, S, 3 * (int)Da, (int)E, EPI_NONE);
           if (rc) return rc; }
-        PrefixAttLaunch a;                                       // the prep pass over one segment of S rows: its K / V^T planes ARE the layer's cache
+        PrefixAttLaunch a = prefix_launch(m, pl);                // the prep pass over one segment of S rows: its K / V^T planes ARE the layer's cache
         a.qkv = m->qkv;
-        a.seg_off = pl.d_seg_off; a.ent_seg = pl.d_ent_seg; a.ent_tile = pl.d_ent_tile;
-        a.n_seg = 1; a.n_ent = pl.n_ent(); a.H = m->cfg.heads;
-        a.q16 = m->qk16; a.q_plane = (size_t)m->max_rows * Da;
-        a.k16 = m->poet_cache + (size_t)l * 4 * cache_plane; a.vt16 = a.k16 + 2 * cache_plane; a.pitch = m->poet_pitch;
-        a.stream = s;
+        a.k16 = m->pfx.k(l); a.vt16 = m->pfx.vt(l); a.pitch = m->pfx.pitch;
         ProfScope p(m, PGMI_K_CROSS_ATTENTION, 0, 4.0 * S * Da * 4);
         rc = launch_prefix_prep(a);
         if (rc) return rc;
     }
     PGMI_HIP(hipStreamSynchronize(s));
-    m->poet_P = S;
+    m->pfx.rows = S;
     return PGMI_OK;
 }
 

@@ -61,6 +61,7 @@ int create_gpt(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_
     const size_t Vp = (V + 63) / 64 * 64;
     m->gpt_Vp = (int)Vp;
     m->slopes = m->zeros;
+    m->final_norm = true;
     m->fc1_epi = EPI_GELU_TANH;
     if (!wide_head(*cfg)) {
         c.upload(&m->head_w, head, V * D);
@@ -86,6 +87,62 @@ static int norm16(pgmi_model* m, const float* x, const float* w, const float* b,
     return PGMI_OK;
 }
 
+// x += W ctx + b: an attention's out-projection of the context rows in m->h16 into the residual stream
+int out_proj(pgmi_model* m, const W16& wo16, const float* bo, int M) {
+    const int D = m->cfg.embed_dim, Da = m->Da;
+    ProfScope p(m, PGMI_K_GEMM_OUT, 2.0 * M * D * Da, 0);
+    return linear(m, nullptr, m->h16, nullptr, wo16, bo, m->x, m->x, nullptr, M, D, Da, EPI_NONE);
+}
+
+static int mlp(pgmi_model* m, const Layer& L, int M) {                // x += fc_out(act(fc_in(h16)))
+    const int D = m->cfg.embed_dim, F = m->cfg.ffn_dim;
+    { ProfScope p(m, PGMI_K_GEMM_FC1, 2.0 * M * F * D, 0);
+      int rc = linear(m, nullptr, m->h16, nullptr, L.w116, L.b1, nullptr, nullptr, m->g16, M, F, D, m->fc1_epi);
+      if (rc) return rc; }
+    ProfScope p(m, PGMI_K_GEMM_FC2, 2.0 * M * F * D, 0);
+    return linear(m, nullptr, m->g16, nullptr, L.w216, L.b2, m->x, m->x, nullptr, M, D, F, EPI_NONE);
+}
+
+int ffn(pgmi_model* m, const Layer& L, int M) {
+    { ProfScope p(m, PGMI_K_LAYERNORM, 0, 2.0 * M * m->cfg.embed_dim * 4);
+      int rc = norm16(m, m->x, L.ln2_w, L.ln2_b, M, m->h16);
+      if (rc) return rc; }
+    return mlp(m, L, M);
+}
+
+// What differs per model is data: rotary tables (m->rot_cos) or none, a layer's depth-wise convolution (L.conv), the slopes.
+int self_attention(pgmi_model* m, const Layer& L, int B, int T, const AttRagged* rg, int rows, double att_flops) {
+    const int M = rg ? rows : B * T, D = m->cfg.embed_dim, Da = m->Da;
+    int rc;
+    { ProfScope p(m, PGMI_K_LAYERNORM, 0, 2.0 * M * D * 4);
+      rc = norm16(m, m->x, L.ln1_w, L.ln1_b, M, m->h16);
+      if (rc) return rc; }
+    { ProfScope p(m, PGMI_K_GEMM_QKV, 2.0 * M * 3 * Da * D, 0);
+      if (L.conv)                           // fp32 q | k | v rows: the attention's prep pass convolves and splits them
+          rc = linear(m, nullptr, m->h16, nullptr, L.wqkv16, L.bqkv, nullptr, m->qkv, nullptr, M, 3 * Da, D, EPI_NONE);
+      else {                                // fused QKV: the epilogue writes the attention's operand planes
+          GemmLaunch g = qkv_launch(m, L.wqkv16, L.bqkv, M, Da, D, T, m->Hs);
+          g.qkv.cos_t = m->rot_cos; g.qkv.sin_t = m->rot_sin; g.qkv.rotary = m->rot_cos != nullptr; g.qkv.rot_halves = m->rot_halves;
+          rc = launch_gemm16(g);
+      }
+      if (rc) return rc; }
+    if (m->parallel_residual) {             // the MLP branch first: it reads ln_1's output, which the context rows then overwrite
+        rc = mlp(m, L, M);
+        if (rc) return rc;
+    }
+    { ProfScope p(m, PGMI_K_ATTENTION, rg ? att_flops : 2.0 * M * T * Da, 0);     // causal: half of the 4 M T Da of a dense pass
+      AttLaunch a;
+      a.qk16 = m->qk16, a.qk_plane = m->qk16_plane, a.vt16 = m->vt16, a.vt_plane = m->vt16_plane;
+      a.B = B, a.T = T, a.H = m->cfg.heads, a.head_dim = m->rot_halves * kHeadDim;
+      a.slopes = m->slopes;
+      a.out = ATT_OUT_SPLIT, a.ctx16 = m->h16;
+      a.stream = m->stream;
+      if (L.conv) a.qkv = m->qkv, a.conv = L.conv;
+      rc = rg ? launch_attention_tr_ragged(a, *rg) : launch_attention_f16x3_v2(a);
+      if (rc) return rc; }
+    return out_proj(m, L.wo16, L.bo, M);
+}
+
 // The decoder body on tokens in m->tokens; leaves the residual stream after the last layer in m->x.  Dense: B sequences of T tokens,
 // [B*T, D].  Ragged (rg != nullptr; Tranception's prefix-shared scoring, api_tranception.hip): `rows` packed suffix rows of sequences
 // of T tokens, their attention over rg (att_flops for the profile).  What differs per model is data: the position kind (rotary tables
@@ -94,72 +151,32 @@ static int norm16(pgmi_model* m, const float* x, const float* w, const float* b,
 // which runs the layer's second norm itself, fused with its router).
 int run_decoder(pgmi_model* m, int B, int T, const AttRagged* rg, int rows, double att_flops) {
     const pgmi_config& c = m->cfg;
-    const int M = rg ? rows : B * T, D = c.embed_dim, F = c.ffn_dim, H = c.heads, Da = m->Da;
-    const bool rotary = m->rot_cos != nullptr;
+    const int M = rg ? rows : B * T, D = c.embed_dim;
     hipStream_t s = m->stream;
     int rc = rg ? PGMI_OK : reset_pad_keys(m, B, T);
     if (rc) return rc;
     { ProfScope p(m, PGMI_K_EMBED, 0, (double)M * D * (m->embed_positions ? 8 : 4));
       if (m->embed_positions) launch_embed_learned(m->tokens, m->embed_tokens, m->embed_positions, M, T, D, m->x, s);
       else launch_gather_rows(m->embed_tokens, m->tokens, M, D, m->x, s); }       // RITA, ProGen2, Tranception: no positional table
-    const double ln_bytes = 2.0 * M * D * 4;
-    auto mlp = [&](const Layer& L) {                                  // x += fc_out(act(fc_in(h16)))
-        { ProfScope p(m, PGMI_K_GEMM_FC1, 2.0 * M * F * D, 0);
-          int rc = linear(m, nullptr, m->h16, nullptr, L.w116, L.b1, nullptr, nullptr, m->g16, M, F, D, m->fc1_epi);
-          if (rc) return rc; }
-        ProfScope p(m, PGMI_K_GEMM_FC2, 2.0 * M * F * D, 0);
-        return linear(m, nullptr, m->g16, nullptr, L.w216, L.b2, m->x, m->x, nullptr, M, D, F, EPI_NONE);
-    };
     for (int l = 0; l < c.layers; ++l) {
         const Layer& L = m->layers[l];
-        { ProfScope p(m, PGMI_K_LAYERNORM, 0, ln_bytes);
-          rc = norm16(m, m->x, L.ln1_w, L.ln1_b, M, m->h16);
-          if (rc) return rc; }
-        { ProfScope p(m, PGMI_K_GEMM_QKV, 2.0 * M * 3 * Da * D, 0);
-          if (L.conv)                           // fp32 q | k | v rows: the attention's prep pass convolves and splits them
-              rc = linear(m, nullptr, m->h16, nullptr, L.wqkv16, L.bqkv, nullptr, m->qkv, nullptr, M, 3 * Da, D, EPI_NONE);
-          else {
-              GemmLaunch g = qkv_launch(m, L.wqkv16, L.bqkv, M, Da, D, T, m->Hs);
-              g.qkv.cos_t = m->rot_cos; g.qkv.sin_t = m->rot_sin; g.qkv.rotary = rotary; g.qkv.rot_halves = m->rot_halves;
-              rc = launch_gemm16(g);
-          }
-          if (rc) return rc; }
-        if (m->parallel_residual) {             // the MLP branch first: it reads ln_1's output, which the context rows then overwrite
-            rc = mlp(L);
-            if (rc) return rc;
-        }
-        { ProfScope p(m, PGMI_K_ATTENTION, rg ? att_flops : 2.0 * M * T * Da, 0);     // causal: half of the 4 M T Da of a dense pass
-          AttLaunch a;
-          a.qk16 = m->qk16, a.qk_plane = m->qk16_plane, a.vt16 = m->vt16, a.vt_plane = m->vt16_plane;
-          a.B = B, a.T = T, a.H = H, a.head_dim = m->rot_halves * kHeadDim;
-          a.slopes = m->slopes;
-          a.out = ATT_OUT_SPLIT, a.ctx16 = m->h16;
-          a.stream = s;
-          if (L.conv) a.qkv = m->qkv, a.conv = L.conv;
-          rc = rg ? launch_attention_tr_ragged(a, *rg) : launch_attention_f16x3_v2(a);
-          if (rc) return rc; }
-        { ProfScope p(m, PGMI_K_GEMM_OUT, 2.0 * M * D * Da, 0);
-          rc = linear(m, nullptr, m->h16, nullptr, L.wo16, L.bo, m->x, m->x, nullptr, M, D, Da, EPI_NONE);
-          if (rc) return rc; }
-        if (c.arch == PGMI_ARCH_PROGEN3) {
-            rc = pg3_ffn(m, L, l, M);
-            if (rc) return rc;
-        } else if (!m->parallel_residual) {
-            { ProfScope p(m, PGMI_K_LAYERNORM, 0, ln_bytes);
-              launch_layernorm16(m->x, L.ln2_w, L.ln2_b, M, D, m->ln_eps, m->h16, 1, s); }
-            rc = mlp(L);
-            if (rc) return rc;
-        }
+        rc = self_attention(m, L, B, T, rg, rows, att_flops);
+        if (!rc && c.arch == PGMI_ARCH_PROGEN3) rc = pg3_ffn(m, L, l, M);
+        else if (!rc && !m->parallel_residual) rc = ffn(m, L, M);
+        if (rc) return rc;
     }
     return PGMI_OK;
 }
 
-// Narrow head (V <= 64) on the M rows of m->x: ln_f, then the log-softmax over all V columns into m->lp [M, V].
-int narrow_head(pgmi_model* m, int M) {
+// The model's last LayerNorm (m->final_norm) and the narrow head (V <= 64): the log-softmax over all V columns of n rows into m->lp.
+int narrow_head(pgmi_model* m, const float* src, int n) {
     const int D = m->cfg.embed_dim, V = m->cfg.vocab;
-    { ProfScope p(m, PGMI_K_HEAD, 2.0 * M * D * V, 0);
-      launch_layernorm(m->x, m->lna_w, m->lna_b, M, D, m->ln_eps, m->h, m->stream);
-      launch_vocab_logsoftmax(m->h, m->head_w, m->head_b, M, D, V, m->lp, m->nonfinite, m->stream); }
+    ProfScope p(m, PGMI_K_HEAD, 2.0 * n * D * V, 0);
+    if (m->final_norm) {
+        launch_layernorm(src, m->lna_w, m->lna_b, n, D, m->ln_eps, m->h, m->stream);
+        src = m->h;
+    }
+    launch_vocab_logsoftmax(src, m->head_w, m->head_b, n, D, V, m->lp, m->nonfinite, m->stream);
     PGMI_HIP(hipGetLastError());
     return PGMI_OK;
 }
@@ -182,6 +199,33 @@ static int wide_head_rows(pgmi_model* m, int R, const int32_t* tgt, float* out, 
             PGMI_HIP(hipStreamSynchronize(m->stream));
         }
     }
+    return PGMI_OK;
+}
+
+int loglik_tail(pgmi_model* m, const int32_t* row_idx, int R, const int32_t* d_off, int bc, double* sum) {
+    const int D = m->cfg.embed_dim, V = m->cfg.vocab;
+    const bool wide = wide_head(m->cfg);
+    hipStream_t s = m->stream;
+    if (R > 0) {
+        if (row_idx) {
+            ProfScope p(m, PGMI_K_EMBED, 0, 2.0 * R * D * 4);
+            launch_gather_rows(m->x, row_idx, R, D, m->g, s);
+        }
+        const float* src = row_idx ? m->g : m->x;
+        int rc;
+        if (wide) {
+            { ProfScope p(m, PGMI_K_LAYERNORM, 0, 2.0 * R * D * 4);
+              rc = norm16(m, src, m->lna_w, m->lna_b, R, m->h16);
+              if (rc) return rc; }
+            rc = wide_head_rows(m, R, m->aux_i, m->denom, nullptr);        // its log-softmax picks the targets itself
+        } else rc = narrow_head(m, src, R);
+        if (rc) return rc;
+    }
+    { ProfScope p(m, PGMI_K_SCORE, 0, (double)R * 8);
+      if (R > 0 && !wide) launch_pppl_pick(m->lp, m->aux_i, R, V, m->denom, s);
+      launch_seq_sum(m->denom, d_off, bc, m->gpt_sum, s); }
+    PGMI_HIP(hipGetLastError());
+    PGMI_HIP(hipMemcpyAsync(sum, m->gpt_sum, (size_t)bc * sizeof(double), hipMemcpyDeviceToHost, s));
     return PGMI_OK;
 }
 
@@ -222,7 +266,7 @@ int decoder_token_logprobs(pgmi_model* m, int arch, const int32_t* tokens, int B
               if (rc) return rc; }
             return wide_head_rows(m, M, nullptr, nullptr, dst);
         }
-        rc = narrow_head(m, M);
+        rc = narrow_head(m, m->x, M);
         if (rc) return rc;
         PGMI_HIP(hipMemcpyAsync(dst, m->lp, (size_t)M * V * 4, hipMemcpyDeviceToHost, s));
         return PGMI_OK;
@@ -241,8 +285,6 @@ int decoder_sequence_loglik(pgmi_model* m, int arch, const int32_t* tokens, cons
     if (rc) return rc;
     for (int b = 0; b < B; ++b)
         if (lens[b] < 2 || lens[b] > T) { set_error("row %d of this call: length %d outside [2, T = %d]", b, lens[b], T); return PGMI_EINVAL; }
-    const pgmi_config& c = m->cfg;
-    const int D = c.embed_dim, V = c.vocab;
     std::vector<int32_t> in((size_t)B * Ti), idx, tgt, off;
     for (int b = 0; b < B; ++b) memcpy(&in[(size_t)b * Ti], tokens + (size_t)b * T, (size_t)Ti * 4);
     if (arch == PGMI_ARCH_PROGEN3)
@@ -270,25 +312,7 @@ int decoder_sequence_loglik(pgmi_model* m, int arch, const int32_t* tokens, cons
         PGMI_HIP(hipMemcpyAsync(m->aux_i, tgt.data(), (size_t)R * 4, hipMemcpyHostToDevice, s));
         PGMI_HIP(hipMemcpyAsync(m->kv_len, off.data(), (size_t)(bc + 1) * 4, hipMemcpyHostToDevice, s));
         int rc = run_decoder(m, bc, Ti);
-        if (rc) return rc;
-        { ProfScope p(m, PGMI_K_EMBED, 0, 2.0 * R * D * 4);
-          launch_gather_rows(m->x, m->row_idx, R, D, m->g, s); }                 // pad rows and last rows never reach the head
-        if (wide_head(c)) {
-            { ProfScope p(m, PGMI_K_LAYERNORM, 0, 2.0 * R * D * 4);
-              rc = norm16(m, m->g, m->lna_w, m->lna_b, R, m->h16);
-              if (rc) return rc; }
-            rc = wide_head_rows(m, R, m->aux_i, m->denom, nullptr);
-            if (rc) return rc;
-        } else {
-            ProfScope p(m, PGMI_K_HEAD, 2.0 * R * D * V, 0);
-            launch_layernorm(m->g, m->lna_w, m->lna_b, R, D, m->ln_eps, m->h, s);
-            launch_vocab_logsoftmax(m->h, m->head_w, m->head_b, R, D, V, m->lp, m->nonfinite, s);
-            launch_pppl_pick(m->lp, m->aux_i, R, V, m->denom, s);
-        }
-        launch_seq_sum(m->denom, m->kv_len, bc, m->gpt_sum, s);
-        PGMI_HIP(hipGetLastError());
-        PGMI_HIP(hipMemcpyAsync(sum + b0, m->gpt_sum, (size_t)bc * sizeof(double), hipMemcpyDeviceToHost, s));
-        return PGMI_OK;
+        return rc ? rc : loglik_tail(m, m->row_idx, R, m->kv_len, bc, sum + b0);     // pad rows and last rows never reach the head
     });
     if (rc) return rc;
     if (n_targets)

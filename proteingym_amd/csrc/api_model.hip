@@ -194,6 +194,33 @@ GemmLaunch qkv_launch(pgmi_model* m, const W16& w16, const float* bias, int M, i
     return g;
 }
 
+// A launch of attention_prefix.hip over the uploaded segments of pl: the q planes in m->qk16, split context rows into m->h16.  The
+// caller sets what differs: qkv / pos and the rotary tables of a prep pass, the own planes and their pitch, the prefix planes and P.
+PrefixAttLaunch prefix_launch(pgmi_model* m, const SegPlan& pl) {
+    PrefixAttLaunch a;
+    a.seg_off = pl.d_seg_off; a.ent_seg = pl.d_ent_seg; a.ent_tile = pl.d_ent_tile;
+    a.n_seg = pl.n_seg(); a.n_ent = pl.n_ent(); a.H = m->cfg.heads;
+    a.q16 = m->qk16; a.q_plane = (size_t)m->max_rows * m->Da;
+    a.out = ATT_OUT_SPLIT; a.ctx16 = m->h16; a.stream = m->stream;
+    return a;
+}
+
+int alloc_prefix_cache(pgmi_model* m) {
+    PrefixCache& c = m->pfx;
+    c.pitch = ((size_t)m->cfg.max_positions + 31) / 32 * 32;
+    c.plane = (size_t)m->Da * c.pitch;
+    c.cap = (size_t)m->max_rows;
+    int rc = PGMI_OK;
+    if (c.pitch) {
+        const size_t n = (size_t)m->cfg.layers * 4 * c.plane;
+        rc = dev_alloc(m->allocs, &c.planes, n);
+        if (!rc) PGMI_HIP(hipMemset(c.planes, 0, n * sizeof(unsigned short)));
+    }
+    if (!rc) rc = dev_alloc(m->allocs, &c.meta, PrefixCache::meta_ints(c.cap));
+    if (!rc) rc = dev_alloc(m->allocs, &m->gpt_sum, c.cap);
+    return rc;
+}
+
 // fp16 range check for the 16-bit modes: the vocabulary kernel raises the flag when a computed
 // log-probability is NaN/inf (an activation exceeded fp16's 65504 upstream).
 int check_nonfinite(pgmi_model* m) {

@@ -612,6 +612,22 @@ int pgmi_op_cross_attention(int device, const float* q, const int32_t* seg_off, 
     return PGMI_OK;
 }
 
+// The chunks pack_chunk cuts a batch of B packed sequences into for a workspace of max_rows rows, as score_packed walks them (host
+// only: no device is touched): out_b1[i] = the end of chunk i, *out_n = the number of chunks.
+int pgmi_op_packed_chunks(const int32_t* lens, int B, int drop_last, int same_length, int max_rows, int32_t* out_b1, int32_t* out_n) {
+    if (!lens || !out_b1 || !out_n || B <= 0 || max_rows <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
+    const int lo = drop_last ? 2 : 1;
+    for (int b = 0; b < B; ++b)
+        if (lens[b] < lo) { set_error("row %d of this call: length %d below %d", b, lens[b], lo); return PGMI_EINVAL; }
+    *out_n = 0;
+    for (int b0 = 0; b0 < B;) {
+        const PackedChunk ch = pack_chunk(lens, b0, B, drop_last != 0, same_length != 0, max_rows, own_pitch(max_rows));
+        if (ch.b1 == b0) { set_error("row %d of this call: %d tokens exceed the workspace of %d rows", b0, lens[b0], max_rows); return PGMI_EINVAL; }
+        out_b1[(*out_n)++] = b0 = ch.b1;
+    }
+    return PGMI_OK;
+}
+
 // The K splits run_msa's rule picks for an alignment of R x C tokens and H heads (host only: no device is touched).
 int pgmi_op_tied_row_splits(int R, int C, int H) {
     if (R <= 0 || C <= 0 || H <= 0) { set_error("bad argument"); return PGMI_EINVAL; }

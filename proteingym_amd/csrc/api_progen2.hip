@@ -32,6 +32,7 @@ int create_progen2(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_
     m->pg2_rotary = rotary_dim;
     m->parallel_residual = true;                                   // the decoder body: no positional table, q / k rotated by the tables
     m->slopes = m->zeros;
+    m->final_norm = true;
     m->fc1_epi = EPI_GELU_TANH;
     BlobCursor c(m, w, n_weights);
     c.upload(&m->embed_tokens, V * D);

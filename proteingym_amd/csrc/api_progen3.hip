@@ -171,6 +171,7 @@ int create_progen3(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_
     m->rms_norm = true;
     m->pg3_E = (int)E; m->pg3_k = p->top_k; m->pg3_gated = p->gated != 0;
     m->slopes = m->zeros;
+    m->final_norm = true;
     BlobCursor c(m, w, n_weights);
     {   // embed_tokens[id] + embed_seq_id[0]: the reference's own fp32 add, once per table element
         const float* tok = c.take(V * D);

@@ -86,6 +86,7 @@ int create_tranception(pgmi_model* m, const pgmi_config* cfg, const float* w, in
         for (double v : quarter) sl.push_back((float)v);
     c.upload(&m->slopes, sl.data(), sl.size());
     m->fc1_epi = EPI_SQRELU;
+    m->final_norm = true;
     return c.finish();
 }
 
@@ -204,7 +205,7 @@ int run_tranception_shared(pgmi_model* m, TrChunk& ck, int T, const float* prior
     PGMI_HIP(hipStreamSynchronize(s));                 // the host vectors go out of scope with the caller's chunk
     m->last_B = m->last_T = 0;                          // the V^T planes now hold another layout: the dense path clears them again
     rc = run_decoder(m, 0, T, &rg, M, ck.att_flops);
-    if (!rc) rc = narrow_head(m, M);
+    if (!rc) rc = narrow_head(m, m->x, M);
     if (rc) return rc;
     { ProfScope ps(m, PGMI_K_SCORE, 0, (double)S * T * 8);
       launch_seq_loglik_ragged(m->lp, m->tokens, rg.seq_off, rg.seq_p, rg.seq_root, S, T, V, prior_dev, d_pa, d_pr, d_pc, d_pf, alpha,
@@ -230,7 +231,7 @@ int pgmi_tr_token_logprobs(pgmi_model* m, const int32_t* tokens, int B, int T, f
     rc = for_each_chunk(m, B, T, [&](int b0, int bc) {
         PGMI_HIP(hipMemcpyAsync(m->tokens, tokens + (size_t)b0 * T, (size_t)bc * T * 4, hipMemcpyHostToDevice, m->stream));
         int rc = run_decoder(m, bc, T);
-        if (!rc) rc = narrow_head(m, bc * T);
+        if (!rc) rc = narrow_head(m, m->x, bc * T);
         if (rc) return rc;
         PGMI_HIP(hipMemcpyAsync(out + (size_t)b0 * T * V, m->lp, (size_t)bc * T * V * 4, hipMemcpyDeviceToHost, m->stream));
         return PGMI_OK;
@@ -284,7 +285,7 @@ int pgmi_tr_sequence_loglik_eve(pgmi_model* m, const int32_t* tokens, const int3
             PGMI_HIP(hipMemcpyAsync(dfl, prior_flip + b0, (size_t)bc * 4, hipMemcpyHostToDevice, s));
         }
         int rc = run_decoder(m, bc, T);
-        if (!rc) rc = narrow_head(m, bc * T);
+        if (!rc) rc = narrow_head(m, m->x, bc * T);
         if (rc) return rc;
         { ProfScope p(m, PGMI_K_SCORE, 0, (double)bc * T * 8);
           launch_seq_loglik(m->lp, m->tokens, m->kv_len, bc, T, V, log_prior ? m->tr_prior : nullptr, da0, dr0, dn, dfl, alpha,

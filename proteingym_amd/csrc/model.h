@@ -1,19 +1,22 @@
 // Internal header of the C ABI's translation units (api_*.hip): the device-resident model / assay / library state behind the opaque
 // handles of include/pgmi.h and the host-side helpers they share.  Nothing here is part of the ABI.
 //   api_model.hip        errors, configuration and token checks, weight split, linear() / qkv_launch() (a model's GEMMs as a
-//                        GemmLaunch), model create (validation, per-arch dispatch, workspace) / destroy, options, profiling
+//                        GemmLaunch), prefix_launch() / alloc_prefix_cache(), model create (validation, per-arch dispatch, workspace) /
+//                        destroy, options, profiling
 //   api_esm.hip          ESM-1b / ESM-1v / ESM2 weights (create_esm), the encoder forward of the ESM family and ESM C (run_encoder,
 //                        run_head), masked-marginals assays, pseudo-ppl libraries
 //   api_tranception.hip  Tranception weights, prefix-shared chunks; token log-probs and sequence log-likelihoods (on run_decoder)
 //   api_progen2.hip      ProGen2 weights (GPT-J rotary, bias-free projections), its 25-column amino-acid head and sequence
 //                        log-likelihoods
 //   api_gpt.hip          causal decoder: RITA / ProtGPT2 weights, the decoder body of RITA / ProtGPT2 / ProGen2 / Tranception (sequential
-//                        or ProGen2's parallel residual; dense or Tranception's ragged prefix-shared rows), narrow and wide LM heads,
-//                        the checks and token log-probs of RITA / ProtGPT2 / ProGen2; RITA / ProtGPT2 sequence log-likelihoods
-//   api_poet.hip         PoET: tiered (within-sequence, then sequence-of-sequences) causal decoder on attention_prefix.hip, the
-//                        per-layer prefix cache of a prompt, variant log-probs and log-likelihoods
-//   api_esmif1.hip       ESM-IF1's decoder: causal self-attention and cross-attention over the cached K / V^T planes of one encoded
-//                        backbone (attention_prefix.hip), token log-probs and per-sequence mean log-likelihoods
+//                        or ProGen2's parallel residual; dense or Tranception's ragged prefix-shared rows) and the sublayers it shares
+//                        with the packed decoders (self_attention, out_proj, ffn), narrow and wide LM heads, the log-likelihood tail
+//                        (loglik_tail), the checks and token log-probs of RITA / ProtGPT2 / ProGen2; RITA / ProtGPT2 log-likelihoods
+//   api_poet.hip         PoET: tiered (within-sequence, then sequence-of-sequences) causal decoder on attention_prefix.hip over the
+//                        prefix cache of a prompt; score_packed, the driver of its and ESM-IF1's token log-prob / log-likelihood
+//                        entries (chunks cut by packed_chunks.h pack_chunk)
+//   api_esmif1.hip       ESM-IF1's decoder: self_attention, then cross-attention over the prefix cache of one encoded backbone
+//                        (attention_prefix.hip); its entries run on score_packed
 //   api_progen3.hip      ProGen3 weights (RMSNorm, grouped-query attention as replicated K/V projection rows, per-expert FC1 / FC2), its
 //                        feed-forward block on moe.hip (pg3_ffn, moe_ffn), the C entries; it runs on run_decoder
 //   api_esmc.hip         ESM C weights (QK-LayerNorm, SwiGLU, scaled residual, untied 64-column head); it runs on run_encoder
@@ -40,6 +43,7 @@
 
 #include "common.h"
 #include "gemm16x_kernel.h"          // XMap (the tied row attention's operand maps); no kernel is instantiated here
+#include "packed_chunks.h"           // SegPlan, pack_chunk
 
 namespace pgmi {
 
@@ -76,6 +80,24 @@ struct Layer {
 struct ProfEvent {
     hipEvent_t start, stop;
     int cls;
+};
+
+// The shared prefix of attention_prefix.hip's launches, per layer, in their operand layout: planes [layers][K | V^T][2 planes][plane]
+// halfs, plane = Da * pitch, for a prefix of at most pitch = roundup(max_positions, 32) rows (0: the model has no cache); `rows` of
+// them are valid (0: no prefix is set).  meta, for a workspace of cap = max_rows rows: two SegPlan slots (upload_plan) of
+// plan_ints(cap) = 3 cap + 2 ints -- seg_off [cap + 1] and a pad, ent_seg [cap], ent_tile [cap]: a plan has at most cap segments and
+// cap tiles -- then the sequence offsets of a log-likelihood chunk, [cap + 1] and 3 of pad: meta_ints(cap) = 7 cap + 8.
+struct PrefixCache {
+    unsigned short* planes = nullptr;
+    size_t pitch = 0, plane = 0, cap = 0;
+    int rows = 0;
+    int32_t* meta = nullptr;
+    static size_t plan_ints(size_t cap) { return 3 * cap + 2; }
+    static size_t meta_ints(size_t cap) { return 2 * plan_ints(cap) + cap + 4; }
+    unsigned short* k(int l) const { return planes ? planes + (size_t)l * 4 * plane : nullptr; }
+    unsigned short* vt(int l) const { return planes ? k(l) + 2 * plane : nullptr; }
+    int32_t* plan(int slot) const { return meta + (size_t)slot * plan_ints(cap); }
+    int32_t* seq_off() const { return plan(2); }
 };
 
 }  // namespace pgmi
@@ -145,19 +167,14 @@ struct pgmi_model {
     size_t tied_part_cap = 0, tied_p_cap = 0, tied_vt_cap = 0;
     int msa_kv_R = 0, msa_kv_C = 0;
     float ln_eps = 1e-5f;
-    // PoET (api_poet.hip): the per-layer prefix cache -- the prompt's tier-2 K (rotated) and V^T in the operand layout of
-    // attention_prefix.hip, [layers][K | V^T][2 planes][H * poet_pitch * 64] -- for a prompt of at most poet_pitch tokens, the prompt's
-    // length (0: none) and its own log-probability rows; the (segment, tile) lists of the two tiers
-    bool poet_final_norm = false;
-    unsigned short* poet_cache = nullptr;
-    size_t poet_pitch = 0;
-    int poet_P = 0;
-    std::vector<float> poet_prompt_lp;
-    int32_t* poet_meta = nullptr;
-    // ESM-IF1 (api_esmif1.hip): the decoder.  The prefix cache above holds the encoded backbone's per-layer K / V^T planes (poet_P = S
-    // memory rows, 0: none set; poet_pitch = roundup(max_positions, 32)); if1_enc = the encoder width, if1_mem / if1_mem16 the staging
-    // of one encoder output [max_positions][if1_enc] (fp32, split), if1_pos the sinusoidal table [if1_pos_len][D] (row t = position
-    // padding_idx + 1 + t)
+    // the narrow head (narrow_head) runs the model's last LayerNorm lna first: every causal decoder and ESM-IF1; PoET by its checkpoint
+    bool final_norm = false;
+    // PoET (the prompt's tier-2 K, rotated, and V^T of every layer) and ESM-IF1 (the encoded backbone's K / V^T of every layer's
+    // encoder_attn): the prefix every packed launch shares, the launches' plans and the sequence offsets of a log-likelihood chunk
+    PrefixCache pfx;
+    std::vector<float> poet_prompt_lp;  // PoET: the log-probability rows of the prompt last set
+    // ESM-IF1 (api_esmif1.hip): if1_enc = the encoder width, if1_mem / if1_mem16 the staging of one encoder output
+    // [max_positions][if1_enc] (fp32, split), if1_pos the sinusoidal table [if1_pos_len][D] (row t = position padding_idx + 1 + t)
     int if1_enc = 0, if1_pos_len = 0;
     float *if1_mem = nullptr, *if1_pos = nullptr;
     unsigned short* if1_mem16 = nullptr;
@@ -295,6 +312,8 @@ int make_w16(std::vector<void*>& pool, const float* host, size_t n, size_t K, in
 int linear(pgmi_model* m, const float* in32, const unsigned short* in16, const float* W32, const W16& w16, const float* bias,
            const float* residual, float* out32, unsigned short* out16, int M, int N, int K, int epi);
 GemmLaunch qkv_launch(pgmi_model* m, const W16& w16, const float* bias, int M, int Da, int K, int T, int H);
+PrefixAttLaunch prefix_launch(pgmi_model* m, const SegPlan& pl);
+int alloc_prefix_cache(pgmi_model* m);              // m->pfx for cfg.max_positions prefix rows (0: no planes), and m->gpt_sum
 int check_nonfinite(pgmi_model* m);
 int reset_pad_keys(pgmi_model* m, int B, int T);
 int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int device, pgmi_model** out, int arch_arg,
@@ -316,7 +335,16 @@ int create_gpt(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_
 int64_t gpt_weight_count(const pgmi_config* c, int pos_kind);
 int decoder_check(pgmi_model* m, int arch, int T);
 int run_decoder(pgmi_model* m, int B, int T, const AttRagged* rg = nullptr, int rows = 0, double att_flops = 0);
-int narrow_head(pgmi_model* m, int M);
+// the sublayers of the 16-bit decoder loops (run_decoder, poet_forward, if1_forward) on the M rows of m->x:
+// x += out_proj(causal_attn(ln_1(x))), dense B x T or ragged as run_decoder takes it (ProGen2: its MLP branch too, before the attention)
+int self_attention(pgmi_model* m, const Layer& L, int B, int T, const AttRagged* rg = nullptr, int rows = 0, double att_flops = 0);
+int out_proj(pgmi_model* m, const W16& wo16, const float* bo, int M);    // x += W ctx + b on the context rows in m->h16
+int ffn(pgmi_model* m, const Layer& L, int M);                           // x += fc2(act(fc1(ln_2(x)))), act = m->fc1_epi
+int narrow_head(pgmi_model* m, const float* src, int n);                 // lna when m->final_norm, log-softmax (V <= 64): src [n,D] -> m->lp [n,V]
+// The end of a log-likelihood chunk: the R rows of m->x that have a target (row_idx on the device; nullptr: the first R rows as they
+// are) through the narrow or wide head, log p(m->aux_i[r]) of each, their sums over the bc sequences (d_off [bc + 1], on the device)
+// into m->gpt_sum and, asynchronously, into sum [bc].  R == 0: every sum is 0.
+int loglik_tail(pgmi_model* m, const int32_t* row_idx, int R, const int32_t* d_off, int bc, double* sum);
 int decoder_token_logprobs(pgmi_model* m, int arch, const int32_t* tokens, int B, int T, float* out);
 int decoder_sequence_loglik(pgmi_model* m, int arch, const int32_t* tokens, const int32_t* lens, int B, int T, double* sum, int32_t* n_targets);
 // api_progen3.hip
@@ -336,6 +364,22 @@ int moe_ffn(pgmi_model* m, const pgmi_model::MoeWs& ws, const std::vector<W16>& 
 // api_poet.hip
 int64_t poet_weight_count(const pgmi_config* c, int final_norm);
 int create_poet(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights, int final_norm);
+// What differs between the packed-decoder entries of PoET and ESM-IF1 (score_packed).
+struct PackedScorer {
+    int (*forward)(pgmi_model* m, int bc, int R, const SegPlan& pl);    // the chunk's bc sequences, R packed rows, uploaded -> m->x
+    int pos_len;                    // the longest sequence the position table takes, and its name in the refusal
+    const char* pos_what;
+    const char* not_ready;          // non-null: the entry cannot run yet, and why
+    bool same_length;               // a chunk is a run of sequences of one length
+    bool vocab_per_row;             // token ids are checked per row over its lens[b] tokens (the pad value is not read); else over [B,T]
+    int skip_target;                // log-likelihood: a target equal to this token does not count (-1: every target counts)
+    bool mean;                      // log-likelihood: the mean over the lens[b] - 1 targets instead of their sum
+};
+// Sequences [B][T] right-padded, lens[b] tokens each, cut into chunks by pack_chunk.  loglik: the model reads tokens[b, :lens[b] - 1]
+// and sum[b] = the sum (mean) of log p(tokens[b, t + 1]) over the targets that count; else it reads all lens[b] tokens and every row's
+// log-probabilities go to out [B][T][V] (rows beyond lens[b]: NaN).
+int score_packed(pgmi_model* m, const PackedScorer& e, const int32_t* tokens, const int32_t* lens, int B, int T, bool loglik, float* out,
+                 double* sum);
 // api_esmif1.hip
 int if1_check(const pgmi_config* c, int enc_dim);
 int64_t if1_weight_count(const pgmi_config* c, int enc_dim);
@@ -441,28 +485,13 @@ int upload_rotary(pgmi_model* m, int n, int groups, Angle angle) {
     return rc;
 }
 
-// attention_prefix.hip's launches (PoET, ESM-IF1): the (segment, tile) lists of a launch, on the host and (slot 0 / 1 of m->poet_meta)
-// on the device; own_pitch = the padded key rows the workspace's own-segment planes hold.
-struct PoetPlan {
-    std::vector<int32_t> seg_off, ent_seg, ent_tile;
-    int32_t *d_seg_off = nullptr, *d_ent_seg = nullptr, *d_ent_tile = nullptr;
-    int n_seg() const { return (int)seg_off.size() - 1; }
-    int n_ent() const { return (int)ent_seg.size(); }
-    void add(int len) {
-        if (seg_off.empty()) seg_off.push_back(0);
-        const int b = n_seg();
-        for (int j = 0; j * 32 < len; ++j) { ent_seg.push_back(b); ent_tile.push_back(j); }
-        seg_off.push_back(seg_off.back() + len);
-    }
-};
+// attention_prefix.hip's launches (PoET, ESM-IF1): upload_plan puts a launch's (segment, tile) lists into plan slot 0 / 1 of m->pfx.meta.
+inline size_t own_pitch(const pgmi_model* m) { return own_pitch(m->max_rows); }
 
-inline size_t own_pitch(const pgmi_model* m) { return (size_t)m->max_rows / 32 * 32; }
-
-inline int upload_plan(pgmi_model* m, PoetPlan& p, int slot) {
-    const size_t cap = (size_t)m->max_rows;
-    p.d_seg_off = m->poet_meta + (size_t)slot * (3 * cap + 2);
-    p.d_ent_seg = p.d_seg_off + cap + 2;
-    p.d_ent_tile = p.d_ent_seg + cap;
+inline int upload_plan(pgmi_model* m, SegPlan& p, int slot) {
+    p.d_seg_off = m->pfx.plan(slot);
+    p.d_ent_seg = p.d_seg_off + m->pfx.cap + 2;
+    p.d_ent_tile = p.d_ent_seg + m->pfx.cap;
     PGMI_HIP(hipMemcpyAsync(p.d_seg_off, p.seg_off.data(), p.seg_off.size() * 4, hipMemcpyHostToDevice, m->stream));
     PGMI_HIP(hipMemcpyAsync(p.d_ent_seg, p.ent_seg.data(), p.ent_seg.size() * 4, hipMemcpyHostToDevice, m->stream));
     PGMI_HIP(hipMemcpyAsync(p.d_ent_tile, p.ent_tile.data(), p.ent_tile.size() * 4, hipMemcpyHostToDevice, m->stream));

@@ -779,3 +779,69 @@ def test_scoring_op_entries_refuse_bad_arguments_before_they_look_for_a_device(l
     refused(seq(tokens=rtok, lens=None, off=i32(3, 0), p=i32(0, 2), root=z, rows=6), "ragged sequence 0")      # the root's rows end at 7
     # what passes every check ends at the device (or, with one, succeeds)
     assert seq() in (0, _lib.ENODEV) and seq(tokens=rtok, lens=None, off=i32(0, 4), p=i32(0, 2), root=z, rows=6) in (0, _lib.ENODEV)
+
+
+def _packed_chunks_rule(lens, drop_last, same_length, max_rows):
+    """The chunk rule of the PoET / ESM-IF1 entries, restated: the sizes of the successive chunks, or the index of the first sequence
+    that fits no chunk alone."""
+    pitch, sizes, b0 = max_rows // 32 * 32, [], 0
+    while b0 < len(lens):
+        rows = padded = 0
+        b1 = b0
+        while b1 < len(lens) and not (same_length and lens[b1] != lens[b0]):
+            n = lens[b1] - (1 if drop_last else 0)
+            if rows + n > max_rows or padded + (n + 31) // 32 * 32 > pitch:
+                break
+            rows, padded, b1 = rows + n, padded + (n + 31) // 32 * 32, b1 + 1
+        if b1 == b0:
+            return b0
+        sizes.append(b1 - b0)
+        b0 = b1
+    return sizes
+
+
+def _packed_chunks(lib, lens, drop_last, same_length, max_rows):
+    lens = np.asarray(lens, np.int32)
+    b1, n = np.full(len(lens), -1, np.int32), np.full(1, -1, np.int32)
+    rc = lib.pgmi_op_packed_chunks(_lib.ptr(lens, _lib._i32p), len(lens), int(drop_last), int(same_length), max_rows, _lib.ptr(b1, _lib._i32p),
+                                   _lib.ptr(n, _lib._i32p))
+    if rc:
+        return rc, lib.pgmi_last_error().decode()
+    assert 1 <= n[0] <= len(lens) and b1[n[0] - 1] == len(lens) and (b1[n[0]:] == -1).all()
+    return 0, np.diff(np.concatenate([[0], b1[:n[0]]])).tolist()
+
+
+@pytest.mark.parametrize("lens,drop_last,same_length,max_rows,want", [
+    ((32, 32, 32, 1), False, False, 100, [3, 1]),       # padding ends the chunk: the fourth has row room (97 <= 100), no padded room (128 > 96)
+    ((33, 33), False, False, 100, [1, 1]),              # padding binds before rows: 64 + 64 > 96
+    ((96, 1), False, False, 96, [1, 1]),                # rows end the chunk exactly
+    ((5, 5, 6, 5), False, True, 100, [2, 1, 1]),        # a chunk is a run of one length
+    ((5, 5, 6, 5), False, False, 100, [3, 1]),          # the length change breaks nothing; the fourth's padding does (4 x 32 = 128 > 96)
+    ((5, 5, 6, 5), False, False, 128, [4]),             # with padded room for four, one chunk ...
+    ((5, 5, 6, 5), False, True, 128, [2, 1, 1]),        # ... that same_length still cuts at the length changes
+    ((33, 33), True, False, 100, [2]),                  # the model reads 32 + 32
+])
+def test_packed_chunk_boundaries(lib, lens, drop_last, same_length, max_rows, want):
+    assert _packed_chunks_rule(lens, drop_last, same_length, max_rows) == want
+    assert _packed_chunks(lib, lens, drop_last, same_length, max_rows) == (0, want)
+
+
+def test_packed_chunks_refuse_a_sequence_that_cannot_start_a_chunk(lib):
+    """97 tokens fit the 100 rows and not the 96 padded key rows (128 > 96): the entries' own message."""
+    assert _packed_chunks_rule((97,), False, False, 100) == 0
+    assert _packed_chunks(lib, (97,), False, False, 100) == (_lib.EINVAL, "row 0 of this call: 97 tokens exceed the workspace of 100 rows")
+    assert _packed_chunks_rule((5, 5, 97, 5), False, False, 100) == 2
+    assert _packed_chunks(lib, (5, 5, 97, 5), False, False, 100) == (_lib.EINVAL, "row 2 of this call: 97 tokens exceed the workspace of 100 rows")
+    for bad in ((0, 5), (5, 1)):
+        rc, msg = _packed_chunks(lib, bad, bad == (5, 1), False, 100)
+        assert rc == _lib.EINVAL and "length" in msg, (bad, rc, msg)
+    assert lib.pgmi_op_packed_chunks(None, 1, 0, 0, 100, None, None) == _lib.EINVAL
+
+
+@pytest.mark.parametrize("drop_last", [False, True])
+@pytest.mark.parametrize("same_length", [False, True])
+def test_packed_chunks_match_the_rule_on_random_lengths(lib, drop_last, same_length):
+    lens = np.random.default_rng(20261020).integers(1 + drop_last, 41, size=200).tolist()
+    want = _packed_chunks_rule(lens, drop_last, same_length, 100)
+    assert isinstance(want, list) and sum(want) == 200 and len(want) > 1
+    assert _packed_chunks(lib, lens, drop_last, same_length, 100) == (0, want)
