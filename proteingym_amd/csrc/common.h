@@ -51,6 +51,36 @@ __device__ __forceinline__ void split_act(float x, _Float16& hi, _Float16& lo) {
     hi = (fabsf(x) < 6.103515625e-05f) ? (_Float16)0.0f : (_Float16)x;
     lo = (_Float16)((x - (float)hi) * kLoScale);
 }
+// split_act for four values at a time, the same (hi, lo) pairs in fewer VALU issue slots: the flush of |x| < 2^-14 is a select on x in front of
+// two PACKED RNE conversions, and lo = fma(hi, -2^11, 2^11 x) is one mixed-precision fma on the fp16 hi (attention_f16_common.h split_p does
+// the same for P).  2^11 x is exact (a power of two; beyond 2^117 it overflows, where hi is already infinite), x - hi is exact in fp32 (hi is x
+// rounded to 11 bits, or 0), so the fma's single rounding has nothing to round: lo32 = (x - hi) 2^11, the value split_act converts.  A NaN or
+// an infinity in x gives a non-finite hi AND lo, as there.  Every fused operation is written out; nothing here is left to -ffp-contract.
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void split_act4(f32x4 x, f16x4& hi, f16x4& lo) {
+    f32x4 xz, lo32;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) xz[e] = (fabsf(x[e]) < 6.103515625e-05f) ? 0.0f : x[e];
+    hi = __builtin_convertvector(xz, f16x4);
+    const f32x4 xs = x * f32x4{kLoScale, kLoScale, kLoScale, kLoScale};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) lo32[e] = __builtin_fmaf((float)hi[e], -kLoScale, xs[e]);
+    lo = __builtin_convertvector(lo32, f16x4);
+}
+// The same for a value that is a product a b (squared ReLU: t t).  Behind split_act the compiler had fused that product into the subtraction
+// of hi in every instantiation (-ffp-contract): lo = (fma(a, b, -hi)) 2^11 sees the UNROUNDED product, hi the rounded one.  Written out here
+// so that the planes keep those bits and no instantiation can decide otherwise.  (SwiGLU's silu(gate) up is fused differently again -- this
+// form does not give its bits -- and keeps the scalar split_act.)
+__device__ __forceinline__ void split_act4_prod(f32x4 a, f32x4 b, f16x4& hi, f16x4& lo) {
+    const f32x4 x = a * b;
+    f32x4 xz, lo32;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) xz[e] = (fabsf(x[e]) < 6.103515625e-05f) ? 0.0f : x[e];
+    hi = __builtin_convertvector(xz, f16x4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) lo32[e] = __builtin_fmaf(a[e], b[e], -(float)hi[e]);
+    lo = __builtin_convertvector(lo32 * f32x4{kLoScale, kLoScale, kLoScale, kLoScale}, f16x4);
+}
 // The columns 4 c .. 4 c + 3 of `row` (D columns, D % 8 == 0) into the K-interleaved split operand, for kernels whose lane `lane` of a wave
 // holds the f32x4 group c = lane + 64 i: lanes (2m, 2m+1) hold one group of 8 columns; the even lane stores the 16 bytes of hi values, the
 // odd lane the 16 bytes of lo values (one exchange of 8 bytes with the neighbour), so 8 lanes write one 128-byte line with one store each.

@@ -418,21 +418,32 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
             }
 #pragma unroll
             for (int g = 0; g < 2; ++g) asm volatile("" :: "v"(bq0[g]), "v"(bq1[g]));      // waited for HERE, not inside the block loop
+            // INT (interior): a q | k wave whose rows are all below M (its 64 columns always are: N = 3 Dm, Dm % 64 == 0) -- no row test per
+            // cell, no V^T code, patch cells at compile-time offsets from one per-lane address (as in the OUT 1 epilogue below)
+            auto emit = [&](auto interior_c) {
+            constexpr bool INT = decltype(interior_c)::value;
+            unsigned char* const lane_cell = patch_q + r * SPQ + kq * 8;
+            // 16-byte chunk lane & 7 of row (lane >> 3) of the wave's first 32-row block: one 64-bit address per lane and item
+            unsigned short* const int_dst = !INT ? nullptr : Ch + (size_t)(em0 + wm * TM * 16 + (lane >> 3)) * (2 * Dm) + (size_t)which * Dm + hcol + (lane & 7) * 8;
             // 32-row blocks of two M16 tiles: the staged q | k rows leave the patch as in a 32x32 layout
 #pragma unroll
             for (int ib = 0; ib < TM / 2; ++ib) {
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
-                const int i = 2 * ib + s, prow = 16 * s + r;   // M16 tile, row in the block's patch
+                const int i = 2 * ib + s;                      // M16 tile; its row in the block's patch is 16 s + r
                 const int m = em0 + (wm * TM + i) * 16 + r;
                 const bool row_ok = m < M;
-                if (!row_ok) continue;
-                const int bb = m / qo.T, t = m - bb * qo.T;
+                if (!INT && !row_ok) continue;
+                int bb = 0, t = 0;
+                if (!INT || qo.rotary) {
+                    bb = m / qo.T;
+                    t = m - bb * qo.T;
+                }
                 // ESM2: the row's rotary table entries for all four column groups, loaded TOGETHER before the group loop (loads inside it
                 // were waited for one group at a time, and the wait -- vmcnt counts stores too -- included the V^T stores just issued)
                 // (a table row holds every angle twice: slots i and 32 + i are the pair (j, j + dh / 2) of one frequency -- api_esm.hip ensure_rotary)
                 f32x4 rc[2], rs[2];
-                if (which < 2 && qo.rotary) {
+                if ((INT || which < 2) && qo.rotary) {
                     const int tr = (min(t, qo.T - 1) * qo.rot_halves + (hh % qo.rot_halves)) * 64;
 #pragma unroll
                     for (int g = 0; g < 2; ++g) {
@@ -454,7 +465,7 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
 #pragma unroll
                         for (int e = 0; e < 4; ++e) { x0[e] *= kQLog2e; x1[e] *= kQLog2e; }
                     }
-                    if (which < 2) {
+                    if (INT || which < 2) {
                         if (qo.rotary) {                       // rotary_embedding.py:11-20
                             const f32x4 c1 = rc[g], s1 = rs[g], c2 = rc[g], s2 = rs[g];
 #pragma unroll
@@ -466,13 +477,9 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
                             }
                         }
                         h4 hi0, lo0, hi1, lo1;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            _Float16 a, b2;
-                            split_act(x0[e], a, b2); hi0[e] = a; lo0[e] = b2;
-                            split_act(x1[e], a, b2); hi1[e] = a; lo1[e] = b2;
-                        }
-                        unsigned char* cell = patch_q + prow * SPQ + d0 * 2;
+                        split_act4(f32x4{x0[0], x0[1], x0[2], x0[3]}, hi0, lo0);
+                        split_act4(f32x4{x1[0], x1[1], x1[2], x1[3]}, hi1, lo1);
+                        unsigned char* cell = lane_cell + (16 * s) * SPQ + 32 * g;      // row 16 s + r, byte 2 d0 of the row
                         lds_put(cell, hi0);
                         lds_put(cell + 32 * SPQ, lo0);
                         lds_put(cell + 64, hi1);
@@ -496,7 +503,7 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
                     }
                 }
             }
-                if (staged_q) {
+                if (INT || staged_q) {
                     __builtin_amdgcn_wave_barrier();
                     const int m_base = em0 + (wm * TM + 2 * ib) * 16;
 #pragma unroll
@@ -504,8 +511,9 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
                         const int q = lane + 64 * k, row = q >> 3, cc = q & 7;
                         const u32x4 vh = *reinterpret_cast<const u32x4*>(patch_q + row * SPQ + cc * 16);
                         const u32x4 vl = *reinterpret_cast<const u32x4*>(patch_q + (32 + row) * SPQ + cc * 16);
-                        if (m_base + row < M) {
-                            unsigned short* dst = Ch + (size_t)(m_base + row) * (2 * Dm) + (size_t)which * Dm + hcol + cc * 8;
+                        if (INT || m_base + row < M) {
+                            unsigned short* dst = INT ? int_dst + (size_t)(32 * ib + 8 * k) * (size_t)(2 * Dm)
+                                                      : Ch + (size_t)(m_base + row) * (2 * Dm) + (size_t)which * Dm + hcol + cc * 8;
                             *reinterpret_cast<u32x4*>(dst) = vh;
                             *reinterpret_cast<u32x4*>(dst + c_plane) = vl;
                         }
@@ -513,6 +521,9 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
                     __builtin_amdgcn_wave_barrier();
                 }
             }
+            };
+            if (staged_q && em0 + (wm + 1) * (TM * 16) <= M) emit(std::true_type{});      // wave-uniform: em0, wm and which live in SGPRs
+            else emit(std::false_type{});
             }
         } else if constexpr (OUT == 0) {
             // fp32 (+ residual) output through a per-wave LDS transpose, one 32 x 32 block (2 x 2 accumulator tiles) at a time.  Patch:
@@ -727,43 +738,45 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
             }
 #pragma unroll
             for (int j = 0; j < TN; ++j) asm volatile("" :: "v"(bvs[j]));              // waited for HERE, not inside the block loop
+            // INT (interior): every row of the wave is below M, its 64 columns are below N and staged -- one wave-uniform test per item
+            // instead of a row test and a column test per cell (exec-mask ladders, 32 cells per wave and item), and the patch cells are
+            // compile-time offsets from ONE per-lane address (row r, column quad kq): immediates of the ds_write.  The values go through the
+            // same fma, activation and split on both paths.
+            auto emit = [&](auto interior_c) {
+            constexpr bool INT = decltype(interior_c)::value;
+            unsigned char* const lane_cell = patch + r * SP + kq * 8;
+            // 16-byte chunk lane & 15 of row (lane >> 4) of the wave's first 32-row block, dense output
+            unsigned short* const int_dst = !INT ? nullptr : Ch + (size_t)(em0 + wm * TM * 16 + (lane >> 4)) * (2 * (size_t)N) + ((size_t)en0 + (size_t)wn * 64) * 2 + (lane & 15) * 8;
             // 32-row blocks of two M16 tiles (patch row 16 s + r)
 #pragma unroll
             for (int ib = 0; ib < TM / 2; ++ib) {
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
-                const int i = 2 * ib + s, prow = 16 * s + r;
+                const int i = 2 * ib + s;
                 const int m = em0 + (wm * TM + i) * 16 + r;
-                if (m >= M) continue;
+                if (!INT && m >= M) continue;
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
                     {
                         const int c = 16 * j + 4 * kq;               // column inside the wave's 64
                         const int n = en0 + wn * 64 + c;
-                        if (n >= N) continue;                    // N % 4 == 0 is required by the launcher
+                        if (!INT && n >= N) continue;            // N % 4 == 0 is required by the launcher
                         const f32x4 bv = bvs[j];
                         f32x4 val;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) val[e] = fmaf(acc[j][i][e], out_scale, bv[e]);
                         if (EPI == EPI_GELU) val = gelu_erf16(val);
                         if (EPI == EPI_GELU_TANH) val = gelu_tanh16(val);
-                        if (EPI == EPI_SQRELU)   // tranception/activations.py:79-84
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) { const float t = fmaxf(val[e], 0.0f); val[e] = t * t; }
-                        if (EPI == EPI_RELU)
+                        if (EPI == EPI_SQRELU || EPI == EPI_RELU)   // squared ReLU (tranception/activations.py:79-84): the split squares it
 #pragma unroll
                         for (int e = 0; e < 4; ++e) val[e] = fmaxf(val[e], 0.0f);
                         {
                             h4 hi, lo;
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                _Float16 a, b;
-                                split_act(val[e], a, b);
-                                hi[e] = a;
-                                lo[e] = b;
-                            }
-                            if (staged) {
-                                unsigned char* cell = patch + prow * SP + (c >> 5) * 128 + (c & 31) * 2;
+                            if (EPI == EPI_SQRELU) split_act4_prod(val, val, hi, lo);
+                            else split_act4(val, hi, lo);
+                            if (INT || staged) {
+                                // row 16 s + r, byte (c >> 5) * 128 + (c & 31) * 2 of the row with c = 16 j + 4 kq
+                                unsigned char* cell = lane_cell + (16 * s) * SP + (j >> 1) * 128 + (j & 1) * 32;
                                 lds_put(cell, hi);
                                 lds_put(cell + 64, lo);
                             } else {
@@ -775,7 +788,7 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
                     }
                 }
                 }
-                if (staged) {
+                if (INT || staged) {
                     // K-interleaved output: the wave's 64 columns are two 32-column groups = 2 x (64 B hi | 64 B lo) = 256
                     // contiguous bytes per row: 16 lanes write one row
                     __builtin_amdgcn_wave_barrier();
@@ -786,7 +799,9 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
                         const int q = lane + 64 * k;                 // 16-byte chunk: row q/16, chunk q%16 of the 256-byte run
                         const int row = q >> 4, cc = q & 15;
                         const u32x4 v = *reinterpret_cast<const u32x4*>(patch + row * SP + cc * 16);
-                        if (m_base + row < M) {
+                        if (INT && !xm.o_ld) {      // one 64-bit row address per lane and item; the rows of the item are uniform steps from it
+                            *reinterpret_cast<u32x4*>(int_dst + (size_t)(32 * ib + 4 * k) * (2 * (size_t)N)) = v;
+                        } else if (INT || m_base + row < M) {
                             if (xm.o_ld)      // scatter (XMap): the wave's 64 columns are one (n / 64) block of the batch's output columns
                                 *reinterpret_cast<u32x4*>(Ch + ((size_t)(m_base + row) + (ncol0 >> 6) * (size_t)xm.o_rows_per_n64) * (2 * (size_t)xm.o_ld) +
                                                           (size_t)eb * (size_t)xm.o_col_per_batch * 2 + cc * 8) = v;
@@ -797,6 +812,14 @@ __global__ __launch_bounds__(XNT, 2) void gemm16x_kernel(
                     __builtin_amdgcn_wave_barrier();
                 }
             }
+            };
+            // wave-uniform: em0 and wm live in SGPRs.  Full items only: the half-height items are the launch's tail, at most one per workgroup
+            bool interior = false;
+            if constexpr (TM == TMX) {
+                interior = staged && em0 + (wm + 1) * (TM * 16) <= M;
+                if (interior) emit(std::true_type{});
+            }
+            if (!interior) emit(std::false_type{});
             }
         }
         return more;
