@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define PGMI_ABI_VERSION 5
+#define PGMI_ABI_VERSION 6
 
 /* error codes */
 #define PGMI_OK 0
@@ -833,6 +833,63 @@ int pgmi_mpnn_graph(pgmi_mpnn* m, int32_t* E_idx, float* E);
 int pgmi_mpnn_encoder(pgmi_mpnn* m, float* h_V, float* h_E);
 int pgmi_mpnn_log_probs(pgmi_mpnn* m, const uint8_t* S, const int32_t* rank, int B, float* out);
 int pgmi_mpnn_scores(pgmi_mpnn* m, const uint8_t* S, const int32_t* rank, int B, double* out);
+
+/* ---- S2F (ESM2 residue rows through a GVP-GNN on the C-alpha radius graph; its own handle and config, fp32) -----------------------
+ * Replaces FusionNetwork / GVPGNN.forward and ResidueTypePrediction.inference (proteingym/baselines/S3F/s3f/{model,gvp,gvp_layer,
+ * task}.py) as script/evaluate.py runs them: one forward per distinct set of masked positions.  The graph and W_e depend on the
+ * structure only and are computed once by pgmi_s2f_set_structure, with every layer's edge share of the first message GVP.  DESIGN.md
+ * 4.6n has the restatement and the factorisation.  S3F's surface branch is not computed.
+ *
+ * Weight blob: fp32, each tensor flattened row-major; a GVP is wh.weight, ws.weight, ws.bias, then (with vector outputs) wv.weight,
+ * wsv.weight, wsv.bias:
+ *   residue_embdding.weight [D, D]; W_v.0.scalar_norm.{weight, bias} [D]; W_v.1.ws.{weight [256, D], bias};
+ *   W_e.0.scalar_norm.{weight, bias} [16]; W_e.1 = GVP (16, 1) -> (64, 1), h = 1;
+ *   layers.{l}: conv.message_func.0 = GVP (576, 33) -> (256, 16), h = 33; .1, .2 = GVP (256, 16) -> (256, 16), h = 16;
+ *     norm.0.scalar_norm.{weight, bias}, norm.1.scalar_norm.{weight, bias} [256];
+ *     ff_func.0 = GVP (256, 16) -> (1024, 32), h = 32; ff_func.1 = GVP (1024, 32) -> (256, 16), h = 32;
+ *   W_out.0.scalar_norm.{weight, bias} [256]; W_out.1 = GVP (256, 16) -> (256, 0), h = 16; linear.{weight [20, 256], bias [20]}
+ * The 20 letters are in the order "GASPVTCILNDQKEMHFRYW".
+ * Limits: node (256, 16), edge (64, 1), 16 RBFs, vector gate, activations (relu, none); node_in a multiple of 32; at most 8 layers;
+ * L <= 8192 (pgmi_s2f_set_logprobs: L + 2 tokens inside the ESM2 model's workspace, no windows: the caller cuts the window). */
+typedef struct pgmi_s2f_config {
+    int32_t abi_version;                          /* = PGMI_ABI_VERSION */
+    int32_t node_in;                              /* D: 1280 for ESM-2-650M */
+    int32_t node_s, node_v, edge_s, edge_v, rbf;  /* = 256, 16, 64, 1, 16 */
+    int32_t layers;                               /* 5 */
+    int32_t max_neighbors;                        /* radius_graph's max_num_neighbors (32) */
+    float radius;                                 /* 10.0 */
+    float plddt_threshold;                        /* 70.0: rows with a smaller pLDDT take the ESM logits */
+} pgmi_s2f_config;
+typedef struct pgmi_s2f pgmi_s2f;
+/* pgmi_s2f_weight_count: size of the blob above; -1 for a config the library refuses (pgmi_last_error).
+ * pgmi_s2f_create: esm (nullable) is an ESM2 model of width node_in; the handle borrows it and its stream (destroy the handle first)
+ *   and runs on its device.  Without one the handle has its own stream on `device` and serves pgmi_s2f_gvp_forward only.
+ * pgmi_s2f_profile_model: the handle's profiling view (owned by the handle).  Classes: PGMI_K_EMBED = the structure pass,
+ *   PGMI_K_GEMM_QKV = the input Linears and the per-node tables of the first message GVP, PGMI_K_ATTENTION = the per-edge row
+ *   kernels (gather + norms, the GVPs' vector halves), PGMI_K_GEMM_OUT = the two per-edge ws GEMMs, PGMI_K_LAYERNORM = aggregation +
+ *   tuple LayerNorm, PGMI_K_GEMM_FC1 / _FC2 = the feed-forward ws GEMMs, PGMI_K_KEPT_ROWS = the feed-forward GVPs' vector halves,
+ *   PGMI_K_HEAD = W_out, the 20-way Linear and the log-softmax.  The ESM2 forward of pgmi_s2f_set_logprobs is timed on the ESM2
+ *   model's own view.
+ * pgmi_s2f_set_structure: pos f32 [L][3] (C-alpha), plddt f32 [L].  Edges (j -> i): per centre i the j in ascending index with
+ *   squared distance < radius^2, self included, the first max_neighbors + 1 kept, then the self edge dropped; sorted by (i, j).
+ * pgmi_s2f_graph (test view): n_edges; src, dst i32 [E]; e_s f32 [E][64], e_v f32 [E][3] (W_e's output); each nullable; E <= 33 L.
+ * pgmi_s2f_gvp_forward: node_feat f32 [B][L][D], seq_logits f32 [B][L][20] -> lp f32 [B][L][20] (the 20-way log-softmax; low-pLDDT
+ *   rows from seq_logits); node_s f32 [B][L][256] and node_v f32 [B][L][16][3] (nullable): the node state after the last layer.
+ * pgmi_s2f_set_logprobs: the hot path.  wt_tokens i32 [T = L + 2] (<cls>, residues, <eos>), aa_cols i32 [20] (the token id of each
+ *   of the 20 letters), position sets as CSR (set_off [n_sets + 1], set_pos: residue indices 0 .. L - 1, ascending inside a set).
+ *   One ESM2 forward per set with the set's residues at <mask>, its emb_layer_norm_after rows through the GNN;
+ *   out f32 [n_entries][20] = the row of (set, position); full (nullable) f32 [n_sets][L][20].  A set's bits do not depend on the
+ *   other sets of the call or on the chunking.
+ * pgmi_set_option("s2f_max_rows", n): rows per chunk, a masked copy costing max(E, L + 2) (0: 262144; test hook, bit-neutral). */
+int64_t pgmi_s2f_weight_count(const pgmi_s2f_config* cfg);
+int pgmi_s2f_create(const pgmi_s2f_config* cfg, const float* weights, int64_t n_weights, pgmi_model* esm, int device, pgmi_s2f** out);
+void pgmi_s2f_destroy(pgmi_s2f* m);
+pgmi_model* pgmi_s2f_profile_model(pgmi_s2f* m);
+int pgmi_s2f_set_structure(pgmi_s2f* m, const float* pos, const float* plddt, int L);
+int pgmi_s2f_graph(pgmi_s2f* m, int32_t* n_edges, int32_t* src, int32_t* dst, float* e_s, float* e_v);
+int pgmi_s2f_gvp_forward(pgmi_s2f* m, const float* node_feat, const float* seq_logits, int B, float* lp, float* node_s, float* node_v);
+int pgmi_s2f_set_logprobs(pgmi_s2f* m, const int32_t* wt_tokens, int T, const int32_t* aa_cols, const int32_t* set_off,
+                          const int32_t* set_pos, int n_sets, float* out, float* full);
 
 /* ---- UniRep (the 1900-unit multiplicative LSTM; its own handle and config, precision f16x3 or fp32) ---------------------------------
  * Replaces babbler1900's graph (proteingym/baselines/unirep/unirep.py:318-408: embedding, mLSTMCell1900.call :81-132 under

@@ -11,7 +11,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libpgmi.so")
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 ARCH_ESM1B, ARCH_ESM2, ARCH_TRANCEPTION = 1, 2, 3
 ARCH_PROGEN2 = 5
 ARCH_GPT = 6
@@ -145,6 +145,14 @@ SIGNATURES = [
     ("pgmi_mpnn_encoder", C.c_int, [C.c_void_p, _f32p, _f32p]),
     ("pgmi_mpnn_log_probs", C.c_int, [C.c_void_p, _u8p, _i32p, C.c_int, _f32p]),
     ("pgmi_mpnn_scores", C.c_int, [C.c_void_p, _u8p, _i32p, C.c_int, _f64p]),
+    ("pgmi_s2f_weight_count", C.c_int64, [C.c_void_p]),
+    ("pgmi_s2f_create", C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    ("pgmi_s2f_destroy", None, [C.c_void_p]),
+    ("pgmi_s2f_profile_model", C.c_void_p, [C.c_void_p]),
+    ("pgmi_s2f_set_structure", C.c_int, [C.c_void_p, _f32p, _f32p, C.c_int]),
+    ("pgmi_s2f_graph", C.c_int, [C.c_void_p, _i32p, _i32p, _i32p, _f32p, _f32p]),
+    ("pgmi_s2f_gvp_forward", C.c_int, [C.c_void_p, _f32p, _f32p, C.c_int, _f32p, _f32p, _f32p]),
+    ("pgmi_s2f_set_logprobs", C.c_int, [C.c_void_p, _i32p, C.c_int, _i32p, _i32p, _i32p, C.c_int, _f32p, _f32p]),
     ("pgmi_unirep_weight_count", C.c_int64, [C.c_void_p]),
     ("pgmi_unirep_model_create", C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     ("pgmi_unirep_destroy", None, [C.c_void_p]),

@@ -271,6 +271,24 @@ void launch_mpnn_head(const float* h, const float* W, const float* bias, const u
 void launch_mpnn_score(const float* nll, const float* mask, int B, int L, double* out, hipStream_t s);
 int mpnn_set_option(const char* name, long long value);   // api_mpnn.hip: "mpnn_max_rows"
 
+// S2F (s2f.hip; operands and shapes at the kernels)
+struct S2fMsgWeights {    // device pointers of a layer's message GVPs: the first one's vector half, then the second and the third
+    const float *wv0, *wsv0, *bsv0;
+    const float *wh1, *ws1, *bs1, *wv1, *wsv1, *bsv1;
+    const float *wh2, *ws2, *bs2, *wv2, *wsv2, *bsv2;
+    int ldw;              // row stride of ws1 / ws2
+};
+int launch_s2f_message(const float* P, const float* VT, const float* Es, const float* ev, const float* whe, const float* Wnt,
+                       const S2fMsgWeights& w, const int32_t* src, const int32_t* off, int L, int64_t nodes, float* ds, float* dv, hipStream_t s);
+int launch_s2f_gvp_mid(const float* spre, const float* vh, const float* wv, const float* gpre, const float* nwh, int so,
+                       int vo, int h, int h2, int relu, int lda, int64_t rows, float* outA, float* outV, hipStream_t s);
+int launch_s2f_node_ln(const float* rs, const float* rv, const float* ds, const float* dv, const float* lnw, const float* lnb, const float* wh, int h, int vn, int lda, int64_t rows, float* os, float* ov,
+                       float* outA, float* outV, hipStream_t s);
+void launch_s2f_head(const float* x, const float* W, const float* bias, const float* seq, const float* plddt, float thr, int L, int64_t rows,
+                     float* lp, hipStream_t s);
+void launch_s2f_pick_logits(const float* lp, const int32_t* cols, int L, int T, int V, int64_t rows, float* out, hipStream_t s);
+int s2f_set_option(const char* name, long long value);    // api_s2f.hip: "s2f_max_rows"
+
 // ---- mlstm.hip (UniRep's mLSTM step around the two GEMMs; the kernels are described there) -------------------------------------
 // m = Tmx[tok[row * tok_stride]] * g1 [rows][Hp] -> the second product's operand: split rows m16, or fp32 m32 (exactly one)
 void launch_mlstm_m(const float* g1, const float* Tmx, const int32_t* tok, int tok_stride, int rows, int Hp, unsigned short* m16,

@@ -1,0 +1,455 @@
+// S2F kernels (include/pgmi.h, S2F section): the GVP-GNN of proteingym/baselines/S3F over ESM2's residue rows.
+// Scalar width 256, 16 vector channels in the node state; fp32 only.  Every kernel works row by row (an edge of a masked copy, or
+// a node of a masked copy) and reads nothing of another copy, so a row's bits do not depend on what else is in the launch; the dense
+// Linears between them are launch_gemm_f32 (api_s2f.hip), whose per-element sum order does not depend on the row count either.
+//
+//   s2f_message_kernel    the three message GVPs of a layer and the mean at the centre, one block per (copy, node), the node's edge
+//                         rows in LDS throughout.  The first GVP is linear in [s_j | e_s | s_i] and [v_j | e_v | v_i] before the norm,
+//                         so its per-node products (P = s [Wj | Wi]^T, VT = [wh_j v | wh_i v]) come from N-row launches and the
+//                         edge's share (Es = We e_s + b, wh_e e_v) from the structure pass; a row gathers the three, takes the 33
+//                         channel norms and adds Wn |vh|.  The two 272 -> 256 GVPs run on the fp32 MFMA with their weights read
+//                         from L2; no per-edge activation goes to HBM.
+//   s2f_gvp_mid_kernel    the vector half of any GVP after its ws GEMM and its gate GEMM (wsv s + b on s before the scalar activation):
+//                         v = wv vh * sigmoid(gate), s = relu(s) or s; then the NEXT GVP's wh v and channel norms, written as that
+//                         GVP's GEMM operand row [s | |vh| | 0 pad].
+//   s2f_node_ln_kernel    (s, v) + dh -> tuple LayerNorm; dh is the mean message or the feed-forward output; then the next GVP's
+//                         wh v / norms as above.
+//   s2f_head_kernel       relu, Linear(256 -> 20), the ESM logits on low-pLDDT rows, log-softmax over 20.
+//   s2f_pick_logits_kernel  the 20 amino-acid columns of ESM2's log-probability rows of the L residues.
+#include <algorithm>
+
+#include "common.h"
+
+namespace pgmi {
+
+constexpr int SS = 256;            // node scalar width
+constexpr int SV = 16;             // node vector channels
+constexpr int SH0 = 33;            // hidden vector channels of the first message GVP (2 * 16 + 1)
+
+__device__ __forceinline__ float s2f_wave_sum(float x) {
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+    return x;
+}
+__device__ __forceinline__ float s2f_vnorm(const float* v3) {
+    return sqrtf(fmaxf(v3[0] * v3[0] + v3[1] * v3[1] + v3[2] * v3[2], 1e-8f));
+}
+
+// ---- fused message kernel ------------------------------------------------------------------------------------------------------
+constexpr int FE_M = 32;             // edge rows of a tile: two 16-row MFMA tiles
+constexpr int FE_K = SS + SV;        // 272 operand columns of the second and third message GVP: [s | |vh|]
+constexpr int FE_LDA = FE_K + 4;     // LDS row stride of the operand tile
+constexpr int FE_LDV = SH0 * 3 + 1;  // LDS row stride of the vector tile
+
+constexpr int FE_LDN = SH0 + 3;      // LDS row stride of the first GVP's channel norms
+constexpr int FE_SCR = 4 * FE_M * SV; // scratch floats: the norms [FE_M][FE_LDN] of the gather, the gate partials [4][FE_M][16] after it
+
+// tile rows -> As [FE_M][FE_LDA] = first message GVP's ws output: P_j + Es + P_i + Wn |vh|, and Vh [FE_M][FE_LDV] = its vh (33 channels).
+// Row `row` of the tile is edge min(c0 + row, e1 - 1): rows past the node's edges repeat the last one and are never summed.
+// The scalar part runs one column per thread over the tile's rows, the column of Wn in registers.
+__device__ __noinline__ void fe_gather(float* As, float* Vh, float* vn, int32_t* rowe, const float* __restrict__ P, const float* __restrict__ VT,
+                                          const float* __restrict__ Es, const float* __restrict__ ev, const float* __restrict__ whe,
+                                          const float* __restrict__ Wnt, const int32_t* __restrict__ src, int64_t nb, int i, int c0, int e1) {
+    const int tid = threadIdx.x;
+    const int64_t ni = nb + i;
+    if (tid < FE_M) {                                           // rowe[row] = the row's edge, rowe[FE_M + row] = its source node
+        const int e = min(c0 + tid, e1 - 1);
+        rowe[tid] = e;
+        rowe[FE_M + tid] = src[e];
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int idx = tid; idx < FE_M * SH0 * 3; idx += 256) {
+        const int row = idx / (SH0 * 3), t = idx - row * (SH0 * 3), h = t / 3, d = t - 3 * h;
+        const int e = rowe[row];
+        float x = whe[h] * ev[(size_t)e * 3 + d];
+        if (VT) x += VT[(nb + rowe[FE_M + row]) * (2 * SH0 * 3) + t] + VT[ni * (2 * SH0 * 3) + SH0 * 3 + t];
+        Vh[row * FE_LDV + t] = x;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < FE_M * SH0; idx += 256) {
+        const int row = idx / SH0, h = idx - row * SH0;
+        vn[row * FE_LDN + h] = s2f_vnorm(Vh + row * FE_LDV + h * 3);
+    }
+    __syncthreads();
+    float wn[SH0];
+#pragma unroll
+    for (int h = 0; h < SH0; ++h) wn[h] = Wnt[h * SS + tid];
+    const float pi = P[ni * 512 + SS + tid];
+#pragma unroll 4
+    for (int row = 0; row < FE_M; ++row) {
+        const float a = P[(nb + rowe[FE_M + row]) * 512 + tid] + Es[(size_t)rowe[row] * SS + tid] + pi;
+        float n = 0.0f;
+#pragma unroll
+        for (int h = 0; h < SH0; ++h) n = fmaf(wn[h], vn[row * FE_LDN + h], n);
+        As[row * FE_LDA + tid] = a + n;
+    }
+    __syncthreads();
+}
+
+// The vector half of one GVP on the tile.  In: As[row][0 .. 256) = ws [s | |vh|] + b, Vh[row] = vh [h][3].
+// gate = sigmoid(wsv s + bsv) on s before the activation; v = wv vh * gate; s = relu(s) or s, in place.  With nwh [16][16], the next
+// GVP's wh: Vh[row] = nwh v and As[row][256 .. 272) = its channel norms, so As[row] is that GVP's operand row.  Without: Vh[row] = v.
+// The gate is a [FE_M][256] x [256][16] product on the MFMA: wave w takes columns [64 w, 64 w + 64) and the four partial sums are
+// added in wave order.  Everything else is FE_M x 48 outputs, six per thread.
+__device__ __noinline__ void fe_mid(float* As, float* Vh, float* gp, float* wl, const float* __restrict__ wv, const float* __restrict__ wsv,
+                                       const float* __restrict__ bsv, const float* __restrict__ nwh, int h, bool relu) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, g = lane >> 4;
+    float *wvl = wl, *nwl = wl + SV * SH0, *bl = nwl + SV * SV;  // wv [16][h], nwh [16][16] and bsv [16] in LDS for the loops below
+    for (int t = tid; t < SV * h; t += 256) wvl[t] = wv[t];
+    if (nwh) nwl[tid] = nwh[tid];
+    if (tid < SV) bl[tid] = bsv[tid];
+    {
+        f32x4 gacc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int c = 64 * wave + 16 * q + 4 * g;
+            const f32x4 bf = *reinterpret_cast<const f32x4*>(wsv + r * SS + c);
+            const f32x4 a0 = *reinterpret_cast<const f32x4*>(As + r * FE_LDA + c);
+            const f32x4 a1 = *reinterpret_cast<const f32x4*>(As + (16 + r) * FE_LDA + c);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                gacc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[e], bf[e], gacc[0], 0, 0, 0);
+                gacc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[e], bf[e], gacc[1], 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) gp[(wave * FE_M + rt * 16 + 4 * g + v) * SV + r] = gacc[rt][v];
+    }
+    __syncthreads();
+    float out[6];
+    int at[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const int idx = tid + 256 * k, row = idx / (SV * 3), t = idx - row * (SV * 3), o = t / 3, d = t - 3 * o;
+        at[k] = row * FE_LDV + t;
+        const float gate = ((gp[row * SV + o] + gp[(FE_M + row) * SV + o]) + gp[(2 * FE_M + row) * SV + o]) + gp[(3 * FE_M + row) * SV + o] + bl[o];
+        float acc = 0.0f;
+#pragma unroll 4
+        for (int q = 0; q < h; ++q) acc = fmaf(wvl[o * h + q], Vh[row * FE_LDV + q * 3 + d], acc);
+        out[k] = acc / (1.0f + expf(-gate));
+    }
+    if (relu) {
+#pragma unroll 4
+        for (int row = 0; row < FE_M; ++row) As[row * FE_LDA + tid] = fmaxf(As[row * FE_LDA + tid], 0.0f);
+    }
+    __syncthreads();                                            // every vh is read
+#pragma unroll
+    for (int k = 0; k < 6; ++k) Vh[at[k]] = out[k];
+    __syncthreads();
+    if (!nwh) return;                                           // block-uniform
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const int idx = tid + 256 * k, row = idx / (SV * 3), t = idx - row * (SV * 3), o = t / 3, d = t - 3 * o;
+        float acc = 0.0f;
+#pragma unroll 4
+        for (int q = 0; q < SV; ++q) acc = fmaf(nwl[o * SV + q], Vh[row * FE_LDV + q * 3 + d], acc);
+        out[k] = acc;
+    }
+    __syncthreads();                                            // every v is read
+#pragma unroll
+    for (int k = 0; k < 6; ++k) Vh[at[k]] = out[k];
+    __syncthreads();
+    for (int idx = tid; idx < FE_M * SV; idx += 256) {
+        const int row = idx / SV, c = idx - row * SV;
+        As[row * FE_LDA + SS + c] = s2f_vnorm(Vh + row * FE_LDV + c * 3);
+    }
+    __syncthreads();
+}
+
+// As[FE_M][0 .. 256) <- As[FE_M][0 .. 272) W^T + bias on v_mfma_f32_16x16x4_f32; W [256][ldw] in global memory (L2 resident: every
+// block reads the same 0.3 MB).  Wave w owns columns [64 w, 64 w + 64).  Lane (r = lane & 15, g = lane >> 4): k step (q, e) of the
+// MFMA is operand column 16 q + 4 g + e for both operands, so a lane reads its A rows and its W rows as float4.  C layout: column
+// lane & 15, row 4 g + v.
+__device__ __noinline__ void fe_gemm(float* As, const float* __restrict__ W, int ldw, const float* __restrict__ bias) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
+    f32x4 acc[2][4];
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const float* wrow = W + (size_t)(wave * 64 + r) * ldw + 4 * g;
+    const float* arow = As + r * FE_LDA + 4 * g;
+    f32x4 a[2], bf[4];
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) bf[ct] = *reinterpret_cast<const f32x4*>(wrow + (size_t)ct * 16 * ldw);
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt) a[rt] = *reinterpret_cast<const f32x4*>(arow + rt * 16 * FE_LDA);
+#pragma unroll 1
+    for (int q = 0; q < FE_K / 16; ++q) {
+        const int qn = min(q + 1, FE_K / 16 - 1);               // the next step's operands load under this step's MFMAs
+        f32x4 an[2], bn[4];
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct) bn[ct] = *reinterpret_cast<const f32x4*>(wrow + (size_t)ct * 16 * ldw + 16 * qn);
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt) an[rt] = *reinterpret_cast<const f32x4*>(arow + rt * 16 * FE_LDA + 16 * qn);
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                for (int ct = 0; ct < 4; ++ct)
+                    acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[rt][e], bf[ct][e], acc[rt][ct], 0, 0, 0);
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct) bf[ct] = bn[ct];
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt) a[rt] = an[rt];
+    }
+    __syncthreads();                                            // every wave has read the operand tile
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) {
+        const int col = wave * 64 + ct * 16 + r;
+        const float bc = bias[col];
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) As[(rt * 16 + 4 * g + v) * FE_LDA + col] = acc[rt][ct][v] + bc;
+    }
+    __syncthreads();
+}
+
+// The three message GVPs of one layer and the mean at the centre, one block per (masked copy b, node i); grid = B L.  The node's
+// edges [off[i], off[i + 1]) go through in tiles of FE_M rows that live in LDS from the gather to the sum; the sum runs over the rows
+// in ascending edge order, one column per thread, so nothing of another node or copy enters a row's bits and no atomics are needed.
+// P [B L][512] = (Pj | Pi); VT [B L][66][3] = (wh_j v | wh_i v), null when v = 0; Es [E][256]; ev [E][3]; whe [33]; Wnt [33][256].
+// ds [B L][256], dv [B L][16][3] = the mean message, zero for a node without edges.
+__global__ __launch_bounds__(256, 2) void s2f_message_kernel(const float* __restrict__ P, const float* __restrict__ VT,
+                                                          const float* __restrict__ Es, const float* __restrict__ ev,
+                                                          const float* __restrict__ whe, const float* __restrict__ Wnt, const S2fMsgWeights w,
+                                                          const int32_t* __restrict__ src, const int32_t* __restrict__ off, int L,
+                                                          float* __restrict__ ds, float* __restrict__ dv) {
+    __shared__ __attribute__((aligned(16))) float As[FE_M * FE_LDA];
+    __shared__ float Vh[FE_M * FE_LDV];
+    __shared__ float scr[FE_SCR];
+    __shared__ float wl[SV * SH0 + SV * SV + SV];
+    __shared__ int32_t rowe[2 * FE_M];
+    const int tid = threadIdx.x;
+    const int64_t node = blockIdx.x;
+    const int i = (int)(node % L);
+    const int64_t nb = node - i;                                // b L
+    const int e0 = off[i], e1 = off[i + 1];
+    float sum_s = 0.0f, sum_v = 0.0f;
+#pragma unroll 1
+    for (int c0 = e0; c0 < e1; c0 += FE_M) {                    // block-uniform: every barrier below is reached by all threads
+        fe_gather(As, Vh, scr, rowe, P, VT, Es, ev, whe, Wnt, src, nb, i, c0, e1);
+        fe_mid(As, Vh, scr, wl, w.wv0, w.wsv0, w.bsv0, w.wh1, SH0, true);
+        fe_gemm(As, w.ws1, w.ldw, w.bs1);
+        fe_mid(As, Vh, scr, wl, w.wv1, w.wsv1, w.bsv1, w.wh2, SV, true);
+        fe_gemm(As, w.ws2, w.ldw, w.bs2);
+        fe_mid(As, Vh, scr, wl, w.wv2, w.wsv2, w.bsv2, nullptr, SV, false);
+        const int n = min(FE_M, e1 - c0);
+        for (int row = 0; row < n; ++row) {
+            sum_s += As[row * FE_LDA + tid];
+            if (tid < SV * 3) sum_v += Vh[row * FE_LDV + tid];
+        }
+        __syncthreads();                                        // the next tile overwrites As and Vh
+    }
+    const float cnt = (float)max(e1 - e0, 1);
+    ds[node * SS + tid] = sum_s / cnt;
+    if (tid < SV * 3) dv[node * (SV * 3) + tid] = sum_v / cnt;
+}
+
+// One GVP's vector half on `rows` rows.  spre [rows][so] = ws [s | |vh|] + b; vh [rows][h][3]; wv [vo][h]; gpre [rows][vo] = wsv spre +
+// b, the gate before its sigmoid (a GEMM of its own on spre: api_s2f.hip).
+// so in {256, 1024}, vo <= 32, h <= 33.  With nwh [h2][vo] (h2 <= 32): outA [rows][lda] = [act(s) | |nwh v| | 0], outV [rows][h2][3] =
+// nwh v.  Without: outV [rows][vo][3] = v, and outA (nullable) [rows][lda] = act(s).
+__global__ __launch_bounds__(256) void s2f_gvp_mid_kernel(const float* __restrict__ spre, const float* __restrict__ vh,
+                                                          const float* __restrict__ wv, const float* __restrict__ gpre,
+                                                          const float* __restrict__ nwh, int so, int vo, int h,
+                                                          int h2, int relu, int lda, int64_t rows, float* __restrict__ outA,
+                                                          float* __restrict__ outV) {
+    __shared__ float vhs[4][SH0 * 3 + 1];
+    __shared__ float vs[4][32 * 3];
+    __shared__ float gs[4][32];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t r0 = (int64_t)blockIdx.x * 4 + wave;
+    const bool live = r0 < rows;
+    const int64_t r = live ? r0 : rows - 1;
+    const int nk = so >> 6;                       // 4 or 16 columns per lane
+    float s[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) s[k] = k < nk ? spre[r * so + lane + 64 * k] : 0.0f;
+    for (int t = lane; t < h * 3; t += 64) vhs[wave][t] = vh[r * (h * 3) + t];
+    if (lane < vo) gs[wave][lane] = 1.0f / (1.0f + expf(-gpre[r * vo + lane]));
+    __syncthreads();
+    for (int t = lane; t < vo * 3; t += 64) {
+        const int o = t / 3, d = t - 3 * o;
+        float a = 0.0f;
+        for (int q = 0; q < h; ++q) a = fmaf(wv[o * h + q], vhs[wave][q * 3 + d], a);
+        a *= gs[wave][o];
+        vs[wave][t] = a;
+        if (!nwh && live) outV[r * (vo * 3) + t] = a;
+    }
+    if (outA && live) {
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            if (k < nk) outA[r * lda + lane + 64 * k] = relu ? fmaxf(s[k], 0.0f) : s[k];
+    }
+    __syncthreads();
+    if (nwh) {
+        for (int t = lane; t < h2 * 3; t += 64) {
+            const int q = t / 3, d = t - 3 * q;
+            float a = 0.0f;
+            for (int o = 0; o < vo; ++o) a = fmaf(nwh[q * vo + o], vs[wave][o * 3 + d], a);
+            vhs[wave][t] = a;                      // vh of this GVP is dead: every lane passed the barrier above
+            if (live) outV[r * (h2 * 3) + t] = a;
+        }
+    }
+    __syncthreads();
+    if (nwh && live) {
+        for (int c = so + lane; c < lda; c += 64) outA[r * lda + c] = c < so + h2 ? s2f_vnorm(&vhs[wave][(c - so) * 3]) : 0.0f;
+    }
+}
+
+// rows = B * L.  x = (rs, rv) + dh; rv null: zero vectors.  dh (ds [rows][256], dv [rows][16][3]) is the mean message or the
+// feed-forward output; ds null: none.
+// Tuple LayerNorm -> os [rows][256], ov [rows][16][3].  Then with wh [h][16] (h <= 66): outV [rows][h][3] = wh ov, and with vn != 0
+// outA [rows][lda] = [os | |wh ov| | 0].
+__global__ __launch_bounds__(256) void s2f_node_ln_kernel(const float* __restrict__ rs, const float* __restrict__ rv,
+                                                          const float* __restrict__ ds, const float* __restrict__ dv,
+                                                          const float* __restrict__ lnw,
+                                                          const float* __restrict__ lnb, const float* __restrict__ wh, int h, int vn, int lda,
+                                                          int64_t rows, float* __restrict__ os, float* __restrict__ ov,
+                                                          float* __restrict__ outA, float* __restrict__ outV) {
+    __shared__ float vs[4][SV * 3];
+    __shared__ float vhs[4][66 * 3];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t r0 = (int64_t)blockIdx.x * 4 + wave;
+    const bool live = r0 < rows;
+    const int64_t r = live ? r0 : rows - 1;
+    float x[4], xv = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) x[k] = rs[r * SS + lane + 64 * k];
+    if (rv && lane < SV * 3) xv = rv[r * (SV * 3) + lane];
+    if (ds) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) x[k] += ds[r * SS + lane + 64 * k];
+        if (lane < SV * 3) xv += dv[r * (SV * 3) + lane];
+    }
+    const float mean = s2f_wave_sum(x[0] + x[1] + x[2] + x[3]) * (1.0f / SS);
+    float var = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { x[k] -= mean; var += x[k] * x[k]; }
+    const float rstd = 1.0f / sqrtf(s2f_wave_sum(var) * (1.0f / SS) + 1e-5f);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int c = lane + 64 * k;
+        x[k] = x[k] * rstd * lnw[c] + lnb[c];
+        if (live) os[r * SS + c] = x[k];
+        if (outA && live) outA[r * lda + c] = x[k];
+    }
+    if (lane < SV * 3) vs[wave][lane] = xv;
+    __syncthreads();
+    float n2 = 0.0f;
+    if (lane < SV) {
+        const float* p = &vs[wave][lane * 3];
+        n2 = fmaxf(p[0] * p[0] + p[1] * p[1] + p[2] * p[2], 1e-8f);
+    }
+    const float vden = sqrtf(s2f_wave_sum(n2) * (1.0f / SV));
+    __syncthreads();
+    if (lane < SV * 3) {
+        xv = xv / vden;
+        vs[wave][lane] = xv;
+        if (live) ov[r * (SV * 3) + lane] = xv;
+    }
+    __syncthreads();
+    if (h > 0) {
+        for (int t = lane; t < h * 3; t += 64) {
+            const int q = t / 3, d = t - 3 * q;
+            float a = 0.0f;
+#pragma unroll
+            for (int o = 0; o < SV; ++o) a = fmaf(wh[q * SV + o], vs[wave][o * 3 + d], a);
+            vhs[wave][t] = a;
+            if (live) outV[r * (h * 3) + t] = a;
+        }
+    }
+    __syncthreads();
+    if (h > 0 && vn && live) {
+        for (int c = SS + lane; c < lda; c += 64) outA[r * lda + c] = c < SS + h ? s2f_vnorm(&vhs[wave][(c - SS) * 3]) : 0.0f;
+    }
+}
+
+// rows = B * L: logits = W relu(x) + b over 20 letters; rows whose plddt[r % L] < thr read seq [rows][20] instead; log-softmax
+__global__ __launch_bounds__(256) void s2f_head_kernel(const float* __restrict__ x, const float* __restrict__ W, const float* __restrict__ bias,
+                                                       const float* __restrict__ seq, const float* __restrict__ plddt, float thr, int L,
+                                                       int64_t rows, float* __restrict__ lp) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    float hx[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) hx[k] = fmaxf(x[r * SS + lane + 64 * k], 0.0f);
+    float logit = -INFINITY;
+    for (int c = 0; c < 20; ++c) {
+        float p = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) p = fmaf(hx[k], W[c * SS + lane + 64 * k], p);
+        p = s2f_wave_sum(p);
+        if (lane == c) logit = p + bias[c];
+    }
+    if (plddt[r % L] < thr && lane < 20) logit = seq[r * 20 + lane];
+    float mx = logit;
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    const float ex = s2f_wave_sum(lane < 20 ? expf(logit - mx) : 0.0f);
+    if (lane < 20) lp[r * 20 + lane] = logit - mx - logf(ex);
+}
+
+// out [B L][20] = lp [(b T + 1 + i)][cols[c]] of ESM2's [B T][V] rows
+__global__ void s2f_pick_logits_kernel(const float* __restrict__ lp, const int32_t* __restrict__ cols, int L, int T, int V, int64_t n,
+                                       float* __restrict__ out) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const int c = (int)(t % 20);
+    const int64_t r = t / 20, b = r / L;
+    const int i = (int)(r % L);
+    out[t] = lp[(b * T + 1 + i) * V + cols[c]];
+}
+
+// ---- launchers -----------------------------------------------------------------------------------------------------------------
+int launch_s2f_message(const float* P, const float* VT, const float* Es, const float* ev, const float* whe, const float* Wnt,
+                       const S2fMsgWeights& w, const int32_t* src, const int32_t* off, int L, int64_t nodes, float* ds, float* dv, hipStream_t s) {
+    if (w.ldw < FE_K || w.ldw % 4 || L < 1 || nodes % L || nodes > 0x7fffffffLL) {
+        set_error("s2f: message stage ldw=%d L=%d nodes=%lld is not one this kernel runs", w.ldw, L, (long long)nodes);
+        return PGMI_EINVAL;
+    }
+    if (nodes <= 0) return PGMI_OK;
+    hipLaunchKernelGGL(s2f_message_kernel, dim3((unsigned)nodes), dim3(256), 0, s, P, VT, Es, ev, whe, Wnt, w, src, off, L, ds, dv);
+    return PGMI_OK;
+}
+
+int launch_s2f_gvp_mid(const float* spre, const float* vh, const float* wv, const float* gpre, const float* nwh, int so,
+                       int vo, int h, int h2, int relu, int lda, int64_t rows, float* outA, float* outV, hipStream_t s) {
+    if ((so != 256 && so != 1024) || vo < 1 || vo > 32 || h < 1 || h > SH0 || h2 < 0 || h2 > 32 || (nwh && (!outA || lda < so + h2)) ||
+        (outA && lda < so)) {
+        set_error("s2f: GVP shape so=%d vo=%d h=%d h2=%d lda=%d is not one this kernel runs", so, vo, h, h2, lda);
+        return PGMI_EINVAL;
+    }
+    if (rows <= 0) return PGMI_OK;
+    hipLaunchKernelGGL(s2f_gvp_mid_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, spre, vh, wv, gpre, nwh, so, vo, h, h2, relu,
+                       lda, rows, outA, outV);
+    return PGMI_OK;
+}
+
+int launch_s2f_node_ln(const float* rs, const float* rv, const float* ds, const float* dv, const float* lnw, const float* lnb, const float* wh, int h, int vn, int lda, int64_t rows, float* os, float* ov,
+                       float* outA, float* outV, hipStream_t s) {
+    if (h < 0 || h > 66 || (h > 0 && vn && (!outA || lda < SS + h)) || (outA && lda < SS) || rows <= 0) {
+        set_error("s2f: node stage h=%d lda=%d rows=%lld is not one this kernel runs", h, lda, (long long)rows);
+        return PGMI_EINVAL;
+    }
+    hipLaunchKernelGGL(s2f_node_ln_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, rs, rv, ds, dv, lnw, lnb, wh, h,
+                       vn, lda, rows, os, ov, outA, outV);
+    return PGMI_OK;
+}
+
+void launch_s2f_head(const float* x, const float* W, const float* bias, const float* seq, const float* plddt, float thr, int L, int64_t rows,
+                     float* lp, hipStream_t s) {
+    hipLaunchKernelGGL(s2f_head_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, W, bias, seq, plddt, thr, L, rows, lp);
+}
+
+void launch_s2f_pick_logits(const float* lp, const int32_t* cols, int L, int T, int V, int64_t rows, float* out, hipStream_t s) {
+    const int64_t n = rows * 20;
+    hipLaunchKernelGGL(s2f_pick_logits_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, lp, cols, L, T, V, n, out);
+}
+
+}  // namespace pgmi
