@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define PGMI_ABI_VERSION 6
+#define PGMI_ABI_VERSION 7
 
 /* error codes */
 #define PGMI_OK 0
@@ -940,6 +940,60 @@ int pgmi_unirep_sequence_nll(pgmi_unirep* m, const int32_t* tokens, const int64_
 int pgmi_unirep_token_logprobs(pgmi_unirep* m, const int32_t* tokens, int L, float* out);
 int pgmi_op_mlstm_step(pgmi_unirep* m, const float* h_prev, const float* c_prev, const int32_t* tokens, int rows, float* h, float* c,
                        float* z);
+
+/* ---- CARP (the dilated-convolution ByteNet masked LM; its own handle and config, precision f16x3 or fp32) ----------------------------
+ * Replaces the ByteNetLM forward of sequence_models (microsoft/protein-sequence-models) as proteingym/baselines/carp_mif/
+ * compute_fitness.py runs it at batch 1.  DESIGN.md 4.6o has the restatement and the list of readings made without that library.
+ * Tokens: indices into the checkpoint's alphabet (proteingym_amd/carp.py PROTEIN_ALPHABET), no start or stop token.
+ * Block n (dilation 2^(n mod (log2 r + 1))): x + PFF2(GELU(LN3(Conv(GELU(LN2(PFF1(GELU(LN1(x))))))))), LN eps ln_eps, erf-GELU; the
+ * convolution is zero-padded at both ends of every sequence.  Head: last_norm, decoder, log-softmax over all vocab columns.
+ * Weight blob (fp32, what proteingym_amd/carp.py blob_from_state folds and permutes):
+ *   token table [vocab][d_model] = embedding rows through the 1x1 up-embedder, bias included;
+ *   per block: LN1 w, b [d_model]; PFF1 [d_hidden][d_model], bias [d_hidden]; LN2 w, b [d_hidden];
+ *              conv [d_hidden out][kernel_size][d_hidden in], bias [d_hidden]; LN3 w, b [d_hidden]; PFF2 [d_model][d_hidden], bias [d_model];
+ *   last_norm w, b [d_model]; decoder [vocab][d_model], bias [vocab].
+ *
+ * pgmi_carp_weight_count: size of the blob; -1 for a config the library refuses (pgmi_last_error).
+ * pgmi_carp_create / pgmi_carp_destroy: the device-resident model (one HIP stream).
+ * pgmi_carp_profile_model: the handle's profiling view (owned by the handle).  Classes: PGMI_K_EMBED = the token table gather,
+ *   PGMI_K_LAYERNORM = the three LayerNorm + GELU row kernels, PGMI_K_GEMM_FC1 = PFF1, PGMI_K_ATTENTION = the dilated convolution,
+ *   PGMI_K_GEMM_FC2 = PFF2, PGMI_K_HEAD = row gather + last_norm + decoder + log-softmax, PGMI_K_SCORE = the per-sequence sum.
+ * pgmi_carp_token_logprobs: B sequences packed in tokens (lens int32 [B], each >= 1); out f32 [sum lens][vocab].
+ * pgmi_carp_masked_logprobs: one copy of wt_tokens [L] per listed position with that token replaced by mask_id; out f32
+ *   [n_pos][vocab] = row positions[i] of copy i.  The row is gathered before last_norm: the head runs on n_pos rows.
+ * pgmi_carp_sequence_loglik: out f64 [B] = the sum over a sequence's tokens of log p(x_t) from one unmasked forward, fp32 terms
+ *   added in double, left to right.
+ * All three cut their rows into chunks of at most max_rows rows between sequences (a longer sequence runs alone); a sequence's
+ *   bits do not depend on the call's other sequences or on the chunking.  PGMI_EOVERFLOW: an activation left the fp16 range
+ *   (precision f16x3); run in fp32.
+ * pgmi_op_dilated_conv: the block's convolution alone, fp32 in and out (the split of x and W happens inside): x [M][C], W
+ *   [C][taps][C] (the blob's permuted form), bias [C], seg_off int32 [n_seg + 1] ascending from 0 to M; precision f16x3 = the
+ *   implicit-GEMM kernel, fp32 = im2col + the fp32 GEMM.
+ * pgmi_op_ln_gelu: gelu_erf(LayerNorm(x)) per row, x [rows][D]; precision f16x3 = the split operand rebuilt as hi + lo 2^-11. */
+typedef struct pgmi_carp_config {
+    int32_t abi_version;                          /* = PGMI_ABI_VERSION */
+    int32_t d_model, d_hidden, n_layers;          /* D; d_h = D / 2 (slim) or D; blocks */
+    int32_t kernel_size;                          /* 5 */
+    int32_t r;                                    /* the dilation cycle's last value, a power of two (128) */
+    int32_t vocab, mask_id;                       /* rows of the token table; the index of '#' */
+    int32_t precision;                            /* PGMI_PREC_F16X3 or PGMI_PREC_FP32 */
+    int32_t max_rows;                             /* rows per chunk; 0 = 16384 */
+    float ln_eps;                                 /* 1e-5 */
+} pgmi_carp_config;
+typedef struct pgmi_carp pgmi_carp;
+int64_t pgmi_carp_weight_count(const pgmi_carp_config* cfg);
+int pgmi_carp_create(const pgmi_carp_config* cfg, const float* weights, int64_t n_weights, int device, pgmi_carp** out);
+void pgmi_carp_destroy(pgmi_carp* m);
+pgmi_model* pgmi_carp_profile_model(pgmi_carp* m);
+int pgmi_carp_token_logprobs(pgmi_carp* m, const int32_t* tokens, const int32_t* lens, int B, float* out);
+int pgmi_carp_masked_logprobs(pgmi_carp* m, const int32_t* wt_tokens, int L, const int32_t* positions, int n_pos, float* out);
+int pgmi_carp_sequence_loglik(pgmi_carp* m, const int32_t* tokens, const int32_t* lens, int B, double* out);
+int pgmi_op_dilated_conv(int device, int precision, const float* x, const float* W, const float* bias, const int32_t* seg_off, int n_seg,
+                         int C, int taps, int dilation, float* out);
+int pgmi_op_ln_gelu(int device, int precision, const float* x, const float* w, const float* b, int rows, int D, float eps, float* y);
+/* Times the f16x3 convolution kernel alone: seeded operands on the device, n_seg equal segments (M % n_seg == 0), two warm-up launches,
+ * then the mean milliseconds of `iters` launches between two events. */
+int pgmi_bench_dilated_conv(int device, int M, int n_seg, int C, int taps, int dilation, int iters, double* ms_per_launch);
 
 /* ---- MSA Transformer (arch PGMI_ARCH_MSA; vocab 33, head_dim 64, precision f16x3) --------------------
  * Replaces MSATransformer.forward (proteingym/baselines/esm/esm/model/msa_transformer.py:146-205; tied

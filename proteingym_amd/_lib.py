@@ -11,7 +11,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libpgmi.so")
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 ARCH_ESM1B, ARCH_ESM2, ARCH_TRANCEPTION = 1, 2, 3
 ARCH_PROGEN2 = 5
 ARCH_GPT = 6
@@ -161,6 +161,16 @@ SIGNATURES = [
     ("pgmi_unirep_sequence_nll", C.c_int, [C.c_void_p, _i32p, _i64p, C.c_int64, C.c_int, _f64p, _i64p]),
     ("pgmi_unirep_token_logprobs", C.c_int, [C.c_void_p, _i32p, C.c_int, _f32p]),
     ("pgmi_op_mlstm_step", C.c_int, [C.c_void_p, _f32p, _f32p, _i32p, C.c_int, _f32p, _f32p, _f32p]),
+    ("pgmi_carp_weight_count", C.c_int64, [C.c_void_p]),
+    ("pgmi_carp_create", C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
+    ("pgmi_carp_destroy", None, [C.c_void_p]),
+    ("pgmi_carp_profile_model", C.c_void_p, [C.c_void_p]),
+    ("pgmi_carp_token_logprobs", C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _f32p]),
+    ("pgmi_carp_masked_logprobs", C.c_int, [C.c_void_p, _i32p, C.c_int, _i32p, C.c_int, _f32p]),
+    ("pgmi_carp_sequence_loglik", C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _f64p]),
+    ("pgmi_op_dilated_conv", C.c_int, [C.c_int, C.c_int, _f32p, _f32p, _f32p, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),
+    ("pgmi_op_ln_gelu", C.c_int, [C.c_int, C.c_int, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_float, _f32p]),
+    ("pgmi_bench_dilated_conv", C.c_int, [C.c_int] * 7 + [_f64p]),
     ("pgmi_bench_gemm", C.c_int, [C.c_int] * 9 + [_f64p]),
     ("pgmi_bench_gemm_ab", C.c_int, [C.c_int] * 7 + [_i32p, C.c_int, C.c_int, C.c_int, _f64p]),
     ("pgmi_op_attention", C.c_int, [C.c_int, C.c_int, _f32p, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),

@@ -315,6 +315,19 @@ void launch_mlstm_head(const float* hwin, size_t slot_stride, int W, const float
 void launch_mlstm_score(const float* terms, const int32_t* tgt, int rows, int Lc, double* out, hipStream_t s);
 int unirep_set_option(const char* name, long long value);   // api_unirep.hip: "unirep_max_rows"
 
+// ---- conv_f16.hip (CARP's ByteNet block; the kernels are described there) ------------------------------------------------------
+// out32 [M][C] = bias + sum over tap j of W[:, j, :] A[m + (j - taps/2) dilation] over the taps that stay inside row m's segment
+// (seg_off [n_seg + 1] on the device, seg_off[n_seg] = M).  A16: the K-interleaved split rows [M][C]; W16: the weight permuted to
+// [C out][taps][C in] = [C][taps C] and split as every f16x3 weight (launch_split16 mode 0), out_scale its W16::out_scale.
+int launch_dilated_conv16(const unsigned short* A16, const unsigned short* W16, float out_scale, const float* bias, const int32_t* seg_off,
+                          int n_seg, int64_t M, int C, int taps, int dilation, float* out32, hipStream_t s);
+// the same in fp32 through an im2col buffer col [M][taps C] and launch_gemm_f32; W fp32 [C][taps C]
+int launch_dilated_conv32(const float* x, const float* W, const float* bias, const int32_t* seg_off, int n_seg, int64_t M, int C, int taps,
+                          int dilation, float* col, float* out32, hipStream_t s);
+// y = gelu_erf(LayerNorm(x)) per row of D columns (D % 32 == 0, D <= 5120): the K-interleaved split operand, or fp32 rows
+int launch_ln_gelu16(const float* x, const float* w, const float* b, int rows, int D, float eps, unsigned short* y16, hipStream_t s);
+int launch_ln_gelu32(const float* x, const float* w, const float* b, int rows, int D, float eps, float* y, hipStream_t s);
+
 // ---- gemm_f32.hip ------------------------------------------------------------------------
 // C[M,N] = epi(A[M,K] W[N,K]^T + bias[N]) (+ residual[M,N]); K % 32 == 0.
 // ---- msa_transformer.hip ------------------------------------------------------------------

@@ -26,6 +26,8 @@
 //   api_eve.hip          EVE / DeepSequence: its own handle (pgmi_eve), blob walk, encoder, one ELBO sample, noise seam, the sampling loop
 //   api_mpnn.hip         ProteinMPNN: its own handle (pgmi_mpnn), blob walk, the per-structure pass (graph, features, encoder, hoisted
 //                        decoder tables), the per-batch decoder and head
+//   api_carp.hip         CARP: its own handle (pgmi_carp), blob walk, the ByteNet forward over packed sequences (conv_f16.hip), masked
+//                        rows / token log-probs / sequence log-likelihoods, the convolution's and the row kernel's op entries
 //   api_msa.hip          MSA Transformer weights and forward (tied row attention, column attention)
 //   api_host.hip         host-only entries: mutant parser, table -> scores, optimal window
 //   api_ops.hip          single-op and timing entries for the numerics tests and the A/B scripts

@@ -5,12 +5,12 @@ publishes.
     python scripts/accept_real_weights.py --proteingym /path/to/ProteinGym --dms-folder DMS_ProteinGym_substitutions \\
         --esm1v esm1v_t33_650M_UR90S_{1,2,3,4,5}.pt [--esm2 esm2_t33_650M_UR50D.pt esm2_t36_3B_UR50D.pt] \\
         [--tranception Tranception_Large [--msa-folder MSA_files --msa-weights-folder MSA_weights]] \\
-        [--progen3 progen3-339m ...] [--unirep unirep_1900_weights] \\
+        [--progen3 progen3-339m ...] [--unirep unirep_1900_weights] [--carp carp_640M.pt ...] \\
         [--assays BLAT_ECOLX_Stiffler_2015] --out accept_out
 
 What it does, with nothing of its own between the scorer and the verdict:
   1. cuts ``<proteingym>/reference_files/DMS_substitutions.csv`` down to ``--assays``;
-  2. scores them with this package's runners (``run_benchmark`` for ESM-1v / ESM2, the single-assay Tranception, ProGen3 and UniRep CLIs -- for
+  2. scores them with this package's runners (``run_benchmark`` for ESM-1v / ESM2, the single-assay Tranception, ProGen3, UniRep and CARP CLIs -- for
      ProGen3 this is also the first proof of the megablocks expert-layout mapping of proteingym_amd/progen3.py, which no toy can give), writing the CSVs
      where ``<proteingym>/config.json`` says each model's scores live;
   3. runs the checkout's OWN ``proteingym/merge.py`` and ``proteingym/performance_DMS_benchmarks.py`` on them (the latter's summary
@@ -53,6 +53,7 @@ def create_parser():
     ap.add_argument("--progen3", nargs="*", default=[], help="ProGen3 checkpoint directories; the size in the directory's name (112m, 219m, 339m, 762m, 1b, 3b) "
                                                              "picks the registry row Progen3_<size>")
     ap.add_argument("--unirep", default=None, help="UniRep checkpoint directory (the .npy arrays of the 1900-unit model): the registry row Unirep")
+    ap.add_argument("--carp", nargs="*", default=[], help="CARP checkpoints (.pt); the file stem (carp_600k, carp_38M, carp_76M, carp_640M) picks the registry row")
     ap.add_argument("--assays", nargs="+", default=["BLAT_ECOLX_Stiffler_2015"], help="DMS_id values")
     ap.add_argument("--out", default="accept_out")
     ap.add_argument("--device", type=int, default=0)
@@ -119,8 +120,11 @@ def missing_inputs(args, reference, subset):
             gone.append(os.path.join(d, "config.json"))
     if args.unirep and not os.path.exists(os.path.join(args.unirep, "embed_matrix:0.npy")):
         gone.append(os.path.join(args.unirep, "embed_matrix:0.npy"))
-    if not (args.esm1v or args.esm2 or args.tranception or args.progen3 or args.unirep):
-        gone.append("no model given: --esm1v / --esm2 / --tranception / --progen3 / --unirep")
+    for p in args.carp:
+        if not os.path.exists(p):
+            gone.append(p)
+    if not (args.esm1v or args.esm2 or args.tranception or args.progen3 or args.unirep or args.carp):
+        gone.append("no model given: --esm1v / --esm2 / --tranception / --progen3 / --unirep / --carp")
     return gone
 
 
@@ -194,6 +198,18 @@ def main(argv=None, make_model=None, make_tranception=None, patch_performance=No
         for i in range(len(subset)):
             ur_cli.main(["--model_path", args.unirep, "--data_path", args.dms_folder, "--mapping_path", sub_csv, "--DMS_index", str(i),
                          "--output_dir", os.path.join(scores, registry["Unirep"]["location"]), "--device", str(args.device)])
+    for ckpt in args.carp:
+        from proteingym_amd import score_carp_proteingym as carp_cli
+        key = next((k for k, v in registry.items() if k.startswith("CARP_") and v["input_score_name"] == stem(ckpt) + "_score"), None)
+        if key is None:
+            print(f"accept_real_weights: {ckpt}: no CARP entry of config.json has the score column {stem(ckpt) + '_score'!r}", file=sys.stderr)
+            return 2
+        models[key] = dict(registry[key])
+        for i in range(len(subset)):                              # location is CARP/<name>: the CLI appends the name itself
+            carp_cli.main(["--model_name", stem(ckpt), "--model_path", os.path.dirname(os.path.abspath(ckpt)), "--DMS_reference_file_path", sub_csv,
+                           "--DMS_data_folder", args.dms_folder, "--DMS_index", str(i), "--output_scores_folder",
+                           os.path.join(scores, os.path.dirname(registry[key]["location"])), "--performance_file",
+                           os.path.join(args.out, stem(ckpt) + "_performance.csv"), "--device", str(args.device)])
     cfg_path = os.path.join(args.out, "config.json")
     json.dump({FIELD: models}, open(cfg_path, "w"), indent=1)
 

@@ -64,6 +64,14 @@ pgmi_unirep() {
     pgmi_run proteingym_amd.score_unirep_proteingym --model_path "${model_path:=/path/to/unirep_weights}" --data_path "${folder}" \
         --output_dir "${output_dir:=${out}}" --mapping_path "${mapping}" --DMS_index "${DMS_index:=0}" --batch_size "${batch_size:=32}" "$@"
 }
+# pgmi_carp <mapping csv> <data folder> <output folder> [more flags]: assay ${DMS_index} through score_carp_proteingym with ${model_name}
+# (carp_600k | carp_38M | carp_76M | carp_640M, resolved as ${model_path}/${model_name}.pt, or a path ending in .pt; nothing is downloaded)
+pgmi_carp() {
+    local mapping="$1" folder="$2" out="$3"; shift 3
+    pgmi_run proteingym_amd.score_carp_proteingym --model_name "${model_name:=carp_640M}" --model_path "${model_path:=/path/to/CARP_checkpoints}" \
+        --DMS_reference_file_path "${mapping}" --DMS_data_folder "${folder}" --DMS_index "${DMS_index:=0}" \
+        --output_scores_folder "${DMS_output_score_folder:=${out}}" --performance_file "${performance_file:=CARP_640M_performance.csv}" "$@"
+}
 # pgmi_causal_lm <module> <model flag> <model path> <mapping csv> <data folder> [more flags]: assay ${DMS_index} through the RITA /
 # ProtGPT2 scorers
 pgmi_causal_lm() {
