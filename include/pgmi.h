@@ -291,6 +291,21 @@ int pgmi_op_attention(int device, int precision, const float* qkv, const int32_t
 int pgmi_op_causal_attention(int device, int lanes, const float* X, const float* W, const float* bias, int K, const float* qkv,
                              const float* conv, const float* rot_cos, const float* rot_sin, const float* slopes, int B, int T,
                              int heads, float* ctx);
+/* The dense (bidirectional) attention of one encoder layer in SLOT SPACE, through the launchers and the argument pattern of run_encoder.
+ * heads of `lanes` (64, or 128: ESM2-15B) lanes, Da = heads * lanes, every head lanes / 64 slot groups of 64.  X [B*T, K] (K % 32 == 0),
+ * W [3 Da, K] (rows q | k | v), bias [3 Da]: the fused QKV projection forms X W^T + bias, multiplies q by log2(e) and rotates the pair
+ * (i, i + 32) of every slot group g of a q / k head at position t (restarting per sequence) by rot_cos / rot_sin [T][lanes / 64][64] at
+ * [t][g][i] (both NULL: no rotary; entries i and i + 32 hold the same angle).  The projection is f16x3 whatever `out` is: the bf16-operand
+ * GEMM that the bf16 mode runs in front of this epilogue is not reached from here.  kv_len int32 [B] (NULL: T everywhere): sequence b's
+ * queries see its keys 0 .. kv_len[b] - 1.  q is taken as given (pre-scaled).  The V^T planes are zeroed before the projection (pad keys
+ * must be finite); the q | k planes and the context start as 0xFF bytes (NaN).  Honours the "att_v3" and "att_xcd_local" options.
+ * ctx [B*T, Da]: the context rebuilt as fp32 -- out 0: the kernel's fp32 rows; 1: the split planes the f16x3 out-projection consumes
+ * (hi + lo 2^-11); 2: the bf16 plane of the bf16 mode (bits << 16).  qk (nullable) [B*T, 2 Da]: the q | k operand planes rebuilt as fp32,
+ * q with its log2(e) factor; v (nullable) [B*T, Da]: the v operand read back out of the transposed, key-permuted V^T planes.
+ * PGMI_EINVAL, before the device is touched: a NULL X / W / bias / ctx, K % 32 != 0, lanes other than 64 / 128, only one of rot_cos /
+ * rot_sin, a kv_len[b] outside [1, T].  What a launcher refuses (out outside 0 .. 2) is PGMI_EINVAL with its message. */
+int pgmi_op_dense_attention(int device, int lanes, const float* X, const float* W, const float* bias, int K, const float* rot_cos,
+                            const float* rot_sin, const int32_t* kv_len, int B, int T, int heads, int out, float* ctx, float* qk, float* v);
 /* The MSA Transformer's two axial attentions (axial_attention.py:108-168, :232-275), through the launchers and the argument pattern of the
  * model's forward.  Heads of 64 lanes, D = 64 H; q is taken as given (pre-scaled by 1/8).
  * pgmi_op_tied_row_attention: qkv [R*C, 3 D] (q | k | v), token order (r, c).  s[h,i,j] = sum_{r,d} q[r,i,h,d] k[r,j,h,d] / sqrt(R) is ONE

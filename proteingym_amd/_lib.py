@@ -177,6 +177,8 @@ SIGNATURES = [
     ("pgmi_op_qkln_prep", C.c_int, [C.c_int, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p, _f64p]),
     ("pgmi_op_causal_attention", C.c_int, [C.c_int, C.c_int, _f32p, _f32p, _f32p, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p,
                                            C.c_int, C.c_int, C.c_int, _f32p]),
+    ("pgmi_op_dense_attention", C.c_int, [C.c_int, C.c_int, _f32p, _f32p, _f32p, C.c_int, _f32p, _f32p, _i32p, C.c_int, C.c_int, C.c_int,
+                                          C.c_int, _f32p, _f32p, _f32p]),
     ("pgmi_op_prefix_attention", C.c_int, [C.c_int, _f32p, _i32p, C.c_int, _f32p, C.c_int, C.c_int, C.c_int, _f32p]),
     ("pgmi_op_cross_attention", C.c_int, [C.c_int, _f32p, _i32p, C.c_int, _f32p, C.c_int, C.c_int, C.c_int, _f32p]),
     ("pgmi_op_packed_chunks", C.c_int, [_i32p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p]),

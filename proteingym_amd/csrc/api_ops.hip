@@ -744,6 +744,95 @@ int pgmi_op_column_attention(int device, const float* X, const float* W, const f
     return PGMI_OK;
 }
 
+// The attention of one encoder layer (run_encoder, api_esm.hip) in slot space, through the launchers and the argument pattern it uses: the
+// activation split, the weight planes, the fused QKV projection with H = heads * lanes / 64 slot groups and rot_halves = lanes / 64 (f16x3
+// whatever `out` is), then the dense attention on its operands with the device kv_len and the requested context kind.  V^T planes are zeroed
+// first (reset_pad_keys); the q | k planes and the context start as 0xFF bytes (NaN): an element the kernels skip shows.  Shapes are the
+// launchers' to refuse; only what the uploads themselves need is checked here, before the device is touched.
+int pgmi_op_dense_attention(int device, int lanes, const float* X, const float* W, const float* bias, int K, const float* rot_cos,
+                            const float* rot_sin, const int32_t* kv_len, int B, int T, int heads, int out, float* ctx, float* qk, float* v) {
+    if (!X || !W || !bias || !ctx || B <= 0 || T <= 0 || heads <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
+    if (!rot_cos != !rot_sin) { set_error("dense attention op: rot_cos and rot_sin go together (both, or neither for no rotary)"); return PGMI_EINVAL; }
+    if (lanes != 64 && lanes != 128) { set_error("dense attention op: lanes = %d is neither 64 nor 128", lanes); return PGMI_EINVAL; }
+    // the activation / weight split writes K-interleaved rows (ki_off) before any launcher sees K: whole groups of 32 only
+    if (K <= 0 || K % 32) { set_error("dense attention op: K = %d is not a positive multiple of 32", K); return PGMI_EINVAL; }
+    for (int b = 0; kv_len && b < B; ++b)
+        if (kv_len[b] < 1 || kv_len[b] > T) { set_error("dense attention op: kv_len[%d] = %d is outside [1, %d]", b, kv_len[b], T); return PGMI_EINVAL; }
+    if (pgmi_device_count() <= 0) { set_error("no HIP device visible"); return PGMI_ENODEV; }
+    PGMI_HIP(hipSetDevice(device));
+    gemm_options_from_env();
+    const size_t M = (size_t)B * T, Da = (size_t)heads * lanes, Tp = (size_t)(T + 31) / 32 * 32, Hs = Da / kHeadDim;
+    const int halves = lanes / kHeadDim, rotary = rot_cos != nullptr;
+    const size_t qk_plane = M * 2 * Da, vt_plane = (size_t)B * Tp * Da;
+    std::vector<void*> pool;
+    auto cleanup = [&]() { for (void* p : pool) hipFree(p); };
+    float *dx = nullptr, *db = nullptr, *dcos = nullptr, *dsin = nullptr, *dc = nullptr;
+    int32_t* dl = nullptr;
+    unsigned short *a16 = nullptr, *qk16 = nullptr, *vt16 = nullptr;
+    int rc = 0;
+    // dc: M Da fp32 values, M Da hi | lo pairs or M Da bf16 values -- one buffer of the largest of the three context kinds
+    if ((rc = dev_upload(pool, &dx, X, M * K)) || (rc = dev_upload(pool, &db, bias, 3 * Da)) || (kv_len && (rc = dev_upload(pool, &dl, kv_len, (size_t)B))) ||
+        (rotary && ((rc = dev_upload(pool, &dcos, rot_cos, (size_t)T * halves * kHeadDim)) || (rc = dev_upload(pool, &dsin, rot_sin, (size_t)T * halves * kHeadDim)))) ||
+        (rc = dev_alloc(pool, &a16, M * K * 2)) || (rc = dev_alloc(pool, &qk16, qk_plane * 2)) || (rc = dev_alloc(pool, &vt16, vt_plane * 2)) ||
+        (rc = dev_alloc(pool, &dc, M * Da))) {
+        cleanup();
+        return rc;
+    }
+    hipError_t e = hipMemset(vt16, 0, vt_plane * 2 * sizeof(unsigned short));      // pad keys: finite (reset_pad_keys)
+    if (e == hipSuccess) e = hipMemset(qk16, 0xFF, qk_plane * 2 * sizeof(unsigned short));
+    if (e == hipSuccess) e = hipMemset(dc, 0xFF, M * Da * sizeof(float));
+    if (e != hipSuccess) { cleanup(); set_error("dense attention op failed: %s", hipGetErrorString(e)); return PGMI_EHIP; }
+    W16 w16;
+    rc = make_w16(pool, W, 3 * Da * K, (size_t)K, PGMI_PREC_F16X3, nullptr, &w16);
+    if (!rc) {
+        launch_split16(dx, (int64_t)(M * K), 1.0f, 2, K, a16, nullptr);
+        GemmLaunch g = op_gemm(a16, w16, db, (int)M, 3 * (int)Da, K, env_int("PGMI_GEMM_VARIANT", 0));
+        g.out16 = qk16;
+        g.qkv.vt16 = vt16; g.qkv.vt_plane = vt_plane; g.qkv.qk_plane = qk_plane;
+        g.qkv.cos_t = dcos; g.qkv.sin_t = dsin; g.qkv.rotary = rotary;
+        g.qkv.T = T; g.qkv.H = (int)Hs; g.qkv.rot_halves = halves;
+        rc = launch_gemm16(g);
+    }
+    AttLaunch a;
+    a.qk16 = qk16, a.qk_plane = qk_plane, a.vt16 = vt16, a.vt_plane = vt_plane;
+    a.B = B, a.T = T, a.H = heads, a.head_dim = lanes;
+    a.kv_len = dl;
+    a.out = (AttOut)out, a.ctx = dc, a.ctx16 = reinterpret_cast<unsigned short*>(dc);
+    if (!rc) rc = launch_attention_f16x3_v2(a);
+    std::vector<float> hc(rc ? 0 : M * Da);
+    std::vector<unsigned short> hq(rc || !qk ? 0 : qk_plane * 2), hv(rc || !v ? 0 : vt_plane * 2);
+    e = hipDeviceSynchronize();
+    if (!rc && e == hipSuccess) e = hipMemcpy(hc.data(), dc, hc.size() * sizeof(float), hipMemcpyDeviceToHost);
+    if (!rc && qk && e == hipSuccess) e = hipMemcpy(hq.data(), qk16, hq.size() * 2, hipMemcpyDeviceToHost);
+    if (!rc && v && e == hipSuccess) e = hipMemcpy(hv.data(), vt16, hv.size() * 2, hipMemcpyDeviceToHost);
+    cleanup();
+    if (rc) return rc;
+    if (e != hipSuccess) { set_error("dense attention op failed: %s", hipGetErrorString(e)); return PGMI_EHIP; }
+    const unsigned short* h16 = reinterpret_cast<const unsigned short*>(hc.data());
+    if (out == ATT_OUT_F32) memcpy(ctx, hc.data(), M * Da * sizeof(float));
+    for (size_t m = 0; m < M && out == ATT_OUT_SPLIT; ++m)       // the context planes (K-interleaved rows of Da) rebuilt as fp32
+        for (size_t n = 0; n < Da; ++n) {
+            const size_t o = ki_off(m, (int)n, (int)Da);
+            ctx[m * Da + n] = rebuild_split(h16[o], h16[o + 32]);
+        }
+    for (size_t i = 0; i < M * Da && out == ATT_OUT_BF16; ++i) {  // one bf16 plane, row-major
+        const unsigned int u = (unsigned int)h16[i] << 16;
+        memcpy(&ctx[i], &u, 4);
+    }
+    if (qk)
+        for (size_t i = 0; i < qk_plane; ++i) qk[i] = rebuild_split(hq[i], hq[qk_plane + i]);
+    if (v)
+        for (int b = 0; b < B; ++b)
+            for (int t = 0; t < T; ++t) {
+                const int tk = t & 31, pos = (t & ~31) + ((tk & 0x13) | ((tk & 4) << 1) | ((tk & 8) >> 1));   // keys with bits 2, 3 swapped
+                for (size_t c = 0; c < Da; ++c) {
+                    const size_t o = ((size_t)b * Da + c) * Tp + pos;
+                    v[((size_t)b * T + t) * Da + c] = rebuild_split(hv[o], hv[vt_plane + o]);
+                }
+            }
+    return PGMI_OK;
+}
+
 // ESM3's geometric attention kernel (geom_attention.hip) through the launcher the model and the structure tokenizer use.
 int pgmi_op_geom_attention(int device, const float* proj, const float* rot, const float* trans, const int32_t* frame_mask,
                            int per_row_frames, const float* w_rot, const float* w_dist, int B, int S, int H, float* out) {

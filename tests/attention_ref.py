@@ -1,8 +1,9 @@
 """Plain NumPy reference of the causal decoder attention in SLOT SPACE (heads of `lanes` = 64 G lanes, each G slot groups of 64), as
 pgmi_op_causal_attention computes it: optional rotation of the slot pairs (i, i + 32) of every group, scores over all lanes of a head,
-+ slope[h] * key, mask key <= query, softmax, P V; and Tranception's right-aligned 7-tap causal depth-wise filter.  Every function
++ slope[h] * key, mask key <= query, softmax, P V; Tranception's right-aligned 7-tap causal depth-wise filter; and the encoder's dense
+attention as pgmi_op_dense_attention computes it: the same rotation, every key below kv_len[b] visible to every query.  Every function
 computes in `dtype`: float64 is the reference, float32 the "same reference in plain fp32" that sizes a tolerance (noise32).  Pinned
-against torch's own operators in test_attention_ref.py; shared with test_gpu_causal_attention.py."""
+against torch's own operators in test_attention_ref.py; shared with test_gpu_causal_attention.py and test_gpu_dense_attention.py."""
 import numpy as np
 
 
@@ -64,3 +65,34 @@ def conv_reference(qkv, conv, B, T, heads, slopes, dtype=np.float64):
     Da = heads * 64
     f = depthwise_filter(qkv.reshape(B, T, 3 * Da), conv, heads, dtype)
     return causal_attention(f[..., :Da], f[..., Da:2 * Da], f[..., 2 * Da:], heads, 64, slopes, dtype=dtype)
+
+
+def dense_attention(q, k, v, heads, lanes, kv_len=None, cos=None, sin=None, dtype=np.float64):
+    """q, k, v [B, T, heads * lanes] (q pre-scaled) -> context [B, T, heads * lanes]: every query of sequence b sees the keys below
+    kv_len[b] (None: T), keys from kv_len[b] on are at -inf.  Rows t >= kv_len[b] are computed like any other query."""
+    B, T, Da = q.shape
+    assert Da == heads * lanes
+    if cos is not None:
+        q, k = rotate_pairs(q, cos, sin, lanes, dtype), rotate_pairs(k, cos, sin, lanes, dtype)
+    q, k, v = (t.astype(dtype).reshape(B, T, heads, lanes).transpose(0, 2, 1, 3) for t in (q, k, v))
+    kv_len = np.full(B, T) if kv_len is None else np.asarray(kv_len)
+    out = np.empty((B, heads, T, lanes), dtype)
+    for b in range(B):
+        s = np.matmul(q[b], k[b].transpose(0, 2, 1))
+        s = np.where(np.arange(T)[None, None, :] < kv_len[b], s, dtype(-np.inf))
+        p = np.exp(s - s.max(-1, keepdims=True))
+        p /= p.sum(-1, keepdims=True)
+        out[b] = np.matmul(p, v[b])
+    return out.transpose(0, 2, 1, 3).reshape(B, T, Da)
+
+
+def dense_fused_reference(X, W, bias, B, T, heads, lanes, kv_len=None, cos=None, sin=None, dtype=np.float64):
+    """The encoder's fused form: q | k | v = X W^T + bias in `dtype`, then dense_attention.  Returns (context [B, T, Da], the rotated
+    q | k rows [B * T, 2 Da] without the kernels' log2(e) on q, the v rows [B * T, Da]) as it formed them."""
+    Da = heads * lanes
+    qkv = (X.astype(dtype) @ W.astype(dtype).T + bias.astype(dtype)).reshape(B, T, 3 * Da)
+    q, k, v = qkv[..., :Da], qkv[..., Da:2 * Da], qkv[..., 2 * Da:]
+    ctx = dense_attention(q, k, v, heads, lanes, kv_len, cos, sin, dtype)
+    if cos is not None:
+        q, k = rotate_pairs(q, cos, sin, lanes, dtype), rotate_pairs(k, cos, sin, lanes, dtype)
+    return ctx, np.concatenate([q, k], -1).reshape(B * T, 2 * Da), np.ascontiguousarray(v).reshape(B * T, Da)

@@ -461,6 +461,45 @@ def test_esm2_beyond_1024_tokens_vs_oracle(lib):
     m1.close()
 
 
+@pytest.mark.parametrize("name", ["esm1v_toy_1", "esm2_toy"])
+def test_token_logprobs_do_not_depend_on_what_the_handle_ran_before(lib, golden, golden_dir, name):
+    """reset_pad_keys zeroes the V^T planes only when (B, T) differs from the previous call, and the workspace keeps whatever the previous
+    call left everywhere else: one handle walked through batches of changing shape and padding, with an Assay.run() in between, gives
+    every batch the bits a fresh handle gives it."""
+    import pandas as pd
+    seq = str(golden["seq"])
+    muts = list(pd.read_csv(os.path.join(golden_dir, "TOY_DMS.csv"))["mutant"])
+    path = os.path.join(golden_dir, name + ".pt")
+    rng = np.random.default_rng(11)
+
+    def batch(B, T, lens):
+        tok = rng.integers(4, 24, size=(B, T)).astype(np.int32)
+        tok[:, 0] = 0
+        for b, n in enumerate(lens):                       # n tokens, <eos> last, <pad> behind it
+            tok[b, n - 1] = 2
+            tok[b, n:] = 1
+        return tok
+    # (3, 70) padded, (3, 41), (3, 70) full, (2, 70) padded, (3, 40) padded, then (3, 40) again with other lengths: no reset in front of it
+    calls = [batch(3, 70, (70, 33, 5)), batch(3, 41, (41, 41, 32)), batch(3, 70, (70, 70, 70)), batch(2, 70, (64, 70)),
+             batch(3, 40, (40, 17, 32)), batch(3, 40, (9, 40, 33))]
+    m = pesm.load_model_and_alphabet(path)[0]
+    got = []
+    for i, tok in enumerate(calls):
+        got.append(m.token_logprobs(tok))
+        if i in (0, 3):
+            a = pesm.Assay(m, seq, muts)
+            a.run()
+            a.close()
+    m.close()
+    for i, tok in enumerate(calls):
+        fresh = pesm.load_model_and_alphabet(path)[0]
+        want = fresh.token_logprobs(tok)
+        fresh.close()
+        keep = tok != 1
+        assert np.isfinite(got[i][keep]).all()
+        assert np.array_equal(got[i][keep], want[keep]), (name, i, tok.shape, float(np.abs(got[i][keep] - want[keep]).max()))
+
+
 @pytest.mark.parametrize("arch", ["ESM1V_650M", "ESM2_650M"])
 def test_attention_launch_options_keep_the_bits_of_a_model(lib, arch):
     """Split-plane attention output (the model path) under the XCD-local block order and under the software-pipelined kernel (att_v3) against the
