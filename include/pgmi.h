@@ -906,6 +906,61 @@ int pgmi_s2f_gvp_forward(pgmi_s2f* m, const float* node_feat, const float* seq_l
 int pgmi_s2f_set_logprobs(pgmi_s2f* m, const int32_t* wt_tokens, int T, const int32_t* aa_cols, const int32_t* set_off,
                           const int32_t* set_pos, int n_sets, float* out, float* full);
 
+/* ---- S3F (S2F plus SurfGVP's surface half: a second GVP-GNN over the 16-NN graph of a surface point cloud; its own handle, fp32) ----
+ * Replaces SurfGVP.forward (proteingym/baselines/S3F/s3f/gvp.py) under FusionNetwork / ResidueTypePrediction.inference as
+ * script/evaluate.py runs them with config/evaluate/s3f.yaml.  The residue half is the S2F handle's code unchanged.  The surface half:
+ * every surface point takes the ESM2 rows of its 3 nearest C-alpha atoms (surf_in_linear on [row | distance], mean), surf_in_mlp on
+ * [mean | 42 features], surf_W_v, five surf_layers over the 16-NN graph (source = neighbour, target = centre, edge vector
+ * p_source - p_centre), surf_W_out.  SurfGVP.residue2surface returns nothing, so the readout is the mean of surf_W_out's rows over ALL
+ * surface points of the loader's batch, one [256] row added to every residue's W_out row; a pool group is that batch.  DESIGN.md 4.6p
+ * has the restatement and the factorisation.  Producing the surface (points, HKS, curvatures) is the caller's.
+ *
+ * Weight blob: fp32, row-major, three parts:
+ *   1. the S2F blob of the residue half (above), linear.{weight, bias} included;
+ *   2. the surface MLP, folded on the host (H = 2 D): Wz [H, D] = W_1h W_x; Wsf [H, surf_feat + 1] = [W_1f | W_1h w_d]; b_1 [H];
+ *      surf_in_mlp.2.{weight, bias} [H] (the LayerNorm); surf_in_mlp.4.{weight [D, H], bias [D]} -- where surf_in_linear.weight =
+ *      [W_x | w_d] and surf_in_mlp.0.weight = [W_1h | W_1f];
+ *   3. the surface GNN in the S2F blob's order with surf_W_v, surf_W_e, surf_layers, surf_W_out for W_v, W_e, layers, W_out, without
+ *      residue_embdding and without linear.
+ * Limits: S2F's; node_in <= 4096; surf_feat = 42, surf_res_neighbors = 3, surf_neighbors = 16; L >= 3; 17 <= Ns <= 1048576.
+ * Workspace per masked copy of a chunk, in bytes: 4 Ns (2 D + 3670 + D) for the surface (the Ns x 2 D hidden of the MLP, the D-wide
+ * rows and the GNN's stages; 30 KB per point at D = 1280) + 4 L (2 D + 2 D + 3670) for the residue half and Z. */
+typedef struct pgmi_s3f_config {
+    pgmi_s2f_config s2f;                          /* the residue half, and the dimensions both halves share */
+    int32_t surf_feat;                            /* 42: HKS (32) | curvatures (10) */
+    int32_t surf_res_neighbors;                   /* 3 */
+    int32_t surf_neighbors;                       /* 16 */
+} pgmi_s3f_config;
+typedef struct pgmi_s3f pgmi_s3f;
+/* pgmi_s3f_weight_count / _create / _destroy: as S2F's.
+ * pgmi_s3f_profile_model(m, part): part 0 = the residue half's view (S2F's classes; PGMI_K_HEAD also holds the pooled row's add),
+ *   part 1 = the surface half's view (owned by the handle).  Surface classes: PGMI_K_EMBED = the structure pass (both k-NN searches,
+ *   surf_W_e, the structure term of the MLP, every layer's edge share), PGMI_K_GEMM_OUT = the surface MLP (Z, the row kernel, its
+ *   second Linear, surf_W_v), PGMI_K_GEMM_QKV = the per-point tables of the first message GVP, PGMI_K_ATTENTION = the surface message
+ *   kernel, PGMI_K_LAYERNORM, PGMI_K_GEMM_FC1 / _FC2, PGMI_K_KEPT_ROWS as S2F's, PGMI_K_HEAD = surf_W_out and the column sum.
+ * pgmi_s3f_set_structure: pos, plddt as S2F's; surf_pos f32 [Ns][3], surf_feat f32 [Ns][42].  On the device, in fp32 squared
+ *   distances with ties to the lower index: every point's 16 nearest other points (stored per centre in ascending source index) and its
+ *   3 nearest C-alpha atoms (nearest first).
+ * pgmi_s3f_graph (test view): the residue edges as pgmi_s2f_graph; src i32 [Ns][16]; res i32 [Ns][3]; res_dist f32 [Ns][3];
+ *   e_s f32 [16 Ns][64], e_v f32 [16 Ns][3] (surf_W_e's output); each nullable.
+ * pgmi_s3f_gvp_forward: node_feat, seq_logits, lp as S2F's for B copies; pool_off i32 [n_pools + 1]: consecutive copies
+ *   [pool_off[g], pool_off[g + 1]) share one pooled row; surf_s f32 [B][Ns][256], surf_v f32 [B][Ns][16][3] (nullable): the surface
+ *   node state after the last layer; pool_sum f32 [B][256] (nullable): per copy the column sum of surf_W_out's rows, in a fixed order
+ *   (its count is Ns).  A copy's sum and everything before it have the same bits alone, in a batch and under any row cap.
+ * pgmi_s3f_set_logprobs: as S2F's, with the pool groups over the sets.
+ * pgmi_set_option("s2f_max_rows", n): a masked copy costs max(E, 16 Ns, L + 2) rows here. */
+int64_t pgmi_s3f_weight_count(const pgmi_s3f_config* cfg);
+int pgmi_s3f_create(const pgmi_s3f_config* cfg, const float* weights, int64_t n_weights, pgmi_model* esm, int device, pgmi_s3f** out);
+void pgmi_s3f_destroy(pgmi_s3f* m);
+pgmi_model* pgmi_s3f_profile_model(pgmi_s3f* m, int part);
+int pgmi_s3f_set_structure(pgmi_s3f* m, const float* pos, const float* plddt, int L, const float* surf_pos, const float* surf_feat, int Ns);
+int pgmi_s3f_graph(pgmi_s3f* m, int32_t* n_edges, int32_t* src, int32_t* dst, float* e_s, float* e_v, int32_t* surf_src, int32_t* surf_res,
+                   float* surf_res_dist, float* surf_e_s, float* surf_e_v);
+int pgmi_s3f_gvp_forward(pgmi_s3f* m, const float* node_feat, const float* seq_logits, int B, const int32_t* pool_off, int n_pools, float* lp,
+                         float* surf_s, float* surf_v, float* pool_sum);
+int pgmi_s3f_set_logprobs(pgmi_s3f* m, const int32_t* wt_tokens, int T, const int32_t* aa_cols, const int32_t* set_off,
+                          const int32_t* set_pos, int n_sets, const int32_t* pool_off, int n_pools, float* out, float* full);
+
 /* ---- UniRep (the 1900-unit multiplicative LSTM; its own handle and config, precision f16x3 or fp32) ---------------------------------
  * Replaces babbler1900's graph (proteingym/baselines/unirep/unirep.py:318-408: embedding, mLSTMCell1900.call :81-132 under
  * tf.nn.dynamic_rnn, Dense(25), tfa.seq2seq.sequence_loss) as unirep_inference.py:48-57 runs it.  DESIGN.md 4.6m has the restatement,

@@ -153,6 +153,14 @@ SIGNATURES = [
     ("pgmi_s2f_graph", C.c_int, [C.c_void_p, _i32p, _i32p, _i32p, _f32p, _f32p]),
     ("pgmi_s2f_gvp_forward", C.c_int, [C.c_void_p, _f32p, _f32p, C.c_int, _f32p, _f32p, _f32p]),
     ("pgmi_s2f_set_logprobs", C.c_int, [C.c_void_p, _i32p, C.c_int, _i32p, _i32p, _i32p, C.c_int, _f32p, _f32p]),
+    ("pgmi_s3f_weight_count", C.c_int64, [C.c_void_p]),
+    ("pgmi_s3f_create", C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    ("pgmi_s3f_destroy", None, [C.c_void_p]),
+    ("pgmi_s3f_profile_model", C.c_void_p, [C.c_void_p, C.c_int]),
+    ("pgmi_s3f_set_structure", C.c_int, [C.c_void_p, _f32p, _f32p, C.c_int, _f32p, _f32p, C.c_int]),
+    ("pgmi_s3f_graph", C.c_int, [C.c_void_p, _i32p, _i32p, _i32p, _f32p, _f32p, _i32p, _i32p, _f32p, _f32p, _f32p]),
+    ("pgmi_s3f_gvp_forward", C.c_int, [C.c_void_p, _f32p, _f32p, C.c_int, _i32p, C.c_int, _f32p, _f32p, _f32p, _f32p]),
+    ("pgmi_s3f_set_logprobs", C.c_int, [C.c_void_p, _i32p, C.c_int, _i32p, _i32p, _i32p, C.c_int, _i32p, C.c_int, _f32p, _f32p]),
     ("pgmi_unirep_weight_count", C.c_int64, [C.c_void_p]),
     ("pgmi_unirep_model_create", C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     ("pgmi_unirep_destroy", None, [C.c_void_p]),

@@ -5,67 +5,19 @@
 // ascending order, and every other kernel is one wave per row, so a masked copy's bits do not depend on the batch or the chunking.
 #include <cmath>
 
-#include "model.h"
+#include "s2f_impl.h"
 
 namespace pgmi {
 
-constexpr int S2F_S = 256, S2F_V = 16, S2F_ES = 64, S2F_RBF = 16, S2F_H0 = 33, S2F_MAX_L = 8192, S2F_MAX_LAYERS = 8;
-constexpr int S2F_KP = 288;                            // 256 + 16 (or 32) norm columns, rounded up to the GEMM's K tile
-constexpr int S2F_FS = 4 * S2F_S, S2F_FV = 2 * S2F_V;  // feed-forward hidden dims (1024, 32)
-constexpr int S2F_FK = S2F_FS + S2F_FV;                // 1056, a multiple of 32
-constexpr long long S2F_ROWS_LIMIT = 1 << 20;
 static long long g_s2f_max_rows = 0;
+long long s2f_row_cap() { return g_s2f_max_rows > 0 ? g_s2f_max_rows : 262144; }
 
 int s2f_set_option(const char* name, long long value) {
     if (!strcmp(name, "s2f_max_rows")) { g_s2f_max_rows = std::min(std::max(value, 0LL), S2F_ROWS_LIMIT); return PGMI_OK; }
     return PGMI_EINVAL;
 }
 
-// one GVP on the device: ws zero-padded along K to Kp columns ([s | norms | 0])
-struct S2fGvp {
-    float *wh = nullptr, *ws = nullptr, *bs = nullptr, *wv = nullptr, *wsv = nullptr, *bsv = nullptr;
-    int si = 0, vi = 0, h = 0, so = 0, vo = 0, Kp = 0;
-};
-struct S2fLayer {
-    // first message GVP, split by input block: Wji [512][256] = Wj rows then Wi rows; We [256][64] + b; Wnt [33][256]; whji [66][16];
-    // whe [33]; and its vector half in m0 (ws unused there)
-    float *Wji = nullptr, *We = nullptr, *b0 = nullptr, *Wnt = nullptr, *whji = nullptr, *whe = nullptr;
-    S2fGvp m0, m1, m2, f0, f1;
-    float *n0w, *n0b, *n1w, *n1b;
-    float* Es = nullptr;      // per structure: We e_s + b [E][256]
-    size_t Es_cap = 0;
-};
-struct S2fBuf { float* p = nullptr; size_t cap = 0; };
-
-}  // namespace pgmi
-
-struct pgmi_s2f {
-    pgmi_model pm;                       // device, stream, allocation pool and profiling state (pgmi_s2f_profile_model)
-    pgmi_model* esm = nullptr;           // borrowed; its stream is pm.stream when set
-    pgmi_s2f_config cfg;
-    int D = 0;
-    float *Wre = nullptr, *vnw = nullptr, *vnb = nullptr, *Wv = nullptr, *bv = nullptr;
-    std::vector<float> we_host;          // W_e's tensors in blob order: the structure pass runs it on the host
-    std::vector<S2fLayer> layers;
-    float *onw = nullptr, *onb = nullptr;
-    S2fGvp wout;
-    float *Wlin = nullptr, *blin = nullptr;
-    // structure
-    int L = 0, E = 0;
-    std::vector<int32_t> h_src, h_dst, h_off;
-    std::vector<float> h_es, h_ev;
-    int32_t *src = nullptr, *off = nullptr;
-    size_t src_cap = 0, off_cap = 0;
-    S2fBuf es, ev, plddt;
-    // workspace of a chunk
-    S2fBuf feat, h0, s, v, s1, v1, P, VT, pre, gate, A, vhA, vhB, mV, seq, lp;
-    int32_t *ridx = nullptr, *toks = nullptr, *cols = nullptr;
-    size_t ridx_cap = 0, toks_cap = 0, cols_cap = 0;
-};
-
-namespace pgmi {
-
-static int s2f_check(const pgmi_s2f_config* c) {
+int s2f_check(const pgmi_s2f_config* c) {
     if (!c) { set_error("null config"); return PGMI_EINVAL; }
     if (c->abi_version != PGMI_ABI_VERSION) { set_error("ABI version mismatch: got %d, library is %d", c->abi_version, PGMI_ABI_VERSION); return PGMI_EINVAL; }
     if (c->node_in < 32 || c->node_in % 32 || c->node_in > 8192) { set_error("S2F: node_in %d must be a multiple of 32 in 32 .. 8192", c->node_in); return PGMI_EINVAL; }
@@ -85,13 +37,13 @@ static int64_t gvp_count(int si, int vi, int so, int vo, int h) {   // wh, ws + 
     return (int64_t)h * vi + (int64_t)so * (si + h) + so + (vo ? (int64_t)vo * h + (int64_t)vo * so + vo : 0);
 }
 static int64_t s2f_we_count() { return 2 * S2F_RBF + gvp_count(S2F_RBF, 1, S2F_ES, 1, 1); }
-static int64_t s2f_count(const pgmi_s2f_config* c) {
+int64_t s2f_count(const pgmi_s2f_config* c, bool surface) {
     const int64_t D = c->node_in;
-    int64_t n = D * D + 2 * D + (int64_t)S2F_S * D + S2F_S + s2f_we_count();
+    int64_t n = (surface ? 0 : D * D) + 2 * D + (int64_t)S2F_S * D + S2F_S + s2f_we_count();
     const int64_t layer = gvp_count(2 * S2F_S + S2F_ES, S2F_H0, S2F_S, S2F_V, S2F_H0) + 2 * gvp_count(S2F_S, S2F_V, S2F_S, S2F_V, S2F_V) +
                           4 * S2F_S + gvp_count(S2F_S, S2F_V, S2F_FS, S2F_FV, S2F_FV) + gvp_count(S2F_FS, S2F_FV, S2F_S, S2F_V, S2F_FV);
     n += c->layers * layer;
-    n += 2 * S2F_S + gvp_count(S2F_S, S2F_V, S2F_S, 0, S2F_V) + 20 * S2F_S + 20;
+    n += 2 * S2F_S + gvp_count(S2F_S, S2F_V, S2F_S, 0, S2F_V) + (surface ? 0 : 20 * S2F_S + 20);
     return n;
 }
 
@@ -119,7 +71,7 @@ static int s2f_build(pgmi_s2f* m, const float* w, int64_t n_weights) {
         return ws;
     };
     const size_t D = m->D;
-    up(&m->Wre, take(D * D), D * D);
+    if (!m->fixed_degree) up(&m->Wre, take(D * D), D * D);
     up(&m->vnw, take(D), D);
     up(&m->vnb, take(D), D);
     up(&m->Wv, take(S2F_S * D), S2F_S * D);
@@ -163,8 +115,10 @@ static int s2f_build(pgmi_s2f* m, const float* w, int64_t n_weights) {
     up(&m->onw, take(S2F_S), S2F_S);
     up(&m->onb, take(S2F_S), S2F_S);
     gvp(&m->wout, S2F_S, S2F_V, S2F_S, 0, S2F_V, true);
-    up(&m->Wlin, take(20 * S2F_S), 20 * S2F_S);
-    up(&m->blin, take(20), 20);
+    if (!m->fixed_degree) {
+        up(&m->Wlin, take(20 * S2F_S), 20 * S2F_S);
+        up(&m->blin, take(20), 20);
+    }
     if (!rc && p != w + n_weights) { set_error("internal: S2F blob walk mismatch"); rc = PGMI_EINVAL; }
     return rc;
 }
@@ -231,9 +185,9 @@ static void s2f_edge_embed(const pgmi_s2f* m, const float* pos, std::vector<floa
     }
 }
 
-static int s2f_buf(pgmi_s2f* m, S2fBuf* b, size_t n) { return ensure_cap(&m->pm, &b->p, &b->cap, n); }
+int s2f_buf(pgmi_s2f* m, S2fBuf* b, size_t n) { return ensure_cap(&m->pm, &b->p, &b->cap, n); }
 
-static int s2f_structure(pgmi_s2f* m, const float* pos, const float* plddt, int L) {
+int s2f_structure(pgmi_s2f* m, const float* pos, const float* plddt, int L) {
     pgmi_model* pm = &m->pm;
     hipStream_t st = pm->stream;
     m->L = 0;
@@ -275,14 +229,15 @@ static int s2f_structure(pgmi_s2f* m, const float* pos, const float* plddt, int 
 
 // rows a masked copy costs in the widest stage, and copies per chunk
 static int s2f_per_chunk(const pgmi_s2f* m, int B) {
-    const long long cap = g_s2f_max_rows > 0 ? g_s2f_max_rows : 262144;
+    const long long cap = s2f_row_cap();
     const long long cost = std::max(m->E, m->L + 2);
     return (int)std::min<long long>(std::max<long long>(1, cap / cost), B);
 }
 
-static int s2f_workspace(pgmi_s2f* m, int per) {
+int s2f_workspace(pgmi_s2f* m, int per) {
     const size_t R = (size_t)per * m->L, D = m->D;
-    int rc = s2f_buf(m, &m->feat, R * D);
+    const bool surface = m->fixed_degree != 0;           // a surface half takes its rows from the surface MLP and has no head
+    int rc = surface ? PGMI_OK : s2f_buf(m, &m->feat, R * D);
     if (!rc) rc = s2f_buf(m, &m->h0, R * D);
     if (!rc) rc = s2f_buf(m, &m->s, R * S2F_S);
     if (!rc) rc = s2f_buf(m, &m->v, R * S2F_V * 3);
@@ -296,8 +251,8 @@ static int s2f_workspace(pgmi_s2f* m, int per) {
     if (!rc) rc = s2f_buf(m, &m->vhA, R * S2F_FV * 3);
     if (!rc) rc = s2f_buf(m, &m->vhB, R * S2F_FV * 3);
     if (!rc) rc = s2f_buf(m, &m->mV, R * S2F_V * 3);
-    if (!rc) rc = s2f_buf(m, &m->seq, R * 20);
-    if (!rc) rc = s2f_buf(m, &m->lp, R * 20);
+    if (!rc && !surface) rc = s2f_buf(m, &m->seq, R * 20);
+    if (!rc && !surface) rc = s2f_buf(m, &m->lp, R * 20);
     return rc;
 }
 
@@ -319,22 +274,26 @@ static int s2f_gvp(pgmi_s2f* m, const S2fGvp& g, const float* vh_in, int relu, c
                               next ? next->Kp : 0, rows, next ? m->A.p : nullptr, outV, st);
 }
 
-// bc masked copies: m->feat [bc L][D] (device) and m->seq [bc L][20] -> m->lp [bc L][20]; the node state after the last layer stays
-// in m->s / m->v
-static int s2f_gnn(pgmi_s2f* m, int bc) {
+// bc masked copies: m->feat [bc L][D] (device) -> m->s [bc L][256] = W_v (LayerNorm (residue_embdding feat))
+int s2f_embed(pgmi_s2f* m, int bc) {
     pgmi_model* pm = &m->pm;
     hipStream_t st = pm->stream;
-    const int L = m->L, E = m->E, D = m->D;
+    const int D = m->D;
+    const int64_t R = (int64_t)bc * m->L;
+    ProfScope p(pm, PGMI_K_GEMM_QKV, 2.0 * R * D * (D + S2F_S), 0);
+    int rc = launch_gemm_f32(m->feat.p, m->Wre, nullptr, nullptr, m->h0.p, (int)R, D, D, EPI_NONE, st);
+    if (rc) return rc;
+    launch_layernorm(m->h0.p, m->vnw, m->vnb, (int)R, D, 1e-5f, m->h0.p, st);
+    return launch_gemm_f32(m->h0.p, m->Wv, m->bv, nullptr, m->s.p, (int)R, S2F_S, D, EPI_NONE, st);
+}
+
+// the layers on m->s (v = 0 before the first), then W_out -> m->pre [bc L][256]; the node state after the last layer stays in m->s / m->v
+int s2f_layers(pgmi_s2f* m, int bc) {
+    pgmi_model* pm = &m->pm;
+    hipStream_t st = pm->stream;
+    const int L = m->L, E = m->E;
     const int64_t R = (int64_t)bc * L, RE = (int64_t)bc * E;
     int rc;
-    {
-        ProfScope p(pm, PGMI_K_GEMM_QKV, 2.0 * R * D * (D + S2F_S), 0);
-        rc = launch_gemm_f32(m->feat.p, m->Wre, nullptr, nullptr, m->h0.p, (int)R, D, D, EPI_NONE, st);
-        if (rc) return rc;
-        launch_layernorm(m->h0.p, m->vnw, m->vnb, (int)R, D, 1e-5f, m->h0.p, st);
-        rc = launch_gemm_f32(m->h0.p, m->Wv, m->bv, nullptr, m->s.p, (int)R, S2F_S, D, EPI_NONE, st);
-        if (rc) return rc;
-    }
     const size_t nl = m->layers.size();
     for (size_t li = 0; li < nl; ++li) {
         const S2fLayer& l = m->layers[li];
@@ -349,7 +308,8 @@ static int s2f_gnn(pgmi_s2f* m, int bc) {
                 ProfScope p(pm, PGMI_K_ATTENTION, 2.0 * RE * S2F_S * (S2F_H0 + 2.0 * S2F_KP + 3.0 * S2F_V), (double)R * (3 * S2F_S + 2 * S2F_H0 * 3) * 4);
                 const S2fMsgWeights w = {l.m0.wv, l.m0.wsv, l.m0.bsv, l.m1.wh, l.m1.ws, l.m1.bs, l.m1.wv, l.m1.wsv, l.m1.bsv,
                                          l.m2.wh, l.m2.ws, l.m2.bs, l.m2.wv, l.m2.wsv, l.m2.bsv, l.m1.Kp};
-                rc = launch_s2f_message(m->P.p, first ? nullptr : m->VT.p, l.Es, m->ev.p, l.whe, l.Wnt, w, m->src, m->off, L, R, m->pre.p, m->mV.p, st);
+                rc = m->fixed_degree ? launch_s3f_message(m->P.p, first ? nullptr : m->VT.p, l.Es, m->ev.p, l.whe, l.Wnt, w, m->src, L, R, m->pre.p, m->mV.p, st)
+                                     : launch_s2f_message(m->P.p, first ? nullptr : m->VT.p, l.Es, m->ev.p, l.whe, l.Wnt, w, m->src, m->off, L, R, m->pre.p, m->mV.p, st);
                 if (rc) return rc;
             }
         }
@@ -370,15 +330,30 @@ static int s2f_gnn(pgmi_s2f* m, int bc) {
         }
     }
     {
-        ProfScope p(pm, PGMI_K_HEAD, 2.0 * R * S2F_S * (S2F_KP + 20), 0);
+        ProfScope p(pm, PGMI_K_HEAD, 2.0 * R * S2F_S * S2F_KP, 0);
         rc = launch_s2f_node_ln(m->s.p, m->v.p, nullptr, nullptr, m->onw, m->onb, m->wout.wh, m->wout.h, 1, m->wout.Kp, R,
                                 m->s1.p, m->v1.p, m->A.p, m->vhA.p, st);
         if (!rc) rc = launch_gemm_f32(m->A.p, m->wout.ws, m->wout.bs, nullptr, m->pre.p, (int)R, S2F_S, m->wout.Kp, EPI_NONE, st);
         if (rc) return rc;
-        launch_s2f_head(m->pre.p, m->Wlin, m->blin, m->seq.p, m->plddt.p, m->cfg.plddt_threshold, L, R, m->lp.p, st);
     }
     PGMI_HIP(hipGetLastError());
     return PGMI_OK;
+}
+
+// relu, the 20-way Linear, the ESM logits on low-pLDDT rows and the log-softmax on `rows` rows of W_out's output
+int s2f_head(pgmi_s2f* m, const float* pre, const float* seq, int64_t rows, float* lp) {
+    ProfScope p(&m->pm, PGMI_K_HEAD, 2.0 * rows * S2F_S * 20, 0);
+    launch_s2f_head(pre, m->Wlin, m->blin, seq, m->plddt.p, m->cfg.plddt_threshold, m->L, rows, lp, m->pm.stream);
+    PGMI_HIP(hipGetLastError());
+    return PGMI_OK;
+}
+
+// bc masked copies: m->feat [bc L][D] (device) and m->seq [bc L][20] -> m->lp [bc L][20]
+static int s2f_gnn(pgmi_s2f* m, int bc) {
+    int rc = s2f_embed(m, bc);
+    if (!rc) rc = s2f_layers(m, bc);
+    if (!rc) rc = s2f_head(m, m->pre.p, m->seq.p, (int64_t)bc * m->L, m->lp.p);
+    return rc;
 }
 
 static int s2f_ready(pgmi_s2f* m) {
@@ -392,17 +367,26 @@ static int s2f_ready(pgmi_s2f* m) {
 extern "C" {
 
 int64_t pgmi_s2f_weight_count(const pgmi_s2f_config* cfg) {
-    if (s2f_check(cfg)) return -1;
-    return s2f_count(cfg);
+    if (pgmi::s2f_check(cfg)) return -1;
+    return pgmi::s2f_count(cfg, false);
 }
 
 int pgmi_s2f_create(const pgmi_s2f_config* cfg, const float* w, int64_t n_weights, pgmi_model* esm, int device, pgmi_s2f** out) {
+    return pgmi::s2f_new(cfg, w, n_weights, esm, nullptr, device, 0, out);
+}
+
+}  // extern "C"
+
+namespace pgmi {
+
+int s2f_new(const pgmi_s2f_config* cfg, const float* w, int64_t n_weights, pgmi_model* esm, pgmi_s2f* stream_of, int device, int fixed_degree,
+            pgmi_s2f** out) {
     if (!out) { set_error("null out"); return PGMI_EINVAL; }
     *out = nullptr;
     int rc = s2f_check(cfg);
     if (rc) return rc;
-    if (!w || n_weights != s2f_count(cfg)) {
-        set_error("S2F weight blob has %lld elements, config needs %lld", (long long)n_weights, (long long)s2f_count(cfg));
+    if (!w || n_weights != s2f_count(cfg, fixed_degree != 0)) {
+        set_error("S2F weight blob has %lld elements, config needs %lld", (long long)n_weights, (long long)s2f_count(cfg, fixed_degree != 0));
         return PGMI_EINVAL;
     }
     if (esm) {
@@ -419,13 +403,20 @@ int pgmi_s2f_create(const pgmi_s2f_config* cfg, const float* w, int64_t n_weight
     m->D = cfg->node_in;
     m->esm = esm;
     m->pm.device = device;
+    m->fixed_degree = fixed_degree;
     if (esm) m->pm.stream = esm->stream;                 // one stream: the GNN reads what the encoder just wrote
+    else if (stream_of) m->pm.stream = stream_of->pm.stream;
     else if (hipStreamCreate(&m->pm.stream) != hipSuccess) { delete m; set_error("hipStreamCreate failed"); return PGMI_EHIP; }
+    else m->own_stream = true;
     rc = s2f_build(m, w, n_weights);
     if (rc) { pgmi_s2f_destroy(m); return rc; }
     *out = m;
     return PGMI_OK;
 }
+
+}  // namespace pgmi
+
+extern "C" {
 
 void pgmi_s2f_destroy(pgmi_s2f* m) {
     if (!m) return;
@@ -433,7 +424,7 @@ void pgmi_s2f_destroy(pgmi_s2f* m) {
     if (m->pm.stream) hipStreamSynchronize(m->pm.stream);
     for (ProfEvent& e : m->pm.events) { hipEventDestroy(e.start); hipEventDestroy(e.stop); }
     for (void* p : m->pm.allocs) hipFree(p);
-    if (m->pm.stream && !m->esm) hipStreamDestroy(m->pm.stream);
+    if (m->pm.stream && m->own_stream) hipStreamDestroy(m->pm.stream);
     delete m;
 }
 

@@ -289,6 +289,18 @@ void launch_s2f_head(const float* x, const float* W, const float* bias, const fl
 void launch_s2f_pick_logits(const float* lp, const int32_t* cols, int L, int T, int V, int64_t rows, float* out, hipStream_t s);
 int s2f_set_option(const char* name, long long value);    // api_s2f.hip: "s2f_max_rows"
 
+// S3F (s3f.hip; operands and shapes at the kernels)
+int launch_s3f_knn(const float* q, int nq, const float* c, int nc, int k, int32_t* idx, float* dist, hipStream_t s);
+void launch_s3f_edges(const float* pos, const int32_t* src, int Ns, const float* we, float* es, float* ev, hipStream_t s);
+int launch_s3f_rows(const float* Z, const float* T, const int32_t* res, const float* lnw, const float* lnb, int L, int Ns, int H, int64_t rows,
+                    float* out, hipStream_t s);
+int launch_s3f_message(const float* P, const float* VT, const float* Es, const float* ev, const float* whe, const float* Wnt,
+                       const S2fMsgWeights& w, const int32_t* src, int Ns, int64_t nodes, float* ds, float* dv, hipStream_t s);
+int s3f_colsum_blocks(int Ns);
+void launch_s3f_colsum(const float* x, int Ns, int copies, float* part, float* sums, hipStream_t s);
+void launch_s3f_head(const float* x, const float* sums, const int32_t* grp, int Ns, const float* W, const float* bias, const float* seq,
+                     const float* plddt, float thr, int L, int64_t rows, float* lp, hipStream_t s);
+
 // ---- mlstm.hip (UniRep's mLSTM step around the two GEMMs; the kernels are described there) -------------------------------------
 // m = Tmx[tok[row * tok_stride]] * g1 [rows][Hp] -> the second product's operand: split rows m16, or fp32 m32 (exactly one)
 void launch_mlstm_m(const float* g1, const float* Tmx, const int32_t* tok, int tok_stride, int rows, int Hp, unsigned short* m16,
