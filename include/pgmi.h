@@ -1065,6 +1065,59 @@ int pgmi_op_ln_gelu(int device, int precision, const float* x, const float* w, c
  * then the mean milliseconds of `iters` launches between two events. */
 int pgmi_bench_dilated_conv(int device, int M, int n_seg, int C, int taps, int dilation, int iters, double* ms_per_launch);
 
+/* ---- ProtSSN (an EGNN over the k-nearest C-alpha graph on ESM2's residue rows; its own handle and config; additions only, the ABI
+ * version is unchanged) ------------------------------------------------------------------------------------------------------------
+ * Replaces the GNN_model forward of proteingym/baselines/protssn (src/module/egnn/network.py EGNN, egnn_pytorch_geometric.py
+ * EGNN_Sparse with mlp_num 2, dropout 0, no coordinate update, no norms, no soft edge) and the ESM2 rows PLM_model feeds it.  The
+ * graph, its 93 edge attributes and the normalisation are built on the host (proteingym_amd/protssn.py); DESIGN.md 4.6q.
+ * Dimensions: D = node_in, h = hidden (m_dim), A = edge_attr_dim; the first edge Linear is Hh = 2 (2 D + A + 1) wide.  Padded:
+ *   Hp = roundup(Hh, 32), hp = roundup(h, 32), Ap = roundup(A + 1, 32); every pad row, column and bias is zero.
+ * Weight blob (fp32, what proteingym_amd/protssn.py pack writes; nn.Linear [out, in]), per layer n of mpnn_layes:
+ *   Wij [2 Hp][D]      edge_mlp.0.weight's columns 0 .. D (rows 0 .. Hp: they meet x[edge_index[1]], the neighbour) and D .. 2 D
+ *                      (rows Hp .. 2 Hp: they meet x[edge_index[0]], the centre)
+ *   We  [Hp][Ap]       its columns 2 D .. 2 D + A + 1: the edge attributes, then the squared distance of the normalised positions
+ *   b1  [Hp]           edge_mlp.0.bias
+ *   W2  [hp][Hp], b2 [hp]           edge_mlp.3
+ *   W3  [2 D][D + hp], b3 [2 D]     node_mlp.0 (input columns x | m_i)
+ *   W4  [D][2 D], b4 [D]            node_mlp.3
+ *   then lin.weight [20][D], lin.bias [20].
+ * pgmi_protssn_weight_count: size of that blob; -1 for a config the library refuses (pgmi_last_error).
+ * pgmi_protssn_create / pgmi_protssn_destroy: the device-resident checkpoint (one HIP stream).
+ * pgmi_protssn_profile_model: the handle's profiling view (owned by the handle).  Classes: PGMI_K_EMBED = the graph's upload
+ *   (pgmi_protssn_set_graph) and the edge share e We^T + b1, PGMI_K_GEMM_QKV = the per-node tables x [Wi; Wj]^T,
+ *   PGMI_K_ATTENTION = the edge-row kernel, PGMI_K_GEMM_OUT = the W2 product, PGMI_K_LAYERNORM = the aggregation (and the split of
+ *   x), PGMI_K_GEMM_FC1 = W3, PGMI_K_KEPT_ROWS = the SiLU between W3 and W4, PGMI_K_GEMM_FC2 = W4 + residual, PGMI_K_HEAD = the
+ *   20-way Linear and log(softmax + 1e-9).
+ * pgmi_protssn_set_graph: the host-built, already normalised graph: pos f32 [L][3], n_edges edges (centre[e], neighbour[e]) =
+ *   (edge_index[0], edge_index[1]), edge_attr f32 [n_edges][A].  The squared distance |pos[centre] - pos[neighbour]|^2 (fp32) and
+ *   the CSR by neighbour (stable: ascending edge order per node) are formed here.  The arrays are free to go on return.
+ * pgmi_protssn_forward: esm_rep f32 [L][D] -> lp f32 [L][20] = log(softmax(lin(x_6)) + 1e-9); hidden (nullable) f32 [L][D] = x_6.
+ *   Edges are processed in chunks of edge_chunk; a row's bits do not depend on the chunk size.
+ * pgmi_esm_residue_rows: one unmasked forward of tokens int32 [T] (<cls> + residues + <eos>) through an ESM2 model; rows f32
+ *   [T - 2][D] = the residue rows after emb_layer_norm_after (HF EsmModel's last_hidden_state[1 : T - 1]).
+ * pgmi_op_egnn_message: one layer's message and aggregation alone on host pointers: weights = a one-layer blob as above, the graph as
+ *   pgmi_protssn_set_graph takes it, x f32 [L][D]; out f32 [L][h] = m_i (precision f16x3: the split operand rebuilt as hi + lo 2^-11).
+ * PGMI_EINVAL before any device work: node_in not a multiple of 32 in 32 .. 8192, hidden outside 1 .. 4096, L < 2, an edge index
+ *   outside 0 .. L - 1, a self edge, a non-finite value. */
+typedef struct pgmi_protssn_config {
+    int32_t abi_version;                          /* = PGMI_ABI_VERSION */
+    int32_t node_in, hidden, layers;              /* 1280; 512, 768 or 1280; 6 */
+    int32_t edge_attr_dim;                        /* 93 */
+    int32_t precision;                            /* PGMI_PREC_F16X3 or PGMI_PREC_FP32 */
+    int32_t edge_chunk;                           /* edges per chunk of the per-edge stages; 0 = 8192 */
+} pgmi_protssn_config;
+typedef struct pgmi_protssn pgmi_protssn;
+int64_t pgmi_protssn_weight_count(const pgmi_protssn_config* cfg);
+int pgmi_protssn_create(const pgmi_protssn_config* cfg, const float* weights, int64_t n_weights, int device, pgmi_protssn** out);
+void pgmi_protssn_destroy(pgmi_protssn* m);
+pgmi_model* pgmi_protssn_profile_model(pgmi_protssn* m);
+int pgmi_protssn_set_graph(pgmi_protssn* m, const float* pos, int L, int n_edges, const int32_t* centre, const int32_t* neighbour,
+                           const float* edge_attr);
+int pgmi_protssn_forward(pgmi_protssn* m, const float* esm_rep, float* lp, float* hidden);
+int pgmi_esm_residue_rows(pgmi_model* esm, const int32_t* tokens, int T, float* rows);
+int pgmi_op_egnn_message(int device, const pgmi_protssn_config* cfg, const float* weights, int64_t n_weights, const float* pos, int L,
+                         int n_edges, const int32_t* centre, const int32_t* neighbour, const float* edge_attr, const float* x, float* out);
+
 /* ---- MSA Transformer (arch PGMI_ARCH_MSA; vocab 33, head_dim 64, precision f16x3) --------------------
  * Replaces MSATransformer.forward (proteingym/baselines/esm/esm/model/msa_transformer.py:146-205; tied
  * row attention esm/axial_attention.py:33-168, column attention :171-297) and the masked-marginals loop

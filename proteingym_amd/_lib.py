@@ -179,6 +179,14 @@ SIGNATURES = [
     ("pgmi_op_dilated_conv", C.c_int, [C.c_int, C.c_int, _f32p, _f32p, _f32p, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),
     ("pgmi_op_ln_gelu", C.c_int, [C.c_int, C.c_int, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_float, _f32p]),
     ("pgmi_bench_dilated_conv", C.c_int, [C.c_int] * 7 + [_f64p]),
+    ("pgmi_protssn_weight_count", C.c_int64, [C.c_void_p]),
+    ("pgmi_protssn_create", C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
+    ("pgmi_protssn_destroy", None, [C.c_void_p]),
+    ("pgmi_protssn_profile_model", C.c_void_p, [C.c_void_p]),
+    ("pgmi_protssn_set_graph", C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, _i32p, _i32p, _f32p]),
+    ("pgmi_protssn_forward", C.c_int, [C.c_void_p, _f32p, _f32p, _f32p]),
+    ("pgmi_esm_residue_rows", C.c_int, [C.c_void_p, _i32p, C.c_int, _f32p]),
+    ("pgmi_op_egnn_message", C.c_int, [C.c_int, C.c_void_p, _f32p, C.c_int64, _f32p, C.c_int, C.c_int, _i32p, _i32p, _f32p, _f32p, _f32p]),
     ("pgmi_bench_gemm", C.c_int, [C.c_int] * 9 + [_f64p]),
     ("pgmi_bench_gemm_ab", C.c_int, [C.c_int] * 7 + [_i32p, C.c_int, C.c_int, C.c_int, _f64p]),
     ("pgmi_op_attention", C.c_int, [C.c_int, C.c_int, _f32p, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),

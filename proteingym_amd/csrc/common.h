@@ -301,6 +301,14 @@ void launch_s3f_colsum(const float* x, int Ns, int copies, float* part, float* s
 void launch_s3f_head(const float* x, const float* sums, const int32_t* grp, int Ns, const float* W, const float* bias, const float* seq,
                      const float* plddt, float thr, int L, int64_t rows, float* lp, hipStream_t s);
 
+// ProtSSN's EGNN (egnn.hip; operands and shapes at the kernels).  split: the operand is written as K-interleaved split planes, else fp32 rows
+void launch_egnn_edge_rows(const float* P, const float* S, const int32_t* centre, const int32_t* nb, int edges, int Hp, bool split, void* out,
+                           hipStream_t s);
+void launch_egnn_aggregate(const float* x, const float* msg, const int32_t* off, const int32_t* eid, int L, int D, int hp, bool split, void* out,
+                           hipStream_t s);
+void launch_egnn_silu_rows(const float* t, int rows, int F, float* out, hipStream_t s);
+void launch_egnn_head(const float* x, const float* W, const float* bias, int rows, int D, float* lp, hipStream_t s);
+
 // ---- mlstm.hip (UniRep's mLSTM step around the two GEMMs; the kernels are described there) -------------------------------------
 // m = Tmx[tok[row * tok_stride]] * g1 [rows][Hp] -> the second product's operand: split rows m16, or fp32 m32 (exactly one)
 void launch_mlstm_m(const float* g1, const float* Tmx, const int32_t* tok, int tok_stride, int rows, int Hp, unsigned short* m16,

@@ -28,6 +28,8 @@
 //                        decoder tables), the per-batch decoder and head
 //   api_carp.hip         CARP: its own handle (pgmi_carp), blob walk, the ByteNet forward over packed sequences (conv_f16.hip), masked
 //                        rows / token log-probs / sequence log-likelihoods, the convolution's and the row kernel's op entries
+//   api_protssn.hip      ProtSSN: its own handle (pgmi_protssn), blob walk, the graph of one structure, the EGNN forward in edge chunks
+//                        (egnn.hip around the existing GEMMs), the ESM2 residue rows that feed it, the message op entry
 //   api_msa.hip          MSA Transformer weights and forward (tied row attention, column attention)
 //   api_host.hip         host-only entries: mutant parser, table -> scores, optimal window
 //   api_ops.hip          single-op and timing entries for the numerics tests and the A/B scripts
