@@ -389,11 +389,7 @@ int pgmi_eve_create(const pgmi_eve_config* cfg, const float* w, int64_t n_weight
 
 void pgmi_eve_destroy(pgmi_eve* m) {
     if (!m) return;
-    hipSetDevice(m->pm.device);
-    if (m->pm.stream) hipStreamSynchronize(m->pm.stream);
-    for (ProfEvent& e : m->pm.events) { hipEventDestroy(e.start); hipEventDestroy(e.stop); }
-    for (void* p : m->pm.allocs) hipFree(p);
-    if (m->pm.stream) hipStreamDestroy(m->pm.stream);
+    side_release(&m->pm, true);
     delete m;
 }
 

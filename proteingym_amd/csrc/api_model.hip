@@ -439,6 +439,19 @@ int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int 
 
 }  // namespace pgmi
 
+namespace pgmi {
+
+// what a side handle's embedded pgmi_model holds: after the stream's work, its profiling events, its pool and the stream if it is the handle's
+void side_release(pgmi_model* pm, bool own_stream) {
+    hipSetDevice(pm->device);
+    if (pm->stream) hipStreamSynchronize(pm->stream);
+    for (ProfEvent& e : pm->events) { hipEventDestroy(e.start); hipEventDestroy(e.stop); }
+    for (void* p : pm->allocs) hipFree(p);
+    if (pm->stream && own_stream) hipStreamDestroy(pm->stream);
+}
+
+}  // namespace pgmi
+
 extern "C" {
 
 void pgmi_model_destroy(pgmi_model* m) {

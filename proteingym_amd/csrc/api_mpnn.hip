@@ -378,11 +378,7 @@ int pgmi_mpnn_create(const pgmi_mpnn_config* cfg, const float* w, int64_t n_weig
 
 void pgmi_mpnn_destroy(pgmi_mpnn* m) {
     if (!m) return;
-    hipSetDevice(m->pm.device);
-    if (m->pm.stream) hipStreamSynchronize(m->pm.stream);
-    for (ProfEvent& e : m->pm.events) { hipEventDestroy(e.start); hipEventDestroy(e.stop); }
-    for (void* p : m->pm.allocs) hipFree(p);
-    if (m->pm.stream) hipStreamDestroy(m->pm.stream);
+    side_release(&m->pm, true);
     delete m;
 }
 

@@ -273,11 +273,7 @@ int pgmi_protssn_create(const pgmi_protssn_config* cfg, const float* w, int64_t 
 
 void pgmi_protssn_destroy(pgmi_protssn* m) {
     if (!m) return;
-    hipSetDevice(m->pm.device);
-    if (m->pm.stream) hipStreamSynchronize(m->pm.stream);
-    for (ProfEvent& e : m->pm.events) { hipEventDestroy(e.start); hipEventDestroy(e.stop); }
-    for (void* p : m->pm.allocs) hipFree(p);
-    if (m->pm.stream) hipStreamDestroy(m->pm.stream);
+    side_release(&m->pm, true);
     delete m;
 }
 

@@ -3,6 +3,7 @@
 // rows of the masked copies.  The kernels are in s2f.hip.  Dense Linears are launch_gemm_f32: a GEMM output element is a two-level sum
 // whose order does not depend on the row count, the message kernel works on one node of one copy per block and sums its edges in
 // ascending order, and every other kernel is one wave per row, so a masked copy's bits do not depend on the batch or the chunking.
+#include <cctype>
 #include <cmath>
 
 #include "s2f_impl.h"
@@ -187,6 +188,16 @@ static void s2f_edge_embed(const pgmi_s2f* m, const float* pos, std::vector<floa
 
 int s2f_buf(pgmi_s2f* m, S2fBuf* b, size_t n) { return ensure_cap(&m->pm, &b->p, &b->cap, n); }
 
+// every layer's edge share of the first message GVP from the E > 0 rows of m->es: Es = We e_s + b [E][256]
+int s2f_edge_tables(pgmi_s2f* m, size_t E) {
+    int rc = PGMI_OK;
+    for (S2fLayer& l : m->layers) {
+        if (!rc) rc = ensure_cap(&m->pm, &l.Es, &l.Es_cap, E * S2F_S);
+        if (!rc) rc = launch_gemm_f32(m->es.p, l.We, l.b0, nullptr, l.Es, (int)E, S2F_S, S2F_ES, EPI_NONE, m->pm.stream);
+    }
+    return rc;
+}
+
 int s2f_structure(pgmi_s2f* m, const float* pos, const float* plddt, int L) {
     pgmi_model* pm = &m->pm;
     hipStream_t st = pm->stream;
@@ -200,8 +211,6 @@ int s2f_structure(pgmi_s2f* m, const float* pos, const float* plddt, int L) {
     if (!rc) rc = s2f_buf(m, &m->es, En * S2F_ES);
     if (!rc) rc = s2f_buf(m, &m->ev, En * 3);
     if (!rc) rc = s2f_buf(m, &m->plddt, (size_t)L);
-    for (S2fLayer& l : m->layers)
-        if (!rc) rc = ensure_cap(pm, &l.Es, &l.Es_cap, En * S2F_S);
     if (rc) return rc;
     auto upload = [&](void* dst, const void* src, size_t bytes) {
         if (rc || !bytes || hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) == hipSuccess) return;
@@ -215,8 +224,7 @@ int s2f_structure(pgmi_s2f* m, const float* pos, const float* plddt, int L) {
     upload(m->plddt.p, plddt, (size_t)L * 4);
     if (!rc && E > 0) {
         ProfScope prof(pm, PGMI_K_EMBED, 2.0 * E * S2F_S * S2F_ES * m->layers.size(), 0);
-        for (S2fLayer& l : m->layers)
-            if (!rc) rc = launch_gemm_f32(m->es.p, l.We, l.b0, nullptr, l.Es, E, S2F_S, S2F_ES, EPI_NONE, st);
+        rc = s2f_edge_tables(m, (size_t)E);
     }
     const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(st);       // the caller's arrays are free to go after this
     if (!rc && (e1 != hipSuccess || e2 != hipSuccess)) {
@@ -340,10 +348,11 @@ int s2f_layers(pgmi_s2f* m, int bc) {
     return PGMI_OK;
 }
 
-// relu, the 20-way Linear, the ESM logits on low-pLDDT rows and the log-softmax on `rows` rows of W_out's output
-int s2f_head(pgmi_s2f* m, const float* pre, const float* seq, int64_t rows, float* lp) {
+// relu, the 20-way Linear, the ESM logits on low-pLDDT rows and the log-softmax on `rows` rows of W_out's output; S3F adds the pooled
+// row of a row's pool group (sums, grp, Ns: s2f_head_kernel; null, null, 0 without)
+int s2f_head(pgmi_s2f* m, const float* pre, const float* seq, const float* sums, const int32_t* grp, int Ns, int64_t rows, float* lp) {
     ProfScope p(&m->pm, PGMI_K_HEAD, 2.0 * rows * S2F_S * 20, 0);
-    launch_s2f_head(pre, m->Wlin, m->blin, seq, m->plddt.p, m->cfg.plddt_threshold, m->L, rows, lp, m->pm.stream);
+    launch_s2f_head(pre, sums, grp, Ns, m->Wlin, m->blin, seq, m->plddt.p, m->cfg.plddt_threshold, m->L, rows, lp, m->pm.stream);
     PGMI_HIP(hipGetLastError());
     return PGMI_OK;
 }
@@ -352,8 +361,94 @@ int s2f_head(pgmi_s2f* m, const float* pre, const float* seq, int64_t rows, floa
 static int s2f_gnn(pgmi_s2f* m, int bc) {
     int rc = s2f_embed(m, bc);
     if (!rc) rc = s2f_layers(m, bc);
-    if (!rc) rc = s2f_head(m, m->pre.p, m->seq.p, (int64_t)bc * m->L, m->lp.p);
+    if (!rc) rc = s2f_head(m, m->pre.p, m->seq.p, nullptr, nullptr, 0, (int64_t)bc * m->L, m->lp.p);
     return rc;
+}
+
+// copies [s0, s0 + bc) of a gvp_forward call: their rows of node_feat [.][L][D] and seq_logits [.][L][20] -> m->feat, m->seq
+int s2f_fill_rows(pgmi_s2f* m, const float* node_feat, const float* seq_logits, int s0, int bc) {
+    const size_t R = (size_t)bc * m->L, r0 = (size_t)s0 * m->L, D = m->D;
+    PGMI_HIP(hipMemcpyAsync(m->feat.p, node_feat + r0 * D, R * D * 4, hipMemcpyHostToDevice, m->pm.stream));
+    PGMI_HIP(hipMemcpyAsync(m->seq.p, seq_logits + r0 * 20, R * 20 * 4, hipMemcpyHostToDevice, m->pm.stream));
+    return PGMI_OK;
+}
+
+// the arguments of a set_logprobs entry of model `name` ("S2F", "S3F") on a handle with a structure
+int s2f_check_sets(const pgmi_s2f* m, const char* name, const int32_t* wt_tokens, int T, const int32_t* aa_cols, const int32_t* set_off,
+                   const int32_t* set_pos, int n_sets, const float* out) {
+    const pgmi_model* esm = m->esm;
+    if (!esm) {
+        char fn[8] = {0};                                      // the entry's prefix: the name in lower case
+        for (int i = 0; i < 7 && name[i]; ++i) fn[i] = (char)tolower(name[i]);
+        set_error("%s: this handle was created without an ESM2 model (pgmi_%s_gvp_forward only)", name, fn);
+        return PGMI_EINVAL;
+    }
+    if (!wt_tokens || !aa_cols || !set_off || !set_pos || !out || n_sets <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
+    const int L = m->L, V = esm->cfg.vocab;
+    if (T != L + 2) { set_error("%s: T = %d tokens, the structure has %d residues (<cls> + residues + <eos>)", name, T, L); return PGMI_EINVAL; }
+    if (T + 31 > esm->max_rows) { set_error("T=%d exceeds the ESM2 model's workspace rows %d", T, esm->max_rows); return PGMI_EINVAL; }
+    const int rc = check_tokens(wt_tokens, 1, T, esm->n_token_ids);
+    if (rc) return rc;
+    for (int c = 0; c < 20; ++c)
+        if (aa_cols[c] < 0 || aa_cols[c] >= V) { set_error("%s: amino-acid column %d = %d outside the vocabulary (%d)", name, c, aa_cols[c], V); return PGMI_EINVAL; }
+    if (set_off[0] != 0) { set_error("set_off[0] must be 0"); return PGMI_EINVAL; }
+    for (int s = 0; s < n_sets; ++s) {
+        if (set_off[s + 1] <= set_off[s] || set_off[s + 1] - set_off[s] > L) { set_error("position set %d is empty or larger than L", s); return PGMI_EINVAL; }
+        for (int e = set_off[s]; e < set_off[s + 1]; ++e) {
+            const int p = set_pos[e];
+            if (p < 0 || p >= L || (e > set_off[s] && p <= set_pos[e - 1])) { set_error("position set %d: residue %d out of range or not ascending", s, p); return PGMI_EINVAL; }
+        }
+    }
+    return PGMI_OK;
+}
+
+// what the ESM2 fill of chunks of `per` copies needs: the device index arrays, aa_cols on the device, the host scratch
+int s2f_set_buffers(pgmi_s2f* m, int per, int T, const int32_t* aa_cols, S2fSetHost* h) {
+    pgmi_model* pm = &m->pm;
+    int rc = ensure_cap(pm, &m->ridx, &m->ridx_cap, (size_t)per * m->L);
+    if (!rc) rc = ensure_cap(pm, &m->toks, &m->toks_cap, (size_t)per * T);
+    if (!rc) rc = ensure_cap(pm, &m->cols, &m->cols_cap, (size_t)20);
+    if (rc) return rc;
+    PGMI_HIP(hipMemcpyAsync(m->cols, aa_cols, 20 * 4, hipMemcpyHostToDevice, pm->stream));
+    h->toks.resize((size_t)per * T);
+    h->ridx.resize((size_t)per * m->L);
+    return PGMI_OK;
+}
+
+// masked copies [s0, s0 + bc) of the wild type, one per position set: ESM2 on them, then m->feat [bc L][D] = emb_layer_norm_after of
+// the residue rows and m->seq [bc L][20] = the amino-acid columns of ESM2's log-probability rows, both left on the stream
+int s2f_fill_esm(pgmi_s2f* m, const int32_t* wt_tokens, int T, const int32_t* set_off, const int32_t* set_pos, int s0, int bc, S2fSetHost* h) {
+    pgmi_model* esm = m->esm;
+    hipStream_t st = m->pm.stream;
+    const int L = m->L, D = m->D, M = bc * T;
+    const int64_t R = (int64_t)bc * L;
+    for (int b = 0; b < bc; ++b) {
+        memcpy(&h->toks[(size_t)b * T], wt_tokens, (size_t)T * 4);
+        for (int e = set_off[s0 + b]; e < set_off[s0 + b + 1]; ++e) h->toks[(size_t)b * T + 1 + set_pos[e]] = esm->mask_id;
+        for (int i = 0; i < L; ++i) h->ridx[(size_t)b * L + i] = b * T + 1 + i;
+    }
+    PGMI_HIP(hipMemcpyAsync(esm->tokens, h->toks.data(), (size_t)M * 4, hipMemcpyHostToDevice, st));
+    PGMI_HIP(hipMemcpyAsync(m->ridx, h->ridx.data(), (size_t)R * 4, hipMemcpyHostToDevice, st));
+    int rc = run_encoder(esm, bc, T);
+    if (rc) return rc;
+    {   // residue_feature: emb_layer_norm_after on the L residue rows, fp32
+        ProfScope p(esm, PGMI_K_LAYERNORM, 0, (double)R * D * 8);
+        launch_gather_rows(esm->x, m->ridx, (int)R, D, m->feat.p, st);
+        launch_layernorm(m->feat.p, esm->lna_w, esm->lna_b, (int)R, D, 1e-5f, m->feat.p, st);
+    }
+    rc = run_head(esm, M, nullptr);                        // esm->lp [M][V]: the log-softmax rows; the 20-way log-softmax drops the shift
+    if (rc) return rc;
+    launch_s2f_pick_logits(esm->lp, m->cols, L, T, esm->cfg.vocab, R, m->seq.p, st);
+    return PGMI_OK;
+}
+
+// lp [bc][L][20] (host) = the tables of sets [s0, s0 + bc): each whole into `full` (nullable), its set's rows into `out`
+void s2f_scatter(const float* lp, int L, const int32_t* set_off, const int32_t* set_pos, int s0, int bc, float* out, float* full) {
+    for (int b = 0; b < bc; ++b) {
+        if (full) memcpy(full + (size_t)(s0 + b) * L * 20, lp + (size_t)b * L * 20, (size_t)L * 20 * 4);
+        for (int e = set_off[s0 + b]; e < set_off[s0 + b + 1]; ++e)
+            memcpy(out + (size_t)e * 20, lp + ((size_t)b * L + set_pos[e]) * 20, 20 * 4);
+    }
 }
 
 static int s2f_ready(pgmi_s2f* m) {
@@ -420,11 +515,7 @@ extern "C" {
 
 void pgmi_s2f_destroy(pgmi_s2f* m) {
     if (!m) return;
-    hipSetDevice(m->pm.device);
-    if (m->pm.stream) hipStreamSynchronize(m->pm.stream);
-    for (ProfEvent& e : m->pm.events) { hipEventDestroy(e.start); hipEventDestroy(e.stop); }
-    for (void* p : m->pm.allocs) hipFree(p);
-    if (m->pm.stream && m->own_stream) hipStreamDestroy(m->pm.stream);
+    side_release(&m->pm, m->own_stream);
     delete m;
 }
 
@@ -460,14 +551,13 @@ int pgmi_s2f_gvp_forward(pgmi_s2f* m, const float* node_feat, const float* seq_l
     PGMI_HIP(hipSetDevice(m->pm.device));
     pgmi_model* pm = &m->pm;
     hipStream_t st = pm->stream;
-    const int L = m->L, D = m->D, per = s2f_per_chunk(m, B);
+    const int L = m->L, per = s2f_per_chunk(m, B);
     rc = s2f_workspace(m, per);
     for (int b0 = 0; b0 < B && !rc; b0 += per) {
         const int bc = std::min(per, B - b0);
         const size_t R = (size_t)bc * L, r0 = (size_t)b0 * L;
-        PGMI_HIP(hipMemcpyAsync(m->feat.p, node_feat + r0 * D, R * D * 4, hipMemcpyHostToDevice, st));
-        PGMI_HIP(hipMemcpyAsync(m->seq.p, seq_logits + r0 * 20, R * 20 * 4, hipMemcpyHostToDevice, st));
-        rc = s2f_gnn(m, bc);
+        rc = s2f_fill_rows(m, node_feat, seq_logits, b0, bc);
+        if (!rc) rc = s2f_gnn(m, bc);
         if (rc) break;
         PGMI_HIP(hipMemcpyAsync(lp + r0 * 20, m->lp.p, R * 20 * 4, hipMemcpyDeviceToHost, st));
         if (node_s) PGMI_HIP(hipMemcpyAsync(node_s + r0 * S2F_S, m->s.p, R * S2F_S * 4, hipMemcpyDeviceToHost, st));
@@ -484,66 +574,25 @@ int pgmi_s2f_set_logprobs(pgmi_s2f* m, const int32_t* wt_tokens, int T, const in
                           const int32_t* set_pos, int n_sets, float* out, float* full) {
     int rc = s2f_ready(m);
     if (rc) return rc;
-    pgmi_model* esm = m->esm;
-    if (!esm) { set_error("S2F: this handle was created without an ESM2 model (pgmi_s2f_gvp_forward only)"); return PGMI_EINVAL; }
-    if (!wt_tokens || !aa_cols || !set_off || !set_pos || !out || n_sets <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
-    const int L = m->L, D = m->D, V = esm->cfg.vocab;
-    if (T != L + 2) { set_error("S2F: T = %d tokens, the structure has %d residues (<cls> + residues + <eos>)", T, L); return PGMI_EINVAL; }
-    if (T + 31 > esm->max_rows) { set_error("T=%d exceeds the ESM2 model's workspace rows %d", T, esm->max_rows); return PGMI_EINVAL; }
-    rc = check_tokens(wt_tokens, 1, T, esm->n_token_ids);
+    rc = s2f_check_sets(m, "S2F", wt_tokens, T, aa_cols, set_off, set_pos, n_sets, out);
     if (rc) return rc;
-    for (int c = 0; c < 20; ++c)
-        if (aa_cols[c] < 0 || aa_cols[c] >= V) { set_error("S2F: amino-acid column %d = %d outside the vocabulary (%d)", c, aa_cols[c], V); return PGMI_EINVAL; }
-    if (set_off[0] != 0) { set_error("set_off[0] must be 0"); return PGMI_EINVAL; }
-    for (int s = 0; s < n_sets; ++s) {
-        if (set_off[s + 1] <= set_off[s] || set_off[s + 1] - set_off[s] > L) { set_error("position set %d is empty or larger than L", s); return PGMI_EINVAL; }
-        for (int e = set_off[s]; e < set_off[s + 1]; ++e) {
-            const int p = set_pos[e];
-            if (p < 0 || p >= L || (e > set_off[s] && p <= set_pos[e - 1])) { set_error("position set %d: residue %d out of range or not ascending", s, p); return PGMI_EINVAL; }
-        }
-    }
     PGMI_HIP(hipSetDevice(m->pm.device));
-    pgmi_model* pm = &m->pm;
+    pgmi_model *pm = &m->pm, *esm = m->esm;
     hipStream_t st = pm->stream;
-    const int per = std::min(s2f_per_chunk(m, n_sets), rows_per_chunk(esm, T));
+    const int L = m->L, per = std::min(s2f_per_chunk(m, n_sets), rows_per_chunk(esm, T));
+    S2fSetHost host;
     rc = s2f_workspace(m, per);
-    if (!rc) rc = ensure_cap(pm, &m->ridx, &m->ridx_cap, (size_t)per * L);
-    if (!rc) rc = ensure_cap(pm, &m->toks, &m->toks_cap, (size_t)per * T);
-    if (!rc) rc = ensure_cap(pm, &m->cols, &m->cols_cap, (size_t)20);
+    if (!rc) rc = s2f_set_buffers(m, per, T, aa_cols, &host);
     if (rc) return rc;
-    PGMI_HIP(hipMemcpyAsync(m->cols, aa_cols, 20 * 4, hipMemcpyHostToDevice, st));
-    std::vector<int32_t> toks((size_t)per * T), ridx((size_t)per * L);
     std::vector<float> lp((size_t)per * L * 20);
     for (int s0 = 0; s0 < n_sets && !rc; s0 += per) {
         const int bc = std::min(per, n_sets - s0);
-        const int M = bc * T;
-        const int64_t R = (int64_t)bc * L;
-        for (int b = 0; b < bc; ++b) {
-            memcpy(&toks[(size_t)b * T], wt_tokens, (size_t)T * 4);
-            for (int e = set_off[s0 + b]; e < set_off[s0 + b + 1]; ++e) toks[(size_t)b * T + 1 + set_pos[e]] = esm->mask_id;
-            for (int i = 0; i < L; ++i) ridx[(size_t)b * L + i] = b * T + 1 + i;
-        }
-        PGMI_HIP(hipMemcpyAsync(esm->tokens, toks.data(), (size_t)M * 4, hipMemcpyHostToDevice, st));
-        PGMI_HIP(hipMemcpyAsync(m->ridx, ridx.data(), (size_t)R * 4, hipMemcpyHostToDevice, st));
-        rc = run_encoder(esm, bc, T);
+        rc = s2f_fill_esm(m, wt_tokens, T, set_off, set_pos, s0, bc, &host);
+        if (!rc) rc = s2f_gnn(m, bc);
         if (rc) break;
-        {   // residue_feature: emb_layer_norm_after on the L residue rows, fp32
-            ProfScope p(esm, PGMI_K_LAYERNORM, 0, (double)R * D * 8);
-            launch_gather_rows(esm->x, m->ridx, (int)R, D, m->feat.p, st);
-            launch_layernorm(m->feat.p, esm->lna_w, esm->lna_b, (int)R, D, 1e-5f, m->feat.p, st);
-        }
-        rc = run_head(esm, M, nullptr);                    // esm->lp [M][V]: the log-softmax rows; the 20-way log-softmax drops the shift
-        if (rc) break;
-        launch_s2f_pick_logits(esm->lp, m->cols, L, T, V, R, m->seq.p, st);
-        rc = s2f_gnn(m, bc);
-        if (rc) break;
-        PGMI_HIP(hipMemcpyAsync(lp.data(), m->lp.p, (size_t)R * 20 * 4, hipMemcpyDeviceToHost, st));
+        PGMI_HIP(hipMemcpyAsync(lp.data(), m->lp.p, (size_t)bc * L * 20 * 4, hipMemcpyDeviceToHost, st));
         PGMI_HIP(hipStreamSynchronize(st));
-        for (int b = 0; b < bc; ++b) {
-            if (full) memcpy(full + (size_t)(s0 + b) * L * 20, &lp[(size_t)b * L * 20], (size_t)L * 20 * 4);
-            for (int e = set_off[s0 + b]; e < set_off[s0 + b + 1]; ++e)
-                memcpy(out + (size_t)e * 20, &lp[((size_t)b * L + set_pos[e]) * 20], 20 * 4);
-        }
+        s2f_scatter(lp.data(), L, set_off, set_pos, s0, bc, out, full);
         if (pm->prof) rc = prof_drain(pm);
         if (!rc && esm->prof) rc = prof_drain(esm);
     }

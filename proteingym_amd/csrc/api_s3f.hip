@@ -10,7 +10,7 @@
 #include "s2f_impl.h"
 
 namespace pgmi {
-constexpr int S3F_FEAT = 42, S3F_RES = 3, S3F_DEG = 16;
+constexpr int S3F_FEAT = 42, S3F_RES = 3;
 constexpr int S3F_KF = 64;                            // the structure term's operand row: 42 features | mean distance | 0 pad
 constexpr int S3F_MAX_NS = 1 << 20;
 }  // namespace pgmi
@@ -78,8 +78,6 @@ static int s3f_structure(pgmi_s3f* m, const float* pos, int L, const float* surf
     if (!rc) rc = s2f_buf(sf, &sf->ev, E * 3);
     if (!rc) rc = s2f_buf(sf, &m->T, (size_t)Ns * H);
     if (!rc) rc = s2f_buf(sf, &m->Asf, (size_t)Ns * S3F_KF);
-    for (S2fLayer& l : sf->layers)
-        if (!rc) rc = ensure_cap(pm, &l.Es, &l.Es_cap, E * S2F_S);
     if (rc) return rc;
     ProfScope prof(pm, PGMI_K_EMBED, 2.0 * E * S2F_S * S2F_ES * sf->layers.size() + 2.0 * Ns * H * S3F_KF, 0);
     PGMI_HIP(hipMemcpyAsync(m->spos, surf_pos, (size_t)Ns * 3 * 4, hipMemcpyHostToDevice, st));
@@ -94,8 +92,7 @@ static int s3f_structure(pgmi_s3f* m, const float* pos, int L, const float* surf
     PGMI_HIP(hipMemcpyAsync(m->h_rnb.data(), m->rnb, (size_t)Ns * S3F_RES * 4, hipMemcpyDeviceToHost, st));
     PGMI_HIP(hipMemcpyAsync(m->h_rdist.data(), m->rdist, (size_t)Ns * S3F_RES * 4, hipMemcpyDeviceToHost, st));
     launch_s3f_edges(m->spos, sf->src, Ns, m->we, sf->es.p, sf->ev.p, st);
-    for (S2fLayer& l : sf->layers)
-        if (!rc) rc = launch_gemm_f32(sf->es.p, l.We, l.b0, nullptr, l.Es, (int)E, S2F_S, S2F_ES, EPI_NONE, st);
+    rc = s2f_edge_tables(sf, E);
     if (rc) return rc;
     PGMI_HIP(hipStreamSynchronize(st));
     // the structure term's operand rows: [features | mean of the three distances | 0]
@@ -182,17 +179,12 @@ static int s3f_copies(pgmi_s3f* m, int bc, int h0) {
 // the group step on the n held copies [a, a + n) = pool groups [g0, g1): the head on relu(W_out) + the pooled row -> hold_lp
 static int s3f_finish(pgmi_s3f* m, const int32_t* pool_off, int g0, int g1, std::vector<int32_t>& grp) {
     pgmi_s2f* rs = m->res;
-    hipStream_t st = rs->pm.stream;
-    const int a = pool_off[g0], n = pool_off[g1] - a, L = rs->L;
+    const int a = pool_off[g0], n = pool_off[g1] - a;
     grp.resize((size_t)n * 2);
     for (int g = g0; g < g1; ++g)
         for (int s = pool_off[g]; s < pool_off[g + 1]; ++s) { grp[(size_t)(s - a) * 2] = pool_off[g] - a; grp[(size_t)(s - a) * 2 + 1] = pool_off[g + 1] - a; }
-    PGMI_HIP(hipMemcpyAsync(m->grp, grp.data(), grp.size() * 4, hipMemcpyHostToDevice, st));
-    ProfScope p(&rs->pm, PGMI_K_HEAD, 2.0 * n * L * S2F_S * 20, 0);
-    launch_s3f_head(m->hold_pre.p, m->hold_sum.p, m->grp, m->Ns, rs->Wlin, rs->blin, m->hold_seq.p, rs->plddt.p, rs->cfg.plddt_threshold, L,
-                    (int64_t)n * L, m->hold_lp.p, st);
-    PGMI_HIP(hipGetLastError());
-    return PGMI_OK;
+    PGMI_HIP(hipMemcpyAsync(m->grp, grp.data(), grp.size() * 4, hipMemcpyHostToDevice, rs->pm.stream));
+    return s2f_head(rs, m->hold_pre.p, m->hold_seq.p, m->hold_sum.p, m->grp, m->Ns, (int64_t)n * rs->L, m->hold_lp.p);
 }
 
 // runs of whole pool groups, each within `hold` copies; fill(s0, bc) puts copies [s0, s0 + bc) into res->feat / res->seq, chunk(s0, bc)
@@ -340,15 +332,10 @@ int pgmi_s3f_gvp_forward(pgmi_s3f* m, const float* node_feat, const float* seq_l
     pgmi_s2f *rs = m->res, *sf = m->surf;
     PGMI_HIP(hipSetDevice(rs->pm.device));
     hipStream_t st = rs->pm.stream;
-    const int L = rs->L, D = m->D, Ns = m->Ns, per = s3f_per_chunk(m, B), hold = std::max(per, max_pool);
+    const int L = rs->L, Ns = m->Ns, per = s3f_per_chunk(m, B), hold = std::max(per, max_pool);
     rc = s3f_workspace(m, per, hold);
     if (rc) return rc;
-    auto fill = [&](int s0, int bc) {
-        const size_t R = (size_t)bc * L, r0 = (size_t)s0 * L;
-        PGMI_HIP(hipMemcpyAsync(rs->feat.p, node_feat + r0 * D, R * D * 4, hipMemcpyHostToDevice, st));
-        PGMI_HIP(hipMemcpyAsync(rs->seq.p, seq_logits + r0 * 20, R * 20 * 4, hipMemcpyHostToDevice, st));
-        return (int)PGMI_OK;
-    };
+    auto fill = [&](int s0, int bc) { return s2f_fill_rows(rs, node_feat, seq_logits, s0, bc); };
     auto chunk = [&](int s0, int bc) {
         const size_t RS = (size_t)bc * Ns, r0 = (size_t)s0 * Ns;
         if (surf_s) PGMI_HIP(hipMemcpyAsync(surf_s + r0 * S2F_S, sf->s.p, RS * S2F_S * 4, hipMemcpyDeviceToHost, st));
@@ -374,72 +361,29 @@ int pgmi_s3f_set_logprobs(pgmi_s3f* m, const int32_t* wt_tokens, int T, const in
     if (rc) return rc;
     pgmi_s2f* rs = m->res;
     pgmi_model* esm = rs->esm;
-    if (!esm) { set_error("S3F: this handle was created without an ESM2 model (pgmi_s3f_gvp_forward only)"); return PGMI_EINVAL; }
-    if (!wt_tokens || !aa_cols || !set_off || !set_pos || !out || n_sets <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
-    const int L = rs->L, D = m->D, V = esm->cfg.vocab;
-    if (T != L + 2) { set_error("S3F: T = %d tokens, the structure has %d residues (<cls> + residues + <eos>)", T, L); return PGMI_EINVAL; }
-    if (T + 31 > esm->max_rows) { set_error("T=%d exceeds the ESM2 model's workspace rows %d", T, esm->max_rows); return PGMI_EINVAL; }
-    rc = check_tokens(wt_tokens, 1, T, esm->n_token_ids);
+    rc = s2f_check_sets(rs, "S3F", wt_tokens, T, aa_cols, set_off, set_pos, n_sets, out);
     if (rc) return rc;
-    for (int c = 0; c < 20; ++c)
-        if (aa_cols[c] < 0 || aa_cols[c] >= V) { set_error("S3F: amino-acid column %d = %d outside the vocabulary (%d)", c, aa_cols[c], V); return PGMI_EINVAL; }
-    if (set_off[0] != 0) { set_error("set_off[0] must be 0"); return PGMI_EINVAL; }
-    for (int s = 0; s < n_sets; ++s) {
-        if (set_off[s + 1] <= set_off[s] || set_off[s + 1] - set_off[s] > L) { set_error("position set %d is empty or larger than L", s); return PGMI_EINVAL; }
-        for (int e = set_off[s]; e < set_off[s + 1]; ++e) {
-            const int p = set_pos[e];
-            if (p < 0 || p >= L || (e > set_off[s] && p <= set_pos[e - 1])) { set_error("position set %d: residue %d out of range or not ascending", s, p); return PGMI_EINVAL; }
-        }
-    }
     int max_pool = 0;
     rc = s3f_check_pools(pool_off, n_pools, n_sets, &max_pool);
     if (rc) return rc;
     PGMI_HIP(hipSetDevice(rs->pm.device));
     pgmi_model* pm = &rs->pm;
     hipStream_t st = pm->stream;
-    const int per = std::min(s3f_per_chunk(m, n_sets), rows_per_chunk(esm, T)), hold = std::max(per, max_pool);
+    const int L = rs->L, per = std::min(s3f_per_chunk(m, n_sets), rows_per_chunk(esm, T)), hold = std::max(per, max_pool);
+    S2fSetHost host;
     rc = s3f_workspace(m, per, hold);
-    if (!rc) rc = ensure_cap(pm, &rs->ridx, &rs->ridx_cap, (size_t)per * L);
-    if (!rc) rc = ensure_cap(pm, &rs->toks, &rs->toks_cap, (size_t)per * T);
-    if (!rc) rc = ensure_cap(pm, &rs->cols, &rs->cols_cap, (size_t)20);
+    if (!rc) rc = s2f_set_buffers(rs, per, T, aa_cols, &host);
     if (rc) return rc;
-    PGMI_HIP(hipMemcpyAsync(rs->cols, aa_cols, 20 * 4, hipMemcpyHostToDevice, st));
-    std::vector<int32_t> toks((size_t)per * T), ridx((size_t)per * L);
     std::vector<float> lp((size_t)hold * L * 20);
-    auto fill = [&](int s0, int bc) {
-        const int M = bc * T;
-        const int64_t R = (int64_t)bc * L;
-        for (int b = 0; b < bc; ++b) {
-            memcpy(&toks[(size_t)b * T], wt_tokens, (size_t)T * 4);
-            for (int e = set_off[s0 + b]; e < set_off[s0 + b + 1]; ++e) toks[(size_t)b * T + 1 + set_pos[e]] = esm->mask_id;
-            for (int i = 0; i < L; ++i) ridx[(size_t)b * L + i] = b * T + 1 + i;
-        }
-        PGMI_HIP(hipMemcpyAsync(esm->tokens, toks.data(), (size_t)M * 4, hipMemcpyHostToDevice, st));
-        PGMI_HIP(hipMemcpyAsync(rs->ridx, ridx.data(), (size_t)R * 4, hipMemcpyHostToDevice, st));
-        int rc2 = run_encoder(esm, bc, T);
-        if (rc2) return rc2;
-        {   // residue_feature: emb_layer_norm_after on the L residue rows, fp32
-            ProfScope p(esm, PGMI_K_LAYERNORM, 0, (double)R * D * 8);
-            launch_gather_rows(esm->x, rs->ridx, (int)R, D, rs->feat.p, st);
-            launch_layernorm(rs->feat.p, esm->lna_w, esm->lna_b, (int)R, D, 1e-5f, rs->feat.p, st);
-        }
-        rc2 = run_head(esm, M, nullptr);
-        if (rc2) return rc2;
-        launch_s2f_pick_logits(esm->lp, rs->cols, L, T, V, R, rs->seq.p, st);
-        return (int)PGMI_OK;
-    };
+    auto fill = [&](int s0, int bc) { return s2f_fill_esm(rs, wt_tokens, T, set_off, set_pos, s0, bc, &host); };
     auto chunk = [&](int, int) {
-        PGMI_HIP(hipStreamSynchronize(st));                    // toks and ridx are free for the next chunk
+        PGMI_HIP(hipStreamSynchronize(st));                    // the host scratch is free for the next chunk
         return s3f_drain(m);
     };
     auto done = [&](int a, int n) {
         PGMI_HIP(hipMemcpyAsync(lp.data(), m->hold_lp.p, (size_t)n * L * 20 * 4, hipMemcpyDeviceToHost, st));
         PGMI_HIP(hipStreamSynchronize(st));
-        for (int b = 0; b < n; ++b) {
-            if (full) memcpy(full + (size_t)(a + b) * L * 20, &lp[(size_t)b * L * 20], (size_t)L * 20 * 4);
-            for (int e = set_off[a + b]; e < set_off[a + b + 1]; ++e)
-                memcpy(out + (size_t)e * 20, &lp[((size_t)b * L + set_pos[e]) * 20], 20 * 4);
-        }
+        s2f_scatter(lp.data(), L, set_off, set_pos, a, n, out, full);
         return s3f_drain(m);
     };
     rc = s3f_run(m, pool_off, n_pools, per, hold, fill, chunk, done);

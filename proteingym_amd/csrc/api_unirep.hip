@@ -293,11 +293,7 @@ int pgmi_unirep_model_create(const pgmi_unirep_config* cfg, const float* w, int6
 
 void pgmi_unirep_destroy(pgmi_unirep* m) {
     if (!m) return;
-    hipSetDevice(m->pm.device);
-    if (m->pm.stream) hipStreamSynchronize(m->pm.stream);
-    for (ProfEvent& e : m->pm.events) { hipEventDestroy(e.start); hipEventDestroy(e.stop); }
-    for (void* p : m->pm.allocs) hipFree(p);
-    if (m->pm.stream) hipStreamDestroy(m->pm.stream);
+    side_release(&m->pm, true);
     delete m;
 }
 

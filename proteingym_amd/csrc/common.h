@@ -272,6 +272,7 @@ void launch_mpnn_score(const float* nll, const float* mask, int B, int L, double
 int mpnn_set_option(const char* name, long long value);   // api_mpnn.hip: "mpnn_max_rows"
 
 // S2F (s2f.hip; operands and shapes at the kernels)
+constexpr int S2F_S = 256, S2F_V = 16, S2F_H0 = 33;    // node scalar width, node vector channels, hidden vector channels of the first message GVP (2 * 16 + 1)
 struct S2fMsgWeights {    // device pointers of a layer's message GVPs: the first one's vector half, then the second and the third
     const float *wv0, *wsv0, *bsv0;
     const float *wh1, *ws1, *bs1, *wv1, *wsv1, *bsv1;
@@ -284,12 +285,13 @@ int launch_s2f_gvp_mid(const float* spre, const float* vh, const float* wv, cons
                        int vo, int h, int h2, int relu, int lda, int64_t rows, float* outA, float* outV, hipStream_t s);
 int launch_s2f_node_ln(const float* rs, const float* rv, const float* ds, const float* dv, const float* lnw, const float* lnb, const float* wh, int h, int vn, int lda, int64_t rows, float* os, float* ov,
                        float* outA, float* outV, hipStream_t s);
-void launch_s2f_head(const float* x, const float* W, const float* bias, const float* seq, const float* plddt, float thr, int L, int64_t rows,
-                     float* lp, hipStream_t s);
+void launch_s2f_head(const float* x, const float* sums, const int32_t* grp, int Ns, const float* W, const float* bias, const float* seq,
+                     const float* plddt, float thr, int L, int64_t rows, float* lp, hipStream_t s);
 void launch_s2f_pick_logits(const float* lp, const int32_t* cols, int L, int T, int V, int64_t rows, float* out, hipStream_t s);
 int s2f_set_option(const char* name, long long value);    // api_s2f.hip: "s2f_max_rows"
 
 // S3F (s3f.hip; operands and shapes at the kernels)
+constexpr int S3F_DEG = 16;                            // incoming edges of every surface point
 int launch_s3f_knn(const float* q, int nq, const float* c, int nc, int k, int32_t* idx, float* dist, hipStream_t s);
 void launch_s3f_edges(const float* pos, const int32_t* src, int Ns, const float* we, float* es, float* ev, hipStream_t s);
 int launch_s3f_rows(const float* Z, const float* T, const int32_t* res, const float* lnw, const float* lnb, int L, int Ns, int H, int64_t rows,
@@ -298,8 +300,6 @@ int launch_s3f_message(const float* P, const float* VT, const float* Es, const f
                        const S2fMsgWeights& w, const int32_t* src, int Ns, int64_t nodes, float* ds, float* dv, hipStream_t s);
 int s3f_colsum_blocks(int Ns);
 void launch_s3f_colsum(const float* x, int Ns, int copies, float* part, float* sums, hipStream_t s);
-void launch_s3f_head(const float* x, const float* sums, const int32_t* grp, int Ns, const float* W, const float* bias, const float* seq,
-                     const float* plddt, float thr, int L, int64_t rows, float* lp, hipStream_t s);
 
 // ProtSSN's EGNN (egnn.hip; operands and shapes at the kernels).  split: the operand is written as K-interleaved split planes, else fp32 rows
 void launch_egnn_edge_rows(const float* P, const float* S, const int32_t* centre, const int32_t* nb, int edges, int Hp, bool split, void* out,

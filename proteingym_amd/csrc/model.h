@@ -308,6 +308,7 @@ int ensure_cap(pgmi_model* m, T** p, size_t* cap, size_t need) {
 
 // ---- shared helpers (api_model.hip unless noted) ----
 int prof_drain(pgmi_model* m);
+void side_release(pgmi_model* pm, bool own_stream);   // teardown of a side handle's embedded model (pgmi_s2f, pgmi_carp, ...): device, sync, events, pool, stream
 int check_cfg(const pgmi_config* c);
 int check_tokens(const int32_t* tokens, int B, int T, int n_ids = PGMI_VOCAB);
 int check_vocab(const int32_t* tokens, int B, int T, int V);

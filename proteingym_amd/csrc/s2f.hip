@@ -14,7 +14,8 @@
 //                         GVP's GEMM operand row [s | |vh| | 0 pad].
 //   s2f_node_ln_kernel    (s, v) + dh -> tuple LayerNorm; dh is the mean message or the feed-forward output; then the next GVP's
 //                         wh v / norms as above.
-//   s2f_head_kernel       relu, Linear(256 -> 20), the ESM logits on low-pLDDT rows, log-softmax over 20.
+//   s2f_head_kernel       relu, S3F's pooled row when there is one, Linear(256 -> 20), the ESM logits on low-pLDDT rows, log-softmax
+//                         over 20.
 //   s2f_pick_logits_kernel  the 20 amino-acid columns of ESM2's log-probability rows of the L residues.
 #include <algorithm>
 
@@ -22,50 +23,7 @@
 
 namespace pgmi {
 
-// ---- fused message kernel (the tile's dimensions, fe_mid and fe_gemm: s2f_tile.h) ------------------------------------------------
-// tile rows -> As [FE_M][FE_LDA] = first message GVP's ws output: P_j + Es + P_i + Wn |vh|, and Vh [FE_M][FE_LDV] = its vh (33 channels).
-// Row `row` of the tile is edge min(c0 + row, e1 - 1): rows past the node's edges repeat the last one and are never summed.
-// The scalar part runs one column per thread over the tile's rows, the column of Wn in registers.
-__device__ __noinline__ void fe_gather(float* As, float* Vh, float* vn, int32_t* rowe, const float* __restrict__ P, const float* __restrict__ VT,
-                                          const float* __restrict__ Es, const float* __restrict__ ev, const float* __restrict__ whe,
-                                          const float* __restrict__ Wnt, const int32_t* __restrict__ src, int64_t nb, int i, int c0, int e1) {
-    const int tid = threadIdx.x;
-    const int64_t ni = nb + i;
-    if (tid < FE_M) {                                           // rowe[row] = the row's edge, rowe[FE_M + row] = its source node
-        const int e = min(c0 + tid, e1 - 1);
-        rowe[tid] = e;
-        rowe[FE_M + tid] = src[e];
-    }
-    __syncthreads();
-#pragma unroll 4
-    for (int idx = tid; idx < FE_M * SH0 * 3; idx += 256) {
-        const int row = idx / (SH0 * 3), t = idx - row * (SH0 * 3), h = t / 3, d = t - 3 * h;
-        const int e = rowe[row];
-        float x = whe[h] * ev[(size_t)e * 3 + d];
-        if (VT) x += VT[(nb + rowe[FE_M + row]) * (2 * SH0 * 3) + t] + VT[ni * (2 * SH0 * 3) + SH0 * 3 + t];
-        Vh[row * FE_LDV + t] = x;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < FE_M * SH0; idx += 256) {
-        const int row = idx / SH0, h = idx - row * SH0;
-        vn[row * FE_LDN + h] = s2f_vnorm(Vh + row * FE_LDV + h * 3);
-    }
-    __syncthreads();
-    float wn[SH0];
-#pragma unroll
-    for (int h = 0; h < SH0; ++h) wn[h] = Wnt[h * SS + tid];
-    const float pi = P[ni * 512 + SS + tid];
-#pragma unroll 4
-    for (int row = 0; row < FE_M; ++row) {
-        const float a = P[(nb + rowe[FE_M + row]) * 512 + tid] + Es[(size_t)rowe[row] * SS + tid] + pi;
-        float n = 0.0f;
-#pragma unroll
-        for (int h = 0; h < SH0; ++h) n = fmaf(wn[h], vn[row * FE_LDN + h], n);
-        As[row * FE_LDA + tid] = a + n;
-    }
-    __syncthreads();
-}
-
+// ---- fused message kernel (the tile, its LDS, the gather and the GVP stages: s2f_tile.h) ------------------------------------------
 // The three message GVPs of one layer and the mean at the centre, one block per (masked copy b, node i); grid = B L.  The node's
 // edges [off[i], off[i + 1]) go through in tiles of FE_M rows that live in LDS from the gather to the sum; the sum runs over the rows
 // in ascending edge order, one column per thread, so nothing of another node or copy enters a row's bits and no atomics are needed.
@@ -76,11 +34,6 @@ __global__ __launch_bounds__(256, 2) void s2f_message_kernel(const float* __rest
                                                           const float* __restrict__ whe, const float* __restrict__ Wnt, const S2fMsgWeights w,
                                                           const int32_t* __restrict__ src, const int32_t* __restrict__ off, int L,
                                                           float* __restrict__ ds, float* __restrict__ dv) {
-    __shared__ __attribute__((aligned(16))) float As[FE_M * FE_LDA];
-    __shared__ float Vh[FE_M * FE_LDV];
-    __shared__ float scr[FE_SCR];
-    __shared__ float wl[SV * SH0 + SV * SV + SV];
-    __shared__ int32_t rowe[2 * FE_M];
     const int tid = threadIdx.x;
     const int64_t node = blockIdx.x;
     const int i = (int)(node % L);
@@ -89,18 +42,13 @@ __global__ __launch_bounds__(256, 2) void s2f_message_kernel(const float* __rest
     float sum_s = 0.0f, sum_v = 0.0f;
 #pragma unroll 1
     for (int c0 = e0; c0 < e1; c0 += FE_M) {                    // block-uniform: every barrier below is reached by all threads
-        fe_gather(As, Vh, scr, rowe, P, VT, Es, ev, whe, Wnt, src, nb, i, c0, e1);
-        fe_mid(As, Vh, scr, wl, w.wv0, w.wsv0, w.bsv0, w.wh1, SH0, true);
-        fe_gemm(As, w.ws1, w.ldw, w.bs1);
-        fe_mid(As, Vh, scr, wl, w.wv1, w.wsv1, w.bsv1, w.wh2, SV, true);
-        fe_gemm(As, w.ws2, w.ldw, w.bs2);
-        fe_mid(As, Vh, scr, wl, w.wv2, w.wsv2, w.bsv2, nullptr, SV, false);
+        fe_tile<false>(P, VT, Es, ev, whe, Wnt, w, src, nb, c0, e1 - 1, i, i);
         const int n = min(FE_M, e1 - c0);
         for (int row = 0; row < n; ++row) {
-            sum_s += As[row * FE_LDA + tid];
-            if (tid < SV * 3) sum_v += Vh[row * FE_LDV + tid];
+            sum_s += fe_As[row * FE_LDA + tid];
+            if (tid < SV * 3) sum_v += fe_Vh[row * FE_LDV + tid];
         }
-        __syncthreads();                                        // the next tile overwrites As and Vh
+        __syncthreads();                                        // the next tile overwrites fe_As and fe_Vh
     }
     const float cnt = (float)max(e1 - e0, 1);
     ds[node * SS + tid] = sum_s / cnt;
@@ -227,8 +175,12 @@ __global__ __launch_bounds__(256) void s2f_node_ln_kernel(const float* __restric
     }
 }
 
-// rows = B * L: logits = W relu(x) + b over 20 letters; rows whose plddt[r % L] < thr read seq [rows][20] instead; log-softmax
-__global__ __launch_bounds__(256) void s2f_head_kernel(const float* __restrict__ x, const float* __restrict__ W, const float* __restrict__ bias,
+// rows = copies * L rows of x [.][256] (W_out before its ReLU): logits = W hx + b over 20 letters, hx = relu(x); rows whose
+// plddt[r % L] < thr read seq [rows][20] instead; log-softmax.  With sums [copies][256] and grp [copies][2] (S3F; both null otherwise),
+// grp = the first and one past the last copy of the row's pool group: hx = relu(x) + the pooled row, the sum of the group's copy sums
+// in ascending copy order over (copies * Ns).  One wave per row.
+__global__ __launch_bounds__(256) void s2f_head_kernel(const float* __restrict__ x, const float* __restrict__ sums, const int32_t* __restrict__ grp,
+                                                       int Ns, const float* __restrict__ W, const float* __restrict__ bias,
                                                        const float* __restrict__ seq, const float* __restrict__ plddt, float thr, int L,
                                                        int64_t rows, float* __restrict__ lp) {
     const int lane = threadIdx.x & 63;
@@ -237,6 +189,16 @@ __global__ __launch_bounds__(256) void s2f_head_kernel(const float* __restrict__
     float hx[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) hx[k] = fmaxf(x[r * SS + lane + 64 * k], 0.0f);
+    if (sums) {
+        const int s = (int)(r / L), g0 = grp[2 * s], g1 = grp[2 * s + 1];
+        const float cnt = (float)(g1 - g0) * (float)Ns;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float a = 0.0f;
+            for (int t = g0; t < g1; ++t) a += sums[(size_t)t * SS + lane + 64 * k];
+            hx[k] = hx[k] + a / cnt;
+        }
+    }
     float logit = -INFINITY;
     for (int c = 0; c < 20; ++c) {
         float p = 0.0f;
@@ -299,9 +261,9 @@ int launch_s2f_node_ln(const float* rs, const float* rv, const float* ds, const 
     return PGMI_OK;
 }
 
-void launch_s2f_head(const float* x, const float* W, const float* bias, const float* seq, const float* plddt, float thr, int L, int64_t rows,
-                     float* lp, hipStream_t s) {
-    hipLaunchKernelGGL(s2f_head_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, W, bias, seq, plddt, thr, L, rows, lp);
+void launch_s2f_head(const float* x, const float* sums, const int32_t* grp, int Ns, const float* W, const float* bias, const float* seq,
+                     const float* plddt, float thr, int L, int64_t rows, float* lp, hipStream_t s) {
+    hipLaunchKernelGGL(s2f_head_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, sums, grp, Ns, W, bias, seq, plddt, thr, L, rows, lp);
 }
 
 void launch_s2f_pick_logits(const float* lp, const int32_t* cols, int L, int T, int V, int64_t rows, float* out, hipStream_t s) {

@@ -7,7 +7,7 @@
 
 namespace pgmi {
 
-constexpr int S2F_S = 256, S2F_V = 16, S2F_ES = 64, S2F_RBF = 16, S2F_H0 = 33, S2F_MAX_L = 8192, S2F_MAX_LAYERS = 8;
+constexpr int S2F_ES = 64, S2F_RBF = 16, S2F_MAX_L = 8192, S2F_MAX_LAYERS = 8;   // S2F_S, S2F_V, S2F_H0 and S3F_DEG: common.h
 constexpr int S2F_KP = 288;                            // 256 + 16 (or 32) norm columns, rounded up to the GEMM's K tile
 constexpr int S2F_FS = 4 * S2F_S, S2F_FV = 2 * S2F_V;  // feed-forward hidden dims (1024, 32)
 constexpr int S2F_FK = S2F_FS + S2F_FV;                // 1056, a multiple of 32
@@ -28,6 +28,7 @@ struct S2fLayer {
     size_t Es_cap = 0;
 };
 struct S2fBuf { float* p = nullptr; size_t cap = 0; };
+struct S2fSetHost { std::vector<int32_t> toks, ridx; };   // host scratch of s2f_fill_esm: a chunk's tokens and residue row indices
 
 }  // namespace pgmi
 
@@ -66,12 +67,23 @@ int s2f_new(const pgmi_s2f_config* cfg, const float* w, int64_t n_weights, pgmi_
             pgmi_s2f** out);
 int s2f_buf(pgmi_s2f* m, S2fBuf* b, size_t n);
 int s2f_structure(pgmi_s2f* m, const float* pos, const float* plddt, int L);
+int s2f_edge_tables(pgmi_s2f* m, size_t E);                     // every layer's Es [E][256] from m->es; both structure passes end in it
 long long s2f_row_cap();                                        // pgmi_set_option("s2f_max_rows"), or the default
 int s2f_workspace(pgmi_s2f* m, int per);
 // bc masked copies, in three steps: m->feat [bc L][D] -> m->s (s2f_embed); the layers and W_out, m->s / m->v -> m->pre [bc L][256], the
-// node state after the last layer left in m->s / m->v (s2f_layers); m->pre and m->seq -> m->lp (s2f_head)
+// node state after the last layer left in m->s / m->v (s2f_layers); m->pre and m->seq -> m->lp (s2f_head; sums, grp, Ns: S3F's pooled
+// row, else null, null, 0)
 int s2f_embed(pgmi_s2f* m, int bc);
 int s2f_layers(pgmi_s2f* m, int bc);
-int s2f_head(pgmi_s2f* m, const float* pre, const float* seq, int64_t rows, float* lp);
+int s2f_head(pgmi_s2f* m, const float* pre, const float* seq, const float* sums, const int32_t* grp, int Ns, int64_t rows, float* lp);
+// What S2F's and S3F's entries share around the GNN (api_s2f.hip, at the definitions): the fill of a gvp_forward chunk; the checks of
+// set_logprobs' arguments, with the model's name in the messages; its buffers; the ESM2 fill of a chunk of masked copies; the scatter
+// of a chunk's tables into `out` and `full`.
+int s2f_fill_rows(pgmi_s2f* m, const float* node_feat, const float* seq_logits, int s0, int bc);
+int s2f_check_sets(const pgmi_s2f* m, const char* name, const int32_t* wt_tokens, int T, const int32_t* aa_cols, const int32_t* set_off,
+                   const int32_t* set_pos, int n_sets, const float* out);
+int s2f_set_buffers(pgmi_s2f* m, int per, int T, const int32_t* aa_cols, S2fSetHost* h);
+int s2f_fill_esm(pgmi_s2f* m, const int32_t* wt_tokens, int T, const int32_t* set_off, const int32_t* set_pos, int s0, int bc, S2fSetHost* h);
+void s2f_scatter(const float* lp, int L, const int32_t* set_off, const int32_t* set_pos, int s0, int bc, float* out, float* full);
 
 }  // namespace pgmi

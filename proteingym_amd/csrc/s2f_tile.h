@@ -1,15 +1,14 @@
 // The 32-row edge tile of the GVP message kernels (s2f.hip: one node's edges per tile; s3f.hip: two surface points of 16 edges each):
-// the dimensions, the vector half of a GVP on the tile and the 272 -> 256 ws product on the fp32 MFMA.  Both kernels gather their
-// rows themselves and sum them themselves; what is here sees rows only, so a row's bits are the same in either kernel.
+// the dimensions and the LDS of a block, the gather of the rows, the vector half of a GVP on the tile, the 272 -> 256 ws product on the
+// fp32 MFMA, and fe_tile, which runs them in order.  A kernel says which edges and which centres its tile holds and sums the rows itself;
+// what is here sees rows only, so a row's bits are the same in either kernel.
 #pragma once
 
 #include "common.h"
 
 namespace pgmi {
 
-constexpr int SS = 256;            // node scalar width
-constexpr int SV = 16;             // node vector channels
-constexpr int SH0 = 33;            // hidden vector channels of the first message GVP (2 * 16 + 1)
+constexpr int SS = S2F_S, SV = S2F_V, SH0 = S2F_H0;   // common.h's dimensions under the names the kernels use
 
 __device__ __forceinline__ float s2f_wave_sum(float x) {
     for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
@@ -26,6 +25,62 @@ constexpr int FE_LDV = SH0 * 3 + 1;  // LDS row stride of the vector tile
 
 constexpr int FE_LDN = SH0 + 3;      // LDS row stride of the first GVP's channel norms
 constexpr int FE_SCR = 4 * FE_M * SV; // scratch floats: the norms [FE_M][FE_LDN] of the gather, the gate partials [4][FE_M][16] after it
+
+// The LDS of a message kernel's block, in each file that has one: the operand tile, the vector tile, the scratch, fe_mid's small
+// weights, and fe_rowe[row] = the row's edge, fe_rowe[FE_M + row] = its source node.  Five arrays and not one struct: the compiler then
+// knows that they do not overlap.  A kernel that does not call fe_tile gets none of them.
+static __shared__ __attribute__((aligned(16))) float fe_As[FE_M * FE_LDA];
+static __shared__ float fe_Vh[FE_M * FE_LDV];
+static __shared__ float fe_scr[FE_SCR];
+static __shared__ float fe_wl[SV * SH0 + SV * SV + SV];
+static __shared__ int32_t fe_rowe[2 * FE_M];
+
+// tile rows -> As [FE_M][FE_LDA] = first message GVP's ws output: P_j + Es + P_i + Wn |vh|, and Vh [FE_M][FE_LDV] = its vh (33 channels).
+// Row `row` of the tile is edge min(first_edge + row, last_edge): rows past last_edge repeat it and are never summed.  Its centre is node
+// centre_lo for rows 0 .. 15 and centre_hi for rows 16 .. 31; TWO = false: every row's centre is centre_lo, which then stays in a register.
+// nb = the first node of the masked copy.  The scalar part runs one column per thread over the tile's rows, the column of Wn in registers.
+template <bool TWO>
+static __device__ __noinline__ void fe_gather(float* As, float* Vh, float* vn, int32_t* rowe, const float* __restrict__ P, const float* __restrict__ VT,
+                                              const float* __restrict__ Es, const float* __restrict__ ev, const float* __restrict__ whe,
+                                              const float* __restrict__ Wnt, const int32_t* __restrict__ src, int64_t nb, int first_edge,
+                                              int last_edge, int centre_lo, int centre_hi) {
+    const int tid = threadIdx.x;
+    const int64_t nlo = nb + centre_lo, nhi = nb + (TWO ? centre_hi : centre_lo);
+    if (tid < FE_M) {
+        const int e = min(first_edge + tid, last_edge);
+        rowe[tid] = e;
+        rowe[FE_M + tid] = src[e];
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int idx = tid; idx < FE_M * SH0 * 3; idx += 256) {
+        const int row = idx / (SH0 * 3), t = idx - row * (SH0 * 3), h = t / 3, d = t - 3 * h;
+        const int e = rowe[row];
+        const int64_t ni = TWO && row >= FE_M / 2 ? nhi : nlo;
+        float x = whe[h] * ev[(size_t)e * 3 + d];
+        if (VT) x += VT[(nb + rowe[FE_M + row]) * (2 * SH0 * 3) + t] + VT[ni * (2 * SH0 * 3) + SH0 * 3 + t];
+        Vh[row * FE_LDV + t] = x;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < FE_M * SH0; idx += 256) {
+        const int row = idx / SH0, h = idx - row * SH0;
+        vn[row * FE_LDN + h] = s2f_vnorm(Vh + row * FE_LDV + h * 3);
+    }
+    __syncthreads();
+    float wn[SH0];
+#pragma unroll
+    for (int h = 0; h < SH0; ++h) wn[h] = Wnt[h * SS + tid];
+    const float pi0 = P[nlo * 512 + SS + tid], pi1 = TWO ? P[nhi * 512 + SS + tid] : pi0;
+#pragma unroll 4
+    for (int row = 0; row < FE_M; ++row) {
+        const float a = P[(nb + rowe[FE_M + row]) * 512 + tid] + Es[(size_t)rowe[row] * SS + tid] + (row < FE_M / 2 ? pi0 : pi1);
+        float n = 0.0f;
+#pragma unroll
+        for (int h = 0; h < SH0; ++h) n = fmaf(wn[h], vn[row * FE_LDN + h], n);
+        As[row * FE_LDA + tid] = a + n;
+    }
+    __syncthreads();
+}
 
 // The vector half of one GVP on the tile.  In: As[row][0 .. 256) = ws [s | |vh|] + b, Vh[row] = vh [h][3].
 // gate = sigmoid(wsv s + bsv) on s before the activation; v = wv vh * gate; s = relu(s) or s, in place.  With nwh [16][16], the next
@@ -148,6 +203,21 @@ static __device__ __noinline__ void fe_gemm(float* As, const float* __restrict__
             for (int v = 0; v < 4; ++v) As[(rt * 16 + 4 * g + v) * FE_LDA + col] = acc[rt][ct][v] + bc;
     }
     __syncthreads();
+}
+
+// One tile through the three message GVPs of a layer: on return fe_As [FE_M][0 .. 256) and fe_Vh [FE_M][16][3] hold the rows' messages.
+// The tile's rows and the gather's operands are fe_gather's; block-uniform, every thread of the block calls it.
+template <bool TWO>
+__device__ __forceinline__ void fe_tile(const float* __restrict__ P, const float* __restrict__ VT, const float* __restrict__ Es,
+                                        const float* __restrict__ ev, const float* __restrict__ whe, const float* __restrict__ Wnt,
+                                        const S2fMsgWeights& w, const int32_t* __restrict__ src, int64_t nb, int first_edge, int last_edge,
+                                        int centre_lo, int centre_hi) {
+    fe_gather<TWO>(fe_As, fe_Vh, fe_scr, fe_rowe, P, VT, Es, ev, whe, Wnt, src, nb, first_edge, last_edge, centre_lo, centre_hi);
+    fe_mid(fe_As, fe_Vh, fe_scr, fe_wl, w.wv0, w.wsv0, w.bsv0, w.wh1, SH0, true);
+    fe_gemm(fe_As, w.ws1, w.ldw, w.bs1);
+    fe_mid(fe_As, fe_Vh, fe_scr, fe_wl, w.wv1, w.wsv1, w.bsv1, w.wh2, SV, true);
+    fe_gemm(fe_As, w.ws2, w.ldw, w.bs2);
+    fe_mid(fe_As, fe_Vh, fe_scr, fe_wl, w.wv2, w.wsv2, w.bsv2, nullptr, SV, false);
 }
 
 }  // namespace pgmi

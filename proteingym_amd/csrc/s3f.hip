@@ -18,8 +18,7 @@
 //                         upper half repeats the last edge and is not summed.
 //   s3f_colsum_*          the column sum of surf_W_out's rows (after its ReLU) of one copy in a fixed order: 64-row partial sums, then
 //                         the partials in ascending order.  Neither depends on what else is in the launch.
-//   s3f_head_kernel       s2f_head_kernel on relu(W_out's row) + the pooled row of the row's pool group: the sum of the group's copy
-//                         sums in ascending copy order over (copies * Ns).
+//                         s2f_head_kernel (s2f.hip) adds the pooled row of a row's pool group from these sums.
 #include <algorithm>
 
 #include "s2f_tile.h"
@@ -88,7 +87,6 @@ __global__ __launch_bounds__(256) void s3f_knn_kernel(const float* __restrict__ 
 }
 
 // ---- surf_W_e ------------------------------------------------------------------------------------------------------------------
-constexpr int S3F_DEG = 16;
 constexpr int S3F_WE = 32 + 1 + 64 * 17 + 64 + 1 + 64 + 1;      // surf_W_e's tensors in blob order: LayerNorm, wh, ws + b, wv, wsv + b
 
 // edge e = (src[e] -> e / 16); es [E][64], ev [E][3]
@@ -174,47 +172,8 @@ __global__ __launch_bounds__(256) void s3f_row_kernel(const float* __restrict__ 
     for (int c = tid; c < H; c += 256) out[r * H + c] = fmaxf((xrow[c] - mean) * rstd * lnw[c] + lnb[c], 0.0f);
 }
 
-// ---- fused message kernel of the fixed-degree graph ------------------------------------------------------------------------------
-// fe_gather (s2f.hip) for a tile of two points: row `row` is edge min(16 p0 + row, 16 Ns - 1), its centre that edge / 16.
-__device__ __noinline__ void fs_gather(float* As, float* Vh, float* vn, int32_t* rowe, const float* __restrict__ P, const float* __restrict__ VT,
-                                       const float* __restrict__ Es, const float* __restrict__ ev, const float* __restrict__ whe,
-                                       const float* __restrict__ Wnt, const int32_t* __restrict__ src, int64_t nb, int p0, int Ns) {
-    const int tid = threadIdx.x;
-    if (tid < FE_M) {                                           // rowe[row] = the row's edge, rowe[FE_M + row] = its source node
-        const int e = min(p0 * S3F_DEG + tid, Ns * S3F_DEG - 1);
-        rowe[tid] = e;
-        rowe[FE_M + tid] = src[e];
-    }
-    __syncthreads();
-#pragma unroll 4
-    for (int idx = tid; idx < FE_M * SH0 * 3; idx += 256) {
-        const int row = idx / (SH0 * 3), t = idx - row * (SH0 * 3), h = t / 3, d = t - 3 * h;
-        const int e = rowe[row];
-        float x = whe[h] * ev[(size_t)e * 3 + d];
-        if (VT) x += VT[(nb + rowe[FE_M + row]) * (2 * SH0 * 3) + t] + VT[(nb + e / S3F_DEG) * (2 * SH0 * 3) + SH0 * 3 + t];
-        Vh[row * FE_LDV + t] = x;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < FE_M * SH0; idx += 256) {
-        const int row = idx / SH0, h = idx - row * SH0;
-        vn[row * FE_LDN + h] = s2f_vnorm(Vh + row * FE_LDV + h * 3);
-    }
-    __syncthreads();
-    float wn[SH0];
-#pragma unroll
-    for (int h = 0; h < SH0; ++h) wn[h] = Wnt[h * SS + tid];
-    const float pi0 = P[(nb + p0) * 512 + SS + tid], pi1 = P[(nb + min(p0 + 1, Ns - 1)) * 512 + SS + tid];
-#pragma unroll 4
-    for (int row = 0; row < FE_M; ++row) {
-        const float a = P[(nb + rowe[FE_M + row]) * 512 + tid] + Es[(size_t)rowe[row] * SS + tid] + (row < S3F_DEG ? pi0 : pi1);
-        float n = 0.0f;
-#pragma unroll
-        for (int h = 0; h < SH0; ++h) n = fmaf(wn[h], vn[row * FE_LDN + h], n);
-        As[row * FE_LDA + tid] = a + n;
-    }
-    __syncthreads();
-}
-
+// ---- fused message kernel of the fixed-degree graph (the tile, its LDS, the gather and the GVP stages: s2f_tile.h) ------------------
+static_assert(FE_M == 2 * S3F_DEG, "a tile holds the edges of two points");
 // grid = B tiles, tiles = ceil(Ns / 2).  Operands as s2f_message_kernel's, with src [Ns][16] (the sources of a centre in ascending
 // index) in place of the CSR.  ds [B Ns][256], dv [B Ns][16][3] = the mean message.
 __global__ __launch_bounds__(256, 2) void s3f_message_kernel(const float* __restrict__ P, const float* __restrict__ VT,
@@ -222,27 +181,17 @@ __global__ __launch_bounds__(256, 2) void s3f_message_kernel(const float* __rest
                                                              const float* __restrict__ whe, const float* __restrict__ Wnt, const S2fMsgWeights w,
                                                              const int32_t* __restrict__ src, int Ns, int tiles, float* __restrict__ ds,
                                                              float* __restrict__ dv) {
-    __shared__ __attribute__((aligned(16))) float As[FE_M * FE_LDA];
-    __shared__ float Vh[FE_M * FE_LDV];
-    __shared__ float scr[FE_SCR];
-    __shared__ float wl[SV * SH0 + SV * SV + SV];
-    __shared__ int32_t rowe[2 * FE_M];
     const int tid = threadIdx.x;
     const int64_t b = blockIdx.x / tiles;
     const int p0 = 2 * (int)(blockIdx.x - b * tiles);
     const int64_t nb = b * Ns;
-    fs_gather(As, Vh, scr, rowe, P, VT, Es, ev, whe, Wnt, src, nb, p0, Ns);
-    fe_mid(As, Vh, scr, wl, w.wv0, w.wsv0, w.bsv0, w.wh1, SH0, true);
-    fe_gemm(As, w.ws1, w.ldw, w.bs1);
-    fe_mid(As, Vh, scr, wl, w.wv1, w.wsv1, w.bsv1, w.wh2, SV, true);
-    fe_gemm(As, w.ws2, w.ldw, w.bs2);
-    fe_mid(As, Vh, scr, wl, w.wv2, w.wsv2, w.bsv2, nullptr, SV, false);
+    fe_tile<true>(P, VT, Es, ev, whe, Wnt, w, src, nb, p0 * S3F_DEG, Ns * S3F_DEG - 1, p0, min(p0 + 1, Ns - 1));
     const int np = min(2, Ns - p0);
     for (int q = 0; q < np; ++q) {
         float sum_s = 0.0f, sum_v = 0.0f;
         for (int row = q * S3F_DEG; row < (q + 1) * S3F_DEG; ++row) {
-            sum_s += As[row * FE_LDA + tid];
-            if (tid < SV * 3) sum_v += Vh[row * FE_LDV + tid];
+            sum_s += fe_As[row * FE_LDA + tid];
+            if (tid < SV * 3) sum_v += fe_Vh[row * FE_LDV + tid];
         }
         const int64_t node = nb + p0 + q;
         ds[node * SS + tid] = sum_s / (float)S3F_DEG;
@@ -266,39 +215,6 @@ __global__ __launch_bounds__(256) void s3f_colsum_final_kernel(const float* __re
     float a = 0.0f;
     for (int k = 0; k < nblk; ++k) a += part[(b * nblk + k) * SS + threadIdx.x];
     sums[b * SS + threadIdx.x] = a;
-}
-// rows = copies * L rows of x [.][256] (W_out before its ReLU); grp [copies][2] = the first and one past the last copy of the row's pool
-// group; sums [copies][256].  logits = W (relu(x) + pooled) + b over 20 letters; rows whose plddt[r % L] < thr read seq [rows][20]
-// instead; log-softmax.  One wave per row, as s2f_head_kernel.
-__global__ __launch_bounds__(256) void s3f_head_kernel(const float* __restrict__ x, const float* __restrict__ sums, const int32_t* __restrict__ grp,
-                                                       int Ns, const float* __restrict__ W, const float* __restrict__ bias,
-                                                       const float* __restrict__ seq, const float* __restrict__ plddt, float thr, int L,
-                                                       int64_t rows, float* __restrict__ lp) {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= rows) return;
-    const int s = (int)(r / L), g0 = grp[2 * s], g1 = grp[2 * s + 1];
-    const float cnt = (float)(g1 - g0) * (float)Ns;
-    float hx[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        float a = 0.0f;
-        for (int t = g0; t < g1; ++t) a += sums[(size_t)t * SS + lane + 64 * k];
-        hx[k] = fmaxf(x[r * SS + lane + 64 * k], 0.0f) + a / cnt;
-    }
-    float logit = -INFINITY;
-    for (int c = 0; c < 20; ++c) {
-        float p = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) p = fmaf(hx[k], W[c * SS + lane + 64 * k], p);
-        p = s2f_wave_sum(p);
-        if (lane == c) logit = p + bias[c];
-    }
-    if (plddt[r % L] < thr && lane < 20) logit = seq[r * 20 + lane];
-    float mx = logit;
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-    const float ex = s2f_wave_sum(lane < 20 ? expf(logit - mx) : 0.0f);
-    if (lane < 20) lp[r * 20 + lane] = logit - mx - logf(ex);
 }
 
 // ---- launchers -----------------------------------------------------------------------------------------------------------------
@@ -346,11 +262,6 @@ void launch_s3f_colsum(const float* x, int Ns, int copies, float* part, float* s
     const int nblk = s3f_colsum_blocks(Ns);
     hipLaunchKernelGGL(s3f_colsum_part_kernel, dim3((unsigned)nblk, (unsigned)copies), dim3(256), 0, s, x, Ns, nblk, part);
     hipLaunchKernelGGL(s3f_colsum_final_kernel, dim3((unsigned)copies), dim3(256), 0, s, part, nblk, sums);
-}
-
-void launch_s3f_head(const float* x, const float* sums, const int32_t* grp, int Ns, const float* W, const float* bias, const float* seq,
-                     const float* plddt, float thr, int L, int64_t rows, float* lp, hipStream_t s) {
-    hipLaunchKernelGGL(s3f_head_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, sums, grp, Ns, W, bias, seq, plddt, thr, L, rows, lp);
 }
 
 }  // namespace pgmi
