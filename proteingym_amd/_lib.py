@@ -293,3 +293,67 @@ class ModelHandle:
             self.close()
         except Exception:
             pass
+
+
+class _ProfileView:
+    """A pgmi_model handle (_h) with the profile methods of every model class."""
+
+    def __init__(self, h=None):
+        self._h = h
+
+    def profile_enable(self, on=True):
+        check(load().pgmi_profile_enable(self._h, int(on)))
+
+    def profile_reset(self):
+        check(load().pgmi_profile_reset(self._h))
+
+    def profile(self) -> dict:
+        lib = load()
+        out = {}
+        for k, name in enumerate(K_NAMES):
+            ms, n, fl, by = C.c_double(), C.c_int64(), C.c_double(), C.c_double()
+            check(lib.pgmi_profile_get(self._h, k, C.byref(ms), C.byref(n), C.byref(fl), C.byref(by)))
+            out[name] = dict(ms=ms.value, launches=n.value, flops=fl.value, bytes=by.value)
+        return out
+
+
+class SideHandle:
+    """A model with a handle of its own (EVE, ProteinMPNN, UniRep, S2F, S3F, CARP, ProtSSN) behind the entries
+    pgmi_<PREFIX>_weight_count / _create / _destroy / _profile_model.  _create checks the blob size against the library's count and
+    creates the handle; `before_device` are the arguments the create entry takes between the blob and the device (S2F / S3F: the ESM2
+    handle).  NAME starts the blob size message."""
+    PREFIX = ""
+    CREATE = None           # the create entry, where it is not pgmi_<PREFIX>_create
+    NAME = ""
+
+    def _create(self, config, blob, device, *before_device):
+        lib = load()
+        w = as_f32(blob)
+        n = getattr(lib, f"pgmi_{self.PREFIX}_weight_count")(C.byref(config))
+        if n < 0:
+            check(EINVAL)
+        if w.size != n:
+            raise PgmiError(f"{self.NAME}weight blob has {w.size} elements, config needs {n}")
+        h = C.c_void_p()
+        create = getattr(lib, self.CREATE or f"pgmi_{self.PREFIX}_create")
+        check(create(C.byref(config), ptr(w, _f32p), w.size, *before_device, device, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(load(), f"pgmi_{self.PREFIX}_destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def profile_handle(self, *part):
+        """The pgmi_model that carries the handle's profile (S3F: of half `part`)."""
+        return C.c_void_p(getattr(load(), f"pgmi_{self.PREFIX}_profile_model")(self._h, *part))
+
+    def profile_view(self, *part):
+        """profile_handle as an object with EsmModel's profile methods."""
+        return _ProfileView(self.profile_handle(*part))

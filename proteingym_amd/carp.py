@@ -273,41 +273,20 @@ def _pack(token_rows):
     return tok, lens
 
 
-class CarpModel:
+class CarpModel(_lib.SideHandle):
     """A device-resident CARP."""
 
+    PREFIX = "carp"
+
     def __init__(self, ck: dict, device: int = 0, precision: str = "f16x3", max_rows: int = 0):
-        lib = _lib.load()
         if precision not in _lib.PRECISIONS:
             raise _lib.PgmiError(f"unknown precision {precision!r}")
         self.spec = check_checkpoint(ck)
         s = self.spec
         c = CarpConfig(abi_version=_lib.ABI_VERSION, d_model=s.d_model, d_hidden=s.d_hidden, n_layers=s.n_layers, kernel_size=s.kernel_size,
                        r=s.r, vocab=s.vocab, mask_id=MASK_ID, precision=_lib.PRECISIONS[precision], max_rows=max_rows, ln_eps=LN_EPS)
-        n = lib.pgmi_carp_weight_count(C.byref(c))
-        if n < 0:
-            raise _lib.PgmiError(f"libpgmi refuses the configuration: {lib.pgmi_last_error().decode(errors='replace')}", code=_lib.EINVAL)
-        w = _lib.as_f32(blob_from_state(ck["model_state_dict"], s))
-        if w.size != n:
-            raise _lib.PgmiError(f"weight blob has {w.size} elements, config needs {n}")
-        h = C.c_void_p()
-        _lib.check(lib.pgmi_carp_create(C.byref(c), _lib.ptr(w, _lib._f32p), w.size, device, C.byref(h)))
-        self._h = h
+        self._create(c, blob_from_state(ck["model_state_dict"], s), device)
         self.V = s.vocab
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.load().pgmi_carp_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def profile_handle(self):
-        return C.c_void_p(_lib.load().pgmi_carp_profile_model(self._h))
 
     def token_logprobs(self, token_rows) -> List[np.ndarray]:
         """One [L_i, V] array of log-probabilities per sequence, from one unmasked forward each."""

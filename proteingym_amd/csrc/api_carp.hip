@@ -27,12 +27,11 @@ struct pgmi_carp {
     std::vector<CarpBlock> blocks;
     // workspace of a chunk of R rows: residual stream x [R][D]; t [R][dh] (PFF1's and the convolution's output); the operand of the
     // next product hs (split rows, or fp32 rows: 4 bytes per element either way) [R][max(D, dh)]; col: the fp32 convolution's im2col
-    int32_t *tokens = nullptr, *seg_off = nullptr, *row_idx = nullptr, *nonfinite = nullptr;
-    float *x = nullptr, *t = nullptr, *g = nullptr, *col = nullptr, *lp = nullptr, *terms = nullptr;
-    uint32_t* hs = nullptr;
-    double* sums = nullptr;
-    size_t tokens_cap = 0, seg_cap = 0, idx_cap = 0, x_cap = 0, t_cap = 0, g_cap = 0, col_cap = 0, lp_cap = 0, terms_cap = 0, hs_cap = 0,
-           sums_cap = 0;
+    int32_t* nonfinite = nullptr;
+    DevBuf<int32_t> tokens, seg_off, row_idx;
+    DevBuf<float> x, t, g, col, lp, terms;
+    DevBuf<uint32_t> hs;
+    DevBuf<double> sums;
 };
 
 namespace pgmi {
@@ -92,17 +91,9 @@ static int carp_rows_cap(const pgmi_carp* m) {
 static int carp_workspace(pgmi_carp* m, size_t R, size_t n_seq) {
     pgmi_model* pm = &m->pm;
     const size_t D = m->D, H = m->dh, W = std::max(D, H);
-    int rc = ensure_cap(pm, &m->tokens, &m->tokens_cap, R);
-    if (!rc) rc = ensure_cap(pm, &m->seg_off, &m->seg_cap, n_seq + 1);
-    if (!rc) rc = ensure_cap(pm, &m->row_idx, &m->idx_cap, n_seq);
-    if (!rc) rc = ensure_cap(pm, &m->x, &m->x_cap, R * D);
-    if (!rc) rc = ensure_cap(pm, &m->t, &m->t_cap, R * H);
-    if (!rc) rc = ensure_cap(pm, &m->g, &m->g_cap, R * D);
-    if (!rc) rc = ensure_cap(pm, &m->hs, &m->hs_cap, R * W);
-    if (!rc) rc = ensure_cap(pm, &m->lp, &m->lp_cap, R * (size_t)m->V);
-    if (!rc) rc = ensure_cap(pm, &m->terms, &m->terms_cap, R);
-    if (!rc) rc = ensure_cap(pm, &m->sums, &m->sums_cap, n_seq);
-    if (!rc && m->cfg.precision == PGMI_PREC_FP32) rc = ensure_cap(pm, &m->col, &m->col_cap, R * H * (size_t)m->taps);
+    int rc = reserve_all(pm, m->tokens, R, m->seg_off, n_seq + 1, m->row_idx, n_seq, m->x, R * D, m->t, R * H, m->g, R * D, m->hs, R * W,
+                         m->lp, R * (size_t)m->V, m->terms, R, m->sums, n_seq);
+    if (!rc && m->cfg.precision == PGMI_PREC_FP32) rc = m->col.reserve(pm, R * H * (size_t)m->taps);
     return rc;
 }
 
@@ -113,19 +104,15 @@ static int carp_forward(pgmi_carp* m, int R, int n_seq) {
     const int D = m->D, H = m->dh, k = m->taps;
     const float eps = m->cfg.ln_eps;
     const bool f32 = m->cfg.precision == PGMI_PREC_FP32;
-    unsigned short* h16 = reinterpret_cast<unsigned short*>(m->hs);
-    float* h32 = reinterpret_cast<float*>(m->hs);
+    unsigned short* h16 = reinterpret_cast<unsigned short*>(m->hs.p);
+    float* h32 = reinterpret_cast<float*>(m->hs.p);
     auto ln_gelu = [&](const float* src, const float* w, const float* b, int width) {
         ProfScope p(pm, PGMI_K_LAYERNORM, 0, (double)R * width * 8);
         return f32 ? launch_ln_gelu32(src, w, b, R, width, eps, h32, st) : launch_ln_gelu16(src, w, b, R, width, eps, h16, st);
     };
     auto gemm = [&](int cls, const float* w32, const W16& w16, const float* bias, const float* residual, float* out, int N, int K) {
         ProfScope p(pm, cls, 2.0 * R * (double)N * K, 0);
-        if (f32) return launch_gemm_f32(h32, w32, bias, residual, out, R, N, K, EPI_NONE, st);
-        GemmLaunch g;
-        g.A = h16; g.W = w16.p; g.out_scale = w16.out_scale; g.bias = bias; g.residual = residual;
-        g.out32 = out; g.M = R; g.N = N; g.K = K; g.stream = st;
-        return launch_gemm16(g);
+        return linear(pm, h32, h16, w32, w16, bias, residual, out, nullptr, R, N, K, EPI_NONE);
     };
     {
         ProfScope p(pm, PGMI_K_EMBED, 0, (double)R * D * 8);
@@ -167,17 +154,11 @@ static int carp_head(pgmi_carp* m, const int32_t* row_idx, int n) {
 // after the chunk's copies are queued: waits for the stream; PGMI_EOVERFLOW when the head saw a non-finite value
 static int carp_finish(pgmi_carp* m) {
     int32_t flag = 0;
-    PGMI_HIP(hipGetLastError());
     PGMI_HIP(hipMemcpyAsync(&flag, m->nonfinite, 4, hipMemcpyDeviceToHost, m->pm.stream));
-    const hipError_t e = hipStreamSynchronize(m->pm.stream);
-    if (e != hipSuccess) { set_error("CARP forward failed: %s", hipGetErrorString(e)); return PGMI_EHIP; }
-    if (flag) {
-        PGMI_HIP(hipMemsetAsync(m->nonfinite, 0, 4, m->pm.stream));
-        set_error("non-finite log-probabilities%s", m->cfg.precision == PGMI_PREC_F16X3
-                  ? ": an activation left the fp16 range in precision f16x3; re-run with precision fp32" : "");
-        return PGMI_EOVERFLOW;
-    }
-    return PGMI_OK;
+    const int rc = side_sync(&m->pm, PGMI_OK, "CARP forward");
+    if (rc || !flag) return rc;
+    PGMI_HIP(hipMemsetAsync(m->nonfinite, 0, 4, m->pm.stream));
+    return overflow_error(m->cfg.precision);
 }
 
 static int carp_check_batch(const pgmi_carp* m, const int32_t* tokens, const int32_t* lens, int B, int64_t* total) {
@@ -242,23 +223,11 @@ int pgmi_carp_create(const pgmi_carp_config* cfg, const float* w, int64_t n_weig
     *out = nullptr;
     int rc = carp_check(cfg);
     if (rc) return rc;
-    if (!w || n_weights != carp_count(cfg)) {
-        set_error("CARP weight blob has %lld elements, config needs %lld", (long long)n_weights, (long long)carp_count(cfg));
-        return PGMI_EINVAL;
-    }
-    for (int64_t i = 0; i < n_weights; ++i)
-        if (!std::isfinite(w[i])) { set_error("CARP: weight blob element %lld is not finite", (long long)i); return PGMI_EINVAL; }
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) { set_error("no HIP device (libpgmi has no CPU fallback)"); return PGMI_ENODEV; }
-    if (device < 0 || device >= n_dev) { set_error("device %d out of range (%d visible)", device, n_dev); return PGMI_EINVAL; }
-    PGMI_HIP(hipSetDevice(device));
-    gemm_options_from_env();
     pgmi_carp* m = new pgmi_carp();
+    rc = side_open(&m->pm, "CARP", w, n_weights, carp_count(cfg), true, device, cfg->precision, nullptr);
+    if (rc) { delete m; return rc; }
     m->cfg = *cfg;
     m->D = cfg->d_model; m->dh = cfg->d_hidden; m->V = cfg->vocab; m->taps = cfg->kernel_size;
-    m->pm.device = device;
-    m->pm.cfg.precision = cfg->precision;                 // what the blob walker reads
-    if (hipStreamCreate(&m->pm.stream) != hipSuccess) { delete m; set_error("hipStreamCreate failed"); return PGMI_EHIP; }
     rc = carp_build(m, w, n_weights);
     if (rc) { pgmi_carp_destroy(m); return rc; }
     *out = m;

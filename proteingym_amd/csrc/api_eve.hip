@@ -16,8 +16,6 @@ int eve_set_option(const char* name, long long value) {
     return PGMI_EINVAL;
 }
 
-static inline int pad32(int n) { return (n + 31) / 32 * 32; }
-
 struct EveLinear {           // deterministic Linear, operand [Np][Kp] zero-padded, bias [Np]
     float *w = nullptr, *b = nullptr;
     int N = 0, K = 0;
@@ -50,16 +48,13 @@ struct pgmi_eve {
           *sp_mean = nullptr, *sp_sd = nullptr, *t_mean = nullptr, *t_sd = nullptr;
     float *wfinal = nullptr, *bout = nullptr, *temp = nullptr;       // sampled: [20 L][Hp], [20 L], [1]
     // workspace (grow-only)
-    uint8_t* res = nullptr;   size_t res_cap = 0;
-    float* mulv = nullptr;    size_t mulv_cap = 0;
-    float *ha = nullptr, *hb = nullptr;  size_t ha_cap = 0, hb_cap = 0;
-    float* logits = nullptr;  size_t logits_cap = 0;
-    float* out3 = nullptr;    size_t out3_cap = 0;   // elbo | bce | kld, [3][M]
-    double* acc = nullptr;    size_t acc_cap = 0;    // [M][3]
+    DevBuf<uint8_t> res;
+    DevBuf<float> mulv, ha, hb, logits;
+    DevBuf<float> out3;       // elbo | bce | kld, [3][M]
+    DevBuf<double> acc;       // [M][3]
     // pgmi_eve_log_prior: hidden vectors [2][EVE_PRIOR_S][wmax], the final kernel's partial sums, accumulators [20 L][3]
-    float* pr_h = nullptr;       size_t pr_h_cap = 0;
-    float* pr_partial = nullptr; size_t pr_partial_cap = 0;
-    double* pr_acc = nullptr;    size_t pr_acc_cap = 0;
+    DevBuf<float> pr_h, pr_partial;
+    DevBuf<double> pr_acc;
 };
 
 namespace pgmi {
@@ -101,15 +96,15 @@ static int64_t eve_count(const pgmi_eve_config* c) {
     return n;
 }
 
-// [N][K] -> zero-padded [pad32(N)][pad32(K)]
+// [N][K] -> zero-padded [roundup32(N)][roundup32(K)]
 static std::vector<float> pad_matrix(const float* w, int N, int K) {
-    const int Np = pad32(N), Kp = pad32(K);
+    const int Np = roundup32(N), Kp = roundup32(K);
     std::vector<float> o((size_t)Np * Kp, 0.0f);
     for (int n = 0; n < N; ++n) memcpy(&o[(size_t)n * Kp], w + (size_t)n * K, (size_t)K * sizeof(float));
     return o;
 }
 static std::vector<float> pad_vector(const float* b, int N) {
-    std::vector<float> o((size_t)pad32(N), 0.0f);
+    std::vector<float> o((size_t)roundup32(N), 0.0f);
     memcpy(o.data(), b, (size_t)N * sizeof(float));
     return o;
 }
@@ -128,40 +123,37 @@ static int zeros_dev(std::vector<void*>& pool, float** p, size_t n) {
 static int eve_build(pgmi_eve* m, const float* w, int64_t n_weights) {
     const pgmi_eve_config& c = m->cfg;
     std::vector<void*>& pool = m->pm.allocs;
-    const float *p = w;
-    auto take = [&](size_t n) { p += n; return p - n; };
-    int rc = PGMI_OK;
-    auto up = [&](float** dst, const std::vector<float>& v) { if (!rc) rc = dev_upload(pool, dst, v.data(), v.size()); };
-    auto up_raw = [&](float** dst, const float* src, size_t n) { if (!rc) rc = dev_upload(pool, dst, src, n); };
+    BlobCursor b(&m->pm, w, n_weights);
+    auto zeros = [&](float** dst, size_t n) { if (!b.rc) b.rc = zeros_dev(pool, dst, n); };
     const int L = c.seq_len, z = c.z_dim, H = c.dec_sizes[c.n_dec - 1], C = c.conv_depth ? c.conv_depth : 20;
-    m->L = L; m->N = 20 * L; m->z = z; m->ldz = pad32(2 * z); m->H = H; m->Hp = pad32(H); m->C = C;
+    m->L = L; m->N = 20 * L; m->z = z; m->ldz = roundup32(2 * z); m->H = H; m->Hp = roundup32(H); m->C = C;
     m->Ht = c.sparsity_tiles ? H / c.sparsity_tiles : 0;
     m->keep24 = c.dropout_p > 0.0f ? (uint32_t)lrint((1.0 - (double)c.dropout_p) * 16777216.0) : 0;
     m->scale = (float)(1.0 / (1.0 - (double)c.dropout_p));
-    m->wmax = pad32(z);
+    m->wmax = roundup32(z);
     // encoder layer 0, transposed: W0t[col][n]
     {
-        const int E0 = c.enc_sizes[0], E0p = pad32(E0);
-        const float* w0 = take((size_t)E0 * m->N);
+        const int E0 = c.enc_sizes[0], E0p = roundup32(E0);
+        const float* w0 = b.take((size_t)E0 * m->N);
         std::vector<float> t((size_t)m->N * E0p, 0.0f);
         for (int n = 0; n < E0; ++n)
             for (int k = 0; k < m->N; ++k) t[(size_t)k * E0p + n] = w0[(size_t)n * m->N + k];
-        up(&m->w0t, t);
-        up(&m->b0, pad_vector(take(E0), E0));
+        b.upload(&m->w0t, t);
+        b.upload(&m->b0, pad_vector(b.take(E0), E0));
         m->wmax = std::max(m->wmax, E0p);
     }
     int in = c.enc_sizes[0];
     for (int i = 1; i < c.n_enc; ++i) {
         EveLinear l;
         l.N = c.enc_sizes[i]; l.K = in;
-        up(&l.w, pad_matrix(take((size_t)l.N * in), l.N, in));
-        up(&l.b, pad_vector(take(l.N), l.N));
+        b.upload(&l.w, pad_matrix(b.take((size_t)l.N * in), l.N, in));
+        b.upload(&l.b, pad_vector(b.take(l.N), l.N));
         m->enc.push_back(l);
-        m->wmax = std::max(m->wmax, pad32(l.N));
+        m->wmax = std::max(m->wmax, roundup32(l.N));
         in = l.N;
     }
     {   // fc_mean | fc_log_var as one layer of 2 z columns
-        const float *wm = take((size_t)z * in), *bm = take(z), *wl = take((size_t)z * in), *bl = take(z);
+        const float *wm = b.take((size_t)z * in), *bm = b.take(z), *wl = b.take((size_t)z * in), *bl = b.take(z);
         std::vector<float> wz((size_t)2 * z * in), bz((size_t)2 * z);
         memcpy(wz.data(), wm, (size_t)z * in * sizeof(float));
         memcpy(wz.data() + (size_t)z * in, wl, (size_t)z * in * sizeof(float));
@@ -169,54 +161,53 @@ static int eve_build(pgmi_eve* m, const float* w, int64_t n_weights) {
         memcpy(bz.data() + z, bl, (size_t)z * sizeof(float));
         EveLinear l;
         l.N = 2 * z; l.K = in;
-        up(&l.w, pad_matrix(wz.data(), 2 * z, in));
-        up(&l.b, pad_vector(bz.data(), 2 * z));
+        b.upload(&l.w, pad_matrix(wz.data(), 2 * z, in));
+        b.upload(&l.b, pad_vector(bz.data(), 2 * z));
         m->enc.push_back(l);
     }
     if (c.sparsity_tiles) {
         const size_t n = (size_t)m->Ht * L;
-        up_raw(&m->sp_mean, take(n), n);
-        up(&m->sp_sd, sd_of(take(n), n));
+        b.upload(&m->sp_mean, n);
+        b.upload(&m->sp_sd, sd_of(b.take(n), n));
     }
     {
         const size_t n = (size_t)C * L * H;
-        up_raw(&m->wout_mean, take(n), n);
-        up(&m->wout_sd, sd_of(take(n), n));
-        up_raw(&m->bout_mean, take(m->N), m->N);
-        up(&m->bout_sd, sd_of(take(m->N), m->N));
+        b.upload(&m->wout_mean, n);
+        b.upload(&m->wout_sd, sd_of(b.take(n), n));
+        b.upload(&m->bout_mean, m->N);
+        b.upload(&m->bout_sd, sd_of(b.take(m->N), m->N));
     }
     if (c.temperature) {
-        up_raw(&m->t_mean, take(1), 1);
-        up(&m->t_sd, sd_of(take(1), 1));
+        b.upload(&m->t_mean, 1);
+        b.upload(&m->t_sd, sd_of(b.take(1), 1));
     }
     m->dec.resize(c.n_dec);
     in = z;
     for (int i = 0; i < c.n_dec; ++i) {
         EveBayes& l = m->dec[i];
         l.N = c.dec_sizes[i]; l.K = in;
-        up_raw(&l.w_mean, take((size_t)l.N * in), (size_t)l.N * in);
-        up_raw(&l.b_mean, take(l.N), l.N);
-        if (!rc) rc = zeros_dev(pool, &l.w, (size_t)pad32(l.N) * pad32(in));
-        if (!rc) rc = zeros_dev(pool, &l.b, pad32(l.N));
-        m->wmax = std::max(m->wmax, pad32(l.N));
+        b.upload(&l.w_mean, (size_t)l.N * in);
+        b.upload(&l.b_mean, l.N);
+        zeros(&l.w, (size_t)roundup32(l.N) * roundup32(in));
+        zeros(&l.b, roundup32(l.N));
+        m->wmax = std::max(m->wmax, roundup32(l.N));
         in = l.N;
     }
     in = z;
     for (int i = 0; i < c.n_dec; ++i) {
         EveBayes& l = m->dec[i];
-        up(&l.w_sd, sd_of(take((size_t)l.N * in), (size_t)l.N * in));
-        up(&l.b_sd, sd_of(take(l.N), l.N));
+        b.upload(&l.w_sd, sd_of(b.take((size_t)l.N * in), (size_t)l.N * in));
+        b.upload(&l.b_sd, sd_of(b.take(l.N), l.N));
         in = l.N;
     }
     if (c.conv_depth) {
-        up_raw(&m->conv_mean, take((size_t)20 * C), (size_t)20 * C);
-        up(&m->conv_sd, sd_of(take((size_t)20 * C), (size_t)20 * C));
+        b.upload(&m->conv_mean, (size_t)20 * C);
+        b.upload(&m->conv_sd, sd_of(b.take((size_t)20 * C), (size_t)20 * C));
     }
-    if (!rc) rc = zeros_dev(pool, &m->wfinal, (size_t)m->N * m->Hp);
-    if (!rc) rc = zeros_dev(pool, &m->bout, m->N);
-    if (!rc) rc = zeros_dev(pool, &m->temp, 1);
-    if (!rc && p != w + n_weights) { set_error("internal: EVE blob walk mismatch"); rc = PGMI_EINVAL; }
-    return rc;
+    zeros(&m->wfinal, (size_t)m->N * m->Hp);
+    zeros(&m->bout, m->N);
+    zeros(&m->temp, 1);
+    return b.finish();
 }
 
 static int eve_rows_per_chunk(const pgmi_eve* m, int M) {
@@ -235,11 +226,8 @@ static int eve_check_call(pgmi_eve* m, const uint8_t* residues, int M) {
 static int eve_encode(pgmi_eve* m, const uint8_t* residues, int M) {
     pgmi_model* pm = &m->pm;
     hipStream_t st = pm->stream;
-    int rc = ensure_cap(pm, &m->res, &m->res_cap, (size_t)M * m->L);
-    if (!rc) rc = ensure_cap(pm, &m->mulv, &m->mulv_cap, (size_t)M * m->ldz);
     const int per = std::min(M, 4096);
-    if (!rc) rc = ensure_cap(pm, &m->ha, &m->ha_cap, (size_t)per * m->wmax);
-    if (!rc) rc = ensure_cap(pm, &m->hb, &m->hb_cap, (size_t)per * m->wmax);
+    int rc = reserve_all(pm, m->res, (size_t)M * m->L, m->mulv, (size_t)M * m->ldz, m->ha, (size_t)per * m->wmax, m->hb, (size_t)per * m->wmax);
     if (rc) return rc;
     PGMI_HIP(hipMemcpyAsync(m->res, residues, (size_t)M * m->L, hipMemcpyHostToDevice, st));
     const int act = m->cfg.enc_act;
@@ -247,15 +235,15 @@ static int eve_encode(pgmi_eve* m, const uint8_t* residues, int M) {
         const int mc = std::min(per, M - r0);
         ProfScope p(pm, PGMI_K_HEAD, 0, 0);
         float *cur = m->ha, *nxt = m->hb;
-        launch_eve_gather(m->res + (size_t)r0 * m->L, m->w0t, m->b0, mc, m->L, pad32(m->cfg.enc_sizes[0]), act, cur, st);
+        launch_eve_gather(m->res + (size_t)r0 * m->L, m->w0t, m->b0, mc, m->L, roundup32(m->cfg.enc_sizes[0]), act, cur, st);
         for (size_t i = 0; i < m->enc.size(); ++i) {
             const EveLinear& l = m->enc[i];
             const bool last = i + 1 == m->enc.size();
             float* dst = last ? m->mulv + (size_t)r0 * m->ldz : nxt;
-            rc = launch_gemm_f32(cur, l.w, l.b, nullptr, dst, mc, pad32(l.N), pad32(l.K), EPI_NONE, st);
+            rc = launch_gemm_f32(cur, l.w, l.b, nullptr, dst, mc, roundup32(l.N), roundup32(l.K), EPI_NONE, st);
             if (rc) return rc;
             if (!last) {
-                launch_eve_act(dst, mc, l.N, pad32(l.N), act, 0, 1.0f, 0, 0, 0, 0, nullptr, 0, st);
+                launch_eve_act(dst, mc, l.N, roundup32(l.N), act, 0, 1.0f, 0, 0, 0, 0, nullptr, 0, st);
                 std::swap(cur, nxt);
             }
         }
@@ -271,8 +259,8 @@ static int eve_sample_weights(pgmi_eve* m, uint64_t seed, uint32_t sample, const
     ProfScope p(pm, PGMI_K_EMBED, 0, (double)m->C * m->L * m->H * 8 + (double)m->N * m->Hp * 4);
     for (size_t i = 0; i < m->dec.size(); ++i) {
         const EveBayes& l = m->dec[i];
-        launch_eve_sample(l.w_mean, l.w_sd, (int64_t)l.N * l.K, l.K, pad32(l.K), seed, sample, PGMI_EVE_T_W + (int)i, inj.w_eps[i], l.w, st);
-        launch_eve_sample(l.b_mean, l.b_sd, l.N, l.N, pad32(l.N), seed, sample, PGMI_EVE_T_B + (int)i, inj.b_eps[i], l.b, st);
+        launch_eve_sample(l.w_mean, l.w_sd, (int64_t)l.N * l.K, l.K, roundup32(l.K), seed, sample, PGMI_EVE_T_W + (int)i, inj.w_eps[i], l.w, st);
+        launch_eve_sample(l.b_mean, l.b_sd, l.N, l.N, roundup32(l.N), seed, sample, PGMI_EVE_T_B + (int)i, inj.b_eps[i], l.b, st);
     }
     launch_eve_sample_final(m->wout_mean, m->wout_sd, m->conv_mean, m->conv_sd, m->sp_mean, m->sp_sd, m->L, m->H, m->Hp, m->C, m->Ht,
                             m->cfg.conv_depth != 0, seed, sample, inj.wout, inj.conv, inj.sparsity, m->wfinal, st);
@@ -293,13 +281,13 @@ static int eve_rows(pgmi_eve* m, int r0, int mc, int64_t row_base, uint64_t seed
         double fl = 0;
         for (const EveBayes& l : m->dec) fl += 2.0 * mc * l.N * l.K;
         ProfScope p(pm, PGMI_K_GEMM_FC1, fl, 0);
-        launch_eve_latent(m->mulv, m->ldz, r0, mc, m->z, pad32(m->z), m->keep24, m->scale, seed, sample, row_base + r0, inj.z_eps, inj.keep[0],
+        launch_eve_latent(m->mulv, m->ldz, r0, mc, m->z, roundup32(m->z), m->keep24, m->scale, seed, sample, row_base + r0, inj.z_eps, inj.keep[0],
                           r0, cur, st);
         for (size_t i = 0; i < m->dec.size(); ++i) {
             const EveBayes& l = m->dec[i];
-            int rc = launch_gemm_f32(cur, l.w, l.b, nullptr, nxt, mc, pad32(l.N), pad32(l.K), EPI_NONE, st);
+            int rc = launch_gemm_f32(cur, l.w, l.b, nullptr, nxt, mc, roundup32(l.N), roundup32(l.K), EPI_NONE, st);
             if (rc) return rc;
-            launch_eve_act(nxt, mc, l.N, pad32(l.N), i + 1 == m->dec.size() ? c.dec_last_act : c.dec_first_act, m->keep24, m->scale, seed, sample,
+            launch_eve_act(nxt, mc, l.N, roundup32(l.N), i + 1 == m->dec.size() ? c.dec_last_act : c.dec_first_act, m->keep24, m->scale, seed, sample,
                            PGMI_EVE_T_KEEP + 1 + (int)i, row_base + r0, inj.keep[i + 1], r0, st);
             std::swap(cur, nxt);
         }
@@ -318,13 +306,8 @@ static int eve_rows(pgmi_eve* m, int r0, int mc, int64_t row_base, uint64_t seed
 }
 
 static int eve_workspace(pgmi_eve* m, int M, int per) {
-    pgmi_model* pm = &m->pm;
-    int rc = ensure_cap(pm, &m->ha, &m->ha_cap, (size_t)per * m->wmax);
-    if (!rc) rc = ensure_cap(pm, &m->hb, &m->hb_cap, (size_t)per * m->wmax);
-    if (!rc) rc = ensure_cap(pm, &m->logits, &m->logits_cap, (size_t)per * m->N);
-    if (!rc) rc = ensure_cap(pm, &m->out3, &m->out3_cap, (size_t)3 * M);
-    if (!rc) rc = ensure_cap(pm, &m->acc, &m->acc_cap, (size_t)3 * M);
-    return rc;
+    return reserve_all(&m->pm, m->ha, (size_t)per * m->wmax, m->hb, (size_t)per * m->wmax, m->logits, (size_t)per * m->N, m->out3, (size_t)3 * M,
+                       m->acc, (size_t)3 * M);
 }
 
 template <typename T>
@@ -369,18 +352,10 @@ int pgmi_eve_create(const pgmi_eve_config* cfg, const float* w, int64_t n_weight
     *out = nullptr;
     int rc = eve_check(cfg);
     if (rc) return rc;
-    if (!w || n_weights != eve_count(cfg)) {
-        set_error("EVE weight blob has %lld elements, config needs %lld", (long long)n_weights, (long long)eve_count(cfg));
-        return PGMI_EINVAL;
-    }
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) { set_error("no HIP device (libpgmi has no CPU fallback)"); return PGMI_ENODEV; }
-    if (device < 0 || device >= n_dev) { set_error("device %d out of range (%d visible)", device, n_dev); return PGMI_EINVAL; }
-    PGMI_HIP(hipSetDevice(device));
     pgmi_eve* m = new pgmi_eve();
+    rc = side_open(&m->pm, "EVE", w, n_weights, eve_count(cfg), false, device, cfg->precision, nullptr);
+    if (rc) { delete m; return rc; }
     m->cfg = *cfg;
-    m->pm.device = device;
-    if (hipStreamCreate(&m->pm.stream) != hipSuccess) { delete m; set_error("hipStreamCreate failed"); return PGMI_EHIP; }
     rc = eve_build(m, w, n_weights);
     if (rc) { pgmi_eve_destroy(m); return rc; }
     *out = m;
@@ -428,9 +403,8 @@ int pgmi_eve_elbo(pgmi_eve* m, const uint8_t* residues, int M, int64_t row_base,
     if (!rc && elbo && hipMemcpyAsync(elbo, m->out3, (size_t)M * 4, hipMemcpyDeviceToHost, st) != hipSuccess) rc = PGMI_EHIP;
     if (!rc && bce && hipMemcpyAsync(bce, m->out3 + M, (size_t)M * 4, hipMemcpyDeviceToHost, st) != hipSuccess) rc = PGMI_EHIP;
     if (!rc && kld && hipMemcpyAsync(kld, m->out3 + 2 * (size_t)M, (size_t)M * 4, hipMemcpyDeviceToHost, st) != hipSuccess) rc = PGMI_EHIP;
-    const hipError_t e = hipStreamSynchronize(st);
+    rc = side_sync(&m->pm, rc, "EVE sample");
     for (void* p : pool) hipFree(p);
-    if (!rc && e != hipSuccess) { set_error("EVE sample failed: %s", hipGetErrorString(e)); rc = PGMI_EHIP; }
     return rc;
 }
 
@@ -563,9 +537,8 @@ extern "C" int pgmi_eve_log_prior(pgmi_eve* m, const uint8_t* residues, int num_
     pgmi_model* pm = &m->pm;
     hipStream_t st = pm->stream;
     rc = eve_encode(m, residues, 1);
-    if (!rc) rc = ensure_cap(pm, &m->pr_h, &m->pr_h_cap, (size_t)2 * EVE_PRIOR_S * m->wmax);
-    if (!rc) rc = ensure_cap(pm, &m->pr_partial, &m->pr_partial_cap, (size_t)EVE_PRIOR_S * eve_prior_blocks(m->L, m->H) * eve_prior_kmax(m->H));
-    if (!rc) rc = ensure_cap(pm, &m->pr_acc, &m->pr_acc_cap, (size_t)3 * m->N);
+    if (!rc) rc = reserve_all(pm, m->pr_h, (size_t)2 * EVE_PRIOR_S * m->wmax,
+                              m->pr_partial, (size_t)EVE_PRIOR_S * eve_prior_blocks(m->L, m->H) * eve_prior_kmax(m->H), m->pr_acc, (size_t)3 * m->N);
     if (rc) return rc;
     // "eve_prior_batch" samples at a time (default: what one launch serves), each batch in launches of at most smax samples
     const int batch = g_eve_prior_batch > 0 ? (int)std::min<long long>(g_eve_prior_batch, num_samples) : smax;
@@ -579,9 +552,8 @@ extern "C" int pgmi_eve_log_prior(pgmi_eve* m, const uint8_t* residues, int num_
                 EveInj inj[EVE_PRIOR_S];
                 for (int s = 0; s < S && !rc; ++s) rc = eve_upload_noise(m, injected + k0 + s, 1, pool, &inj[s], false);
                 if (!rc) rc = eve_prior_group(m, seed, k0, S, inj);
-                const hipError_t e = hipStreamSynchronize(st);
+                rc = side_sync(pm, rc, "EVE log-prior");
                 for (void* p : pool) hipFree(p);
-                if (!rc && e != hipSuccess) { set_error("EVE log-prior failed: %s", hipGetErrorString(e)); rc = PGMI_EHIP; }
             } else {
                 rc = eve_prior_group(m, seed, k0, S, nullptr);
             }

@@ -441,7 +441,41 @@ int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int 
 
 namespace pgmi {
 
-// what a side handle's embedded pgmi_model holds: after the stream's work, its profiling events, its pool and the stream if it is the handle's
+int side_open(pgmi_model* pm, const char* name, const float* w, int64_t n_weights, int64_t want, bool scan_finite, int device, int precision,
+              hipStream_t lend) {
+    if (!w || n_weights != want) {
+        set_error("%s weight blob has %lld elements, config needs %lld", name, (long long)n_weights, (long long)want);
+        return PGMI_EINVAL;
+    }
+    for (int64_t i = 0; scan_finite && i < n_weights; ++i)
+        if (!std::isfinite(w[i])) { set_error("%s: weight blob element %lld is not finite", name, (long long)i); return PGMI_EINVAL; }
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) { set_error("no HIP device (libpgmi has no CPU fallback)"); return PGMI_ENODEV; }
+    if (device < 0 || device >= n_dev) { set_error("device %d out of range (%d visible)", device, n_dev); return PGMI_EINVAL; }
+    PGMI_HIP(hipSetDevice(device));
+    gemm_options_from_env();
+    pm->device = device;
+    pm->cfg.precision = precision;                       // what BlobCursor and linear() read
+    if (lend) pm->stream = lend;
+    else if (hipStreamCreate(&pm->stream) != hipSuccess) { set_error("hipStreamCreate failed"); return PGMI_EHIP; }
+    return PGMI_OK;
+}
+
+int side_sync(pgmi_model* pm, int rc, const char* what) {
+    const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(pm->stream);
+    if (!rc && (e1 != hipSuccess || e2 != hipSuccess)) {
+        set_error("%s failed: %s", what, hipGetErrorString(e1 != hipSuccess ? e1 : e2));
+        rc = PGMI_EHIP;
+    }
+    return rc;
+}
+
+int overflow_error(int precision) {
+    set_error("non-finite log-probabilities%s", precision == PGMI_PREC_F16X3
+              ? ": an activation left the fp16 range in precision f16x3; re-run with precision fp32" : "");
+    return PGMI_EOVERFLOW;
+}
+
 void side_release(pgmi_model* pm, bool own_stream) {
     hipSetDevice(pm->device);
     if (pm->stream) hipStreamSynchronize(pm->stream);

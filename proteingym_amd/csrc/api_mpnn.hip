@@ -31,8 +31,7 @@ struct MpnnDec {
     float *W1b = nullptr;                     // [128][128]
     float *T = nullptr;                       // [22][128]: W1c W_s[s], row 21 zeros
     MpnnLin W2, W3, Win, Wout;
-    float *Ep = nullptr, *Penc = nullptr;     // per structure: W1b h_E [L K][128], W1d h_V^enc [L][128]
-    size_t Ep_cap = 0, Penc_cap = 0;
+    DevBuf<float> Ep, Penc;                   // per structure: W1b h_E [L K][128], W1d h_V^enc [L][128]
 };
 
 }  // namespace pgmi
@@ -46,18 +45,15 @@ struct pgmi_mpnn {
     std::vector<MpnnDec> dec;
     // structure
     int L = 0, K = 0;
-    float *X = nullptr, *mask = nullptr, *Dnb = nullptr, *E = nullptr, *hE = nullptr, *hV = nullptr, *AP0 = nullptr;
-    int32_t *ridx = nullptr, *chain = nullptr, *E_idx = nullptr;
-    size_t X_cap = 0, mask_cap = 0, Dnb_cap = 0, E_cap = 0, hE_cap = 0, hV_cap = 0, AP0_cap = 0, ridx_cap = 0, chain_cap = 0, Eidx_cap = 0;
+    DevBuf<float> X, mask, Dnb, E, hE, hV, AP0;
+    DevBuf<int32_t> ridx, chain, E_idx;
     // workspace of the structure pass
-    float *cat = nullptr, *t1 = nullptr, *t2 = nullptr, *n1 = nullptr, *n2 = nullptr, *nf = nullptr;
-    size_t cat_cap = 0, t1_cap = 0, t2_cap = 0, n1_cap = 0, n2_cap = 0, nf_cap = 0;
+    DevBuf<float> cat, t1, t2, n1, n2, nf;
     // workspace of a chunk of mutants
-    uint8_t* S = nullptr;     size_t S_cap = 0;
-    int32_t* rank = nullptr;  size_t rank_cap = 0;
-    float *sum = nullptr, *tmp = nullptr, *h1 = nullptr, *h = nullptr, *ffn = nullptr, *AP = nullptr, *nll = nullptr, *lp = nullptr;
-    size_t sum_cap = 0, tmp_cap = 0, h1_cap = 0, h_cap = 0, ffn_cap = 0, AP_cap = 0, nll_cap = 0, lp_cap = 0;
-    double* score = nullptr;  size_t score_cap = 0;
+    DevBuf<uint8_t> S;
+    DevBuf<int32_t> rank;
+    DevBuf<float> sum, tmp, h1, h, ffn, AP, nll, lp;
+    DevBuf<double> score;
 };
 
 namespace pgmi {
@@ -88,40 +84,36 @@ static int64_t mpnn_count(const pgmi_mpnn_config* c) {
 }
 
 static int mpnn_build(pgmi_mpnn* m, const float* w, int64_t n_weights) {
-    std::vector<void*>& pool = m->pm.allocs;
-    const float* p = w;
-    auto take = [&](size_t n) { p += n; return p - n; };
-    int rc = PGMI_OK;
-    auto up = [&](float** dst, const float* src, size_t n) { if (!rc) rc = dev_upload(pool, dst, src, n); };
-    auto lin = [&](MpnnLin* l, size_t N, size_t K) { up(&l->w, take(N * K), N * K); up(&l->b, take(N), N); };
-    up(&m->Wpos, take(16 * 66), 16 * 66);
-    up(&m->bpos, take(16), 16);
+    BlobCursor blob(&m->pm, w, n_weights);
+    auto lin = [&](MpnnLin* l, size_t N, size_t K) { blob.upload(&l->w, N * K); blob.upload(&l->b, N); };
+    blob.upload(&m->Wpos, 16 * 66);
+    blob.upload(&m->bpos, 16);
     {   // edge_embedding [128][416] -> transposed [416][128]: the feature kernel reads a feature's 128 columns as one line
-        const float* we = take((size_t)H * 416);
+        const float* we = blob.take((size_t)H * 416);
         std::vector<float> t((size_t)416 * H);
         for (int n = 0; n < H; ++n)
             for (int f = 0; f < 416; ++f) t[(size_t)f * H + n] = we[(size_t)n * 416 + f];
-        up(&m->Wt, t.data(), t.size());
+        blob.upload(&m->Wt, t);
     }
-    up(&m->nEw, take(H), H);
-    up(&m->nEb, take(H), H);
+    blob.upload(&m->nEw, H);
+    blob.upload(&m->nEb, H);
     lin(&m->We, H, H);
-    const float* Ws = take((size_t)V * H);
+    const float* Ws = blob.take((size_t)V * H);
     m->enc.resize(m->cfg.enc_layers);
     for (MpnnEnc& e : m->enc) {
-        up(&e.n1w, take(H), H); up(&e.n1b, take(H), H);
-        up(&e.n2w, take(H), H); up(&e.n2b, take(H), H);
-        up(&e.n3w, take(H), H); up(&e.n3b, take(H), H);
+        blob.upload(&e.n1w, H); blob.upload(&e.n1b, H);
+        blob.upload(&e.n2w, H); blob.upload(&e.n2b, H);
+        blob.upload(&e.n3w, H); blob.upload(&e.n3b, H);
         lin(&e.W1, H, 3 * H); lin(&e.W2, H, H); lin(&e.W3, H, H);
         lin(&e.W11, H, 3 * H); lin(&e.W12, H, H); lin(&e.W13, H, H);
         lin(&e.Win, FF, H); lin(&e.Wout, H, FF);
     }
     m->dec.resize(m->cfg.dec_layers);
     for (MpnnDec& d : m->dec) {
-        up(&d.n1w, take(H), H); up(&d.n1b, take(H), H);
-        up(&d.n2w, take(H), H); up(&d.n2b, take(H), H);
-        const float* W1 = take((size_t)H * 4 * H);          // [128][512] = [W1a | W1b | W1c | W1d] by input block
-        const float* b1 = take(H);
+        blob.upload(&d.n1w, H); blob.upload(&d.n1b, H);
+        blob.upload(&d.n2w, H); blob.upload(&d.n2b, H);
+        const float* W1 = blob.take((size_t)H * 4 * H);          // [128][512] = [W1a | W1b | W1c | W1d] by input block
+        const float* b1 = blob.take(H);
         std::vector<float> wap((size_t)2 * H * H), bap((size_t)2 * H, 0.0f), w1b((size_t)H * H), T((size_t)(V + 1) * H, 0.0f);
         for (int n = 0; n < H; ++n) {
             memcpy(&wap[(size_t)n * H], W1 + (size_t)n * 4 * H, H * sizeof(float));
@@ -134,16 +126,15 @@ static int mpnn_build(pgmi_mpnn* m, const float* w, int64_t n_weights) {
                 T[(size_t)s * H + n] = (float)a;
             }
         }
-        up(&d.Wap, wap.data(), wap.size());
-        up(&d.bap, bap.data(), bap.size());
-        up(&d.W1b, w1b.data(), w1b.size());
-        up(&d.T, T.data(), T.size());
+        blob.upload(&d.Wap, wap);
+        blob.upload(&d.bap, bap);
+        blob.upload(&d.W1b, w1b);
+        blob.upload(&d.T, T);
         lin(&d.W2, H, H); lin(&d.W3, H, H);
         lin(&d.Win, FF, H); lin(&d.Wout, H, FF);
     }
     lin(&m->Whead, V, H);
-    if (!rc && p != w + n_weights) { set_error("internal: ProteinMPNN blob walk mismatch"); rc = PGMI_EINVAL; }
-    return rc;
+    return blob.finish();
 }
 
 // one edge MLP of an encoder layer on the concatenated rows: out = W_c GELU(W_b GELU(W_a cat)) (+ residual)
@@ -183,26 +174,12 @@ static int mpnn_structure(pgmi_mpnn* m, const float* X, const float* mask, const
     const int K = std::min(m->cfg.num_edges, L);
     const size_t LK = (size_t)L * K;
     m->L = 0;                                    // no structure while this pass has not succeeded
-    int rc = ensure_cap(pm, &m->X, &m->X_cap, (size_t)L * 12);
-    if (!rc) rc = ensure_cap(pm, &m->mask, &m->mask_cap, (size_t)L);
-    if (!rc) rc = ensure_cap(pm, &m->ridx, &m->ridx_cap, (size_t)L);
-    if (!rc) rc = ensure_cap(pm, &m->chain, &m->chain_cap, (size_t)L);
-    if (!rc) rc = ensure_cap(pm, &m->E_idx, &m->Eidx_cap, LK);
-    if (!rc) rc = ensure_cap(pm, &m->Dnb, &m->Dnb_cap, LK);
-    if (!rc) rc = ensure_cap(pm, &m->E, &m->E_cap, LK * H);
-    if (!rc) rc = ensure_cap(pm, &m->hE, &m->hE_cap, LK * H);
-    if (!rc) rc = ensure_cap(pm, &m->hV, &m->hV_cap, (size_t)L * H);
-    if (!rc) rc = ensure_cap(pm, &m->AP0, &m->AP0_cap, (size_t)L * 2 * H);
-    if (!rc) rc = ensure_cap(pm, &m->cat, &m->cat_cap, LK * 3 * H);
-    if (!rc) rc = ensure_cap(pm, &m->t1, &m->t1_cap, LK * H);
-    if (!rc) rc = ensure_cap(pm, &m->t2, &m->t2_cap, LK * H);
-    if (!rc) rc = ensure_cap(pm, &m->n1, &m->n1_cap, (size_t)L * H);
-    if (!rc) rc = ensure_cap(pm, &m->n2, &m->n2_cap, (size_t)L * H);
-    if (!rc) rc = ensure_cap(pm, &m->nf, &m->nf_cap, (size_t)L * FF);
-    for (MpnnDec& d : m->dec) {
-        if (!rc) rc = ensure_cap(pm, &d.Ep, &d.Ep_cap, LK * H);
-        if (!rc) rc = ensure_cap(pm, &d.Penc, &d.Penc_cap, (size_t)L * H);
-    }
+    const size_t Ln = L;
+    int rc = reserve_all(pm, m->X, Ln * 12, m->mask, Ln, m->ridx, Ln, m->chain, Ln, m->E_idx, LK, m->Dnb, LK, m->E, LK * H, m->hE, LK * H,
+                         m->hV, Ln * H, m->AP0, Ln * 2 * H, m->cat, LK * 3 * H, m->t1, LK * H, m->t2, LK * H, m->n1, Ln * H, m->n2, Ln * H,
+                         m->nf, Ln * FF);
+    for (MpnnDec& d : m->dec)
+        if (!rc) rc = reserve_all(pm, d.Ep, LK * H, d.Penc, Ln * H);
     if (rc) return rc;
     m->K = K;
     m->L = L;                                    // the helpers below read m->L / m->K; back to 0 at the end if anything failed
@@ -242,11 +219,7 @@ static int mpnn_structure(pgmi_mpnn* m, const float* X, const float* mask, const
         if (!rc) rc = launch_gemm_f32(m->hV, m->dec[0].Wap, m->dec[0].bap, nullptr, m->AP0, L, 2 * H, H, EPI_NONE, st);
     }
     // always reached once a copy may be in flight: the caller's arrays are free to go when this returns
-    const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(st);
-    if (!rc && (e1 != hipSuccess || e2 != hipSuccess)) {
-        set_error("ProteinMPNN structure pass failed: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2));
-        rc = PGMI_EHIP;
-    }
+    rc = side_sync(pm, rc, "ProteinMPNN structure pass");
     if (rc) m->L = 0;
     return rc;
 }
@@ -320,17 +293,9 @@ static int mpnn_run(pgmi_mpnn* m, const uint8_t* S, const int32_t* rank, int B, 
     pgmi_model* pm = &m->pm;
     const int per = mpnn_per_chunk(m, B);
     const size_t R = (size_t)per * L;
-    int rc = ensure_cap(pm, &m->S, &m->S_cap, R);
-    if (!rc) rc = ensure_cap(pm, &m->rank, &m->rank_cap, R);
-    if (!rc) rc = ensure_cap(pm, &m->sum, &m->sum_cap, R * H);
-    if (!rc) rc = ensure_cap(pm, &m->tmp, &m->tmp_cap, R * H);
-    if (!rc) rc = ensure_cap(pm, &m->h1, &m->h1_cap, R * H);
-    if (!rc) rc = ensure_cap(pm, &m->h, &m->h_cap, R * H);
-    if (!rc) rc = ensure_cap(pm, &m->ffn, &m->ffn_cap, R * FF);
-    if (!rc) rc = ensure_cap(pm, &m->AP, &m->AP_cap, R * 2 * H);
-    if (!rc) rc = ensure_cap(pm, &m->nll, &m->nll_cap, R);
-    if (!rc && lp) rc = ensure_cap(pm, &m->lp, &m->lp_cap, R * V);
-    if (!rc) rc = ensure_cap(pm, &m->score, &m->score_cap, (size_t)B);
+    int rc = reserve_all(pm, m->S, R, m->rank, R, m->sum, R * H, m->tmp, R * H, m->h1, R * H, m->h, R * H, m->ffn, R * FF, m->AP, R * 2 * H,
+                         m->nll, R, m->score, (size_t)B);
+    if (!rc && lp) rc = m->lp.reserve(pm, R * V);
     if (rc) return rc;
     int chunks = 0;
     for (int b0 = 0; b0 < B && !rc; b0 += per) {
@@ -339,9 +304,7 @@ static int mpnn_run(pgmi_mpnn* m, const uint8_t* S, const int32_t* rank, int B, 
         if (!rc && pm->prof && (++chunks & 15) == 15) rc = prof_drain(pm);
     }
     if (!rc && scores && hipMemcpyAsync(scores, m->score, (size_t)B * 8, hipMemcpyDeviceToHost, pm->stream) != hipSuccess) rc = PGMI_EHIP;
-    const hipError_t e = hipStreamSynchronize(pm->stream);
-    if (!rc && e != hipSuccess) { set_error("ProteinMPNN decoder failed: %s", hipGetErrorString(e)); rc = PGMI_EHIP; }
-    return rc;
+    return side_sync(pm, rc, "ProteinMPNN decoder");
 }
 
 }  // namespace pgmi
@@ -358,18 +321,10 @@ int pgmi_mpnn_create(const pgmi_mpnn_config* cfg, const float* w, int64_t n_weig
     *out = nullptr;
     int rc = mpnn_check(cfg);
     if (rc) return rc;
-    if (!w || n_weights != mpnn_count(cfg)) {
-        set_error("ProteinMPNN weight blob has %lld elements, config needs %lld", (long long)n_weights, (long long)mpnn_count(cfg));
-        return PGMI_EINVAL;
-    }
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) { set_error("no HIP device (libpgmi has no CPU fallback)"); return PGMI_ENODEV; }
-    if (device < 0 || device >= n_dev) { set_error("device %d out of range (%d visible)", device, n_dev); return PGMI_EINVAL; }
-    PGMI_HIP(hipSetDevice(device));
     pgmi_mpnn* m = new pgmi_mpnn();
+    rc = side_open(&m->pm, "ProteinMPNN", w, n_weights, mpnn_count(cfg), false, device, cfg->precision, nullptr);
+    if (rc) { delete m; return rc; }
     m->cfg = *cfg;
-    m->pm.device = device;
-    if (hipStreamCreate(&m->pm.stream) != hipSuccess) { delete m; set_error("hipStreamCreate failed"); return PGMI_EHIP; }
     rc = mpnn_build(m, w, n_weights);
     if (rc) { pgmi_mpnn_destroy(m); return rc; }
     *out = m;

@@ -27,19 +27,15 @@ struct pgmi_protssn {
     float *wlin = nullptr, *blin = nullptr;
     // the graph last set: edges in the caller's order, the CSR by neighbour (off [L + 1], eid [E]), ea [E][Ap] = attributes | d2 | 0
     int L = 0, E = 0;
-    int32_t *centre = nullptr, *nb = nullptr, *off = nullptr, *eid = nullptr;
-    float* ea = nullptr;
-    size_t centre_cap = 0, nb_cap = 0, off_cap = 0, eid_cap = 0, ea_cap = 0;
+    DevBuf<int32_t> centre, nb, off, eid;
+    DevBuf<float> ea;
     // workspace: x [L][D]; P [L][2 Hp]; S [chunk][Hp]; msg [E][hp]; t [L][2 D]; lp [L][20]; the operands (split planes or fp32 rows, 4
     // bytes per element either way) x16 [L][D], a [chunk][Hp], nA [L][D + hp], g [L][2 D]
-    float *x = nullptr, *P = nullptr, *S = nullptr, *msg = nullptr, *t = nullptr, *lp = nullptr;
-    uint32_t *x16 = nullptr, *a = nullptr, *nA = nullptr, *g = nullptr;
-    size_t x_cap = 0, P_cap = 0, S_cap = 0, msg_cap = 0, t_cap = 0, lp_cap = 0, x16_cap = 0, a_cap = 0, nA_cap = 0, g_cap = 0;
+    DevBuf<float> x, P, S, msg, t, lp;
+    DevBuf<uint32_t> x16, a, nA, g;
 };
 
 namespace pgmi {
-
-static int roundup32(int v) { return (v + 31) / 32 * 32; }
 
 static int protssn_check(const pgmi_protssn_config* c) {
     if (!c) { set_error("null config"); return PGMI_EINVAL; }
@@ -78,31 +74,17 @@ static int protssn_build(pgmi_protssn* m, const float* w, int64_t n_weights) {
 }
 
 static int protssn_workspace(pgmi_protssn* m) {
-    pgmi_model* pm = &m->pm;
     const size_t L = m->L, E = m->E, D = m->D, hp = m->hp, Hp = m->Hp, C = std::min<size_t>(m->chunk, E);
-    int rc = ensure_cap(pm, &m->x, &m->x_cap, L * D);
-    if (!rc) rc = ensure_cap(pm, &m->x16, &m->x16_cap, L * D);
-    if (!rc) rc = ensure_cap(pm, &m->P, &m->P_cap, L * 2 * Hp);
-    if (!rc) rc = ensure_cap(pm, &m->S, &m->S_cap, C * Hp);
-    if (!rc) rc = ensure_cap(pm, &m->a, &m->a_cap, C * Hp);
-    if (!rc) rc = ensure_cap(pm, &m->msg, &m->msg_cap, E * hp);
-    if (!rc) rc = ensure_cap(pm, &m->nA, &m->nA_cap, L * (D + hp));
-    if (!rc) rc = ensure_cap(pm, &m->t, &m->t_cap, L * 2 * D);
-    if (!rc) rc = ensure_cap(pm, &m->g, &m->g_cap, L * 2 * D);
-    if (!rc) rc = ensure_cap(pm, &m->lp, &m->lp_cap, L * 20);
-    return rc;
+    return reserve_all(&m->pm, m->x, L * D, m->x16, L * D, m->P, L * 2 * Hp, m->S, C * Hp, m->a, C * Hp, m->msg, E * hp, m->nA, L * (D + hp),
+                       m->t, L * 2 * D, m->g, L * 2 * D, m->lp, L * 20);
 }
 
 // a Linear on `rows` operand rows (split planes in precision f16x3, fp32 rows otherwise)
 static int protssn_gemm(pgmi_protssn* m, int cls, const void* in, const float* w32, const W16& w16, const float* bias, const float* residual,
                         float* out, int rows, int N, int K) {
     ProfScope p(&m->pm, cls, 2.0 * rows * (double)N * K, 0);
-    hipStream_t st = m->pm.stream;
-    if (m->cfg.precision == PGMI_PREC_FP32) return launch_gemm_f32(static_cast<const float*>(in), w32, bias, residual, out, rows, N, K, EPI_NONE, st);
-    GemmLaunch g;
-    g.A = static_cast<const unsigned short*>(in); g.W = w16.p; g.out_scale = w16.out_scale; g.bias = bias; g.residual = residual;
-    g.out32 = out; g.M = rows; g.N = N; g.K = K; g.stream = st;
-    return launch_gemm16(g);
+    return linear(&m->pm, static_cast<const float*>(in), static_cast<const unsigned short*>(in), w32, w16, bias, residual, out, nullptr, rows, N, K,
+                  EPI_NONE);
 }
 
 // one layer's messages and their sums: m->x [L][D] -> m->nA [L][D + hp] = [x | m_i], the W3 product's operand
@@ -114,7 +96,7 @@ static int protssn_message(pgmi_protssn* m, const EgnnLayer& l) {
     int rc;
     if (split) {
         ProfScope p(pm, PGMI_K_LAYERNORM, 0, (double)L * D * 8);
-        launch_split16(m->x, (int64_t)L * D, 1.0f, 2, D, reinterpret_cast<unsigned short*>(m->x16), st);
+        launch_split16(m->x, (int64_t)L * D, 1.0f, 2, D, reinterpret_cast<unsigned short*>(m->x16.p), st);
     }
     if ((rc = protssn_gemm(m, PGMI_K_GEMM_QKV, split ? (const void*)m->x16 : (const void*)m->x, l.wij, l.wij16, nullptr, nullptr, m->P, L, 2 * Hp, D)))
         return rc;
@@ -146,8 +128,8 @@ static int protssn_layers(pgmi_protssn* m) {
         if ((rc = protssn_gemm(m, PGMI_K_GEMM_FC1, m->nA, l.w3, l.w316, l.b3, nullptr, m->t, L, 2 * D, D + hp))) return rc;
         {
             ProfScope p(pm, PGMI_K_KEPT_ROWS, 0, (double)L * 2 * D * 8);
-            if (split) launch_silu_split(m->t, L, 2 * D, reinterpret_cast<unsigned short*>(m->g), st);
-            else launch_egnn_silu_rows(m->t, L, 2 * D, reinterpret_cast<float*>(m->g), st);
+            if (split) launch_silu_split(m->t, L, 2 * D, reinterpret_cast<unsigned short*>(m->g.p), st);
+            else launch_egnn_silu_rows(m->t, L, 2 * D, reinterpret_cast<float*>(m->g.p), st);
         }
         if ((rc = protssn_gemm(m, PGMI_K_GEMM_FC2, m->g, l.w4, l.w416, l.b4, m->x, m->x, L, D, 2 * D))) return rc;
         if (pm->prof && (rc = prof_drain(pm))) return rc;
@@ -163,25 +145,13 @@ static int protssn_new(const pgmi_protssn_config* cfg, const float* w, int64_t n
     *out = nullptr;
     int rc = protssn_check(cfg);
     if (rc) return rc;
-    if (!w || n_weights != protssn_count(cfg)) {
-        set_error("ProtSSN weight blob has %lld elements, config needs %lld", (long long)n_weights, (long long)protssn_count(cfg));
-        return PGMI_EINVAL;
-    }
-    for (int64_t i = 0; i < n_weights; ++i)
-        if (!std::isfinite(w[i])) { set_error("ProtSSN: weight blob element %lld is not finite", (long long)i); return PGMI_EINVAL; }
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) { set_error("no HIP device (libpgmi has no CPU fallback)"); return PGMI_ENODEV; }
-    if (device < 0 || device >= n_dev) { set_error("device %d out of range (%d visible)", device, n_dev); return PGMI_EINVAL; }
-    PGMI_HIP(hipSetDevice(device));
-    gemm_options_from_env();
     pgmi_protssn* m = new pgmi_protssn();
+    rc = side_open(&m->pm, "ProtSSN", w, n_weights, protssn_count(cfg), true, device, cfg->precision, nullptr);
+    if (rc) { delete m; return rc; }
     m->cfg = *cfg;
     m->D = cfg->node_in; m->h = cfg->hidden; m->hp = roundup32(cfg->hidden); m->A = cfg->edge_attr_dim; m->Ap = roundup32(cfg->edge_attr_dim + 1);
     m->Hp = roundup32(2 * (2 * cfg->node_in + cfg->edge_attr_dim + 1));
     m->chunk = cfg->edge_chunk > 0 ? cfg->edge_chunk : PROTSSN_CHUNK_DEFAULT;
-    m->pm.device = device;
-    m->pm.cfg.precision = cfg->precision;                 // what the blob walker reads
-    if (hipStreamCreate(&m->pm.stream) != hipSuccess) { delete m; set_error("hipStreamCreate failed"); return PGMI_EHIP; }
     rc = protssn_build(m, w, n_weights);
     if (rc) { pgmi_protssn_destroy(m); return rc; }
     *out = m;
@@ -229,11 +199,7 @@ static int protssn_set_graph(pgmi_protssn* m, const float* pos, int L, int E, co
         std::vector<int32_t> next(off.begin(), off.end() - 1);
         for (int e = 0; e < E; ++e) eid[next[nb[e]]++] = e;            // ascending e per node: a stable sort by target
     }
-    int rc = ensure_cap(pm, &m->centre, &m->centre_cap, (size_t)E);
-    if (!rc) rc = ensure_cap(pm, &m->nb, &m->nb_cap, (size_t)E);
-    if (!rc) rc = ensure_cap(pm, &m->eid, &m->eid_cap, (size_t)E);
-    if (!rc) rc = ensure_cap(pm, &m->off, &m->off_cap, (size_t)L + 1);
-    if (!rc) rc = ensure_cap(pm, &m->ea, &m->ea_cap, (size_t)E * Ap);
+    const int rc = reserve_all(pm, m->centre, E, m->nb, E, m->eid, E, m->off, (size_t)L + 1, m->ea, (size_t)E * Ap);
     if (rc) return rc;
     {
         ProfScope p(pm, PGMI_K_EMBED, 0, (double)E * (Ap + 3) * 4);
@@ -250,12 +216,8 @@ static int protssn_set_graph(pgmi_protssn* m, const float* pos, int L, int E, co
 }
 
 static int protssn_finish(pgmi_protssn* m, const char* what) {
-    const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(m->pm.stream);
-    if (e1 != hipSuccess || e2 != hipSuccess) {
-        set_error("ProtSSN %s failed: %s", what, hipGetErrorString(e1 != hipSuccess ? e1 : e2));
-        return PGMI_EHIP;
-    }
-    return m->pm.prof ? prof_drain(&m->pm) : PGMI_OK;
+    const int rc = side_sync(&m->pm, PGMI_OK, what);
+    return rc || !m->pm.prof ? rc : prof_drain(&m->pm);
 }
 
 }  // namespace pgmi
@@ -300,13 +262,9 @@ int pgmi_protssn_forward(pgmi_protssn* m, const float* esm_rep, float* lp, float
     if (rc) { hipStreamSynchronize(st); return rc; }
     PGMI_HIP(hipMemcpyAsync(lp, m->lp, (size_t)m->L * 20 * 4, hipMemcpyDeviceToHost, st));
     if (hidden) PGMI_HIP(hipMemcpyAsync(hidden, m->x, n * 4, hipMemcpyDeviceToHost, st));
-    if ((rc = protssn_finish(m, "forward"))) return rc;
+    if ((rc = protssn_finish(m, "ProtSSN forward"))) return rc;
     for (size_t i = 0; i < (size_t)m->L * 20; ++i)
-        if (!std::isfinite(lp[i])) {
-            set_error("non-finite log-probabilities%s", m->cfg.precision == PGMI_PREC_F16X3
-                      ? ": an activation left the fp16 range in precision f16x3; re-run with precision fp32" : "");
-            return PGMI_EOVERFLOW;
-        }
+        if (!std::isfinite(lp[i])) return overflow_error(m->cfg.precision);
     return PGMI_OK;
 }
 
@@ -352,7 +310,7 @@ int pgmi_op_egnn_message(int device, const pgmi_protssn_config* cfg, const float
         if (e == hipSuccess) rc = protssn_message(m, m->layers[0]);
         if (!rc && e == hipSuccess) e = hipMemcpyAsync(A.data(), m->nA, A.size() * 4, hipMemcpyDeviceToHost, st);
         if (!rc && e != hipSuccess) { set_error("egnn message op failed: %s", hipGetErrorString(e)); rc = PGMI_EHIP; }
-        if (!rc) rc = protssn_finish(m, "message op");
+        if (!rc) rc = protssn_finish(m, "ProtSSN message op");
     }
     if (!rc) {
         const bool split = cfg->precision != PGMI_PREC_FP32;

@@ -49,42 +49,38 @@ int64_t s2f_count(const pgmi_s2f_config* c, bool surface) {
 }
 
 static int s2f_build(pgmi_s2f* m, const float* w, int64_t n_weights) {
-    std::vector<void*>& pool = m->pm.allocs;
-    const float* p = w;
-    auto take = [&](size_t n) { p += n; return p - n; };
-    int rc = PGMI_OK;
-    auto up = [&](float** dst, const float* src, size_t n) { if (!rc) rc = dev_upload(pool, dst, src, n); };
+    BlobCursor c(&m->pm, w, n_weights);
     auto gvp = [&](S2fGvp* g, int si, int vi, int so, int vo, int h, bool with_ws) {
-        g->si = si, g->vi = vi, g->so = so, g->vo = vo, g->h = h, g->Kp = (si + h + 31) / 32 * 32;
-        up(&g->wh, take((size_t)h * vi), (size_t)h * vi);
-        const float* ws = take((size_t)so * (si + h));
+        g->si = si, g->vi = vi, g->so = so, g->vo = vo, g->h = h, g->Kp = roundup32(si + h);
+        c.upload(&g->wh, (size_t)h * vi);
+        const float* ws = c.take((size_t)so * (si + h));
         if (with_ws) {
             std::vector<float> t((size_t)so * g->Kp, 0.0f);
             for (int n = 0; n < so; ++n) memcpy(&t[(size_t)n * g->Kp], ws + (size_t)n * (si + h), (size_t)(si + h) * sizeof(float));
-            up(&g->ws, t.data(), t.size());
+            c.upload(&g->ws, t);
         }
-        up(&g->bs, take(so), so);
+        c.upload(&g->bs, so);
         if (vo) {
-            up(&g->wv, take((size_t)vo * h), (size_t)vo * h);
-            up(&g->wsv, take((size_t)vo * so), (size_t)vo * so);
-            up(&g->bsv, take(vo), vo);
+            c.upload(&g->wv, (size_t)vo * h);
+            c.upload(&g->wsv, (size_t)vo * so);
+            c.upload(&g->bsv, vo);
         }
         return ws;
     };
     const size_t D = m->D;
-    if (!m->fixed_degree) up(&m->Wre, take(D * D), D * D);
-    up(&m->vnw, take(D), D);
-    up(&m->vnb, take(D), D);
-    up(&m->Wv, take(S2F_S * D), S2F_S * D);
-    up(&m->bv, take(S2F_S), S2F_S);
+    if (!m->fixed_degree) c.upload(&m->Wre, D * D);
+    c.upload(&m->vnw, D);
+    c.upload(&m->vnb, D);
+    c.upload(&m->Wv, S2F_S * D);
+    c.upload(&m->bv, S2F_S);
     {
-        const float* we = take((size_t)s2f_we_count());
+        const float* we = c.take((size_t)s2f_we_count());
         m->we_host.assign(we, we + s2f_we_count());
     }
     m->layers.resize(m->cfg.layers);
     for (S2fLayer& l : m->layers) {
         const int K0 = 2 * S2F_S + S2F_ES + S2F_H0;          // 609 columns: s_j | e_s | s_i | norms
-        const float* wh = p;                                 // [33][33]: v_j | e_v | v_i columns
+        const float* wh = c.p;                                // [33][33]: v_j | e_v | v_i columns
         const float* ws = gvp(&l.m0, 2 * S2F_S + S2F_ES, S2F_H0, S2F_S, S2F_V, S2F_H0, false);
         l.b0 = l.m0.bs;
         std::vector<float> wji((size_t)2 * S2F_S * S2F_S), we((size_t)S2F_S * S2F_ES), wnt((size_t)S2F_H0 * S2F_S),
@@ -101,27 +97,26 @@ static int s2f_build(pgmi_s2f* m, const float* w, int64_t n_weights) {
             whe[h] = wh[(size_t)h * S2F_H0 + S2F_V];
             memcpy(&whji[(size_t)(S2F_H0 + h) * S2F_V], wh + (size_t)h * S2F_H0 + S2F_V + 1, S2F_V * sizeof(float));
         }
-        up(&l.Wji, wji.data(), wji.size());
-        up(&l.We, we.data(), we.size());
-        up(&l.Wnt, wnt.data(), wnt.size());
-        up(&l.whji, whji.data(), whji.size());
-        up(&l.whe, whe.data(), whe.size());
+        c.upload(&l.Wji, wji);
+        c.upload(&l.We, we);
+        c.upload(&l.Wnt, wnt);
+        c.upload(&l.whji, whji);
+        c.upload(&l.whe, whe);
         gvp(&l.m1, S2F_S, S2F_V, S2F_S, S2F_V, S2F_V, true);
         gvp(&l.m2, S2F_S, S2F_V, S2F_S, S2F_V, S2F_V, true);
-        up(&l.n0w, take(S2F_S), S2F_S); up(&l.n0b, take(S2F_S), S2F_S);
-        up(&l.n1w, take(S2F_S), S2F_S); up(&l.n1b, take(S2F_S), S2F_S);
+        c.upload(&l.n0w, S2F_S); c.upload(&l.n0b, S2F_S);
+        c.upload(&l.n1w, S2F_S); c.upload(&l.n1b, S2F_S);
         gvp(&l.f0, S2F_S, S2F_V, S2F_FS, S2F_FV, S2F_FV, true);
         gvp(&l.f1, S2F_FS, S2F_FV, S2F_S, S2F_V, S2F_FV, true);
     }
-    up(&m->onw, take(S2F_S), S2F_S);
-    up(&m->onb, take(S2F_S), S2F_S);
+    c.upload(&m->onw, S2F_S);
+    c.upload(&m->onb, S2F_S);
     gvp(&m->wout, S2F_S, S2F_V, S2F_S, 0, S2F_V, true);
     if (!m->fixed_degree) {
-        up(&m->Wlin, take(20 * S2F_S), 20 * S2F_S);
-        up(&m->blin, take(20), 20);
+        c.upload(&m->Wlin, 20 * S2F_S);
+        c.upload(&m->blin, 20);
     }
-    if (!rc && p != w + n_weights) { set_error("internal: S2F blob walk mismatch"); rc = PGMI_EINVAL; }
-    return rc;
+    return c.finish();
 }
 
 // radius_graph(pos, r, max_num_neighbors) without self loops, as torch_cluster's CUDA kernel keeps it: per centre i the candidates j in
@@ -186,13 +181,11 @@ static void s2f_edge_embed(const pgmi_s2f* m, const float* pos, std::vector<floa
     }
 }
 
-int s2f_buf(pgmi_s2f* m, S2fBuf* b, size_t n) { return ensure_cap(&m->pm, &b->p, &b->cap, n); }
-
 // every layer's edge share of the first message GVP from the E > 0 rows of m->es: Es = We e_s + b [E][256]
 int s2f_edge_tables(pgmi_s2f* m, size_t E) {
     int rc = PGMI_OK;
     for (S2fLayer& l : m->layers) {
-        if (!rc) rc = ensure_cap(&m->pm, &l.Es, &l.Es_cap, E * S2F_S);
+        if (!rc) rc = l.Es.reserve(&m->pm, E * S2F_S);
         if (!rc) rc = launch_gemm_f32(m->es.p, l.We, l.b0, nullptr, l.Es, (int)E, S2F_S, S2F_ES, EPI_NONE, m->pm.stream);
     }
     return rc;
@@ -206,11 +199,7 @@ int s2f_structure(pgmi_s2f* m, const float* pos, const float* plddt, int L) {
     const int E = m->E = (int)m->h_src.size();
     s2f_edge_embed(m, pos, m->h_es, m->h_ev);
     const size_t En = std::max(E, 1);
-    int rc = ensure_cap(pm, &m->src, &m->src_cap, En);
-    if (!rc) rc = ensure_cap(pm, &m->off, &m->off_cap, (size_t)L + 1);
-    if (!rc) rc = s2f_buf(m, &m->es, En * S2F_ES);
-    if (!rc) rc = s2f_buf(m, &m->ev, En * 3);
-    if (!rc) rc = s2f_buf(m, &m->plddt, (size_t)L);
+    int rc = reserve_all(pm, m->src, En, m->off, (size_t)L + 1, m->es, En * S2F_ES, m->ev, En * 3, m->plddt, (size_t)L);
     if (rc) return rc;
     auto upload = [&](void* dst, const void* src, size_t bytes) {
         if (rc || !bytes || hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) == hipSuccess) return;
@@ -226,11 +215,7 @@ int s2f_structure(pgmi_s2f* m, const float* pos, const float* plddt, int L) {
         ProfScope prof(pm, PGMI_K_EMBED, 2.0 * E * S2F_S * S2F_ES * m->layers.size(), 0);
         rc = s2f_edge_tables(m, (size_t)E);
     }
-    const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(st);       // the caller's arrays are free to go after this
-    if (!rc && (e1 != hipSuccess || e2 != hipSuccess)) {
-        set_error("S2F structure pass failed: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2));
-        rc = PGMI_EHIP;
-    }
+    rc = side_sync(pm, rc, "S2F structure pass");         // the caller's arrays are free to go after this
     if (!rc) m->L = L;
     return rc;
 }
@@ -245,22 +230,11 @@ static int s2f_per_chunk(const pgmi_s2f* m, int B) {
 int s2f_workspace(pgmi_s2f* m, int per) {
     const size_t R = (size_t)per * m->L, D = m->D;
     const bool surface = m->fixed_degree != 0;           // a surface half takes its rows from the surface MLP and has no head
-    int rc = surface ? PGMI_OK : s2f_buf(m, &m->feat, R * D);
-    if (!rc) rc = s2f_buf(m, &m->h0, R * D);
-    if (!rc) rc = s2f_buf(m, &m->s, R * S2F_S);
-    if (!rc) rc = s2f_buf(m, &m->v, R * S2F_V * 3);
-    if (!rc) rc = s2f_buf(m, &m->s1, R * S2F_S);
-    if (!rc) rc = s2f_buf(m, &m->v1, R * S2F_V * 3);
-    if (!rc) rc = s2f_buf(m, &m->P, R * 2 * S2F_S);
-    if (!rc) rc = s2f_buf(m, &m->VT, R * 2 * S2F_H0 * 3);
-    if (!rc) rc = s2f_buf(m, &m->pre, R * S2F_FS);
-    if (!rc) rc = s2f_buf(m, &m->gate, R * S2F_FV);
-    if (!rc) rc = s2f_buf(m, &m->A, R * S2F_FK);
-    if (!rc) rc = s2f_buf(m, &m->vhA, R * S2F_FV * 3);
-    if (!rc) rc = s2f_buf(m, &m->vhB, R * S2F_FV * 3);
-    if (!rc) rc = s2f_buf(m, &m->mV, R * S2F_V * 3);
-    if (!rc && !surface) rc = s2f_buf(m, &m->seq, R * 20);
-    if (!rc && !surface) rc = s2f_buf(m, &m->lp, R * 20);
+    pgmi_model* pm = &m->pm;
+    int rc = reserve_all(pm, m->h0, R * D, m->s, R * S2F_S, m->v, R * S2F_V * 3, m->s1, R * S2F_S, m->v1, R * S2F_V * 3, m->P, R * 2 * S2F_S,
+                         m->VT, R * 2 * S2F_H0 * 3, m->pre, R * S2F_FS, m->gate, R * S2F_FV, m->A, R * S2F_FK, m->vhA, R * S2F_FV * 3,
+                         m->vhB, R * S2F_FV * 3, m->mV, R * S2F_V * 3);
+    if (!rc && !surface) rc = reserve_all(pm, m->feat, R * D, m->seq, R * 20, m->lp, R * 20);
     return rc;
 }
 
@@ -405,9 +379,7 @@ int s2f_check_sets(const pgmi_s2f* m, const char* name, const int32_t* wt_tokens
 // what the ESM2 fill of chunks of `per` copies needs: the device index arrays, aa_cols on the device, the host scratch
 int s2f_set_buffers(pgmi_s2f* m, int per, int T, const int32_t* aa_cols, S2fSetHost* h) {
     pgmi_model* pm = &m->pm;
-    int rc = ensure_cap(pm, &m->ridx, &m->ridx_cap, (size_t)per * m->L);
-    if (!rc) rc = ensure_cap(pm, &m->toks, &m->toks_cap, (size_t)per * T);
-    if (!rc) rc = ensure_cap(pm, &m->cols, &m->cols_cap, (size_t)20);
+    const int rc = reserve_all(pm, m->ridx, (size_t)per * m->L, m->toks, (size_t)per * T, m->cols, 20);
     if (rc) return rc;
     PGMI_HIP(hipMemcpyAsync(m->cols, aa_cols, 20 * 4, hipMemcpyHostToDevice, pm->stream));
     h->toks.resize((size_t)per * T);
@@ -480,29 +452,21 @@ int s2f_new(const pgmi_s2f_config* cfg, const float* w, int64_t n_weights, pgmi_
     *out = nullptr;
     int rc = s2f_check(cfg);
     if (rc) return rc;
-    if (!w || n_weights != s2f_count(cfg, fixed_degree != 0)) {
-        set_error("S2F weight blob has %lld elements, config needs %lld", (long long)n_weights, (long long)s2f_count(cfg, fixed_degree != 0));
-        return PGMI_EINVAL;
-    }
     if (esm) {
         if (esm->cfg.arch != PGMI_ARCH_ESM2) { set_error("S2F: the sequence model must be an ESM2 model (arch %d)", esm->cfg.arch); return PGMI_EINVAL; }
         if (esm->cfg.embed_dim != cfg->node_in) { set_error("S2F: node_in %d differs from the ESM2 model's width %d", cfg->node_in, esm->cfg.embed_dim); return PGMI_EINVAL; }
         device = esm->device;
     }
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) { set_error("no HIP device (libpgmi has no CPU fallback)"); return PGMI_ENODEV; }
-    if (device < 0 || device >= n_dev) { set_error("device %d out of range (%d visible)", device, n_dev); return PGMI_EINVAL; }
-    PGMI_HIP(hipSetDevice(device));
+    // one stream with the ESM2 model: the GNN reads what the encoder just wrote
+    hipStream_t lend = esm ? esm->stream : stream_of ? stream_of->pm.stream : nullptr;
     pgmi_s2f* m = new pgmi_s2f();
+    rc = side_open(&m->pm, "S2F", w, n_weights, s2f_count(cfg, fixed_degree != 0), false, device, PGMI_PREC_FP32, lend);
+    if (rc) { delete m; return rc; }
     m->cfg = *cfg;
     m->D = cfg->node_in;
     m->esm = esm;
-    m->pm.device = device;
     m->fixed_degree = fixed_degree;
-    if (esm) m->pm.stream = esm->stream;                 // one stream: the GNN reads what the encoder just wrote
-    else if (stream_of) m->pm.stream = stream_of->pm.stream;
-    else if (hipStreamCreate(&m->pm.stream) != hipSuccess) { delete m; set_error("hipStreamCreate failed"); return PGMI_EHIP; }
-    else m->own_stream = true;
+    m->own_stream = !lend;
     rc = s2f_build(m, w, n_weights);
     if (rc) { pgmi_s2f_destroy(m); return rc; }
     *out = m;
@@ -565,9 +529,7 @@ int pgmi_s2f_gvp_forward(pgmi_s2f* m, const float* node_feat, const float* seq_l
         PGMI_HIP(hipStreamSynchronize(st));
         if (pm->prof) rc = prof_drain(pm);
     }
-    const hipError_t e = hipStreamSynchronize(st);
-    if (!rc && e != hipSuccess) { set_error("S2F forward failed: %s", hipGetErrorString(e)); rc = PGMI_EHIP; }
-    return rc;
+    return side_sync(pm, rc, "S2F forward");
 }
 
 int pgmi_s2f_set_logprobs(pgmi_s2f* m, const int32_t* wt_tokens, int T, const int32_t* aa_cols, const int32_t* set_off,
@@ -596,8 +558,7 @@ int pgmi_s2f_set_logprobs(pgmi_s2f* m, const int32_t* wt_tokens, int T, const in
         if (pm->prof) rc = prof_drain(pm);
         if (!rc && esm->prof) rc = prof_drain(esm);
     }
-    const hipError_t e = hipStreamSynchronize(st);
-    if (!rc && e != hipSuccess) { set_error("S2F scoring failed: %s", hipGetErrorString(e)); rc = PGMI_EHIP; }
+    rc = side_sync(pm, rc, "S2F scoring");
     return rc ? rc : check_nonfinite(esm);
 }
 

@@ -24,16 +24,14 @@ struct pgmi_s3f {
     float *Wz = nullptr, *Wsf = nullptr, *b1 = nullptr, *lnw = nullptr, *lnb = nullptr, *W2 = nullptr, *b2 = nullptr, *we = nullptr;
     // structure
     int Ns = 0;
-    float *spos = nullptr, *cpos = nullptr, *rdist = nullptr;
-    int32_t* rnb = nullptr;                            // [Ns][3] nearest C-alpha atoms
-    size_t spos_cap = 0, cpos_cap = 0, rdist_cap = 0, rnb_cap = 0;
+    pgmi::DevBuf<float> spos, cpos, rdist;
+    pgmi::DevBuf<int32_t> rnb;                         // [Ns][3] nearest C-alpha atoms
     std::vector<int32_t> h_src, h_rnb;
     std::vector<float> h_rdist;
-    pgmi::S2fBuf T, Asf;                               // T [Ns][H]: the structure term of the MLP's first Linear
+    pgmi::DevBuf<float> T, Asf;                           // T [Ns][H]: the structure term of the MLP's first Linear
     // workspace
-    pgmi::S2fBuf Z, Hd, part, hold_pre, hold_seq, hold_lp, hold_sum;
-    int32_t* grp = nullptr;
-    size_t grp_cap = 0;
+    pgmi::DevBuf<float> Z, Hd, part, hold_pre, hold_seq, hold_lp, hold_sum;
+    pgmi::DevBuf<int32_t> grp;
 };
 
 namespace pgmi {
@@ -69,15 +67,8 @@ static int s3f_structure(pgmi_s3f* m, const float* pos, int L, const float* surf
     hipStream_t st = pm->stream;
     const size_t E = (size_t)Ns * S3F_DEG;
     const int H = m->H;
-    int rc = ensure_cap(pm, &m->spos, &m->spos_cap, (size_t)Ns * 3);
-    if (!rc) rc = ensure_cap(pm, &m->cpos, &m->cpos_cap, (size_t)L * 3);
-    if (!rc) rc = ensure_cap(pm, &m->rnb, &m->rnb_cap, (size_t)Ns * S3F_RES);
-    if (!rc) rc = ensure_cap(pm, &m->rdist, &m->rdist_cap, (size_t)Ns * S3F_RES);
-    if (!rc) rc = ensure_cap(pm, &sf->src, &sf->src_cap, E);
-    if (!rc) rc = s2f_buf(sf, &sf->es, E * S2F_ES);
-    if (!rc) rc = s2f_buf(sf, &sf->ev, E * 3);
-    if (!rc) rc = s2f_buf(sf, &m->T, (size_t)Ns * H);
-    if (!rc) rc = s2f_buf(sf, &m->Asf, (size_t)Ns * S3F_KF);
+    int rc = reserve_all(pm, m->spos, (size_t)Ns * 3, m->cpos, (size_t)L * 3, m->rnb, (size_t)Ns * S3F_RES, m->rdist, (size_t)Ns * S3F_RES,
+                         sf->src, E, sf->es, E * S2F_ES, sf->ev, E * 3, m->T, (size_t)Ns * H, m->Asf, (size_t)Ns * S3F_KF);
     if (rc) return rc;
     ProfScope prof(pm, PGMI_K_EMBED, 2.0 * E * S2F_S * S2F_ES * sf->layers.size() + 2.0 * Ns * H * S3F_KF, 0);
     PGMI_HIP(hipMemcpyAsync(m->spos, surf_pos, (size_t)Ns * 3 * 4, hipMemcpyHostToDevice, st));
@@ -104,12 +95,7 @@ static int s3f_structure(pgmi_s3f* m, const float* pos, int L, const float* surf
     }
     PGMI_HIP(hipMemcpyAsync(m->Asf.p, a.data(), a.size() * 4, hipMemcpyHostToDevice, st));
     rc = launch_gemm_f32(m->Asf.p, m->Wsf, m->b1, nullptr, m->T.p, Ns, H, S3F_KF, EPI_NONE, st);
-    const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(st);
-    if (!rc && (e1 != hipSuccess || e2 != hipSuccess)) {
-        set_error("S3F structure pass failed: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2));
-        rc = PGMI_EHIP;
-    }
-    return rc;
+    return side_sync(pm, rc, "S3F structure pass");
 }
 
 // copies per chunk: a masked copy costs max(E, 16 Ns, L + 2) rows
@@ -133,14 +119,9 @@ static int s3f_workspace(pgmi_s3f* m, int per, int hold) {
     const size_t L = m->res->L, Ns = m->Ns, H = m->H;
     int rc = s2f_workspace(m->res, per);
     if (!rc) rc = s2f_workspace(sf, per);
-    if (!rc) rc = s2f_buf(sf, &m->Z, per * L * H);
-    if (!rc) rc = s2f_buf(sf, &m->Hd, per * Ns * H);
-    if (!rc) rc = s2f_buf(sf, &m->part, (size_t)per * s3f_colsum_blocks(m->Ns) * S2F_S);
-    if (!rc) rc = s2f_buf(sf, &m->hold_pre, hold * L * S2F_S);
-    if (!rc) rc = s2f_buf(sf, &m->hold_seq, hold * L * 20);
-    if (!rc) rc = s2f_buf(sf, &m->hold_lp, hold * L * 20);
-    if (!rc) rc = s2f_buf(sf, &m->hold_sum, (size_t)hold * S2F_S);
-    if (!rc) rc = ensure_cap(&sf->pm, &m->grp, &m->grp_cap, (size_t)hold * 2);
+    if (!rc) rc = reserve_all(&sf->pm, m->Z, per * L * H, m->Hd, per * Ns * H, m->part, (size_t)per * s3f_colsum_blocks(m->Ns) * S2F_S,
+                              m->hold_pre, hold * L * S2F_S, m->hold_seq, hold * L * 20, m->hold_lp, hold * L * 20, m->hold_sum, (size_t)hold * S2F_S,
+                              m->grp, (size_t)hold * 2);
     return rc;
 }
 
@@ -350,9 +331,7 @@ int pgmi_s3f_gvp_forward(pgmi_s3f* m, const float* node_feat, const float* seq_l
         return s3f_drain(m);
     };
     rc = s3f_run(m, pool_off, n_pools, per, hold, fill, chunk, done);
-    const hipError_t e = hipStreamSynchronize(st);
-    if (!rc && e != hipSuccess) { set_error("S3F forward failed: %s", hipGetErrorString(e)); rc = PGMI_EHIP; }
-    return rc;
+    return side_sync(&rs->pm, rc, "S3F forward");
 }
 
 int pgmi_s3f_set_logprobs(pgmi_s3f* m, const int32_t* wt_tokens, int T, const int32_t* aa_cols, const int32_t* set_off,
@@ -387,8 +366,7 @@ int pgmi_s3f_set_logprobs(pgmi_s3f* m, const int32_t* wt_tokens, int T, const in
         return s3f_drain(m);
     };
     rc = s3f_run(m, pool_off, n_pools, per, hold, fill, chunk, done);
-    const hipError_t e = hipStreamSynchronize(st);
-    if (!rc && e != hipSuccess) { set_error("S3F scoring failed: %s", hipGetErrorString(e)); rc = PGMI_EHIP; }
+    rc = side_sync(pm, rc, "S3F scoring");
     return rc ? rc : check_nonfinite(esm);
 }
 

@@ -28,17 +28,14 @@ struct pgmi_unirep {
     // the target: inputs ttok [tL], state table entries 0 .. tL (entry j = the state after j steps; entry 0 = zeros), log-prob rows
     int tL = 0;
     std::vector<int32_t> ttok;
-    float *ctab = nullptr, *tlp = nullptr;
-    uint32_t* htab = nullptr;
-    size_t ctab_cap = 0, htab_cap = 0, tlp_cap = 0;
+    DevBuf<float> ctab, tlp;
+    DevBuf<uint32_t> htab;
     // workspace of a chunk
-    int32_t *inp = nullptr, *tgt = nullptr, *join = nullptr;
-    size_t inp_cap = 0, tgt_cap = 0, join_cap = 0;
-    float *c = nullptr, *g1 = nullptr, *mm = nullptr, *z = nullptr, *hwin = nullptr, *terms = nullptr, *lp = nullptr, *zout = nullptr;
-    uint32_t* hs = nullptr;              // the h operand of product 1: split rows or fp32 rows, 4 bytes per unit either way
-    size_t c_cap = 0, g1_cap = 0, mm_cap = 0, z_cap = 0, hwin_cap = 0, terms_cap = 0, lp_cap = 0, zout_cap = 0, hs_cap = 0;
+    DevBuf<int32_t> inp, tgt, join;
+    DevBuf<float> c, g1, mm, z, hwin, terms, lp, zout;
+    DevBuf<uint32_t> hs;                 // the h operand of product 1: split rows or fp32 rows, 4 bytes per unit either way
     size_t win_rows = 0;                 // rows per window slot of hwin
-    double* score = nullptr;  size_t score_cap = 0;
+    DevBuf<double> score;
 };
 
 namespace pgmi {
@@ -62,58 +59,47 @@ static int64_t ur_count(const pgmi_unirep_config* c) {
 }
 
 static int ur_build(pgmi_unirep* m, const float* w, int64_t n_weights) {
-    std::vector<void*>& pool = m->pm.allocs;
     const size_t H = m->H, Hp = m->Hp;
-    const float* p = w;
-    auto take = [&](size_t n) { p += n; return p - n; };
-    int rc = PGMI_OK;
-    auto up = [&](float** dst, const std::vector<float>& v) { if (!rc) rc = dev_upload(pool, dst, v.data(), v.size()); };
-    auto lin = [&](float** w32, W16* w16, const std::vector<float>& v, size_t K) {
-        if (rc) return;
-        if (m->cfg.precision == PGMI_PREC_FP32) rc = dev_upload(pool, w32, v.data(), v.size());
-        else rc = make_w16(pool, v.data(), v.size(), K, m->cfg.precision, m->pm.stream, w16);
-    };
+    BlobCursor c(&m->pm, w, n_weights);
     {   // Tmx [26][H] -> [26][Hp]
-        const float* s = take(UR_TOKENS * H);
+        const float* s = c.take(UR_TOKENS * H);
         std::vector<float> t(UR_TOKENS * Hp, 0.0f);
         for (size_t a = 0; a < UR_TOKENS; ++a) memcpy(&t[a * Hp], s + a * H, H * sizeof(float));
-        up(&m->Tmx, t);
+        c.upload(&m->Tmx, t);
     }
     {   // Tx [26][4 H] -> [26][4][Hp]
-        const float* s = take(UR_TOKENS * 4 * H);
+        const float* s = c.take(UR_TOKENS * 4 * H);
         std::vector<float> t(UR_TOKENS * 4 * Hp, 0.0f);
         for (size_t a = 0; a < UR_TOKENS; ++a)
             for (size_t g = 0; g < 4; ++g) memcpy(&t[(a * 4 + g) * Hp], s + a * 4 * H + g * H, H * sizeof(float));
-        up(&m->Tx, t);
+        c.upload(&m->Tx, t);
     }
     {   // wmh [H in][H out] -> [Hp out][Hp in]
-        const float* s = take(H * H);
+        const float* s = c.take(H * H);
         std::vector<float> t(Hp * Hp, 0.0f);
         for (size_t k = 0; k < H; ++k)
             for (size_t n = 0; n < H; ++n) t[n * Hp + k] = s[k * H + n];
-        lin(&m->wmh32, &m->wmh16, t, Hp);
+        c.linear(&m->wmh32, &m->wmh16, t, Hp);
     }
     {   // wh [H in][4 H out] -> [4][Hp out][Hp in]
-        const float* s = take(H * 4 * H);
+        const float* s = c.take(H * 4 * H);
         std::vector<float> t(4 * Hp * Hp, 0.0f);
         for (size_t k = 0; k < H; ++k)
             for (size_t g = 0; g < 4; ++g)
                 for (size_t n = 0; n < H; ++n) t[(g * Hp + n) * Hp + k] = s[k * 4 * H + g * H + n];
-        lin(&m->wh32, &m->wh16, t, Hp);
+        c.linear(&m->wh32, &m->wh16, t, Hp);
     }
     {   // Dense kernel [H][25] -> [25][Hp]; bias [25]
-        const float* s = take(H * UR_OUT);
+        const float* s = c.take(H * UR_OUT);
         std::vector<float> t(UR_OUT * Hp, 0.0f);
         for (size_t k = 0; k < H; ++k)
             for (size_t v = 0; v < UR_OUT; ++v) t[v * Hp + k] = s[k * UR_OUT + v];
-        up(&m->Wd, t);
-        const float* b = take(UR_OUT);
-        up(&m->bd, std::vector<float>(b, b + UR_OUT));
+        c.upload(&m->Wd, t);
+        c.upload(&m->bd, UR_OUT);
     }
-    if (!rc && p != w + n_weights) { set_error("internal: UniRep blob walk mismatch"); rc = PGMI_EINVAL; }
+    int rc = c.finish();
     // entry 0 of the state table: the zero state (unirep.py:76-79), also what a handle without a target starts from
-    if (!rc) rc = ensure_cap(&m->pm, &m->ctab, &m->ctab_cap, Hp);
-    if (!rc) rc = ensure_cap(&m->pm, &m->htab, &m->htab_cap, Hp);
+    if (!rc) rc = reserve_all(&m->pm, m->ctab, Hp, m->htab, Hp);
     if (!rc) {
         PGMI_HIP(hipMemset(m->ctab, 0, Hp * 4));
         PGMI_HIP(hipMemset(m->htab, 0, Hp * 4));
@@ -130,22 +116,14 @@ static int ur_rows_cap(const pgmi_unirep* m) {
 static int ur_workspace(pgmi_unirep* m, size_t R, size_t Lc, bool want_lp, bool want_z) {
     pgmi_model* pm = &m->pm;
     const size_t Hp = m->Hp;
-    int rc = ensure_cap(pm, &m->inp, &m->inp_cap, R * Lc);
-    if (!rc) rc = ensure_cap(pm, &m->tgt, &m->tgt_cap, R * Lc);
-    if (!rc) rc = ensure_cap(pm, &m->join, &m->join_cap, R);
-    if (!rc) rc = ensure_cap(pm, &m->c, &m->c_cap, R * Hp);
-    if (!rc) rc = ensure_cap(pm, &m->hs, &m->hs_cap, R * Hp);
-    if (!rc) rc = ensure_cap(pm, &m->g1, &m->g1_cap, R * Hp);
-    if (!rc) rc = ensure_cap(pm, &m->mm, &m->mm_cap, R * Hp);
-    if (!rc) rc = ensure_cap(pm, &m->z, &m->z_cap, R * 4 * Hp);
+    int rc = reserve_all(pm, m->inp, R * Lc, m->tgt, R * Lc, m->join, R, m->c, R * Hp, m->hs, R * Hp, m->g1, R * Hp, m->mm, R * Hp,
+                         m->z, R * 4 * Hp, m->terms, R * Lc, m->score, R);
     if (!rc && R > m->win_rows) {
-        rc = ensure_cap(pm, &m->hwin, &m->hwin_cap, (size_t)UR_WINDOW * R * Hp);
+        rc = m->hwin.reserve(pm, (size_t)UR_WINDOW * R * Hp);
         if (!rc) m->win_rows = R;
     }
-    if (!rc) rc = ensure_cap(pm, &m->terms, &m->terms_cap, R * Lc);
-    if (!rc) rc = ensure_cap(pm, &m->score, &m->score_cap, R);
-    if (!rc && want_lp) rc = ensure_cap(pm, &m->lp, &m->lp_cap, R * Lc * UR_OUT);
-    if (!rc && want_z) rc = ensure_cap(pm, &m->zout, &m->zout_cap, R * 4 * Hp);
+    if (!rc && want_lp) rc = m->lp.reserve(pm, R * Lc * UR_OUT);
+    if (!rc && want_z) rc = m->zout.reserve(pm, R * 4 * Hp);
     return rc;
 }
 
@@ -158,36 +136,26 @@ static int ur_step(pgmi_unirep* m, int rows, const int32_t* tok, int tok_stride,
     int rc;
     {
         ProfScope p(pm, PGMI_K_GEMM_FC1, 2.0 * rows * (double)m->H * m->H, 0);
-        if (f32) rc = launch_gemm_f32(reinterpret_cast<const float*>(m->hs), m->wmh32, nullptr, nullptr, m->g1, rows, Hp, Hp, EPI_NONE, st);
-        else {
-            GemmLaunch g;
-            g.A = reinterpret_cast<const unsigned short*>(m->hs); g.W = m->wmh16.p; g.out_scale = m->wmh16.out_scale;
-            g.out32 = m->g1; g.M = rows; g.N = Hp; g.K = Hp; g.stream = st;
-            rc = launch_gemm16(g);
-        }
+        rc = linear(pm, reinterpret_cast<const float*>(m->hs.p), reinterpret_cast<const unsigned short*>(m->hs.p), m->wmh32, m->wmh16, nullptr, nullptr,
+                    m->g1, nullptr, rows, Hp, Hp, EPI_NONE);
     }
     if (rc) return rc;
     {
         ProfScope p(pm, PGMI_K_LAYERNORM, 0, (double)rows * Hp * 12);
-        launch_mlstm_m(m->g1, m->Tmx, tok, tok_stride, rows, Hp, f32 ? nullptr : reinterpret_cast<unsigned short*>(m->mm),
+        launch_mlstm_m(m->g1, m->Tmx, tok, tok_stride, rows, Hp, f32 ? nullptr : reinterpret_cast<unsigned short*>(m->mm.p),
                        f32 ? m->mm : nullptr, st);
     }
     {
         ProfScope p(pm, PGMI_K_GEMM_FC2, 2.0 * rows * (double)m->H * 4 * m->H, 0);
-        if (f32) rc = launch_gemm_f32(m->mm, m->wh32, nullptr, nullptr, m->z, rows, 4 * Hp, Hp, EPI_NONE, st);
-        else {
-            GemmLaunch g;
-            g.A = reinterpret_cast<const unsigned short*>(m->mm); g.W = m->wh16.p; g.out_scale = m->wh16.out_scale;
-            g.out32 = m->z; g.M = rows; g.N = 4 * Hp; g.K = Hp; g.stream = st;
-            rc = launch_gemm16(g);
-        }
+        rc = linear(pm, m->mm, reinterpret_cast<const unsigned short*>(m->mm.p), m->wh32, m->wh16, nullptr, nullptr, m->z, nullptr, rows, 4 * Hp, Hp,
+                    EPI_NONE);
     }
     if (rc) return rc;
     {
         ProfScope p(pm, PGMI_K_ATTENTION, 0, (double)rows * Hp * 36);
         MlstmGate a;
         a.z = m->z; a.Tx = m->Tx; a.tok = tok; a.tok_stride = tok_stride; a.c = m->c;
-        if (f32) a.h32 = reinterpret_cast<float*>(m->hs); else a.h16 = reinterpret_cast<unsigned short*>(m->hs);
+        if (f32) a.h32 = reinterpret_cast<float*>(m->hs.p); else a.h16 = reinterpret_cast<unsigned short*>(m->hs.p);
         a.hwin = hwin; a.z_out = z_out; a.rows = rows; a.Hp = Hp;
         launch_mlstm_gate(a, st);
     }
@@ -243,9 +211,7 @@ static int ur_chunk(pgmi_unirep* m, const int32_t* inp, const int32_t* tgt, cons
     if (lp_host) PGMI_HIP(hipMemcpyAsync(lp_host, m->lp, nt * UR_OUT * 4, hipMemcpyDeviceToHost, st));
     if (scores) PGMI_HIP(hipMemcpyAsync(scores, m->score, (size_t)n * 8, hipMemcpyDeviceToHost, st));
     // the chunk's host arrays and the workspace are reused by the next chunk: wait for the copies
-    const hipError_t e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { set_error("UniRep step loop failed: %s", hipGetErrorString(e)); return PGMI_EHIP; }
-    return PGMI_OK;
+    return side_sync(pm, PGMI_OK, "UniRep step loop");
 }
 
 static int ur_check_tokens(const int32_t* tok, size_t n) {
@@ -268,23 +234,12 @@ int pgmi_unirep_model_create(const pgmi_unirep_config* cfg, const float* w, int6
     *out = nullptr;
     int rc = ur_check(cfg);
     if (rc) return rc;
-    if (!w || n_weights != ur_count(cfg)) {
-        set_error("UniRep weight blob has %lld elements, config needs %lld", (long long)n_weights, (long long)ur_count(cfg));
-        return PGMI_EINVAL;
-    }
-    for (int64_t i = 0; i < n_weights; ++i)
-        if (!std::isfinite(w[i])) { set_error("UniRep: weight blob element %lld is not finite", (long long)i); return PGMI_EINVAL; }
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) { set_error("no HIP device (libpgmi has no CPU fallback)"); return PGMI_ENODEV; }
-    if (device < 0 || device >= n_dev) { set_error("device %d out of range (%d visible)", device, n_dev); return PGMI_EINVAL; }
-    PGMI_HIP(hipSetDevice(device));
-    gemm_options_from_env();
     pgmi_unirep* m = new pgmi_unirep();
+    rc = side_open(&m->pm, "UniRep", w, n_weights, ur_count(cfg), true, device, cfg->precision, nullptr);
+    if (rc) { delete m; return rc; }
     m->cfg = *cfg;
     m->H = cfg->hidden;
-    m->Hp = (cfg->hidden + 31) / 32 * 32;
-    m->pm.device = device;
-    if (hipStreamCreate(&m->pm.stream) != hipSuccess) { delete m; set_error("hipStreamCreate failed"); return PGMI_EHIP; }
+    m->Hp = roundup32(cfg->hidden);
     rc = ur_build(m, w, n_weights);
     if (rc) { pgmi_unirep_destroy(m); return rc; }
     *out = m;
@@ -310,9 +265,7 @@ int pgmi_unirep_set_target(pgmi_unirep* m, const int32_t* tokens, int L) {
     PGMI_HIP(hipSetDevice(m->pm.device));
     pgmi_model* pm = &m->pm;
     const size_t Hp = m->Hp;
-    rc = ensure_cap(pm, &m->ctab, &m->ctab_cap, (size_t)(L + 1) * Hp);
-    if (!rc) rc = ensure_cap(pm, &m->htab, &m->htab_cap, (size_t)(L + 1) * Hp);
-    if (!rc) rc = ensure_cap(pm, &m->tlp, &m->tlp_cap, (size_t)L * UR_OUT);
+    rc = reserve_all(pm, m->ctab, (size_t)(L + 1) * Hp, m->htab, (size_t)(L + 1) * Hp, m->tlp, (size_t)L * UR_OUT);
     if (rc) return rc;
     PGMI_HIP(hipMemsetAsync(m->ctab, 0, Hp * 4, pm->stream));
     PGMI_HIP(hipMemsetAsync(m->htab, 0, Hp * 4, pm->stream));
@@ -406,7 +359,7 @@ int pgmi_op_mlstm_step(pgmi_unirep* m, const float* h_prev, const float* c_prev,
     if (m->cfg.precision == PGMI_PREC_FP32) PGMI_HIP(hipMemcpyAsync(m->hs, hp.data(), R * Hp * 4, hipMemcpyHostToDevice, st));
     else {   // the operand form the gate kernel writes between steps: split rows
         PGMI_HIP(hipMemcpyAsync(m->g1, hp.data(), R * Hp * 4, hipMemcpyHostToDevice, st));
-        launch_split16(m->g1, (int64_t)(R * Hp), 1.0f, 2, (int)Hp, reinterpret_cast<unsigned short*>(m->hs), st);
+        launch_split16(m->g1, (int64_t)(R * Hp), 1.0f, 2, (int)Hp, reinterpret_cast<unsigned short*>(m->hs.p), st);
     }
     rc = ur_step(m, rows, m->inp, 1, m->hwin, m->zout);
     if (rc) return rc;

@@ -30,6 +30,9 @@
 //                        rows / token log-probs / sequence log-likelihoods, the convolution's and the row kernel's op entries
 //   api_protssn.hip      ProtSSN: its own handle (pgmi_protssn), blob walk, the graph of one structure, the EGNN forward in edge chunks
 //                        (egnn.hip around the existing GEMMs), the ESM2 residue rows that feed it, the message op entry
+//   side handles         what the handles outside pgmi_model (pgmi_eve, pgmi_mpnn, pgmi_unirep, pgmi_s2f, pgmi_carp, pgmi_protssn; pgmi_s3f
+//                        holds two pgmi_s2f) share, in api_model.hip and below: side_open (blob, device and stream of a create),
+//                        BlobCursor, linear(), DevBuf / reserve_all (grow-only workspace), side_sync, overflow_error, side_release
 //   api_msa.hip          MSA Transformer weights and forward (tied row attention, column attention)
 //   api_host.hip         host-only entries: mutant parser, table -> scores, optimal window
 //   api_ops.hip          single-op and timing entries for the numerics tests and the A/B scripts
@@ -306,9 +309,38 @@ int ensure_cap(pgmi_model* m, T** p, size_t* cap, size_t need) {
     return PGMI_OK;
 }
 
+template <typename T>
+constexpr T roundup32(T v) { return (v + 31) / 32 * 32; }
+
+// A grow-only device buffer of a side handle, owned by the pool of the model it is reserved on; it reads as its pointer.
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+    int reserve(pgmi_model* m, size_t n) { return ensure_cap(m, &p, &cap, n); }
+    operator T*() const { return p; }
+};
+
+// reserve_all(m, buf, n, buf, n, ...): every buffer to at least its n elements; the first failure ends it
+inline int reserve_all(pgmi_model*) { return PGMI_OK; }
+template <typename T, typename... Rest>
+int reserve_all(pgmi_model* m, DevBuf<T>& b, size_t n, Rest&&... rest) {
+    const int rc = b.reserve(m, n);
+    return rc ? rc : reserve_all(m, rest...);
+}
+
 // ---- shared helpers (api_model.hip unless noted) ----
 int prof_drain(pgmi_model* m);
-void side_release(pgmi_model* pm, bool own_stream);   // teardown of a side handle's embedded model (pgmi_s2f, pgmi_carp, ...): device, sync, events, pool, stream
+// The embedded model of a side handle (pgmi_s2f, pgmi_carp, ...).  side_open: the refusals of a create after its config check -- the
+// blob against the `want` elements the config needs, its values when scan_finite, the device -- then the GEMM test hooks, pm's device
+// and precision and its stream (`lend` when given, else a new one).  Nothing is held when it fails.  side_sync: the end of a call --
+// waits for the stream; rc unless it is PGMI_OK and a launch or the stream failed ("<what> failed: ...").  overflow_error: a head
+// saw a non-finite log-probability.  side_release: teardown -- device, sync, events, pool, and the stream if it is the handle's.
+int side_open(pgmi_model* pm, const char* name, const float* w, int64_t n_weights, int64_t want, bool scan_finite, int device, int precision,
+              hipStream_t lend);
+int side_sync(pgmi_model* pm, int rc, const char* what);
+int overflow_error(int precision);
+void side_release(pgmi_model* pm, bool own_stream);
 int check_cfg(const pgmi_config* c);
 int check_tokens(const int32_t* tokens, int B, int T, int n_ids = PGMI_VOCAB);
 int check_vocab(const int32_t* tokens, int B, int T, int V);
@@ -421,6 +453,7 @@ struct BlobCursor {
     const float* take(size_t n) { p += n; return p - n; }
     void upload(float** dst, const float* host, size_t n) { if (!rc) rc = dev_upload(m->allocs, dst, host, n); }
     void upload(float** dst, size_t n) { upload(dst, take(n), n); }
+    void upload(float** dst, const std::vector<float>& host) { upload(dst, host.data(), host.size()); }
     void w16(W16* dst, const float* host, size_t n, size_t K) { if (!rc) rc = make_w16(m->allocs, host, n, K, m->cfg.precision, m->stream, dst); }
     void w16(W16* dst, size_t n, size_t K) { w16(dst, take(n), n, K); }
     // a Linear weight [n / K, K]: fp32 in precision fp32, 16-bit planes otherwise
@@ -428,6 +461,7 @@ struct BlobCursor {
         if (m->cfg.precision == PGMI_PREC_FP32) upload(w32, host, n); else w16(w16_, host, n, K);
     }
     void linear(float** w32, W16* w16_, size_t n, size_t K) { linear(w32, w16_, take(n), n, K); }
+    void linear(float** w32, W16* w16_, const std::vector<float>& host, size_t K) { linear(w32, w16_, host.data(), host.size(), K); }
     int finish() {
         if (!rc && p != end) { set_error("internal: blob walk mismatch"); rc = PGMI_EINVAL; }
         return rc;
@@ -504,7 +538,7 @@ inline int upload_plan(pgmi_model* m, SegPlan& p, int slot) {
 }
 
 // Sequences of T tokens per workspace chunk: B * roundup(T, 32) <= max_rows, at least one.
-inline int rows_per_chunk(const pgmi_model* m, int T) { return std::max(1, m->max_rows / ((T + 31) / 32 * 32)); }
+inline int rows_per_chunk(const pgmi_model* m, int T) { return std::max(1, m->max_rows / roundup32(T)); }
 
 // Drives a fixed-T batch through the workspace: fn(b0, bc) copies chunk [b0, b0 + bc) in, runs it and copies its results out
 // (asynchronously); the stream is synchronized after every chunk, so host buffers of the chunk outlive their copies.

@@ -24,10 +24,8 @@ struct S2fLayer {
     float *Wji = nullptr, *We = nullptr, *b0 = nullptr, *Wnt = nullptr, *whji = nullptr, *whe = nullptr;
     S2fGvp m0, m1, m2, f0, f1;
     float *n0w, *n0b, *n1w, *n1b;
-    float* Es = nullptr;      // per structure: We e_s + b [E][256]
-    size_t Es_cap = 0;
+    DevBuf<float> Es;         // per structure: We e_s + b [E][256]
 };
-struct S2fBuf { float* p = nullptr; size_t cap = 0; };
 struct S2fSetHost { std::vector<int32_t> toks, ridx; };   // host scratch of s2f_fill_esm: a chunk's tokens and residue row indices
 
 }  // namespace pgmi
@@ -49,13 +47,11 @@ struct pgmi_s2f {
     int L = 0, E = 0;
     std::vector<int32_t> h_src, h_dst, h_off;
     std::vector<float> h_es, h_ev;
-    int32_t *src = nullptr, *off = nullptr;
-    size_t src_cap = 0, off_cap = 0;
-    pgmi::S2fBuf es, ev, plddt;
+    pgmi::DevBuf<int32_t> src, off;
+    pgmi::DevBuf<float> es, ev, plddt;
     // workspace of a chunk
-    pgmi::S2fBuf feat, h0, s, v, s1, v1, P, VT, pre, gate, A, vhA, vhB, mV, seq, lp;
-    int32_t *ridx = nullptr, *toks = nullptr, *cols = nullptr;
-    size_t ridx_cap = 0, toks_cap = 0, cols_cap = 0;
+    pgmi::DevBuf<float> feat, h0, s, v, s1, v1, P, VT, pre, gate, A, vhA, vhB, mV, seq, lp;
+    pgmi::DevBuf<int32_t> ridx, toks, cols;
 };
 
 namespace pgmi {
@@ -65,7 +61,6 @@ int64_t s2f_count(const pgmi_s2f_config* c, bool surface);     // surface: witho
 // a handle on `device`; esm (nullable) lends its stream, else stream_of (nullable) does, else the handle creates one
 int s2f_new(const pgmi_s2f_config* cfg, const float* w, int64_t n_weights, pgmi_model* esm, pgmi_s2f* stream_of, int device, int fixed_degree,
             pgmi_s2f** out);
-int s2f_buf(pgmi_s2f* m, S2fBuf* b, size_t n);
 int s2f_structure(pgmi_s2f* m, const float* pos, const float* plddt, int L);
 int s2f_edge_tables(pgmi_s2f* m, size_t E);                     // every layer's Es [E][256] from m->es; both structure passes end in it
 long long s2f_row_cap();                                        // pgmi_set_option("s2f_max_rows"), or the default

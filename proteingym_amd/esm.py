@@ -295,20 +295,9 @@ class EsmModel(_lib.ModelHandle):
         return out
 
     # -- profiling ------------------------------------------------------------------------------
-    def profile_enable(self, on=True):
-        _lib.check(_lib.load().pgmi_profile_enable(self._h, int(on)))
-
-    def profile_reset(self):
-        _lib.check(_lib.load().pgmi_profile_reset(self._h))
-
-    def profile(self) -> dict:
-        lib = _lib.load()
-        out = {}
-        for k, name in enumerate(_lib.K_NAMES):
-            ms, n, fl, by = C.c_double(), C.c_int64(), C.c_double(), C.c_double()
-            _lib.check(lib.pgmi_profile_get(self._h, k, C.byref(ms), C.byref(n), C.byref(fl), C.byref(by)))
-            out[name] = dict(ms=ms.value, launches=n.value, flops=fl.value, bytes=by.value)
-        return out
+    profile_enable = _lib._ProfileView.profile_enable
+    profile_reset = _lib._ProfileView.profile_reset
+    profile = _lib._ProfileView.profile
 
 
 class Assay:

@@ -190,11 +190,12 @@ def _u8p(a):
     return a.ctypes.data_as(C.POINTER(C.c_uint8))
 
 
-class EveModel:
+class EveModel(_lib.SideHandle):
     """A device-resident EVE / DeepSequence model."""
 
+    PREFIX = "eve"
+
     def __init__(self, dims: dict, blob: np.ndarray, device: int = 0, precision: int = _lib.PREC_FP32):
-        lib = _lib.load()
         self.dims = dict(dims)
         d = self.dims
         c = EveConfig(abi_version=_lib.ABI_VERSION, seq_len=d["seq_len"], alphabet=20, z_dim=d["z_dim"], n_enc=len(d["enc_sizes"]),
@@ -207,30 +208,8 @@ class EveModel:
             c.enc_sizes[i] = v
         for i, v in enumerate(d["dec_sizes"]):
             c.dec_sizes[i] = v
-        w = _lib.as_f32(blob)
-        n = lib.pgmi_eve_weight_count(C.byref(c))
-        if n < 0:
-            raise _lib.PgmiError(f"libpgmi refuses the configuration: {lib.pgmi_last_error().decode(errors='replace')}", code=_lib.EINVAL)
-        if w.size != n:
-            raise _lib.PgmiError(f"weight blob has {w.size} elements, config needs {n}")
-        h = C.c_void_p()
-        _lib.check(lib.pgmi_eve_create(C.byref(c), _lib.ptr(w, _lib._f32p), w.size, device, C.byref(h)))
-        self._h = h
+        self._create(c, blob, device)
         self.L, self.z = d["seq_len"], d["z_dim"]
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.load().pgmi_eve_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def profile_handle(self):
-        return C.c_void_p(_lib.load().pgmi_eve_profile_model(self._h))
 
     def _res(self, residues):
         r = np.ascontiguousarray(residues, dtype=np.uint8)

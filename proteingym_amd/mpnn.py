@@ -212,39 +212,18 @@ def encode_sequences(seqs: Sequence[str], L: int) -> np.ndarray:
 
 
 # ---- the model -------------------------------------------------------------------------------------------------------------------
-class MpnnModel:
+class MpnnModel(_lib.SideHandle):
     """A device-resident ProteinMPNN."""
 
+    PREFIX = "mpnn"
+
     def __init__(self, blob: np.ndarray, num_edges: int = 48, device: int = 0, enc_layers: int = 3, dec_layers: int = 3):
-        lib = _lib.load()
         c = MpnnConfig(abi_version=_lib.ABI_VERSION, hidden=HIDDEN, num_edges=num_edges, enc_layers=enc_layers, dec_layers=dec_layers,
                        precision=_lib.PREC_FP32)
-        w = _lib.as_f32(blob)
-        n = lib.pgmi_mpnn_weight_count(C.byref(c))
-        if n < 0:
-            raise _lib.PgmiError(f"libpgmi refuses the configuration: {lib.pgmi_last_error().decode(errors='replace')}", code=_lib.EINVAL)
-        if w.size != n:
-            raise _lib.PgmiError(f"weight blob has {w.size} elements, config needs {n}")
-        h = C.c_void_p()
-        _lib.check(lib.pgmi_mpnn_create(C.byref(c), _lib.ptr(w, _lib._f32p), w.size, device, C.byref(h)))
-        self._h = h
+        self._create(c, blob, device)
         self.num_edges = num_edges
         self.L = self.K = 0
         self.mask = self.chain_M = self.chain_M_pos = None
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.load().pgmi_mpnn_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def profile_handle(self):
-        return C.c_void_p(_lib.load().pgmi_mpnn_profile_model(self._h))
 
     def set_structure(self, X, mask, residue_idx, chain_encoding, chain_M=None, chain_M_pos=None):
         """Graph, edge features, encoder and the mutant-independent decoder tables of one backbone; chain_M / chain_M_pos are kept

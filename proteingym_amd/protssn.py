@@ -431,38 +431,20 @@ def check_yaml(cfg: dict) -> int:
 
 
 # -- model -------------------------------------------------------------------------------------------------------------------
-class ProtSSN:
+class ProtSSN(_lib.SideHandle):
     """One device-resident checkpoint (EGNN + head)."""
+
+    PREFIX, NAME = "protssn", "ProtSSN "
 
     def __init__(self, blob: np.ndarray, node_in: int = NODE_IN, hidden: int = 512, layers: int = LAYERS, device: int = 0,
                  precision: str = "f16x3", edge_chunk: int = 0):
-        lib = _lib.load()
         if precision not in ("f16x3", "fp32"):
             raise ValueError(f"precision {precision!r}: ProtSSN runs in f16x3 or fp32")
         self.D, self.h = node_in, hidden
         self.config = ProtssnConfig(abi_version=_lib.ABI_VERSION, node_in=node_in, hidden=hidden, layers=layers, edge_attr_dim=EDGE_ATTR_DIM,
                                     precision=_lib.PRECISIONS[precision], edge_chunk=edge_chunk)
-        w = _lib.as_f32(blob)
-        n = lib.pgmi_protssn_weight_count(C.byref(self.config))
-        if n < 0:
-            _lib.check(_lib.EINVAL)
-        if w.size != n:
-            raise _lib.PgmiError(f"ProtSSN weight blob has {w.size} elements, config needs {n}")
-        h = C.c_void_p()
-        _lib.check(lib.pgmi_protssn_create(C.byref(self.config), _lib.ptr(w, _lib._f32p), w.size, device, C.byref(h)))
-        self._h = h
+        self._create(self.config, blob, device)
         self.L = 0
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.load().pgmi_protssn_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_graph(self, pos, centre, nb, edge_attr):
         p, c, n, ea = _lib.as_f32(pos), _lib.as_i32(centre), _lib.as_i32(nb), _lib.as_f32(edge_attr)
@@ -481,17 +463,6 @@ class ProtSSN:
         hid = np.empty((self.L, self.D), np.float32) if want_hidden else None
         _lib.check(_lib.load().pgmi_protssn_forward(self._h, _lib.ptr(x, _lib._f32p), _lib.ptr(lp, _lib._f32p), _lib.ptr(hid, _lib._f32p)))
         return (lp, hid) if want_hidden else lp
-
-    def profile_view(self):
-        view = _ProfileView()
-        view._h = C.c_void_p(_lib.load().pgmi_protssn_profile_model(self._h))
-        return view
-
-
-class _ProfileView:
-    profile_enable = pesm.EsmModel.profile_enable
-    profile_reset = pesm.EsmModel.profile_reset
-    profile = pesm.EsmModel.profile
 
 
 def from_state_dict(sd, node_in: int = NODE_IN, hidden: int = 512, layers: int = LAYERS, **kw) -> ProtSSN:

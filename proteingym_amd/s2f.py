@@ -335,40 +335,21 @@ def check_yaml(cfg: dict, node_in: int = 1280, esm_name: Optional[str] = "ESM-2-
 
 
 # -- model -------------------------------------------------------------------------------------------------------------------
-class S2F:
+class S2F(_lib.SideHandle):
     """Device-resident S2F: an ESM2 model (nullable: GNN only) plus the GVP blob."""
+
+    PREFIX, NAME = "s2f", "GVP "
 
     def __init__(self, gvp_blob: np.ndarray, esm: Optional[pesm.EsmModel] = None, node_in: Optional[int] = None, layers: int = LAYERS,
                  device: int = 0, max_neighbors: int = MAX_NEIGHBORS, radius: float = RADIUS,
                  plddt_threshold: Optional[float] = PLDDT_THRESHOLD):
-        lib = _lib.load()
         self.esm = esm
         self.D = int(esm.cfg["embed_dim"] if esm is not None else node_in)
         # task.py: `if self.plddt_threshold:` -- no threshold, no fallback: every pLDDT is above -inf
         thr = float(plddt_threshold) if plddt_threshold else -3.0e38
         self.config = make_config(self.D, layers, max_neighbors, radius, thr)
-        w = _lib.as_f32(gvp_blob)
-        n = lib.pgmi_s2f_weight_count(C.byref(self.config))
-        if n < 0:
-            _lib.check(_lib.EINVAL)
-        if w.size != n:
-            raise _lib.PgmiError(f"GVP weight blob has {w.size} elements, config needs {n}")
-        h = C.c_void_p()
-        _lib.check(lib.pgmi_s2f_create(C.byref(self.config), _lib.ptr(w, _lib._f32p), w.size, esm._h if esm is not None else None, device,
-                                       C.byref(h)))
-        self._h = h
+        self._create(self.config, gvp_blob, device, esm._h if esm is not None else None)
         self.L = 0
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.load().pgmi_s2f_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_structure(self, pos, plddt):
         p, q = _lib.as_f32(pos), _lib.as_f32(plddt)
@@ -412,12 +393,6 @@ class S2F:
                                                      _lib.ptr(out, _lib._f32p), _lib.ptr(full, _lib._f32p)))
         return (out, full) if want_full else out
 
-    def profile_view(self):
-        """The GNN's profiling view as an object with EsmModel's profile methods."""
-        view = _ProfileView()
-        view._h = C.c_void_p(_lib.load().pgmi_s2f_profile_model(self._h))
-        return view
-
     def score_assay(self, dms_id: str, target_seq: str, rows, pos, plddt, s_start: int, s_end: int) -> np.ndarray:
         """The sorted mutants (sort_mutants) of one assay against its structure: float32 [n]."""
         windows, csr, where = position_sets(rows, dms_id, len(target_seq))
@@ -427,12 +402,6 @@ class S2F:
             self.set_structure(p, q)
             tables.append(self.set_logprobs(tokenize(target_seq[start:end]), set_off, set_pos, want_full=True)[1])
         return score_rows(rows, where, tables, windows)
-
-
-class _ProfileView:
-    profile_enable = pesm.EsmModel.profile_enable
-    profile_reset = pesm.EsmModel.profile_reset
-    profile = pesm.EsmModel.profile
 
 
 def from_state_dict(sd, esm_cfg: dict, layers: int = LAYERS, device: int = 0, precision: str = "f16x3", max_rows: int = 0, **kw) -> S2F:

@@ -191,40 +191,21 @@ def check_yaml(cfg: dict, node_in: int = 1280, esm_name: Optional[str] = "ESM-2-
 
 
 # -- model -------------------------------------------------------------------------------------------------------------------
-class S3F:
+class S3F(_lib.SideHandle):
     """Device-resident S3F: an ESM2 model (nullable: the two GNNs only) plus the S3F blob."""
+
+    PREFIX, NAME = "s3f", "S3F "
 
     def __init__(self, blob: np.ndarray, esm: Optional[pesm.EsmModel] = None, node_in: Optional[int] = None, layers: int = s2f.LAYERS,
                  device: int = 0, max_neighbors: int = s2f.MAX_NEIGHBORS, radius: float = s2f.RADIUS,
                  plddt_threshold: Optional[float] = s2f.PLDDT_THRESHOLD):
-        lib = _lib.load()
         self.esm = esm
         self.D = int(esm.cfg["embed_dim"] if esm is not None else node_in)
         thr = float(plddt_threshold) if plddt_threshold else -3.0e38
         self.config = S3fConfig(s2f=s2f.make_config(self.D, layers, max_neighbors, radius, thr), surf_feat=SURF_IN[0],
                                 surf_res_neighbors=SURF_RES_NEIGHBORS, surf_neighbors=SURF_NEIGHBORS)
-        w = _lib.as_f32(blob)
-        n = lib.pgmi_s3f_weight_count(C.byref(self.config))
-        if n < 0:
-            _lib.check(_lib.EINVAL)
-        if w.size != n:
-            raise _lib.PgmiError(f"S3F weight blob has {w.size} elements, config needs {n}")
-        h = C.c_void_p()
-        _lib.check(lib.pgmi_s3f_create(C.byref(self.config), _lib.ptr(w, _lib._f32p), w.size, esm._h if esm is not None else None, device,
-                                       C.byref(h)))
-        self._h = h
+        self._create(self.config, blob, device, esm._h if esm is not None else None)
         self.L = self.Ns = 0
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.load().pgmi_s3f_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_structure(self, pos, plddt, surf_pos, surf_feat):
         p, q, sp, sf = _lib.as_f32(pos), _lib.as_f32(plddt), _lib.as_f32(surf_pos), _lib.as_f32(surf_feat)
@@ -282,9 +263,7 @@ class S3F:
 
     def profile_view(self, part: int):
         """The profiling view of the residue half (0) or the surface half (1), with EsmModel's profile methods."""
-        view = s2f._ProfileView()
-        view._h = C.c_void_p(_lib.load().pgmi_s3f_profile_model(self._h, part))
-        return view
+        return super().profile_view(part)
 
     def score_assay(self, dms_id: str, target_seq: str, rows, pos, plddt, s_start: int, s_end: int, surface, batch_size: int = 1) -> np.ndarray:
         """The sorted mutants (s2f.sort_mutants) of one assay against its structure and surface (load_surface): float32 [n].  One

@@ -183,43 +183,22 @@ def plan(token_rows: Sequence[np.ndarray], target: Optional[np.ndarray] = None, 
 
 
 # ---- the model ---------------------------------------------------------------------------------------------------------------------
-class UniRepModel:
+class UniRepModel(_lib.SideHandle):
     """A device-resident UniRep."""
 
+    PREFIX, CREATE = "unirep", "pgmi_unirep_model_create"
+
     def __init__(self, arrays: Dict[str, np.ndarray], device: int = 0, precision: str = "f16x3", max_rows: int = 0):
-        lib = _lib.load()
         if precision not in _lib.PRECISIONS:
             raise _lib.PgmiError(f"unknown precision {precision!r}")
         check_arrays(arrays)
         self.H = int(arrays["wmh"].shape[0])
         self.Hp = (self.H + 31) // 32 * 32
         c = UniRepConfig(abi_version=_lib.ABI_VERSION, hidden=self.H, vocab=VOCAB, precision=_lib.PRECISIONS[precision], max_rows=max_rows)
-        n = lib.pgmi_unirep_weight_count(C.byref(c))
-        if n < 0:
-            raise _lib.PgmiError(f"libpgmi refuses the configuration: {lib.pgmi_last_error().decode(errors='replace')}", code=_lib.EINVAL)
-        w = _lib.as_f32(blob_from_arrays(arrays))
-        if w.size != n:
-            raise _lib.PgmiError(f"weight blob has {w.size} elements, config needs {n}")
-        h = C.c_void_p()
-        _lib.check(lib.pgmi_unirep_model_create(C.byref(c), _lib.ptr(w, _lib._f32p), w.size, device, C.byref(h)))
-        self._h = h
+        self._create(c, blob_from_arrays(arrays), device)
         self.max_rows = max_rows or 8192
         self.target: Optional[np.ndarray] = None
         self.last_row_steps = 0
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.load().pgmi_unirep_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def profile_handle(self):
-        return C.c_void_p(_lib.load().pgmi_unirep_profile_model(self._h))
 
     def set_target(self, seq: Optional[str]):
         """Runs the target sequence once; later ``nll`` calls start every sequence from the state stored at its join step."""
