@@ -304,40 +304,33 @@ int pgmi_op_dilated_conv(int device, int precision, const float* x, const float*
         if (seg_off[s + 1] <= seg_off[s]) { set_error("dilated conv op: segment %d is empty or out of order", s); return PGMI_EINVAL; }
     const size_t M = (size_t)seg_off[n_seg], K = (size_t)taps * C;
     if (M > (1u << 20)) { set_error("dilated conv op: %zu rows", M); return PGMI_EINVAL; }
-    if (pgmi_device_count() <= 0) { set_error("no HIP device visible"); return PGMI_ENODEV; }
-    PGMI_HIP(hipSetDevice(device));
-    std::vector<void*> pool;
-    auto cleanup = [&]() { for (void* p : pool) hipFree(p); };
-    float *dx = nullptr, *dw = nullptr, *db = nullptr, *dy = nullptr, *col = nullptr;
-    int32_t* dseg = nullptr;
-    unsigned short* x16 = nullptr;
-    W16 w16;
-    int rc = 0;
-    if ((rc = dev_upload(pool, &dx, x, M * C)) || (rc = dev_upload(pool, &db, bias, (size_t)C)) ||
-        (rc = dev_upload(pool, &dseg, seg_off, (size_t)n_seg + 1)) || (rc = dev_alloc(pool, &dy, M * C))) { cleanup(); return rc; }
-    if (precision == PGMI_PREC_FP32) {
-        if ((rc = dev_upload(pool, &dw, W, (size_t)C * K)) || (rc = dev_alloc(pool, &col, M * K))) { cleanup(); return rc; }
-        rc = launch_dilated_conv32(dx, dw, db, dseg, n_seg, (int64_t)M, C, taps, dilation, col, dy, nullptr);
+    OpScope s("dilated conv op", device);
+    const bool f32 = precision == PGMI_PREC_FP32;
+    float* dx = s.up(x, M * C);
+    float* db = s.up(bias, (size_t)C);
+    int32_t* dseg = s.up(seg_off, (size_t)n_seg + 1);
+    float* dy = s.alloc<float>(M * C);
+    float* dw = f32 ? s.up(W, (size_t)C * K) : nullptr;
+    float* col = f32 ? s.alloc<float>(M * K) : nullptr;
+    const W16 w16 = f32 ? W16() : s.w16(W, (size_t)C * K, K, precision);
+    unsigned short* x16 = f32 ? nullptr : s.alloc<unsigned short>(M * C * 2);
+    if (s.rc) return s.rc;
+    if (f32) {
+        s.rc = launch_dilated_conv32(dx, dw, db, dseg, n_seg, (int64_t)M, C, taps, dilation, col, dy, nullptr);
     } else {
-        if ((rc = make_w16(pool, W, (size_t)C * K, K, precision, nullptr, &w16)) || (rc = dev_alloc(pool, &x16, M * C * 2))) { cleanup(); return rc; }
         launch_split16(dx, (int64_t)(M * C), 1.0f, 2, C, x16, nullptr);
-        rc = launch_dilated_conv16(x16, w16.p, w16.out_scale, db, dseg, n_seg, (int64_t)M, C, taps, dilation, dy, nullptr);
+        s.rc = launch_dilated_conv16(x16, w16.p, w16.out_scale, db, dseg, n_seg, (int64_t)M, C, taps, dilation, dy, nullptr);
     }
-    hipError_t e = hipDeviceSynchronize();
-    if (!rc && e == hipSuccess) e = hipMemcpy(out, dy, M * C * 4, hipMemcpyDeviceToHost);
-    cleanup();
-    if (rc) return rc;
-    if (e != hipSuccess) { set_error("dilated conv op failed: %s", hipGetErrorString(e)); return PGMI_EHIP; }
-    return PGMI_OK;
+    s.sync();
+    s.down(out, dy, M * C);
+    return s.rc;
 }
 
 int pgmi_bench_dilated_conv(int device, int M, int n_seg, int C, int taps, int dilation, int iters, double* ms_per_launch) {
     if (!ms_per_launch || M < 1 || n_seg < 1 || M % n_seg || iters < 1 || C < 32 || C % 32 || C > 8192 || taps < 1 || taps > 15 || !(taps & 1) ||
         dilation < 1) { set_error("bad argument"); return PGMI_EINVAL; }
-    if (pgmi_device_count() <= 0) { set_error("no HIP device visible"); return PGMI_ENODEV; }
-    PGMI_HIP(hipSetDevice(device));
-    std::vector<void*> pool;
-    auto cleanup = [&]() { for (void* p : pool) hipFree(p); };
+    OpScope s("dilated conv bench", device);
+    if (s.rc) return s.rc;
     const size_t n = (size_t)M * C, K = (size_t)taps * C, blk = std::min(n, (size_t)1 << 22);
     // seeded values of the magnitudes the block sees (GELU outputs, weights ~ 1 / sqrt K); x repeats a 4 M-element block
     std::vector<float> hx(blk), hw((size_t)C * K), hb(C, 0.01f);
@@ -346,77 +339,40 @@ int pgmi_bench_dilated_conv(int device, int M, int n_seg, int C, int taps, int d
     auto rnd = [&]() { st = st * 1664525u + 1013904223u; return (float)(int32_t)st * (1.0f / 2147483648.0f); };
     for (float& v : hx) v = 1.5f * rnd();
     for (float& v : hw) v = rnd() * 1.7f / sqrtf((float)K);
-    for (int s = 0; s <= n_seg; ++s) seg[s] = s * (M / n_seg);
-    float *dx = nullptr, *db = nullptr, *dy = nullptr;
-    int32_t* dseg = nullptr;
-    unsigned short* x16 = nullptr;
-    W16 w16;
-    int rc = 0;
-    if ((rc = dev_alloc(pool, &dx, n)) || (rc = dev_upload(pool, &db, hb.data(), hb.size())) || (rc = dev_upload(pool, &dseg, seg.data(), seg.size())) ||
-        (rc = dev_alloc(pool, &dy, n)) || (rc = dev_alloc(pool, &x16, 2 * n)) || (rc = make_w16(pool, hw.data(), hw.size(), K, PGMI_PREC_F16X3, nullptr, &w16))) {
-        cleanup();
-        return rc;
-    }
-    hipError_t e = hipSuccess;
-    for (size_t o = 0; o < n && e == hipSuccess; o += blk) e = hipMemcpy(dx + o, hx.data(), std::min(blk, n - o) * 4, hipMemcpyHostToDevice);
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    if (e == hipSuccess) e = hipEventCreate(&t0);
-    if (e == hipSuccess) e = hipEventCreate(&t1);
-    float ms = 0.f;
-    if (e == hipSuccess) {
-        launch_split16(dx, (int64_t)n, 1.0f, 2, C, x16, nullptr);
-        for (int i = 0; i < 2 && !rc; ++i) rc = launch_dilated_conv16(x16, w16.p, w16.out_scale, db, dseg, n_seg, M, C, taps, dilation, dy, nullptr);
-        hipEventRecord(t0, nullptr);
-        for (int i = 0; i < iters && !rc; ++i) rc = launch_dilated_conv16(x16, w16.p, w16.out_scale, db, dseg, n_seg, M, C, taps, dilation, dy, nullptr);
-        hipEventRecord(t1, nullptr);
-        e = hipEventSynchronize(t1);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, t0, t1);
-    }
-    if (t0) hipEventDestroy(t0);
-    if (t1) hipEventDestroy(t1);
-    cleanup();
-    if (rc) return rc;
-    if (e != hipSuccess) { set_error("dilated conv bench failed: %s", hipGetErrorString(e)); return PGMI_EHIP; }
-    *ms_per_launch = ms / iters;
-    return PGMI_OK;
+    for (int i = 0; i <= n_seg; ++i) seg[i] = i * (M / n_seg);
+    float* dx = s.alloc<float>(n);
+    float* db = s.up(hb);
+    int32_t* dseg = s.up(seg);
+    float* dy = s.alloc<float>(n);
+    unsigned short* x16 = s.alloc<unsigned short>(2 * n);
+    const W16 w16 = s.w16(hw.data(), hw.size(), K);
+    for (size_t o = 0; o < n && !s.rc; o += blk) s.hip(hipMemcpy(dx + o, hx.data(), std::min(blk, n - o) * 4, hipMemcpyHostToDevice));
+    if (s.rc) return s.rc;
+    auto launch = [&]() { return launch_dilated_conv16(x16, w16.p, w16.out_scale, db, dseg, n_seg, M, C, taps, dilation, dy, nullptr); };
+    launch_split16(dx, (int64_t)n, 1.0f, 2, C, x16, nullptr);
+    for (int i = 0; i < 2 && !s.rc; ++i) s.rc = launch();
+    const double ms = s.time_ms(launch, iters);
+    if (!s.rc) *ms_per_launch = ms;
+    return s.rc;
 }
 
 int pgmi_op_ln_gelu(int device, int precision, const float* x, const float* w, const float* b, int rows, int D, float eps, float* y) {
     if (!x || !w || !b || !y || rows < 1 || rows > (1 << 20)) { set_error("bad argument"); return PGMI_EINVAL; }
     if (precision != PGMI_PREC_FP32 && precision != PGMI_PREC_F16X3) { set_error("ln_gelu op: precision f16x3 or fp32"); return PGMI_EINVAL; }
     if (D < 32 || D % 32 || D > 5120) { set_error("ln_gelu op: D = %d must be a multiple of 32 in 32 .. 5120", D); return PGMI_EINVAL; }
-    if (pgmi_device_count() <= 0) { set_error("no HIP device visible"); return PGMI_ENODEV; }
-    PGMI_HIP(hipSetDevice(device));
-    std::vector<void*> pool;
-    auto cleanup = [&]() { for (void* p : pool) hipFree(p); };
+    OpScope s("ln_gelu op", device);
+    const bool f32 = precision == PGMI_PREC_FP32;
     const size_t n = (size_t)rows * D;
-    float *dx = nullptr, *dw = nullptr, *db = nullptr, *dy = nullptr;
-    unsigned short* y16 = nullptr;
-    int rc = 0;
-    if ((rc = dev_upload(pool, &dx, x, n)) || (rc = dev_upload(pool, &dw, w, (size_t)D)) || (rc = dev_upload(pool, &db, b, (size_t)D)) ||
-        (rc = dev_alloc(pool, &dy, n)) || (rc = dev_alloc(pool, &y16, 2 * n))) { cleanup(); return rc; }
-    hipError_t e = hipSuccess;
-    if (precision == PGMI_PREC_FP32) {
-        rc = launch_ln_gelu32(dx, dw, db, rows, D, eps, dy, nullptr);
-        if (!rc) e = hipMemcpy(y, dy, n * 4, hipMemcpyDeviceToHost);
-    } else {
-        e = hipMemset(y16, 0xFF, 2 * n * sizeof(unsigned short));          // an element the kernel skips shows as NaN
-        if (e == hipSuccess) rc = launch_ln_gelu16(dx, dw, db, rows, D, eps, y16, nullptr);
-        std::vector<unsigned short> h(rc ? 0 : 2 * n);
-        if (!rc && e == hipSuccess) e = hipMemcpy(h.data(), y16, h.size() * 2, hipMemcpyDeviceToHost);
-        if (!rc && e == hipSuccess)
-            for (int r = 0; r < rows; ++r)
-                for (int k = 0; k < D; ++k) {
-                    const size_t o = ki_off((size_t)r, k, D);
-                    _Float16 hi, lo;
-                    memcpy(&hi, &h[o], 2); memcpy(&lo, &h[o + 32], 2);
-                    y[(size_t)r * D + k] = (float)hi + (float)lo * (1.0f / kLoScale);
-                }
-    }
-    cleanup();
-    if (rc) return rc;
-    if (e != hipSuccess) { set_error("ln_gelu op failed: %s", hipGetErrorString(e)); return PGMI_EHIP; }
-    return PGMI_OK;
+    float* dx = s.up(x, n);
+    float* dw = s.up(w, (size_t)D);
+    float* db = s.up(b, (size_t)D);
+    float* dy = f32 ? s.alloc<float>(n) : nullptr;
+    unsigned short* y16 = f32 ? nullptr : s.alloc<unsigned short>(2 * n, 0xFF);      // an element the kernel skips shows as NaN
+    if (!s.rc) s.rc = f32 ? launch_ln_gelu32(dx, dw, db, rows, D, eps, dy, nullptr) : launch_ln_gelu16(dx, dw, db, rows, D, eps, y16, nullptr);
+    s.sync();
+    if (f32) s.down(y, dy, n);
+    else s.planes(y, y16, (size_t)rows, (size_t)D);
+    return s.rc;
 }
 
 }  // extern "C"

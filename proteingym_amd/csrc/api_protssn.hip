@@ -321,9 +321,7 @@ int pgmi_op_egnn_message(int device, const pgmi_protssn_config* cfg, const float
                 float v;
                 if (split) {
                     const size_t o = ki_off((size_t)r, (int)D + k, (int)K);
-                    _Float16 hi, lo;
-                    memcpy(&hi, &a16[o], 2); memcpy(&lo, &a16[o + 32], 2);
-                    v = (float)hi + (float)lo * (1.0f / kLoScale);
+                    v = rebuild_split(a16[o], a16[o + 32]);
                 } else {
                     v = a32[(size_t)r * K + D + k];
                 }

@@ -468,6 +468,118 @@ struct BlobCursor {
     }
 };
 
+// a value of the split fp16 planes (common.h split_act) back as fp32: hi + lo 2^-11
+inline float rebuild_split(unsigned short h, unsigned short l) {
+    _Float16 a, b;
+    memcpy(&a, &h, 2); memcpy(&b, &l, 2);
+    return (float)a + (float)b * (1.0f / kLoScale);
+}
+
+// The scope of one single-op or timing entry (pgmi_op_* / pgmi_bench_*: api_ops.hip, api_carp.hip), made after the entry's argument
+// checks.  Making it refuses a machine without a device and selects `device`; it owns what the entry puts on the device -- the pool
+// (tmp.allocs; tmp is the model-shaped argument of the helpers that want one), MoE's pinned counts, the timer's events -- and releases
+// it when the entry returns, on every path.  The first error sticks (BlobCursor's idiom): every later call does nothing and hands
+// back null, so an entry is a list of plain statements and one `if (s.rc) return s.rc;` before its first launch.  `what` names the
+// entry in "<what> failed: ..." ("rmsnorm op", "bench").
+struct OpScope {
+    const char* what;
+    int rc = PGMI_OK;
+    pgmi_model tmp{};
+    std::vector<void*>& pool = tmp.allocs;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool opened = false;
+
+    OpScope(const char* what_, int device) : what(what_) {
+        rc = open(device);
+        opened = rc == PGMI_OK;
+        if (rc == PGMI_EHIP) (void)hipGetLastError();    // reported here: not left for the next entry's sync() to find
+    }
+    OpScope(const OpScope&) = delete;
+    ~OpScope() {
+        for (hipEvent_t e : ev)
+            if (e) hipEventDestroy(e);
+        if (tmp.moe.counts_host) hipHostFree(tmp.moe.counts_host);
+        for (void* p : pool) hipFree(p);
+    }
+    // a HIP call of the entry itself: its failure is the entry's "<what> failed: ..."
+    int hip(hipError_t e) {
+        if (!rc && e != hipSuccess) { set_error("%s failed: %s", what, hipGetErrorString(e)); rc = PGMI_EHIP; }
+        return rc;
+    }
+    // n elements; fill = 0x00 or 0xFF: every byte starts as that (0xFF: NaN in fp32 and fp16, so an element a kernel skips shows)
+    template <typename T>
+    T* alloc(size_t n, int fill = -1) {
+        T* p = nullptr;
+        if (!rc) rc = dev_alloc(pool, &p, n);
+        if (!rc && fill >= 0) hip(hipMemset(p, fill, n * sizeof(T)));
+        return rc ? nullptr : p;
+    }
+    template <typename T>
+    T* up(const T* host, size_t n) {
+        T* p = nullptr;
+        if (!rc) rc = dev_upload(pool, &p, host, n);
+        return rc ? nullptr : p;
+    }
+    template <typename T>
+    T* up(const std::vector<T>& host) { return up(host.data(), host.size()); }
+    W16 w16(const float* host, size_t n, size_t K, int precision = PGMI_PREC_F16X3) {
+        W16 w;
+        if (!rc) rc = make_w16(pool, host, n, K, precision, nullptr, &w);
+        return w;
+    }
+    // the end of the launches: waits for the device whatever rc is, unless the scope never opened (nothing is released under a
+    // running kernel), then reads the launch error
+    int sync() {
+        if (!opened) return rc;
+        hipError_t e = hipDeviceSynchronize();
+        if (e == hipSuccess) e = hipGetLastError();
+        return hip(e);
+    }
+    template <typename T>
+    void down(T* host, const T* dev, size_t n) {
+        if (!rc) hip(hipMemcpy(host, dev, n * sizeof(T), hipMemcpyDeviceToHost));
+    }
+    // split fp16 planes in K-interleaved rows (ki_off) [rows][cols] back as fp32 = hi + lo 2^-11
+    void planes(float* host, const unsigned short* dev16, size_t rows, size_t cols) {
+        std::vector<unsigned short> h(rc ? 0 : rows * cols * 2);
+        down(h.data(), dev16, h.size());
+        for (size_t r = 0; r < rows && !rc; ++r)
+            for (size_t c = 0; c < cols; ++c) {
+                const size_t o = ki_off(r, (int)c, (int)cols);
+                host[r * cols + c] = rebuild_split(h[o], h[o + 32]);
+            }
+    }
+    // one bf16 plane, row-major, back as fp32
+    void bf16_plane(float* host, const unsigned short* dev16, size_t n) {
+        std::vector<unsigned short> h(rc ? 0 : n);
+        down(h.data(), dev16, n);
+        for (size_t i = 0; i < n && !rc; ++i) {
+            const unsigned int u = (unsigned int)h[i] << 16;
+            memcpy(&host[i], &u, 4);
+        }
+    }
+    // ms per launch of `iters` launches on the null stream between two events; 0 once rc is set.  launch() returns a PGMI code.
+    template <typename F>
+    double time_ms(F launch, int iters) {
+        for (hipEvent_t& e : ev)
+            if (!rc && !e) hip(hipEventCreate(&e));
+        if (!rc) hip(hipEventRecord(ev[0], nullptr));
+        for (int i = 0; i < iters && !rc; ++i) rc = launch();
+        if (!rc) hip(hipEventRecord(ev[1], nullptr));
+        if (!rc) hip(hipEventSynchronize(ev[1]));
+        float ms = 0.f;
+        if (!rc) hip(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        return (double)ms / iters;
+    }
+
+private:
+    int open(int device) {
+        if (pgmi_device_count() <= 0) { set_error("no HIP device visible"); return PGMI_ENODEV; }
+        PGMI_HIP(hipSetDevice(device));
+        return PGMI_OK;
+    }
+};
+
 // Attention slot of model dim `col` in the rotate-half layout (ESM2, RITA): every head owns 64 lanes of the attention kernels; dim j
 // of a head sits in slot j (first half) or 32 + (j - dh/2) (second half) so that rotary pairs (j, j + dh/2) are the kernels' pairs
 // (i, i + 32).  dh == 64 is the identity layout; smaller heads leave zero slots (zero weight rows -> q,k,v slots exactly 0 -> scores
