@@ -74,6 +74,10 @@ extern "C" {
  * layer cross-attending to one encoded backbone; created with pgmi_esmif1_model_create, the backbone's encoder output bound with
  * pgmi_esmif1_set_memory, scored with pgmi_esmif1_* (see the ESM-IF1 section below) */
 #define PGMI_ARCH_ESMIF1 12
+/* MULAN (proteingym/baselines/mulan/mulan/model.py): ESM2's or SaProt's encoder with a structure adapter over per-residue angle rows
+ * added to the word embeddings; created with pgmi_mulan_model_create, a chunk's angles bound with pgmi_mulan_set_structure, scored
+ * with pgmi_mulan_* (see the MULAN section below) */
+#define PGMI_ARCH_MULAN 13
 
 /* GEMM operand precision.  Residual stream, LayerNorm statistics, softmax and every
  * accumulator are fp32 in all modes. */
@@ -626,6 +630,35 @@ int pgmi_saprot_model_create(const pgmi_config* cfg, int mask_id, const float* w
 int pgmi_saprot_token_logprobs(pgmi_model* m, const int32_t* tokens, int B, int T, float* out);
 int pgmi_saprot_group_logprobs(pgmi_model* m, const int32_t* wt_tokens, int T, const int32_t* set_off, const int32_t* set_pos,
                                int n_sets, float* out);
+
+/* ---- MULAN (arch PGMI_ARCH_MULAN; vocab 33 or 446, max_positions 0, every precision) ----------------------------------------------
+ * The main stack is ESM2 (groups = 0: the 33-token ESM alphabet, <mask> = 32) or SaProt's encoder (groups = 21: the 446-token layout
+ * of the SaProt section, <mask> = 4).  In front of it sits the structure adapter (mulan/model_utils.py:59-97): per token a row of
+ * seven angles (phi, psi, chi1..chi5, radians) goes through Linear(7 -> D), one full ESM layer of width D WITHOUT rotary (and without
+ * a position table), and a final LayerNorm; the result is added to the word embedding before token dropout:
+ *   x = (E[token] + adapter(row)), zero at <mask>, times 0.88 / (1 - #mask / #tokens) with token_dropout.
+ * The angle row of token t is chosen per forward: 4.0 (seven times) for the first and last token and where plddt[t] <= 70, -4.0 where
+ * t is one of the forward's masked positions (this wins), else the bound angles (dataset.py:306-314, compute_fitness.py:117-126).
+ * Weight blob: ESM2's in pgmi_weight_count's order with V = vocab, then MLP.weight [D][7], MLP.bias [D], one layer in the same
+ * per-layer order with fc1 [4D,D] and fc2 [D,4D], and the adapter's final LayerNorm w, b (HF names: proteingym_amd/mulan.py).
+ *
+ * pgmi_mulan_model_create: groups must fit cfg->vocab (0: 33, 21: 446); mask_id is the tokenizer's <mask> id.
+ * pgmi_mulan_set_structure: binds the chunk -- angles f32 [T][7], plddt f32 [T] (the values of the two end tokens are not read) -- for
+ *   the T tokens <cls> + residues + <eos>.  The forward entries refuse another T, and PGMI_EINVAL without a bound chunk.
+ * pgmi_mulan_token_logprobs: B explicit rows tokens int32 [B][T] (no <pad>); row b's masked positions are
+ *   row_pos[row_off[b] .. row_off[b+1]) (ascending, possibly none): they choose the -4 angle rows, the tokens are taken as given.
+ *   out f32 [B][T][V]: log_softmax over all V columns.
+ * pgmi_mulan_set_logprobs: one forward per position set (CSR as in pgmi_saprot_group_logprobs, on residue tokens) of the wild type
+ *   wt_tokens [T], the set's tokens replaced by <mask> and its angle rows by -4.  out f32 [set_off[n_sets]][V] (groups = 0: the
+ *   log-softmax row at every (set, position)) or [..][21] (groups = 21: SaProt's group table).  An entry's bits do not depend on the
+ *   other sets of the call.  T + 31 > max_rows is PGMI_EINVAL: sequences are not windowed. */
+int64_t pgmi_mulan_weight_count(const pgmi_config* cfg);
+int pgmi_mulan_model_create(const pgmi_config* cfg, int mask_id, int groups, const float* weights, int64_t n_weights, int device,
+                            pgmi_model** out);
+int pgmi_mulan_set_structure(pgmi_model* m, const float* angles, const float* plddt, int T);
+int pgmi_mulan_token_logprobs(pgmi_model* m, const int32_t* tokens, int B, int T, const int32_t* row_off, const int32_t* row_pos, float* out);
+int pgmi_mulan_set_logprobs(pgmi_model* m, const int32_t* wt_tokens, int T, const int32_t* set_off, const int32_t* set_pos, int n_sets,
+                            float* out);
 
 /* ---- PoET (arch PGMI_ARCH_POET; vocab 24 .. 64, head_dim an even value up to 64, precision f16x3) ------------------------------
  * Tokens (poet/alphabets.py Uniprot21 with gap and distinct start / stop): "ARNDCQEGHILKMFPSTWYV" 0..19, gap 20, start 21, stop 22,

@@ -21,6 +21,7 @@ ARCH_POET = 9
 ARCH_PROGEN3 = 10
 ARCH_ESM3 = 11
 ARCH_ESMIF1 = 12
+ARCH_MULAN = 13
 GPT_POS_ROTARY, GPT_POS_LEARNED = 0, 1
 PREC_FP32, PREC_BF16, PREC_F16X3 = 0, 1, 2
 PRECISIONS = {"fp32": PREC_FP32, "bf16": PREC_BF16, "f16x3": PREC_F16X3}
@@ -108,6 +109,11 @@ SIGNATURES = [
     ("pgmi_saprot_model_create", C.c_int, [C.POINTER(Config), C.c_int, _f32p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     ("pgmi_saprot_token_logprobs", C.c_int, [C.c_void_p, _i32p, C.c_int, C.c_int, _f32p]),
     ("pgmi_saprot_group_logprobs", C.c_int, [C.c_void_p, _i32p, C.c_int, _i32p, _i32p, C.c_int, _f32p]),
+    ("pgmi_mulan_weight_count", C.c_int64, [C.POINTER(Config)]),
+    ("pgmi_mulan_model_create", C.c_int, [C.POINTER(Config), C.c_int, C.c_int, _f32p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
+    ("pgmi_mulan_set_structure", C.c_int, [C.c_void_p, _f32p, _f32p, C.c_int]),
+    ("pgmi_mulan_token_logprobs", C.c_int, [C.c_void_p, _i32p, C.c_int, C.c_int, _i32p, _i32p, _f32p]),
+    ("pgmi_mulan_set_logprobs", C.c_int, [C.c_void_p, _i32p, C.c_int, _i32p, _i32p, C.c_int, _f32p]),
     ("pgmi_poet_weight_count", C.c_int64, [C.POINTER(Config), C.c_int]),
     ("pgmi_poet_model_create", C.c_int, [C.POINTER(Config), C.c_int, _f32p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     ("pgmi_poet_set_prompt", C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int]),
@@ -259,8 +265,8 @@ class ModelHandle:
     """A device-resident model behind its libpgmi handle.  __init__ builds the Config from cfg's dimensions and the fields the
     subclass passes, checks the blob size against the library's count and creates the model through CREATE; close / __del__ destroy
     it.  pgmi_pg2_model_create, pgmi_gpt_model_create and pgmi_saprot_model_create take arch_arg (ProGen2's rotary_dim, the causal
-    decoder's pos_kind, SaProt's <mask> id) after
-    the config, and their subclasses name their weight count."""
+    decoder's pos_kind, SaProt's <mask> id; a tuple for
+    pgmi_mulan_model_create's <mask> id and groups) after the config, and their subclasses name their weight count."""
     CREATE = "pgmi_model_create"
 
     def __init__(self, cfg: dict, weights: np.ndarray, device: int = 0, max_rows: int = 0, arch_arg=None,
@@ -275,7 +281,7 @@ class ModelHandle:
         if w.size != n:
             raise PgmiError(f"weight blob has {w.size} elements, config needs {n}")
         h = C.c_void_p()
-        head = (C.byref(c),) if arch_arg is None else (C.byref(c), arch_arg)
+        head = (C.byref(c),) if arch_arg is None else (C.byref(c), *arch_arg) if isinstance(arch_arg, tuple) else (C.byref(c), arch_arg)
         check(getattr(lib, self.CREATE)(*head, ptr(w, _f32p), w.size, device, C.byref(h)))
         self._h = h
 

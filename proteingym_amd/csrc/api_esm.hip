@@ -8,35 +8,48 @@ namespace pgmi {
 // ESM-1b / ESM2 weight blob (include/pgmi.h).  embed_tokens == the tied lm_head.weight (esm1.py:101-105): the host passes the matrix
 // that load_state_dict leaves in the tied parameter (pretrained.py:97,216), see proteingym_amd/esm.py.
 int create_esm(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights) {
-    const size_t D = cfg->embed_dim, F = cfg->ffn_dim, V = cfg->vocab, dh = m->dh, Da = m->Da;
     BlobCursor c(m, w, n_weights);
+    walk_esm(c);
+    return c.finish();
+}
+
+// One layer of the blob (self_attn_layer_norm .. fc2) into L: the attention's slot layout, q pre-scaled.
+void walk_esm_layer(BlobCursor& c, Layer* Lp, size_t F) {
+    pgmi_model* m = c.m;
+    const size_t D = m->cfg.embed_dim, dh = m->dh, Da = m->Da;
+    auto slot = [&](size_t col) -> size_t { return rotate_half_slot(col, dh); };
+    const float qscale = 1.0f / sqrtf((float)dh);           // multihead_attention.py:261 (exact 1/8 for dh 64)
+    std::vector<float> wq(3 * Da * D, 0.0f), bq(3 * Da, 0.0f), wo_r(D * Da, 0.0f);
+    Layer& L = *Lp;
+    c.upload(&L.ln1_w, D);
+    c.upload(&L.ln1_b, D);
+    pack_qkv_slots(c.take(3 * (D * D + D)), D, Da, slot, qscale, wq.data(), bq.data());
+    c.linear(&L.wqkv, &L.wqkv16, wq.data(), wq.size(), D);
+    c.upload(&L.bqkv, bq.data(), bq.size());
+    pack_out_cols(c.take(D * D), D, Da, slot, wo_r.data());
+    c.linear(&L.wo, &L.wo16, wo_r.data(), wo_r.size(), Da);
+    c.upload(&L.bo, D);
+    c.upload(&L.ln2_w, D);
+    c.upload(&L.ln2_b, D);
+    c.linear(&L.w1, &L.w116, F * D, D);
+    c.upload(&L.b1, F);
+    c.linear(&L.w2, &L.w216, D * F, F);
+    c.upload(&L.b2, D);
+}
+
+// The whole ESM-1b / ESM2 blob; the cursor is left at its end (MULAN's adapter follows it: api_mulan.hip).
+void walk_esm(BlobCursor& c) {
+    pgmi_model* m = c.m;
+    const pgmi_config* cfg = &m->cfg;
+    const size_t D = cfg->embed_dim, V = cfg->vocab;
     c.upload(&m->embed_tokens, V * D);
     if (cfg->arch == PGMI_ARCH_ESM1B) c.upload(&m->embed_positions, (size_t)(cfg->max_positions + 2) * D);
     if (cfg->emb_layer_norm_before) {
         c.upload(&m->lnb_w, D);
         c.upload(&m->lnb_b, D);
     }
-    auto slot = [&](size_t col) -> size_t { return rotate_half_slot(col, dh); };
-    const float qscale = 1.0f / sqrtf((float)dh);           // multihead_attention.py:261 (exact 1/8 for dh 64)
     m->layers.resize(cfg->layers);
-    std::vector<float> wq(3 * Da * D, 0.0f), bq(3 * Da, 0.0f), wo_r(D * Da, 0.0f);
-    for (int l = 0; l < cfg->layers; ++l) {
-        Layer& L = m->layers[l];
-        c.upload(&L.ln1_w, D);
-        c.upload(&L.ln1_b, D);
-        pack_qkv_slots(c.take(3 * (D * D + D)), D, Da, slot, qscale, wq.data(), bq.data());
-        c.linear(&L.wqkv, &L.wqkv16, wq.data(), wq.size(), D);
-        c.upload(&L.bqkv, bq.data(), bq.size());
-        pack_out_cols(c.take(D * D), D, Da, slot, wo_r.data());
-        c.linear(&L.wo, &L.wo16, wo_r.data(), wo_r.size(), Da);
-        c.upload(&L.bo, D);
-        c.upload(&L.ln2_w, D);
-        c.upload(&L.ln2_b, D);
-        c.linear(&L.w1, &L.w116, F * D, D);
-        c.upload(&L.b1, F);
-        c.linear(&L.w2, &L.w216, D * F, F);
-        c.upload(&L.b2, D);
-    }
+    for (int l = 0; l < cfg->layers; ++l) walk_esm_layer(c, &m->layers[l], cfg->ffn_dim);
     c.upload(&m->lna_w, D);
     c.upload(&m->lna_b, D);
     c.linear(&m->hd_w, &m->hd16, D * D, D);
@@ -45,7 +58,6 @@ int create_esm(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_
     c.upload(&m->hln_b, D);
     c.upload(&m->head_b, V);
     m->head_w = m->embed_tokens;
-    return c.finish();
 }
 
 int ensure_rotary(pgmi_model* m, int T) {
@@ -67,6 +79,95 @@ int upload_rotate_half(pgmi_model* m, int n) {
     });
 }
 
+// One encoder layer on the M = B T rows of m->x; run_encoder's loop and MULAN's structure adapter (api_mulan.hip) run this body.
+// rotary: ESM2's rotate-half on q and k -- in the fused QKV epilogue of the 16-bit modes, launch_rotary in precision fp32; the adapter
+// runs with it off inside a rotary model.  keep != nullptr (the last layer of a kept-rows forward, see run_encoder): the stages after
+// the attention run on the n_keep gathered rows and *compacted is set.
+int encoder_layer(pgmi_model* m, const Layer& L, int B, int T, bool rotary, const int32_t* keep, int n_keep, bool* compacted) {
+    const pgmi_config& c = m->cfg;
+    const int M = B * T, D = c.embed_dim, F = L.ffn ? L.ffn : c.ffn_dim, N1 = L.ffn ? L.ffn : m->fc1_cols, H = c.heads, Da = m->Da;
+    hipStream_t s = m->stream;
+    int rc = PGMI_OK;
+    const double ln_bytes = 2.0 * M * D * 4;
+    const int prec = c.precision;
+    const int mode16 = (prec == PGMI_PREC_F16X3) ? 1 : 2;          // LN / attention output mode
+    { ProfScope p(m, PGMI_K_LAYERNORM, 0, ln_bytes);
+      if (prec == PGMI_PREC_FP32) launch_layernorm(m->x, L.ln1_w, L.ln1_b, M, D, 1e-5f, m->h, s);
+      else launch_layernorm16(m->x, L.ln1_w, L.ln1_b, M, D, 1e-5f, m->h16, mode16, s); }
+    // attention operands straight from the QKV projection's epilogue -- in the bf16 mode too (round 6): the epilogue splits the fp32
+    // accumulators whatever the GEMM's operand type was, so that mode's attention runs on the 16-bit pipe as well.  A layer with a
+    // q / k LayerNorm (ESM C) writes fp32 rows for its prep pass instead.
+    const bool fused_qkv = prec != PGMI_PREC_FP32 && !L.q_ln;
+    { ProfScope p(m, PGMI_K_GEMM_QKV, 2.0 * M * 3 * D * D, 0);
+      if (fused_qkv) {
+          GemmLaunch g = qkv_launch(m, L.wqkv16, L.bqkv, M, Da, D, T, m->Hs);
+          g.bf = prec == PGMI_PREC_BF16;
+          g.qkv.cos_t = m->rot_cos; g.qkv.sin_t = m->rot_sin; g.qkv.rotary = rotary; g.qkv.rot_halves = m->rot_halves;
+          rc = launch_gemm16(g);
+      } else
+          rc = linear(m, m->h, m->h16, L.wqkv, L.wqkv16, L.bqkv, nullptr, m->qkv, nullptr, M, 3 * Da, D, EPI_NONE);
+      if (rc) return rc; }
+    // the q / k LayerNorm prep pass is profiled as attention (it produces the attention's operands): PGMI_K_ATTENTION counts both
+    { ProfScope p(m, PGMI_K_ATTENTION, 4.0 * M * T * D, L.q_ln ? (double)M * D * 20 : 0);
+      if (L.q_ln && (rc = launch_qkln_prep(m->qkv, L.q_ln, L.k_ln, 1e-5f, m->rot_cos, m->rot_sin, B, T, H, m->qk16, m->qk16_plane,
+                                           m->vt16, m->vt16_plane, s)))
+          return rc;
+      const bool v2 = prec != PGMI_PREC_FP32;
+      if (rotary && !v2) launch_rotary(m->qkv, m->rot_cos, m->rot_sin, M, T, m->Hs, s, m->rot_halves);
+      if (v2) {
+          AttLaunch a;
+          a.qk16 = m->qk16, a.qk_plane = m->qk16_plane, a.vt16 = m->vt16, a.vt_plane = m->vt16_plane;
+          a.B = B, a.T = T, a.H = H, a.head_dim = m->rot_halves * kHeadDim;
+          a.kv_len = m->kv_len;
+          a.out = prec == PGMI_PREC_F16X3 ? ATT_OUT_SPLIT : ATT_OUT_BF16;      // bf16 mode: one bf16 plane (the out-projection's operand)
+          a.ctx16 = m->h16;
+          a.stream = s;
+          rc = launch_attention_f16x3_v2(a);
+      } else {
+          rc = launch_attention_f32(m->qkv, m->kv_len, B, T, H, m->h, s, m->rot_halves * kHeadDim);
+      }
+      if (rc) return rc; }
+    // (a block with the geometric branch is not row-local after its attention: a one-block ESM3 takes the full path)
+    if (keep && !L.g_norm_w) {
+        const int R = n_keep;
+        ProfScope p(m, PGMI_K_KEPT_ROWS, 2.0 * R * D * (Da + N1 + F), 0);
+        launch_gather_rows(m->x, keep, R, D, m->qkv, s);                       // residual rows (qkv is free after attention)
+        if (prec == PGMI_PREC_FP32) launch_gather_rows(m->h, keep, R, Da, m->g, s);
+        else        // a 16-bit context row is one contiguous run (K-interleaved hi|lo: 4 Da bytes; bf16: 2 Da bytes)
+            launch_gather_rows(reinterpret_cast<const float*>(m->h16), keep, R, prec == PGMI_PREC_F16X3 ? Da : Da / 2,
+                               reinterpret_cast<float*>(m->g16), s);
+        rc = linear(m, m->g, m->g16, L.wo, L.wo16, L.bo, m->qkv, m->x, nullptr, R, D, Da, EPI_NONE);
+        if (rc) return rc;
+        if (prec == PGMI_PREC_FP32) launch_layernorm(m->x, L.ln2_w, L.ln2_b, R, D, 1e-5f, m->h, s);
+        else launch_layernorm16(m->x, L.ln2_w, L.ln2_b, R, D, 1e-5f, m->h16, mode16, s);
+        rc = linear(m, m->h, m->h16, L.w1, L.w116, L.b1, nullptr,
+                    prec == PGMI_PREC_FP32 ? m->g : nullptr, prec == PGMI_PREC_FP32 ? nullptr : m->g16,
+                    R, N1, D, m->fc1_epi);
+        if (rc) return rc;
+        rc = linear(m, m->g, m->g16, L.w2, L.w216, L.b2, m->x, m->x, nullptr, R, D, F, EPI_NONE);
+        if (rc) return rc;
+        if (compacted) *compacted = true;
+        return PGMI_OK;
+    }
+    { ProfScope p(m, PGMI_K_GEMM_OUT, 2.0 * M * D * D, 0);
+      rc = linear(m, m->h, m->h16, L.wo, L.wo16, L.bo, m->x, m->x, nullptr, M, D, Da, EPI_NONE);
+      if (rc) return rc; }
+    // ESM3 block 0: the geometric attention branch; exactly zero, and not launched, when no token of the window has a frame
+    if (L.g_norm_w && m->e3_framed && (rc = geom_branch(m, L, B, T))) return rc;
+    { ProfScope p(m, PGMI_K_LAYERNORM, 0, ln_bytes);
+      if (prec == PGMI_PREC_FP32) launch_layernorm(m->x, L.ln2_w, L.ln2_b, M, D, 1e-5f, m->h, s);
+      else launch_layernorm16(m->x, L.ln2_w, L.ln2_b, M, D, 1e-5f, m->h16, mode16, s); }
+    { ProfScope p(m, PGMI_K_GEMM_FC1, 2.0 * M * N1 * D, 0);
+      rc = linear(m, m->h, m->h16, L.w1, L.w116, L.b1, nullptr,
+                  prec == PGMI_PREC_FP32 ? m->g : nullptr, prec == PGMI_PREC_FP32 ? nullptr : m->g16,
+                  M, N1, D, m->fc1_epi);
+      if (rc) return rc; }
+    { ProfScope p(m, PGMI_K_GEMM_FC2, 2.0 * M * F * D, 0);
+      rc = linear(m, m->g, m->g16, L.w2, L.w216, L.b2, m->x, m->x, nullptr, M, D, F, EPI_NONE);
+      if (rc) return rc; }
+    return PGMI_OK;
+}
+
 // Runs the encoder on tokens already in m->tokens [B,T]; leaves the residual stream in m->x.
 // keep != nullptr (device, n_keep row indices into [B*T]): the caller reads only these rows of the output (the masked
 // position of every sequence: compute_fitness.py:503 `token_probs[:, i]`, :274-276).  Everything after the last layer's
@@ -76,9 +177,10 @@ int upload_rotate_half(pgmi_model* m, int n) {
 // kernel on the way computes a row from that row's inputs only, in an order that does not depend on the row count
 // (tests/test_gpu_esm.py::test_last_layer_kept_rows_bit_identical, tests/test_gpu_esmc.py).  PGMI_KEEP_ROWS=0 turns it off.
 // What differs per model is data: the embedding (embed_gather), a layer's q / k LayerNorm (L.q_ln: ESM C), FC1's epilogue and width.
+// MULAN: the caller has left the structure adapter's input rows in m->x (launch_mulan_rows); mulan_embed turns them into the embedding.
 int run_encoder(pgmi_model* m, int B, int T, const int32_t* keep, int n_keep, bool* compacted) {
     const pgmi_config& c = m->cfg;
-    const int M = B * T, D = c.embed_dim, F = c.ffn_dim, N1 = m->fc1_cols, H = c.heads, Da = m->Da;
+    const int M = B * T, D = c.embed_dim;
     hipStream_t s = m->stream;
     if (c.arch == PGMI_ARCH_ESM1B && T > c.max_positions) {
         set_error("Sequence length %d above maximum sequence length of %d", T, c.max_positions);   // modules.py:256-260
@@ -92,6 +194,7 @@ int run_encoder(pgmi_model* m, int B, int T, const int32_t* keep, int n_keep, bo
         // kv_len: keys before the first <pad>
         launch_seq_stats(m->tokens, B, T, m->embed_gather ? 0 : c.token_dropout, m->denom, m->pos_idx, m->kv_len, s, m->mask_id);
         if (c.arch == PGMI_ARCH_ESM3) { if ((rc = esm3_embed(m, B, T))) return rc; }
+        else if (c.arch == PGMI_ARCH_MULAN) { if ((rc = mulan_embed(m, B, T))) return rc; }
         else if (m->embed_gather) launch_gather_rows(m->embed_tokens, m->tokens, M, D, m->x, s);
         else launch_embed(m->tokens, m->denom, m->pos_idx, m->embed_tokens, m->embed_positions, c.token_dropout, M, T, D, m->x, s, m->mask_id);
         if (m->lnb_w) {                                        // emb_layer_norm_before
@@ -99,85 +202,9 @@ int run_encoder(pgmi_model* m, int B, int T, const int32_t* keep, int n_keep, bo
             launch_zero_pad_rows(m->tokens, M, D, m->x, s);
         }
     }
-    const double ln_bytes = 2.0 * M * D * 4;
-    const int prec = c.precision;
-    const int mode16 = (prec == PGMI_PREC_F16X3) ? 1 : 2;          // LN / attention output mode
     for (int l = 0; l < c.layers; ++l) {
-        const Layer& L = m->layers[l];
-        { ProfScope p(m, PGMI_K_LAYERNORM, 0, ln_bytes);
-          if (prec == PGMI_PREC_FP32) launch_layernorm(m->x, L.ln1_w, L.ln1_b, M, D, 1e-5f, m->h, s);
-          else launch_layernorm16(m->x, L.ln1_w, L.ln1_b, M, D, 1e-5f, m->h16, mode16, s); }
-        // attention operands straight from the QKV projection's epilogue -- in the bf16 mode too (round 6): the epilogue splits the fp32
-        // accumulators whatever the GEMM's operand type was, so that mode's attention runs on the 16-bit pipe as well.  A layer with a
-        // q / k LayerNorm (ESM C) writes fp32 rows for its prep pass instead.
-        const bool fused_qkv = prec != PGMI_PREC_FP32 && !L.q_ln;
-        { ProfScope p(m, PGMI_K_GEMM_QKV, 2.0 * M * 3 * D * D, 0);
-          if (fused_qkv) {
-              GemmLaunch g = qkv_launch(m, L.wqkv16, L.bqkv, M, Da, D, T, m->Hs);
-              g.bf = prec == PGMI_PREC_BF16;
-              g.qkv.cos_t = m->rot_cos; g.qkv.sin_t = m->rot_sin; g.qkv.rotary = esm2_rotary(c.arch); g.qkv.rot_halves = m->rot_halves;
-              rc = launch_gemm16(g);
-          } else
-              rc = linear(m, m->h, m->h16, L.wqkv, L.wqkv16, L.bqkv, nullptr, m->qkv, nullptr, M, 3 * Da, D, EPI_NONE);
-          if (rc) return rc; }
-        // the q / k LayerNorm prep pass is profiled as attention (it produces the attention's operands): PGMI_K_ATTENTION counts both
-        { ProfScope p(m, PGMI_K_ATTENTION, 4.0 * M * T * D, L.q_ln ? (double)M * D * 20 : 0);
-          if (L.q_ln && (rc = launch_qkln_prep(m->qkv, L.q_ln, L.k_ln, 1e-5f, m->rot_cos, m->rot_sin, B, T, H, m->qk16, m->qk16_plane,
-                                               m->vt16, m->vt16_plane, s)))
-              return rc;
-          const bool v2 = prec != PGMI_PREC_FP32;
-          if (esm2_rotary(c.arch) && !v2) launch_rotary(m->qkv, m->rot_cos, m->rot_sin, M, T, m->Hs, s, m->rot_halves);
-          if (v2) {
-              AttLaunch a;
-              a.qk16 = m->qk16, a.qk_plane = m->qk16_plane, a.vt16 = m->vt16, a.vt_plane = m->vt16_plane;
-              a.B = B, a.T = T, a.H = H, a.head_dim = m->rot_halves * kHeadDim;
-              a.kv_len = m->kv_len;
-              a.out = prec == PGMI_PREC_F16X3 ? ATT_OUT_SPLIT : ATT_OUT_BF16;      // bf16 mode: one bf16 plane (the out-projection's operand)
-              a.ctx16 = m->h16;
-              a.stream = s;
-              rc = launch_attention_f16x3_v2(a);
-          } else {
-              rc = launch_attention_f32(m->qkv, m->kv_len, B, T, H, m->h, s, m->rot_halves * kHeadDim);
-          }
-          if (rc) return rc; }
-        // (a block with the geometric branch is not row-local after its attention: a one-block ESM3 takes the full path)
-        if (keep && m->keep_rows && l == c.layers - 1 && !L.g_norm_w) {
-            const int R = n_keep;
-            ProfScope p(m, PGMI_K_KEPT_ROWS, 2.0 * R * D * (Da + N1 + F), 0);
-            launch_gather_rows(m->x, keep, R, D, m->qkv, s);                       // residual rows (qkv is free after attention)
-            if (prec == PGMI_PREC_FP32) launch_gather_rows(m->h, keep, R, Da, m->g, s);
-            else        // a 16-bit context row is one contiguous run (K-interleaved hi|lo: 4 Da bytes; bf16: 2 Da bytes)
-                launch_gather_rows(reinterpret_cast<const float*>(m->h16), keep, R, prec == PGMI_PREC_F16X3 ? Da : Da / 2,
-                                   reinterpret_cast<float*>(m->g16), s);
-            rc = linear(m, m->g, m->g16, L.wo, L.wo16, L.bo, m->qkv, m->x, nullptr, R, D, Da, EPI_NONE);
-            if (rc) return rc;
-            if (prec == PGMI_PREC_FP32) launch_layernorm(m->x, L.ln2_w, L.ln2_b, R, D, 1e-5f, m->h, s);
-            else launch_layernorm16(m->x, L.ln2_w, L.ln2_b, R, D, 1e-5f, m->h16, mode16, s);
-            rc = linear(m, m->h, m->h16, L.w1, L.w116, L.b1, nullptr,
-                        prec == PGMI_PREC_FP32 ? m->g : nullptr, prec == PGMI_PREC_FP32 ? nullptr : m->g16,
-                        R, N1, D, m->fc1_epi);
-            if (rc) return rc;
-            rc = linear(m, m->g, m->g16, L.w2, L.w216, L.b2, m->x, m->x, nullptr, R, D, F, EPI_NONE);
-            if (rc) return rc;
-            if (compacted) *compacted = true;
-            break;
-        }
-        { ProfScope p(m, PGMI_K_GEMM_OUT, 2.0 * M * D * D, 0);
-          rc = linear(m, m->h, m->h16, L.wo, L.wo16, L.bo, m->x, m->x, nullptr, M, D, Da, EPI_NONE);
-          if (rc) return rc; }
-        // ESM3 block 0: the geometric attention branch; exactly zero, and not launched, when no token of the window has a frame
-        if (L.g_norm_w && m->e3_framed && (rc = geom_branch(m, L, B, T))) return rc;
-        { ProfScope p(m, PGMI_K_LAYERNORM, 0, ln_bytes);
-          if (prec == PGMI_PREC_FP32) launch_layernorm(m->x, L.ln2_w, L.ln2_b, M, D, 1e-5f, m->h, s);
-          else launch_layernorm16(m->x, L.ln2_w, L.ln2_b, M, D, 1e-5f, m->h16, mode16, s); }
-        { ProfScope p(m, PGMI_K_GEMM_FC1, 2.0 * M * N1 * D, 0);
-          rc = linear(m, m->h, m->h16, L.w1, L.w116, L.b1, nullptr,
-                      prec == PGMI_PREC_FP32 ? m->g : nullptr, prec == PGMI_PREC_FP32 ? nullptr : m->g16,
-                      M, N1, D, m->fc1_epi);
-          if (rc) return rc; }
-        { ProfScope p(m, PGMI_K_GEMM_FC2, 2.0 * M * F * D, 0);
-          rc = linear(m, m->g, m->g16, L.w2, L.w216, L.b2, m->x, m->x, nullptr, M, D, F, EPI_NONE);
-          if (rc) return rc; }
+        const bool kept = keep && m->keep_rows && l == c.layers - 1;
+        if ((rc = encoder_layer(m, m->layers[l], B, T, esm2_rotary(c.arch), kept ? keep : nullptr, n_keep, compacted))) return rc;
     }
     PGMI_HIP(hipGetLastError());
     return PGMI_OK;
@@ -230,6 +257,7 @@ extern "C" {
 int pgmi_token_logprobs(pgmi_model* m, const int32_t* tokens, int B, int T, float* out) {
     if (!m || !tokens || !out || B <= 0 || T <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
     if (m->cfg.arch == PGMI_ARCH_SAPROT) { set_error("SaProt models are scored with pgmi_saprot_token_logprobs / pgmi_saprot_group_logprobs"); return PGMI_EINVAL; }
+    if (m->cfg.arch == PGMI_ARCH_MULAN) { set_error("MULAN models are scored with pgmi_mulan_token_logprobs / pgmi_mulan_set_logprobs"); return PGMI_EINVAL; }
     if (T + 31 > m->max_rows) { set_error("T=%d exceeds workspace rows %d", T, m->max_rows); return PGMI_EINVAL; }
     int rc = check_tokens(tokens, B, T);
     if (rc) return rc;
@@ -248,6 +276,7 @@ int pgmi_token_logprobs(pgmi_model* m, const int32_t* tokens, int B, int T, floa
 int pgmi_masked_logprobs(pgmi_model* m, const int32_t* tokens, const int32_t* mask_pos, int B, int T, float* out) {
     if (!m || !tokens || !mask_pos || !out || B <= 0 || T <= 0) { set_error("bad argument"); return PGMI_EINVAL; }
     if (m->cfg.arch == PGMI_ARCH_SAPROT) { set_error("SaProt models are scored with pgmi_saprot_token_logprobs / pgmi_saprot_group_logprobs"); return PGMI_EINVAL; }
+    if (m->cfg.arch == PGMI_ARCH_MULAN) { set_error("MULAN models are scored with pgmi_mulan_token_logprobs / pgmi_mulan_set_logprobs"); return PGMI_EINVAL; }
     if (esmc_blocks(m->cfg.arch) && T + 31 > m->max_rows) { set_error("T=%d exceeds workspace rows %d", T, m->max_rows); return PGMI_EINVAL; }
     if (T > m->max_rows) { set_error("T=%d exceeds workspace rows %d", T, m->max_rows); return PGMI_EINVAL; }
     int rc = check_tokens(tokens, B, T);
@@ -280,6 +309,7 @@ int pgmi_assay_create(pgmi_model* m, const int32_t* wt_tokens, int n_tok, const 
     if (!m || !wt_tokens || n_tok <= 0 || P < 0 || (P > 0 && !positions) || window <= 0 || n_mut < 0) { set_error("bad argument"); return PGMI_EINVAL; }
     if (esmc_blocks(m->cfg.arch)) { set_error("ESM C / ESM3 assays run through pgmi_masked_logprobs (their window rule is not pgmi_optimal_window)"); return PGMI_EINVAL; }
     if (m->cfg.arch == PGMI_ARCH_SAPROT) { set_error("SaProt assays run through pgmi_saprot_group_logprobs (position sets, no window)"); return PGMI_EINVAL; }
+    if (m->cfg.arch == PGMI_ARCH_MULAN) { set_error("MULAN assays run through pgmi_mulan_set_logprobs (position sets, no window)"); return PGMI_EINVAL; }
     for (int i = 0; i < n_tok; ++i)
         if (wt_tokens[i] < 0 || wt_tokens[i] >= PGMI_VOCAB || wt_tokens[i] == PGMI_TOK_PAD) { set_error("wt token %d invalid at %d", wt_tokens[i], i); return PGMI_EINVAL; }
     const int T = std::min(n_tok, window);

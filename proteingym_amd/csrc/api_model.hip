@@ -30,7 +30,8 @@ int check_cfg(const pgmi_config* c) {
     if (c->abi_version != PGMI_ABI_VERSION) { set_error("ABI version mismatch: got %d, library is %d", c->abi_version, PGMI_ABI_VERSION); return PGMI_EINVAL; }
     if (c->arch != PGMI_ARCH_ESM1B && c->arch != PGMI_ARCH_ESM2 && c->arch != PGMI_ARCH_TRANCEPTION && c->arch != PGMI_ARCH_MSA &&
         c->arch != PGMI_ARCH_PROGEN2 && c->arch != PGMI_ARCH_GPT && c->arch != PGMI_ARCH_ESMC && c->arch != PGMI_ARCH_SAPROT &&
-        c->arch != PGMI_ARCH_POET && c->arch != PGMI_ARCH_PROGEN3 && c->arch != PGMI_ARCH_ESM3 && c->arch != PGMI_ARCH_ESMIF1) { set_error("unknown arch %d", c->arch); return PGMI_EINVAL; }
+        c->arch != PGMI_ARCH_POET && c->arch != PGMI_ARCH_PROGEN3 && c->arch != PGMI_ARCH_ESM3 && c->arch != PGMI_ARCH_ESMIF1 &&
+        c->arch != PGMI_ARCH_MULAN) { set_error("unknown arch %d", c->arch); return PGMI_EINVAL; }
     if (c->layers <= 0 || c->embed_dim <= 0 || c->heads <= 0 || c->ffn_dim <= 0) { set_error("non-positive model dimension"); return PGMI_EINVAL; }
     if (c->arch == PGMI_ARCH_ESMIF1) return if1_check(c, c->embed_dim);      // the encoder width is checked at creation
     if (esmc_blocks(c->arch)) {
@@ -50,7 +51,8 @@ int check_cfg(const pgmi_config* c) {
         // (api_progen2.hip)
         const bool pg2 = c->arch == PGMI_ARCH_PROGEN2;
         // causal decoder: ESM2's layout (RITA XL: head_dim 128)
-        const bool esm_layout = c->arch == PGMI_ARCH_ESM1B || c->arch == PGMI_ARCH_ESM2 || c->arch == PGMI_ARCH_GPT || c->arch == PGMI_ARCH_SAPROT;
+        const bool esm_layout = c->arch == PGMI_ARCH_ESM1B || c->arch == PGMI_ARCH_ESM2 || c->arch == PGMI_ARCH_GPT || c->arch == PGMI_ARCH_SAPROT ||
+                                c->arch == PGMI_ARCH_MULAN;
         const bool pg3 = c->arch == PGMI_ARCH_PROGEN3;        // what the causal attention runs: 64, 128 and ProGen2's padded 80 / 96 / 256
         if (pg3 && (c->embed_dim % c->heads || (dh != 64 && dh != 80 && dh != 96 && dh != 128 && dh != 256))) {
             set_error("unsupported head_dim %d (embed_dim %d / heads %d): ProGen3 runs head dims 64, 80, 96, 128 and 256", dh, c->embed_dim, c->heads);
@@ -89,6 +91,9 @@ int check_cfg(const pgmi_config* c) {
     } else if (c->arch == PGMI_ARCH_SAPROT) {
         if (c->vocab != PGMI_SAPROT_VOCAB) { set_error("SaProt vocab must be %d (5 specials + 21 x 21 residue tokens)", PGMI_SAPROT_VOCAB); return PGMI_EINVAL; }
         if (c->max_positions != 0) { set_error("SaProt has rotary positions: max_positions must be 0"); return PGMI_EINVAL; }
+    } else if (c->arch == PGMI_ARCH_MULAN) {
+        if (c->vocab != PGMI_VOCAB && c->vocab != PGMI_SAPROT_VOCAB) { set_error("MULAN vocab must be %d (ESM2's alphabet) or %d (SaProt's)", PGMI_VOCAB, PGMI_SAPROT_VOCAB); return PGMI_EINVAL; }
+        if (c->max_positions != 0) { set_error("MULAN has rotary positions: max_positions must be 0"); return PGMI_EINVAL; }
     } else if (c->arch == PGMI_ARCH_POET) {
         if (c->vocab <= PGMI_POET_TOK_MASK || c->vocab > kWave) { set_error("PoET vocab must be in [%d, 64], got %d", PGMI_POET_TOK_MASK + 1, c->vocab); return PGMI_EINVAL; }
         if (c->precision != PGMI_PREC_F16X3) { set_error("PoET is available in precision f16x3 only"); return PGMI_EINVAL; }
@@ -276,6 +281,7 @@ int64_t pgmi_weight_count(const pgmi_config* c) {
     if (c->arch == PGMI_ARCH_ESM3) return -1;     // the blob depends on v_heads: pgmi_esm3_weight_count
     if (c->arch == PGMI_ARCH_ESMIF1) return -1;   // the blob depends on the encoder width: pgmi_esmif1_weight_count
     if (c->arch == PGMI_ARCH_ESMC) return esmc_weight_count(c);
+    if (c->arch == PGMI_ARCH_MULAN) return -1;    // ESM2's blob and the adapter's: pgmi_mulan_weight_count
     if (c->arch == PGMI_ARCH_MSA) {
         const int64_t attn = 2 * D + 4 * (D * D + D);
         return V * D + (int64_t)(c->max_positions + 2) * D + 1024 * D + 2 * D +
@@ -303,6 +309,11 @@ int pgmi_model_create(const pgmi_config* cfg, const float* w, int64_t n_weights,
     if (cfg && cfg->arch == PGMI_ARCH_SAPROT) {
         if (out) *out = nullptr;
         set_error("SaProt models are created with pgmi_saprot_model_create (it takes the tokenizer's <mask> id)");
+        return PGMI_EINVAL;
+    }
+    if (cfg && cfg->arch == PGMI_ARCH_MULAN) {
+        if (out) *out = nullptr;
+        set_error("MULAN models are created with pgmi_mulan_model_create (it takes the <mask> id and the vocabulary's groups)");
         return PGMI_EINVAL;
     }
     if (cfg && cfg->arch == PGMI_ARCH_POET) {
@@ -335,7 +346,8 @@ namespace pgmi {
 // Workspace of max_rows token rows, shared by every forward of the model.
 static int alloc_workspace(pgmi_model* m) {
     const pgmi_config& c = m->cfg;
-    const size_t R = m->max_rows, D = c.embed_dim, F = c.ffn_dim, V = c.vocab, Da = m->Da;
+    const size_t R = m->max_rows, D = c.embed_dim, V = c.vocab, Da = m->Da;
+    const size_t F = c.arch == PGMI_ARCH_MULAN ? std::max<size_t>(c.ffn_dim, 4 * D) : c.ffn_dim;   // MULAN's adapter layer: 4 D
     const size_t Dw = std::max(D, Da);                   // h / h16 hold LN output [.,D] and attention context [.,Da]
     const bool f32mode = c.precision == PGMI_PREC_FP32;
     int rc = PGMI_OK;
@@ -377,7 +389,7 @@ static int alloc_workspace(pgmi_model* m) {
 }
 
 // pgmi_model_create, pgmi_pg2_model_create and pgmi_gpt_model_create; arch_arg is ProGen2's rotary_dim or the causal decoder's
-// pos_kind, SaProt's <mask> id, PoET's final_norm, ESM3's v_heads, ESM-IF1's encoder width (0 for every other arch); pg3: ProGen3's parameters
+// pos_kind, SaProt's and MULAN's <mask> id, PoET's final_norm, ESM3's v_heads, ESM-IF1's encoder width (0 for every other arch); pg3: ProGen3's parameters
 int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int device, pgmi_model** out, int arch_arg,
                  const pgmi_pg3_params* pg3) {
     if (!out) { set_error("null out"); return PGMI_EINVAL; }
@@ -391,7 +403,8 @@ int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int 
                          : cfg->arch == PGMI_ARCH_PROGEN3 ? pg3_weight_count(cfg, pg3)
                          : cfg->arch == PGMI_ARCH_POET ? poet_weight_count(cfg, arch_arg)
                          : cfg->arch == PGMI_ARCH_ESM3 ? esm3_weight_count(cfg, arch_arg)
-                         : cfg->arch == PGMI_ARCH_ESMIF1 ? if1_weight_count(cfg, arch_arg) : pgmi_weight_count(cfg);
+                         : cfg->arch == PGMI_ARCH_ESMIF1 ? if1_weight_count(cfg, arch_arg)
+                         : cfg->arch == PGMI_ARCH_MULAN ? mulan_weight_count(cfg) : pgmi_weight_count(cfg);
     if (need < 0) { set_error("causal decoder pos_kind %d: must be PGMI_GPT_POS_ROTARY or PGMI_GPT_POS_LEARNED", arch_arg); return PGMI_EINVAL; }
     if (!w || n_weights != need) {
         set_error("weight blob has %lld elements, config needs %lld", (long long)n_weights, (long long)need);
@@ -422,6 +435,7 @@ int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int 
         case PGMI_ARCH_GPT: rc = create_gpt(m, cfg, w, n_weights, arch_arg); break;
         case PGMI_ARCH_ESMC: rc = create_esmc(m, cfg, w, n_weights); break;
         case PGMI_ARCH_SAPROT: rc = create_saprot(m, cfg, w, n_weights, arch_arg); break;
+        case PGMI_ARCH_MULAN: rc = create_mulan(m, cfg, w, n_weights, arch_arg); break;
         case PGMI_ARCH_POET: rc = create_poet(m, cfg, w, n_weights, arch_arg); break;
         case PGMI_ARCH_PROGEN3: rc = create_progen3(m, cfg, w, n_weights, pg3); break;
         case PGMI_ARCH_ESM3: rc = create_esm3(m, cfg, w, n_weights, arch_arg); break;

@@ -177,6 +177,16 @@ void launch_pppl_sum(const float* terms, const int64_t* rp, const int32_t* sid, 
 // set) with the masked ids, and keep[e - set_off[s0]] = the flat row of entry e
 void launch_saprot_rows(const int32_t* wt, const int32_t* set_off, const int32_t* set_pos, int s0, int bc, int T, int first, int groups,
                         int width, int32_t* tokens, int32_t* keep, hipStream_t s);
+// MULAN (api_mulan.hip): per row (b, t) of the position sets [s0, s0 + bc) the adapter's input y[row][D] = bias + sum_k a_k W[:, k]
+// (W [D][7], fp32, k ascending), the row's seven values a chosen on the fly: 4 for t = 0, t = T - 1 and plddt[t] <= 70, -4 where t is
+// in the set (this wins), else angles[t][7].  wt != nullptr: also tokens[row] = wt[t] or mask_id in the set, and
+// keep[e - set_off[s0]] = the flat row of entry e (launch_saprot_rows' outputs); nullptr: the tokens are the caller's
+void launch_mulan_rows(const int32_t* wt, const int32_t* set_off, const int32_t* set_pos, int s0, int bc, int T, int mask_id,
+                       const float* angles, const float* plddt, const float* W, const float* bias, int D, int32_t* tokens, int32_t* keep,
+                       float* y, hipStream_t s);
+// MULAN: x[row] = (E[tokens[row]] + st[row]), zero for <mask> under token dropout, * 0.88 / scale[b] (launch_embed's order); pad rows 0
+void launch_mulan_embed(const int32_t* tokens, const float* scale, const float* E, const float* st, int token_dropout, int rows, int T,
+                        int D, float* x, hipStream_t s, int mask_id);
 // per row of h [rows][D] against E [V][D] (V <= 512), in double: full [rows][V] = log-softmax (nullable); group [rows][groups] =
 // lse(logits[first + g width .. + width)) - lse(row) (nullable)
 int launch_group_logsoftmax(const float* h, const float* E, const float* bias, int rows, int D, int V, int first, int groups, int width,

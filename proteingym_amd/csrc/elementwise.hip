@@ -780,6 +780,83 @@ void launch_saprot_rows(const int32_t* wt, const int32_t* set_off, const int32_t
                        tokens, keep);
 }
 
+// ---- MULAN (api_mulan.hip) ---------------------------------------------------------------------------------------------------
+// The structure adapter's input rows for the position sets [s0, s0 + bc) (mulan/dataset.py:306-314, compute_fitness.py:117-126).  One
+// wave per row (b, t): the row looks itself up in its set by bisection, picks its seven values -- 4 for the two end rows and for
+// plddt <= 70, -4 in the set, else the stored angles -- and every lane writes y[row][d] = bias[d] + sum_k a_k W[d][k] for its d, in
+// fp32, k ascending.  With wt, lane 0 also writes the token (<mask> in the set) and, for a row of the set, its keep entry: every
+// entry of the chunk belongs to exactly one row, so keep is written once.
+__global__ __launch_bounds__(256) void mulan_rows_kernel(const int32_t* __restrict__ wt, const int32_t* __restrict__ set_off,
+                                                         const int32_t* __restrict__ set_pos, int s0, int bc, int T, int mask_id,
+                                                         const float* __restrict__ angles, const float* __restrict__ plddt,
+                                                         const float* __restrict__ W, const float* __restrict__ bias, int D,
+                                                         int32_t* __restrict__ tokens, int32_t* __restrict__ keep, float* __restrict__ y) {
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= (int64_t)bc * T) return;
+    const int b = (int)(row / T), t = (int)(row % T);
+    const int e0 = set_off[s0], lo0 = set_off[s0 + b], hi0 = set_off[s0 + b + 1];
+    int lo = lo0, hi = hi0;                                  // first entry with set_pos >= t
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (set_pos[mid] < t) lo = mid + 1; else hi = mid;
+    }
+    const bool in_set = lo < hi0 && set_pos[lo] == t;
+    float a[7];
+    const bool padded = t == 0 || t == T - 1 || plddt[t] <= 70.0f;
+#pragma unroll
+    for (int k = 0; k < 7; ++k) a[k] = in_set ? -4.0f : padded ? 4.0f : angles[(size_t)t * 7 + k];
+    if (wt && lane == 0) {
+        tokens[row] = in_set ? mask_id : wt[t];
+        if (in_set) keep[lo - e0] = (int32_t)row;
+    }
+    float* yo = y + (size_t)row * D;
+    for (int d = lane; d < D; d += 64) {
+        float acc = bias[d];
+#pragma unroll
+        for (int k = 0; k < 7; ++k) acc = fmaf(a[k], W[(size_t)d * 7 + k], acc);
+        yo[d] = acc;
+    }
+}
+void launch_mulan_rows(const int32_t* wt, const int32_t* set_off, const int32_t* set_pos, int s0, int bc, int T, int mask_id,
+                       const float* angles, const float* plddt, const float* W, const float* bias, int D, int32_t* tokens, int32_t* keep,
+                       float* y, hipStream_t s) {
+    const int64_t rows = (int64_t)bc * T;
+    hipLaunchKernelGGL(mulan_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, wt, set_off, set_pos, s0, bc, T, mask_id,
+                       angles, plddt, W, bias, D, tokens, keep, y);
+}
+
+// x = (E[tok] + st[row]), zero for <mask> under token dropout, times 0.88 / denom[b] in embed_kernel's order (model_utils.py:156-176);
+// pad rows -> 0.  D % 4 == 0.
+__global__ void mulan_embed_kernel(const int32_t* __restrict__ tokens, const float* __restrict__ denom, const float* __restrict__ E,
+                                   const float* __restrict__ st, int token_dropout, int mask_id, int rows, int T, int D,
+                                   float* __restrict__ x) {
+    const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const int tok = tokens[row];
+    const float dn = denom[row / T];
+    const f32x4* e = reinterpret_cast<const f32x4*>(E + (size_t)tok * D);
+    const f32x4* sr = reinterpret_cast<const f32x4*>(st + (size_t)row * D);
+    f32x4* xo = reinterpret_cast<f32x4*>(x + (size_t)row * D);
+    const bool zero = tok == PGMI_TOK_PAD || (token_dropout && tok == mask_id);
+    for (int i = lane; i < D / 4; i += 64) {
+        f32x4 v = e[i];
+        const f32x4 sv = sr[i];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            v[c] += sv[c];
+            if (token_dropout) v[c] = (v[c] * 0.88f) / dn;
+        }
+        xo[i] = zero ? f32x4{0.f, 0.f, 0.f, 0.f} : v;
+    }
+}
+void launch_mulan_embed(const int32_t* tokens, const float* denom, const float* E, const float* st, int token_dropout, int rows, int T,
+                        int D, float* x, hipStream_t s, int mask_id) {
+    hipLaunchKernelGGL(mulan_embed_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, tokens, denom, E, st, token_dropout, mask_id, rows, T,
+                       D, x);
+}
+
 // Vocabulary projection + grouped log-softmax (compute_fitness.py:42-53).  One wave per row of h [rows][D] (D % 4 == 0), V <= 512 logits
 // against the tied table E [V][D]:
 //   full  [row][V]      (nullable) = logit - lse(row)                                    the log-softmax of all V columns

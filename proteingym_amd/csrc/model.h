@@ -23,6 +23,8 @@
 //   api_esm3.hip         ESM3 weights (ESM C's blocks, the folded multi-track embedding, block 0's geometric attention branch), the
 //                        bound window structure, geom_branch (run_encoder calls it after block 0's attention); it runs on run_encoder
 //   api_saprot.hip       SaProt: ESM2's weights and encoder with a 446-token vocabulary; position-set rows and the grouped log-softmax head
+//   api_mulan.hip        MULAN: ESM2's (or SaProt's) weights and encoder behind a structure adapter -- Linear(7 -> D) over per-residue
+//                        angle rows, one encoder layer without rotary, LayerNorm -- added to the word embeddings; position-set rows
 //   api_eve.hip          EVE / DeepSequence: its own handle (pgmi_eve), blob walk, encoder, one ELBO sample, noise seam, the sampling loop
 //   api_mpnn.hip         ProteinMPNN: its own handle (pgmi_mpnn), blob walk, the per-structure pass (graph, features, encoder, hoisted
 //                        decoder tables), the per-batch decoder and head
@@ -65,6 +67,7 @@ struct W16 {
 struct Layer {
     float *ln1_w, *ln1_b, *wqkv, *bqkv, *wo, *bo, *ln2_w, *ln2_b, *w1, *b1, *w2, *b2;
     W16 wqkv16, wo16, w116, w216;
+    int ffn = 0;                  // the layer's own FC1 / FC2 width where it is not cfg.ffn_dim (MULAN's adapter: 4 D); 0: cfg.ffn_dim
     float* conv = nullptr;        // Tranception: [3][4][64][8] right-aligned 7-tap filters + bias (attention_f16.hip)
     // MSA Transformer: ln1/wqkv/wo = tied row attention, c_* = column attention, ln2/w1/w2 = feed forward
     float *c_ln_w = nullptr, *c_ln_b = nullptr, *c_bqkv = nullptr, *c_bo = nullptr;
@@ -194,6 +197,14 @@ struct pgmi_model {
     size_t e3_cap = 0;
     int e3_T = 0;
     bool e3_framed = false;
+    // MULAN (api_mulan.hip): mu_groups = 0 (ESM2's 33 tokens) or 21 (SaProt's layout); the adapter -- MLP [D][7] and bias, one layer, its
+    // final LayerNorm --; the bound chunk (pgmi_mulan_set_structure): raw angle rows [mu_T][7] and pLDDT [mu_T] (mu_T = 0: none bound)
+    int mu_groups = 0;
+    float *mu_w = nullptr, *mu_b = nullptr, *mu_lna_w = nullptr, *mu_lna_b = nullptr;
+    Layer mu_layer;
+    float *mu_angles = nullptr, *mu_plddt = nullptr;
+    size_t mu_angles_cap = 0, mu_plddt_cap = 0;
+    int mu_T = 0;
     // 16-bit activations: h16_plane = R*D and g16_plane = R*F elements (f16x3: K-interleaved hi | lo rows, 2 halfs per element; bf16: 1
     // half).  They are allocation sizes; no launcher takes them as a stride.
     unsigned short *h16 = nullptr, *g16 = nullptr;
@@ -274,9 +285,12 @@ int dev_upload(std::vector<void*>& pool, T** p, const T* host, size_t n) {
     return PGMI_OK;
 }
 
+// Scopes may nest (MULAN's adapter layer runs inside run_encoder's embed scope) and an inner scope may grow m->events: a scope keeps
+// the INDEX of its event, never a pointer into the vector.
 struct ProfScope {
     pgmi_model* m;
-    ProfEvent* ev = nullptr;
+    bool on = false;
+    size_t idx = 0;
     ProfScope(pgmi_model* m_, int cls, double flops, double bytes) : m(m_) {
         if (!m->prof) return;
         if (m->events_used == m->events.size()) {
@@ -284,15 +298,17 @@ struct ProfScope {
             if (hipEventCreate(&e.start) != hipSuccess || hipEventCreate(&e.stop) != hipSuccess) return;
             m->events.push_back(e);
         }
-        ev = &m->events[m->events_used++];
-        ev->cls = cls;
+        idx = m->events_used++;
+        on = true;
+        m->events[idx].cls = cls;
         m->prof_n[cls] += 1;
         m->prof_flops[cls] += flops;
         m->prof_bytes[cls] += bytes;
-        hipEventRecord(ev->start, m->stream);
+        hipEventRecord(m->events[idx].start, m->stream);
     }
+    ProfScope(const ProfScope&) = delete;
     ~ProfScope() {
-        if (ev) hipEventRecord(ev->stop, m->stream);
+        if (on) hipEventRecord(m->events[idx].stop, m->stream);
     }
 };
 
@@ -356,6 +372,12 @@ int reset_pad_keys(pgmi_model* m, int B, int T);
 int model_create(const pgmi_config* cfg, const float* w, int64_t n_weights, int device, pgmi_model** out, int arch_arg,
                  const pgmi_pg3_params* pg3 = nullptr);
 // api_esm.hip
+struct BlobCursor;
+void walk_esm(BlobCursor& c);                       // the ESM-1b / ESM2 blob into m; the cursor stays at its end
+void walk_esm_layer(BlobCursor& c, Layer* L, size_t F);   // one layer of it, FC1 / FC2 of width F
+// one encoder layer on the B T rows of m->x (run_encoder's loop body; MULAN's adapter with rotary off)
+int encoder_layer(pgmi_model* m, const Layer& L, int B, int T, bool rotary, const int32_t* keep = nullptr, int n_keep = 0,
+                  bool* compacted = nullptr);
 int create_esm(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights);
 int ensure_rotary(pgmi_model* m, int T);            // ESM2 / ESM C: tables for at least T positions
 int upload_rotate_half(pgmi_model* m, int n);       // ESM2's rotary tables for positions 0..n-1 (rotate_half_slot layout)
@@ -432,12 +454,16 @@ int esm3_embed(pgmi_model* m, int B, int T);                        // m->tokens
 int geom_branch(pgmi_model* m, const Layer& L, int B, int T);       // x += out_proj(geom_attn(s_norm(x))) / s on the M = B T rows of m->x
 // api_saprot.hip
 int create_saprot(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights, int mask_id);
+// api_mulan.hip
+int64_t mulan_weight_count(const pgmi_config* c);
+int create_mulan(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights, int mask_id);
+int mulan_embed(pgmi_model* m, int B, int T);       // the adapter on its input rows in m->x, then m->x = the embedding of m->tokens
 // api_msa.hip
 int create_msa(pgmi_model* m, const pgmi_config* cfg, const float* w, int64_t n_weights);
 int run_msa(pgmi_model* m, int R, int C, int keep_col = -1, bool* compacted = nullptr);
 
-// ESM2's rotate-half rotary on q and k (SaProt is ESM2 with another vocabulary)
-inline bool esm2_rotary(int arch) { return arch == PGMI_ARCH_ESM2 || arch == PGMI_ARCH_SAPROT; }
+// ESM2's rotate-half rotary on q and k (SaProt is ESM2 with another vocabulary; MULAN's main stack is either)
+inline bool esm2_rotary(int arch) { return arch == PGMI_ARCH_ESM2 || arch == PGMI_ARCH_SAPROT || arch == PGMI_ARCH_MULAN; }
 // ESM C's blocks (q / k LayerNorm, SwiGLU, scaled residual, 64-column head): ESM C itself and ESM3
 inline bool esmc_blocks(int arch) { return arch == PGMI_ARCH_ESMC || arch == PGMI_ARCH_ESM3; }
 

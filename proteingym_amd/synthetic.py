@@ -561,6 +561,44 @@ def saprot_state_dict(cfg: dict, seed: int, embed_std: float = 0.15) -> Dict[str
     return sd
 
 
+def mulan_config(embed_dim: int = 320, heads: int = 20, layers: int = 6, ffn_dim: int = 0, use_foldseek: bool = False) -> dict:
+    """A MULAN configuration (MULAN-small by default: ESM2 8M's shape): ESM2's alphabet (<mask> 32), or SaProt's 446 tokens (<mask> 4,
+    21 amino-acid groups) with use_foldseek; token dropout, rotary positions, no LayerNorm before the encoder."""
+    return dict(arch=_lib.ARCH_MULAN, layers=layers, embed_dim=embed_dim, heads=heads, ffn_dim=ffn_dim or 4 * embed_dim,
+                vocab=446 if use_foldseek else 33, max_positions=0, token_dropout=1, emb_layer_norm_before=0,
+                mask_token_id=4 if use_foldseek else 32, groups=21 if use_foldseek else 0)
+
+
+def mulan_state_dict(cfg: dict, seed: int, embed_std: float = 0.15, adapter_scale: float = 1.0) -> Dict[str, np.ndarray]:
+    """Seeded random MULAN weights under StructEsmForMaskedLM's keys: saprot_state_dict's main stack, then the structure adapter --
+    MLP [D,7], one layer whose feed-forward width is 4 D whatever the main stack's, and its final LayerNorm, whose gain and bias are
+    multiplied by adapter_scale (0: the adapter adds exactly nothing)."""
+    sd = saprot_state_dict(cfg, seed, embed_std)
+    normal = _causal_normal(seed + 7919)
+    D = cfg["embed_dim"]
+    p = "esm.embeddings.struct_embeddings."
+
+    def ln(k, scale=1.0, spread=0.1):
+        sd[k + ".weight"] = ((1.0 + normal((D,), spread)) * scale).astype(np.float32)
+        sd[k + ".bias"] = (normal((D,), 0.02) * scale).astype(np.float32)
+
+    def linear(k, n_out, n_in):
+        sd[k + ".weight"] = normal((n_out, n_in), n_in ** -0.5)
+        sd[k + ".bias"] = normal((n_out,), 0.02)
+    linear(p + "MLP", D, 7)
+    q = p + "encoder.layer.0."
+    ln(q + "attention.LayerNorm")
+    for n in ("query", "key", "value"):
+        linear(q + "attention.self." + n, D, D)
+    linear(q + "attention.output.dense", D, D)
+    ln(q + "LayerNorm")
+    linear(q + "intermediate.dense", 4 * D, D)
+    linear(q + "output.dense", D, 4 * D)
+    # the adapter's output is a LayerNorm row (unit variance times the gain) added to embeddings of std embed_std
+    ln(p + "encoder.emb_layer_norm_after", embed_std * adapter_scale)
+    return sd
+
+
 def esm3_config(embed_dim: int = 1536, layers: int = 48, v_heads: int = 256) -> dict:
     """An ESM3 configuration (esm/pretrained.py:101-117 by default): ESM C's block shape plus the geometric attention's v_heads."""
     return dict(esmc_config(embed_dim, layers), v_heads=v_heads)
