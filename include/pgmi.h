@@ -1151,6 +1151,61 @@ int pgmi_esm_residue_rows(pgmi_model* esm, const int32_t* tokens, int T, float* 
 int pgmi_op_egnn_message(int device, const pgmi_protssn_config* cfg, const float* weights, int64_t n_weights, const float* pos, int L,
                          int n_edges, const int32_t* centre, const int32_t* neighbour, const float* edge_attr, const float* x, float* out);
 
+/* ---- VespaG (a two-Linear head over ESM2-3B's residue rows, every protein of a FASTA; its own handle and config; additions only, the
+ * ABI version is unchanged) ---------------------------------------------------------------------------------------------------------
+ * Replaces the model side of proteingym/baselines/vespag/vespag: the embedder (data/embeddings.py: last_hidden_state[1 : L + 1] of one
+ * unmasked forward per protein) and FNN([256], 2560, 20) (models/fnn.py, models/utils.py construct_fnn: Linear, Dropout -- identity in
+ * eval --, LeakyReLU(0.01), Linear) with mask_non_mutations (utils/utils.py).  Tokenisation, mutations and the score are host work
+ * (proteingym_amd/vespag.py); DESIGN.md 4.6s.
+ * A library is what pgmi_pppl_create takes: tokens u8, concatenated, and seq_off i64 [n_seq + 1] with seq_off[0] = 0; every sequence
+ *   <cls> + L_i >= 1 residues + <eos>.  Packed rows: [sum L_i][D] in the caller's order, sequence n at row seq_off[n] - 2 n.
+ * pgmi_esm_packed_rows: emb_layer_norm_after of every residue row of the library through an ESM2 model.  Sequences run in descending
+ *   length (stable), in chunks of max(1, cap / roundup(T, 32)) sequences, T = the chunk's longest, shorter ones <pad>-filled; cap =
+ *   row_cap when 0 < row_cap < the workspace rows, else the workspace rows.  The last layer's row-local stages run on the residue rows
+ *   only.  rows_host (nullable) f32 [sum L_i][D].  stats (nullable) i64 [3] = chunks, residue tokens + 2 per sequence, tokens with pads.
+ *   The fp16 range flag is read on the device after every chunk (PGMI_EOVERFLOW).
+ * pgmi_op_packed_rows_plan: that plan alone, on the host (no device is touched): order i32 [n_seq] = the sequences as they run,
+ *   chunk_end i32 [n_seq] = the end (in `order`) of chunk i, *n_chunks, packed_off i64 [n_seq + 1] = the packed row of sequence n.
+ * Weight blob (fp32, nn.Linear [out, in]): net.0.weight [hidden][input_dim], net.0.bias [hidden], net.3.weight [20][hidden],
+ *   net.3.bias [20].
+ * pgmi_vespag_create: esm (nullable) is an ESM2 model of width input_dim and the config's precision; the handle borrows it and its
+ *   stream (destroy the handle first).  Without it the handle has a stream of its own and runs pgmi_vespag_head only.
+ * pgmi_vespag_profile_model: the handle's profiling view (owned by the handle).  Classes: PGMI_K_LAYERNORM = the split of the rows
+ *   (f16x3), PGMI_K_GEMM_FC1 = the first Linear, PGMI_K_HEAD = the row kernel.  The encoder is timed on the ESM2 model's own profile,
+ *   where PGMI_K_SCORE = the scatter of a chunk's rows to their packed place.
+ * wt_cols i32 [rows]: the column (0 .. 19, AMINO_ACIDS = "ACDEFGHIKLMNPQRSTVWY") of each row's wild type, which gets exact 0.0
+ *   (mask_non_mutations); -1 leaves the row as it is.
+ * pgmi_vespag_landscapes: packed rows of the library, then the head, without leaving the device: y_host f32 [sum L_i][20];
+ *   rows_host (nullable) f32 [sum L_i][input_dim].
+ * pgmi_vespag_head: the head on pre-computed rows_host f32 [R][input_dim] -> y_host f32 [R][20]; bit-equal to pgmi_vespag_landscapes
+ *   on the same rows.  The rows come from a file, so every one of the R x input_dim values is read on the host before the upload (one
+ *   serial pass) and a non-finite one is PGMI_EINVAL; the packed route checks its rows on the device instead and refuses one the same way
+ *   in precision fp32 (f16x3: PGMI_EOVERFLOW).  Both entries read the [R][20] result on the host: a non-finite value is PGMI_EOVERFLOW.
+ * pgmi_op_vespag_head: the head alone on host pointers (W1 [hidden][input_dim], b1, W2 [20][hidden], b2).
+ * PGMI_EINVAL before any device work: input_dim or hidden not a multiple of 32 (32 .. 8192, 32 .. 768), out != 20, a non-ESM2 model,
+ *   a width or precision that differs, a sequence below 3 tokens, a token id outside the alphabet or <pad>, the longest sequence + 31
+ *   above the workspace rows, a wt_cols value outside -1 .. 19, a non-finite row. */
+typedef struct pgmi_vespag_config {
+    int32_t abi_version;                          /* = PGMI_ABI_VERSION */
+    int32_t input_dim, hidden, out;               /* 2560, 256, 20 */
+    int32_t precision;                            /* PGMI_PREC_F16X3 or PGMI_PREC_FP32 */
+    float negative_slope;                         /* 0.01 */
+} pgmi_vespag_config;
+typedef struct pgmi_vespag pgmi_vespag;
+int pgmi_esm_packed_rows(pgmi_model* esm, const uint8_t* tokens, const int64_t* seq_off, int64_t n_seq, int row_cap, float* rows_host,
+                         int64_t* stats);
+int pgmi_op_packed_rows_plan(const int64_t* seq_off, int64_t n_seq, int row_cap, int32_t* order, int32_t* chunk_end, int32_t* n_chunks,
+                             int64_t* packed_off);
+int64_t pgmi_vespag_weight_count(const pgmi_vespag_config* cfg);
+int pgmi_vespag_create(const pgmi_vespag_config* cfg, const float* weights, int64_t n_weights, pgmi_model* esm, int device, pgmi_vespag** out);
+void pgmi_vespag_destroy(pgmi_vespag* m);
+pgmi_model* pgmi_vespag_profile_model(pgmi_vespag* m);
+int pgmi_vespag_landscapes(pgmi_vespag* m, const uint8_t* tokens, const int64_t* seq_off, int64_t n_seq, const int32_t* wt_cols, float* y_host,
+                           float* rows_host);
+int pgmi_vespag_head(pgmi_vespag* m, const float* rows_host, const int32_t* wt_cols, int64_t R, float* y_host);
+int pgmi_op_vespag_head(int device, int precision, const float* rows, const float* W1, const float* b1, const float* W2, const float* b2,
+                        const int32_t* wt_cols, int R, int input_dim, int hidden, float slope, float* y);
+
 /* ---- MSA Transformer (arch PGMI_ARCH_MSA; vocab 33, head_dim 64, precision f16x3) --------------------
  * Replaces MSATransformer.forward (proteingym/baselines/esm/esm/model/msa_transformer.py:146-205; tied
  * row attention esm/axial_attention.py:33-168, column attention :171-297) and the masked-marginals loop

@@ -193,6 +193,16 @@ SIGNATURES = [
     ("pgmi_protssn_forward", C.c_int, [C.c_void_p, _f32p, _f32p, _f32p]),
     ("pgmi_esm_residue_rows", C.c_int, [C.c_void_p, _i32p, C.c_int, _f32p]),
     ("pgmi_op_egnn_message", C.c_int, [C.c_int, C.c_void_p, _f32p, C.c_int64, _f32p, C.c_int, C.c_int, _i32p, _i32p, _f32p, _f32p, _f32p]),
+    ("pgmi_esm_packed_rows", C.c_int, [C.c_void_p, _u8p, _i64p, C.c_int64, C.c_int, _f32p, _i64p]),
+    ("pgmi_op_packed_rows_plan", C.c_int, [_i64p, C.c_int64, C.c_int, _i32p, _i32p, _i32p, _i64p]),
+    ("pgmi_vespag_weight_count", C.c_int64, [C.c_void_p]),
+    ("pgmi_vespag_create", C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    ("pgmi_vespag_destroy", None, [C.c_void_p]),
+    ("pgmi_vespag_profile_model", C.c_void_p, [C.c_void_p]),
+    ("pgmi_vespag_landscapes", C.c_int, [C.c_void_p, _u8p, _i64p, C.c_int64, _i32p, _f32p, _f32p]),
+    ("pgmi_vespag_head", C.c_int, [C.c_void_p, _f32p, _i32p, C.c_int64, _f32p]),
+    ("pgmi_op_vespag_head", C.c_int, [C.c_int, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p, _i32p, C.c_int, C.c_int, C.c_int, C.c_float,
+                                      _f32p]),
     ("pgmi_bench_gemm", C.c_int, [C.c_int] * 9 + [_f64p]),
     ("pgmi_bench_gemm_ab", C.c_int, [C.c_int] * 7 + [_i32p, C.c_int, C.c_int, C.c_int, _f64p]),
     ("pgmi_op_attention", C.c_int, [C.c_int, C.c_int, _f32p, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),
@@ -324,7 +334,7 @@ class _ProfileView:
 
 
 class SideHandle:
-    """A model with a handle of its own (EVE, ProteinMPNN, UniRep, S2F, S3F, CARP, ProtSSN) behind the entries
+    """A model with a handle of its own (EVE, ProteinMPNN, UniRep, S2F, S3F, CARP, ProtSSN, VespaG) behind the entries
     pgmi_<PREFIX>_weight_count / _create / _destroy / _profile_model.  _create checks the blob size against the library's count and
     creates the handle; `before_device` are the arguments the create entry takes between the blob and the device (S2F / S3F: the ESM2
     handle).  NAME starts the blob size message."""

@@ -319,6 +319,13 @@ void launch_egnn_aggregate(const float* x, const float* msg, const int32_t* off,
 void launch_egnn_silu_rows(const float* t, int rows, int F, float* out, hipStream_t s);
 void launch_egnn_head(const float* x, const float* W, const float* bias, int rows, int D, float* lp, hipStream_t s);
 
+// ---- vespag.hip (VespaG: the packed-row scatter and the head's row kernel; the kernels are described there) ---------------------
+// out[dst_row[i], :] = src[i, :], i < n (D % 4 == 0); *nonfinite |= 1 when a value is NaN / inf (nullable)
+void launch_packed_scatter(const float* src, const int32_t* dst_row, int n, int D, float* out, int32_t* nonfinite, hipStream_t s);
+// y [rows][20] = LeakyReLU(h [rows][H], slope) W2^T + b2 with exact 0.0 at column wt_col[row] (-1: none); W2 [20][H], H <= 768
+void launch_vespag_head(const float* h, const float* W2, const float* b2, const int32_t* wt_col, int rows, int H, float slope, float* y,
+                        hipStream_t s);
+
 // ---- mlstm.hip (UniRep's mLSTM step around the two GEMMs; the kernels are described there) -------------------------------------
 // m = Tmx[tok[row * tok_stride]] * g1 [rows][Hp] -> the second product's operand: split rows m16, or fp32 m32 (exactly one)
 void launch_mlstm_m(const float* g1, const float* Tmx, const int32_t* tok, int tok_stride, int rows, int Hp, unsigned short* m16,

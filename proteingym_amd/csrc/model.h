@@ -32,7 +32,10 @@
 //                        rows / token log-probs / sequence log-likelihoods, the convolution's and the row kernel's op entries
 //   api_protssn.hip      ProtSSN: its own handle (pgmi_protssn), blob walk, the graph of one structure, the EGNN forward in edge chunks
 //                        (egnn.hip around the existing GEMMs), the ESM2 residue rows that feed it, the message op entry
-//   side handles         what the handles outside pgmi_model (pgmi_eve, pgmi_mpnn, pgmi_unirep, pgmi_s2f, pgmi_carp, pgmi_protssn; pgmi_s3f
+//   api_vespag.hip       VespaG: the packed residue rows of a library of sequences through an ESM2 model (length-sorted chunks, the residue
+//                        rows as run_encoder's keep list, the scatter to the caller's order), its own handle (pgmi_vespag), blob walk,
+//                        the head on packed rows (vespag.hip after one GEMM), the head's op entry
+//   side handles         what the handles outside pgmi_model (pgmi_eve, pgmi_mpnn, pgmi_unirep, pgmi_s2f, pgmi_carp, pgmi_protssn, pgmi_vespag; pgmi_s3f
 //                        holds two pgmi_s2f) share, in api_model.hip and below: side_open (blob, device and stream of a create),
 //                        BlobCursor, linear(), DevBuf / reserve_all (grow-only workspace), side_sync, overflow_error, side_release
 //   api_msa.hip          MSA Transformer weights and forward (tied row attention, column attention)
