@@ -1206,6 +1206,73 @@ int pgmi_vespag_head(pgmi_vespag* m, const float* rows_host, const int32_t* wt_c
 int pgmi_op_vespag_head(int device, int precision, const float* rows, const float* W1, const float* b1, const float* W2, const float* b2,
                         const int32_t* wt_cols, int R, int input_dim, int hidden, float slope, float* y);
 
+/* ---- ProSST structure quantizer (one local subgraph per residue through a GVP-GNN, k-means tokens; its own handle, fp32) -----------
+ * Replaces PdbQuantizer's model side (proteingym/baselines/prosst/prosst/structure/{quantizer.py, encoder/gvp.py, encoder/layer.py};
+ * venusrem/structure is the same code): generate_graph's features, generate_pos_subgraph(pure_subgraph = True, interval 1),
+ * AutoGraphEncoder.get_embedding in eval mode, scatter_mean, F.normalize and KMeans.predict.  DESIGN.md 4.6t has the restatement, the
+ * stand-ins and the sharing.  The ProSST transformer itself is not computed: its code is not in the reference tree.
+ *
+ * Weight blob: fp32, each tensor flattened row-major; a GVP is wh.weight, ws.weight, ws.bias, then (with vector outputs) wv.weight
+ * (vector_gate = False: no wsv):
+ *   W_v.0.scalar_norm.{weight, bias} [20]; W_v.1 = GVP (20, 3) -> (256, 32), h = 32;
+ *   W_e.0.scalar_norm.{weight, bias} [32]; W_e.1 = GVP (32, 1) -> (64, 2), h = 2;
+ *   layers.{l}: conv.message_func.0 = GVP (576, 66) -> (256, 32), h = 66; .1, .2 = GVP (256, 32) -> (256, 32), h = 32;
+ *     norm.0.scalar_norm.{weight, bias}, norm.1.scalar_norm.{weight, bias} [256];
+ *     ff_func.0 = GVP (256, 32) -> (1024, 64), h = 64; ff_func.1 = GVP (1024, 64) -> (256, 32), h = 64;
+ *   W_out.0.scalar_norm.{weight, bias} [256]; W_out.1 = GVP (256, 32) -> (256, 0), h = 32.
+ * Limits: node (256, 32), edge (64, 2), at most 8 layers, max_nodes <= 40, 1 <= L <= 8192 and L != 3 (the reference's torch.cross
+ * without dim runs over the residue axis there), K <= 8192 centres of width 256. */
+typedef struct pgmi_prosst_config {
+    int32_t abi_version;                          /* = PGMI_ABI_VERSION */
+    int32_t node_s, node_v, edge_s, edge_v;       /* = 256, 32, 64, 2 */
+    int32_t layers;                               /* 6 */
+    int32_t max_nodes;                            /* 40: nodes kept of a subgraph with more than `threshold` candidates */
+    int32_t threshold;                            /* 30 */
+    float radius;                                 /* 10.0 */
+} pgmi_prosst_config;
+typedef struct pgmi_prosst pgmi_prosst;
+/* pgmi_prosst_weight_count: size of the blob above; -1 for a config the library refuses (pgmi_last_error).
+ * pgmi_prosst_create / _destroy: a handle with a stream of its own on `device`.
+ * pgmi_prosst_profile_model: the handle's profiling view (owned by the handle).  Classes: PGMI_K_EMBED = the structure pass on the
+ *   device (every layer's edge tables, layer 0's messages over the global edges), PGMI_K_GEMM_QKV = the per-node tables of the first
+ *   message GVP, PGMI_K_ATTENTION = the message kernel, PGMI_K_LAYERNORM = aggregation, tuple LayerNorms and the feed-forward operand
+ *   rows, PGMI_K_GEMM_FC1 / _FC2 = the feed-forward ws GEMMs, PGMI_K_KEPT_ROWS = the feed-forward GVPs' vector halves, PGMI_K_HEAD =
+ *   W_out, the mean per subgraph and the normalisation, PGMI_K_SCORE = the codebook assignment.
+ * pgmi_prosst_set_structure: X f32 [L][4][3] = N, CA, C, O.  On the host, in double on these float32 values: CA-CA distances; the
+ *   global edges (a -> b), a != b, d < radius, in row-major order of (a, b), a the source and b the target; per anchor i the
+ *   subgraph's nodes = row i of the distances sorted ascending (ties: lower index first), the first 50, those with d < radius, the
+ *   first max_nodes of them when more than `threshold` remain, sorted by index; a subgraph's edges = the global edges between its
+ *   nodes, with the global edge's features.  W_v (once per residue) and W_e (once per global edge) run there too.
+ * pgmi_prosst_subgraphs (test view; every pointer nullable): counts i64 [3] = E global edges, N node copies, ES subgraph edges;
+ *   edges i32 [2][E] = a then b; e_s f32 [E][64], e_v f32 [E][2][3] = W_e's output; node_off i32 [L + 1], nodes i32 [N] = the node
+ *   CSR; edge_off i32 [L + 1], edge_gid i32 [ES] = per subgraph the global edge of each of its edges, ascending (the reference's
+ *   row-major order over the sorted node set).
+ * pgmi_op_prosst_subgraphs: the same host graph pass without a handle or a device (cfg's radius, max_nodes and threshold; no weights):
+ *   the view above without W_e's output, and the arrays the kernels read: in_off i32 [N + 1], in_gid i32 [ES], in_src i32 [ES] = per
+ *   node copy (node q of anchor i, in CSR order) its incoming subgraph edges p -> q in ascending p, as (global edge, copy of p).
+ * pgmi_prosst_embed: the encoder on every subgraph; out f32 [L][256] = the L2-normalised mean of W_out's rows, pooled (nullable)
+ *   f32 [L][256] the mean before the normalisation; node_s f32 [n][256] / node_v f32 [n][32][3] (nullable): the node state after the
+ *   last layer of the n nodes of subgraph `sub`.  Layer 0's messages are computed once per global edge (every copy of a residue
+ *   enters it with the same state); from layer 1 on the work is per node copy.  A subgraph's bits do not depend on the chunking.
+ * pgmi_prosst_assign: tokens i32 [L] = argmin_k |c_k|^2 - 2 x.c_k over centres f32 [K][256] in fp32, the lowest index on a tie, for
+ *   the embeddings of the last pgmi_prosst_embed (kept on the device): any number of codebooks per encoder pass.
+ * pgmi_op_prosst_assign: the same assignment on host embeddings emb f32 [n][256]; bit-equal to pgmi_prosst_assign on the same rows.
+ *   At most 2^20 rows and 2^28 products n K per call (the [n][K] table is one allocation); more is refused: call it in slices.
+ * pgmi_set_option("prosst_max_rows", n): node copies per chunk (0: 32768; test hook, bit-neutral).
+ * pgmi_set_option("prosst_share_layer0", 0 / 1): 0 runs layer 0 per node copy like the others (measurement only). */
+int64_t pgmi_prosst_weight_count(const pgmi_prosst_config* cfg);
+int pgmi_prosst_create(const pgmi_prosst_config* cfg, const float* weights, int64_t n_weights, int device, pgmi_prosst** out);
+void pgmi_prosst_destroy(pgmi_prosst* m);
+pgmi_model* pgmi_prosst_profile_model(pgmi_prosst* m);
+int pgmi_prosst_set_structure(pgmi_prosst* m, const float* X, int L);
+int pgmi_prosst_subgraphs(pgmi_prosst* m, int64_t* counts, int32_t* edges, float* e_s, float* e_v, int32_t* node_off, int32_t* nodes,
+                          int32_t* edge_off, int32_t* edge_gid);
+int pgmi_op_prosst_subgraphs(const pgmi_prosst_config* cfg, const float* X, int L, int64_t* counts, int32_t* edges, int32_t* node_off,
+                             int32_t* nodes, int32_t* edge_off, int32_t* edge_gid, int32_t* in_off, int32_t* in_gid, int32_t* in_src);
+int pgmi_prosst_embed(pgmi_prosst* m, float* out, float* pooled, int sub, float* node_s, float* node_v);
+int pgmi_prosst_assign(pgmi_prosst* m, const float* centres, int K, int32_t* tokens);
+int pgmi_op_prosst_assign(int device, const float* emb, int64_t n, const float* centres, int K, int32_t* tokens);
+
 /* ---- MSA Transformer (arch PGMI_ARCH_MSA; vocab 33, head_dim 64, precision f16x3) --------------------
  * Replaces MSATransformer.forward (proteingym/baselines/esm/esm/model/msa_transformer.py:146-205; tied
  * row attention esm/axial_attention.py:33-168, column attention :171-297) and the masked-marginals loop

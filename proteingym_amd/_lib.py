@@ -203,6 +203,16 @@ SIGNATURES = [
     ("pgmi_vespag_head", C.c_int, [C.c_void_p, _f32p, _i32p, C.c_int64, _f32p]),
     ("pgmi_op_vespag_head", C.c_int, [C.c_int, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p, _i32p, C.c_int, C.c_int, C.c_int, C.c_float,
                                       _f32p]),
+    ("pgmi_prosst_weight_count", C.c_int64, [C.c_void_p]),
+    ("pgmi_prosst_create", C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
+    ("pgmi_prosst_destroy", None, [C.c_void_p]),
+    ("pgmi_prosst_profile_model", C.c_void_p, [C.c_void_p]),
+    ("pgmi_prosst_set_structure", C.c_int, [C.c_void_p, _f32p, C.c_int]),
+    ("pgmi_prosst_subgraphs", C.c_int, [C.c_void_p, _i64p, _i32p, _f32p, _f32p, _i32p, _i32p, _i32p, _i32p]),
+    ("pgmi_op_prosst_subgraphs", C.c_int, [C.c_void_p, _f32p, C.c_int, _i64p] + [_i32p] * 8),
+    ("pgmi_prosst_embed", C.c_int, [C.c_void_p, _f32p, _f32p, C.c_int, _f32p, _f32p]),
+    ("pgmi_prosst_assign", C.c_int, [C.c_void_p, _f32p, C.c_int, _i32p]),
+    ("pgmi_op_prosst_assign", C.c_int, [C.c_int, _f32p, C.c_int64, _f32p, C.c_int, _i32p]),
     ("pgmi_bench_gemm", C.c_int, [C.c_int] * 9 + [_f64p]),
     ("pgmi_bench_gemm_ab", C.c_int, [C.c_int] * 7 + [_i32p, C.c_int, C.c_int, C.c_int, _f64p]),
     ("pgmi_op_attention", C.c_int, [C.c_int, C.c_int, _f32p, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),
@@ -334,7 +344,7 @@ class _ProfileView:
 
 
 class SideHandle:
-    """A model with a handle of its own (EVE, ProteinMPNN, UniRep, S2F, S3F, CARP, ProtSSN, VespaG) behind the entries
+    """A model with a handle of its own (EVE, ProteinMPNN, UniRep, S2F, S3F, CARP, ProtSSN, VespaG, ProSST) behind the entries
     pgmi_<PREFIX>_weight_count / _create / _destroy / _profile_model.  _create checks the blob size against the library's count and
     creates the handle; `before_device` are the arguments the create entry takes between the blob and the device (S2F / S3F: the ESM2
     handle).  NAME starts the blob size message."""

@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libpgmi.so")
 BUILD = os.path.join(HERE, "csrc", "_build")
-SOURCES = ["api_model.hip", "api_esm.hip", "api_tranception.hip", "api_progen2.hip", "api_gpt.hip", "api_esmc.hip", "api_esm3.hip", "api_saprot.hip", "api_mulan.hip", "api_poet.hip", "api_esmif1.hip", "api_progen3.hip", "api_eve.hip", "api_mpnn.hip", "api_unirep.hip", "api_s2f.hip", "api_s3f.hip", "api_carp.hip", "api_protssn.hip", "api_vespag.hip", "api_msa.hip", "api_host.hip", "api_ops.hip", "elementwise.hip", "eve.hip", "mpnn.hip", "s2f.hip", "s3f.hip", "egnn.hip", "vespag.hip", "mlstm.hip", "conv_f16.hip", "moe.hip", "gemm_f32.hip", "gemm_f16.hip", "attention_f32.hip", "attention_f16.hip", "attention_f16_v3.hip", "attention_f16_prep.hip", "attention_prefix.hip", "geom_attention.hip", "msa_weights.hip", "msa_transformer.hip"]
+SOURCES = ["api_model.hip", "api_esm.hip", "api_tranception.hip", "api_progen2.hip", "api_gpt.hip", "api_esmc.hip", "api_esm3.hip", "api_saprot.hip", "api_mulan.hip", "api_poet.hip", "api_esmif1.hip", "api_progen3.hip", "api_eve.hip", "api_mpnn.hip", "api_unirep.hip", "api_s2f.hip", "api_s3f.hip", "api_carp.hip", "api_protssn.hip", "api_vespag.hip", "api_prosst.hip", "api_msa.hip", "api_host.hip", "api_ops.hip", "elementwise.hip", "eve.hip", "mpnn.hip", "s2f.hip", "s3f.hip", "egnn.hip", "vespag.hip", "prosst_gvp.hip", "mlstm.hip", "conv_f16.hip", "moe.hip", "gemm_f32.hip", "gemm_f16.hip", "attention_f32.hip", "attention_f16.hip", "attention_f16_v3.hip", "attention_f16_prep.hip", "attention_prefix.hip", "geom_attention.hip", "msa_weights.hip", "msa_transformer.hip"]
 # attention_f16.hip: keep the MFMA accumulators in ArchVGPRs.  hipcc put the running O / S accumulators into AGPRs and then
 # paid 64 v_accvgpr_read + 64 v_accvgpr_write around every online-softmax rescale and around the S -> P conversion (VALU work
 # on accumulator data); the kernel fits 184 VGPRs at the same occupancy without them.

@@ -535,7 +535,8 @@ int pgmi_set_option(const char* name, int64_t value) {
     if (rc) rc = mpnn_set_option(name, (long long)value);
     if (rc) rc = unirep_set_option(name, (long long)value);
     if (rc) rc = s2f_set_option(name, (long long)value);
-    if (rc) set_error("unknown option '%s' (gemm_half_tail, gemm_max_rows, att_xcd_local, att_v3, eve_max_rows, eve_fixed_sample, eve_prior_batch, mpnn_max_rows, unirep_max_rows, s2f_max_rows)", name);
+    if (rc) rc = prosst_set_option(name, (long long)value);
+    if (rc) set_error("unknown option '%s' (gemm_half_tail, gemm_max_rows, att_xcd_local, att_v3, eve_max_rows, eve_fixed_sample, eve_prior_batch, mpnn_max_rows, unirep_max_rows, s2f_max_rows, prosst_max_rows, prosst_share_layer0)", name);
     return rc;
 }
 

@@ -299,6 +299,7 @@ void launch_s2f_head(const float* x, const float* sums, const int32_t* grp, int 
                      const float* plddt, float thr, int L, int64_t rows, float* lp, hipStream_t s);
 void launch_s2f_pick_logits(const float* lp, const int32_t* cols, int L, int T, int V, int64_t rows, float* out, hipStream_t s);
 int s2f_set_option(const char* name, long long value);    // api_s2f.hip: "s2f_max_rows"
+int prosst_set_option(const char* name, long long value); // api_prosst.hip: "prosst_max_rows", "prosst_share_layer0"
 
 // S3F (s3f.hip; operands and shapes at the kernels)
 constexpr int S3F_DEG = 16;                            // incoming edges of every surface point
